@@ -8,7 +8,9 @@ HIP PPO update), ANYmal-C flat, 4096 envs per GPU (BASELINE.json configs[1]).
 A "step" is one PPO iteration: num_steps_per_env(24) x num_envs env steps (each = 4 physics
 substeps + actuator net + post-physics logic) followed by 5 epochs x 4 minibatches of PPO.
 value = 24 * num_envs * n_gpus / mean iteration time  (rsl_rl's fps definition).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs below): same arguments, same seeds, same inputs, so two builds can be compared output for output.  It runs the
+learner in its deterministic mode (fixed-point sums, lg_ppo_set_deterministic) so that a run's files repeat bit for bit.
 """
 import argparse
 import json
@@ -84,11 +86,12 @@ class TimedReduce:
         return ms, n
 
 
-def time_iterations(runner, steps, warmup, world, comm_out=None):
+def time_iterations(runner, steps, warmup, world, comm_out=None, after_timed=None):
     """(wall seconds of the `steps` timed iterations = MAX over ranks, rollout seconds of as many iterations).  With world > 1 and
     `comm_out` a dict: per-rank communication time of the timed iterations (ms per iteration on every rank: the all-reduces of the
     default collective, or what the learner's stream waited for the overlapped buckets of LG_COMM=native) and every rank's own
-    iteration time, so that a scaling loss can be attributed."""
+    iteration time, so that a scaling loss can be attributed.  `after_timed()` is called once right after the timed window, before
+    any further iteration runs (--dump-outputs reads the last timed iteration's results there)."""
     ar = runner._grad_reduce
     for _ in range(warmup):
         runner.rollout()
@@ -114,6 +117,8 @@ def time_iterations(runner, steps, warmup, world, comm_out=None):
         torch.distributed.barrier()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if after_timed is not None:
+        after_timed()
     if world > 1 and comm_out is not None:
         if native:
             ms, n = runner.ppo.comm_wait_ms()
@@ -147,6 +152,56 @@ def time_iterations(runner, steps, warmup, world, comm_out=None):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el, t_roll = float(t[0]), float(t[1])
     return el, t_roll * steps
+
+
+DUMP_BYTES_MAX = 64 * 10 ** 6      # --dump-outputs: every file together, .npy headers included
+NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(env, runner, out_dir, budget=DUMP_BYTES_MAX):
+    """Write what the last timed iteration handed its caller to out_dir/<name>.npy (float32; the env sample index float64): the
+    rollout storage of its 24 env steps (what the update trained on), the env's last step (observations, rewards, resets), and
+    the policy the update left (named parameters, mean losses, learner stats).  If the arrays with an env axis do not fit the
+    budget, the same fixed, seeded sample of envs is kept in each of them and its indices go to env_index.npy.
+    Returns {"files", "bytes", "envs_kept"}."""
+    import numpy as np
+    ppo, t = runner.ppo, runner.ppo.t
+    per_env = {f"storage_{k}": (1, t[k]) for k in ("obs", "actions", "rewards", "dones", "values", "returns", "advantages",
+                                                    "log_prob", "mu")}
+    if ppo.privileged:
+        per_env["storage_critic_obs"] = (1, t["critic_obs"])
+    per_env.update({"env_obs": (0, env.obs_buf), "env_rew": (0, env.rew_buf), "env_reset": (0, env.reset_buf)})
+    if env.privileged_obs_buf is not None:
+        per_env["env_privileged_obs"] = (0, env.privileged_obs_buf)
+    st = t["stats"]
+    fixed = {f"param_{k}": v for k, v in ppo.param_views.items()}
+    fixed["losses"] = torch.stack([st[2] / st[5], st[3] / st[5]])     # (mean value loss, mean surrogate loss): ppo.update()'s return
+    fixed["learner_stats"] = st
+    n = ppo.N
+    fixed_bytes = sum(4 * v.numel() + NPY_HEADER_BYTES for v in fixed.values())
+    env_bytes = sum(4 * v.numel() // n for _, v in per_env.values())          # per env, over every array with an env axis
+    room = budget - fixed_bytes - NPY_HEADER_BYTES * (len(per_env) + 1)
+    idx = None
+    if n * env_bytes > room + NPY_HEADER_BYTES:
+        keep = room // (env_bytes + 8)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: the policy alone ({fixed_bytes} bytes) leaves no room in {budget} bytes")
+        idx = np.sort(np.random.default_rng(0).choice(n, size=int(keep), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    sel = None if idx is None else torch.as_tensor(idx, device=t["obs"].device)
+    for name, (axis, v) in per_env.items():
+        arrays[name] = (v if sel is None else v.index_select(axis, sel)).float().cpu().numpy()
+    for name, v in fixed.items():
+        arrays[name] = v.detach().float().cpu().numpy()
+    if idx is not None:
+        arrays["env_index"] = idx.astype(np.float64)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, np.ascontiguousarray(a))
+        total += os.path.getsize(path)
+    return {"files": len(arrays), "bytes": total, "envs_kept": n if idx is None else int(idx.size)}
 
 
 def gemm_roofline(runner, hidden, with_largest=True, task="anymal_c_flat"):
@@ -479,7 +534,12 @@ def main():
     ap.add_argument("--no_alt", action="store_true", help="skip the [128,64,32] pass (profiling runs)")
     ap.add_argument("--no_other", action="store_true", help="skip the anymal_c_rough / cassie passes (BASELINE configs[2], [4])")
     ap.add_argument("--sustained", type=int, default=300, help="iterations of the sustained-speed pass after the timed steps (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; at most 64 MB, seeded env sample beyond); "
+                         "runs the learner in its deterministic mode so that the files repeat bit for bit")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     hidden = [int(v) for v in args.hidden.split(",")]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -510,7 +570,19 @@ def main():
         env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
         args.no_other = args.no_alt = args.no_cpu_baseline = True
     comm_info = {} if world > 1 else None
-    el, t_roll = time_iterations(runner, args.steps, args.warmup, world, comm_out=comm_info)
+    dumped = {}
+    after_timed = None
+    if args.dump_outputs:
+        # float atomics in the update leave one run's parameters ~1e-5 from another's, and the warm-up and timed iterations amplify that
+        # into different trajectories: with fixed-point sums (lg_ppo_set_deterministic) the dump is the same bit for bit from run to run;
+        # the mode costs ~3 % of ms_per_step at 4096 envs
+        deterministic = os.environ.get("LG_DETERMINISTIC", "0") not in ("", "0")
+        if not deterministic and not getattr(runner.comm, "overlapped", False):
+            runner.ppo.set_deterministic(True)
+            deterministic = True
+        if rank == 0:
+            after_timed = lambda: dumped.update(dump_outputs(env, runner, args.dump_outputs), deterministic=deterministic)
+    el, t_roll = time_iterations(runner, args.steps, args.warmup, world, comm_out=comm_info, after_timed=after_timed)
     steps_per_iter = runner.num_steps_per_env * args.num_envs * world
     sustained = None
     # what the timed steps were measured on: how often the random-init policy makes robots fall, and how often the
@@ -536,6 +608,8 @@ def main():
     out["config"]["base_velocity_clamps"] = int(env.vel_clamp_total.cpu())
     if comm_info:
         out["comm"] = comm_info
+    if dumped:
+        out["dump_outputs"] = dict(dumped, dir=args.dump_outputs)
     if world > 1:
         # the GEMM-group probe on every rank (a communicator that reduces inside the backward pass needs all of them in it); rank 0 reports
         rf = gemm_roofline(runner, hidden, with_largest=False, task=args.task)
