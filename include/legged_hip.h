@@ -337,7 +337,29 @@ typedef struct lg_ppo_buffers {
 
 typedef struct lg_ppo lg_ppo;
 
+/* rsl_rl's ActorCriticRecurrent: memory_a / memory_c = one nn.LSTM layer each (type 0 = LSTM; the only one), hidden a multiple of 32,
+ * <= 512; the actor / critic MLPs of lg_ppo_cfg take the hidden state as input.  lg_ppo_begin_update and lg_ppo_minibatch_backward
+ * refuse a learner whose num_envs is not a multiple of num_mini_batches (rollout and inference work for any num_envs). */
+typedef struct lg_ppo_rnn_cfg {
+    int32_t type, hidden, layers, _pad;
+} lg_ppo_rnn_cfg;
+
+typedef struct lg_ppo_rnn_buffers {
+    float *h[2], *c[2];                            /* live state (N, H) of memory_a [0] and memory_c [1] */
+    float *saved_h[2], *saved_c[2];                /* state before each rollout step (T, N, H): RolloutStorage.saved_hidden_states_{a,c} */
+    int64_t hidden;
+} lg_ppo_rnn_buffers;
+
 int lg_ppo_create(const lg_ppo_cfg *cfg, lg_ppo **out);
+/* A recurrent learner.  Parameters: std, actor.*, critic.*, then memory_a.rnn.{weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0}
+ * and the same four of memory_c (lg_ppo_param_layout).  lg_ppo_act stores the state before the step and advances both memories;
+ * lg_ppo_process_env_step zeroes the state of the envs that are done; lg_ppo_compute_returns advances memory_c once more on the
+ * last observations (rsl_rl's evaluate); lg_ppo_act_inference advances memory_a and needs rows == num_envs.  The update runs
+ * rsl_rl's recurrent minibatch generator: minibatch i = envs [i N / nmb, (i + 1) N / nmb) over all T steps, same order every epoch,
+ * each trajectory starting from its saved state.  lg_ppo_set_comm is refused (its per-layer buckets do not cover the LSTM). */
+int lg_ppo_create_recurrent(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rnn, lg_ppo **out);
+int lg_ppo_get_rnn_buffers(lg_ppo *p, lg_ppo_rnn_buffers *out);     /* error on a feed-forward learner */
+int lg_ppo_reset_hidden(lg_ppo *p, const uint8_t *dones);           /* zero the state of the envs with dones[i] set; NULL = all */
 int lg_ppo_destroy(lg_ppo *p);
 int lg_ppo_get_buffers(lg_ppo *p, lg_ppo_buffers *out);
 int lg_ppo_set_stream(lg_ppo *p, void *stream);

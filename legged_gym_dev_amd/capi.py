@@ -176,6 +176,14 @@ class lg_ppo_buffers(C.Structure):
         ("num_params", i64), ("num_reduce", i64)]
 
 
+class lg_ppo_rnn_cfg(C.Structure):
+    _fields_ = [("type", i32), ("hidden", i32), ("layers", i32), ("_pad", i32)]
+
+
+class lg_ppo_rnn_buffers(C.Structure):
+    _fields_ = [("h", PF * 2), ("c", PF * 2), ("saved_h", PF * 2), ("saved_c", PF * 2), ("hidden", i64)]
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p
@@ -209,7 +217,7 @@ ENV_SYMBOLS = ["last_error", "create", "destroy", "get_buffers", "set_step_count
 PPO_SYMBOLS = ["ppo_create", "ppo_destroy", "ppo_get_buffers", "ppo_set_stream", "ppo_param_layout",
                "ppo_inject_noise", "ppo_act", "ppo_process_env_step", "ppo_compute_returns",
                "ppo_normalize_advantages", "ppo_begin_update", "ppo_minibatch_backward", "ppo_minibatch_step",
-               "ppo_end_update", "ppo_act_inference"]
+               "ppo_end_update", "ppo_act_inference", "ppo_create_recurrent", "ppo_get_rnn_buffers", "ppo_reset_hidden"]
 HIP_ONLY_SYMBOLS = ["version", "set_stream"]
 COMM_SYMBOLS = ["comm_get_unique_id", "comm_init", "comm_destroy", "comm_rank", "comm_size", "comm_allreduce_sum", "comm_broadcast",
                 "ppo_set_comm", "ppo_allreduce_adv_moments", "ppo_broadcast_params"]

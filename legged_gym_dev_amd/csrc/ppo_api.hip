@@ -7,6 +7,7 @@
 
 #include "ppo_device.h"
 #include "ppo_mlp_args.h"
+#include "ppo_rnn.h"
 
 void lg_set_error(const std::string &s);
 
@@ -34,7 +35,26 @@ int ppok_step(const PpoDev *P, int par, const PpoDev *G, int gather_mb, hipStrea
 size_t ppok_head_part_floats();
 int ppok_head_fused(const PpoDev *P, int H3, const float *xa, const float *xc, float *dza, float *dzc, int64_t w_a, int64_t b_a,
                     int64_t w_c, int64_t b_c, int64_t b_prev_a, int64_t b_prev_c, hipStream_t s);
+void ppok_lstm_fwd(const RnnStepArgs *a, int nz, hipStream_t s);
+void ppok_lstm_bwd(const RnnBwdArgs *a, int nz, hipStream_t s);
+void ppok_lstm_bias_grad(const PpoDev *P, const RnnBiasArgs *a, hipStream_t s);
+void ppok_lstm_reset(float *h0, float *c0, float *h1, float *c1, const uint8_t *done, int N, int H, hipStream_t s);
 }
+
+// LSTM front ends of a recurrent learner (lg_ppo_create_recurrent); H = 0 on a feed-forward one
+struct Rnn {
+    int H, mbs;                              // hidden size; envs per minibatch
+    int in_dim[2];                           // LSTM input width: num_obs, num_critic_obs
+    int64_t w_ih[2], w_hh[2], b_ih[2], b_hh[2];   // flat parameter offsets
+    float *h[2], *c[2];                      // live state (N, H)
+    float *sv_h[2], *sv_c[2];                // state before each rollout step (T, N, H)
+    float *tmp_h[2], *tmp_c[2];              // input copy of the live state for the steps outside the rollout (N, H)
+    // update workspace, rows t-major over the minibatch's envs (T x mbs)
+    float *pg[2];                            // x . W_ih^T + b_ih (forward), then dG (backward)   [R][4H]
+    float *hout[2], *cout[2], *hused[2], *cused[2], *dh[2];   // [R][H]
+    float *gates[2];                         // [R][4H]
+    float *dc[2];                            // [mbs][H]
+};
 
 struct Net {
     int nl;                                  // linear layers (hidden + head)
@@ -99,6 +119,7 @@ struct lg_ppo {
     int mb_cur, mb_ready, mb_last;           // set the kernels read now; minibatch held by the other set (-1: none); last backward
     int gather_ahead;
     lg_ppo_buffers pub;
+    Rnn rnn;
 };
 
 template <typename T>
@@ -196,7 +217,7 @@ static void backward(lg_ppo *p, int M, const float *in0, const float *in1, int s
             g.B[z] = l == 0 ? in[z] : n.act[l]; g.ldb[z] = n.dims[l];
             g.C[z] = p->dev.grads + n.w_off[l]; g.ldc[z] = n.dims[l];
             g.M[z] = n.dims[l + 1]; g.N[z] = n.dims[l]; g.K[z] = M;
-            if (l == 0) {                            // the minibatch gathers: padded rows, the pad columns computed but not stored
+            if (l == 0 && !p->rnn.H) {               // the minibatch gathers: padded rows, the pad columns computed but not stored
                 const int ldp = z == 0 ? p->dev.Op : p->dev.OCp;
                 g.ldb[z] = ldp;
                 if (ldp != n.dims[0]) { g.N[z] = ldp; g.nstore[z] = n.dims[0]; }
@@ -244,6 +265,22 @@ static void backward(lg_ppo *p, int M, const float *in0, const float *in1, int s
             ppok_gemm_dx(&g, 2, p->stream);
         }
     }
+    if (p->rnn.H) {                                  // recurrent: dL/dh = dz[1] . W_0 (no activation derivative: h feeds W_0 directly)
+        GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        for (int z = 0; z < 2; ++z) {
+            Net &n = p->net[z];
+            g.A[z] = n.dz[1]; g.lda[z] = n.dims[1];
+            g.B[z] = p->dev.params + n.w_off[0]; g.ldb[z] = n.dims[0];
+            g.Bpl[z] = p->dev.wpl + n.pl_off[0];
+            g.C[z] = p->rnn.dh[z]; g.ldc[z] = n.dims[0];
+            g.aux[z] = p->rnn.dh[z]; g.ldaux[z] = n.dims[0];   // read before written by the same lane; activation code 0 ignores it
+            g.M[z] = M; g.N[z] = n.dims[0]; g.K[z] = n.dims[1];
+        }
+        g.elu = 0;
+        g.pl_stride = p->dev.pl_stride;
+        ppok_gemm_dx(&g, 2, p->stream);
+    }
     if (p->overlap) {                                // join: the optimiser step (main stream) needs every dW
         (void)hipEventRecord(p->ev_side, p->side);
         (void)hipStreamWaitEvent(p->stream, p->ev_side, 0);
@@ -272,6 +309,148 @@ static void flush_rollout_epilogue(lg_ppo *p) {
     }
 }
 
+// ------------------------------------------------------------------ recurrent learner (ActorCriticRecurrent)
+static void rnn_net_params(lg_ppo *p, int z, RnnNetArgs &n) {
+    const Rnn &q = p->rnn;
+    n.Wih = p->dev.params + q.w_ih[z]; n.Whh = p->dev.params + q.w_hh[z];
+    n.bih = p->dev.params + q.b_ih[z]; n.bhh = p->dev.params + q.b_hh[z];
+}
+
+// one step of the selected memories (mask bit z) on all N envs from (tmp_h, tmp_c) or, at rollout step t >= 0, from the saved state
+// of step t; the new state goes to the live buffers
+static void rnn_live_step(lg_ppo *p, int mask, const float *x0, const float *x1, int t) {
+    Rnn &q = p->rnn;
+    const int N = p->cfg.num_envs, H = q.H;
+    RnnStepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = N; a.H = H; a.reload_all = 1;
+    const float *x[2] = {x0, x1};
+    int nz = 0;
+    for (int z = 0; z < 2; ++z) {
+        if (!(mask & (1 << z))) continue;
+        RnnNetArgs &n = a.n[nz++];
+        rnn_net_params(p, z, n);
+        n.X = x[z]; n.ldx = q.in_dim[z]; n.K = q.in_dim[z];
+        n.h_sv = t >= 0 ? q.sv_h[z] + (size_t)t * N * H : q.tmp_h[z];
+        n.c_sv = t >= 0 ? q.sv_c[z] + (size_t)t * N * H : q.tmp_c[z];
+        n.h_out = q.h[z]; n.c_out = q.c[z];
+    }
+    ppok_lstm_fwd(&a, nz, p->stream);
+}
+
+// copy the live state of the selected memories to the saved state of rollout step t (t < 0: to tmp)
+static void rnn_stash_live(lg_ppo *p, int mask, int t) {
+    Rnn &q = p->rnn;
+    const size_t nh = (size_t)p->cfg.num_envs * q.H;
+    for (int z = 0; z < 2; ++z) {
+        if (!(mask & (1 << z))) continue;
+        float *dh = t >= 0 ? q.sv_h[z] + (size_t)t * nh : q.tmp_h[z];
+        float *dc = t >= 0 ? q.sv_c[z] + (size_t)t * nh : q.tmp_c[z];
+        (void)hipMemcpyAsync(dh, q.h[z], nh * sizeof(float), hipMemcpyDeviceToDevice, p->stream);
+        (void)hipMemcpyAsync(dc, q.c[z], nh * sizeof(float), hipMemcpyDeviceToDevice, p->stream);
+    }
+}
+
+// update forward of minibatch mb: the input projection of all T x mbs rows in one GEMM, then T step launches
+static void rnn_forward_seq(lg_ppo *p, int mb) {
+    Rnn &q = p->rnn;
+    PpoDev &d = p->dev;
+    const int T = d.T, N = d.N, mbs = q.mbs, H = q.H, R = d.mb_rows, e0 = mb * mbs;
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    for (int z = 0; z < 2; ++z) {
+        g.A[z] = z ? d.mb_critic_obs : d.mb_obs; g.lda[z] = z ? d.OCp : d.Op;
+        g.B[z] = d.params + q.w_ih[z]; g.ldb[z] = q.in_dim[z];
+        g.bias[z] = d.params + q.b_ih[z];
+        g.C[z] = q.pg[z]; g.ldc[z] = 4 * H;
+        g.M[z] = R; g.N[z] = 4 * H; g.K[z] = q.in_dim[z];
+    }
+    g.elu = 0;
+    ppok_gemm_fwd(&g, 2, p->stream);
+    for (int t = 0; t < T; ++t) {
+        RnnStepArgs a;
+        memset(&a, 0, sizeof(a));
+        a.M = mbs; a.H = H;
+        a.reload_all = t == 0;
+        a.reload = t ? d.st_dones + (size_t)(t - 1) * N + e0 : nullptr;
+        for (int z = 0; z < 2; ++z) {
+            RnnNetArgs &n = a.n[z];
+            rnn_net_params(p, z, n);
+            const size_t r0 = (size_t)t * mbs, rp = (size_t)(t ? t - 1 : 0) * mbs;
+            n.P = q.pg[z] + r0 * 4 * H; n.ldp = 4 * H;
+            n.h_prev = t ? q.hout[z] + rp * H : nullptr; n.c_prev = t ? q.cout[z] + rp * H : nullptr;
+            n.h_sv = q.sv_h[z] + ((size_t)t * N + e0) * H; n.c_sv = q.sv_c[z] + ((size_t)t * N + e0) * H;
+            n.h_out = q.hout[z] + r0 * H; n.c_out = q.cout[z] + r0 * H;
+            n.gates = q.gates[z] + r0 * 4 * H;
+            n.h_used = q.hused[z] + r0 * H; n.c_used = q.cused[z] + r0 * H;
+        }
+        ppok_lstm_fwd(&a, 2, p->stream);
+    }
+}
+
+// update backward of minibatch mb, after the MLP backward left dL/dh in rnn.dh: T step launches back through time, then the
+// weight gradients over all T x mbs rows (dW_ih = dG^T X, dW_hh = dG^T h_used, db_ih = db_hh = colsum dG)
+static void rnn_backward_seq(lg_ppo *p, int mb) {
+    Rnn &q = p->rnn;
+    PpoDev &d = p->dev;
+    const int T = d.T, N = d.N, mbs = q.mbs, H = q.H, R = d.mb_rows, e0 = mb * mbs;
+    for (int z = 0; z < 2; ++z) (void)hipMemsetAsync(q.dc[z], 0, (size_t)mbs * H * sizeof(float), p->stream);
+    for (int t = T - 1; t >= 0; --t) {
+        RnnBwdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.M = mbs; a.H = H;
+        a.cut_next = t < T - 1 ? d.st_dones + (size_t)t * N + e0 : nullptr;
+        a.cut = t ? d.st_dones + (size_t)(t - 1) * N + e0 : nullptr;
+        a.cut_all = t == 0;
+        for (int z = 0; z < 2; ++z) {
+            RnnBwdNet &n = a.n[z];
+            const size_t r0 = (size_t)t * mbs;
+            n.dG_next = t < T - 1 ? q.pg[z] + (r0 + mbs) * 4 * H : nullptr;
+            n.Whh = d.params + q.w_hh[z];
+            n.dh_mlp = q.dh[z] + r0 * H;
+            n.dc = q.dc[z];
+            n.gates = q.gates[z] + r0 * 4 * H; n.c_t = q.cout[z] + r0 * H; n.c_used = q.cused[z] + r0 * H;
+            n.dG = q.pg[z] + r0 * 4 * H;
+        }
+        ppok_lstm_bwd(&a, 2, p->stream);
+    }
+    for (int w = 0; w < 2; ++w) {                   // 0: W_ih against the gathered inputs, 1: W_hh against the states used
+        GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.det_base = d.grads; g.det64 = d.det64; g.det_n = d.num_params + 2;
+        long tiles = 0;
+        for (int z = 0; z < 2; ++z) {
+            g.A[z] = q.pg[z]; g.lda[z] = 4 * H;
+            g.M[z] = 4 * H; g.K[z] = R;
+            if (w == 0) {
+                const int ldp = z ? d.OCp : d.Op;
+                g.B[z] = z ? d.mb_critic_obs : d.mb_obs; g.ldb[z] = ldp;
+                g.C[z] = d.grads + q.w_ih[z]; g.ldc[z] = q.in_dim[z];
+                g.N[z] = ldp;
+                if (ldp != q.in_dim[z]) g.nstore[z] = q.in_dim[z];
+            } else {
+                g.B[z] = q.hused[z]; g.ldb[z] = H;
+                g.C[z] = d.grads + q.w_hh[z]; g.ldc[z] = H;
+                g.N[z] = H;
+            }
+            const int tile = (g.M[z] > 64 && g.N[z] > 64) ? 128 : 64;
+            const long tz = (long)((g.M[z] + tile - 1) / tile) * ((g.N[z] + tile - 1) / tile);
+            tiles = tz > tiles ? tz : tiles;
+        }
+        int splits = (int)((384 + tiles - 1) / tiles);      // the MLP's weight-gradient split rule (backward())
+        const int max_splits = R / 256 > 0 ? R / 256 : 1;
+        if (splits > max_splits) splits = max_splits;
+        if (splits >= 8) splits &= ~7;
+        if (splits < 1) splits = 1;
+        ppok_gemm_dw(&g, 2, splits, p->stream);
+    }
+    RnnBiasArgs b;
+    memset(&b, 0, sizeof(b));
+    b.M = R; b.H = H;
+    for (int z = 0; z < 2; ++z) { b.dG[z] = q.pg[z]; b.db_ih[z] = d.grads + q.b_ih[z]; b.db_hh[z] = d.grads + q.b_hh[z]; }
+    ppok_lstm_bias_grad(&d, &b, p->stream);
+}
+
 extern "C" {
 
 int lg_ppo_destroy(lg_ppo *p) {
@@ -287,7 +466,7 @@ int lg_ppo_destroy(lg_ppo *p) {
     return 0;
 }
 
-int lg_ppo_create(const lg_ppo_cfg *cfg, lg_ppo **out) {
+static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **out) {
     if (!cfg || !out) { lg_set_error("null argument"); return -1; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { lg_set_error("no HIP device: no CPU fallback"); return -2; }
@@ -298,8 +477,15 @@ int lg_ppo_create(const lg_ppo_cfg *cfg, lg_ppo **out) {
     const int N = cfg->num_envs, T = cfg->num_steps, A = cfg->num_actions, O = cfg->num_obs;
     const int OC = cfg->num_critic_obs > 0 ? cfg->num_critic_obs : O;
     if ((long)N * T % cfg->num_mini_batches != 0 && (long)N * T / cfg->num_mini_batches == 0) { lg_set_error("bad minibatch count"); return -5; }
+    const int H = rc ? rc->hidden : 0;
+    if (rc) {
+        if (rc->type != 0) { lg_set_error("recurrent policy: only rnn_type 'lstm' (0) is implemented"); return -6; }
+        if (rc->layers != 1) { lg_set_error("recurrent policy: only rnn_num_layers = 1 is implemented"); return -6; }
+        if (H < 32 || H > 512 || H % 32) { lg_set_error("recurrent policy: rnn_hidden_size must be a multiple of 32 in [32, 512]"); return -6; }
+    }
     lg_ppo *p = new lg_ppo();
     p->cfg = *cfg;
+    memset(&p->rnn, 0, sizeof(p->rnn));
     p->stream = nullptr;
     p->act_code = cfg->activation + 1;
     p->fused_act = getenv("LG_FUSED_ACT") ? atoi(getenv("LG_FUSED_ACT")) : 1;   // one-launch rollout forward (ppo_mlp_fused.hip) when the shape allows
@@ -327,13 +513,25 @@ int lg_ppo_create(const lg_ppo_cfg *cfg, lg_ppo **out) {
     for (int z = 0; z < 2; ++z) {
         Net &n = p->net[z];
         n.nl = cfg->num_hidden + 1;
-        n.dims[0] = z == 0 ? O : OC;
+        n.dims[0] = H ? H : z == 0 ? O : OC;              // a recurrent learner's MLPs read the LSTM's hidden state
         for (int l = 0; l < cfg->num_hidden; ++l) n.dims[l + 1] = z == 0 ? cfg->actor_hidden[l] : cfg->critic_hidden[l];
         n.dims[n.nl] = z == 0 ? A : 1;
         for (int l = 0; l < n.nl; ++l) {
             n.w_off[l] = off; off += (int64_t)n.dims[l + 1] * n.dims[l];
             n.b_off[l] = off; off += n.dims[l + 1];
         }
+    }
+    if (H) {                                 // then memory_a.rnn.*, memory_c.rnn.*: weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0
+        Rnn &q = p->rnn;
+        q.H = H; q.mbs = N / cfg->num_mini_batches;
+        for (int z = 0; z < 2; ++z) {
+            q.in_dim[z] = z == 0 ? O : OC;
+            q.w_ih[z] = off; off += (int64_t)4 * H * q.in_dim[z];
+            q.w_hh[z] = off; off += (int64_t)4 * H * H;
+            q.b_ih[z] = off; off += 4 * H;
+            q.b_hh[z] = off; off += 4 * H;
+        }
+        p->fused_act = 0;                    // the one-launch rollout forward has no LSTM stage
     }
     d.num_params = off;
     int seg_ld[LG_PPO_MAX_SEG];
@@ -402,6 +600,24 @@ int lg_ppo_create(const lg_ppo_cfg *cfg, lg_ppo **out) {
         n.act[0] = nullptr; n.dz[0] = nullptr;
         for (int l = 1; l <= n.nl; ++l) { PA(n.act[l], (size_t)p->Mmax * n.dims[l]); PA(n.dz[l], (size_t)p->Mmax * n.dims[l]); }
     }
+    if (H) {
+        Rnn &q = p->rnn;
+        const size_t NH = (size_t)N * H, Rr = (size_t)R;
+        for (int z = 0; z < 2; ++z) {
+            PA(q.h[z], NH); PA(q.c[z], NH); PA(q.sv_h[z], TN * H); PA(q.sv_c[z], TN * H); PA(q.tmp_h[z], NH); PA(q.tmp_c[z], NH);
+            PA(q.pg[z], Rr * 4 * H); PA(q.gates[z], Rr * 4 * H);
+            PA(q.hout[z], Rr * H); PA(q.cout[z], Rr * H); PA(q.hused[z], Rr * H); PA(q.cused[z], Rr * H); PA(q.dh[z], Rr * H);
+            PA(q.dc[z], (size_t)q.mbs * H);
+        }
+        // rsl_rl's reccurent_mini_batch_generator: no permutation, minibatch mb = envs [mb mbs, (mb + 1) mbs) over all T steps, rows
+        // t-major -- as a fixed gather table, so the MLP's gathers (and the gather-ahead of the optimiser step) serve it unchanged.
+        // A learner whose envs do not split into whole minibatches (play / inference on one env) is created but refuses to update.
+        std::vector<int32_t> perm(TN);
+        for (int mb = 0; N % cfg->num_mini_batches == 0 && mb < cfg->num_mini_batches; ++mb)
+            for (int t = 0; t < T; ++t)
+                for (int e = 0; e < q.mbs; ++e) perm[(size_t)mb * R + (size_t)t * q.mbs + e] = (int32_t)((size_t)t * N + (size_t)mb * q.mbs + e);
+        (void)hipMemcpy(d.perm, perm.data(), TN * sizeof(int32_t), hipMemcpyHostToDevice);
+    }
     if (p->fused_act) {                                         // arguments + weight image of the one-launch rollout forward
         MlpArgs &g = p->mlp;
         memset(&g, 0, sizeof(g));
@@ -441,6 +657,26 @@ int lg_ppo_create(const lg_ppo_cfg *cfg, lg_ppo **out) {
     return 0;
 }
 
+int lg_ppo_create(const lg_ppo_cfg *cfg, lg_ppo **out) { return ppo_create(cfg, nullptr, out); }
+int lg_ppo_create_recurrent(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rnn, lg_ppo **out) {
+    if (!rnn) { lg_set_error("null argument"); return -1; }
+    return ppo_create(cfg, rnn, out);
+}
+int lg_ppo_get_rnn_buffers(lg_ppo *p, lg_ppo_rnn_buffers *out) {
+    if (!p->rnn.H) { lg_set_error("lg_ppo_get_rnn_buffers: not a recurrent learner"); return -15; }
+    for (int z = 0; z < 2; ++z) {
+        out->h[z] = p->rnn.h[z]; out->c[z] = p->rnn.c[z]; out->saved_h[z] = p->rnn.sv_h[z]; out->saved_c[z] = p->rnn.sv_c[z];
+    }
+    out->hidden = p->rnn.H;
+    return 0;
+}
+int lg_ppo_reset_hidden(lg_ppo *p, const uint8_t *dones) {
+    if (!p->rnn.H) { lg_set_error("lg_ppo_reset_hidden: not a recurrent learner"); return -15; }
+    flush_rollout_epilogue(p);
+    const Rnn &q = p->rnn;
+    ppok_lstm_reset(q.h[0], q.c[0], q.h[1], q.c[1], dones, p->cfg.num_envs, q.H, p->stream);
+    return launch_ok();
+}
 int lg_ppo_get_buffers(lg_ppo *p, lg_ppo_buffers *out) { *out = p->pub; return 0; }
 int lg_ppo_set_stream(lg_ppo *p, void *s) { p->stream = (hipStream_t)s; return 0; }
 int lg_ppo_inject_noise(lg_ppo *p, int enable) { p->inject = enable; return 0; }
@@ -462,6 +698,13 @@ int lg_ppo_param_layout(lg_ppo *p, int64_t *offsets, int64_t *shapes, int max_en
             put(p->net[z].w_off[l], p->net[z].dims[l + 1], p->net[z].dims[l]);
             put(p->net[z].b_off[l], p->net[z].dims[l + 1], 0);
         }
+    const Rnn &q = p->rnn;
+    for (int z = 0; q.H && z < 2; ++z) {
+        put(q.w_ih[z], 4 * q.H, q.in_dim[z]);
+        put(q.w_hh[z], 4 * q.H, q.H);
+        put(q.b_ih[z], 4 * q.H, 0);
+        put(q.b_hh[z], 4 * q.H, 0);
+    }
     return k;
 }
 
@@ -519,7 +762,13 @@ int lg_ppo_act(lg_ppo *p, const float *obs, const float *critic_obs) {
         // per-layer GEMMs on the optimiser's weight planes (no re-split of W per tile); same freshness rule as above
         static const int act_planes = getenv("LG_ACT_PLANES") ? atoi(getenv("LG_ACT_PLANES")) : 1;
         if (act_planes && dirty) ppok_sync_planes(&p->dev, p->stream);
-        forward(p, p->cfg.num_envs, obs, cobs, 3, 0, act_planes != 0);
+        const float *in0 = obs, *in1 = cobs;
+        if (p->rnn.H) {                          // the transition keeps the state before the step; both memories advance
+            rnn_stash_live(p, 3, p->step);
+            rnn_live_step(p, 3, obs, cobs, p->step);
+            in0 = p->rnn.h[0]; in1 = p->rnn.h[1];
+        }
+        forward(p, p->cfg.num_envs, in0, in1, 3, 0, act_planes != 0);
     }
     ppok_act_sample(&p->dev, obs, cobs, p->net[0].act[p->net[0].nl], p->net[1].act[p->net[1].nl], p->step, p->act_count,
                     p->inject, p->stream);
@@ -542,13 +791,19 @@ int lg_ppo_process_env_step(lg_ppo *p, const float *rew, const uint8_t *dones, c
         flush_rollout_epilogue(p);
     }
     ppok_process_step(&p->dev, rew, dones, time_outs, p->step, p->stream);
+    if (p->rnn.H) ppok_lstm_reset(p->rnn.h[0], p->rnn.c[0], p->rnn.h[1], p->rnn.c[1], dones, p->cfg.num_envs, p->rnn.H, p->stream);
     p->step++;
     return launch_ok();
 }
 
 int lg_ppo_compute_returns(lg_ppo *p, const float *last_critic_obs) {
     flush_rollout_epilogue(p);
-    forward(p, p->cfg.num_envs, nullptr, last_critic_obs, 2);
+    if (p->rnn.H) {                              // rsl_rl's evaluate() advances memory_c once more on the last observations
+        rnn_stash_live(p, 2, -1);
+        rnn_live_step(p, 2, nullptr, last_critic_obs, -1);
+        forward(p, p->cfg.num_envs, nullptr, p->rnn.h[1], 2);
+    } else
+        forward(p, p->cfg.num_envs, nullptr, last_critic_obs, 2);
     ppok_gae(&p->dev, p->net[1].act[p->net[1].nl], p->stream);
     return launch_ok();
 }
@@ -558,11 +813,18 @@ int lg_ppo_normalize_advantages(lg_ppo *p) {
     return launch_ok();
 }
 
+static int rnn_update_refused(const lg_ppo *p) {
+    if (!p->rnn.H || p->cfg.num_envs % p->cfg.num_mini_batches == 0) return 0;
+    lg_set_error("recurrent policy: the update needs num_envs to be a multiple of num_mini_batches (its minibatches are whole envs)");
+    return 1;
+}
+
 int lg_ppo_begin_update(lg_ppo *p) {
+    if (rnn_update_refused(p)) return -6;
     flush_rollout_epilogue(p);
     // randperm(num_mini_batches * mini_batch_size), drawn once per update and reused by every epoch (Appendix B): on the device
     const size_t n = (size_t)p->dev.mb_rows * p->cfg.num_mini_batches;
-    ppok_randperm(&p->dev, (int)n, (uint64_t)p->perm_count++, p->stream);
+    if (!p->rnn.H) ppok_randperm(&p->dev, (int)n, (uint64_t)p->perm_count++, p->stream);   // recurrent: the fixed table of create
     p->mb_ready = -1;                           // a set gathered ahead belongs to the previous permutation
     (void)hipMemsetAsync(p->dev.stats + 2, 0, 2 * sizeof(float), p->stream);
     (void)hipMemsetAsync(p->dev.stats + 5, 0, sizeof(float), p->stream);
@@ -574,6 +836,7 @@ int lg_ppo_begin_update(lg_ppo *p) {
 
 int lg_ppo_minibatch_backward(lg_ppo *p, int epoch, int mb) {
     (void)epoch;
+    if (rnn_update_refused(p)) return -6;
     PpoDev &d = p->dev;
     const int R = d.mb_rows;
     // k_opt_adam leaves the gradient buffer zeroed; only a backward pass that was never stepped needs a clear
@@ -599,7 +862,11 @@ int lg_ppo_minibatch_backward(lg_ppo *p, int epoch, int mb) {
     // long pole (profiles/r02_timelines.txt) it is 9 us faster than head GEMM + k_loss + two head-gradient GEMMs (A/B on one box)
     static const int fuse128 = getenv("LG_HEAD_FUSE128") ? atoi(getenv("LG_HEAD_FUSE128")) : 1;
     const bool fuse = p->act_code == 1 && nl >= 2 && nc.dims[nl - 1] == H3 && (H3 == 64 || H3 == 32 || (H3 == 128 && fuse128));
-    forward(p, R, d.mb_obs, d.mb_critic_obs, 3, fuse ? 1 : 0, true, true);
+    if (p->rnn.H) {
+        rnn_forward_seq(p, mb);
+        forward(p, R, p->rnn.hout[0], p->rnn.hout[1], 3, fuse ? 1 : 0, true, false);
+    } else
+        forward(p, R, d.mb_obs, d.mb_critic_obs, 3, fuse ? 1 : 0, true, true);
     if (fuse) {
         ppok_head_fused(&d, H3, na.act[nl - 1], nc.act[nl - 1], na.dz[nl - 1], nc.dz[nl - 1], na.w_off[nl - 1], na.b_off[nl - 1],
                         nc.w_off[nl - 1], nc.b_off[nl - 1], na.b_off[nl - 2], nc.b_off[nl - 2], p->stream);
@@ -607,7 +874,11 @@ int lg_ppo_minibatch_backward(lg_ppo *p, int epoch, int mb) {
         ppok_loss(&d, na.act[na.nl], nc.act[nc.nl], na.dz[na.nl], nc.dz[nc.nl], p->stream);
     }
     if (fuse && p->comm) reduce_layer_bucket(p, nl - 1, p->stream);   // the fused head produced the head layer's gradients itself
-    backward(p, R, d.mb_obs, d.mb_critic_obs, fuse ? 1 : 0);
+    if (p->rnn.H) {
+        backward(p, R, p->rnn.hout[0], p->rnn.hout[1], fuse ? 1 : 0);
+        rnn_backward_seq(p, mb);
+    } else
+        backward(p, R, d.mb_obs, d.mb_critic_obs, fuse ? 1 : 0);
     if (d.det64) ppok_det_fold(&d, p->stream);       // gradients, KL sum and loss sums of this minibatch, order-independent
     if (p->comm_rc) { const int rc = p->comm_rc; p->comm_rc = 0; return rc; }
     return launch_ok();
@@ -633,6 +904,7 @@ int lg_ppo_minibatch_step(lg_ppo *p) {
 int lg_ppo_end_update(lg_ppo *p) { p->step = 0; return 0; }
 
 int lg_ppo_set_comm(lg_ppo *p, lg_comm *c) {
+    if (c && p->rnn.H) { lg_set_error("lg_ppo_set_comm: the per-layer gradient buckets do not cover the LSTM of a recurrent learner; reduce the whole gradient buffer between lg_ppo_minibatch_backward and lg_ppo_minibatch_step instead"); return -14; }
     if (c && p->dev.det64) { lg_set_error("gradient buckets inside the backward pass cannot be combined with deterministic mode"); return -14; }
     p->comm = c;
     return 0;
@@ -685,6 +957,12 @@ int lg_ppo_debug_bucket_extents(lg_ppo *p, int l, int64_t *offsets, int64_t *cou
 
 int lg_ppo_act_inference(lg_ppo *p, const float *obs, float *actions_out, int64_t rows) {
     if (rows > p->Mmax) { lg_set_error("too many rows for act_inference"); return -11; }
+    if (p->rnn.H) {                              // rsl_rl's act_inference advances memory_a
+        if (rows != p->cfg.num_envs) { lg_set_error("act_inference of a recurrent learner takes exactly num_envs rows"); return -11; }
+        rnn_stash_live(p, 1, -1);
+        rnn_live_step(p, 1, obs, nullptr, -1);
+        obs = p->rnn.h[0];
+    }
     forward(p, (int)rows, obs, nullptr, 1);
     Net &na = p->net[0];
     if (hipMemcpyAsync(actions_out, na.act[na.nl], (size_t)rows * p->cfg.num_actions * sizeof(float), hipMemcpyDeviceToDevice,

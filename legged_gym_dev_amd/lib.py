@@ -64,6 +64,9 @@ def _declare_ppo(lib):
     lib.lg_ppo_params_changed.argtypes = [vp]
     lib.lg_ppo_set_deterministic.argtypes = [vp, C.c_int]
     lib.lg_ppo_attach_env.argtypes = [vp, vp]
+    lib.lg_ppo_create_recurrent.argtypes = [C.POINTER(capi.lg_ppo_cfg), C.POINTER(capi.lg_ppo_rnn_cfg), C.POINTER(vp)]
+    lib.lg_ppo_get_rnn_buffers.argtypes = [vp, C.POINTER(capi.lg_ppo_rnn_buffers)]
+    lib.lg_ppo_reset_hidden.argtypes = [vp, vp]
     lib.lg_ppo_debug_bucket_extents.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
 
 

@@ -7,6 +7,9 @@ parameter buffers of the HIP learner.
   "iter": int, "infos": ...}``.  The optimiser entry is written in torch's own Adam layout (per-parameter
   ``step / exp_avg / exp_avg_sq`` in ``ActorCritic.parameters()`` order) so either stack can resume the other's run.
 * ``policy_1.pt``: TorchScript of the actor MLP (legged_gym/utils/helpers.py:274-285, play.py:78-82).
+* ``policy_lstm_1.pt``: for ActorCriticRecurrent, TorchScript of memory_a + the actor MLP with the module surface of the reference's
+  ``PolicyExporterLSTM`` (helpers.py:288-313): ``forward(x)`` carries ``hidden_state`` / ``cell_state`` buffers (1, 1, H) from call
+  to call, ``reset_memory()`` zeroes them.
 
 Pure torch/CPU code: nothing here is on the training path.
 """
@@ -21,10 +24,16 @@ ACTIVATIONS = {"elu": torch.nn.ELU, "selu": torch.nn.SELU, "relu": torch.nn.ReLU
 
 
 def parameter_order(state_dict):
-    """Names in ``ActorCritic.parameters()`` order: std, actor.*, critic.* (registration order in rsl_rl)."""
+    """Names in ``ActorCritic.parameters()`` order: std, actor.*, critic.* (registration order in rsl_rl); ActorCriticRecurrent
+    continues with memory_a.rnn.* and memory_c.rnn.* (weight_ih, weight_hh, bias_ih, bias_hh)."""
     names = list(state_dict.keys())
-    rank = lambda n: (0 if n == "std" else 1 if n.startswith("actor.") else 2, int(n.split(".")[1]) if "." in n else 0,
-                      0 if n.endswith("weight") else 1)
+    rnn = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+    def rank(n):
+        if n.startswith("memory_"):
+            return (3 if n.startswith("memory_a.") else 4, rnn.index(n.split(".")[-1]), 0)
+        return (0 if n == "std" else 1 if n.startswith("actor.") else 2, int(n.split(".")[1]) if "." in n else 0,
+                0 if n.endswith("weight") else 1)
     return sorted(names, key=rank)
 
 
@@ -80,11 +89,45 @@ def build_mlp(state_dict, prefix="actor", activation="elu"):
     return torch.nn.Sequential(layers)
 
 
+class LSTMPolicy(torch.nn.Module):
+    """memory_a's LSTM followed by the actor MLP, one observation row per call, the state kept in buffers (batch of 1)."""
+
+    def __init__(self, state_dict, activation):
+        super().__init__()
+        w_ih = state_dict["memory_a.rnn.weight_ih_l0"]
+        H = w_ih.shape[0] // 4
+        self.memory = torch.nn.LSTM(w_ih.shape[1], H, 1)
+        with torch.no_grad():
+            for k in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+                getattr(self.memory, k).copy_(state_dict[f"memory_a.rnn.{k}"].detach().cpu())
+        self.actor = build_mlp(state_dict, "actor", activation)
+        self.register_buffer("hidden_state", torch.zeros(1, 1, H))
+        self.register_buffer("cell_state", torch.zeros(1, 1, H))
+
+    def forward(self, x):
+        seq = x.reshape(1, x.shape[0], x.shape[1])                        # one time step of a batch of rows
+        y, state = self.memory(seq, (self.hidden_state, self.cell_state))
+        self.hidden_state.copy_(state[0])
+        self.cell_state.copy_(state[1])
+        return self.actor(y[0])
+
+    @torch.jit.export
+    def reset_memory(self):
+        self.hidden_state.zero_()
+        self.cell_state.zero_()
+
+
 def export_policy_as_jit(actor_critic, path, activation=None):
-    """helpers.py:274-285: ``<path>/policy_1.pt`` = torch.jit.script(actor MLP on CPU)."""
+    """helpers.py:274-285: ``<path>/policy_1.pt`` = torch.jit.script(actor MLP on CPU); a recurrent policy (memory_a.* in its
+    state dict) goes to ``<path>/policy_lstm_1.pt`` instead (helpers.py:288-313)."""
     os.makedirs(path, exist_ok=True)
     sd = actor_critic.state_dict()
     activation = activation or getattr(actor_critic, "activation", "elu")
+    if "memory_a.rnn.weight_ih_l0" in sd:
+        scripted = torch.jit.script(LSTMPolicy(sd, activation).to("cpu"))
+        out = os.path.join(path, "policy_lstm_1.pt")
+        scripted.save(out)
+        return out
     model = copy.deepcopy(build_mlp(sd, "actor", activation)).to("cpu")
     scripted = torch.jit.script(model)
     out = os.path.join(path, "policy_1.pt")

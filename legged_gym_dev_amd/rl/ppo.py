@@ -23,10 +23,46 @@ def _vp(t):
 # entry returns nn.ReLU(), so the name listed at legged_robot_config.py:244 is plain ReLU with unchanged layer widths
 _ACTIVATIONS = {"elu": 0, "selu": 1, "relu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5, "crelu": 2}
 
+POLICY_CLASSES = ("ActorCritic", "ActorCriticRecurrent")
+
+
+def parse_policy_class(policy_class_name, policy_cfg, num_envs, num_mini_batches):
+    """``runner.policy_class_name`` and the ``policy.rnn_*`` keys (legged_robot_config.py:240-248,266) -> None for rsl_rl's
+    ``ActorCritic`` (the feed-forward learner, unchanged) or the recurrent settings {"type", "hidden", "layers"} of
+    ``ActorCriticRecurrent`` (rnn_type 'lstm', rnn_hidden_size 256, rnn_num_layers 1 by default).  Host-only; anything the HIP
+    learner does not implement is refused here rather than trained as something else.  The minibatch split is checked where an
+    update runs (:func:`check_recurrent_update`): playing a recurrent checkpoint on one env is legitimate."""
+    name = policy_class_name or "ActorCritic"
+    if name not in POLICY_CLASSES:
+        raise NotImplementedError(f"policy_class_name {name!r}: the HIP learner implements {list(POLICY_CLASSES)}")
+    if name == "ActorCritic":
+        return None
+    get = policy_cfg.get if isinstance(policy_cfg, dict) else (lambda k, d=None: getattr(policy_cfg, k, d))
+    rnn_type = get("rnn_type", "lstm")
+    hidden = get("rnn_hidden_size", 256)
+    layers = get("rnn_num_layers", 1)
+    if str(rnn_type).lower() != "lstm":
+        raise NotImplementedError(f"ActorCriticRecurrent rnn_type {rnn_type!r}: only 'lstm' is implemented (as in the reference's "
+                                  "policy exporter)")
+    if int(layers) != 1:
+        raise NotImplementedError(f"ActorCriticRecurrent rnn_num_layers {layers}: only 1 is implemented")
+    if int(hidden) != hidden or hidden <= 0 or int(hidden) % 32 or int(hidden) > 512:
+        raise NotImplementedError(f"ActorCriticRecurrent rnn_hidden_size {hidden}: the HIP LSTM needs a multiple of 32, at most 512")
+    return {"type": 0, "hidden": int(hidden), "layers": 1}
+
+
+def check_recurrent_update(num_envs, num_mini_batches):
+    """rsl_rl's recurrent generator splits the envs into whole minibatches: an update with a remainder is refused (host-only)."""
+    if num_envs % num_mini_batches:
+        raise NotImplementedError(f"ActorCriticRecurrent: num_envs {num_envs} is not a multiple of num_mini_batches "
+                                  f"{num_mini_batches} (the recurrent minibatches are whole envs)")
+
 
 class HipPPO:
     def __init__(self, num_envs, num_obs, num_critic_obs, num_actions, policy_cfg, alg_cfg, num_steps,
-                 device="cuda:0", seed=1, world_size=1, rank=0):
+                 device="cuda:0", seed=1, world_size=1, rank=0, policy_class_name="ActorCritic"):
+        self.rnn = parse_policy_class(policy_class_name, policy_cfg, num_envs, alg_cfg["num_mini_batches"])
+        self.is_recurrent = self.rnn is not None
         self.lib = load()
         if not hasattr(self.lib, "lg_ppo_create"):
             raise LeggedHipError("liblegged_hip.so was built without the PPO kernels")
@@ -63,7 +99,12 @@ class HipPPO:
         self.OC = num_critic_obs if self.privileged else num_obs
         self.world_size = world_size
         self.ctx = C.c_void_p()
-        rc = self.lib.lg_ppo_create(C.byref(c), C.byref(self.ctx))
+        if self.is_recurrent:
+            rcfg = capi.lg_ppo_rnn_cfg()
+            rcfg.type, rcfg.hidden, rcfg.layers = self.rnn["type"], self.rnn["hidden"], self.rnn["layers"]
+            rc = self.lib.lg_ppo_create_recurrent(C.byref(c), C.byref(rcfg), C.byref(self.ctx))
+        else:
+            rc = self.lib.lg_ppo_create(C.byref(c), C.byref(self.ctx))
         if rc != 0:
             raise LeggedHipError(f"lg_ppo_create failed ({rc}): {self.lib.lg_last_error().decode()}")
         b = capi.lg_ppo_buffers()
@@ -91,6 +132,8 @@ class HipPPO:
         for net, nl in (("actor", len(ah) + 1), ("critic", len(ch) + 1)):
             for l in range(nl):
                 names += [f"{net}.{2 * l}.weight", f"{net}.{2 * l}.bias"]
+        if self.is_recurrent:                       # ActorCriticRecurrent.parameters(): then memory_a, memory_c
+            names += [f"{m}.rnn.{k}_l0" for m in ("memory_a", "memory_c") for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
         assert n == len(names), (n, names)
         self.param_views, self.grad_views = {}, {}
         for k, name in enumerate(names):
@@ -99,21 +142,37 @@ class HipPPO:
             view_shape = (r, cdim) if cdim else (r,)
             self.param_views[name] = self.t["params"][int(offs[k]):int(offs[k]) + size].view(view_shape)
             self.grad_views[name] = self.t["grads"][int(offs[k]):int(offs[k]) + size].view(view_shape)
+        if self.is_recurrent:
+            rb = capi.lg_ppo_rnn_buffers()
+            self._call("get_rnn_buffers", C.byref(rb))
+            H = self.H = int(rb.hidden)
+            for z, m in enumerate(("a", "c")):
+                self.t[f"h_{m}"] = device_tensor(C.cast(rb.h[z], C.c_void_p).value, (N, H), "f4", self, self.device)
+                self.t[f"c_{m}"] = device_tensor(C.cast(rb.c[z], C.c_void_p).value, (N, H), "f4", self, self.device)
+                self.t[f"saved_h_{m}"] = device_tensor(C.cast(rb.saved_h[z], C.c_void_p).value, (T, N, H), "f4", self, self.device)
+                self.t[f"saved_c_{m}"] = device_tensor(C.cast(rb.saved_c[z], C.c_void_p).value, (T, N, H), "f4", self, self.device)
         self._init_parameters(ah, ch)
         self.params_changed()
         self.use_current_stream()
         if os.environ.get("LG_DETERMINISTIC", "0") not in ("", "0"):
             self.set_deterministic(True)
 
-    # nn.Linear default initialisation, drawn in the order rsl_rl's ActorCritic constructs its layers
+    # nn.Linear default initialisation, drawn in the order rsl_rl's ActorCritic constructs its layers; ActorCriticRecurrent's MLPs
+    # take the hidden state, and its two nn.LSTM (reset_parameters: U(+-1/sqrt(H))) are drawn after them, memory_a first
     def _init_parameters(self, ah, ch):
         def mlp(i, hidden, o):
             dims = [i] + list(hidden) + [o]
             return [torch.nn.Linear(dims[k], dims[k + 1]) for k in range(len(dims) - 1)]
-        for net, layers in (("actor", mlp(self.O, ah, self.A)), ("critic", mlp(self.OC, ch, 1))):
+        ia, ic = (self.H, self.H) if self.is_recurrent else (self.O, self.OC)
+        for net, layers in (("actor", mlp(ia, ah, self.A)), ("critic", mlp(ic, ch, 1))):
             for l, lin in enumerate(layers):
                 self.param_views[f"{net}.{2 * l}.weight"].copy_(lin.weight.detach())
                 self.param_views[f"{net}.{2 * l}.bias"].copy_(lin.bias.detach())
+        if self.is_recurrent:
+            for m, width in (("memory_a", self.O), ("memory_c", self.OC)):
+                lstm = torch.nn.LSTM(width, self.H, 1)
+                for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+                    self.param_views[f"{m}.rnn.{k}_l0"].copy_(getattr(lstm, f"{k}_l0").detach())
 
     def use_current_stream(self):
         self.lib.lg_ppo_set_stream(self.ctx, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
@@ -140,6 +199,8 @@ class HipPPO:
 
     def update(self, all_reduce=None):
         """5 epochs x 4 minibatches (cfg); returns (mean_value_loss, mean_surrogate_loss) lazily as tensors."""
+        if self.is_recurrent:
+            check_recurrent_update(self.N, self.cfg.num_mini_batches)
         self._call("begin_update")
         reduce_view = self.t["grads"][: self.num_reduce]
         for epoch in range(self.cfg.num_epochs):
@@ -156,6 +217,16 @@ class HipPPO:
         out = torch.empty(obs.shape[0], self.A, device=self.device)
         self._call("act_inference", _vp(obs.contiguous()), _vp(out), C.c_int64(obs.shape[0]))
         return out
+
+    def reset_hidden(self, dones=None):
+        """ActorCriticRecurrent.reset(dones): zero both memories' state where ``dones`` (uint8/bool, N) is set; None = every env."""
+        if dones is not None:
+            dones = dones.to(self.device, torch.uint8).contiguous()
+        self._call("reset_hidden", _vp(dones))
+
+    def get_hidden_states(self):
+        """ActorCriticRecurrent.get_hidden_states(): ((h_a, c_a), (h_c, c_c)), each (1, N, H) -- live views."""
+        return tuple((self.t[f"h_{m}"].unsqueeze(0), self.t[f"c_{m}"].unsqueeze(0)) for m in ("a", "c"))
 
     def inject_noise(self, enable):
         self.lib.lg_ppo_inject_noise(self.ctx, int(enable))

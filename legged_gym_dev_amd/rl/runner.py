@@ -35,6 +35,15 @@ class ActorCriticFacade:
         self._ppo = ppo
         self.actor = _ActorFacade(ppo)
         self.activation = ppo.activation
+        self.is_recurrent = ppo.is_recurrent
+
+    def reset(self, dones=None):
+        """ActorCriticRecurrent.reset: zero the memories of the envs that are done (a no-op for the feed-forward policy)."""
+        if self.is_recurrent:
+            self._ppo.reset_hidden(dones)
+
+    def get_hidden_states(self):
+        return self._ppo.get_hidden_states() if self.is_recurrent else None
 
     @property
     def std(self):
@@ -93,7 +102,8 @@ class OnPolicyRunner:
         ncrit = env.num_privileged_obs if env.num_privileged_obs is not None else env.num_obs
         self.ppo = HipPPO(env.num_envs, env.num_obs, ncrit, env.num_actions, self.policy_cfg, self.alg_cfg,
                           self.num_steps_per_env, device=self.device, seed=train_cfg.get("seed", 1),
-                          world_size=self.world_size, rank=self.rank)
+                          world_size=self.world_size, rank=self.rank,
+                          policy_class_name=self.cfg.get("policy_class_name", "ActorCritic"))
         self.alg = _Alg(self.ppo)
         if self.comm:                                 # identical initial policy on every rank
             torch.cuda.synchronize()

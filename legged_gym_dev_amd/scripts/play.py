@@ -1,7 +1,8 @@
 """python legged_gym_dev_amd/scripts/play.py --task=anymal_c_flat [--load_run R --checkpoint K --num_envs N]
 Evaluate a trained policy (reference scripts/play.py:53-212): resume the latest checkpoint, export the actor
-as TorchScript (policy_1.pt), run the inference policy for one episode length, log robot 0 and the episode
-rewards, and write the per-step arrays to play_data.mat.  Headless: there is no viewer in this stack."""
+as TorchScript (policy_1.pt; policy_lstm_1.pt, memory_a + actor, for an ActorCriticRecurrent checkpoint), run the
+inference policy for one episode length, log robot 0 and the episode rewards, and write the per-step arrays to
+play_data.mat.  Headless: there is no viewer in this stack."""
 import os
 import sys
 
