@@ -133,7 +133,18 @@ typedef struct lg_xterm {
 #define LG_TG_SIN_MEAN 22  /* 2 */
 #define LG_TG_STATIONARY 24 /* 0 | 1 */
 #define LG_TG_V 25         /* 2: the mixed input of the last evaluation (TrajectoryGenerator.v, what dataset rollouts log) */
-#define LG_TG_STRIDE 28
+#define LG_TG_CENTER 28    /* 2: CircleTrajectoryGenerator.center (rom_dynamics.py:677-681); untouched by the other generators */
+#define LG_TG_STRIDE 30
+/* generator classes (trajectory_generator.cls; rom_dynamics.py:441-699) and weight samplers (weight_samp_cls; deep_tube_learning/
+ * utils.py:27-79), chosen per context by lg_set_traj_generator.  RANDOM is TrajectoryGenerator, the training generator; ZERO,
+ * SQUARE and CIRCLE are the fixed evaluation paths (no draws: their resample never samples).  The weight sampler only matters for
+ * RANDOM: NO_RAMP zeroes the ramp weight before normalising. */
+#define LG_TG_KIND_RANDOM 0
+#define LG_TG_KIND_ZERO 1
+#define LG_TG_KIND_SQUARE 2
+#define LG_TG_KIND_CIRCLE 3
+#define LG_TG_WSAMP_UNIFORM 0
+#define LG_TG_WSAMP_NO_RAMP 1
 typedef struct lg_traj_cfg {
     int32_t enabled, N, dN, randomize_rom_distance;
     float rom_dt, t_low, t_high, freq_low, freq_high, prob_stationary, zero_rom_dist_llh, max_push_vel_xy;
@@ -300,6 +311,13 @@ int lg_reset_all(lg_ctx *ctx);                                 /* reset_idx(aran
  * over the ids and extras["time_outs"].  ids: DEVICE int32[n], local env indices, no duplicates.  n == 0 returns at once
  * (legged_robot.py:156-157).  Draws come from the env's reset slots at the current step counter. */
 int lg_reset_ids(lg_ctx *ctx, const int32_t *ids, int n);
+/* Trajectory env: the generator class and weight sampler (LG_TG_KIND_*, LG_TG_WSAMP_*) of this context; call before the first
+ * reset.  At creation: LG_TG_KIND_RANDOM / LG_TG_WSAMP_UNIFORM.  Refused for the velocity-command env. */
+int lg_set_traj_generator(lg_ctx *ctx, int kind, int weight_sampler);
+/* Trajectory env: TrajectoryGenerator.reset(z) (rom_dynamics.py:592-593) for every env -- the window restarts at z, the clocks at
+ * -N rom_dt, and N ROM steps fill the window -- without touching the rest of the env (the observed trajectory follows at the next
+ * step callback).  z: DEVICE f32 (N, 2).  RANDOM draws its resample from the reset slots at the current step counter. */
+int lg_traj_reset(lg_ctx *ctx, const float *z);
 /* Runs the step's single-workgroup epilogue (extras["episode"], extras["time_outs"], counters) if a learner attached with
  * lg_ppo_attach_env left it pending; a no-op otherwise.  Every env entry point does this itself before it touches the env. */
 int lg_finalize(lg_ctx *ctx);

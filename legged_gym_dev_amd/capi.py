@@ -25,7 +25,11 @@ XT_EXP_NEG_WSQ_ERR, XT_WSQ, XT_SLOPED_ERR_CHANGE = 1, 2, 3
 SIGNALS = {"zero": (0, 8), "base_lin_vel": (1, 3), "base_ang_vel": (2, 3), "projected_gravity": (3, 3), "commands": (4, 4),
            "root_pos": (5, 3), "traj0": (6, 2), "prev_error": (7, 2), "dof_pos_rel": (8, MAX_DOF), "dof_vel": (9, MAX_DOF),
            "torques": (10, MAX_DOF), "actions": (11, MAX_DOF), "last_actions": (12, MAX_DOF)}      # name -> (lg_signal, length)
-TRAJ_MAX_PTS, TG_NDRAW, TG_STRIDE = 17, 20, 28
+TRAJ_MAX_PTS, TG_NDRAW, TG_STRIDE = 17, 20, 30
+TG_CENTER = 28                                                   # LG_TG_CENTER: 2 floats, CircleTrajectoryGenerator.center
+TG_KINDS = {"TrajectoryGenerator": 0, "ZeroTrajectoryGenerator": 1, "SquareTrajectoryGenerator": 2,
+            "CircleTrajectoryGenerator": 3}                      # LG_TG_KIND_*
+TG_WEIGHT_SAMPLERS = {"UniformWeightSampler": 0, "UniformWeightSamplerNoRamp": 1}    # LG_TG_WSAMP_*
 TG_FIELDS = {"weights": (0, 4), "t_final": (4, 1), "t": (5, 1), "k": (6, 1), "const": (7, 2), "extreme": (9, 2),
              "ramp_t_start": (11, 1), "ramp_v_start": (12, 2), "ramp_v_end": (14, 2), "sin_mag": (16, 2), "sin_freq": (18, 2),
              "sin_off": (20, 2), "sin_mean": (22, 2), "stationary": (24, 1), "v": (25, 2)}                        # LG_TG_* offsets

@@ -16,6 +16,7 @@ extern "C" void lgk_post_step(const DevParams *P, int N, int64_t counter, int in
 extern "C" void lgk_finalize(const DevParams *P, int accumulate, hipStream_t s);
 extern "C" void lgk_set_stage(DevParams *P, const lg_stage *st, int what, hipStream_t s);
 extern "C" void lgk_reset_all(const DevParams *P, int N, int64_t counter, int inject, int init_done, hipStream_t s);
+extern "C" void lgk_traj_reset(const DevParams *P, const float *z, int N, int64_t counter, int inject, hipStream_t s);
 extern "C" void lgk_reset_ids(const DevParams *P, const int32_t *ids, int n, int N, int64_t counter, int inject, int init_done, int traj,
                               hipStream_t s);
 
@@ -244,6 +245,19 @@ int lg_set_stream(lg_ctx *c, void *stream) { c->stream = (hipStream_t)stream; re
 int lg_set_step_counter(lg_ctx *c, int64_t v) { c->step_counter = v; return 0; }
 int64_t lg_get_step_counter(lg_ctx *c) { return c->step_counter; }
 int lg_set_init_done(lg_ctx *c, int v) { c->init_done = v; return 0; }
+int lg_set_traj_generator(lg_ctx *c, int kind, int weight_sampler) {
+    if (!c) { g_err = "null argument"; return -1; }
+    if (!c->h.cfg.traj.enabled) { g_err = "lg_set_traj_generator: not a trajectory env"; return -1; }
+    if (kind < LG_TG_KIND_RANDOM || kind > LG_TG_KIND_CIRCLE) { g_err = "lg_set_traj_generator: unknown generator kind"; return -1; }
+    if (weight_sampler != LG_TG_WSAMP_UNIFORM && weight_sampler != LG_TG_WSAMP_NO_RAMP) {
+        g_err = "lg_set_traj_generator: unknown weight sampler"; return -1;
+    }
+    c->h.tg_kind = kind;
+    c->h.tg_wsamp = weight_sampler;
+    HIPCHK(hipStreamSynchronize(c->stream));                    // kernels read the pair from the device copy of DevParams
+    HIPCHK(hipMemcpy(&c->d->tg_kind, &c->h.tg_kind, 2 * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
 int lg_inject_uniforms(lg_ctx *c, int enable) { c->inject = enable; return 0; }
 
 static int chk_launch() {
@@ -308,7 +322,8 @@ int lg_post_physics_step(lg_ctx *c) {
     const double pt = c->stage.push_time;
     const int push_now = c->h.cfg.push_robots && pt > 0.0 && std::fmod((double)c->step_counter, pt) == 0.0;
     if (c->has_pending) lgk_set_stage(c->d, &c->pending, 1, c->stream);          // what follows the callback sees the new stage
-    lgk_post_step(c->d, c->h.cfg.num_envs, c->step_counter, c->inject, c->init_done, c->h.cfg.traj.enabled, push_now, !c->defer_finalize,
+    const int traj = !c->h.cfg.traj.enabled ? 0 : (c->h.tg_kind == LG_TG_KIND_RANDOM && c->h.tg_wsamp == LG_TG_WSAMP_UNIFORM) ? 1 : 2;
+    lgk_post_step(c->d, c->h.cfg.num_envs, c->step_counter, c->inject, c->init_done, traj, push_now, !c->defer_finalize,
                   c->stream);
     c->finalize_pending = c->defer_finalize;
     if (c->has_pending) {                                                        // ... and from the next step on the callback too
@@ -327,6 +342,13 @@ int lg_debug_post_step_cycles(lg_ctx *c, unsigned long long *out /* host, 64 x 8
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(out, c->h.dbg_cycles, 64 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 0;
+}
+int lg_traj_reset(lg_ctx *c, const float *z) {                 // rom_dynamics.py:592-593
+    if (!c || !z) { g_err = "null argument"; return -1; }
+    if (!c->h.cfg.traj.enabled) { g_err = "lg_traj_reset: not a trajectory env"; return -1; }
+    flush_finalize(c);
+    lgk_traj_reset(c->d, z, c->h.cfg.num_envs, c->step_counter, c->inject, c->stream);
+    return chk_launch();
 }
 int lg_reset_ids(lg_ctx *c, const int32_t *ids, int n) {        // legged_robot.py:147-187
     if (n < 0 || (n > 0 && !ids)) { g_err = "lg_reset_ids: bad id list"; return -1; }

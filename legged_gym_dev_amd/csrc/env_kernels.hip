@@ -516,6 +516,7 @@ __device__ float xterm_value(const DevParams *P, int i, const lg_xterm &t, const
 // Inlined into their callers: as separate functions they cost k_post_step a call frame in scratch (saved registers on the
 // phase-A latency chain) and the callee's register interface -- post-step 17.3 -> 14.5 us flat, 29.2 -> 25.1 us rough terrain
 // (profiles/r03_ab.txt).
+template <bool GEN = true>
 __device__ __forceinline__ void reset_trajectory(const DevParams *P, int i, int64_t counter, int inject, float *__restrict__ win) {
     const lg_cfg &c = P->cfg;
     const int A = c.num_actions;
@@ -525,7 +526,7 @@ __device__ __forceinline__ void reset_trajectory(const DevParams *P, int i, int6
         zx += (c.traj.max_rom_dist[0] - (-c.traj.max_rom_dist[0])) * uni(P, i, LG_TSLOT_ROMD(A) + 1, counter, inject) + (-c.traj.max_rom_dist[0]);
         zy += (c.traj.max_rom_dist[1] - (-c.traj.max_rom_dist[1])) * uni(P, i, LG_TSLOT_ROMD(A) + 2, counter, inject) + (-c.traj.max_rom_dist[1]);
     }
-    tg_reset(P, i, zx, zy, counter, inject, win);
+    tg_reset<GEN>(P, i, zx, zy, counter, inject, win);
     for (int k = 0; k < 2; ++k) {
         const float d = P->buf.trajectory[(size_t)i * c.traj.N * 2 + k] - r[k];
         P->buf.prev_error[(size_t)i * 2 + k] = d * d;
@@ -596,7 +597,7 @@ __device__ void reset_env(const DevParams *P, int i, int64_t counter, int inject
 // lane before the loads of another) -- the waves of k_post_step each take one of the tile's resetting envs, so a workgroup with
 // two or three resets (Cassie under a random policy: 55 resets per step) lasts as long as one with a single reset.  The caller
 // places a barrier after its last reset.
-template <bool WAVE = false>
+template <bool WAVE = false, bool GEN = true>
 __device__ __forceinline__ void reset_env_coop(const DevParams *P, int i, int64_t counter, int inject, int init_done, float *__restrict__ win) {
     const lg_cfg &c = P->cfg;
     const int A = c.num_actions, N = c.num_envs, F = c.num_feet;
@@ -662,7 +663,7 @@ __device__ __forceinline__ void reset_env_coop(const DevParams *P, int i, int64_
     }
     sync();
     if (tj) {                                                      // needs the new root pose: after the barrier, one lane (a serial 10-step
-        if (tid == 0) reset_trajectory(P, i, counter, inject, win);   // ROM integration; resets are rare)
+        if (tid == 0) reset_trajectory<GEN>(P, i, counter, inject, win);   // ROM integration; resets are rare)
         sync();
     }
 }
@@ -688,7 +689,7 @@ __device__ __forceinline__ float height_sample(const DevParams *P, const float *
 }
 
 // The body works on one tile of TILE environments starting at env0 and touches no other environment's state.
-template <int TILE>
+template <int TILE, bool GEN>
 __device__ __forceinline__ void post_step_tile(const DevParams *__restrict__ P, const int env0, int64_t counter, int inject, int init_done,
                                                int push_now) {
     const lg_cfg &c = P->cfg;
@@ -843,7 +844,7 @@ __device__ __forceinline__ void post_step_tile(const DevParams *__restrict__ P, 
         const bool flt = P->fault[i] != 0;                                  // physics fault guard (lg_physics.h)
         const bool to = ep > c.max_episode_length;
         rst = rst || flt || to;
-        if (c.traj.enabled) tg_callback_step(P, i, counter, inject, s_win[e16]);   // LT:405-417
+        if (c.traj.enabled) tg_callback_step<GEN>(P, i, counter, inject, s_win[e16]);   // LT:405-417
         else if (ep % c.resample_steps == 0) resample_commands(P, i, LG_SLOT_CMD, counter, inject, P->cb.cmd_lo, P->cb.cmd_hi);   // LR:348-350
         if (c.heading_command && !c.traj.enabled) {                         // LR:351-354, math.py:45-48
             V3 fwd = quat_apply(r + 3, V3{1.0f, 0.0f, 0.0f});
@@ -920,7 +921,7 @@ __device__ __forceinline__ void post_step_tile(const DevParams *__restrict__ P, 
     __syncthreads();
     STAMP(2);
     for (int q = tid >> 6; q < s_cnt; q += LG_TILE_THREADS / 64)      // one wave per resetting env (wave-uniform trip count)
-        reset_env_coop<true>(P, s_list[q], counter, inject, init_done, s_win[tid >> 6]);
+        reset_env_coop<true, GEN>(P, s_list[q], counter, inject, init_done, s_win[tid >> 6]);
     if (s_cnt > 0) __syncthreads();                                   // workgroup-uniform: phase O reads what the resets wrote
     STAMP(3);
     if (s_cnt > 0) {
@@ -1023,10 +1024,11 @@ __device__ __forceinline__ void post_step_tile(const DevParams *__restrict__ P, 
 // Measured and not kept: __attribute__((amdgpu_waves_per_eu(1, 2))) (a 256-VGPR budget: the launch is one wave per SIMD at 4096
 // envs).  It removes the last scratch bytes but the allocator then parks the trajectory window in LDS (+32 KB) and the kernel
 // schedules for occupancy 2: 26.4 vs 14.5 us flat, 38.4 vs 25.1 us rough (profiles/r03_ab.txt).
-template <int TILE>
+// GEN: the trajectory env's generator dispatch (lg_traj.h); false for every env whose generator is the default one.
+template <int TILE, bool GEN>
 __global__ void __launch_bounds__(LG_TILE_THREADS) k_post_step(const DevParams *__restrict__ P, int64_t counter, int inject,
                                                                int init_done, int push_now) {
-    post_step_tile<TILE>(P, (int)blockIdx.x * TILE, counter, inject, init_done, push_now);
+    post_step_tile<TILE, GEN>(P, (int)blockIdx.x * TILE, counter, inject, init_done, push_now);
 }
 
 // A curriculum stage (legged_hip.h lg_stage) into the device constants.  what & 1: the values read after the step callback
@@ -1090,6 +1092,14 @@ __global__ void __launch_bounds__(64) k_reset_all(const DevParams *__restrict__ 
     P->reset_mark[i] = 0;
 }
 
+// TrajectoryGenerator.reset(z) (RD:592-593) for every env from a device z (N, 2): the generator alone, one lane per env
+__global__ void __launch_bounds__(64) k_traj_reset(const DevParams *__restrict__ P, const float *__restrict__ z, int64_t counter, int inject) {
+    __shared__ float s_win[64][LG_TG_WIN];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P->cfg.num_envs) return;
+    tg_reset(P, i, z[2 * i], z[2 * i + 1], counter, inject, s_win[threadIdx.x]);
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
 extern "C" void lgk_set_actions(const DevParams *P, const float *a, int n, hipStream_t s) {
     int blocks = (n + 255) / 256;
@@ -1142,16 +1152,23 @@ extern "C" void lgk_set_stage(DevParams *P, const lg_stage *st, int what, hipStr
 extern "C" void lgk_finalize(const DevParams *P, int accumulate, hipStream_t s) {
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, s, P, accumulate);
 }
-// finalize = 0: the caller defers the single-workgroup epilogue (lg_ctx.defer_finalize)
+// finalize = 0: the caller defers the single-workgroup epilogue (lg_ctx.defer_finalize).  traj: 0 velocity-command env, 1 trajectory
+// env with TrajectoryGenerator + UniformWeightSampler, 2 any other generator / weight sampler (lg_set_traj_generator)
 extern "C" void lgk_post_step(const DevParams *P, int N, int64_t counter, int inject, int init_done, int traj, int push_now, int finalize,
                               hipStream_t s) {
     constexpr int TILE = 16;
-    hipLaunchKernelGGL((k_post_step<TILE>), dim3((N + TILE - 1) / TILE), dim3(LG_TILE_THREADS), 0, s, P, counter, inject, init_done, push_now);
+    if (traj == 2)
+        hipLaunchKernelGGL((k_post_step<TILE, true>), dim3((N + TILE - 1) / TILE), dim3(LG_TILE_THREADS), 0, s, P, counter, inject, init_done, push_now);
+    else
+        hipLaunchKernelGGL((k_post_step<TILE, false>), dim3((N + TILE - 1) / TILE), dim3(LG_TILE_THREADS), 0, s, P, counter, inject, init_done, push_now);
     if (traj) hipLaunchKernelGGL(k_traj_late, dim3((N + 255) / 256), dim3(256), 0, s, P, counter, inject);
     if (finalize) hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, s, P, 1);
 }
 extern "C" void lgk_reset_all(const DevParams *P, int N, int64_t counter, int inject, int init_done, hipStream_t s) {
     hipLaunchKernelGGL(k_reset_all, dim3((N + 63) / 64), dim3(64), 0, s, P, counter, inject, init_done);
+}
+extern "C" void lgk_traj_reset(const DevParams *P, const float *z, int N, int64_t counter, int inject, hipStream_t s) {
+    hipLaunchKernelGGL(k_traj_reset, dim3((N + 63) / 64), dim3(64), 0, s, P, z, counter, inject);
 }
 extern "C" void lgk_reset_ids(const DevParams *P, const int32_t *ids, int n, int N, int64_t counter, int inject, int init_done, int traj,
                               hipStream_t s) {

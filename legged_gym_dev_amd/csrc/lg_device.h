@@ -89,6 +89,9 @@ struct DevParams {
     // every model constant one (env, leg) lane of the physics reads, flattened per leg (host-built once;
     // the kernel copies it into LDS with one coalesced pass): LG_LT_* offsets below
     float leg_tab[8][LG_LT_STRIDE];
+    // trajectory env: generator class / weight sampler (LG_TG_KIND_*, LG_TG_WSAMP_*; lg_set_traj_generator).  Last, so that no
+    // member the other kernels read moves.
+    int tg_kind, tg_wsamp;
 };
 
 struct lg_ctx {

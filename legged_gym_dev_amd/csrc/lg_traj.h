@@ -24,7 +24,11 @@ __device__ __forceinline__ TgPar tg_par_cb(const DevParams *P) {           // ..
     const StageCb &b = P->cb;
     return {{b.v_min[0], b.v_min[1]}, {b.v_max[0], b.v_max[1]}, b.t_low, b.t_high, c.freq_low, c.freq_high, c.prob_stationary};
 }
+// GEN (template flag of the functions below): false = TrajectoryGenerator with UniformWeightSampler only, the kind and sampler
+// folded at compile time so that k_post_step's default build is the code it was before the evaluation generators existed (a
+// runtime branch there cost 21 -> 26 us per post-step at 4096 envs); true = dispatch on DevParams.tg_kind / tg_wsamp.
 // RD:507-515
+template <bool GEN = true>
 __device__ inline void tg_resample(const DevParams *P, const TgPar &t, int i, int slot0, int64_t counter, int inject) {
 #pragma clang fp contract(off)      // one rounding per torch op: the event comparisons below must agree with the reference
     float *s = P->buf.tg_state + (size_t)i * LG_TG_STRIDE;
@@ -61,7 +65,10 @@ __device__ inline void tg_resample(const DevParams *P, const TgPar &t, int i, in
     s[LG_TG_T_FINAL] += (t.t_high - t.t_low) * tg_uni(P, i, slot0 + 14, counter, inject) + t.t_low;
     float w[4], sum = 0.0f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { w[k] = tg_uni(P, i, slot0 + 15 + k, counter, inject); sum += w[k]; }
+    for (int k = 0; k < 4; ++k) w[k] = tg_uni(P, i, slot0 + 15 + k, counter, inject);
+    if (GEN && P->tg_wsamp == LG_TG_WSAMP_NO_RAMP) w[1] = 0.0f;          // UniformWeightSamplerNoRamp (DU:69-79): the same 4 draws, no ramp
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sum += w[k];
 #pragma unroll
     for (int k = 0; k < 4; ++k) s[LG_TG_W + k] = w[k] / sum;
     s[LG_TG_STATIONARY] = ((1.0f - 0.0f) * tg_uni(P, i, slot0 + 19, counter, inject) + 0.0f) < t.prob_stationary ? 1.0f : 0.0f;
@@ -79,6 +86,46 @@ __device__ inline void tg_input(const DevParams *P, int i, float tt, float v[2])
         float x = s[LG_TG_W + 0] * s[LG_TG_CONST + d] + s[LG_TG_W + 1] * ramp + s[LG_TG_W + 2] * s[LG_TG_EXTREME + d] + s[LG_TG_W + 3] * sinus;
         v[d] = s[LG_TG_STATIONARY] != 0.0f ? 0.0f : x;
     }
+}
+
+// The fixed evaluation paths (RD:618-699, SingleInt2D): input laws without draws.  b: the ROM bounds in force (rom.v_min / v_max).
+// RD:627-666 SquareTrajectoryGenerator: piecewise constant in the env's own time, zero outside [0, c4) (the reset loop's negative
+// times included); the fourth leg is v_x = v_min[1], as the reference writes it.
+__device__ __forceinline__ void tg_input_square(const TgPar &b, float tt, float v[2]) {
+#pragma clang fp contract(off)
+    const float c1 = 2.0f / b.v_max[1];
+    const float c2 = c1 + 1.0f / b.v_max[0];
+    const float c3 = c2 + 2.0f / fabsf(b.v_min[1]);
+    const float c4 = c3 + 1.0f / fabsf(b.v_min[0]);
+    v[0] = 0.0f; v[1] = 0.0f;
+    if (0.0f <= tt && tt < c1) v[1] = b.v_max[1] / 2.0f;
+    if (c1 <= tt && tt < c2) v[0] = b.v_max[0];
+    if (c2 <= tt && tt < c3) v[1] = b.v_min[1] / 2.0f;
+    if (c3 <= tt && tt < c4) v[0] = b.v_min[1];
+}
+// RD:684-690 CircleTrajectoryGenerator: steer the last window point z onto the circle of radius 0.5 about the env's centre
+__device__ __forceinline__ void tg_input_circle(const TgPar &b, const float *s, float zx, float zy, float v[2]) {
+#pragma clang fp contract(off)
+    const float ex = zx - s[LG_TG_CENTER], ey = zy - s[LG_TG_CENTER + 1];
+    float vx = -ey, vy = ex;
+    const float n0 = sqrtf(vx * vx + vy * vy);
+    vx = vx + -(ex - 0.5f * ex / n0);
+    vy = vy + -(ey - 0.5f * ey / n0);
+    const float n1 = sqrtf(vx * vx + vy * vy);
+    const float m = fminf(fminf(b.v_max[0], fabsf(b.v_min[0])), fminf(b.v_max[1], fabsf(b.v_min[1])));
+    v[0] = vx / n1 * m;
+    v[1] = vy / n1 * m;
+}
+// get_input_t of the configured class + the stationary mask of step_rom_idx (RD:579-580).  kind is kernel-uniform (DevParams):
+// TrajectoryGenerator takes the first branch and never reads z.  z: the window's last point (LDS or HBM).
+__device__ __forceinline__ void tg_input_kind(const DevParams *P, const TgPar &b, int i, float tt, const float *z, float v[2]) {
+    const int kind = P->tg_kind;
+    if (kind == LG_TG_KIND_RANDOM) { tg_input(P, i, tt, v); return; }
+    const float *s = P->buf.tg_state + (size_t)i * LG_TG_STRIDE;
+    v[0] = 0.0f; v[1] = 0.0f;                                      // ZeroTrajectoryGenerator (RD:618-625)
+    if (kind == LG_TG_KIND_SQUARE) tg_input_square(b, tt, v);
+    else if (kind == LG_TG_KIND_CIRCLE) tg_input_circle(b, s, z[0], z[1], v);
+    if (s[LG_TG_STATIONARY] != 0.0f) { v[0] = 0.0f; v[1] = 0.0f; }
 }
 
 // The window of ROM states of env i while it is being stepped: a workspace of LG_TG_WIN floats in LDS handed in by the kernel
@@ -119,15 +166,20 @@ __device__ inline void tg_window_interpolate(const DevParams *P, int i, const fl
 }
 
 // LT:409-411: traj_gen.step() (RD:567-576) + get_trajectory
+template <bool GEN = true>
 __device__ inline void tg_callback_step(const DevParams *P, int i, int64_t counter, int inject, float *__restrict__ w) {
 #pragma clang fp contract(off)      // one rounding per torch op: the event comparisons below must agree with the reference
     const lg_traj_cfg &t = P->cfg.traj;
     float *s = P->buf.tg_state + (size_t)i * LG_TG_STRIDE;
     tg_window_load(P, i, w);
     const float tt = s[LG_TG_T];
-    if (tt > s[LG_TG_T_FINAL]) tg_resample(P, tg_par_cb(P), i, LG_TSLOT_TG, counter, inject);
     float v[2];
-    tg_input(P, i, tt, v);
+    if (!GEN || P->tg_kind == LG_TG_KIND_RANDOM) {
+        if (tt > s[LG_TG_T_FINAL]) tg_resample<GEN>(P, tg_par_cb(P), i, LG_TSLOT_TG, counter, inject);
+        tg_input(P, i, tt, v);
+    } else {                                                       // the evaluation classes never resample here (RD:618-699)
+        tg_input_kind(P, tg_par_cb(P), i, tt, w + 2 * (t.N * t.dN), v);
+    }
     float k = s[LG_TG_K];
     const bool rom = tt >= k * t.rom_dt - 1e-5f;
     if (rom) { tg_window_step(P, w, v); k += 1.0f; }
@@ -140,6 +192,7 @@ __device__ inline void tg_callback_step(const DevParams *P, int i, int64_t count
 }
 
 // RD:597-608 with the start state z0 (LT:222-229)
+template <bool GEN = true>
 __device__ inline void tg_reset(const DevParams *P, int i, float z0x, float z0y, int64_t counter, int inject, float *__restrict__ w) {
 #pragma clang fp contract(off)      // one rounding per torch op: the event comparisons below must agree with the reference
     const lg_traj_cfg &t = P->cfg.traj;
@@ -150,10 +203,14 @@ __device__ inline void tg_reset(const DevParams *P, int i, float z0x, float z0y,
     s[LG_TG_K] = -(float)(t.N * t.dN);
     s[LG_TG_T] = s[LG_TG_K] * t.rom_dt;
     s[LG_TG_T_FINAL] = s[LG_TG_K] * t.rom_dt;
-    tg_resample(P, tg_par_cfg(P), i, LG_TSLOT_RTG(A), counter, inject);
+    const int kind = GEN ? P->tg_kind : LG_TG_KIND_RANDOM;
+    if (kind == LG_TG_KIND_RANDOM) tg_resample<GEN>(P, tg_par_cfg(P), i, LG_TSLOT_RTG(A), counter, inject);
+    else if (kind == LG_TG_KIND_ZERO) s[LG_TG_STATIONARY] = 1.0f;              // RD:620-621
+    else if (kind == LG_TG_KIND_CIRCLE) { s[LG_TG_CENTER] = z0x - 0.5f; s[LG_TG_CENTER + 1] = z0y; }   // RD:679-681
     float tt = s[LG_TG_T], k = s[LG_TG_K], v[2] = {0.0f, 0.0f};
     for (int it = 0; it < t.N * t.dN; ++it) {
-        tg_input(P, i, tt, v);
+        if (kind == LG_TG_KIND_RANDOM) tg_input(P, i, tt, v);
+        else tg_input_kind(P, tg_par_cfg(P), i, tt, w + 2 * (npts - 1), v);
         tg_window_step(P, w, v);
         k += 1.0f;
         tt += t.rom_dt;
@@ -168,8 +225,17 @@ __device__ inline void tg_reset(const DevParams *P, int i, float z0x, float z0y,
 __device__ inline void tg_late_resample(const DevParams *P, int i, int64_t counter, int inject) {
 #pragma clang fp contract(off)      // one rounding per torch op: the event comparisons below must agree with the reference
     float *s = P->buf.tg_state + (size_t)i * LG_TG_STRIDE;
-    if (s[LG_TG_T] > s[LG_TG_T_FINAL]) tg_resample(P, tg_par_cfg(P), i, LG_TSLOT_RTG(P->cfg.num_actions), counter, inject);
     float v[2];                                                    // and leaves self.v evaluated at the env's new time
-    tg_input(P, i, s[LG_TG_T], v);
+    if (P->tg_kind == LG_TG_KIND_RANDOM) {
+        if (s[LG_TG_T] > s[LG_TG_T_FINAL]) tg_resample(P, tg_par_cfg(P), i, LG_TSLOT_RTG(P->cfg.num_actions), counter, inject);
+        tg_input(P, i, s[LG_TG_T], v);
+    } else {
+        if (P->tg_kind == LG_TG_KIND_CIRCLE) {                     // Circle.resample re-centres EVERY env on reset_traj's p_zx
+            const float *r = P->buf.root_states + (size_t)i * 13;  // (LT:248-253): a non-reset env's own root xy, no start offset
+            s[LG_TG_CENTER] = r[0] - 0.5f; s[LG_TG_CENTER + 1] = r[1];
+        }
+        const int n2 = 2 * (P->cfg.traj.N * P->cfg.traj.dN + 1);
+        tg_input_kind(P, tg_par_cfg(P), i, s[LG_TG_T], P->buf.tg_traj + (size_t)i * n2 + n2 - 2, v);
+    }
     s[LG_TG_V] = v[0]; s[LG_TG_V + 1] = v[1];
 }

@@ -104,15 +104,18 @@ CONTRACT = [
     ("rewards.reward_weighting.*", INERT, "weights of reduced-order models other than SingleInt2D (rom_dynamics.py:209-211 reads position only)"),
     ("rewards.*", CONSUMED, "setup"),
     # ---- trajectory generator / reduced-order model (trajectory env)
-    ("rom.cls", FIXED, "SingleInt2D is the implemented reduced-order model", ("SingleInt2D",)),
+    ("rom.cls", FIXED, "SingleInt2D is the implemented reduced-order model; the reference env cannot run the others either "
+     "(legged_robot_trajectory.py:279 subtracts an (N, 1, 2) offset from an (N, N_traj, n) window)", ("SingleInt2D",)),
     ("rom.dt", CONSUMED, "setup"),
     ("rom.v_min", CONSUMED, "setup"),
     ("rom.v_max", CONSUMED, "setup"),
     ("rom.*", INERT, "state bounds / curricula of other reduced-order models: SingleInt2D.clip_v_z returns v unchanged (rom_dynamics.py:201-202) "
      "and legged_robot_trajectory.py:89-103 passes nothing else"),
-    ("trajectory_generator.cls", FIXED, "TrajectoryGenerator is the implemented generator", ("TrajectoryGenerator",)),
+    ("trajectory_generator.cls", CONSUMED, "setup: lg_set_traj_generator (TrajectoryGenerator and the Zero / Square / Circle "
+     "evaluation generators; env_setup._parse_trajectory refuses any other name)"),
     ("trajectory_generator.t_samp_cls", FIXED, "UniformSampleHoldDT is the implemented hold-time sampler", ("UniformSampleHoldDT",)),
-    ("trajectory_generator.weight_samp_cls", FIXED, "UniformWeightSampler is the implemented weight sampler", ("UniformWeightSampler",)),
+    ("trajectory_generator.weight_samp_cls", CONSUMED, "setup: lg_set_traj_generator (UniformWeightSampler, UniformWeightSamplerNoRamp; "
+     "env_setup._parse_trajectory refuses UniformWeightSamplerNoExtreme, which raises in the reference, and unknown names)"),
     ("trajectory_generator.dN", FIXED, "one ROM step per trajectory point", (1,)),
     ("trajectory_generator.DN", INERT, "the fork's misspelling of dN; nothing reads it"),
     ("trajectory_generator.seed", INERT, "seeds the numpy generator of the casadi backend; the torch backend the env uses draws from torch's "

@@ -218,17 +218,27 @@ class EnvSetup:
         rom, tg, dr = cfg.rom, cfg.trajectory_generator, cfg.domain_rand
         if rom.cls != "SingleInt2D":
             raise NotImplementedError(f"reduced-order model {rom.cls!r}: the HIP step implements SingleInt2D (the fork's ANYmal "
-                                      "trajectory tasks); DoubleInt2D / unicycle models are not implemented")
-        if tg.cls != "TrajectoryGenerator" or tg.t_samp_cls != "UniformSampleHoldDT":
-            raise NotImplementedError(f"trajectory generator {tg.cls!r} / time sampler {tg.t_samp_cls!r} are not implemented")
-        if tg.weight_samp_cls != "UniformWeightSampler":
-            raise NotImplementedError(f"weight sampler {tg.weight_samp_cls!r}: only UniformWeightSampler is implemented")
+                                      "trajectory tasks); the reference env cannot run the others either (legged_robot_trajectory.py:279 "
+                                      "subtracts an (N, 1, 2) offset from the (N, N_traj, n) window of any model with n != 2)")
+        if tg.cls not in capi.TG_KINDS:
+            raise NotImplementedError(f"trajectory generator {tg.cls!r}: not a generator class of rom_dynamics.py (implemented: "
+                                      f"{', '.join(capi.TG_KINDS)})")
+        if tg.t_samp_cls != "UniformSampleHoldDT":
+            raise NotImplementedError(f"time sampler {tg.t_samp_cls!r}: only UniformSampleHoldDT is implemented")
+        if tg.weight_samp_cls == "UniformWeightSamplerNoExtreme":
+            raise NotImplementedError("weight sampler 'UniformWeightSamplerNoExtreme': not implemented because the reference cannot "
+                                      "run it -- its sample() applies np.sum to a torch tensor, which raises TypeError "
+                                      "(deep_tube_learning/utils.py:64)")
+        if tg.weight_samp_cls not in capi.TG_WEIGHT_SAMPLERS:
+            raise NotImplementedError(f"weight sampler {tg.weight_samp_cls!r}: not a sampler of deep_tube_learning/utils.py "
+                                      f"(implemented: {', '.join(capi.TG_WEIGHT_SAMPLERS)})")
         dN = int(getattr(tg, "dN", 1))
         if int(tg.N) * dN + 1 > capi.TRAJ_MAX_PTS:
             raise ValueError("trajectory window longer than LG_TRAJ_MAX_PTS")
         if dN != 1:
-            raise NotImplementedError("trajectory_generator.dN != 1 is not implemented")
-        return {"N": int(tg.N), "dN": dN, "rom_dt": float(rom.dt), "t_low": float(tg.t_low), "t_high": float(tg.t_high),
+            raise NotImplementedError("trajectory_generator.dN != 1 is not implemented: the interpolated window is one ROM step "
+                                      "per observed point")
+        return {"kind": capi.TG_KINDS[tg.cls], "weight_sampler": capi.TG_WEIGHT_SAMPLERS[tg.weight_samp_cls], "N": int(tg.N), "dN": dN, "rom_dt": float(rom.dt), "t_low": float(tg.t_low), "t_high": float(tg.t_high),
                 "freq_low": float(tg.freq_low), "freq_high": float(tg.freq_high), "prob_stationary": float(tg.prob_stationary),
                 "v_min": [float(v) for v in rom.v_min], "v_max": [float(v) for v in rom.v_max],
                 "obs_scale": [float(v) for v in cfg.normalization.obs_scales.trajectory],

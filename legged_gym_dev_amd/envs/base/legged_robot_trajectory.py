@@ -16,18 +16,30 @@ from .reward_terms import ExpNegWeightedSqErr, SlopedErrChange
 
 class _TrajGenView:
     """Read-only face of the device-side generator state under the reference's TrajectoryGenerator attribute names
-    (rom_dynamics.py:484-505)."""
+    (rom_dynamics.py:484-505); ``center`` for CircleTrajectoryGenerator (:679-681), ``reset(z)`` (:592-593).  The class name
+    is the configured generator's (trajectory_generator.cls)."""
 
     def __init__(self, env):
-        self._t, self.N, self.dN = env.core.t, env.setup.traj["N"], env.setup.traj["dN"]
+        self._core, self._t, self.N, self.dN = env.core, env.core.t, env.setup.traj["N"], env.setup.traj["dN"]
         for name, (off, n) in capi.TG_FIELDS.items():
             v = self._t["tg_state"][:, off:off + n]
             setattr(self, {"const": "sample_hold_input", "extreme": "extreme_input", "stationary": "stationary_inds"}.get(name, name),
                     v if n > 1 else v[:, 0])
+        if env.setup.traj["kind"] == capi.TG_KINDS["CircleTrajectoryGenerator"]:
+            self.center = self._t["tg_state"][:, capi.TG_CENTER:capi.TG_CENTER + 2]
         self.trajectory = self._t["tg_traj"]
 
     def get_trajectory(self):
         return self._t["trajectory"]
+
+    def reset(self, z):
+        """TrajectoryGenerator.reset(z) for every env from z (N, 2): the window restarts at z (lg_traj_reset)."""
+        import ctypes as C
+        zc = torch.as_tensor(z, device=self._t["tg_traj"].device, dtype=torch.float32).reshape(-1, 2).contiguous()
+        if zc.shape[0] != self._t["tg_traj"].shape[0]:
+            raise ValueError(f"reset(z): z has {zc.shape[0]} rows, the generator {self._t['tg_traj'].shape[0]} envs")
+        self._z = zc                                     # kept alive until the next call (the launch is asynchronous)
+        self._core.call("traj_reset", C.c_void_p(zc.data_ptr()))
 
 
 class _RomView:
@@ -59,7 +71,7 @@ class LeggedRobotTrajectory(LeggedRobot):
         self.trajectory, self.prev_error = t["trajectory"], t["prev_error"]
         self.time_until_next_push = t["push_timer"].view(self.num_envs, 1)
         self.trajectory_scale = torch.tensor(tj["obs_scale"], device=self.device).repeat(tj["N"], 1)
-        self.traj_gen = _TrajGenView(self)
+        self.traj_gen = type(self.cfg.trajectory_generator.cls, (_TrajGenView,), {})(self)
         self.rom = self.traj_gen.rom = _RomView(tj, self.device)
         self.tracking_sigma = float(self.cfg.rewards.tracking_sigma)
         self.max_rom_distance = torch.tensor(tj["max_rom_dist"], device=self.device)

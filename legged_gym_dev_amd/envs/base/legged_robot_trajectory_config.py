@@ -10,6 +10,12 @@ trajectory config give them:
     domain_rand.randomize_rom_distance = False, .max_rom_dist = [0, 0], .zero_rom_distance_likelihood = 0.25,
     domain_rand.rigid_shape_properties.* = False, .randomize_inv_base_mass = False,
     rewards.tracking_sigma = 0.25, curriculum.use_curriculum = False.
+
+trajectory_generator.cls selects the generator as the reference's globals() lookup does (legged_robot_trajectory.py:105-122):
+'TrajectoryGenerator' (training) or the evaluation paths 'ZeroTrajectoryGenerator', 'SquareTrajectoryGenerator',
+'CircleTrajectoryGenerator' (trajopt/rom_dynamics.py:618-699; scripts/evaluate_tracking.py).  weight_samp_cls:
+'UniformWeightSampler' or 'UniformWeightSamplerNoRamp' (deep_tube_learning/utils.py:69-79).  Refused at construction:
+rom.cls other than 'SingleInt2D', 'UniformWeightSamplerNoExtreme' (raises TypeError in the reference), dN != 1.
 """
 from .base_config import BaseConfig, S, cfg_class
 from .legged_robot_config import LeggedRobotCfg, LeggedRobotCfgPPO

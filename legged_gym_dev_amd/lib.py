@@ -123,6 +123,8 @@ class HipEnvCore:
             ptr = C.cast(getattr(bufs, name), C.c_void_p).value
             self.t[name] = device_tensor(ptr, shape, dt, self, self.device)
         self.use_current_stream()
+        if setup.traj is not None:                        # before the first reset (include/legged_hip.h lg_set_traj_generator)
+            self.call("set_traj_generator", int(setup.traj["kind"]), int(setup.traj["weight_sampler"]))
 
     def use_current_stream(self):
         import torch
