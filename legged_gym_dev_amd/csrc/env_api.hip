@@ -359,27 +359,14 @@ int lg_reset_ids(lg_ctx *c, const int32_t *ids, int n) {        // legged_robot.
 }
 // the control loop alone (clip + decimation x {torques, physics}), without the post-step: timing / profiling entry
 int lg_debug_control_loop(lg_ctx *c, const float *actions) { return run_substeps(c, actions, 3, c->h.cfg.decimation); }
-static int g_fused_substeps = 1;
-int lg_debug_set_fused(int v) { g_fused_substeps = v; return 0; }
 extern "C" void lgk_debug_set_substeps_nw(int v);
 extern "C" void lgk_debug_set_substeps_occ(int v);
 int lg_debug_set_substeps_occ(int v) { lgk_debug_set_substeps_occ(v); return 0; }     // control-loop register budget: 0 by grid size, 1 / 2 forced
 int lg_debug_set_substeps_nw(int v) { lgk_debug_set_substeps_nw(v); return 0; }   // control-loop block shape: 4 waves / 64/L envs, or 2 / 32/L
-extern "C" void lgk_debug_set_phys_pair(int v);
-int lg_debug_set_phys_pair(int v) { lgk_debug_set_phys_pair(v); return 0; }   // physics lane map: 1 pair-lane (default), 0 one lane per leg
 
 int lg_step(lg_ctx *c, const float *actions) {                  // legged_robot.py:80-104
-    int rc;
     flush_finalize(c);
-    if (g_fused_substeps) {                                     // one launch for clip + decimation x {torques, physics}
-        rc = run_substeps(c, actions, 3, c->h.cfg.decimation);
-    } else {                                                    // launch per substep (A/B and debugging)
-        rc = lg_set_actions(c, actions);
-        for (int d = 0; d < c->h.cfg.decimation && !rc; ++d) {
-            rc = lg_compute_torques(c);
-            if (!rc) rc = lg_simulate(c);
-        }
-    }
+    int rc = run_substeps(c, actions, 3, c->h.cfg.decimation);     // one launch for clip + decimation x {torques, physics}
     if (!rc) rc = lg_post_physics_step(c);
     return rc;
 }

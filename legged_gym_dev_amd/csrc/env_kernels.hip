@@ -102,7 +102,7 @@ __device__ __forceinline__ void lstm8_rows(const float *__restrict__ wr, int k, 
 // the robot state (root, q, qd), the actuator-net state (h, c of both layers) and the model constants resident in
 // registers / LDS for the whole loop -- read once and written once per env step instead of once per substep, and 1 launch
 // instead of 1 + 2 x decimation.  Block = 4 waves = 64/L environments.  Waves 0 and 1 run the physics, two lanes per
-// (env, leg) (lg_physics_pair.h; PAIR = false: wave 0 alone, one lane per (env, leg), lg_physics.h).  All 256 lanes run the
+// (env, leg) (lg_physics_pair.h).  All 256 lanes run the
 // actuator net (8 lanes per (env, joint) row, 2J rounds per substep, the state of each round in VGPRs); PD laws are evaluated
 // by the physics lanes for their own joints.  q, qd and tau cross between the two lane maps through LDS.
 //
@@ -120,14 +120,14 @@ __device__ __forceinline__ void lstm8_rows(const float *__restrict__ wr, int k, 
 // OCC = waves per SIMD the kernel is compiled for.  1: the whole register file (292 VGPRs for the quadruped), the shape every launch of up
 // to one workgroup per CU takes; 2: 256 VGPRs (152 B of scratch), so that two workgroups of a larger env count share a CU instead of
 // running one after the other (8192 envs: 110 us against 143; at 4096 the spills cost 6 %: profiles/r04_env_count_sweep.txt).
-template <int L, int J, bool LSTM, bool PAIR, int NW = 4, int OCC = 1>
+template <int L, int J, bool LSTM, int NW = 4, int OCC = 1>
 __global__ void __launch_bounds__(64 * NW, OCC) k_substeps(const DevParams *__restrict__ P, const float *__restrict__ a_in, int mode, int iters) {
-    // NW waves per block.  NW = 4: two physics waves (pair-lane map) + two that only run the actuator net, 64/L envs.  NW = 2 (pair-lane
-    // map only): one physics wave + one actuator-net wave, 32/L envs -- two such blocks per CU, and no physics wave ever waits at a
-    // substep barrier for the other one's contacts (LG_SUBSTEPS_NW).
-    static_assert(NW == 4 || (NW == 2 && PAIR), "block shapes: 4 waves, or 2 waves with the pair-lane physics");
+    // NW waves per block.  NW = 4: two physics waves + two that only run the actuator net, 64/L envs.  NW = 2: one physics wave + one
+    // actuator-net wave, 32/L envs -- two such blocks per CU, and no physics wave ever waits at a substep barrier for the other one's
+    // contacts (LG_SUBSTEPS_NW).
+    static_assert(NW == 4 || NW == 2, "block shapes: 4 waves or 2 waves");
     constexpr int NT = 64 * NW, RPP = NT / 8;                   // threads; actuator-net rows per pass (8 lanes per row)
-    constexpr int PW = PAIR ? NW / 2 : 1, LPE = PAIR ? 2 * L : L;    // physics waves of the block, physics lanes per env
+    constexpr int PW = NW / 2, LPE = 2 * L;                  // physics waves of the block, physics lanes per env
     constexpr int A = L * J, EPW = 64 * PW / LPE, ROWS = EPW * A, NR = ROWS * 8 / NT;
     const lg_cfg &c = P->cfg;
     const lg_model &m = P->model;
@@ -177,13 +177,12 @@ __global__ void __launch_bounds__(64 * NW, OCC) k_substeps(const DevParams *__re
             h0[r] = P->buf.lstm_h[idx]; c0[r] = P->buf.lstm_c[idx]; h1[r] = P->buf.lstm_h[ls + idx]; c1[r] = P->buf.lstm_c[ls + idx];
         }
     }
-    // physics lanes: wave 0, one lane per (env, leg) -- or waves 0 and 1, two lanes per (env, leg) (lg_physics_pair.h);
-    // of a pair, lane h = 0 does the stores
+    // physics lanes: the first PW waves, two lanes per (env, leg) (lg_physics_pair.h); of a pair, lane h = 0 does the stores
     const int ptid = tid & (64 * PW - 1);
-    const bool phys = wave < PW, hrole = PAIR && (ptid & 1), writer = !hrole;
+    const bool phys = wave < PW, hrole = ptid & 1, writer = !hrole;
     const int pe = ptid / LPE;                               // env of this lane within the block
     int env = env0 + pe;
-    const int leg = PAIR ? (ptid >> 1) % L : ptid % L;
+    const int leg = (ptid >> 1) % L;
     const bool live = env < N;
     if (!live) env = N - 1;
     const int rl0 = pe * A + leg * J;                        // first row of this lane's joints in the block
@@ -286,15 +285,9 @@ __global__ void __launch_bounds__(64 * NW, OCC) k_substeps(const DevParams *__re
             for (int s = 0; s < ns; ++s) {
                 V3 fslot[LG_MAX_LEG_SLOTS], fbase;
                 int fault;                                          // bit 0: non-finite solve (reset), bit 1: base velocity clamped
-                V3 fb;
-                if constexpr (PAIR) {
-                    fault = physics_pair<L, J>(pk, leg, hrole, ptid >> 1, ptid, dt, root, q, qd, tau, fr, dm, s_mat + 4 * pe, fslot, fbase, s_ct, s_lk,
-                                               s_lk + J * LG_LKP_NF * 64, s_lt, s_lm, pr, last);
-                    fb = pleg_sum<L>(fbase);
-                } else {
-                    fault = physics_lane<L, J>(P, leg, dt, root, q, qd, tau, fr, dm, s_mat + 4 * pe, fslot, fbase, s_ct, s_lk, s_lt, s_lm);
-                    fb = {leg_sum<L>(fbase.x), leg_sum<L>(fbase.y), leg_sum<L>(fbase.z)};
-                }
+                fault = physics_pair<L, J>(pk, leg, hrole, ptid >> 1, ptid, dt, root, q, qd, tau, fr, dm, s_mat + 4 * pe, fslot, fbase, s_ct, s_lk,
+                                           s_lk + J * LG_LKP_NF * 64, s_lt, s_lm, pr, last);
+                const V3 fb = pleg_sum<L>(fbase);
                 if ((fault & 1) && live && leg == 0 && writer) P->fault[env] = 1;
                 if ((fault & 2) && live && leg == 0 && writer) atomicAdd(P->clamp_count, 1);
                 if (last && live && writer) {
@@ -841,7 +834,7 @@ __device__ __forceinline__ void post_step_tile(const DevParams *__restrict__ P, 
         }
         bool rst = false;                                                   // LR:139-145 (contact forces do not change below)
         for (int b = 0; b < c.num_term; ++b) rst |= fnorm3(cf + 3 * c.term_idx[b]) > 1.0f;
-        const bool flt = P->fault[i] != 0;                                  // physics fault guard (lg_physics.h)
+        const bool flt = P->fault[i] != 0;                                  // physics fault guard (lg_physics_pair.h)
         const bool to = ep > c.max_episode_length;
         rst = rst || flt || to;
         if (c.traj.enabled) tg_callback_step<GEN>(P, i, counter, inject, s_win[e16]);   // LT:405-417
@@ -1105,15 +1098,7 @@ extern "C" void lgk_set_actions(const DevParams *P, const float *a, int n, hipSt
     int blocks = (n + 255) / 256;
     hipLaunchKernelGGL(k_set_actions, dim3(blocks > 1024 ? 1024 : blocks), dim3(256), 0, s, P, a);
 }
-// The one-lane-per-leg physics (lg_physics.h) stays selectable for A/B runs and for the equivalence test of the two lane maps:
-// LG_PHYS_PAIR=0 in the environment, or lg_debug_set_phys_pair() at run time.  Default: the pair-lane map.
-static int g_phys_pair = -1;
-extern "C" void lgk_debug_set_phys_pair(int v) { g_phys_pair = v ? 1 : 0; }
-static int phys_pair_enabled() {
-    if (g_phys_pair < 0) { const char *e = getenv("LG_PHYS_PAIR"); g_phys_pair = e ? (atoi(e) ? 1 : 0) : 1; }
-    return g_phys_pair;
-}
-// LG_SUBSTEPS_NW (pair-lane physics only): 4 = blocks of 4 waves and 64/L envs, 2 = blocks of 2 waves and 32/L envs; 0 / unset = by
+// LG_SUBSTEPS_NW: 4 = blocks of 4 waves and 64/L envs, 2 = blocks of 2 waves and 32/L envs; 0 / unset = by
 // topology.  Measured per lg_step: quadruped 117.2 (4) vs 122.4 us (2: two blocks share a CU and its LDS / instruction cache for
 // nothing, the chain per wave is the same); biped 148.7 (4: 128 blocks, half the CUs idle) vs 145.5 us (2: 256 blocks).  Results are
 // bit-identical either way (tests/test_hip_env.py::test_control_loop_block_shapes_are_bit_identical).
@@ -1126,18 +1111,17 @@ static void launch_substeps(int N, const DevParams *P, const float *a_in, int mo
     if (g_substeps_nw < 0) { const char *e = getenv("LG_SUBSTEPS_NW"); g_substeps_nw = e ? (atoi(e) == 2 ? 2 : atoi(e) == 4 ? 4 : 0) : 0; }
     const int epw4 = 64 / L, epw2 = 32 / L;
     const int nw = g_substeps_nw ? g_substeps_nw : (L == 2 ? 2 : 4);
-    if (phys_pair_enabled() && nw == 2)
-        hipLaunchKernelGGL((k_substeps<L, J, LSTM, true, 2>), dim3((N + epw2 - 1) / epw2), dim3(128), 0, s, P, a_in, mode, iters);
-    else if (phys_pair_enabled()) {
-        static int cus = 0;
-        if (!cus) { int dev = 0; hipDeviceProp_t pr; cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
-        const int grid = (N + epw4 - 1) / epw4;
-        if (L == 4 && (g_substeps_occ ? g_substeps_occ == 2 : grid > cus))   // more workgroups than CUs: the 256-register build, two per CU (bit-identical results)
-            hipLaunchKernelGGL((k_substeps<L, J, LSTM, true, 4, (L == 4 ? 2 : 1)>), dim3(grid), dim3(256), 0, s, P, a_in, mode, iters);
-        else
-            hipLaunchKernelGGL((k_substeps<L, J, LSTM, true>), dim3(grid), dim3(256), 0, s, P, a_in, mode, iters);
+    if (nw == 2) {
+        hipLaunchKernelGGL((k_substeps<L, J, LSTM, 2>), dim3((N + epw2 - 1) / epw2), dim3(128), 0, s, P, a_in, mode, iters);
+        return;
     }
-    else hipLaunchKernelGGL((k_substeps<L, J, LSTM, false>), dim3((N + epw4 - 1) / epw4), dim3(256), 0, s, P, a_in, mode, iters);
+    static int cus = 0;
+    if (!cus) { int dev = 0; hipDeviceProp_t pr; cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
+    const int grid = (N + epw4 - 1) / epw4;
+    if (L == 4 && (g_substeps_occ ? g_substeps_occ == 2 : grid > cus))   // more workgroups than CUs: the 256-register build, two per CU (bit-identical results)
+        hipLaunchKernelGGL((k_substeps<L, J, LSTM, 4, (L == 4 ? 2 : 1)>), dim3(grid), dim3(256), 0, s, P, a_in, mode, iters);
+    else
+        hipLaunchKernelGGL((k_substeps<L, J, LSTM>), dim3(grid), dim3(256), 0, s, P, a_in, mode, iters);
 }
 extern "C" int lgk_substeps(const DevParams *P, const float *a_in, int N, int L, int J, int lstm, int mode, int iters, hipStream_t s) {
     if (L == 4 && J == 3 && lstm) launch_substeps<4, 3, true>(N, P, a_in, mode, iters, s);

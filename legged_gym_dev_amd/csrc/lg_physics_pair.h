@@ -1,9 +1,9 @@
-// Pair-lane articulated-body physics for gfx950: TWO lanes per (environment, leg).
+// Articulated-body physics for gfx950, two lanes per (environment, leg): the solver of the control loop (k_substeps in
+// env_kernels.hip).  The algorithm is the one lg_physics.h states, and oracle/lgo_physics.cpp restates it scalar.
 //
-// Same algorithm, same LDS records and same results (up to fp32 summation order) as physics_lane in lg_physics.h; the
-// difference is the lane map.  The control loop lasts as long as the dependent instruction chain of the wave that runs the
+// The control loop lasts as long as the dependent instruction chain of the wave that runs the
 // physics (it fills about half of its VALU issue slots: profiles/r03_substeps_pmc.json, r03_substeps_clock.json), and most of
-// that chain is 6-vector / 6x6 arithmetic.  Here the two lanes of a
+// that chain is 6-vector / 6x6 arithmetic.  So the two lanes of a
 // pair split every spatial quantity by rows: lane h = 0 holds the angular half (w rows), lane h = 1 the linear half
 // (v rows) of every spatial vector, and the matching three rows of every 6x6 matrix, stored as two 3x3 blocks relative to
 // the lane's own role:  mm multiplies the lane's own half of an operand, mo the partner's half.  With that convention a
@@ -364,8 +364,8 @@ __device__ __forceinline__ int physics_pair(const PhysCfg &c /* phys_cfg(P): reg
         // W = G^T Phi G (G = the three unit impulses at the contact, Phi = the chain's response at the link) from the INWARD pass alone:
         // with the innovations u_a[k] = -S_k . p_a,k and the force p_a,0 that reaches the base, the articulated-body factorisation
         // M^-1 = (I - H psi K)^T D^-1 (I - H psi K) gives  W_ab = sum_k u_a[k] u_b[k] / D_k + p_a,0 . I0^-1 p_b,0  -- no outward pass, no
-        // point-velocity reconstruction (a third fewer instructions than propagating each impulse out again; the one-lane map and the
-        // oracle keep the literal form, and the parity tests compare the two).  Joints outside the contact's chain (k > jl) drop out
+        // point-velocity reconstruction (a third fewer instructions than propagating each impulse out again; the oracle keeps the
+        // literal form, and the parity tests compare the two).  Joints outside the contact's chain (k > jl) drop out
         // through a zero factor, not a branch: as `if (k <= jl) { ... }` the three impulses compiled into 31 basic blocks (exec-mask
         // regions) that the scheduler could not interleave.
         float Wc[3][3], uu[3][J];

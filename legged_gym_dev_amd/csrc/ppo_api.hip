@@ -21,7 +21,6 @@ int64_t ppok_mlp_frag_elems(int K, int N);
 void ppok_mlp_frag_build(const MlpArgs *g, hipStream_t s);
 void ppok_gemm_dw(const GemmArgs *g, int nz, int splits, hipStream_t s);
 void ppok_debug_set_xcd_remap(int v);
-void ppok_debug_set_dw_t(int v);
 void ppok_act_sample(const PpoDev *P, const float *obs, const float *cobs, const float *mu, const float *val, int t,
                      int64_t cnt, int inject, hipStream_t s);
 void ppok_process_step(const PpoDev *P, const float *rew, const uint8_t *dones, const uint8_t *tos, int t, hipStream_t s);
@@ -114,10 +113,10 @@ struct lg_ppo {
     std::vector<void *> allocs;
     int64_t perm_count;                      // updates begun: keys the device-side minibatch permutation
     // minibatch gathers are double-buffered: the optimiser step of minibatch mb gathers mb + 1 into the other set in the spare
-    // workgroups of its norm-reduction launch (the gather depends on the rollout storage and the permutation only)
+    // workgroups of its norm-reduction launch (the gather depends on the rollout storage and the permutation only).  A gather launch
+    // of its own before each minibatch: 0.474 / 0.485 ms per minibatch against 0.465 / 0.469, within that bench's noise (profiles/r02_ab.txt)
     struct MbSet { float *obs, *critic_obs, *actions, *mu, *scalars; } mbset[2];
     int mb_cur, mb_ready, mb_last;           // set the kernels read now; minibatch held by the other set (-1: none); last backward
-    int gather_ahead;
     lg_ppo_buffers pub;
     Rnn rnn;
 };
@@ -230,7 +229,7 @@ static void backward(lg_ppo *p, int M, const float *in0, const float *in1, int s
         // (splits x output floats) stay well below the MFMA time
         // workgroups per net over (output tiles x reduction splits); swept 64..384 inside the update (side stream beside the
         // input-gradient chain): 0.637 / 0.585 / 0.597 / 0.574 / 0.560 ms per minibatch at 64 / 128 / 192 / 256 / 384
-        static const int dw_target = getenv("LG_DW_WGS") ? atoi(getenv("LG_DW_WGS")) : 384;
+        constexpr int dw_target = 384;
         int splits = (int)((dw_target + tiles - 1) / tiles);
         int max_splits = M / 256 > 0 ? M / 256 : 1;
         if (splits > max_splits) splits = max_splits;
@@ -238,8 +237,8 @@ static void backward(lg_ppo *p, int M, const float *in0, const float *in1, int s
         if (splits < 1) splits = 1;
         // the weight gradient of layer l runs beside the input-gradient chain on the side stream -- except the last one
         // (l = 0), which has nothing left to overlap with: on the main stream it starts without the cross-stream event wait
-        static const int dw0_main = getenv("LG_DW0_MAIN") ? atoi(getenv("LG_DW0_MAIN")) : 1;
-        const bool on_side = p->overlap && (l > 0 || !dw0_main);
+        // (on the side stream: 0.479 / 0.490 ms per minibatch against 0.465 / 0.469, within that bench's noise: profiles/r02_ab.txt)
+        const bool on_side = p->overlap && l > 0;
         hipStream_t dw_stream = on_side ? p->side : p->stream;
         if (on_side) {                               // dz[l+1] is complete on the main stream at this point
             (void)hipEventRecord(p->ev_dz, p->stream);
@@ -500,7 +499,6 @@ static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **
     p->comm = nullptr; p->comm_rc = 0; p->comm_timing = 0; p->comm_ev_used = 0;
     p->env = nullptr; p->pp_pending = 0;
     if (getenv("LG_XCD_REMAP")) ppok_debug_set_xcd_remap(atoi(getenv("LG_XCD_REMAP")));
-    if (getenv("LG_DW_T")) ppok_debug_set_dw_t(atoi(getenv("LG_DW_T")));
     p->perm_count = 0;
     const int R = (int)((long)N * T / cfg->num_mini_batches);
     p->Mmax = R > N ? R : N;
@@ -590,7 +588,6 @@ static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **
         PA(m.actions, (size_t)R * A); PA(m.mu, (size_t)R * A); PA(m.scalars, (size_t)R * 4);
     }
     p->mb_cur = 0; p->mb_ready = -1; p->mb_last = -1;
-    p->gather_ahead = getenv("LG_GATHER_AHEAD") ? atoi(getenv("LG_GATHER_AHEAD")) : 1;
     d.mb_obs = p->mbset[0].obs; d.mb_critic_obs = p->mbset[0].critic_obs; d.mb_actions = p->mbset[0].actions;
     d.mb_mu = p->mbset[0].mu; d.mb_scalars = p->mbset[0].scalars;
     PA(d.head_part, ppok_head_part_floats());
@@ -737,12 +734,12 @@ int lg_ppo_act(lg_ppo *p, const float *obs, const float *critic_obs) {
         g.in[0] = obs; g.in[1] = cobs;
         g.out[0] = p->net[0].act[p->net[0].nl]; g.out[1] = p->net[1].act[p->net[1].nl];
         if (dirty) ppok_mlp_frag_build(&g, p->stream);
-        static const int fuse_sample = getenv("LG_FUSED_SAMPLE") ? atoi(getenv("LG_FUSED_SAMPLE")) : 1;
-        g.sample = fuse_sample; g.t = p->step; g.inject = p->inject; g.act_count = p->act_count;
+        // sampled and stored by the same launch (a separate k_act_sample: rollout 4.40 / 4.41 ms against 4.15 / 4.19, profiles/r02_ab.txt)
+        g.sample = 1; g.t = p->step; g.inject = p->inject; g.act_count = p->act_count;
         g.pp = 0;
         const int N = p->cfg.num_envs;
         const bool fits = (N + 255) / 256 + 1 <= (N + 31) / 32;  // epilogue workgroups within the launch's grid.x
-        if (p->env && p->pp_pending && g.sample && fits) {        // the previous step's epilogue rides on this launch
+        if (p->env && p->pp_pending && fits) {        // the previous step's epilogue rides on this launch
             g.pp = lg_internal_finalize_pending(p->env) ? 2 : 1;
             g.pp_t = p->pp_t; g.pp_use_tos = p->pp_use_tos;
             g.pp_env = lg_internal_take_finalize(p->env, &g.pp_counter);
@@ -750,7 +747,7 @@ int lg_ppo_act(lg_ppo *p, const float *obs, const float *critic_obs) {
         } else flush_rollout_epilogue(p);
         fused = ppok_mlp_fwd(&g, &p->dev, 3, p->stream);
         if (fused != 0 && g.pp) { lg_set_error("fused act launch refused with a rollout epilogue attached"); return -13; }
-        if (fused == 0 && g.sample) {                                             // sampled and stored by the same launch
+        if (fused == 0) {                                                         // sampled and stored by the same launch
             p->act_count++;
             const int rc = launch_ok();
             if (rc == 0) p->params_dirty = 0;
@@ -760,15 +757,14 @@ int lg_ppo_act(lg_ppo *p, const float *obs, const float *critic_obs) {
     if (!p->fused_act) flush_rollout_epilogue(p);
     if (fused != 0) {
         // per-layer GEMMs on the optimiser's weight planes (no re-split of W per tile); same freshness rule as above
-        static const int act_planes = getenv("LG_ACT_PLANES") ? atoi(getenv("LG_ACT_PLANES")) : 1;
-        if (act_planes && dirty) ppok_sync_planes(&p->dev, p->stream);
+        if (dirty) ppok_sync_planes(&p->dev, p->stream);
         const float *in0 = obs, *in1 = cobs;
         if (p->rnn.H) {                          // the transition keeps the state before the step; both memories advance
             rnn_stash_live(p, 3, p->step);
             rnn_live_step(p, 3, obs, cobs, p->step);
             in0 = p->rnn.h[0]; in1 = p->rnn.h[1];
         }
-        forward(p, p->cfg.num_envs, in0, in1, 3, 0, act_planes != 0);
+        forward(p, p->cfg.num_envs, in0, in1, 3, 0, true);
     }
     ppok_act_sample(&p->dev, obs, cobs, p->net[0].act[p->net[0].nl], p->net[1].act[p->net[1].nl], p->step, p->act_count,
                     p->inject, p->stream);
@@ -860,8 +856,7 @@ int lg_ppo_minibatch_backward(lg_ppo *p, int epoch, int mb) {
     // supported width; otherwise head GEMMs + k_loss
     // at 128 wide the fused head was 18 us slower per minibatch while the weight-gradient stream had slack; with that stream the
     // long pole (profiles/r02_timelines.txt) it is 9 us faster than head GEMM + k_loss + two head-gradient GEMMs (A/B on one box)
-    static const int fuse128 = getenv("LG_HEAD_FUSE128") ? atoi(getenv("LG_HEAD_FUSE128")) : 1;
-    const bool fuse = p->act_code == 1 && nl >= 2 && nc.dims[nl - 1] == H3 && (H3 == 64 || H3 == 32 || (H3 == 128 && fuse128));
+    const bool fuse = p->act_code == 1 && nl >= 2 && nc.dims[nl - 1] == H3 && (H3 == 128 || H3 == 64 || H3 == 32);
     if (p->rnn.H) {
         rnn_forward_seq(p, mb);
         forward(p, R, p->rnn.hout[0], p->rnn.hout[1], 3, fuse ? 1 : 0, true, false);
@@ -887,7 +882,7 @@ int lg_ppo_minibatch_backward(lg_ppo *p, int epoch, int mb) {
 int lg_ppo_minibatch_step(lg_ppo *p) {
     int next = -1;
     PpoDev other = p->dev;
-    if (p->gather_ahead && p->cfg.num_mini_batches > 1 && p->mb_last >= 0) {
+    if (p->cfg.num_mini_batches > 1 && p->mb_last >= 0) {
         // the next minibatch of the generator's order (the permutation is fixed for the whole update)
         next = (p->mb_last + 1) % p->cfg.num_mini_batches;
         const lg_ppo::MbSet &m = p->mbset[p->mb_cur ^ 1];

@@ -220,24 +220,11 @@ __device__ __forceinline__ void gemm_mainloop(const float *__restrict__ A, const
 // four different bank phases while fragment reads (32 consecutive rows) stay conflict-free.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define X6_ROWB 80
-#ifndef LG_GEMM_STEADY              // compile-time A/B: 1 = steady-state loop with unconditional prefetch (forward / input gradient)
-#define LG_GEMM_STEADY 0
-#endif
-#ifndef LG_DW_STEADY                // the same for the weight-gradient kernel
-#define LG_DW_STEADY 0
-#endif
 // Workgroup barrier of the GEMM mainloops: LDS traffic only.  __syncthreads() carries workgroup-scope fences, for which hipcc drains
 // EVERY outstanding memory operation (s_waitcnt vmcnt(0)) -- including the global loads issued two k-tiles ahead, whose latency
 // the prefetch distance exists to hide.  The mainloops exchange data through LDS alone: waiting for this wave's LDS operations
 // and the barrier is all the ordering they need; the loaded registers are waited for where they are used (counted vmcnt).
-// LG_GEMM_FULL_BARRIER (compile-time, A/B) restores __syncthreads().
-__device__ __forceinline__ void lds_barrier() {
-#ifdef LG_GEMM_FULL_BARRIER
-    __syncthreads();
-#else
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-}
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
     uint32_t r;
@@ -246,10 +233,6 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
 }
 // (x0, x1) -> packed bf16 pairs of the three split terms
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t &h, uint32_t &m, uint32_t &l) {
-#ifdef LG_EXP_NOSPLIT                                              // timing experiment only (make exp): what the split arithmetic costs
-    h = __float_as_uint(x0); m = __float_as_uint(x1); l = h ^ m;
-    return;
-#endif
     typedef float f32x2 __attribute__((ext_vector_type(2)));      // v_pk_add_f32: both remainders in one instruction
     h = cvt_pk_bf16(x0, x1);
     f32x2 r = f32x2{x0, x1} - f32x2{__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};
@@ -353,20 +336,18 @@ __device__ __forceinline__ void stage_store_pl(unsigned char *__restrict__ lds, 
 // chunk XOR of cdna_hip_programming.md T10 image (a): off(row, ch) = GRP (row>>3) + 512 (ch>>2) + 64 (row&7) +
 // 16 ((ch&3) ^ ((row>>2)&3)), ch = 16-byte chunk of the row, GRP = 512 BN/32 -- conflict-free for both the b128 stores'
 // rows and the transposed reads.
-// Subtile stride PLT_SUB = 512 + 64 bytes (LG_PLT_SUB): with subtiles exactly 512 B apart the 4 (stores of 16 B: 16 lanes, stores of 8 B: 32
+// Subtile stride PLT_SUB = 512 + 64 bytes: with subtiles exactly 512 B apart the 4 (stores of 16 B: 16 lanes, stores of 8 B: 32
 // lanes) subtiles one k-row spans fall on the SAME 16 banks -- a 4-way conflict on every staging store (SQ_LDS_BANK_CONFLICT = 17 % of the LDS
 // cycles of the input-gradient kernel, 29-33 % of the weight-gradient kernels': profiles/r03_kernel_clocks.txt).  The 64-byte pad rotates
 // them onto the four quarters of the bank row; a transposed read stays inside one subtile and is unaffected.
-#ifndef LG_PLT_SUB
-#define LG_PLT_SUB 576
-#endif
+constexpr int PLT_SUB = 576;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 template <int BN>
 __device__ __forceinline__ int plt_off(int row, int ch) {
-    return (BN / 32 * LG_PLT_SUB) * (row >> 3) + LG_PLT_SUB * (ch >> 2) + 64 * (row & 7) + 16 * ((ch & 3) ^ ((row >> 2) & 3));
+    return (BN / 32 * PLT_SUB) * (row >> 3) + PLT_SUB * (ch >> 2) + 64 * (row & 7) + 16 * ((ch & 3) ^ ((row >> 2) & 3));
 }
 template <int BN>
-constexpr int plt_plane_bytes() { return BK / 8 * (BN / 32) * LG_PLT_SUB; }
+constexpr int plt_plane_bytes() { return BK / 8 * (BN / 32) * PLT_SUB; }
 
 template <int BN, int NT>
 __device__ __forceinline__ void stage_load_plt(const uint16_t *__restrict__ src, int64_t pl_stride, int ld, int n0, int red0, int ncols,
@@ -399,7 +380,7 @@ __device__ __forceinline__ s16x4 lds_read_tr16(const unsigned char *p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)p);
 }
 
-template <bool A_RC, bool B_RC, int TM, int TN, int WGM, int WGN, bool VEC, bool FULL = false, int B_PL = 0, bool LDB = false>
+template <bool A_RC, bool B_RC, int TM, int TN, int WGM, int WGN, bool VEC, bool FULL = false, int B_PL = 0>
 __device__ __forceinline__ void gemm_mainloop_x6(const float *__restrict__ A, const float *__restrict__ B, int lda, int ldb, int m0, int n0,
                                                  int M, int N, int k_begin, int k_end, unsigned char *__restrict__ lds, int wm, int wn, int li,
                                                  int lk, f32x16 (&acc)[TM][TN], const uint16_t *__restrict__ Bpl = nullptr,
@@ -409,43 +390,31 @@ __device__ __forceinline__ void gemm_mainloop_x6(const float *__restrict__ A, co
     constexpr int NVA = BM * BK / 4 / NT, NVB = BN * BK / 4 / NT;
     // two register sets: the global loads of k-tile t+2 are issued before the MFMAs of tile t, and tile t+1 (already
     // landed) is split and stored after them -- one full iteration to cover the L2/HBM latency.
-    // LDB: two LDS stages -- the split + store of tile t+1 goes to the other stage with no barrier before it and can overlap
-    // the MFMAs of tile t (one barrier per k-tile instead of two).  Built for the 64x64 configuration; measured NEUTRAL there
-    // (12.5 vs 13.1 us per rollout GEMM; tools/kernel_avg.sh), as was a prefetch distance of 4: those launches are bound by
+    // Measured and not kept: two LDS stages (the split + store of tile t+1 to the other stage, overlapping the MFMAs of tile t), NEUTRAL
+    // for the 64x64 configuration (12.5 vs 13.1 us per rollout GEMM), as was a prefetch distance of 4: those launches are bound by
     // their fixed cost (~7 us for a K = 48 or K = 128 layer) and were replaced by the one-launch forward of ppo_mlp_fused.hip.
-    // Kept selectable (LG_GEMM_LDB) for shapes the fused forward does not cover; off by default.
     constexpr int PD = 2;
     constexpr int NVP = B_PL ? BN * 12 / NT : 1;                 // 16-byte chunks of a plane k-tile per thread (either plane layout)
     struct Regs { float4 a[NVA], b[NVB]; uint4 p[NVP]; unsigned ma = 0, mb = 0; };
     Regs R[PD];
     unsigned char *lds_b = lds + 3 * APL;
     auto load_tile = [&](Regs &r, int k) {
-#ifdef LG_EXP_A_SAME_TILE           // timing experiment only (make exp): every k-tile re-reads the first A tile (cache hits instead of HBM)
-        stage_load<A_RC, BM, VEC, true, NT, FULL>(A, lda, m0, k_begin, M, k_end, r.a, r.ma);
-#else
         stage_load<A_RC, BM, VEC, true, NT, FULL>(A, lda, m0, k, M, k_end, r.a, r.ma);
-#endif
-#ifdef LG_EXP_B_SAME_TILE           // timing experiment only: the same for the weight-plane tile
-        if constexpr (B_PL == 2) stage_load_plt<BN, NT>(Bpl, pl_stride, ldb, n0, k_begin, N, k_end, r.p, r.mb);
-        else if constexpr (B_PL == 1) stage_load_pl<BN, NT>(Bpl, pl_stride, ldb, n0, k_begin, N, k_end, r.p, r.mb);
-#else
         if constexpr (B_PL == 2) stage_load_plt<BN, NT>(Bpl, pl_stride, ldb, n0, k, N, k_end, r.p, r.mb);
         else if constexpr (B_PL == 1) stage_load_pl<BN, NT>(Bpl, pl_stride, ldb, n0, k, N, k_end, r.p, r.mb);
-#endif
         else stage_load<B_RC, BN, VEC, true, NT, FULL>(B, ldb, n0, k, N, k_end, r.b, r.mb);
     };
-    constexpr int STAGE = 3 * APL + 3 * BPL;                     // bytes of one LDS stage
-    auto store_tile = [&](Regs &r, int st) {
-        stage_store_x6<A_RC, BM, NT, FULL>(lds + st * STAGE, r.a, r.ma);
-        if constexpr (B_PL == 2) stage_store_plt<BN, NT>(lds_b + st * STAGE, r.p, r.mb);
-        else if constexpr (B_PL == 1) stage_store_pl<BN, NT>(lds_b + st * STAGE, r.p, r.mb);
-        else stage_store_x6<B_RC, BN, NT, FULL>(lds_b + st * STAGE, r.b, r.mb);
+    auto store_tile = [&](Regs &r) {
+        stage_store_x6<A_RC, BM, NT, FULL>(lds, r.a, r.ma);
+        if constexpr (B_PL == 2) stage_store_plt<BN, NT>(lds_b, r.p, r.mb);
+        else if constexpr (B_PL == 1) stage_store_pl<BN, NT>(lds_b, r.p, r.mb);
+        else stage_store_x6<B_RC, BN, NT, FULL>(lds_b, r.b, r.mb);
     };
     load_tile(R[0], k_begin);
 #pragma unroll
     for (int d = 1; d < PD; ++d)
         if (k_begin + d * BK < k_end) load_tile(R[d], k_begin + d * BK);
-    store_tile(R[0], 0);
+    store_tile(R[0]);
     lds_barrier();
     // fragment of tile a, plane p, k-step s: base + a*8*X6_ROWB (32 logical rows = 8 physical) + p*PL + s*32
     const unsigned char *fa = lds + x6_prow<BM>(wm + li) * X6_ROWB + 16 * lk;
@@ -456,42 +425,36 @@ __device__ __forceinline__ void gemm_mainloop_x6(const float *__restrict__ A, co
     const unsigned char *ft[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h)
-        ft[h] = lds_b + (BN / 32 * LG_PLT_SUB) * (tg >> 1) + LG_PLT_SUB * (wn / 32) + 64 * (4 * h + tq) +
+        ft[h] = lds_b + (BN / 32 * PLT_SUB) * (tg >> 1) + PLT_SUB * (wn / 32) + 64 * (4 * h + tq) +
                 16 * ((2 * (tg & 1) + (tp >> 1)) ^ (2 * (tg >> 1) + h)) + 8 * (tp & 1);
-    auto read_b = [&](int b, int p, int s, int so) -> bf16x8 {
+    auto read_b = [&](int b, int p, int s) -> bf16x8 {
         if constexpr (B_PL == 2) {
-            const int o = so + LG_PLT_SUB * b + p * BPL + (BN / 32 * LG_PLT_SUB) * 2 * s;
+            const int o = PLT_SUB * b + p * BPL + (BN / 32 * PLT_SUB) * 2 * s;
             const s16x4 lo = lds_read_tr16(ft[0] + o), hi = lds_read_tr16(ft[1] + o);
             typedef short s16x8 __attribute__((ext_vector_type(8)));
             const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             return __builtin_bit_cast(bf16x8, v);
         } else {
-            return *reinterpret_cast<const bf16x8 *>(fb + so + b * 8 * X6_ROWB + p * BPL + s * 32);
+            return *reinterpret_cast<const bf16x8 *>(fb + b * 8 * X6_ROWB + p * BPL + s * 32);
         }
     };
 
     // one k-tile: x = the set holding tile k0 + BK (stored to LDS after the MFMAs), y = the set tile k0 + PD BK is loaded into.
-    // steady = std::true_type: both exist (the caller checked), so the loads and the store are UNCONDITIONAL.  hipcc counts
-    // s_waitcnt vmcnt per path and takes the minimum where paths join: with the prefetch under `if (k0 + PD BK < k_end)` the
-    // store of tile k0 + BK -- whose loads are a whole iteration old -- waited as if the prefetch had not been issued, i.e. until the
-    // loads issued a few hundred cycles earlier had landed (vmcnt(3)..(0) instead of (8)..(5) in the ISA): every k-tile exposed a
-    // memory round trip behind its MFMA block.  The steady-state loop below has no such join; the last 2 PD - 1 tiles run the guarded form.
-    auto body = [&](auto steady, int k0, Regs &x, Regs &y, int st) {
-        constexpr bool ST = decltype(steady)::value;
-        const int so = LDB ? st * STAGE : 0;                     // stage the MFMAs of this k-tile read
-        if (ST || k0 + PD * BK < k_end) load_tile(y, k0 + PD * BK);
-        if constexpr (LDB) {
-            if (ST || k0 + BK < k_end) store_tile(x, st ^ 1);
-        }
+    // Measured and not kept: a steady-state loop with the prefetch and the store unconditional.  hipcc counts s_waitcnt vmcnt per
+    // path and takes the minimum where paths join, so behind the guarded prefetch the store of tile k0 + BK waits for loads issued a
+    // few hundred cycles earlier (vmcnt(3)..(0) instead of (8)..(5) in the ISA); without the join it does not, and measures the same
+    // (profiles/r03_ab.txt: the other resident workgroup covers the wait).
+    auto body = [&](int k0, Regs &x, Regs &y) {
+        if (k0 + PD * BK < k_end) load_tile(y, k0 + PD * BK);
         bf16x8 av[2][TM][3], bv[2][TN][3];
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) av[0][a][p] = *reinterpret_cast<const bf16x8 *>(fa + so + a * 8 * X6_ROWB + p * APL);
+            for (int p = 0; p < 3; ++p) av[0][a][p] = *reinterpret_cast<const bf16x8 *>(fa + a * 8 * X6_ROWB + p * APL);
 #pragma unroll
         for (int b = 0; b < TN; ++b)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) bv[0][b][p] = read_b(b, p, 0, so);
+            for (int p = 0; p < 3; ++p) bv[0][b][p] = read_b(b, p, 0);
 #pragma unroll
         for (int s = 0; s < BK / 16; ++s) {
             if (s + 1 < BK / 16) {
@@ -499,12 +462,12 @@ __device__ __forceinline__ void gemm_mainloop_x6(const float *__restrict__ A, co
                 for (int a = 0; a < TM; ++a)
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
-                        av[(s + 1) & 1][a][p] = *reinterpret_cast<const bf16x8 *>(fa + so + a * 8 * X6_ROWB + p * APL + (s + 1) * 32);
+                        av[(s + 1) & 1][a][p] = *reinterpret_cast<const bf16x8 *>(fa + a * 8 * X6_ROWB + p * APL + (s + 1) * 32);
 #pragma unroll
                 for (int b = 0; b < TN; ++b)
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
-                        bv[(s + 1) & 1][b][p] = read_b(b, p, s + 1, so);
+                        bv[(s + 1) & 1][b][p] = read_b(b, p, s + 1);
             }
 #pragma unroll
             for (int a = 0; a < TM; ++a)
@@ -512,33 +475,23 @@ __device__ __forceinline__ void gemm_mainloop_x6(const float *__restrict__ A, co
                 for (int b = 0; b < TN; ++b) {
                     const bf16x8 *x = av[s & 1][a], *y = bv[s & 1][b];
                     f32x16 c = acc[a][b];                 // smallest terms first
-#ifndef LG_EXP_THREE_PRODUCTS        // timing experiment only (make exp): what a three-product scheme (two-term fp16 split) would execute
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], y[1], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[2], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[2], y[0], c, 0, 0, 0);
-#endif
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[1], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], y[0], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[0], c, 0, 0, 0);
                     acc[a][b] = c;
                 }
         }
-        if constexpr (!LDB) {
-            lds_barrier();                     // every wave is done reading before the tile is refilled
-            if (ST || k0 + BK < k_end) store_tile(x, 0);
-        }
+        lds_barrier();                         // every wave is done reading before the tile is refilled
+        if (k0 + BK < k_end) store_tile(x);
         lds_barrier();
     };
-    int k0 = k_begin;
-    if (LG_GEMM_STEADY)
-        for (; k0 + (2 * PD - 1) * BK < k_end; k0 += PD * BK) {      // every tile of the group has its successor and its prefetch target
-#pragma unroll
-            for (int d = 0; d < PD; ++d) body(std::true_type{}, k0 + d * BK, R[(d + 1) % PD], R[d], d & 1);
-        }
-    for (; k0 < k_end; k0 += PD * BK) {
+    for (int k0 = k_begin; k0 < k_end; k0 += PD * BK) {
 #pragma unroll
         for (int d = 0; d < PD; ++d)
-            if (d == 0 || k0 + d * BK < k_end) body(std::false_type{}, k0 + d * BK, R[(d + 1) % PD], R[d], d & 1);
+            if (d == 0 || k0 + d * BK < k_end) body(k0 + d * BK, R[(d + 1) % PD], R[d]);
     }
 }
 
@@ -580,13 +533,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, int z, int M, i
                         *cp = v;
                         csum += v;
                     } else {
-#ifdef LG_EXP_NO_DW_ATOMICS                                           // timing experiment only (make exp): what the split-K atomics cost
-                        asm volatile("" :: "v"(v), "v"(cp));
-#elif defined(LG_EXP_DW_PLAIN_STORE)                                  // timing experiment only: plain stores of the same bytes
-                        *cp = v;
-#else
                         acc_add(g, cp, v);
-#endif
                     }
                 }
             }
@@ -630,18 +577,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, int z, int M, i
     }
 }
 
-#ifdef LG_EXP_GEMM_CLOCK             // diagnostic build only (make exp): in-kernel clock of the GEMM workgroups, s_memtime / s_memrealtime
-__device__ unsigned long long g_gemm_clk[2 * 2048];
-extern "C" void ppok_debug_read_gemm_clock(unsigned long long *host) { (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_clk), sizeof(g_gemm_clk)); }
-#endif
-template <bool A_RC, bool B_RC, int EPI, int TM, int TN, bool DBUF, bool X6 = false, int WGM = 2, int WGN = 2, int B_PL = 0, bool LDB = false>
+template <bool A_RC, bool B_RC, int EPI, int TM, int TN, bool DBUF, bool X6 = false, int WGM = 2, int WGN = 2, int B_PL = 0>
 __global__ void __launch_bounds__(64 * WGM * WGN, X6 ? (WGM * WGN == 8 ? 4 : 2) : 1) k_gemm(GemmArgs g) {
-#ifdef LG_EXP_GEMM_CLOCK
-    const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-    struct ClkEnd { unsigned long long t0, r0; __device__ ~ClkEnd() {
-        const unsigned b = blockIdx.x + gridDim.x * blockIdx.z;
-        if (threadIdx.x == 0 && b < 2048) { g_gemm_clk[2 * b] = __builtin_amdgcn_s_memtime() - t0; g_gemm_clk[2 * b + 1] = __builtin_amdgcn_s_memrealtime() - r0; } } } clk_end{clk_t0, clk_r0};
-#endif
     static_assert(B_PL == 0 || (X6 && (B_PL == 1) == B_RC), "weight planes feed the split-bf16 mainloop: [n][k] planes as the reduction-"
                   "contiguous operand (1), the same planes read along their rows through the transposing LDS read (2)");
     constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN;       // WGM x WGN waves, each TM x TN tiles of 32x32
@@ -670,8 +607,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, X6 ? (WGM * WGN == 8 ? 4 : 2) 
     const bool b_vec = (ldb & 3) == 0 && ((uintptr_t)B & 15) == 0 && (((B_RC ? k_end : N) & 3) == 0) && (B_RC ? k_end : N) >= 4;
 
     constexpr int AF = tile_floats<A_RC, BM>(), BF = tile_floats<B_RC, BN>();
-    static_assert(!LDB || B_PL, "two LDS stages: weight-plane mainloops only");
-    constexpr int LDS_BYTES = X6 ? (LDB ? 2 : 1) * 3 * (x6_plane_bytes<BM>() + (B_PL == 2 ? plt_plane_bytes<BN>() : x6_plane_bytes<BN>()))
+    constexpr int LDS_BYTES = X6 ? 3 * (x6_plane_bytes<BM>() + (B_PL == 2 ? plt_plane_bytes<BN>() : x6_plane_bytes<BN>()))
                                  : (DBUF ? 2 : 1) * (AF + BF) * 4;
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
     float *lds = reinterpret_cast<float *>(lds_raw);
@@ -693,9 +629,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN, X6 ? (WGM * WGN == 8 ? 4 : 2) 
         const bool full = a_vec && b_vec && m0 + BM <= M && n0 + BN <= N && ((k_end - k_begin) % BK) == 0;
         if (B_PL) {
             const bool fullp = a_vec && m0 + BM <= M && n0 + BN <= N && ((k_end - k_begin) % BK) == 0;
-            if (fullp) gemm_mainloop_x6<A_RC, B_RC, TM, TN, WGM, WGN, true, true, B_PL, LDB>(A, B, lda, ldb, m0, n0, M, N, k_begin, k_end, lds_raw, wm, wn, li, lk, acc, g.Bpl[z], g.pl_stride);
-            else if (a_vec) gemm_mainloop_x6<A_RC, B_RC, TM, TN, WGM, WGN, true, false, B_PL, LDB>(A, B, lda, ldb, m0, n0, M, N, k_begin, k_end, lds_raw, wm, wn, li, lk, acc, g.Bpl[z], g.pl_stride);
-            else gemm_mainloop_x6<A_RC, B_RC, TM, TN, WGM, WGN, false, false, B_PL, LDB>(A, B, lda, ldb, m0, n0, M, N, k_begin, k_end, lds_raw, wm, wn, li, lk, acc, g.Bpl[z], g.pl_stride);
+            if (fullp) gemm_mainloop_x6<A_RC, B_RC, TM, TN, WGM, WGN, true, true, B_PL>(A, B, lda, ldb, m0, n0, M, N, k_begin, k_end, lds_raw, wm, wn, li, lk, acc, g.Bpl[z], g.pl_stride);
+            else if (a_vec) gemm_mainloop_x6<A_RC, B_RC, TM, TN, WGM, WGN, true, false, B_PL>(A, B, lda, ldb, m0, n0, M, N, k_begin, k_end, lds_raw, wm, wn, li, lk, acc, g.Bpl[z], g.pl_stride);
+            else gemm_mainloop_x6<A_RC, B_RC, TM, TN, WGM, WGN, false, false, B_PL>(A, B, lda, ldb, m0, n0, M, N, k_begin, k_end, lds_raw, wm, wn, li, lk, acc, g.Bpl[z], g.pl_stride);
         } else
         if (full) gemm_mainloop_x6<A_RC, B_RC, TM, TN, WGM, WGN, true, true>(A, B, lda, ldb, m0, n0, M, N, k_begin, k_end, lds_raw, wm, wn, li, lk, acc);
         else if (a_vec && b_vec) gemm_mainloop_x6<A_RC, B_RC, TM, TN, WGM, WGN, true>(A, B, lda, ldb, m0, n0, M, N, k_begin, k_end, lds_raw, wm, wn, li, lk, acc);
@@ -776,8 +712,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 4 : 2) k_gemm
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int lane_off = 64 * (4 * h + tq) + 16 * ((2 * (tg & 1) + (tp >> 1)) ^ (2 * (tg >> 1) + h)) + 8 * (tp & 1);
-        fa[h] = lds + (BM / 32 * LG_PLT_SUB) * (tg >> 1) + LG_PLT_SUB * (wm / 32) + lane_off;
-        fb[h] = lds_b + (BN / 32 * LG_PLT_SUB) * (tg >> 1) + LG_PLT_SUB * (wn / 32) + lane_off;
+        fa[h] = lds + (BM / 32 * PLT_SUB) * (tg >> 1) + PLT_SUB * (wm / 32) + lane_off;
+        fb[h] = lds_b + (BN / 32 * PLT_SUB) * (tg >> 1) + PLT_SUB * (wn / 32) + lane_off;
     }
     auto frag = [&](const unsigned char *const (&f)[2], int o) -> bf16x8 {
         const s16x4 lo = lds_read_tr16(f[0] + o), hi = lds_read_tr16(f[1] + o);
@@ -788,9 +724,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 4 : 2) k_gemm
     const bool a_vec = (lda & 3) == 0 && ((uintptr_t)A & 15) == 0 && (M & 3) == 0 && M >= 4;
     const bool b_vec = (ldb & 3) == 0 && ((uintptr_t)B & 15) == 0 && (N & 3) == 0 && N >= 4;
     // The whole k-loop once per load form (16-byte loads for both operands, or the element-wise fallback): with the choice as a
-    // branch INSIDE the loop hipcc's s_waitcnt insertion lost track of the prefetched registers across the join -- in the
-    // steady-state loop below the split read a register set with no vmcnt wait at all (wrong sums), in the guarded form it
-    // waited for everything.
+    // branch INSIDE the loop hipcc's s_waitcnt insertion lost track of the prefetched registers across the join -- in a
+    // steady-state loop form (see gemm_mainloop_x6) the split read a register set with no vmcnt wait at all (wrong sums), in the
+    // guarded form it waited for everything.
     auto run = [&](auto vec) {
         constexpr bool VEC = decltype(vec)::value;
         float4 ra[PD][NVA], rb[PD][NVB];
@@ -808,22 +744,20 @@ __global__ void __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 4 : 2) k_gemm
         stage_store_x6t<BN, NT>(lds_b, rb[0], mb[0]);
         lds_barrier();
         // one k-tile (in LDS; its register set c is free): loads of tile + PD into set c, MFMAs, then the next tile (set n) to LDS
-        // steady: unconditional prefetch and store (see gemm_mainloop_x6: a guarded prefetch makes the store wait for it)
-        auto body = [&](auto steady, int k0, float4 (&ca)[NVA], float4 (&cb)[NVB], unsigned &cma, unsigned &cmb, float4 (&na)[NVA], float4 (&nb)[NVB],
+        auto body = [&](int k0, float4 (&ca)[NVA], float4 (&cb)[NVB], unsigned &cma, unsigned &cmb, float4 (&na)[NVA], float4 (&nb)[NVB],
                         unsigned &nma, unsigned &nmb) {
-            constexpr bool ST = decltype(steady)::value;
-            if (ST || k0 + PD * BK < k_end) load(k0 + PD * BK, ca, cb, cma, cmb);
+            if (k0 + PD * BK < k_end) load(k0 + PD * BK, ca, cb, cma, cmb);
     #pragma unroll
             for (int s = 0; s < BK / 16; ++s) {
                 bf16x8 av[TM][3], bv[TN][3];
     #pragma unroll
                 for (int a = 0; a < TM; ++a)
     #pragma unroll
-                    for (int p = 0; p < 3; ++p) av[a][p] = frag(fa, LG_PLT_SUB * a + p * APL + (BM / 32 * LG_PLT_SUB) * 2 * s);
+                    for (int p = 0; p < 3; ++p) av[a][p] = frag(fa, PLT_SUB * a + p * APL + (BM / 32 * PLT_SUB) * 2 * s);
     #pragma unroll
                 for (int b = 0; b < TN; ++b)
     #pragma unroll
-                    for (int p = 0; p < 3; ++p) bv[b][p] = frag(fb, LG_PLT_SUB * b + p * BPL + (BN / 32 * LG_PLT_SUB) * 2 * s);
+                    for (int p = 0; p < 3; ++p) bv[b][p] = frag(fb, PLT_SUB * b + p * BPL + (BN / 32 * PLT_SUB) * 2 * s);
     #pragma unroll
                 for (int a = 0; a < TM; ++a)
     #pragma unroll
@@ -840,24 +774,17 @@ __global__ void __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 4 : 2) k_gemm
                     }
             }
             lds_barrier();
-            if (ST || k0 + BK < k_end) {
+            if (k0 + BK < k_end) {
                 stage_store_x6t<BM, NT>(lds, na, nma);
                 stage_store_x6t<BN, NT>(lds_b, nb, nmb);
             }
             lds_barrier();
         };
-        int k0 = k_begin;
-        if (LG_DW_STEADY)
-            for (; k0 + (2 * PD - 1) * BK < k_end; k0 += PD * BK) {
-    #pragma unroll
-                for (int d = 0; d < PD; ++d)
-                    body(std::true_type{}, k0 + d * BK, ra[d], rb[d], ma[d], mb[d], ra[(d + 1) % PD], rb[(d + 1) % PD], ma[(d + 1) % PD], mb[(d + 1) % PD]);
-            }
-        for (; k0 < k_end; k0 += PD * BK) {
+        for (int k0 = k_begin; k0 < k_end; k0 += PD * BK) {
     #pragma unroll
             for (int d = 0; d < PD; ++d)
                 if (d == 0 || k0 + d * BK < k_end)
-                    body(std::false_type{}, k0 + d * BK, ra[d], rb[d], ma[d], mb[d], ra[(d + 1) % PD], rb[(d + 1) % PD], ma[(d + 1) % PD], mb[(d + 1) % PD]);
+                    body(k0 + d * BK, ra[d], rb[d], ma[d], mb[d], ra[(d + 1) % PD], rb[(d + 1) % PD], ma[(d + 1) % PD], mb[(d + 1) % PD]);
         }
     };
     if (a_vec && b_vec) run(std::true_type{});
@@ -867,113 +794,63 @@ __global__ void __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 4 : 2) k_gemm
 }
 
 extern "C" void ppok_debug_set_xcd_remap(int v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_xcd_remap), &v, sizeof(int)); }
-static int g_gemm_dw_t = 1;    // weight gradients through k_gemm_dw_t (0: the transposing-store path of k_gemm, for A/B)
-extern "C" void ppok_debug_set_dw_t(int v) { g_gemm_dw_t = v; }
-
-static int g_gemm_dbuf = 0;   // single LDS buffer (34 KB, 4 workgroups/CU) measured 3-15 % faster than double buffering
-extern "C" void ppok_debug_set_dbuf(int v) { g_gemm_dbuf = v; }
-static int g_gemm_x6 = 1;     // split-bf16 mainloop (fp32 accuracy on the bf16 matrix cores); 0 = fp32-input MFMA
-static int g_gemm_w8 = 1;     // 128x128 tile on 8 waves (2x4, each 64x32) instead of 4 waves (2x2, each 64x64)
-extern "C" void ppok_debug_set_x6(int v) { g_gemm_x6 = v & 1; g_gemm_w8 = (v >> 1) & 1; }
-
-static int g_gemm_planes = 1;  // forward / input-gradient GEMMs take the weight operand from the optimiser's bf16 planes
-extern "C" void ppok_debug_set_planes(int v) { g_gemm_planes = v; }
-
-// forward (EPI 0) and input gradient (EPI 1) with B = pre-split weight planes, reduction-contiguous
-#ifdef LG_EXP_KERNELS
-static int g_gemm_t96 = 0;     // 96x128 tile where it fills the 512 workgroup slots in fuller rounds: measured slower end to end
-extern "C" void ppok_debug_set_t96(int v) { g_gemm_t96 = v; }
-#endif
+static int g_gemm_x6 = 1;     // split-bf16 mainloops (fp32 accuracy on the bf16 matrix cores); 0 = fp32-input MFMA, the reference of the tests
+extern "C" void ppok_debug_set_x6(int v) { g_gemm_x6 = v != 0; }
 
 #include "ppo_gemm_glds.h"
-#ifdef LG_EXP_KERNELS
-#include "exp/ppo_gemm_exp.h"
-#endif
 
+// forward (EPI 0) and input gradient (EPI 1) with B = pre-split weight planes: PL 1 reduction-contiguous, PL 2 read along their rows
 template <int EPI, bool B_RC = true, int PL = 1>
 static void launch_gemm_pl(const GemmArgs &g, int nz, hipStream_t s) {
     int maxM = 0, maxN = 0;
     for (int z = 0; z < nz; ++z) { maxM = g.M[z] > maxM ? g.M[z] : maxM; maxN = g.N[z] > maxN ? g.N[z] : maxN; }
-    {
-        // LDS-DMA forward (ppo_gemm_glds.h): 40 KB workgroups, up to four per CU -- update -2.6 % (profiles/r04_ab.txt).  LG_GEMM_GLDS=0: the
-        // register-staged k_gemm.  The input-gradient variant (bit 1; bit-identical, tests green) LOSES inside the update, where it shares the
-        // CUs with the weight-gradient kernels of the side stream (minibatch 0.472 -> 0.486 ms): exp builds only.
-        static const int glds = getenv("LG_GEMM_GLDS") ? atoi(getenv("LG_GEMM_GLDS")) : 1;
-#ifdef LG_EXP_KERNELS
-        constexpr bool have = true;
-#else
-        constexpr bool have = EPI == 0;
-#endif
-        if constexpr (have) {
-            if ((glds & (EPI == 0 ? 1 : 2)) && maxM > 64 && glds_ok<PL>(g, nz)) {
-                dim3 grid((unsigned)(((maxM + GLDS_BM - 1) / GLDS_BM) * (maxN / GLDS_BN)), 1, nz);
-                hipLaunchKernelGGL((k_gemm_glds<EPI, PL>), grid, dim3(256), 0, s, g);
-                return;
-            }
+    // LDS-DMA forward (ppo_gemm_glds.h): 40 KB workgroups, up to four per CU -- update -2.6 % (profiles/r04_ab.txt).  The input-gradient
+    // variant (bit-identical, tests green) LOSES inside the update, where it shares the CUs with the weight-gradient kernels of the side
+    // stream (minibatch 0.472 -> 0.486 ms): not launched.
+    if constexpr (EPI == 0) {
+        if (maxM > 64 && glds_ok<PL>(g, nz)) {
+            dim3 grid((unsigned)(((maxM + GLDS_BM - 1) / GLDS_BM) * (maxN / GLDS_BN)), 1, nz);
+            hipLaunchKernelGGL((k_gemm_glds<EPI, PL>), grid, dim3(256), 0, s, g);
+            return;
         }
     }
     const long big_tiles = (long)((maxM + 127) / 128) * ((maxN + 127) / 128);
     if (big_tiles >= 192 && maxN > 64 && maxM > 64) {
         dim3 grid((unsigned)big_tiles, 1, nz);
-#ifdef LG_EXP_KERNELS
-        // 256 CUs x 2 resident workgroups: time ~ rounds x tile area.  24576 rows in 128-row tiles give 768 or 384
-        // workgroups for the 256- and 128-wide layers (1.5 and 0.75 rounds); 96-row tiles give 1024 and 512.
-        const long t96 = (long)((maxM + 95) / 96) * ((maxN + 127) / 128);
-        const double c128 = (double)((big_tiles * nz + 511) / 512), c96 = 0.75 * (double)((t96 * nz + 511) / 512);
-        if (g_gemm_t96 && c96 < c128) {
-            hipLaunchKernelGGL((k_gemm<true, B_RC, EPI, 3, 1, false, true, 1, 4, PL>), dim3((unsigned)t96, 1, nz), dim3(256), 0, s, g);
-            return;
-        }
-        static const int pp = getenv("LG_GEMM_PP") ? atoi(getenv("LG_GEMM_PP")) : 0;     // bit 0 forward, bit 1 input gradient
-        if ((pp & 1) && EPI == 0 || (pp & 2) && EPI == 1) {
-            dim3 gpp((unsigned)(((maxM + 255) / 256) * ((maxN + 127) / 128)), 1, nz);
-            hipLaunchKernelGGL((k_gemm_pp<B_RC, EPI, PL>), gpp, dim3(512), 0, s, g);
-            return;
-        }
-        static const int w4 = getenv("LG_GEMM_W4") ? atoi(getenv("LG_GEMM_W4")) : 0;
-        if ((w4 & 1) && EPI == 0 || (w4 & 2) && EPI == 1) {
-            hipLaunchKernelGGL((k_gemm<true, B_RC, EPI, 2, 2, false, true, 2, 2, PL>), grid, dim3(256), 0, s, g);
-            return;
-        }
-#endif
         hipLaunchKernelGGL((k_gemm<true, B_RC, EPI, 2, 1, false, true, 2, 4, PL>), grid, dim3(512), 0, s, g);
     } else {
         dim3 grid((unsigned)(((maxM + 63) / 64) * ((maxN + 63) / 64)), 1, nz);
-#ifdef LG_EXP_KERNELS
-        static const int ldb = getenv("LG_GEMM_LDB") ? atoi(getenv("LG_GEMM_LDB")) : 0;
-        if (ldb) { hipLaunchKernelGGL((k_gemm<true, B_RC, EPI, 1, 1, false, true, 2, 2, PL, true>), grid, dim3(256), 0, s, g); return; }
-#endif
         hipLaunchKernelGGL((k_gemm<true, B_RC, EPI, 1, 1, false, true, 2, 2, PL>), grid, dim3(256), 0, s, g);
     }
 }
 static bool planes_ok(const GemmArgs &g, int nz) {
-    if (!g_gemm_planes || !g_gemm_x6) return false;
+    if (!g_gemm_x6) return false;
     for (int z = 0; z < nz; ++z)
         if (!g.Bpl[z] || (g.ldb[z] & 7) || (g.K[z] & 7) || g.K[z] < 8 || ((uintptr_t)g.Bpl[z] & 15) || (g.pl_stride & 7)) return false;
     return true;
 }
 
-template <bool A_RC, bool B_RC, int EPI>
+// fp32 operands in memory.  X6: the split-bf16 mainloop, 128x128 tiles on 8 waves (2x4, each 64x32); otherwise the fp32-input MFMA
+// reference, 128x128 tiles on one LDS buffer (34 KB, 4 workgroups/CU: measured 3-15 % faster than double buffering).  Small problems
+// (rollout forward on 4096 rows, heads) use 64x64 tiles to fill more CUs.
+template <bool A_RC, bool B_RC, int EPI, bool X6>
 static void launch_gemm(const GemmArgs &g, int nz, int splits, hipStream_t s) {
     int maxM = 0, maxN = 0;
     for (int z = 0; z < nz; ++z) { maxM = g.M[z] > maxM ? g.M[z] : maxM; maxN = g.N[z] > maxN ? g.N[z] : maxN; }
-    // small problems (rollout forward on 4096 rows, heads) use 64x64 tiles to fill more CUs
     const long big_tiles = (long)((maxM + 127) / 128) * ((maxN + 127) / 128);
     if (big_tiles * splits >= 192 && maxN > 64 && maxM > 64) {
         dim3 grid((unsigned)big_tiles, splits, nz);
-        if (g_gemm_x6 && g_gemm_w8) hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 2, 1, false, true, 2, 4>), grid, dim3(512), 0, s, g);
-        else if (g_gemm_x6) hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 2, 2, false, true>), grid, dim3(256), 0, s, g);
-        else if (g_gemm_dbuf) hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 2, 2, true>), grid, dim3(256), 0, s, g);
+        if constexpr (X6) hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 2, 1, false, true, 2, 4>), grid, dim3(512), 0, s, g);
         else hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 2, 2, false>), grid, dim3(256), 0, s, g);
     } else {
         dim3 grid((unsigned)(((maxM + 63) / 64) * ((maxN + 63) / 64)), splits, nz);
-        if (g_gemm_x6) hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 1, 1, false, true>), grid, dim3(256), 0, s, g);
+        if constexpr (X6) hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 1, 1, false, true>), grid, dim3(256), 0, s, g);
         else hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 1, 1, true>), grid, dim3(256), 0, s, g);
     }
 }
 // planes read along their rows (input gradient): column count and leading dimension in whole 16-byte chunks
 static bool planes_t_ok(const GemmArgs &g, int nz) {
-    if (!g_gemm_planes || !g_gemm_x6) return false;
+    if (!g_gemm_x6) return false;
     for (int z = 0; z < nz; ++z)
         if (!g.Bpl[z] || (g.ldb[z] & 7) || (g.N[z] & 7) || g.N[z] < 8 || ((uintptr_t)g.Bpl[z] & 15) || (g.pl_stride & 7)) return false;
     return true;
@@ -988,27 +865,26 @@ extern "C" void ppok_gemm_fwd(const GemmArgs *g, int nz, hipStream_t s) {
         if (g->ldbpl[z]) gp.ldb[z] = g->ldbpl[z];
     }
     if (planes_ok(gp, nz)) launch_gemm_pl<0>(gp, nz, s);
-    else launch_gemm<true, true, 0>(*g, nz, 1, s);
+    else if (g_gemm_x6) launch_gemm<true, true, 0, true>(*g, nz, 1, s);
+    else launch_gemm<true, true, 0, false>(*g, nz, 1, s);
 }
 extern "C" void ppok_gemm_dx(const GemmArgs *g, int nz, hipStream_t s) {
     if (planes_t_ok(*g, nz)) launch_gemm_pl<1, false, 2>(*g, nz, s);
-    else launch_gemm<true, false, 1>(*g, nz, 1, s);
+    else if (g_gemm_x6) launch_gemm<true, false, 1, true>(*g, nz, 1, s);
+    else launch_gemm<true, false, 1, false>(*g, nz, 1, s);
 }
+// weight gradients: k_gemm_dw_t on the split-bf16 path, k_gemm's fp32-input reference otherwise
 extern "C" void ppok_gemm_dw(const GemmArgs *g, int nz, int splits, hipStream_t s) {
-    if (!(g_gemm_dw_t && g_gemm_x6)) {         // k_gemm's store guard is its N: compute the true width only
+    if (!g_gemm_x6) {                          // k_gemm's store guard is its N: compute the true width only
         GemmArgs gt = *g;
         for (int z = 0; z < nz; ++z) if (g->nstore[z]) gt.N[z] = g->nstore[z];
-        launch_gemm<false, false, 2>(gt, nz, splits, s);
+        launch_gemm<false, false, 2, false>(gt, nz, splits, s);
         return;
     }
     int maxM = 0, maxN = 0;
     for (int z = 0; z < nz; ++z) { maxM = g->M[z] > maxM ? g->M[z] : maxM; maxN = g->N[z] > maxN ? g->N[z] : maxN; }
     const long big_tiles = (long)((maxM + 127) / 128) * ((maxN + 127) / 128);
     if (big_tiles * splits >= 192 && maxN > 64 && maxM > 64) {
-#ifdef LG_EXP_KERNELS
-        static const int w4 = getenv("LG_DW_W4") ? atoi(getenv("LG_DW_W4")) : 0;     // A/B: 4 waves of 64x64 per 128x128 tile
-        if (w4) { hipLaunchKernelGGL((k_gemm_dw_t<2, 2, 2, 2>), dim3((unsigned)big_tiles, splits, nz), dim3(256), 0, s, *g); return; }
-#endif
         hipLaunchKernelGGL((k_gemm_dw_t<2, 1, 2, 4>), dim3((unsigned)big_tiles, splits, nz), dim3(512), 0, s, *g);
     } else {
         const unsigned tiles = ((maxM + 63) / 64) * ((maxN + 63) / 64);
@@ -1294,7 +1170,7 @@ __global__ void __launch_bounds__(256) k_loss(PpoDev P, const float *__restrict_
 // workgroup per 64 minibatch rows.  Replaces four launches (head GEMM, k_loss, head weight-gradient
 // GEMM, head input-gradient GEMM) whose matrices are too thin for the MFMA tiles: the last hidden
 // activations of both nets are staged once in LDS and reused for mu/V, for d(loss)/d(act3) and for
-// the outer-product weight gradients.  H3 = last hidden width (<= 128).
+// the outer-product weight gradients.  H3 = last hidden width: 64 or 32 (128 wide: k_head_net + k_head_finish below).
 #define HEAD_ROWS 64
 #define HEAD_GRID 192
 #define HEAD_NET_GRID 384                                  // workgroups per network of k_head_net (= scratch rows per network)
@@ -1918,10 +1794,8 @@ size_t ppok_head_part_floats() { return (size_t)2 * HEAD_NET_GRID * HEAD_PART_ST
 int ppok_head_fused(const PpoDev *P, int H3, const float *xa, const float *xc, float *dza, float *dzc, int64_t w_a, int64_t b_a,
                     int64_t w_c, int64_t b_c, int64_t b_prev_a, int64_t b_prev_c, hipStream_t s) {
     const int ntiles = (P->mb_rows + HEAD_ROWS - 1) / HEAD_ROWS;
-    static const int head_grid = getenv("LG_HEAD_GRID") ? atoi(getenv("LG_HEAD_GRID")) : HEAD_GRID;
-    dim3 grid(ntiles < head_grid ? ntiles : head_grid), block(256);
-    static const int per_net = getenv("LG_HEAD_PER_NET") ? atoi(getenv("LG_HEAD_PER_NET")) : 1;
-    if (H3 == 128 && per_net) {
+    dim3 grid(ntiles < HEAD_GRID ? ntiles : HEAD_GRID), block(256);
+    if (H3 == 128) {                                       // one network per workgroup: 3 per CU, a 24576-row minibatch resident at once
         const int nrows = ntiles < HEAD_NET_GRID ? ntiles : HEAD_NET_GRID;
         if (P->A <= 12)
             hipLaunchKernelGGL((k_head_net<128, 12>), dim3(nrows, 2), block, 0, s, *P, xa, xc, dza, dzc, P->params + w_a, P->params + w_c, b_a, b_c);
@@ -1930,8 +1804,7 @@ int ppok_head_fused(const PpoDev *P, int H3, const float *xa, const float *xc, f
         constexpr int NTOT = HEAD_PART_STRIDE(128);
         hipLaunchKernelGGL((k_head_finish<128>), dim3((NTOT + 255) / 256, HEAD_FIN_CHUNKS, 2), block, 0, s, *P, nrows, w_a, b_a, w_c, b_c,
                            b_prev_a, b_prev_c);
-    } else if (H3 == 128) hipLaunchKernelGGL((k_head_fused<128>), grid, block, 0, s, *P, xa, xc, dza, dzc, w_a, b_a, w_c, b_c, b_prev_a, b_prev_c);
-    else if (H3 == 64) hipLaunchKernelGGL((k_head_fused<64>), grid, block, 0, s, *P, xa, xc, dza, dzc, w_a, b_a, w_c, b_c, b_prev_a, b_prev_c);
+    } else if (H3 == 64) hipLaunchKernelGGL((k_head_fused<64>), grid, block, 0, s, *P, xa, xc, dza, dzc, w_a, b_a, w_c, b_c, b_prev_a, b_prev_c);
     else if (H3 == 32) hipLaunchKernelGGL((k_head_fused<32>), grid, block, 0, s, *P, xa, xc, dza, dzc, w_a, b_a, w_c, b_c, b_prev_a, b_prev_c);
     else return -1;
     return 0;
@@ -1949,7 +1822,7 @@ int ppok_step(const PpoDev *P, int par, const PpoDev *G, int gather_mb, hipStrea
     if (P->det64) ppok_det_fold(P, s);                   // the squared gradient norm
     // one parameter per thread: the per-parameter chain (4 loads, Adam, 4 stores + the three plane stores through pl_dest) is a
     // memory round trip that a grid-stride loop repeats serially (6 x for [512,256,128] on 256 workgroups: 12.2 us; 8.9 us on 1024, 10.2 on 2048)
-    static const int adam_max = getenv("LG_ADAM_WGS") ? atoi(getenv("LG_ADAM_WGS")) : 1024;
+    constexpr int adam_max = 1024;
     const long want = (P->num_params + 255) / 256;
     hipLaunchKernelGGL(k_opt_adam, dim3((unsigned)(want < adam_max ? (want > 0 ? want : 1) : adam_max)), dim3(256), 0, s, *P, par);
     return g4 ? 1 : 0;
@@ -1962,8 +1835,8 @@ extern "C" void ppok_debug_gemm(const float *A, const float *B, float *C, int M,
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A[0] = A; g.B[0] = B; g.C[0] = C; g.M[0] = M; g.N[0] = N; g.K[0] = K; g.ldc[0] = N;
-    if (mode == 0) { g.lda[0] = K; g.ldb[0] = K; launch_gemm<true, true, 0>(g, 1, 1, (hipStream_t)stream); }
-    else if (mode == 1) { g.lda[0] = K; g.ldb[0] = N; g.aux[0] = C; g.ldaux[0] = N; g.elu = 1; launch_gemm<true, false, 1>(g, 1, 1, (hipStream_t)stream); }
+    if (mode == 0) { g.lda[0] = K; g.ldb[0] = K; ppok_gemm_fwd(&g, 1, (hipStream_t)stream); }                 // no planes: k_gemm
+    else if (mode == 1) { g.lda[0] = K; g.ldb[0] = N; g.aux[0] = C; g.ldaux[0] = N; g.elu = 1; ppok_gemm_dx(&g, 1, (hipStream_t)stream); }
     else { g.lda[0] = M; g.ldb[0] = N; ppok_gemm_dw(&g, 1, splits, (hipStream_t)stream); }
 }
 

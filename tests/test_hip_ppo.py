@@ -324,7 +324,7 @@ def test_split_bf16_gemm_is_fp32_accurate(mode, M, N, K):
     splits = 1 if mode < 2 else 3
     err = {}
     try:
-        for x6 in (0, 1, 3):
+        for x6 in (0, 1):
             lib.ppok_debug_set_x6(ctypes.c_int(x6))
             C = torch.ones(M, N, device="cuda") if mode < 2 else torch.zeros(M, N, device="cuda")
             lib.ppok_debug_gemm(vp(A), vp(B), vp(C), M, N, K, mode, splits, st)
@@ -332,9 +332,9 @@ def test_split_bf16_gemm_is_fp32_accurate(mode, M, N, K):
             assert torch.isfinite(C).all()
             err[x6] = float((C.double() - ref).abs().max())
     finally:
-        lib.ppok_debug_set_x6(ctypes.c_int(3))
+        lib.ppok_debug_set_x6(ctypes.c_int(1))
     bound = 2.0 * err[0] + 2.0 ** -22 * float(ref.abs().max())
-    assert err[1] <= bound and err[3] <= bound, err
+    assert err[1] <= bound, err
 
 
 @pytest.mark.parametrize("mode", [0, 1])
@@ -376,7 +376,7 @@ def test_weight_plane_gemms_are_fp32_accurate(mode, M, rows, cols):
         torch.cuda.synchronize()
         err_f32 = float((C0.double() - ref).abs().max())
     finally:
-        lib.ppok_debug_set_x6(ctypes.c_int(3))
+        lib.ppok_debug_set_x6(ctypes.c_int(1))
     assert torch.isfinite(C).all()
     assert err_pl <= 2.0 * err_f32 + 2.0 ** -22 * float(ref.abs().max()), (err_pl, err_f32)
 

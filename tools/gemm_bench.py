@@ -9,8 +9,8 @@ lib.ppok_debug_gemm.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [cty
 vp = lambda t: ctypes.c_void_p(t.data_ptr())
 st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 shapes = [(4096, 4096, 4096), (24576, 256, 512), (24576, 512, 48), (24576, 128, 256), (24576, 512, 256), (4096, 512, 48), (4096, 256, 512)]
-for dbuf in (3, 1, 0):
-    lib.ppok_debug_set_x6(ctypes.c_int(dbuf))
+for x6 in (1, 0):
+    lib.ppok_debug_set_x6(ctypes.c_int(x6))
     for (M, N, K) in shapes:
         for mode in (0, 1, 2):
             if mode == 2 and M > 4096:
@@ -32,4 +32,4 @@ for dbuf in (3, 1, 0):
                 lib.ppok_debug_gemm(vp(A), vp(B), vp(C), M, N, K, mode, splits, st)
             e1.record(); torch.cuda.synchronize()
             ms = e0.elapsed_time(e1) / reps
-            print(f"x6 {dbuf} mode {mode} M{M} N{N} K{K}: {ms*1e3:8.1f} us  {2*M*N*K/ms/1e9:7.1f} TF  relerr {err:.1e}", flush=True)
+            print(f"x6 {x6} mode {mode} M{M} N{N} K{K}: {ms*1e3:8.1f} us  {2*M*N*K/ms/1e9:7.1f} TF  relerr {err:.1e}", flush=True)

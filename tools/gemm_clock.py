@@ -10,7 +10,7 @@ lib.ppok_debug_gemm.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [cty
 vp = lambda t: ctypes.c_void_p(t.data_ptr())
 st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 for (M, N, K) in ((4096, 4096, 4096), (24576, 512, 256)):
-    for x6 in (3, 0):
+    for x6 in (1, 0):
         lib.ppok_debug_set_x6(ctypes.c_int(x6))
         for name, gen in (("random", torch.randn), ("zeros ", torch.zeros)):
             A, B, C = gen(M, K, device="cuda"), gen(N, K, device="cuda"), torch.empty(M, N, device="cuda")

@@ -1,6 +1,6 @@
 """One GEMM shape through ppok_debug_gemm, a few launches -- the target of rocprofv3 --pmc runs.
 
-    python tools/gemm_prof.py M N K MODE X6 [REPS]
+    python tools/gemm_prof.py M N K MODE X6 [REPS]      (X6: 1 the split-bf16 product path, 0 the fp32-input MFMA reference)
 """
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -6,8 +6,7 @@ by that constant, and the first row above the MFMA peak of the CUs it can occupy
     cd /tmp && rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 tools/gemm_quant.py run      # launches only
     python tools/gemm_quant.py digest OUT                                                                 # per-configuration kernel times
 
-LG_GEMM_GLDS=0 selects the register-staged k_gemm (2 workgroups of 8 waves per CU = 512 slots), the default the LDS-DMA kernel
-(4 workgroups of 4 waves per CU = 1024 slots)."""
+The forward on the weight planes runs the LDS-DMA kernel (4 workgroups of 4 waves per CU = 1024 slots)."""
 import csv
 import glob
 import os
