@@ -15,12 +15,11 @@ extern "C" {
 void ppok_gemm_fwd(const GemmArgs *g, int nz, hipStream_t s);
 void ppok_gemm_dx(const GemmArgs *g, int nz, hipStream_t s);
 void ppok_sync_planes(const PpoDev *P, hipStream_t s);
-int ppok_mlp_fwd(const MlpArgs *g, const PpoDev *P, int mask, hipStream_t s);
+int ppok_mlp_fwd(const MlpArgs *g, const PpoDev *P, hipStream_t s);
 int ppok_mlp_supported(const MlpArgs *g);
 int64_t ppok_mlp_frag_elems(int K, int N);
 void ppok_mlp_frag_build(const MlpArgs *g, hipStream_t s);
-void ppok_gemm_dw(const GemmArgs *g, int nz, int splits, hipStream_t s);
-void ppok_debug_set_xcd_remap(int v);
+void ppok_gemm_dw(const GemmArgs *g, int nz, hipStream_t s);
 void ppok_act_sample(const PpoDev *P, const float *obs, const float *cobs, const float *mu, const float *val, int t,
                      int64_t cnt, int inject, hipStream_t s);
 void ppok_process_step(const PpoDev *P, const float *rew, const uint8_t *dones, const uint8_t *tos, int t, hipStream_t s);
@@ -209,7 +208,6 @@ static void backward(lg_ppo *p, int M, const float *in0, const float *in1, int s
         GemmArgs g;
         memset(&g, 0, sizeof(g));
         det_args(g);
-        long tiles = 0;
         for (int z = 0; z < 2; ++z) {                // dW_l += dz[l+1]^T . act[l]
             Net &n = p->net[z];
             g.A[z] = n.dz[l + 1]; g.lda[z] = n.dims[l + 1];
@@ -221,20 +219,7 @@ static void backward(lg_ppo *p, int M, const float *in0, const float *in1, int s
                 g.ldb[z] = ldp;
                 if (ldp != n.dims[0]) { g.N[z] = ldp; g.nstore[z] = n.dims[0]; }
             }
-            const int tile = (g.M[z] > 64 && g.N[z] > 64) ? 128 : 64;
-            long t = (long)((g.M[z] + tile - 1) / tile) * ((g.N[z] + tile - 1) / tile);
-            tiles = t > tiles ? t : tiles;
         }
-        // ~256 workgroups per net: enough to fill the chip, few enough that the split-M float atomics
-        // (splits x output floats) stay well below the MFMA time
-        // workgroups per net over (output tiles x reduction splits); swept 64..384 inside the update (side stream beside the
-        // input-gradient chain): 0.637 / 0.585 / 0.597 / 0.574 / 0.560 ms per minibatch at 64 / 128 / 192 / 256 / 384
-        constexpr int dw_target = 384;
-        int splits = (int)((dw_target + tiles - 1) / tiles);
-        int max_splits = M / 256 > 0 ? M / 256 : 1;
-        if (splits > max_splits) splits = max_splits;
-        if (splits >= 8) splits &= ~7;                 // whole groups of 8 slices: one per XCD (xcd_tile)
-        if (splits < 1) splits = 1;
         // the weight gradient of layer l runs beside the input-gradient chain on the side stream -- except the last one
         // (l = 0), which has nothing left to overlap with: on the main stream it starts without the cross-stream event wait
         // (on the side stream: 0.479 / 0.490 ms per minibatch against 0.465 / 0.469, within that bench's noise: profiles/r02_ab.txt)
@@ -244,7 +229,7 @@ static void backward(lg_ppo *p, int M, const float *in0, const float *in1, int s
             (void)hipEventRecord(p->ev_dz, p->stream);
             (void)hipStreamWaitEvent(p->side, p->ev_dz, 0);
         }
-        ppok_gemm_dw(&g, 2, splits, dw_stream);
+        ppok_gemm_dw(&g, 2, dw_stream);
         if (p->comm) reduce_layer_bucket(p, l, dw_stream);
         if (l > 0) {                                 // dz[l] = (dz[l+1] . W_l) * act'(act[l]); db_{l-1} = colsum(dz[l])
             memset(&g, 0, sizeof(g));
@@ -417,7 +402,6 @@ static void rnn_backward_seq(lg_ppo *p, int mb) {
         GemmArgs g;
         memset(&g, 0, sizeof(g));
         g.det_base = d.grads; g.det64 = d.det64; g.det_n = d.num_params + 2;
-        long tiles = 0;
         for (int z = 0; z < 2; ++z) {
             g.A[z] = q.pg[z]; g.lda[z] = 4 * H;
             g.M[z] = 4 * H; g.K[z] = R;
@@ -432,16 +416,8 @@ static void rnn_backward_seq(lg_ppo *p, int mb) {
                 g.C[z] = d.grads + q.w_hh[z]; g.ldc[z] = H;
                 g.N[z] = H;
             }
-            const int tile = (g.M[z] > 64 && g.N[z] > 64) ? 128 : 64;
-            const long tz = (long)((g.M[z] + tile - 1) / tile) * ((g.N[z] + tile - 1) / tile);
-            tiles = tz > tiles ? tz : tiles;
         }
-        int splits = (int)((384 + tiles - 1) / tiles);      // the MLP's weight-gradient split rule (backward())
-        const int max_splits = R / 256 > 0 ? R / 256 : 1;
-        if (splits > max_splits) splits = max_splits;
-        if (splits >= 8) splits &= ~7;
-        if (splits < 1) splits = 1;
-        ppok_gemm_dw(&g, 2, splits, p->stream);
+        ppok_gemm_dw(&g, 2, p->stream);
     }
     RnnBiasArgs b;
     memset(&b, 0, sizeof(b));
@@ -498,7 +474,6 @@ static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **
     p->step = 0; p->inject = 0; p->act_count = 0; p->update_count = 0; p->params_dirty = 1;
     p->comm = nullptr; p->comm_rc = 0; p->comm_timing = 0; p->comm_ev_used = 0;
     p->env = nullptr; p->pp_pending = 0;
-    if (getenv("LG_XCD_REMAP")) ppok_debug_set_xcd_remap(atoi(getenv("LG_XCD_REMAP")));
     p->perm_count = 0;
     const int R = (int)((long)N * T / cfg->num_mini_batches);
     p->Mmax = R > N ? R : N;
@@ -735,7 +710,7 @@ int lg_ppo_act(lg_ppo *p, const float *obs, const float *critic_obs) {
         g.out[0] = p->net[0].act[p->net[0].nl]; g.out[1] = p->net[1].act[p->net[1].nl];
         if (dirty) ppok_mlp_frag_build(&g, p->stream);
         // sampled and stored by the same launch (a separate k_act_sample: rollout 4.40 / 4.41 ms against 4.15 / 4.19, profiles/r02_ab.txt)
-        g.sample = 1; g.t = p->step; g.inject = p->inject; g.act_count = p->act_count;
+        g.t = p->step; g.inject = p->inject; g.act_count = p->act_count;
         g.pp = 0;
         const int N = p->cfg.num_envs;
         const bool fits = (N + 255) / 256 + 1 <= (N + 31) / 32;  // epilogue workgroups within the launch's grid.x
@@ -745,7 +720,7 @@ int lg_ppo_act(lg_ppo *p, const float *obs, const float *critic_obs) {
             g.pp_env = lg_internal_take_finalize(p->env, &g.pp_counter);
             p->pp_pending = 0;
         } else flush_rollout_epilogue(p);
-        fused = ppok_mlp_fwd(&g, &p->dev, 3, p->stream);
+        fused = ppok_mlp_fwd(&g, &p->dev, p->stream);
         if (fused != 0 && g.pp) { lg_set_error("fused act launch refused with a rollout epilogue attached"); return -13; }
         if (fused == 0) {                                                         // sampled and stored by the same launch
             p->act_count++;

@@ -8,8 +8,8 @@ struct MlpArgs {
     const float *params;           // fp32 parameters (biases)
     const uint16_t *wfrag;         // fragment-order weight image (ppo_mlp_fused.hip), frag_off[z][l] elements in
     int M, nl, act;                // rows, linear layers, activation code of the hidden layers (as k_gemm)
-    // PPO.act epilogue in the same launch (sample = 1): a ~ N(mu, sigma), log-prob, transition store of step t
-    int sample, t, inject;
+    // PPO.act epilogue in the same launch: a ~ N(mu, sigma), log-prob, transition store of step t
+    int t, inject;
     int64_t act_count;
     // Rollout epilogue of the PREVIOUS policy step in the same launch (lg_ppo_attach_env): blockIdx.y == 2 workgroups run
     // process_env_step of step `pp_t` for 256 envs each and, one of them, the env's deferred single-workgroup epilogue.

@@ -5,52 +5,14 @@
 // Workgroup = 32 rows of one net (grid.y: 0 actor, 1 critic), 4 waves.  The activations of the 32 rows never leave
 // LDS (two fp32 images [32][K + 4]: K + 4 = 4 x odd keeps the 16-lane groups of ds_read_b128 on distinct 16-B
 // slots).  Per layer every wave owns the column tiles n = 32 * (wave + 4 i): the A fragment (32 rows x 16 k) is read
-// from LDS and split into its three bf16 terms in registers (same exact split as the GEMM staging), the B fragments
+// from LDS and split into its three bf16 terms in registers (split8 of ppo_split_bf16.h, as the GEMM staging), the B fragments
 // come straight from the optimiser's bf16 weight planes in L2 (W [n][k]: 16 B per lane per plane, two k-steps
 // prefetched), six v_mfma_f32_32x32x16_bf16 per fp32 product block as in k_gemm.  Bias + activation in registers,
-// result back to LDS for the next layer; only the head outputs (means, value) go to HBM.
+// result back to LDS for the next layer; the head outputs (means, value) stay in LDS for the sampling epilogue.
 #include "ppo_device.h"
 #include "ppo_mlp_args.h"
 #include "lg_finalize.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-
-__device__ __forceinline__ uint32_t mlp_cvt_pk_bf16(float a, float b) {
-    uint32_t r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// 8 consecutive floats -> the three bf16x8 terms (h, m, l), x = h + m + l exactly (see k_gemm's split2)
-__device__ __forceinline__ void mlp_split8(const float (&x)[8], bf16x8 &h, bf16x8 &m, bf16x8 &l) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    uint32_t hh[4], mm[4], ll[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float x0 = x[2 * i], x1 = x[2 * i + 1];
-        hh[i] = mlp_cvt_pk_bf16(x0, x1);
-        f32x2 r = f32x2{x0, x1} - f32x2{__uint_as_float(hh[i] << 16), __uint_as_float(hh[i] & 0xffff0000u)};
-        mm[i] = mlp_cvt_pk_bf16(r.x, r.y);
-        r -= f32x2{__uint_as_float(mm[i] << 16), __uint_as_float(mm[i] & 0xffff0000u)};
-        ll[i] = mlp_cvt_pk_bf16(r.x, r.y);
-    }
-    h = __builtin_bit_cast(bf16x8, make_uint4(hh[0], hh[1], hh[2], hh[3]));
-    m = __builtin_bit_cast(bf16x8, make_uint4(mm[0], mm[1], mm[2], mm[3]));
-    l = __builtin_bit_cast(bf16x8, make_uint4(ll[0], ll[1], ll[2], ll[3]));
-}
-__device__ __forceinline__ float mlp_act(int code, float v) {
-    switch (code) {
-    case 1: return v > 0.f ? v : __expf(v) - 1.0f;
-    case 2: return v > 0.f ? 1.0507009873554804934193349852946f * v
-                           : 1.0507009873554804934193349852946f * 1.6732632423543772848170429916717f * (__expf(v) - 1.0f);
-    case 3: return fmaxf(v, 0.f);
-    case 4: return v > 0.f ? v : 0.01f * v;
-    case 5: return 2.0f * __frcp_rn(1.0f + __expf(-2.0f * v)) - 1.0f;
-    case 6: return __frcp_rn(1.0f + __expf(-v));
-    default: return v;
-    }
-}
+#include "ppo_split_bf16.h"
 
 #define MLP_ROWS 32
 #ifndef MLP_NW
@@ -80,8 +42,7 @@ __device__ __forceinline__ BFrag mlp_load_frag(const uint16_t *__restrict__ wf, 
 // from LDS and split once per k-step.  k is walked in blocks of S k-steps (S CT = 4: twelve 1 KB loads per block and wave, two
 // blocks in flight = 24 KB per wave, enough to cover the L2 round trip at the CU's fill rate).
 template <int CT, int S, int ACT>
-__device__ __forceinline__ void mlp_layer(const MlpArgs &g, int z, int l, const float *__restrict__ cur, float *__restrict__ nxt, int row0,
-                                          int wave, int t0, int li, int lk) {
+__device__ __forceinline__ void mlp_layer(const MlpArgs &g, int z, int l, const float *__restrict__ cur, float *__restrict__ nxt, int wave, int t0, int li, int lk) {
     // K: the layer's input width rounded up to whole k-steps (only an observation width can be off the grid: 235 rough terrain,
     // 169 Cassie, 65 trajectory task; the pad columns are zero in the LDS image and in the weight image)
     const int K = mlp_kpad(g.dims[z][l]), N = g.dims[z][l + 1], ld = K + 4, ldo = N + 4, nks = K / 16, nkb = (nks + S - 1) / S;
@@ -109,19 +70,16 @@ __device__ __forceinline__ void mlp_layer(const MlpArgs &g, int z, int l, const 
 #pragma unroll
         for (int q = 0; q < S; ++q) {
             if (S * kb + q >= nks) break;                              // tail of a K that is not a whole number of blocks (uniform)
-            float x[8];
-            *reinterpret_cast<float4 *>(x) = *reinterpret_cast<const float4 *>(arow + 16 * (S * kb + q));
-            *reinterpret_cast<float4 *>(x + 4) = *reinterpret_cast<const float4 *>(arow + 16 * (S * kb + q) + 4);
-            bf16x8 ah, am, al;
-            mlp_split8(x, ah, am, al);
-            // the six term products, smallest first; column tiles interleaved so that consecutive MFMAs never share an accumulator
-            const bf16x8 *ax[3] = {&ah, &am, &al};
-            constexpr int PA[6] = {1, 0, 2, 0, 1, 0}, PB[6] = {1, 2, 0, 1, 0, 0};
+            const float4 lo = *reinterpret_cast<const float4 *>(arow + 16 * (S * kb + q));
+            const float4 hi = *reinterpret_cast<const float4 *>(arow + 16 * (S * kb + q) + 4);
+            bf16x8 ax[3];
+            split8(lo, hi, ax[0], ax[1], ax[2]);
+            // the six term products in X6_TERMS order; column tiles interleaved so that consecutive MFMAs never share an accumulator
 #pragma unroll
             for (int t = 0; t < 6; ++t)
 #pragma unroll
                 for (int c = 0; c < CT; ++c)
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*ax[PA[t]], src[q][c].p[PB[t]], acc[c], 0, 0, 0);
+                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ax[X6_TERMS[t].a], src[q][c].p[X6_TERMS[t].b], acc[c], 0, 0, 0);
         }
     };
     // sched_barrier: hipcc otherwise sinks the prefetch loads down to their uses and waits on each (vmcnt(0..5) all over
@@ -148,27 +106,26 @@ __device__ __forceinline__ void mlp_layer(const MlpArgs &g, int z, int l, const 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float v = acc[c][r] + bv;          // ACT 1: ELU compiled in (a per-element switch bloats the kernel past the I-cache)
-                nxt[((r & 3) + 8 * (r >> 2) + 4 * lk) * ldo + n[c]] = ACT == 1 ? (v > 0.f ? v : __expf(v) - 1.0f) : mlp_act(g.act, v);
+                nxt[((r & 3) + 8 * (r >> 2) + 4 * lk) * ldo + n[c]] = ACT == 1 ? (v > 0.f ? v : __expf(v) - 1.0f) : act_fwd(g.act, v);
             }
         } else if (n[c] < N) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int lr = (r & 3) + 8 * (r >> 2) + 4 * lk, gr = row0 + lr;
-                if (g.sample) nxt[lr * ldo + n[c]] = acc[c][r] + bv;     // stays in LDS for the sampling epilogue
-                else if (gr < g.M) g.out[z][(size_t)gr * N + n[c]] = acc[c][r] + bv;
+                const int lr = (r & 3) + 8 * (r >> 2) + 4 * lk;
+                nxt[lr * ldo + n[c]] = acc[c][r] + bv;     // stays in LDS for the sampling epilogue
             }
         }
     }
 }
 // the column tiles of a wave, four / two / one at a time (S CT = 4)
 template <int ACT>
-__device__ __forceinline__ void mlp_layer_tiles(const MlpArgs &g, int z, int l, const float *cur, float *nxt, int row0, int wave, int mine,
+__device__ __forceinline__ void mlp_layer_tiles(const MlpArgs &g, int z, int l, const float *cur, float *nxt, int wave, int mine,
                                                 int li, int lk) {
     for (int t0 = 0; t0 < mine;) {
         const int c = mine - t0;
-        if (c >= 4) { mlp_layer<4, 1, ACT>(g, z, l, cur, nxt, row0, wave, t0, li, lk); t0 += 4; }
-        else if (c >= 2) { mlp_layer<2, 2, ACT>(g, z, l, cur, nxt, row0, wave, t0, li, lk); t0 += 2; }
-        else { mlp_layer<1, 4, ACT>(g, z, l, cur, nxt, row0, wave, t0, li, lk); t0 += 1; }
+        if (c >= 4) { mlp_layer<4, 1, ACT>(g, z, l, cur, nxt, wave, t0, li, lk); t0 += 4; }
+        else if (c >= 2) { mlp_layer<2, 2, ACT>(g, z, l, cur, nxt, wave, t0, li, lk); t0 += 2; }
+        else { mlp_layer<1, 4, ACT>(g, z, l, cur, nxt, wave, t0, li, lk); t0 += 1; }
     }
 }
 
@@ -187,7 +144,7 @@ __global__ void __launch_bounds__(256) k_mlp_frag_build(MlpArgs g, uint16_t *__r
 #pragma unroll
                 for (int j = 0; j < 8; ++j) x[j] = (n < N && k + j < K) ? W[(size_t)n * K + min(k + j, K - 1)] : 0.f;
                 bf16x8 h, m, lo;
-                mlp_split8(x, h, m, lo);
+                split8(make_float4(x[0], x[1], x[2], x[3]), make_float4(x[4], x[5], x[6], x[7]), h, m, lo);
                 uint16_t *q = dst + ((size_t)(tile * nks + ks) * 3) * 512 + lane * 8;
                 *reinterpret_cast<bf16x8 *>(q) = h;
                 *reinterpret_cast<bf16x8 *>(q + 512) = m;
@@ -240,7 +197,7 @@ __global__ void __launch_bounds__(MLP_NT, 1) k_mlp_fwd(MlpArgs g, PpoDev P) {
             cur[r * ld + k] = v;
             // storage.add of the observations (rsl_rl RolloutStorage): the actor workgroup stores its rows, the critic's its own
             // when the critic has privileged observations
-            if (g.sample && g.t >= 0 && row0 + r < g.M) {
+            if (g.t >= 0 && row0 + r < g.M) {
                 if (z == 0) P.st_obs[((size_t)g.t * g.M + gr) * K + k] = v;
                 else if (P.st_critic_obs != P.st_obs) P.st_critic_obs[((size_t)g.t * g.M + gr) * K + k] = v;
             }
@@ -252,13 +209,12 @@ __global__ void __launch_bounds__(MLP_NT, 1) k_mlp_fwd(MlpArgs g, PpoDev P) {
         const int ntiles = (g.dims[z][l + 1] + 31) / 32;
         // column tiles of this wave: wave, wave + 4, ... (workgroup-uniform count per wave up to rounding)
         const int mine = ntiles > wave ? (ntiles - wave + MLP_NW - 1) / MLP_NW : 0;
-        if (g.act == 1) mlp_layer_tiles<1>(g, z, l, cur, nxt, row0, wave, mine, li, lk);
-        else mlp_layer_tiles<-1>(g, z, l, cur, nxt, row0, wave, mine, li, lk);
+        if (g.act == 1) mlp_layer_tiles<1>(g, z, l, cur, nxt, wave, mine, li, lk);
+        else mlp_layer_tiles<-1>(g, z, l, cur, nxt, wave, mine, li, lk);
         __syncthreads();
         MSTAMP();
         float *t = cur; cur = nxt; nxt = t;
     }
-    if (!g.sample) return;
     // ---- PPO.act epilogue (the arithmetic of k_act_sample, term by term): cur = head outputs [32][N + 4]
     const int A = P.A, t = g.t, N = g.M, ldh = g.dims[z][g.nl] + 4;
     if (z == 0) {
@@ -311,10 +267,10 @@ extern "C" int64_t ppok_mlp_frag_elems(int K, int N) { return (int64_t)((N + 31)
 extern "C" void ppok_mlp_frag_build(const MlpArgs *g, hipStream_t s) {
     hipLaunchKernelGGL(k_mlp_frag_build, dim3(256), dim3(256), 0, s, *g, const_cast<uint16_t *>(g->wfrag));
 }
-// P: the learner's device struct (sampling epilogue when g->sample; otherwise only passed through)
-extern "C" int ppok_mlp_fwd(const MlpArgs *g, const PpoDev *P, int mask, hipStream_t s) {
-    if (mask != 3 || ppok_mlp_supported(g) || ((uintptr_t)g->wfrag & 15)) return -1;
-    if (g->sample && (g->M != P->N || g->dims[0][g->nl] != P->A || g->dims[1][g->nl] != 1 || P->A > LG_PPO_MAX_A)) return -1;
+// P: the learner's device struct (the sampling epilogue's storage and parameters)
+extern "C" int ppok_mlp_fwd(const MlpArgs *g, const PpoDev *P, hipStream_t s) {
+    if (ppok_mlp_supported(g) || ((uintptr_t)g->wfrag & 15)) return -1;
+    if ((g->M != P->N || g->dims[0][g->nl] != P->A || g->dims[1][g->nl] != 1 || P->A > LG_PPO_MAX_A)) return -1;
     static_assert(MLP_NT == 256, "finalize_body and the process lanes are written for 256 threads");
     if (g->pp && (P->N + MLP_NT - 1) / MLP_NT + 1 > (g->M + MLP_ROWS - 1) / MLP_ROWS) return -1;   // epilogue blocks must fit grid.x
     dim3 grid((g->M + MLP_ROWS - 1) / MLP_ROWS, g->pp ? 3 : 2);

@@ -43,10 +43,10 @@ Workload: anymal_c_flat, 4096 envs, ActorCritic [512,256,128] (BASELINE.json con
 ## Kernel table (3 timed + 1 warm-up iterations, + the roofline probes of bench.py)
 
 {tab}
-`k_gemm<A_RC, B_RC, EPI, TM, TN, DBUF, X6, WGM, WGN, B_PL>`: all instantiations here are the split-bf16 mainloop (X6 = true).
+`k_gemm<A_RC, B_RC, EPI, TM, TN, WGM, WGN, B_PL>`: the split-bf16 GEMM.
 EPI 0 forward (bias + activation; B_PL = weight operand from the optimiser's bf16 planes), EPI 1 input gradient (activation
-derivative + bias-gradient column sums), EPI 2 weight gradient (split-M atomics, side stream).  `2,1,...,2,4` = 128x128 tile on
-8 waves, `1,1,...,2,2` = 64x64 tile on 4 waves.  `k_substeps` is the whole control loop of one policy step (clip + 4 x (actuator
+derivative + bias-gradient column sums); weight gradients (split-M atomics, side stream) are `k_gemm_dw_t`.  `2,1,2,4` = 128x128
+tile on 8 waves, `1,1,2,2` = 64x64 tile on 4 waves.  `k_substeps` is the whole control loop of one policy step (clip + 4 x (actuator
 LSTM, ABA + contact + joint limits)).
 
 Agreement with the live measurement: bench.py times one minibatch forward+backward (13 launches: gather, 4 forward GEMMs,
