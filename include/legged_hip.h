@@ -445,6 +445,58 @@ int lg_ppo_broadcast_params(lg_ppo *p, lg_comm *c, int root);   /* identical ini
 int lg_ppo_comm_timing(lg_ppo *p, int enable);
 int lg_ppo_comm_wait_ms(lg_ppo *p, double *ms_total, int64_t *minibatches);
 
+/* ------------------------------------------------------------------ tube-model trainer (deep_tube_learning/train_tube.py: the
+ * reference MLP, ScalarTube / VectorTube / ScalarHorizonTube / Error losses, Adam + StepLR).
+ * One training step = one fused forward / loss / backward launch + one launch that reduces the per-workgroup gradients in a
+ * fixed order and runs Adam: bit-reproducible from run to run.  Nothing in a step synchronises the host. */
+#define LG_TUBE_MAX_IN 256
+#define LG_TUBE_MAX_OUT 64
+#define LG_TUBE_MAX_UNITS 128                      /* num_units: 16..128, multiple of 16; num_layers 1..4 */
+#define LG_TUBE_ACT_RELU 0
+#define LG_TUBE_ACT_SOFTPLUS 1                     /* torch.nn.Softplus(beta, threshold=20) */
+#define LG_TUBE_ACT_TANH 2
+#define LG_TUBE_ACT_ELU 3                          /* alpha 1 */
+#define LG_TUBE_LOSS_SCALAR 0                      /* ScalarTubeLoss / ScalarHorizonTubeLoss: Huber mean over rows x outputs */
+#define LG_TUBE_LOSS_VECTOR 1                      /* VectorTubeLoss: pinball residuals summed per row, Huber mean over rows */
+#define LG_TUBE_LOSS_MSE 2                         /* ErrorLoss */
+typedef struct lg_tube_cfg {
+    int32_t input_dim, output_dim, num_units, num_layers;
+    int32_t activation, loss, horizon /*0: flat (data, target) rows; 1: ScalarHorizonTubeDataset windows*/, batch_size;
+    int32_t H_fwd, H_rev, step_size /*StepLR*/, _pad;
+    uint64_t seed;                                 /* epoch permutations and horizon window draws */
+    float alpha, delta, softplus_beta, _padf;
+    double lr, gamma;                              /* Adam lr0; StepLR: lr = lr0 * gamma^floor(step / step_size) */
+} lg_tube_cfg;
+
+typedef struct lg_tube_buffers {
+    float *params, *grads, *adam_m, *adam_v;      /* flat, num_params, lg_tube_param_layout order; grads = the last step's */
+    float *log;                                    /* (log_cap, 4) per step, slot (step - 1) % log_cap: loss, lr after the step
+                                                      (StepLR's get_last_lr), gradient norm, rows */
+    float *eval;                                   /* 4: test loss, fraction of outputs with fw > w, mean |w - fw| where fw > w, rows */
+    int32_t *starts;                               /* horizon dataset: window start drawn per row of the last step / eval */
+    int32_t *perm;                                 /* the epoch's permutation of the training rows */
+    int64_t num_params, log_cap, starts_cap, perm_cap, step;
+} lg_tube_buffers;
+
+typedef struct lg_tube lg_tube;
+int lg_tube_check_cfg(const lg_tube_cfg *cfg);    /* 0 inside the supported envelope, else -1 and lg_last_error says why */
+int lg_tube_create(const lg_tube_cfg *cfg, lg_tube **out);
+int lg_tube_destroy(lg_tube *t);
+int lg_tube_set_stream(lg_tube *t, void *stream);
+int lg_tube_get_buffers(lg_tube *t, lg_tube_buffers *out);
+/* per Linear layer: weight (offset, [out, in]) then bias (offset, [out, 0]); returns #tensors = 2 * (num_layers + 1) */
+int lg_tube_param_layout(lg_tube *t, int64_t *offsets, int64_t *shapes, int max_entries);
+int lg_tube_params_changed(lg_tube *t);            /* after the caller wrote params (initialisation, checkpoint load) */
+int lg_tube_set_step(lg_tube *t, int64_t step);    /* Adam / StepLR step count (resume) */
+/* which: 0 train, 1 test.  Device pointers the caller keeps alive.  Flat: x = data (rows, input_dim), y = target
+ * (rows, output_dim), v unused.  Horizon: x = w (rows, T), y = z (rows, T, nz), v = v (rows, T, m), padded in front by H_rev. */
+int lg_tube_set_data(lg_tube *t, int which, const float *x, const float *y, const float *v, int64_t rows, int32_t T, int32_t nz,
+                     int32_t m);
+int lg_tube_begin_epoch(lg_tube *t, int64_t epoch);   /* a new permutation of the training rows, keyed by (seed, epoch) */
+/* One Adam step on `count` rows: rows (device, count) or NULL = the next count rows of the epoch's permutation. */
+int lg_tube_step(lg_tube *t, const int32_t *rows, int64_t count);
+int lg_tube_eval(lg_tube *t);                      /* metrics of the test split into lg_tube_buffers.eval (one window per row) */
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,44 @@ class lg_ppo_rnn_buffers(C.Structure):
     _fields_ = [("h", PF * 2), ("c", PF * 2), ("saved_h", PF * 2), ("saved_c", PF * 2), ("hidden", i64)]
 
 
+TUBE_MAX_IN, TUBE_MAX_OUT, TUBE_MAX_UNITS = 256, 64, 128     # LG_TUBE_MAX_*; num_units a multiple of 16, num_layers 1..4
+TUBE_ACT = {"relu": 0, "softplus": 1, "tanh": 2, "elu": 3}      # LG_TUBE_ACT_*
+TUBE_LOSS = {"scalar": 0, "vector": 1, "mse": 2}                # LG_TUBE_LOSS_*
+
+
+class lg_tube_cfg(C.Structure):
+    _fields_ = [
+        ("input_dim", i32), ("output_dim", i32), ("num_units", i32), ("num_layers", i32),
+        ("activation", i32), ("loss", i32), ("horizon", i32), ("batch_size", i32),
+        ("H_fwd", i32), ("H_rev", i32), ("step_size", i32), ("_pad", i32),
+        ("seed", u64),
+        ("alpha", f32), ("delta", f32), ("softplus_beta", f32), ("_padf", f32),
+        ("lr", C.c_double), ("gamma", C.c_double)]
+
+
+class lg_tube_buffers(C.Structure):
+    _fields_ = [
+        ("params", PF), ("grads", PF), ("adam_m", PF), ("adam_v", PF), ("log", PF), ("eval", PF),
+        ("starts", PI32), ("perm", PI32),
+        ("num_params", i64), ("log_cap", i64), ("starts_cap", i64), ("perm_cap", i64), ("step", i64)]
+
+
+def declare_tube_api(lib):
+    vp = C.c_void_p
+    lib.lg_tube_check_cfg.argtypes = [C.POINTER(lg_tube_cfg)]
+    lib.lg_tube_create.argtypes = [C.POINTER(lg_tube_cfg), C.POINTER(vp)]
+    lib.lg_tube_destroy.argtypes = [vp]
+    lib.lg_tube_set_stream.argtypes = [vp, vp]
+    lib.lg_tube_get_buffers.argtypes = [vp, C.POINTER(lg_tube_buffers)]
+    lib.lg_tube_param_layout.argtypes = [vp, PI64, PI64, C.c_int]
+    lib.lg_tube_params_changed.argtypes = [vp]
+    lib.lg_tube_set_step.argtypes = [vp, i64]
+    lib.lg_tube_set_data.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32]
+    lib.lg_tube_begin_epoch.argtypes = [vp, i64]
+    lib.lg_tube_step.argtypes = [vp, vp, i64]
+    lib.lg_tube_eval.argtypes = [vp]
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p

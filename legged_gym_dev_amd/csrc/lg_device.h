@@ -210,3 +210,24 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint32_t env, uin
     uint32_t r = (slot & 3) == 0 ? c[0] : (slot & 3) == 1 ? c[1] : (slot & 3) == 2 ? c[2] : c[3];
     return (float)(r >> 8) * (1.0f / 16777216.0f);
 }
+
+// Element i of a keyed bijection of [0, n) (k_randperm, k_tube_perm): b = bits of n rounded up to even, a 6-round balanced
+// Feistel network on [0, 2^b) whose round function is one Philox block keyed by (seed, key, round), restricted to [0, n) by
+// cycle walking (re-encrypt until the value falls below n: a bijection of the superset walks every element of [0, n) to a
+// distinct element of [0, n)).  half_bits = b / 2.  No sort, no host round trip; each lane is independent.
+__device__ __forceinline__ uint32_t feistel_perm(uint64_t seed, uint64_t key, int n, int half_bits, uint32_t i) {
+    const uint32_t mask = (1u << half_bits) - 1u;
+    uint32_t x = i;
+    do {
+        uint32_t l = x >> half_bits, r = x & mask;
+#pragma unroll 1
+        for (int round = 0; round < 6; ++round) {
+            uint32_t c[4] = {r, (uint32_t)round, (uint32_t)key, (uint32_t)(key >> 32) ^ 0x9e3779b9u};
+            philox4x32((uint32_t)seed, (uint32_t)(seed >> 32), c);
+            const uint32_t t = l ^ (c[0] & mask);
+            l = r; r = t;
+        }
+        x = (l << half_bits) | r;
+    } while (x >= (uint32_t)n);
+    return x;
+}

@@ -103,27 +103,11 @@ __global__ void k_adv_normalize(PpoDev P) {
 }
 
 // mini_batch_generator's randperm(T*N), drawn on the device once per update and reused by every epoch:
-// a keyed bijection of [0, 2^b) -- b = bits of n rounded up to even, 6-round balanced Feistel whose round function is one
-// Philox block keyed by (seed, update index, round) -- restricted to [0, n) by cycle walking (re-encrypt until the value
-// falls below n: a bijection of the superset walks every element of [0, n) to a distinct element of [0, n)).  No sort, no
-// host round trip; each lane is independent.  Not torch.randperm's stream (parity with rsl_rl's sample order is unpinned).
+// feistel_perm (lg_device.h) keyed by the update index.  Not torch.randperm's stream (parity with rsl_rl's sample order is unpinned).
 __global__ void __launch_bounds__(256) k_randperm(PpoDev P, int n, int half_bits, uint64_t update_idx) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const uint32_t mask = (1u << half_bits) - 1u;
-    uint32_t x = (uint32_t)i;
-    do {
-        uint32_t l = x >> half_bits, r = x & mask;
-#pragma unroll 1
-        for (int round = 0; round < 6; ++round) {
-            uint32_t c[4] = {r, (uint32_t)round, (uint32_t)update_idx, (uint32_t)(update_idx >> 32) ^ 0x9e3779b9u};
-            philox4x32((uint32_t)P.seed, (uint32_t)(P.seed >> 32), c);
-            const uint32_t t = l ^ (c[0] & mask);
-            l = r; r = t;
-        }
-        x = (l << half_bits) | r;
-    } while (x >= (uint32_t)n);
-    P.perm[i] = (int32_t)x;
+    P.perm[i] = (int32_t)feistel_perm(P.seed, update_idx, n, half_bits, (uint32_t)i);
 }
 
 // mini_batch_generator: rows perm[mb*R .. (mb+1)*R) of the (T*N)-flattened storage

@@ -1,0 +1,34 @@
+// Device-side struct of the tube-model trainer (tube_kernels.hip, tube_api.hip).
+#pragma once
+#include "lg_device.h"
+#include "../../include/legged_hip.h"
+
+#define LG_TUBE_ROWS 32                 // rows per workgroup tile of k_tube_rows
+#define LG_TUBE_THREADS 256
+#define LG_TUBE_MAX_LIN 5               // num_layers (<= 4) hidden Linear layers + the output Linear
+
+struct TubeSplit {                      // one side of random_split, device memory owned by the caller
+    const float *x, *y, *v;             // flat: data (rows, in), target (rows, out).  horizon: w (rows, T), z (rows, T, nz), v (rows, T, m)
+    int64_t rows;
+};
+
+struct TubeDev {                        // passed by value to kernels
+    int in_dim, out_dim, units, layers, act, loss, horizon;
+    int H_fwd, H_rev, T, nz, m;         // horizon dataset: padded time length T, z / v widths
+    float alpha, delta, sp_beta;
+    uint64_t seed;
+    int64_t num_params, slab_ld;        // slab row: num_params gradients + the loss sum, padded to slab_ld
+    int64_t off_w[LG_TUBE_MAX_LIN], off_b[LG_TUBE_MAX_LIN];
+    int din[LG_TUBE_MAX_LIN], dout[LG_TUBE_MAX_LIN];
+    float *params, *wt;                 // wt: every weight matrix transposed ([k][j], same offsets), for the forward's coalesced reads
+    float *grads, *adam_m, *adam_v;
+    float *slab;                        // (workgroups, slab_ld) per-workgroup partial gradients of one step
+    float *evpart;                      // (workgroups, 4) per-workgroup partial eval sums
+    float *normpart;                    // per-block sums of g^2 of k_tube_adam
+    uint32_t *done_ctr;                 // k_tube_adam's last-block counter (returns to 0 after every launch)
+    float *log;                         // (log_cap, 4): loss, lr after the step, grad_norm, rows
+    float *eval;                        // 4: loss, fraction fw > w, mean |w - fw| where fw > w, rows
+    int32_t *starts;                    // horizon window start per row of the last step / eval
+    int32_t *perm;
+    int64_t log_cap;
+};

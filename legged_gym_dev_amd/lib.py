@@ -39,6 +39,7 @@ def load():
         _lib = C.CDLL(SO_PATH)
         capi.declare_env_api(_lib, prefix="lg_")
         _declare_ppo(_lib)
+        capi.declare_tube_api(_lib)
     return _lib
 
 

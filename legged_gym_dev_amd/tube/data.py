@@ -1,0 +1,216 @@
+"""Tube-learning datasets (the semantics of deep_tube_learning/datasets.py, built from a local folder instead of wandb).
+
+The input is the folder ``scripts/collect_trajectory_data.py`` writes: ``epoch_<k>.pickle`` files, each a dict of numpy arrays
+z (N, T+1, n), pz_x (N, T+1, n), v (N, T, m) and done (N, T).  Datasets hold host float32 torch tensors; the trainer copies them
+to the device once.
+"""
+import glob
+import os
+import pickle
+import re
+
+import numpy as np
+import torch
+
+
+def _epoch_files(folder):
+    files = glob.glob(os.path.join(folder, "epoch_*.pickle"))
+    key = lambda f: int(re.match(r"epoch_(\d+)\.pickle$", os.path.basename(f)).group(1))
+    return sorted((f for f in files if re.match(r"epoch_\d+\.pickle$", os.path.basename(f))), key=key)
+
+
+def construct_dataset(folder):
+    """Concatenate the epochs of `folder` on axis 0 (in numeric epoch order) and add the one-step-ahead arrays.
+
+    Returns a dict with z, pz_x (E*N, T+1, n), v (E*N, T, m), z_p1 = z[:, 1:], pz_x_p1 = pz_x[:, 1:] and done (E*N, T).
+
+    Every epoch's ``done[-1, :]`` is set before concatenating, as the reference does.  On this (env, time) layout that marks
+    every step of the *last env* of each epoch as done (so its rows are all dropped by the row datasets), not the last step of
+    every env.  Nothing is cached on disk.
+    """
+    files = _epoch_files(folder)
+    if not files:
+        raise FileNotFoundError(f"no epoch_<k>.pickle files in {folder}")
+    parts = {k: [] for k in ("z", "pz_x", "v", "done")}
+    for f in files:
+        with open(f, "rb") as fh:
+            rec = pickle.load(fh)
+        done = np.array(rec["done"], copy=True)
+        done[-1, :] = True
+        parts["done"].append(done)
+        for k in ("z", "pz_x", "v"):
+            parts[k].append(rec[k])
+    out = {k: np.concatenate(v, axis=0) for k, v in parts.items()}
+    out["z_p1"] = out["z"][:, 1:, :].copy()
+    out["pz_x_p1"] = out["pz_x"][:, 1:, :].copy()
+    return out
+
+
+def get_slice(data, i, dN, m):
+    """data (E, T, c) delayed by i * dN steps with stride dN: entry t holds data[:, t - i*dN - k*dN] for the k that keeps the
+    steps aligned to the end of the window; the front that has no such step is filled with the first sample, whose last m
+    (input) columns are zeroed."""
+    T = data.shape[-2]
+    steps = np.arange(T - 1 - i * dN, -1, -dN)[::-1]
+    first = data[:, :1, :].copy()
+    first[:, :, -m:] = 0
+    return np.concatenate((np.repeat(first, T - steps.size, axis=-2), data[:, steps, :]), axis=-2)
+
+
+def sliding_window(data, N, dN, m):
+    """The N delayed copies of get_slice side by side on the last axis (delay 0 first)."""
+    return np.concatenate([get_slice(data, i, dN, m) for i in range(N)], axis=-1)
+
+
+def _load(src):
+    return construct_dataset(src) if isinstance(src, (str, os.PathLike)) else src
+
+
+class TubeDataset:
+    """Rows of (data, target): float32 torch tensors (rows, input_dim), (rows, output_dim)."""
+
+    def __init__(self, data, target, input_dim, output_dim):
+        self.data, self.target = data, target
+        self.input_dim, self.output_dim = input_dim, output_dim
+
+    def __len__(self):
+        return self.data.shape[0]
+
+    def __getitem__(self, idx):
+        return self.data[idx, :], self.target[idx, :]
+
+    def update(self):
+        pass
+
+    def random_split(self, p):
+        """Train part: one contiguous piece of int(len * p) rows starting at np.random.randint(len - that); test: the rest."""
+        n = int(len(self) * p)
+        s = np.random.randint(len(self) - n)
+        cut = lambda t: (t[s:s + n], torch.vstack((t[:s], t[s + n:])))
+        (d1, d2), (t1, t2) = cut(self.data), cut(self.target)
+        return (type(self)(d1, t1, self.input_dim, self.output_dim), type(self)(d2, t2, self.input_dim, self.output_dim))
+
+    @staticmethod
+    def _rows(data, target, done):
+        flat = data.reshape((-1, data.shape[-1]))
+        tgt = target.reshape((flat.shape[0], -1))
+        keep = np.logical_not(done.reshape(-1))
+        return torch.from_numpy(flat[keep]).float(), torch.from_numpy(tgt[keep]).float()
+
+
+class ScalarTubeDataset(TubeDataset):
+    """Input: the tracking error norm w_t = |pz_x - z| and the non-position ROM state and input, over a window of N samples
+    dN apart (recursive: the window covers w too); target w_{t+1}."""
+
+    @classmethod
+    def from_folder(cls, src, N=1, dN=1, recursive=False):
+        ds = _load(src)
+        z, pz_x, v = ds["z"][:, :-1, :], ds["pz_x"][:, :-1, :], ds["v"]
+        w = np.linalg.norm(pz_x - z, axis=-1)
+        w_p1 = np.linalg.norm(ds["pz_x_p1"] - ds["z_p1"], axis=-1)
+        m = v.shape[-1]
+        if recursive:
+            data = sliding_window(np.concatenate((w[:, :, None], z[:, :, 2:], v), axis=-1), N, dN, m)
+        else:
+            data = np.concatenate((w[:, :, None], sliding_window(np.concatenate((z[:, :, 2:], v), axis=-1), N, dN, m)), axis=-1)
+        x, y = cls._rows(data, w_p1, ds["done"])
+        return cls(x, y, x.shape[1], 1)
+
+
+class VectorTubeDataset(TubeDataset):
+    """Input: |pz_x - z| per axis, z and v over the window; target |pz_x - z| per axis one step ahead."""
+
+    @classmethod
+    def from_folder(cls, src, N=1, dN=1):
+        ds = _load(src)
+        z, pz_x, v = ds["z"][:, :-1, :], ds["pz_x"][:, :-1, :], ds["v"]
+        data = sliding_window(np.concatenate((np.abs(pz_x - z), z, v), axis=-1), N, dN, v.shape[-1])
+        x, y = cls._rows(data, np.abs(ds["pz_x_p1"] - ds["z_p1"]), ds["done"])
+        return cls(x, y, x.shape[1], y.shape[1])
+
+
+class ErrorDynamicsDataset(TubeDataset):
+    """Input: the signed error pz_x - z, z and v over the window; target the signed error one step ahead."""
+
+    @classmethod
+    def from_folder(cls, src, N=1, dN=1):
+        ds = _load(src)
+        z, pz_x, v = ds["z"][:, :-1, :], ds["pz_x"][:, :-1, :], ds["v"]
+        data = sliding_window(np.concatenate((pz_x - z, z, v), axis=-1), N, dN, v.shape[-1])
+        x, y = cls._rows(data, ds["pz_x_p1"] - ds["z_p1"], ds["done"])
+        return cls(x, y, x.shape[1], y.shape[1])
+
+
+class ScalarHorizonTubeDataset:
+    """Per env: the error norm w, the non-position ROM state z and the input v over time, padded in front by H_rev steps
+    (w and z with their first sample, v with zeros).  Item (env, ind) -- ind drawn uniformly from [H_rev, T' - H_fwd - 1) -- is
+    input [w[ind-H_rev:ind], z[ind], v[ind-H_rev:ind+H_fwd].flatten()] and target w[ind+1:ind+H_fwd+1].  As in the reference,
+    the input does not hold the current error w[ind]."""
+
+    def __init__(self, w, z, v, H_fwd, H_rev, input_dim, output_dim):
+        self.w, self.z, self.v = w, z, v
+        self.H_fwd, self.H_rev = H_fwd, H_rev
+        self.input_dim, self.output_dim = input_dim, output_dim
+
+    @classmethod
+    def from_folder(cls, src, H_fwd=50, H_rev=10):
+        ds = _load(src)
+        z, pz_x, v = ds["z"][:, :-1, :], ds["pz_x"][:, :-1, :], ds["v"]
+        v = np.concatenate((np.zeros((v.shape[0], H_rev, v.shape[2])), v), axis=1)
+        z = np.concatenate((np.repeat(z[:, None, 0, :], H_rev, axis=1), z), axis=1)
+        pz_x = np.concatenate((np.repeat(pz_x[:, None, 0, :], H_rev, axis=1), pz_x), axis=1)
+        w = np.linalg.norm(pz_x - z, axis=-1)
+        z_no_pos = z[:, :, 2:]
+        input_dim = H_rev + z_no_pos.shape[-1] + (H_rev + H_fwd) * v.shape[-1]
+        return cls(torch.from_numpy(w).float(), torch.from_numpy(z_no_pos).float(), torch.from_numpy(v).float(),
+                   H_fwd, H_rev, input_dim, H_fwd)
+
+    def __len__(self):
+        return self.w.shape[0]
+
+    def __getitem__(self, idx):
+        ind = int(torch.randint(self.H_rev, self.w.shape[1] - self.H_fwd - 1, (1,)))
+        return self._get_item_helper(idx, ind)
+
+    def _get_item_helper(self, idx, ind):
+        Hr, Hf = self.H_rev, self.H_fwd
+        x = torch.cat((self.w[idx, ind - Hr:ind], self.z[idx, ind, :], self.v[idx, ind - Hr:ind + Hf].reshape((-1,))))
+        return x, self.w[idx, ind + 1:ind + Hf + 1]
+
+    def update(self):
+        pass
+
+    def random_split(self, p):
+        """As TubeDataset.random_split, over envs."""
+        n = int(len(self) * p)
+        s = np.random.randint(len(self) - n)
+        cut = lambda t: (t[s:s + n], torch.vstack((t[:s], t[s + n:])))
+        (w1, w2), (z1, z2), (v1, v2) = cut(self.w), cut(self.z), cut(self.v)
+        mk = lambda w, z, v: type(self)(w, z, v, self.H_fwd, self.H_rev, self.input_dim, self.output_dim)
+        return mk(w1, z1, v1), mk(w2, z2, v2)
+
+
+_ALPHA_REASON = ("is not supported: in the reference, alpha = data[:, -1] has shape (B,) while the residual has shape (B, 1), so "
+                 "torch.where broadcasts the loss to B x B; no configuration uses it")
+
+
+class AlphaScalarTubeDataset(TubeDataset):
+    def __init__(self, *a, **k):
+        raise NotImplementedError("AlphaScalarTubeDataset " + _ALPHA_REASON)
+
+    @classmethod
+    def from_folder(cls, *a, **k):
+        raise NotImplementedError("AlphaScalarTubeDataset " + _ALPHA_REASON)
+
+
+class AlphaVectorTubeDataset(TubeDataset):
+    def __init__(self, *a, **k):
+        raise NotImplementedError("AlphaVectorTubeDataset " + _ALPHA_REASON)
+
+    @classmethod
+    def from_folder(cls, *a, **k):
+        raise NotImplementedError("AlphaVectorTubeDataset " + _ALPHA_REASON)
+
+
+DATASETS = {"scalar": ScalarTubeDataset, "vector": VectorTubeDataset, "error_dynamics": ErrorDynamicsDataset,
+            "scalar_horizon": ScalarHorizonTubeDataset}

@@ -1,0 +1,206 @@
+"""HipTubeTrainer: the reference tube MLP trained by the HIP kernels of tube_kernels.hip (lg_tube_* in include/legged_hip.h).
+
+A step is two launches on the current stream -- fused forward / loss / backward over the minibatch, then the fixed-order gradient
+reduction, Adam and StepLR -- and nothing in it waits for the device.  Loss, lr and gradient norm of every step stay in a device
+log until ``read_log``.  There is no CPU fallback: without the library or a GPU the constructor raises.
+"""
+import ctypes as C
+from collections import OrderedDict
+
+import torch
+
+from .. import capi
+from ..lib import LeggedHipError, device_tensor, load
+
+ACTIVATIONS = tuple(capi.TUBE_ACT)
+LOSSES = {"scalar": "scalar", "scalar_horizon": "scalar", "vector": "vector", "error": "mse"}   # reference loss -> kernel loss
+
+
+def check_envelope(input_dim, output_dim, num_units, num_layers, activation="relu", final_activation=None):
+    """The supported model envelope (the C side refuses the same); raises ValueError / NotImplementedError outside it."""
+    if final_activation is not None:
+        raise NotImplementedError("final_activation other than None is not supported (no reference configuration uses one)")
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation {activation!r}: one of {ACTIVATIONS}")
+    if not (16 <= num_units <= capi.TUBE_MAX_UNITS and num_units % 16 == 0):
+        raise ValueError(f"num_units={num_units}: 16..{capi.TUBE_MAX_UNITS} in steps of 16")
+    if not 1 <= num_layers <= 4:
+        raise ValueError(f"num_layers={num_layers}: 1..4")
+    if not 1 <= input_dim <= capi.TUBE_MAX_IN:
+        raise ValueError(f"input_dim={input_dim}: 1..{capi.TUBE_MAX_IN}")
+    if not 1 <= output_dim <= capi.TUBE_MAX_OUT:
+        raise ValueError(f"output_dim={output_dim}: 1..{capi.TUBE_MAX_OUT}")
+
+
+def param_shapes(input_dim, output_dim, num_units, num_layers):
+    """[(state-dict key, shape)] of the reference MLP: Linear layers at the even indices of `layers`."""
+    dims = [input_dim] + [num_units] * num_layers + [output_dim]
+    out = []
+    for i in range(num_layers + 1):
+        out += [(f"layers.{2 * i}.weight", (dims[i + 1], dims[i])), (f"layers.{2 * i}.bias", (dims[i + 1],))]
+    return out
+
+
+def initial_params(input_dim, output_dim, num_units, num_layers, seed):
+    """nn.Linear's default initialisation, drawn in the reference MLP's construction order after torch.manual_seed(seed)."""
+    torch.manual_seed(seed)
+    dims = [input_dim] + [num_units] * num_layers + [output_dim]
+    sd = OrderedDict()
+    for i in range(num_layers + 1):
+        lin = torch.nn.Linear(dims[i], dims[i + 1])
+        sd[f"layers.{2 * i}.weight"] = lin.weight.detach().clone()
+        sd[f"layers.{2 * i}.bias"] = lin.bias.detach().clone()
+    return sd
+
+
+class HipTubeTrainer:
+    def __init__(self, input_dim, output_dim, num_units=32, num_layers=2, activation="relu", softplus_beta=1.0,
+                 loss="scalar", alpha=0.8, delta=1.0, lr=1e-3, gamma=0.1, step_size=10000, batch_size=2048, seed=42,
+                 horizon=None, final_activation=None, device="cuda:0"):
+        """horizon: None for the row datasets, (H_fwd, H_rev) for ScalarHorizonTubeDataset."""
+        check_envelope(input_dim, output_dim, num_units, num_layers, activation, final_activation)
+        if loss not in LOSSES:
+            raise ValueError(f"loss {loss!r}: one of {tuple(LOSSES)}")
+        if loss in ("scalar", "scalar_horizon", "vector") and alpha is None:
+            raise ValueError(f"loss {loss!r} needs alpha")
+        self.device = torch.device(device)
+        if self.device.type != "cuda" or not torch.cuda.is_available():
+            raise LeggedHipError("the tube trainer needs a GPU device (no CPU fallback); got " + str(device))
+        self.lib = load()
+        self.dims = (input_dim, output_dim, num_units, num_layers)
+        self.activation, self.softplus_beta, self.loss = activation, softplus_beta, loss
+        self.horizon = horizon
+        cfg = capi.lg_tube_cfg(input_dim=input_dim, output_dim=output_dim, num_units=num_units, num_layers=num_layers,
+                               activation=capi.TUBE_ACT[activation], loss=capi.TUBE_LOSS[LOSSES[loss]],
+                               horizon=int(horizon is not None), batch_size=batch_size,
+                               H_fwd=horizon[0] if horizon else 0, H_rev=horizon[1] if horizon else 0, step_size=step_size,
+                               seed=seed, alpha=alpha if alpha is not None else 0.0, delta=delta, softplus_beta=softplus_beta,
+                               lr=lr, gamma=gamma)
+        self.batch_size = batch_size
+        torch.cuda.set_device(self.device)
+        self.h = C.c_void_p()
+        self._call("create", C.byref(cfg), C.byref(self.h), obj=False)
+        self.use_current_stream()
+        self._views()
+        self.load_state_dict(initial_params(input_dim, output_dim, num_units, num_layers, seed))
+        self._data = {}
+
+    # ---------------------------------------------------------------- plumbing
+    def _call(self, fn, *args, obj=True):
+        rc = getattr(self.lib, "lg_tube_" + fn)(*((self.h,) if obj else ()), *args)
+        if rc != 0:
+            raise LeggedHipError(f"lg_tube_{fn} failed ({rc}): {self.lib.lg_last_error().decode()}")
+
+    def use_current_stream(self):
+        self._call("set_stream", C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+
+    def _views(self):
+        b = capi.lg_tube_buffers()
+        self._call("get_buffers", C.byref(b))
+        ptr = lambda p: C.cast(p, C.c_void_p).value
+        P = int(b.num_params)
+        self.num_params, self.log_cap = P, int(b.log_cap)
+        self.params = device_tensor(ptr(b.params), (P,), "f4", self, self.device)
+        self.grads = device_tensor(ptr(b.grads), (P,), "f4", self, self.device)
+        self.adam_m = device_tensor(ptr(b.adam_m), (P,), "f4", self, self.device)
+        self.adam_v = device_tensor(ptr(b.adam_v), (P,), "f4", self, self.device)
+        self.log = device_tensor(ptr(b.log), (self.log_cap, 4), "f4", self, self.device)
+        self.eval_buf = device_tensor(ptr(b.eval), (4,), "f4", self, self.device)
+        self.starts = device_tensor(ptr(b.starts), (int(b.starts_cap),), "i4", self, self.device) if b.starts_cap else None
+        self.perm = device_tensor(ptr(b.perm), (int(b.perm_cap),), "i4", self, self.device) if b.perm_cap else None
+        self.step_count = int(b.step)
+        offs, shp = (C.c_int64 * 16)(), (C.c_int64 * 32)()
+        n = self.lib.lg_tube_param_layout(self.h, offs, shp, 16)
+        self.layout = []
+        for (key, shape), i in zip(param_shapes(*self.dims), range(n)):
+            o = int(offs[i])
+            self.layout.append((key, o, shape))
+
+    # ---------------------------------------------------------------- model state
+    def state_dict(self):
+        """The reference MLP's keys (layers.{0,2,4,...}.weight / .bias); loads into deep_tube_learning.models.MLP."""
+        return OrderedDict((k, self.params[o:o + _numel(s)].view(s).detach().clone()) for k, o, s in self.layout)
+
+    def load_state_dict(self, sd):
+        want = [k for k, _, _ in self.layout]
+        if list(sd.keys()) != want:
+            raise KeyError(f"state dict keys {list(sd.keys())} != {want}")
+        for k, o, s in self.layout:
+            if tuple(sd[k].shape) != tuple(s):
+                raise ValueError(f"{k}: shape {tuple(sd[k].shape)} != {tuple(s)}")
+            self.params[o:o + _numel(s)].copy_(sd[k].reshape(-1).to(self.device, torch.float32))
+        self._call("params_changed")
+
+    # ---------------------------------------------------------------- data
+    def set_data(self, train, test=None):
+        """train / test: TubeDataset-like (data, target) or ScalarHorizonTubeDataset-like (w, z, v)."""
+        for which, ds in ((0, train), (1, test)):
+            if ds is None:
+                continue
+            if self.horizon is not None:
+                w, z, v = (t.to(self.device, torch.float32).contiguous() for t in (ds.w, ds.z, ds.v))
+                if (ds.H_fwd, ds.H_rev) != tuple(self.horizon):
+                    raise ValueError("dataset horizon != trainer horizon")
+                self._data[which] = (w, z, v)
+                self._call("set_data", which, C.c_void_p(w.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(v.data_ptr()),
+                           w.shape[0], w.shape[1], z.shape[2], v.shape[2])
+            else:
+                x, y = (t.to(self.device, torch.float32).contiguous() for t in (ds.data, ds.target))
+                if x.shape[1] != self.dims[0] or y.shape[1] != self.dims[1]:
+                    raise ValueError(f"dataset dims {(x.shape[1], y.shape[1])} != model dims {self.dims[:2]}")
+                self._data[which] = (x, y)
+                self._call("set_data", which, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), None, x.shape[0], 0, 0, 0)
+        self._views()
+
+    def n_train(self):
+        return int(self._data[0][0].shape[0])
+
+    # ---------------------------------------------------------------- training
+    def begin_epoch(self, epoch):
+        self._call("begin_epoch", int(epoch))
+
+    def step(self, count=None, rows=None):
+        """One Adam step on the next `count` rows of the epoch permutation, or on `rows` (int32 device tensor)."""
+        if rows is not None:
+            rows = rows.to(self.device, torch.int32).contiguous()
+            self._rows_keep = rows
+            self._call("step", C.c_void_p(rows.data_ptr()), rows.numel())
+        else:
+            self._call("step", None, int(count))
+        self.step_count += 1
+
+    def set_step(self, step):
+        self._call("set_step", int(step))
+        self.step_count = int(step)
+
+    def read_log(self, first, last):
+        """Host copy (rows = steps first..last, 1-based, at most log_cap of them) of [loss, lr after the step, grad_norm, rows]."""
+        if last - first + 1 > self.log_cap:
+            raise ValueError("more steps than the device log holds")
+        idx = torch.arange(first - 1, last, device=self.device) % self.log_cap
+        return self.log[idx].cpu()
+
+    def evaluate(self):
+        """Launches the eval over the test split; returns a device tensor [loss, fraction fw > w, mean |w - fw| where fw > w,
+        rows] (a copy, valid once the stream reaches it)."""
+        self._call("eval")
+        return self.eval_buf.clone()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.params = self.grads = self.adam_m = self.adam_v = self.log = self.eval_buf = self.starts = self.perm = None
+            self.lib.lg_tube_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n
