@@ -497,6 +497,24 @@ int lg_tube_begin_epoch(lg_tube *t, int64_t epoch);   /* a new permutation of th
 int lg_tube_step(lg_tube *t, const int32_t *rows, int64_t count);
 int lg_tube_eval(lg_tube *t);                      /* metrics of the test split into lg_tube_buffers.eval (one window per row) */
 
+/* Inference.  The three entries read params / the transposed copy and change neither; all pointers are device pointers, everything
+ * runs on the handle's stream and nothing waits for the device.  A row's result does not depend on the batch it is in.
+ * Each returns -1 (reason in lg_last_error) for the wrong handle kind, fb out of range, non-positive counts, or nz / m that
+ * disagree with input_dim. */
+/* out[i] = MLP(x[rows ? rows[i] : i]);  x (n, input_dim), out (count, output_dim).  Flat (non-horizon) handles.  The caller
+ * guarantees 0 <= rows[i] < n. */
+int lg_tube_predict(lg_tube *t, const float *x, const int32_t *rows, int64_t count, float *out);
+/* Horizon handles: item (env[i], start[i]) built as ScalarHorizonTubeDataset._get_item_helper does, out (count, H_fwd).
+ * w (n, T), z (n, T, nz), v (n, T, m) padded in front by H_rev as for lg_tube_set_data.
+ * Caller guarantees 0 <= env[i] < n, H_rev <= start[i] and start[i] + H_fwd <= T. */
+int lg_tube_predict_windows(lg_tube *t, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz,
+                            int32_t m, const int32_t *env, const int32_t *start, int64_t count, float *out);
+/* Closed loop over time, one launch.  x (n_seq, T, input_dim): the teacher rows in time order.  out (n_seq, T, output_dim).
+ * out[s, t] = MLP(xt) where xt = x[s, t] with its leading fb columns replaced by out[s, t-1, 0:fb],
+ * except at t == 0 and where reseed[s, t] != 0 (reseed (n_seq, T) may be NULL): there xt = x[s, t] unchanged.
+ * 0 <= fb <= min(input_dim, output_dim).  Flat handles. */
+int lg_tube_rollout(lg_tube *t, const float *x, int64_t n_seq, int32_t T, int32_t fb, const uint8_t *reseed, float *out);
+
 #ifdef __cplusplus
 }
 #endif

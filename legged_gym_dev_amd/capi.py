@@ -224,6 +224,9 @@ def declare_tube_api(lib):
     lib.lg_tube_begin_epoch.argtypes = [vp, i64]
     lib.lg_tube_step.argtypes = [vp, vp, i64]
     lib.lg_tube_eval.argtypes = [vp]
+    lib.lg_tube_predict.argtypes = [vp, vp, vp, i64, vp]
+    lib.lg_tube_predict_windows.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp]
+    lib.lg_tube_rollout.argtypes = [vp, vp, i64, i32, i32, vp, vp]
 
 
 def declare_env_api(lib, prefix="lg_"):

@@ -1,5 +1,6 @@
 // C-ABI (include/legged_hip.h, lg_tube_*) of the tube-model trainer: parameter / optimiser / slab allocation in HBM, epoch
-// permutation, the two launches of a training step and the eval launch (tube_kernels.hip).
+// permutation, the two launches of a training step, the eval launch, and the inference entries: predict, window prediction and
+// the closed-loop roll-out (tube_kernels.hip).
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -19,6 +20,9 @@ void tubek_eval(const TubeDev *D, const TubeSplit *S, const int32_t *rows, uint6
 void tubek_wt(const TubeDev *D, hipStream_t s);
 void tubek_perm(const TubeDev *D, int n, uint64_t epoch, hipStream_t s);
 void tubek_iota(int32_t *p, int64_t n, hipStream_t s);
+void tubek_predict(const TubeDev *D, const float *x, const float *y, const float *v, const int32_t *rows, const int32_t *env,
+                   const int32_t *start, int T, int nz, int m, int64_t count, float *o, hipStream_t s);
+void tubek_rollout(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed, float *o, hipStream_t s);
 }
 
 struct lg_tube {
@@ -210,6 +214,40 @@ int lg_tube_eval(lg_tube *p) {
     const uint64_t key = 0x8000000000000000ull | (uint64_t)p->eval_count++;
     tubek_eval(&p->dev, &S, p->eval_rows, key, loss_norm(p, S.rows), p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_eval: launch failed"), -3);
+}
+
+// ---------------------------------------------------------------- inference: reads params / wt, changes neither
+int lg_tube_predict(lg_tube *p, const float *x, const int32_t *rows, int64_t count, float *out) {
+    if (p->dev.horizon) { lg_set_error("lg_tube_predict: a horizon handle predicts windows (lg_tube_predict_windows)"); return -1; }
+    if (count < 1) { lg_set_error("lg_tube_predict: count must be positive"); return -1; }
+    if (!x || !out) { lg_set_error("lg_tube_predict: missing array"); return -1; }
+    tubek_predict(&p->dev, x, nullptr, nullptr, rows, nullptr, nullptr, 0, 0, 0, count, out, p->stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict: launch failed"), -3);
+}
+
+int lg_tube_predict_windows(lg_tube *p, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz, int32_t m,
+                            const int32_t *env, const int32_t *start, int64_t count, float *out) {
+    const TubeDev &D = p->dev;
+    if (!D.horizon) { lg_set_error("lg_tube_predict_windows: a flat handle predicts rows (lg_tube_predict)"); return -1; }
+    if (count < 1 || n < 1) { lg_set_error("lg_tube_predict_windows: n and count must be positive"); return -1; }
+    if (nz < 0 || m < 0 || D.H_rev + nz + (D.H_rev + D.H_fwd) * m != D.in_dim) {
+        lg_set_error("lg_tube_predict_windows: input_dim != H_rev + nz + (H_rev + H_fwd) * m"); return -1;
+    }
+    if (T < D.H_rev + D.H_fwd) { lg_set_error("lg_tube_predict_windows: T is shorter than H_rev + H_fwd"); return -1; }
+    if (!w || (nz && !z) || (m && !v) || !env || !start || !out) { lg_set_error("lg_tube_predict_windows: missing array"); return -1; }
+    tubek_predict(&p->dev, w, z, v, nullptr, env, start, T, nz, m, count, out, p->stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict_windows: launch failed"), -3);
+}
+
+int lg_tube_rollout(lg_tube *p, const float *x, int64_t n_seq, int32_t T, int32_t fb, const uint8_t *reseed, float *out) {
+    const TubeDev &D = p->dev;
+    if (D.horizon) { lg_set_error("lg_tube_rollout: a horizon handle has no closed loop (lg_tube_predict_windows)"); return -1; }
+    if (n_seq < 1 || T < 1) { lg_set_error("lg_tube_rollout: n_seq and T must be positive"); return -1; }
+    if (n_seq > INT32_MAX / 16) { lg_set_error("lg_tube_rollout: n_seq must be below 2^27"); return -1; }
+    if (fb < 0 || fb > D.in_dim || fb > D.out_dim) { lg_set_error("lg_tube_rollout: fb must be 0..min(input_dim, output_dim)"); return -1; }
+    if (!x || !out) { lg_set_error("lg_tube_rollout: missing array"); return -1; }
+    tubek_rollout(&p->dev, x, n_seq, T, fb, reseed, out, p->stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_rollout: launch failed"), -3);
 }
 
 }  // extern "C"

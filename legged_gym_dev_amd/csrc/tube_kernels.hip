@@ -325,7 +325,189 @@ __global__ void k_tube_iota(int32_t *p, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = (int32_t)i;
 }
 
+// ------------------------------------------------------------------ inference: predict and the closed-loop roll-out
+// One Linear layer of a tile of RT rows, shared by k_tube_predict and every k_tube_rollout shape.  Each output is the same chain
+// as in k_tube_rows -- acc = 0, fmaf over k = 0..K-1 in order, + bias, activation -- whatever RT, RB or the weights' address
+// space, so a row's result does not depend on the tile it sits in.  w: the layer's transposed weights [k][j]; b: its bias.
+// Hidden layers write the activated output to `out` (LDS, (RT, N)); the LAST one writes the raw output to `out` (LDS, may be
+// null) and to g[r * gld + j] for the rows r < nr.
+template <int RT, int RB_, int NT_, bool LAST>
+__device__ __forceinline__ void tube_layer(int tid, int K, int N, const float *in, const float *w, const float *b, int act, float beta,
+                                           float *out, float *g, int64_t gld, int nr) {
+    for (int e = tid; e < N * (RT / RB_); e += NT_) {
+        const int j = e % N, r0 = (e / N) * RB_;
+        float acc[RB_];
+#pragma unroll
+        for (int q = 0; q < RB_; ++q) acc[q] = 0.f;
+#pragma unroll 8                        // eight operand loads in flight per wait: a lone wave per SIMD has nothing else to hide LDS latency behind
+        for (int k = 0; k < K; ++k) {
+            const float wv = w[k * N + j];
+#pragma unroll
+            for (int q = 0; q < RB_; ++q) acc[q] = fmaf(in[(r0 + q) * K + k], wv, acc[q]);
+        }
+        const float bj = b[j];
+#pragma unroll
+        for (int q = 0; q < RB_; ++q) {
+            const float z = acc[q] + bj;
+            if (LAST) {
+                if (out) out[(r0 + q) * N + j] = z;
+                if (r0 + q < nr) g[(int64_t)(r0 + q) * gld + j] = z;
+            } else {
+                out[(r0 + q) * N + j] = tube_act(act, z, beta);
+            }
+        }
+    }
+}
+
+// out[i] = MLP(item i).  Flat: item i = x[rows ? rows[i] : i].  Horizon: the ScalarHorizonTubeDataset item at (env[i], start[i])
+// of the arrays in G (the caller guarantees H_rev <= start and start + H_fwd <= T).  No loss, no slab; weights through wt.
+struct TubeGather {
+    const float *x, *y, *v;             // flat: x (n, in).  horizon: w (n, T), z (n, T, nz), v (n, T, m)
+    const int32_t *rows, *env, *start;
+    int T, nz, m;
+};
+
+__global__ void __launch_bounds__(NT) k_tube_predict(TubeDev D, TubeGather G, int64_t count, float *o) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, I = D.in_dim, O = D.out_dim, U = D.units, L = D.layers;
+    const int64_t base = (int64_t)blockIdx.x * R;
+    const int nr = (int)(count - base < R ? count - base : R);
+    float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U;
+    for (int e = tid; e < R * I; e += NT) {
+        const int r = e / I, c = e - r * I;
+        float x = 0.f;
+        if (r < nr) {
+            if (!D.horizon) {
+                const int64_t s = G.rows ? (int64_t)G.rows[base + r] : base + r;
+                x = G.x[s * I + c];
+            } else {
+                const int64_t s = G.env[base + r];
+                const int t0 = G.start[base + r];
+                if (c < D.H_rev) x = G.x[s * G.T + t0 - D.H_rev + c];
+                else if (c < D.H_rev + G.nz) x = G.y[(s * G.T + t0) * G.nz + (c - D.H_rev)];
+                else {
+                    const int q = c - D.H_rev - G.nz, tt = q / G.m;
+                    x = G.v[(s * G.T + t0 - D.H_rev + tt) * G.m + (q - tt * G.m)];
+                }
+            }
+        }
+        X[e] = x;
+    }
+    __syncthreads();
+    const float *in = X;
+    for (int li = 0; li < L; ++li) {
+        float *out = li & 1 ? H1 : H0;
+        tube_layer<R, RB, NT, false>(tid, D.din[li], U, in, D.wt + D.off_w[li], D.params + D.off_b[li], D.act, D.sp_beta, out, nullptr, 0, 0);
+        __syncthreads();
+        in = out;
+    }
+    tube_layer<R, RB, NT, true>(tid, D.din[L], O, in, D.wt + D.off_w[L], D.params + D.off_b[L], D.act, D.sp_beta, nullptr, o + base * O, O, nr);
+}
+
+// Closed loop over time: a workgroup owns RT sequences and walks t = 0..T-1 itself; the carried output of the tile stays in LDS.
+// Step t: X = x[s, t] with its leading fb columns replaced by the previous output unless t == 0 or reseed[s, t]; forward; store.
+// The teacher row and the reseed flag of step t + 1 are loaded into registers before step t's layers run, so their latency
+// hides behind the chain.  WLDS: the transposed weights and the biases are staged to LDS once (params' own offsets).
+#define TUBE_RO_PRE 16                  // teacher elements a thread holds for the next step: RT * LG_TUBE_MAX_IN / NT_ at most
+template <int RT, int NT_, bool WLDS>
+__global__ void __launch_bounds__(NT_) k_tube_rollout(TubeDev D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed,
+                                                      float *o) {
+    constexpr int RB_ = RT < 4 ? RT : 4;
+    static_assert(RT * LG_TUBE_MAX_IN <= TUBE_RO_PRE * NT_ && RT <= NT_, "tile shape");
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, I = D.in_dim, O = D.out_dim, U = D.units, L = D.layers;
+    const int64_t base = (int64_t)blockIdx.x * RT;
+    const int nr = (int)(n_seq - base < RT ? n_seq - base : RT);
+    float *W = lds;
+    float *X = W + (WLDS ? D.num_params : 0), *H0 = X + RT * I, *H1 = H0 + RT * U, *F = H1 + RT * U;
+    int *fresh = (int *)(F + RT * O);   // (RT) 1: the row takes the teacher's columns this step
+    if (WLDS) {
+        for (int64_t p = tid; p < D.num_params; p += NT_) W[p] = D.wt[p];
+        __syncthreads();
+        for (int li = 0; li <= L; ++li)
+            for (int j = tid; j < D.dout[li]; j += NT_) W[D.off_b[li] + j] = D.params[D.off_b[li] + j];
+    }
+    const float *wsrc = WLDS ? W : D.wt, *bsrc = WLDS ? W : D.params;
+    const int nq = (RT * I + NT_ - 1) / NT_;
+    // element e = tid + q NT_ of the (RT, I) tile: its offset in x at t = 0 and, for a fed-back column, row * 64 + column (else -1).
+    // Elements past the tile repeat its last one and rows past the batch read sequence n_seq - 1; neither is stored.
+    int64_t poff[TUBE_RO_PRE];
+    int pfb[TUBE_RO_PRE];
+    float pre[TUBE_RO_PRE];
+    int pfresh = 1;
+#pragma unroll
+    for (int q = 0; q < TUBE_RO_PRE; ++q) {
+        int e = tid + q * NT_;
+        const bool live = e < RT * I;
+        e = live ? e : RT * I - 1;
+        const int r = e / I, c = e - r * I;
+        poff[q] = (r < nr ? base + r : n_seq - 1) * T * I + c;
+        pfb[q] = live ? (c < fb ? r * 64 + c : -1) : -2;
+    }
+    auto fetch = [&](int t) {
+#pragma unroll
+        for (int q = 0; q < TUBE_RO_PRE; ++q)
+            if (q < nq) pre[q] = x[poff[q] + (int64_t)t * I];
+        if (tid < RT) pfresh = reseed && tid < nr && reseed[(base + tid) * T + t];
+    };
+    fetch(0);
+    if (tid < RT) fresh[tid] = 1;
+    __syncthreads();
+    for (int t = 0; t < T; ++t) {
+#pragma unroll
+        for (int q = 0; q < TUBE_RO_PRE; ++q) {
+            if (q < nq && pfb[q] != -2) {
+                const int fbi = pfb[q];
+                X[tid + q * NT_] = fbi >= 0 && !fresh[fbi >> 6] ? F[(fbi >> 6) * O + (fbi & 63)] : pre[q];
+            }
+        }
+        if (t + 1 < T) fetch(t + 1);
+        __syncthreads();
+        const float *in = X;
+        for (int li = 0; li < L; ++li) {
+            float *out = li & 1 ? H1 : H0;
+            tube_layer<RT, RB_, NT_, false>(tid, D.din[li], U, in, wsrc + D.off_w[li], bsrc + D.off_b[li], D.act, D.sp_beta, out, nullptr, 0, 0);
+            __syncthreads();
+            in = out;
+        }
+        tube_layer<RT, RB_, NT_, true>(tid, D.din[L], O, in, wsrc + D.off_w[L], bsrc + D.off_b[L], D.act, D.sp_beta, F,
+                                       o + (base * T + t) * O, (int64_t)T * O, nr);
+        if (tid < RT) fresh[tid] = pfresh;
+        __syncthreads();
+    }
+}
+
+// LDS of a roll-out tile in floats, without the weights
+static size_t tubek_rollout_acts(const TubeDev *D, int rt) { return (size_t)rt * (D->in_dim + 2 * D->units + D->out_dim + 1); }
+// rows per workgroup from the batch: the smallest tile that keeps the launch within about two workgroups per CU of the chip's 256
+static int tubek_rollout_tile(int64_t n_seq) { return n_seq <= 256 ? 1 : n_seq <= 2048 ? 4 : 16; }
+// weights go to LDS where weights + tile fit LG_TUBE_ROLLOUT_LDS
+static int tubek_rollout_wlds(const TubeDev *D, int rt) { return sizeof(float) * (D->num_params + tubek_rollout_acts(D, rt)) <= LG_TUBE_ROLLOUT_LDS; }
+
+template <int RT, int NT_>
+static void rollout_launch(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed, float *o, hipStream_t s) {
+    const int nwg = (int)((n_seq + RT - 1) / RT);
+    const bool wl = tubek_rollout_wlds(D, RT);
+    const size_t bytes = sizeof(float) * (tubek_rollout_acts(D, RT) + (wl ? D->num_params : 0));
+    if (wl) hipLaunchKernelGGL((k_tube_rollout<RT, NT_, true>), dim3(nwg), dim3(NT_), bytes, s, *D, x, n_seq, T, fb, reseed, o);
+    else hipLaunchKernelGGL((k_tube_rollout<RT, NT_, false>), dim3(nwg), dim3(NT_), bytes, s, *D, x, n_seq, T, fb, reseed, o);
+}
+
 extern "C" {
+void tubek_rollout(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed, float *o, hipStream_t s) {
+    switch (tubek_rollout_tile(n_seq)) {
+    case 1: rollout_launch<1, 64>(D, x, n_seq, T, fb, reseed, o, s); break;
+    case 4: rollout_launch<4, 64>(D, x, n_seq, T, fb, reseed, o, s); break;
+    default: rollout_launch<16, 256>(D, x, n_seq, T, fb, reseed, o, s); break;
+    }
+}
+void tubek_predict(const TubeDev *D, const float *x, const float *y, const float *v, const int32_t *rows, const int32_t *env,
+                   const int32_t *start, int T, int nz, int m, int64_t count, float *o, hipStream_t s) {
+    const TubeGather G{x, y, v, rows, env, start, T, nz, m};
+    const size_t bytes = sizeof(float) * (size_t)R * (D->in_dim + 2 * D->units);
+    hipLaunchKernelGGL(k_tube_predict, dim3((unsigned)((count + R - 1) / R)), dim3(NT), bytes, s, *D, G, count, o);
+}
+
 size_t tubek_lds_bytes(const TubeDev *D) {
     return sizeof(float) * (size_t)R * (D->in_dim + D->layers * D->units + 2 * D->out_dim + 2 * D->units);
 }
@@ -333,6 +515,12 @@ int tubek_init() {
     const int lim = (int)(sizeof(float) * R * (LG_TUBE_MAX_IN + 4 * LG_TUBE_MAX_UNITS + 2 * LG_TUBE_MAX_OUT + 2 * LG_TUBE_MAX_UNITS));
     if (hipFuncSetAttribute((const void *)k_tube_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
     if (hipFuncSetAttribute((const void *)k_tube_rows<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
+    const int plim = (int)(sizeof(float) * R * (LG_TUBE_MAX_IN + 2 * LG_TUBE_MAX_UNITS));
+    if (hipFuncSetAttribute((const void *)k_tube_predict, hipFuncAttributeMaxDynamicSharedMemorySize, plim) != hipSuccess) return -1;
+    for (const void *f : {(const void *)k_tube_rollout<1, 64, true>, (const void *)k_tube_rollout<1, 64, false>,
+                          (const void *)k_tube_rollout<4, 64, true>, (const void *)k_tube_rollout<4, 64, false>,
+                          (const void *)k_tube_rollout<16, 256, true>, (const void *)k_tube_rollout<16, 256, false>})
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
     return 0;
 }
 void tubek_step(const TubeDev *D, const TubeSplit *S, const int32_t *rows, int64_t count, uint64_t key, float norm, hipStream_t s) {

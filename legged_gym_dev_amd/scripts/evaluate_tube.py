@@ -1,0 +1,179 @@
+"""Evaluate a trained tube model on recorded ROM tracking data: the numerical content of the reference's
+deep_tube_learning/evaluation/evaluate_tube.py, evaluate_error_dyn.py and evaluate_tube_oneshot.py on the HIP kernels, without
+wandb or hydra and on recorded data instead of a fresh simulation.
+
+    python legged_gym_dev_amd/scripts/evaluate_tube.py --run tube_runs/run0 --data rom_tracking_data/run1 \\
+        [--checkpoint best|latest] [--horizon K] [--window_stride S] [--plot] [--out DIR]
+
+The run's config.json (train_tube.py writes it) says how the model and its inputs are built; for a run without one, give
+--dataset, --activation and the other train_tube.py flags here (a flag given here replaces the file's value).
+
+Flat datasets (scalar, vector, error_dynamics): the one-step prediction fw_single = model(data) on every row, and the closed-loop
+roll-out fw[t+1] = model([fw[t], rest of row t]) -- one launch for all envs and steps -- reseeded from the data at t = 0, after
+every done and, with --horizon K, every K steps.  scalar_horizon: the one-shot prediction at the window starts H_rev, H_rev + S,
+... of every env, scored overall and per step ahead.  Writes eval.json to --out (default: the run folder) and prints the
+reference's "Total Success Rate" (and, for error_dynamics, "Mean Error" / "Mean One Step Error") lines.
+
+Deliberate deviations from the reference scripts:
+  * evaluate_tube.py:53 feeds the full z[t] to a model that ScalarTubeDataset trained on z[:, 2:] (the input widths differ).  The
+    rows here are the dataset's own (tube/data.py sequences()): what the model was trained on.
+  * evaluate_tube_oneshot.py:111 divides a sum over 100 windows by n_robots = 2.  The success rate here is a mean over the windows.
+  * The scripts score one robot and prepend the initial value to the prediction; here every env is scored, prediction t against
+    the dataset's target t (the quantity at t + 1), and done rows are left out.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import torch  # noqa: E402
+
+from legged_gym_dev_amd.tube import evaluate as ev  # noqa: E402
+from legged_gym_dev_amd.tube.data import DATASETS, construct_dataset, feedback_width, sequences  # noqa: E402
+from legged_gym_dev_amd.tube.model import CONFIG_NAME, HipTubeModel, read_config  # noqa: E402
+
+DEFAULTS = {"N": 1, "dN": 1, "recursive": False, "H_fwd": 50, "H_rev": 10, "softplus_beta": 1.0}
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--run", required=True, help="folder train_tube.py wrote (model.pth, model_best.pth, config.json)")
+    ap.add_argument("--data", required=True, help="folder of epoch_<k>.pickle files")
+    ap.add_argument("--checkpoint", choices=["best", "latest"], default="best")
+    ap.add_argument("--horizon", type=int, default=None, help="flat datasets: reseed the roll-out every K steps")
+    ap.add_argument("--window_stride", type=int, default=1, help="scalar_horizon: distance between window starts")
+    ap.add_argument("--plot", action="store_true", help="save w / fw / fw_single PNGs per env to --out")
+    ap.add_argument("--plot_envs", type=int, default=4)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--device", default="cuda:0")
+    # what config.json holds; for runs older than it
+    ap.add_argument("--dataset", choices=sorted(DATASETS), default=None)
+    ap.add_argument("--N", type=int, default=None)
+    ap.add_argument("--dN", type=int, default=None)
+    ap.add_argument("--recursive", action="store_true", default=None)
+    ap.add_argument("--H_fwd", type=int, default=None)
+    ap.add_argument("--H_rev", type=int, default=None)
+    ap.add_argument("--activation", choices=["relu", "softplus", "tanh", "elu"], default=None)
+    ap.add_argument("--softplus_beta", type=float, default=None)
+    return ap.parse_args(argv)
+
+
+def resolve_config(a):
+    """config.json of the run, with the flags given here on top; without the file, --dataset and --activation are required."""
+    path = os.path.join(a.run, CONFIG_NAME)
+    if os.path.isfile(path):
+        cfg = read_config(a.run)
+    elif a.dataset is None or a.activation is None:
+        raise FileNotFoundError(f"{path} is missing: give --dataset and --activation (and the window / horizon flags the run used)")
+    else:
+        cfg = {}
+    for k in ("dataset", "N", "dN", "recursive", "H_fwd", "H_rev", "activation", "softplus_beta"):
+        if getattr(a, k) is not None:
+            cfg[k] = getattr(a, k)
+    return {**DEFAULTS, **cfg}
+
+
+def evaluate_flat(model, cfg, raw, horizon, dev):
+    kind = cfg["dataset"]
+    win = {"N": cfg["N"], "dN": cfg["dN"]}
+    if kind == "scalar":
+        win["recursive"] = cfg["recursive"]
+    data, target, done = (t.to(dev) for t in sequences(kind, raw, **win))
+    fb = feedback_width(kind, cfg["N"], cfg["dN"], cfg["recursive"], n=raw["z"].shape[-1])
+    E, T, I = data.shape
+    fw_single = model.predict(data.reshape(E * T, I)).reshape(E, T, -1)
+    reseed = ev.reseed_mask(done, horizon)
+    fw = model.rollout(data, fb, reseed)
+    ed = kind == "error_dynamics"
+    res = {"one_step": ev.tube_metrics(fw_single, target, done, None, ed), "rollout": ev.tube_metrics(fw, target, done, reseed, ed),
+           "feedback_width": fb, "envs": E, "steps_per_env": T, "reseed_every": horizon}
+    return res, {"w": target, "fw": fw, "fw_single": fw_single, "done": done}
+
+
+def evaluate_horizon(model, cfg, raw, stride, dev):
+    ds = DATASETS["scalar_horizon"].from_folder(raw, H_fwd=cfg["H_fwd"], H_rev=cfg["H_rev"])
+    Hf, Hr = ds.H_fwd, ds.H_rev
+    E, T = ds.w.shape
+    starts = torch.arange(Hr, T - Hf, max(1, stride), dtype=torch.int32)        # targets reach w[start + H_fwd] <= w[T - 1]
+    if starts.numel() == 0:
+        raise ValueError(f"episodes of {T - Hr} steps are shorter than H_fwd + 1 = {Hf + 1}")
+    env = torch.arange(E, dtype=torch.int32).repeat_interleave(starts.numel())
+    start = starts.repeat(E)
+    fw = model.predict_windows(ds, env, start)
+    w = ds.w.to(dev)
+    idx = start.to(dev).long()[:, None] + torch.arange(1, Hf + 1, device=dev)[None, :]
+    target = w[env.to(dev).long()[:, None], idx]
+    res = {"one_shot": ev.window_metrics(fw, target), "envs": E, "windows_per_env": int(starts.numel()), "window_stride": stride}
+    return res, {"w": target.reshape(E, -1, Hf), "fw": fw.reshape(E, -1, Hf), "starts": starts}
+
+
+def plot(kind, series, out, n_envs):
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    files = []
+    for e in range(min(n_envs, series["w"].shape[0])):
+        fig, ax = plt.subplots(figsize=(9, 4))
+        if kind == "scalar_horizon":
+            for k in range(0, series["w"].shape[1], max(1, series["w"].shape[1] // 8)):
+                t = int(series["starts"][k]) + 1 + torch.arange(series["w"].shape[2])
+                ax.plot(t, series["w"][e, k].cpu(), "b", label="w" if k == 0 else None)
+                ax.plot(t, series["fw"][e, k].cpu(), "k", label="fw (one shot)" if k == 0 else None)
+        else:
+            for name, style in (("w", "-"), ("fw", "-"), ("fw_single", "--")):
+                ax.plot(series[name][e].cpu().norm(dim=-1) if series[name].shape[-1] > 1 else series[name][e, :, 0].cpu(), style, label=name)
+        ax.set_xlabel("Time")
+        ax.set_ylabel("Tube Size")
+        ax.legend()
+        files.append(os.path.join(out, f"tube_env{e}.png"))
+        fig.savefig(files[-1], dpi=100)
+        plt.close(fig)
+    return files
+
+
+def _json_safe(o):
+    """nan (an age or a selection with nothing in it) becomes null: eval.json stays strict JSON."""
+    if isinstance(o, dict):
+        return {k: _json_safe(v) for k, v in o.items()}
+    if isinstance(o, (list, tuple)):
+        return [_json_safe(v) for v in o]
+    return None if isinstance(o, float) and o != o else o
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    cfg = resolve_config(a)
+    dev = torch.device(a.device)
+    out = a.out or a.run
+    os.makedirs(out, exist_ok=True)
+    horizon = (cfg["H_fwd"], cfg["H_rev"]) if cfg["dataset"] == "scalar_horizon" else None
+    model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, activation=cfg["activation"], softplus_beta=cfg["softplus_beta"],
+                              horizon=horizon, device=a.device)
+    raw = construct_dataset(a.data)
+    try:
+        if horizon is None:
+            res, series = evaluate_flat(model, cfg, raw, a.horizon, dev)
+        else:
+            res, series = evaluate_horizon(model, cfg, raw, a.window_stride, dev)
+        torch.cuda.synchronize(dev)
+    finally:
+        model.close()
+    res.update({"run": os.path.abspath(a.run), "data": os.path.abspath(a.data), "checkpoint": a.checkpoint, "dataset": cfg["dataset"]})
+    if a.plot:
+        res["plots"] = plot(cfg["dataset"], series, out, a.plot_envs)
+    with open(os.path.join(out, "eval.json"), "w") as f:
+        json.dump(_json_safe(res), f, indent=1, allow_nan=False)
+    if horizon is None:
+        print(f"Single Success Rate: {res['one_step']['success_rate']}")
+        print(f"Total Success Rate: {res['rollout']['success_rate']}")
+        if cfg["dataset"] == "error_dynamics":
+            print(f"Mean Error: {res['rollout']['mse']}")
+            print(f"Mean One Step Error: {res['one_step']['mse']}")
+    else:
+        print(f"Total Success Rate: {res['one_shot']['success_rate']}")
+    return res
+
+
+if __name__ == "__main__":
+    main()

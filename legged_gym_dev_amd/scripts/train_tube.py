@@ -9,6 +9,7 @@ Writes to --out: model.pth (the latest checkpoint) and model_best.pth (the check
 "latest" and "best" aliases), and metrics.jsonl: one line per step with loss_step, lr_step, grad_norm (plus the test metrics
 on evaluation steps), one line per epoch with loss_epoch and lr_epoch.  loss_epoch is the true mean step loss of the epoch:
 the reference adds every step's loss twice (epoch_loss += loss.item() and epoch_loss += loss), so its value is twice this.
+config.json holds the dataset, window, horizon, loss and model flags: what evaluate_tube.py needs to rebuild the model and its inputs.
 
 The host waits for the device only at checkpoints and once per epoch (to write the log); steps and evaluations are queued.
 """
@@ -56,6 +57,15 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
+CONFIG_KEYS = ("dataset", "N", "dN", "recursive", "H_fwd", "H_rev", "loss", "alpha", "delta", "num_units", "num_layers", "activation",
+               "softplus_beta", "seed", "validation_split")
+
+
+def run_config(a):
+    """The flags a later evaluation needs, as the dict written to config.json."""
+    return {k: getattr(a, k) for k in CONFIG_KEYS}
+
+
 def make_dataset(a):
     ds = construct_dataset(a.data)
     if a.dataset == "scalar":
@@ -86,6 +96,8 @@ def main(argv=None):
                         device=a.device)
     tr.set_data(train, test)
     os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "config.json"), "w") as f:
+        json.dump(run_config(a), f, indent=1)
     n = tr.n_train()
     steps_per_epoch = math.ceil(n / a.batch_size)          # DataLoader(shuffle=True), drop_last=False
     best = float("inf")

@@ -102,9 +102,8 @@ class ScalarTubeDataset(TubeDataset):
     """Input: the tracking error norm w_t = |pz_x - z| and the non-position ROM state and input, over a window of N samples
     dN apart (recursive: the window covers w too); target w_{t+1}."""
 
-    @classmethod
-    def from_folder(cls, src, N=1, dN=1, recursive=False):
-        ds = _load(src)
+    @staticmethod
+    def _sequences(ds, N=1, dN=1, recursive=False):
         z, pz_x, v = ds["z"][:, :-1, :], ds["pz_x"][:, :-1, :], ds["v"]
         w = np.linalg.norm(pz_x - z, axis=-1)
         w_p1 = np.linalg.norm(ds["pz_x_p1"] - ds["z_p1"], axis=-1)
@@ -113,31 +112,44 @@ class ScalarTubeDataset(TubeDataset):
             data = sliding_window(np.concatenate((w[:, :, None], z[:, :, 2:], v), axis=-1), N, dN, m)
         else:
             data = np.concatenate((w[:, :, None], sliding_window(np.concatenate((z[:, :, 2:], v), axis=-1), N, dN, m)), axis=-1)
-        x, y = cls._rows(data, w_p1, ds["done"])
+        return data, w_p1[:, :, None]
+
+    @classmethod
+    def from_folder(cls, src, N=1, dN=1, recursive=False):
+        ds = _load(src)
+        x, y = cls._rows(*cls._sequences(ds, N, dN, recursive), ds["done"])
         return cls(x, y, x.shape[1], 1)
 
 
 class VectorTubeDataset(TubeDataset):
     """Input: |pz_x - z| per axis, z and v over the window; target |pz_x - z| per axis one step ahead."""
 
+    @staticmethod
+    def _sequences(ds, N=1, dN=1):
+        z, pz_x, v = ds["z"][:, :-1, :], ds["pz_x"][:, :-1, :], ds["v"]
+        data = sliding_window(np.concatenate((np.abs(pz_x - z), z, v), axis=-1), N, dN, v.shape[-1])
+        return data, np.abs(ds["pz_x_p1"] - ds["z_p1"])
+
     @classmethod
     def from_folder(cls, src, N=1, dN=1):
         ds = _load(src)
-        z, pz_x, v = ds["z"][:, :-1, :], ds["pz_x"][:, :-1, :], ds["v"]
-        data = sliding_window(np.concatenate((np.abs(pz_x - z), z, v), axis=-1), N, dN, v.shape[-1])
-        x, y = cls._rows(data, np.abs(ds["pz_x_p1"] - ds["z_p1"]), ds["done"])
+        x, y = cls._rows(*cls._sequences(ds, N, dN), ds["done"])
         return cls(x, y, x.shape[1], y.shape[1])
 
 
 class ErrorDynamicsDataset(TubeDataset):
     """Input: the signed error pz_x - z, z and v over the window; target the signed error one step ahead."""
 
+    @staticmethod
+    def _sequences(ds, N=1, dN=1):
+        z, pz_x, v = ds["z"][:, :-1, :], ds["pz_x"][:, :-1, :], ds["v"]
+        data = sliding_window(np.concatenate((pz_x - z, z, v), axis=-1), N, dN, v.shape[-1])
+        return data, ds["pz_x_p1"] - ds["z_p1"]
+
     @classmethod
     def from_folder(cls, src, N=1, dN=1):
         ds = _load(src)
-        z, pz_x, v = ds["z"][:, :-1, :], ds["pz_x"][:, :-1, :], ds["v"]
-        data = sliding_window(np.concatenate((pz_x - z, z, v), axis=-1), N, dN, v.shape[-1])
-        x, y = cls._rows(data, ds["pz_x_p1"] - ds["z_p1"], ds["done"])
+        x, y = cls._rows(*cls._sequences(ds, N, dN), ds["done"])
         return cls(x, y, x.shape[1], y.shape[1])
 
 
@@ -214,3 +226,34 @@ class AlphaVectorTubeDataset(TubeDataset):
 
 DATASETS = {"scalar": ScalarTubeDataset, "vector": VectorTubeDataset, "error_dynamics": ErrorDynamicsDataset,
             "scalar_horizon": ScalarHorizonTubeDataset}
+
+
+def sequences(kind, src, **window_args):
+    """The per-env, time-ordered rows that ``DATASETS[kind].from_folder(src, **window_args)`` builds before it drops the done
+    rows: float32 tensors data (E, T, input_dim) and target (E, T, output_dim), and done (E, T) bool.  Row (e, t) holds the
+    model's input at step t and its target, the quantity one step ahead; a done row's target belongs to the next episode.
+    Flat kinds only: the horizon dataset has no rows."""
+    if kind not in DATASETS or kind == "scalar_horizon":
+        raise ValueError(f"sequences: kind {kind!r} has no per-step rows; one of {[k for k in DATASETS if k != 'scalar_horizon']}")
+    ds = _load(src)
+    data, target = DATASETS[kind]._sequences(ds, **window_args)
+    return (torch.from_numpy(np.ascontiguousarray(data)).float(), torch.from_numpy(np.ascontiguousarray(target)).float(),
+            torch.from_numpy(np.array(ds["done"], dtype=bool)))
+
+
+def feedback_width(kind, N=1, dN=1, recursive=False, n=None):
+    """How many leading input columns of a `kind` row are the model's own previous output, i.e. what a closed-loop roll-out
+    feeds back: 1 (the error norm w) for scalar, n (the ROM state width) for vector and error_dynamics.  Raises
+    NotImplementedError where the fed-back quantity also sits in delayed window taps (N > 1 with vector, error_dynamics or
+    recursive=True): those taps would have to come from the roll-out's own past, and the reference rolls out N = 1 only."""
+    if kind == "scalar":
+        if N > 1 and recursive:
+            raise NotImplementedError("roll-out of a recursive scalar window (N > 1): the delayed taps hold w too")
+        return 1
+    if kind in ("vector", "error_dynamics"):
+        if N > 1:
+            raise NotImplementedError(f"roll-out of a {kind} window with N > 1: the delayed taps hold the error too")
+        if n is None or n < 1:
+            raise ValueError(f"feedback_width({kind!r}) needs n, the ROM state width")
+        return int(n)
+    raise ValueError(f"feedback_width: kind {kind!r} has no closed loop")

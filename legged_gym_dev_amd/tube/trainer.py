@@ -1,8 +1,10 @@
-"""HipTubeTrainer: the reference tube MLP trained by the HIP kernels of tube_kernels.hip (lg_tube_* in include/legged_hip.h).
+"""HipTubeTrainer: the reference tube MLP trained and run by the HIP kernels of tube_kernels.hip (lg_tube_* in
+include/legged_hip.h).
 
 A step is two launches on the current stream -- fused forward / loss / backward over the minibatch, then the fixed-order gradient
 reduction, Adam and StepLR -- and nothing in it waits for the device.  Loss, lr and gradient norm of every step stay in a device
-log until ``read_log``.  There is no CPU fallback: without the library or a GPU the constructor raises.
+log until ``read_log``.  ``predict``, ``predict_windows`` and ``rollout`` run the model as it stands (one launch each, the roll-out
+included) and return device tensors.  There is no CPU fallback: without the library or a GPU the constructor raises.
 """
 import ctypes as C
 from collections import OrderedDict
@@ -185,6 +187,82 @@ class HipTubeTrainer:
         rows] (a copy, valid once the stream reaches it)."""
         self._call("eval")
         return self.eval_buf.clone()
+
+    # ---------------------------------------------------------------- inference (reads the parameters, changes nothing)
+    def predict(self, x, rows=None):
+        """MLP(x[rows]) (every row of x in order when rows is None) as a device tensor (count, output_dim); flat models."""
+        if self.horizon is not None:
+            raise ValueError("a horizon model predicts windows: predict_windows(ds, env, start)")
+        x = self._f32(x)
+        if x.dim() != 2 or x.shape[1] != self.dims[0] or x.shape[0] < 1:
+            raise ValueError(f"x must be (n >= 1, {self.dims[0]}); got {tuple(x.shape)}")
+        count, rp = x.shape[0], None
+        if rows is not None:
+            rows = rows.to(self.device, torch.int32).contiguous().reshape(-1)
+            count = rows.numel()
+            if count < 1:
+                raise ValueError("rows is empty")
+            if int(rows.min()) < 0 or int(rows.max()) >= x.shape[0]:
+                raise IndexError(f"rows must lie in 0..{x.shape[0] - 1}")
+            rp = C.c_void_p(rows.data_ptr())
+        out = torch.empty(count, self.dims[1], device=self.device, dtype=torch.float32)
+        self._call("predict", C.c_void_p(x.data_ptr()), rp, count, C.c_void_p(out.data_ptr()))
+        self._keep = (x, rows)
+        return out
+
+    def predict_windows(self, ds, env, start):
+        """The H_fwd predictions of the ScalarHorizonTubeDataset items (env[i], start[i]) of `ds` (w, z, v padded in front by
+        H_rev): a device tensor (count, H_fwd).  Every start must satisfy H_rev <= start and start + H_fwd <= T."""
+        if self.horizon is None:
+            raise ValueError("a flat model predicts rows: predict(x, rows)")
+        Hf, Hr = self.horizon
+        if (ds.H_fwd, ds.H_rev) != (Hf, Hr):
+            raise ValueError("dataset horizon != model horizon")
+        w, z, v = (self._f32(t) for t in (ds.w, ds.z, ds.v))
+        n, T = w.shape
+        if z.shape[:2] != (n, T) or v.shape[:2] != (n, T):
+            raise ValueError("w, z and v differ in envs or time steps")
+        if Hr + z.shape[2] + (Hr + Hf) * v.shape[2] != self.dims[0]:
+            raise ValueError(f"H_rev + nz + (H_rev + H_fwd) * m != input_dim {self.dims[0]}")
+        env = torch.as_tensor(env).to(self.device, torch.int32).contiguous().reshape(-1)
+        start = torch.as_tensor(start).to(self.device, torch.int32).contiguous().reshape(-1)
+        if env.numel() != start.numel() or env.numel() < 1:
+            raise ValueError("env and start must have the same positive length")
+        if int(env.min()) < 0 or int(env.max()) >= n:
+            raise IndexError(f"env must lie in 0..{n - 1}")
+        if int(start.min()) < Hr or int(start.max()) + Hf > T:
+            raise IndexError(f"window out of range: need {Hr} <= start and start + {Hf} <= {T}")
+        out = torch.empty(env.numel(), Hf, device=self.device, dtype=torch.float32)
+        self._call("predict_windows", C.c_void_p(w.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(v.data_ptr()), n, T,
+                   z.shape[2], v.shape[2], C.c_void_p(env.data_ptr()), C.c_void_p(start.data_ptr()), env.numel(),
+                   C.c_void_p(out.data_ptr()))
+        self._keep = (w, z, v, env, start)
+        return out
+
+    def rollout(self, x, fb, reseed=None):
+        """Closed loop over time in one launch.  x (n_seq, T, input_dim): the teacher rows in time order.  Returns out
+        (n_seq, T, output_dim) with out[s, t] = MLP(x[s, t] with its leading fb columns replaced by out[s, t-1, :fb]); at t = 0
+        and where reseed[s, t] (bool / uint8, (n_seq, T)) is set the row is taken as it is."""
+        if self.horizon is not None:
+            raise ValueError("a horizon model has no closed loop: predict_windows(ds, env, start)")
+        x = self._f32(x)
+        if x.dim() != 3 or x.shape[2] != self.dims[0] or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"x must be (n_seq >= 1, T >= 1, {self.dims[0]}); got {tuple(x.shape)}")
+        if not 0 <= int(fb) <= min(self.dims[:2]):
+            raise ValueError(f"fb={fb}: 0..min(input_dim, output_dim) = {min(self.dims[:2])}")
+        rp = None
+        if reseed is not None:
+            reseed = reseed.to(self.device).ne(0).to(torch.uint8).contiguous()
+            if tuple(reseed.shape) != tuple(x.shape[:2]):
+                raise ValueError(f"reseed must be {tuple(x.shape[:2])}; got {tuple(reseed.shape)}")
+            rp = C.c_void_p(reseed.data_ptr())
+        out = torch.empty(x.shape[0], x.shape[1], self.dims[1], device=self.device, dtype=torch.float32)
+        self._call("rollout", C.c_void_p(x.data_ptr()), x.shape[0], x.shape[1], int(fb), rp, C.c_void_p(out.data_ptr()))
+        self._keep = (x, reseed)
+        return out
+
+    def _f32(self, t):
+        return t.to(self.device, torch.float32).contiguous()
 
     def close(self):
         if getattr(self, "h", None):
