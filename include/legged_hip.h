@@ -515,6 +515,82 @@ int lg_tube_predict_windows(lg_tube *t, const float *w, const float *z, const fl
  * 0 <= fb <= min(input_dim, output_dim).  Flat handles. */
 int lg_tube_rollout(lg_tube *t, const float *x, int64_t n_seq, int32_t T, int32_t fb, const uint8_t *reseed, float *out);
 
+/* ------------------------------------------------------------------ ROM-on-ROM simulator (deep_tube_learning/custom_sim.py
+ * CustomSim with the `custom` branch of data_collection_trajectory.py:87-90 and configs/data_generation/double_single_int.yaml;
+ * DESIGN.md section 10.2): a DoubleInt2D "robot" (state x, y, vx, vy; input = acceleration) tracks the random trajectory of the
+ * SingleInt2D reduced-order model under the DoubleSingleTracking law (controllers.py:80-92).  Tube data without a policy.
+ * One lane per env; lg_romsim_collect runs a whole epoch -- reset, every env step, every record -- in one launch.
+ * The generator state is the LG_TG_* row and its laws are those of the trajectory env (csrc/lg_traj.h).
+ * Draws: Philox keyed (seed, env_offset + env, counter, slot) with counter = epoch << 32 | event; event 0 = the reset of that
+ * epoch (LG_RS_SLOT_*), event r + 1 = the env's r-th generator resample since that reset (LG_TG_NDRAW slots; r = 0 is the
+ * reset's own).  The epoch counts resets, from 1.  With lg_romsim_inject the draws are read from lg_romsim_buffers.inject
+ * instead: per env LG_RS_NRESET floats in LG_RS_SLOT_* order, then R blocks of LG_TG_NDRAW (torch.randint's value as itself). */
+#define LG_RS_SLOT_ROOT 0      /* 4: root_states in [noise_lo, noise_hi] (custom_sim.py:88-91) */
+#define LG_RS_SLOT_MASK 4      /* 1: start offset applied when u > zero_rom_dist_llh (:83) */
+#define LG_RS_SLOT_DIST 5      /* 2: start offset in +-max_rom_dist (:84) */
+#define LG_RS_SLOT_RAMP 7      /* 2: ramp_v_end drawn at construction (rom_dynamics.py:495); read by the first reset only */
+#define LG_RS_NRESET 9
+#define LG_RS_NOBS 8           /* root_states 4, interpolated trajectory point 0 (2), v_trajectory[:, 1] (2)  (custom_sim.py:95-100) */
+typedef struct lg_romsim_cfg {
+    int32_t num_envs, env_offset, N, dN;
+    /* class selectors: 0 is the supported class, anything else is refused (lg_romsim_check_cfg) */
+    int32_t model_cls /*0 DoubleInt2D*/, rom_cls /*0 SingleInt2D*/, controller_cls /*0 DoubleSingleTracking*/;
+    int32_t generator_cls /*LG_TG_KIND_*: RANDOM only*/, t_samp_cls /*0 UniformSampleHoldDT*/, weight_sampler /*LG_TG_WSAMP_**/;
+    int32_t randomize_rom_distance, _pad;
+    uint64_t seed;
+    float model_dt, rom_dt, Kp, Kd;
+    float model_z_min[4], model_z_max[4];         /* only the velocity bounds [2..3] act (DoubleInt2D.clip_v_z) */
+    float model_v_min[2], model_v_max[2];         /* acceleration bounds */
+    float rom_v_min[2], rom_v_max[2];
+    float t_low, t_high, freq_low, freq_high, prob_stationary, zero_rom_dist_llh;
+    float max_rom_dist[2];
+    float noise_lo[4], noise_hi[4];               /* init_state.default_noise_lower / upper */
+} lg_romsim_cfg;
+
+typedef struct lg_romsim_buffers {
+    float *root_states;                   /* (N, 4) */
+    float *tg_state;                      /* (N, LG_TG_STRIDE), LG_TG_* */
+    float *tg_traj;                       /* (N, N dN + 1, 2) ROM states, oldest first (TrajectoryGenerator.trajectory) */
+    float *v_traj;                        /* (N, N dN, 2) ROM inputs (TrajectoryGenerator.v_trajectory, rom_dynamics.py:505,586-587) */
+    float *trajectory;                    /* (N, N, 2) the window interpolated at the env's time (get_trajectory) */
+    float *obs;                           /* (N, LG_RS_NOBS) */
+    float *actions;                       /* (N, 2) the action the last env step applied */
+    uint8_t *done;                        /* (N) zeros: CustomSim.step returns done all False */
+    float *inject;                        /* (N, inject_K) or NULL before lg_romsim_inject */
+    int32_t *n_resample;                  /* (N) generator resamples of the env since its last reset */
+    int32_t *inject_overrun;              /* 1: resamples that found the injected blocks used up (lg_romsim_inject_status) */
+    int64_t inject_K;                     /* LG_RS_NRESET + R LG_TG_NDRAW */
+} lg_romsim_buffers;
+
+typedef struct lg_romsim lg_romsim;
+int lg_romsim_check_cfg(const lg_romsim_cfg *cfg);   /* 0 inside the supported envelope, else -1 and lg_last_error names the field */
+/* CustomSim.__init__ (custom_sim.py:7-35): buffers only; the construction draw of ramp_v_end is made by the first reset. */
+int lg_romsim_create(const lg_romsim_cfg *cfg, lg_romsim **out);
+int lg_romsim_destroy(lg_romsim *s);
+int lg_romsim_set_stream(lg_romsim *s, void *stream);
+int lg_romsim_get_buffers(lg_romsim *s, lg_romsim_buffers *out);
+/* resets made so far (the Philox epoch of the last reset); set by tests / resume.  epoch >= 0. */
+int lg_romsim_set_epoch(lg_romsim *s, int64_t epoch);
+int64_t lg_romsim_get_epoch(lg_romsim *s);
+/* enable != 0: replay recorded draws with room for R >= 1 resamples per env (allocates inject, zero-filled, when R changes).
+ * The state installed through the buffers is taken as constructed (no construction draw) when constructed != 0. */
+int lg_romsim_inject(lg_romsim *s, int enable, int32_t R, int constructed);
+/* Waits for the stream.  -1 if a resample since the last call needed more injected blocks than R (those resamples re-read the
+ * last block: nothing is read out of bounds); clears the count. */
+int lg_romsim_inject_status(lg_romsim *s);
+/* CustomSim.reset_idx (custom_sim.py:77-93) for all envs: ids = NULL or DEVICE int32[num_envs] holding 0..num_envs-1 in order;
+ * n != num_envs (a partial reset) is refused. */
+int lg_romsim_reset(lg_romsim *s, const int32_t *ids, int n);
+/* CustomSim.step (custom_sim.py:71-75) + get_observations (:95-100).  actions: DEVICE (N, 2) f32, or NULL = DoubleSingleTracking
+ * with DoubleInt2D.clip_v_z (controllers.py:87-92, rom_dynamics.py:244-250) on the current observation. */
+int lg_romsim_step(lg_romsim *s, const float *actions);
+/* The controller alone: out (rows, 2) from obs (rows, LG_RS_NOBS), both DEVICE. */
+int lg_romsim_policy(lg_romsim *s, const float *obs, float *out, int64_t rows);
+/* One epoch of data_collection_trajectory.py:111-149 in one launch: reset, then T records, each after as many env steps (built-in
+ * controller) as the ROM step counter k needs to advance.  DEVICE outputs z (N, T+1, 2), v (N, T, 2), pz_x (N, T+1, 2),
+ * done (N, T) u8, x (N, T+1, 4) or NULL.  An env's records equal, bit for bit, lg_romsim_reset + repeated lg_romsim_step(NULL). */
+int lg_romsim_collect(lg_romsim *s, int32_t T, float *z, float *v, float *pz_x, uint8_t *done, float *x);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,48 @@ def declare_tube_api(lib):
     lib.lg_tube_rollout.argtypes = [vp, vp, i64, i32, i32, vp, vp]
 
 
+RS_SLOT_ROOT, RS_SLOT_MASK, RS_SLOT_DIST, RS_SLOT_RAMP, RS_NRESET, RS_NOBS = 0, 4, 5, 7, 9, 8     # LG_RS_*
+
+
+class lg_romsim_cfg(C.Structure):
+    _fields_ = [
+        ("num_envs", i32), ("env_offset", i32), ("N", i32), ("dN", i32),
+        ("model_cls", i32), ("rom_cls", i32), ("controller_cls", i32), ("generator_cls", i32), ("t_samp_cls", i32),
+        ("weight_sampler", i32), ("randomize_rom_distance", i32), ("_pad", i32),
+        ("seed", u64),
+        ("model_dt", f32), ("rom_dt", f32), ("Kp", f32), ("Kd", f32),
+        ("model_z_min", f32 * 4), ("model_z_max", f32 * 4), ("model_v_min", f32 * 2), ("model_v_max", f32 * 2),
+        ("rom_v_min", f32 * 2), ("rom_v_max", f32 * 2),
+        ("t_low", f32), ("t_high", f32), ("freq_low", f32), ("freq_high", f32), ("prob_stationary", f32),
+        ("zero_rom_dist_llh", f32), ("max_rom_dist", f32 * 2), ("noise_lo", f32 * 4), ("noise_hi", f32 * 4)]
+
+
+class lg_romsim_buffers(C.Structure):
+    _fields_ = [
+        ("root_states", PF), ("tg_state", PF), ("tg_traj", PF), ("v_traj", PF), ("trajectory", PF), ("obs", PF),
+        ("actions", PF), ("done", PU8), ("inject", PF), ("n_resample", PI32), ("inject_overrun", PI32), ("inject_K", i64)]
+
+
+def declare_romsim_api(lib):
+    vp = C.c_void_p
+    if not hasattr(lib, "lg_romsim_create"):       # an A/B library (LG_HIP_LIB) built before the simulator: its entries stay undeclared
+        return
+    lib.lg_romsim_check_cfg.argtypes = [C.POINTER(lg_romsim_cfg)]
+    lib.lg_romsim_create.argtypes = [C.POINTER(lg_romsim_cfg), C.POINTER(vp)]
+    lib.lg_romsim_destroy.argtypes = [vp]
+    lib.lg_romsim_set_stream.argtypes = [vp, vp]
+    lib.lg_romsim_get_buffers.argtypes = [vp, C.POINTER(lg_romsim_buffers)]
+    lib.lg_romsim_set_epoch.argtypes = [vp, i64]
+    lib.lg_romsim_get_epoch.argtypes = [vp]
+    lib.lg_romsim_get_epoch.restype = i64
+    lib.lg_romsim_inject.argtypes = [vp, C.c_int, i32, C.c_int]
+    lib.lg_romsim_inject_status.argtypes = [vp]
+    lib.lg_romsim_reset.argtypes = [vp, vp, C.c_int]
+    lib.lg_romsim_step.argtypes = [vp, vp]
+    lib.lg_romsim_policy.argtypes = [vp, vp, vp, i64]
+    lib.lg_romsim_collect.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p

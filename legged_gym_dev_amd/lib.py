@@ -40,6 +40,7 @@ def load():
         capi.declare_env_api(_lib, prefix="lg_")
         _declare_ppo(_lib)
         capi.declare_tube_api(_lib)
+        capi.declare_romsim_api(_lib)
     return _lib
 
 
