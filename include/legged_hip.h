@@ -514,6 +514,15 @@ int lg_tube_predict_windows(lg_tube *t, const float *w, const float *z, const fl
  * except at t == 0 and where reseed[s, t] != 0 (reseed (n_seq, T) may be NULL): there xt = x[s, t] unchanged.
  * 0 <= fb <= min(input_dim, output_dim).  Flat handles. */
 int lg_tube_rollout(lg_tube *t, const float *x, int64_t n_seq, int32_t T, int32_t fb, const uint8_t *reseed, float *out);
+/* The closed loop of a windowed model, one launch.  An input row is `taps` blocks of `stride` columns, block i the dataset row
+ * delayed by i * dN steps; the leading fb columns of every block hold the fed-back quantity.  With s0(t) the last step t' <= t
+ * that is 0 or has reseed[s, t'] != 0:  out[s, t] = MLP(xt), xt = x[s, t] except that for every tap i with t - i*dN > s0(t)
+ * columns [i*stride, i*stride + fb) are out[s, t-1-i*dN, 0:fb].  Every other column is the teacher's, taps that reach back to
+ * or before the seed included.  taps == 1 is lg_tube_rollout (stride is then not read).  The history stays on chip.
+ * Returns -1 unless fb, taps, dN >= 1, fb <= output_dim, stride >= fb (taps > 1), (taps-1)*stride + fb <= input_dim and
+ * ((taps-1)*dN + 1) * fb <= 1024 (the ring of past outputs a sequence keeps).  Flat handles. */
+int lg_tube_rollout_window(lg_tube *t, const float *x, int64_t n_seq, int32_t T, int32_t fb, int32_t taps, int32_t dN,
+                           int32_t stride, const uint8_t *reseed, float *out);
 
 /* ------------------------------------------------------------------ ROM-on-ROM simulator (deep_tube_learning/custom_sim.py
  * CustomSim with the `custom` branch of data_collection_trajectory.py:87-90 and configs/data_generation/double_single_int.yaml;

@@ -189,6 +189,7 @@ class lg_ppo_rnn_buffers(C.Structure):
 
 
 TUBE_MAX_IN, TUBE_MAX_OUT, TUBE_MAX_UNITS = 256, 64, 128     # LG_TUBE_MAX_*; num_units a multiple of 16, num_layers 1..4
+TUBE_RING_MAX = 1024                                            # LG_TUBE_RING_MAX: floats of output history per sequence (rollout_window)
 TUBE_ACT = {"relu": 0, "softplus": 1, "tanh": 2, "elu": 3}      # LG_TUBE_ACT_*
 TUBE_LOSS = {"scalar": 0, "vector": 1, "mse": 2}                # LG_TUBE_LOSS_*
 
@@ -227,6 +228,7 @@ def declare_tube_api(lib):
     lib.lg_tube_predict.argtypes = [vp, vp, vp, i64, vp]
     lib.lg_tube_predict_windows.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp]
     lib.lg_tube_rollout.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+    lib.lg_tube_rollout_window.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp]
 
 
 RS_SLOT_ROOT, RS_SLOT_MASK, RS_SLOT_DIST, RS_SLOT_RAMP, RS_NRESET, RS_NOBS = 0, 4, 5, 7, 9, 8     # LG_RS_*

@@ -1,6 +1,6 @@
 // C-ABI (include/legged_hip.h, lg_tube_*) of the tube-model trainer: parameter / optimiser / slab allocation in HBM, epoch
 // permutation, the two launches of a training step, the eval launch, and the inference entries: predict, window prediction and
-// the closed-loop roll-out (tube_kernels.hip).
+// the closed-loop roll-outs, single-tap and windowed (tube_kernels.hip).
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -23,6 +23,8 @@ void tubek_iota(int32_t *p, int64_t n, hipStream_t s);
 void tubek_predict(const TubeDev *D, const float *x, const float *y, const float *v, const int32_t *rows, const int32_t *env,
                    const int32_t *start, int T, int nz, int m, int64_t count, float *o, hipStream_t s);
 void tubek_rollout(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed, float *o, hipStream_t s);
+void tubek_rollout_window(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, int taps, int dN, int stride,
+                          const uint8_t *reseed, float *o, hipStream_t s);
 }
 
 struct lg_tube {
@@ -248,6 +250,24 @@ int lg_tube_rollout(lg_tube *p, const float *x, int64_t n_seq, int32_t T, int32_
     if (!x || !out) { lg_set_error("lg_tube_rollout: missing array"); return -1; }
     tubek_rollout(&p->dev, x, n_seq, T, fb, reseed, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_rollout: launch failed"), -3);
+}
+
+int lg_tube_rollout_window(lg_tube *p, const float *x, int64_t n_seq, int32_t T, int32_t fb, int32_t taps, int32_t dN, int32_t stride,
+                           const uint8_t *reseed, float *out) {
+    const TubeDev &D = p->dev;
+    const char *e = nullptr;
+    if (D.horizon) e = "a horizon handle has no closed loop (lg_tube_predict_windows)";
+    else if (n_seq < 1 || T < 1) e = "n_seq and T must be positive";
+    else if (n_seq > INT32_MAX / 16) e = "n_seq must be below 2^27";
+    else if (fb < 1 || taps < 1 || dN < 1) e = "fb, taps and dN must be at least 1";
+    else if (fb > D.out_dim) e = "fb must not exceed output_dim";
+    else if (taps > 1 && stride < fb) e = "stride must be at least fb";
+    else if ((int64_t)(taps - 1) * (taps > 1 ? stride : 0) + fb > D.in_dim) e = "(taps - 1) * stride + fb must not exceed input_dim";
+    else if (((int64_t)(taps - 1) * dN + 1) * fb > LG_TUBE_RING_MAX) e = "the ring ((taps - 1) * dN + 1) * fb must not exceed 1024 floats per sequence";
+    else if (!x || !out) e = "missing array";
+    if (e) { lg_set_error(std::string("lg_tube_rollout_window: ") + e); return -1; }
+    tubek_rollout_window(&p->dev, x, n_seq, T, fb, taps, dN, taps > 1 ? stride : D.in_dim, reseed, out, p->stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_rollout_window: launch failed"), -3);
 }
 
 }  // extern "C"

@@ -6,6 +6,8 @@
 #define LG_TUBE_ROWS 32                 // rows per workgroup tile of k_tube_rows
 #define LG_TUBE_THREADS 256
 #define LG_TUBE_ROLLOUT_LDS (144 * 1024) // k_tube_rollout keeps the weights in LDS where weights + tile fit this (a CU has 160 KiB)
+#define LG_TUBE_RING_MAX 1024           // floats of output history per sequence of k_tube_rollout_window, ((taps-1) dN + 1) * fb at most:
+                                        // the largest model's 16-row tile (36 KiB) plus 16 such rings (64 KiB) fits LG_TUBE_ROLLOUT_LDS
 #define LG_TUBE_MAX_LIN 5               // num_layers (<= 4) hidden Linear layers + the output Linear
 
 struct TubeSplit {                      // one side of random_split, device memory owned by the caller

@@ -477,12 +477,108 @@ __global__ void __launch_bounds__(NT_) k_tube_rollout(TubeDev D, const float *x,
     }
 }
 
+// The closed loop of a windowed model: the input row is `taps` blocks of `stride` columns, block i the
+// dataset row delayed by i * dN steps, and the leading fb columns of EVERY block are fed back -- block i takes out[s, t-1-i*dN]
+// where that step lies after the row's last seed (t == 0 or reseed[s, t']), the teacher's column otherwise.  k_tube_rollout's
+// shapes and step; added to it are a ring of the tile's own last depth = (taps-1) * dN + 1 outputs (fb floats each) per row and
+// a per-row count of the steps since the seed, both in LDS.  The ring slot of out[t-1] is written from F during step t's input
+// build; the delayed taps read slots of lag >= 1 in the same phase, which are other slots because lag < depth.  Tap 0 reads F.
+// A fed-back element is lag << 10 | row << 6 | column (lag < depth <= LG_TUBE_RING_MAX = 1024, row < 16, column < 64).
+template <int RT, int NT_, bool WLDS>
+__global__ void __launch_bounds__(NT_) k_tube_rollout_window(TubeDev D, const float *x, int64_t n_seq, int T, int fb, int taps, int dN,
+                                                             int stride, const uint8_t *reseed, float *o) {
+    constexpr int RB_ = RT < 4 ? RT : 4;
+    static_assert(RT * LG_TUBE_MAX_IN <= TUBE_RO_PRE * NT_ && RT <= NT_ && RT <= 16, "tile shape");
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, I = D.in_dim, O = D.out_dim, U = D.units, L = D.layers;
+    const int depth = (taps - 1) * dN + 1;
+    const int64_t base = (int64_t)blockIdx.x * RT;
+    const int nr = (int)(n_seq - base < RT ? n_seq - base : RT);
+    float *W = lds;
+    float *X = W + (WLDS ? D.num_params : 0), *H0 = X + RT * I, *H1 = H0 + RT * U, *F = H1 + RT * U;
+    float *ring = F + RT * O;           // (RT, depth, fb): slot t % depth of row r holds out[r, t, 0:fb]
+    int *age = (int *)(ring + RT * depth * fb);   // (RT) steps since the row's seed: 0 at t == 0 and at a reseed
+    if (WLDS) {
+        for (int64_t p = tid; p < D.num_params; p += NT_) W[p] = D.wt[p];
+        __syncthreads();
+        for (int li = 0; li <= L; ++li)
+            for (int j = tid; j < D.dout[li]; j += NT_) W[D.off_b[li] + j] = D.params[D.off_b[li] + j];
+    }
+    const float *wsrc = WLDS ? W : D.wt, *bsrc = WLDS ? W : D.params;
+    const int nq = (RT * I + NT_ - 1) / NT_;
+    // as in k_tube_rollout; pfb: the fed-back element's code (above), -1 a teacher-only column, -2 past the tile
+    int64_t poff[TUBE_RO_PRE];
+    int pfb[TUBE_RO_PRE];
+    float pre[TUBE_RO_PRE];
+    int pfresh = 1;
+#pragma unroll
+    for (int q = 0; q < TUBE_RO_PRE; ++q) {
+        int e = tid + q * NT_;
+        const bool live = e < RT * I;
+        e = live ? e : RT * I - 1;
+        const int r = e / I, c = e - r * I;
+        const int tap = taps > 1 ? c / stride : 0, cc = c - tap * stride;
+        poff[q] = (r < nr ? base + r : n_seq - 1) * T * I + c;
+        pfb[q] = live ? (tap < taps && cc < fb ? (tap * dN) << 10 | r << 6 | cc : -1) : -2;
+    }
+    auto fetch = [&](int t) {
+#pragma unroll
+        for (int q = 0; q < TUBE_RO_PRE; ++q)
+            if (q < nq) pre[q] = x[poff[q] + (int64_t)t * I];
+        if (tid < RT) pfresh = reseed && tid < nr && reseed[(base + tid) * T + t];
+    };
+    fetch(0);
+    if (tid < RT) age[tid] = 0;
+    __syncthreads();
+    int head = -1;                      // (t - 1) % depth: the slot of out[t-1]
+    for (int t = 0; t < T; ++t) {
+        if (t > 0) {
+            head = head + 1 == depth ? 0 : head + 1;
+            for (int e = tid; e < RT * fb; e += NT_) {
+                const int r = e / fb, c = e - r * fb;
+                ring[(r * depth + head) * fb + c] = F[r * O + c];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < TUBE_RO_PRE; ++q) {
+            if (q < nq && pfb[q] != -2) {
+                const int code = pfb[q];
+                float v = pre[q];
+                if (code >= 0) {
+                    const int r = (code >> 6) & 15, c = code & 63, lag = code >> 10;
+                    if (age[r] > lag) {
+                        const int slot = head - lag + (head < lag ? depth : 0);
+                        v = lag ? ring[(r * depth + slot) * fb + c] : F[r * O + c];
+                    }
+                }
+                X[tid + q * NT_] = v;
+            }
+        }
+        if (t + 1 < T) fetch(t + 1);
+        __syncthreads();
+        const float *in = X;
+        for (int li = 0; li < L; ++li) {
+            float *out = li & 1 ? H1 : H0;
+            tube_layer<RT, RB_, NT_, false>(tid, D.din[li], U, in, wsrc + D.off_w[li], bsrc + D.off_b[li], D.act, D.sp_beta, out, nullptr, 0, 0);
+            __syncthreads();
+            in = out;
+        }
+        tube_layer<RT, RB_, NT_, true>(tid, D.din[L], O, in, wsrc + D.off_w[L], bsrc + D.off_b[L], D.act, D.sp_beta, F,
+                                       o + (base * T + t) * O, (int64_t)T * O, nr);
+        if (tid < RT) age[tid] = pfresh ? 0 : age[tid] + 1;
+        __syncthreads();
+    }
+}
+
 // LDS of a roll-out tile in floats, without the weights
 static size_t tubek_rollout_acts(const TubeDev *D, int rt) { return (size_t)rt * (D->in_dim + 2 * D->units + D->out_dim + 1); }
 // rows per workgroup from the batch: the smallest tile that keeps the launch within about two workgroups per CU of the chip's 256
 static int tubek_rollout_tile(int64_t n_seq) { return n_seq <= 256 ? 1 : n_seq <= 2048 ? 4 : 16; }
 // weights go to LDS where weights + tile fit LG_TUBE_ROLLOUT_LDS
-static int tubek_rollout_wlds(const TubeDev *D, int rt) { return sizeof(float) * (D->num_params + tubek_rollout_acts(D, rt)) <= LG_TUBE_ROLLOUT_LDS; }
+// (ring: the floats of a windowed roll-out's output ring per row, 0 for the single-tap kernel)
+static int tubek_rollout_wlds(const TubeDev *D, int rt, int ring = 0) {
+    return sizeof(float) * (D->num_params + tubek_rollout_acts(D, rt) + (size_t)rt * ring) <= LG_TUBE_ROLLOUT_LDS;
+}
 
 template <int RT, int NT_>
 static void rollout_launch(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed, float *o, hipStream_t s) {
@@ -493,7 +589,25 @@ static void rollout_launch(const TubeDev *D, const float *x, int64_t n_seq, int 
     else hipLaunchKernelGGL((k_tube_rollout<RT, NT_, false>), dim3(nwg), dim3(NT_), bytes, s, *D, x, n_seq, T, fb, reseed, o);
 }
 
+template <int RT, int NT_>
+static void rollout_window_launch(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, int taps, int dN, int stride,
+                                  const uint8_t *reseed, float *o, hipStream_t s) {
+    const int nwg = (int)((n_seq + RT - 1) / RT), ring = ((taps - 1) * dN + 1) * fb;
+    const bool wl = tubek_rollout_wlds(D, RT, ring);
+    const size_t bytes = sizeof(float) * (tubek_rollout_acts(D, RT) + (size_t)RT * ring + (wl ? D->num_params : 0));
+    if (wl) hipLaunchKernelGGL((k_tube_rollout_window<RT, NT_, true>), dim3(nwg), dim3(NT_), bytes, s, *D, x, n_seq, T, fb, taps, dN, stride, reseed, o);
+    else hipLaunchKernelGGL((k_tube_rollout_window<RT, NT_, false>), dim3(nwg), dim3(NT_), bytes, s, *D, x, n_seq, T, fb, taps, dN, stride, reseed, o);
+}
+
 extern "C" {
+void tubek_rollout_window(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, int taps, int dN, int stride,
+                          const uint8_t *reseed, float *o, hipStream_t s) {
+    switch (tubek_rollout_tile(n_seq)) {
+    case 1: rollout_window_launch<1, 64>(D, x, n_seq, T, fb, taps, dN, stride, reseed, o, s); break;
+    case 4: rollout_window_launch<4, 64>(D, x, n_seq, T, fb, taps, dN, stride, reseed, o, s); break;
+    default: rollout_window_launch<16, 256>(D, x, n_seq, T, fb, taps, dN, stride, reseed, o, s); break;
+    }
+}
 void tubek_rollout(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed, float *o, hipStream_t s) {
     switch (tubek_rollout_tile(n_seq)) {
     case 1: rollout_launch<1, 64>(D, x, n_seq, T, fb, reseed, o, s); break;
@@ -519,7 +633,10 @@ int tubek_init() {
     if (hipFuncSetAttribute((const void *)k_tube_predict, hipFuncAttributeMaxDynamicSharedMemorySize, plim) != hipSuccess) return -1;
     for (const void *f : {(const void *)k_tube_rollout<1, 64, true>, (const void *)k_tube_rollout<1, 64, false>,
                           (const void *)k_tube_rollout<4, 64, true>, (const void *)k_tube_rollout<4, 64, false>,
-                          (const void *)k_tube_rollout<16, 256, true>, (const void *)k_tube_rollout<16, 256, false>})
+                          (const void *)k_tube_rollout<16, 256, true>, (const void *)k_tube_rollout<16, 256, false>,
+                          (const void *)k_tube_rollout_window<1, 64, true>, (const void *)k_tube_rollout_window<1, 64, false>,
+                          (const void *)k_tube_rollout_window<4, 64, true>, (const void *)k_tube_rollout_window<4, 64, false>,
+                          (const void *)k_tube_rollout_window<16, 256, true>, (const void *)k_tube_rollout_window<16, 256, false>})
         if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
     return 0;
 }

@@ -1,5 +1,6 @@
 """Evaluate a trained tube model on recorded ROM tracking data: the numerical content of the reference's
-deep_tube_learning/evaluation/evaluate_tube.py, evaluate_error_dyn.py and evaluate_tube_oneshot.py on the HIP kernels, without
+deep_tube_learning/evaluation/evaluate_tube.py, evaluate_error_dyn.py, evaluate_tube_oneshot.py, evaluate_tube_simple.py and
+evaluate_error_dyn_simple.py on the HIP kernels, without
 wandb or hydra and on recorded data instead of a fresh simulation.
 
     python legged_gym_dev_amd/scripts/evaluate_tube.py --run tube_runs/run0 --data rom_tracking_data/run1 \\
@@ -10,8 +11,11 @@ The run's config.json (train_tube.py writes it) says how the model and its input
 
 Flat datasets (scalar, vector, error_dynamics): the one-step prediction fw_single = model(data) on every row, and the closed-loop
 roll-out fw[t+1] = model([fw[t], rest of row t]) -- one launch for all envs and steps -- reseeded from the data at t = 0, after
-every done and, with --horizon K, every K steps.  scalar_horizon: the one-shot prediction at the window starts H_rev, H_rev + S,
-... of every env, scored overall and per step ahead.  Writes eval.json to --out (default: the run folder) and prints the
+every done and, with --horizon K, every K steps.  Windowed rows (N > 1 with recursive scalar, vector or error_dynamics) hold the
+fed-back quantity in every delayed tap too: tap i takes the roll-out's own output of i rows earlier once that row lies after the
+last reseed (HipTubeModel.rollout_window; evaluate_tube_simple.py:62-72, evaluate_error_dyn_simple.py:44-50).  eval.json's
+feedback_dN is that distance in rows, 1 for every dataset (tube/data.py feedback_layout).  scalar_horizon: the one-shot
+prediction at the window starts H_rev, H_rev + S, ... of every env, scored overall and per step ahead.  Writes eval.json to --out (default: the run folder) and prints the
 reference's "Total Success Rate" (and, for error_dynamics, "Mean Error" / "Mean One Step Error") lines.
 
 Deliberate deviations from the reference scripts:
@@ -20,6 +24,11 @@ Deliberate deviations from the reference scripts:
   * evaluate_tube_oneshot.py:111 divides a sum over 100 windows by n_robots = 2.  The success rate here is a mean over the windows.
   * The scripts score one robot and prepend the initial value to the prediction; here every env is scored, prediction t against
     the dataset's target t (the quantity at t + 1), and done rows are left out.
+  * evaluate_error_dyn_simple.py:48 indexes fe[t - n*dN] with a negative index while t < n*dN, which Python wraps to the end of
+    the array.  Here such a tap keeps the dataset's own front padding: what the model was trained on.
+  * The same line delays tap n by n*dN raw samples, while datasets.py get_slice, which built the training rows, keeps every
+    dN-th sample in every tap, so that tap n trails tap 0 by n rows of a subsampled series.  The two agree for dN = 1 (every
+    reference configuration); for dN > 1 the rows and the tap distance here are the dataset's: what the model was trained on.
 """
 import argparse
 import json
@@ -30,7 +39,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch  # noqa: E402
 
 from legged_gym_dev_amd.tube import evaluate as ev  # noqa: E402
-from legged_gym_dev_amd.tube.data import DATASETS, construct_dataset, feedback_width, sequences  # noqa: E402
+from legged_gym_dev_amd.tube.data import DATASETS, construct_dataset, feedback_layout, sequences  # noqa: E402
 from legged_gym_dev_amd.tube.model import CONFIG_NAME, HipTubeModel, read_config  # noqa: E402
 
 DEFAULTS = {"N": 1, "dN": 1, "recursive": False, "H_fwd": 50, "H_rev": 10, "softplus_beta": 1.0}
@@ -80,14 +89,14 @@ def evaluate_flat(model, cfg, raw, horizon, dev):
     if kind == "scalar":
         win["recursive"] = cfg["recursive"]
     data, target, done = (t.to(dev) for t in sequences(kind, raw, **win))
-    fb = feedback_width(kind, cfg["N"], cfg["dN"], cfg["recursive"], n=raw["z"].shape[-1])
+    fb, taps, lag, stride = feedback_layout(kind, cfg["N"], cfg["dN"], cfg["recursive"], n=raw["z"].shape[-1], m=raw["v"].shape[-1])
     E, T, I = data.shape
     fw_single = model.predict(data.reshape(E * T, I)).reshape(E, T, -1)
     reseed = ev.reseed_mask(done, horizon)
-    fw = model.rollout(data, fb, reseed)
+    fw = model.rollout_window(data, fb, taps, lag, stride, reseed)
     ed = kind == "error_dynamics"
     res = {"one_step": ev.tube_metrics(fw_single, target, done, None, ed), "rollout": ev.tube_metrics(fw, target, done, reseed, ed),
-           "feedback_width": fb, "envs": E, "steps_per_env": T, "reseed_every": horizon}
+           "feedback_width": fb, "feedback_taps": taps, "feedback_dN": lag, "feedback_stride": stride, "envs": E, "steps_per_env": T, "reseed_every": horizon}
     return res, {"w": target, "fw": fw, "fw_single": fw_single, "done": done}
 
 

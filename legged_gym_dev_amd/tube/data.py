@@ -257,3 +257,29 @@ def feedback_width(kind, N=1, dN=1, recursive=False, n=None):
             raise ValueError(f"feedback_width({kind!r}) needs n, the ROM state width")
         return int(n)
     raise ValueError(f"feedback_width: kind {kind!r} has no closed loop")
+
+
+def feedback_layout(kind, N=1, dN=1, recursive=False, n=None, m=None):
+    """(fb, taps, lag, stride) of a `kind` row of sequences() for the windowed closed-loop roll-out
+    (HipTubeModel.rollout_window(x, fb, taps, lag, stride)): the row is `taps` blocks of `stride` columns, block i is block 0 of
+    the row i * lag steps earlier, and the leading fb columns of every block hold the model's own output.  n: the width of z,
+    m: the width of v.
+        scalar, not recursive   (1, 1, 1, input width): only the leading w is fed back, the window holds z and v alone
+        scalar, recursive       (1, N, 1, 1 + (n - 2) + m): every block is (w, z without its position, v)
+        vector, error_dynamics  (n, N, 1, 2 n + m): every block is (error, z, v)
+    The lag is 1 row whatever dN is: get_slice keeps every dN-th sample counted back from the end of the episode in EVERY
+    block, block 0 included, so the rows of a dN > 1 dataset are a subsampled series (padded in front) in which block i still
+    trails block 0 by i rows.  That is the window the model was trained on, so it is the one a roll-out over these rows feeds.
+    Unlike feedback_width it refuses no window: the delayed taps come from the roll-out's own past."""
+    if N < 1 or dN < 1:
+        raise ValueError(f"feedback_layout: N={N} and dN={dN} must be at least 1")
+    if kind not in ("scalar", "vector", "error_dynamics"):
+        raise ValueError(f"feedback_layout: kind {kind!r} has no closed loop")
+    if n is None or m is None or n < 1 or m < 1:
+        raise ValueError(f"feedback_layout({kind!r}) needs n and m, the widths of z and v")
+    n, m = int(n), int(m)
+    if kind == "scalar":
+        if not recursive:
+            return 1, 1, 1, 1 + N * (n - 2 + m)
+        return 1, int(N), 1, 1 + (n - 2) + m
+    return n, int(N), 1, 2 * n + m

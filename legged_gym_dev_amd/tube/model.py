@@ -1,4 +1,5 @@
-"""HipTubeModel: a trained tube MLP for inference only -- ``predict``, ``predict_windows`` and ``rollout`` on the HIP kernels.
+"""HipTubeModel: a trained tube MLP for inference only -- ``predict``, ``predict_windows``, ``rollout`` and
+``rollout_window`` on the HIP kernels.
 
 It wraps the same ``lg_tube`` handle the trainer uses; the model's shape comes from the state dict, and what the state dict
 cannot say (activation, Softplus beta, the horizon) from the run's ``config.json`` (train_tube.py writes it) or from keywords.
@@ -70,6 +71,9 @@ class HipTubeModel:
 
     def rollout(self, x, fb, reseed=None):
         return self._tr.rollout(x, fb, reseed)
+
+    def rollout_window(self, x, fb, taps, dN, stride, reseed=None):
+        return self._tr.rollout_window(x, fb, taps, dN, stride, reseed)
 
     def state_dict(self):
         return self._tr.state_dict()

@@ -3,8 +3,8 @@ include/legged_hip.h).
 
 A step is two launches on the current stream -- fused forward / loss / backward over the minibatch, then the fixed-order gradient
 reduction, Adam and StepLR -- and nothing in it waits for the device.  Loss, lr and gradient norm of every step stay in a device
-log until ``read_log``.  ``predict``, ``predict_windows`` and ``rollout`` run the model as it stands (one launch each, the roll-out
-included) and return device tensors.  There is no CPU fallback: without the library or a GPU the constructor raises.
+log until ``read_log``.  ``predict``, ``predict_windows``, ``rollout`` and ``rollout_window`` run the model as it stands (one launch
+each, the roll-outs included) and return device tensors.  There is no CPU fallback: without the library or a GPU the constructor raises.
 """
 import ctypes as C
 from collections import OrderedDict
@@ -258,6 +258,40 @@ class HipTubeTrainer:
             rp = C.c_void_p(reseed.data_ptr())
         out = torch.empty(x.shape[0], x.shape[1], self.dims[1], device=self.device, dtype=torch.float32)
         self._call("rollout", C.c_void_p(x.data_ptr()), x.shape[0], x.shape[1], int(fb), rp, C.c_void_p(out.data_ptr()))
+        self._keep = (x, reseed)
+        return out
+
+    def rollout_window(self, x, fb, taps, dN, stride, reseed=None):
+        """Closed loop of a windowed model in one launch.  A row of x (n_seq, T, input_dim) is `taps` blocks of `stride` columns,
+        block i the dataset row delayed by i * dN steps, and the leading fb columns of every block are fed back: with s0(t) the
+        last step <= t that is 0 or has reseed[s, t] set, block i of x[s, t] takes out[s, t-1-i*dN, :fb] where t - i*dN > s0(t)
+        and keeps the teacher's columns otherwise.  taps == 1 is rollout(x, fb, reseed)."""
+        if self.horizon is not None:
+            raise ValueError("a horizon model has no closed loop: predict_windows(ds, env, start)")
+        x = self._f32(x)
+        if x.dim() != 3 or x.shape[2] != self.dims[0] or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"x must be (n_seq >= 1, T >= 1, {self.dims[0]}); got {tuple(x.shape)}")
+        fb, taps, dN, stride = int(fb), int(taps), int(dN), int(stride)
+        if fb < 1 or taps < 1 or dN < 1:
+            raise ValueError(f"fb={fb}, taps={taps}, dN={dN}: each at least 1")
+        if fb > self.dims[1]:
+            raise ValueError(f"fb={fb} exceeds output_dim {self.dims[1]}")
+        if taps > 1 and stride < fb:
+            raise ValueError(f"stride={stride} is below fb={fb}")
+        if (taps - 1) * (stride if taps > 1 else 0) + fb > self.dims[0]:
+            raise ValueError(f"(taps - 1) * stride + fb = {(taps - 1) * stride + fb} exceeds input_dim {self.dims[0]}")
+        if ((taps - 1) * dN + 1) * fb > capi.TUBE_RING_MAX:
+            raise ValueError(f"ring ((taps - 1) * dN + 1) * fb = {((taps - 1) * dN + 1) * fb} floats per sequence exceeds "
+                             f"{capi.TUBE_RING_MAX}")
+        rp = None
+        if reseed is not None:
+            reseed = reseed.to(self.device).ne(0).to(torch.uint8).contiguous()
+            if tuple(reseed.shape) != tuple(x.shape[:2]):
+                raise ValueError(f"reseed must be {tuple(x.shape[:2])}; got {tuple(reseed.shape)}")
+            rp = C.c_void_p(reseed.data_ptr())
+        out = torch.empty(x.shape[0], x.shape[1], self.dims[1], device=self.device, dtype=torch.float32)
+        self._call("rollout_window", C.c_void_p(x.data_ptr()), x.shape[0], x.shape[1], fb, taps, dN, stride if taps > 1 else 0, rp,
+                   C.c_void_p(out.data_ptr()))
         self._keep = (x, reseed)
         return out
 

@@ -6,8 +6,14 @@
     rollout_vector_64 / _4096    the same with 128 units x 2 layers Softplus(beta 5), vector rows (|e|, z, v: 6 inputs, 2 outputs,
                                  2 columns fed back)
     oneshot                      ScalarHorizonTubeDataset 50 / 10, 128 units x 2 layers Softplus: 4096 envs x every 10th window
-Torch eager is the literal loop: T times (write the fed-back columns, run the nn.Sequential on the batch); for the one-shot config
-the gather of every window by advanced indexing, then one forward.  Each timing ends in a device synchronise; median of
+    window_scalar_64 / _4096     the windowed closed loop (rollout_window), recursive scalar rows with N = 10 taps of (w, v):
+                                 30 inputs, 1 output, 1 column fed back per tap, 32 units x 2 layers ReLU
+    window_error_64 / _4096      the same for error-dynamics rows, N = 10 taps of (e, z, v): 60 inputs, 2 outputs, 2 columns fed
+                                 back per tap, 128 units x 2 layers Softplus(beta 5)
+                                 Both also time rollout() -- one tap fed back -- on the same model and rows: the ring's cost.
+Torch eager is the literal loop: T times (write the fed-back columns -- for the windowed configs those of every tap, from the
+loop's own past outputs, as the reference's evaluate_error_dyn_simple.py gathers them -- and run the nn.Sequential on the batch);
+for the one-shot config the gather of every window by advanced indexing, then one forward.  Each timing ends in a device synchronise; median of
 --repeats runs after a warm-up run of the same shape.
 
     python tools/bench_tube_eval.py [--configs a,b] [--repeats 3] [--steps 1000]
@@ -29,7 +35,10 @@ from tests import tube_ref  # noqa: E402
 DEV = "cuda:0"
 MODELS = {"default": dict(I=3, O=1, U=32, L=2, act="relu", beta=1.0, fb=1),
           "vector": dict(I=6, O=2, U=128, L=2, act="softplus", beta=5.0, fb=2)}
-CONFIGS = ["rollout_default_64", "rollout_default_4096", "rollout_vector_64", "rollout_vector_4096", "oneshot"]
+WINDOWS = {"scalar": dict(I=30, O=1, U=32, L=2, act="relu", beta=1.0, fb=1, taps=10, dN=1, stride=3),
+           "error": dict(I=60, O=2, U=128, L=2, act="softplus", beta=5.0, fb=2, taps=10, dN=1, stride=6)}
+CONFIGS = ["rollout_default_64", "rollout_default_4096", "rollout_vector_64", "rollout_vector_4096", "oneshot",
+           "window_scalar_64", "window_scalar_4096", "window_error_64", "window_error_4096"]
 
 
 class _Horizon:
@@ -83,6 +92,37 @@ def bench_rollout(name, n_seq, T, repeats):
             "hip_us_per_step": hip_t * 1e6 / T, "max_abs_diff": diff, "torch_launches": T * (2 * k["L"] + 1)}
 
 
+def bench_window(name, n_seq, T, repeats):
+    k = WINDOWS[name]
+    g = torch.Generator().manual_seed(0)
+    x = (torch.rand(n_seq, T, k["I"], generator=g) * 0.8).to(DEV)
+    m = HipTubeModel(initial_params(k["I"], k["O"], k["U"], k["L"], 1), activation=k["act"], softplus_beta=k["beta"], device=DEV)
+    ref, fb, taps, dN, stride = torch_model(m), k["fb"], k["taps"], k["dN"], k["stride"]
+    xt = x.transpose(0, 1).contiguous()
+
+    def eager():
+        out = torch.empty(T, n_seq, k["O"], device=DEV)
+        with torch.no_grad():
+            for t in range(T):
+                row = xt[t]
+                if t:
+                    row = row.clone()
+                    for i in range(min(taps, (t - 1) // dN + 1)):
+                        row[:, i * stride:i * stride + fb] = out[t - 1 - i * dN, :, :fb]
+                out[t] = ref(row)
+        return out
+    hip_t, hip_all = timed(lambda: m.rollout_window(x, fb, taps, dN, stride), repeats)
+    one_t, one_all = timed(lambda: m.rollout(x, fb), repeats)
+    ref_t, ref_all = timed(eager, repeats)
+    diff = float((m.rollout_window(x, fb, taps, dN, stride).transpose(0, 1) - eager()).abs().max())
+    m.close()
+    return {"n_seq": n_seq, "T": T, "taps": taps, "dN": dN, "hip_ms": hip_t * 1e3, "hip_single_tap_ms": one_t * 1e3,
+            "torch_eager_ms": ref_t * 1e3, "speedup": ref_t / hip_t, "window_over_single_tap": hip_t / one_t,
+            "hip_ms_all": [t * 1e3 for t in hip_all], "hip_single_tap_ms_all": [t * 1e3 for t in one_all],
+            "torch_eager_ms_all": [t * 1e3 for t in ref_all], "hip_us_per_step": hip_t * 1e6 / T,
+            "hip_single_tap_us_per_step": one_t * 1e6 / T, "max_abs_diff": diff}
+
+
 def bench_oneshot(repeats):
     E, T, Hf, Hr, nz, mv = 4096, 1000, 50, 10, 2, 2
     g = torch.Generator().manual_seed(0)
@@ -121,8 +161,8 @@ def main():
         if cfg == "oneshot":
             res = bench_oneshot(a.repeats)
         else:
-            _, name, n = cfg.split("_")
-            res = bench_rollout(name, int(n), a.steps, a.repeats)
+            kind, name, n = cfg.split("_")
+            res = (bench_window if kind == "window" else bench_rollout)(name, int(n), a.steps, a.repeats)
         res = {"config": cfg, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
                **{k: (round(v, 4) if isinstance(v, float) else v) for k, v in res.items()}}
         print(json.dumps(res), flush=True)
