@@ -524,6 +524,35 @@ int lg_tube_rollout(lg_tube *t, const float *x, int64_t n_seq, int32_t T, int32_
 int lg_tube_rollout_window(lg_tube *t, const float *x, int64_t n_seq, int32_t T, int32_t fb, int32_t taps, int32_t dN,
                            int32_t stride, const uint8_t *reseed, float *out);
 
+/* ------------------------------------------------------------------ sweep of tube trainers: K models
+ * of one shape train on one dataset in the same two launches per step, the members along the grid's y axis.  Member k is, bit for
+ * bit, the lg_tube built from cfgs[k] and given the same calls.  Members share input_dim, output_dim, num_units, num_layers, loss,
+ * horizon, H_fwd, H_rev and batch_size; they may differ in alpha, delta, activation, softplus_beta, lr, gamma, step_size and seed.
+ * Every member owns a full set of a single trainer's buffers (parameters, moments, gradient slab, log, eval, starts, perm), so a
+ * sweep takes K times a single trainer's memory; the dataset is held once.  The members step together: one step count, one
+ * position in the epoch (each member in its own permutation).  Every entry returns 0, or -1 / a negative code with the reason in
+ * lg_last_error. */
+#define LG_TUBE_SWEEP_MAX 64
+typedef struct lg_tube_sweep lg_tube_sweep;
+/* -1: K outside 1..LG_TUBE_SWEEP_MAX; a member outside lg_tube_check_cfg's envelope (the message names the member and the reason);
+ * a shared field that differs (the message names the field and both members).  -100: a failed allocation. */
+int lg_tube_sweep_create(const lg_tube_cfg *cfgs, int32_t K, lg_tube_sweep **out);
+int lg_tube_sweep_destroy(lg_tube_sweep *s);
+int lg_tube_sweep_set_stream(lg_tube_sweep *s, void *stream);
+int lg_tube_sweep_get_buffers(lg_tube_sweep *s, int32_t k, lg_tube_buffers *out);   /* member k's buffers */
+int lg_tube_sweep_param_layout(lg_tube_sweep *s, int64_t *offsets, int64_t *shapes, int max_entries);   /* as lg_tube_param_layout */
+int lg_tube_sweep_params_changed(lg_tube_sweep *s, int32_t k);   /* after the caller wrote member k's params; k = -1: all members
+                                                                    (one launch per member) */
+int lg_tube_sweep_set_step(lg_tube_sweep *s, int64_t step);
+/* The arguments of lg_tube_set_data; the split is shared by all members. */
+int lg_tube_sweep_set_data(lg_tube_sweep *s, int which, const float *x, const float *y, const float *v, int64_t rows, int32_t T,
+                           int32_t nz, int32_t m);
+int lg_tube_sweep_begin_epoch(lg_tube_sweep *s, int64_t epoch);   /* every member's permutation, keyed by (its seed, epoch); one launch */
+/* One Adam step of every member on `count` rows: rows (device, count) shared by all members, or NULL = the next count rows of
+ * each member's own permutation.  Two launches for all members. */
+int lg_tube_sweep_step(lg_tube_sweep *s, const int32_t *rows, int64_t count);
+int lg_tube_sweep_eval(lg_tube_sweep *s);          /* every member's test metrics into its lg_tube_buffers.eval; two launches */
+
 /* ------------------------------------------------------------------ ROM-on-ROM simulator (deep_tube_learning/custom_sim.py
  * CustomSim with the `custom` branch of data_collection_trajectory.py:87-90 and configs/data_generation/double_single_int.yaml;
  * DESIGN.md section 10.2): a DoubleInt2D "robot" (state x, y, vx, vy; input = acceleration) tracks the random trajectory of the

@@ -189,6 +189,7 @@ class lg_ppo_rnn_buffers(C.Structure):
 
 
 TUBE_MAX_IN, TUBE_MAX_OUT, TUBE_MAX_UNITS = 256, 64, 128     # LG_TUBE_MAX_*; num_units a multiple of 16, num_layers 1..4
+TUBE_SWEEP_MAX = 64                                             # LG_TUBE_SWEEP_MAX: members of one lg_tube_sweep
 TUBE_RING_MAX = 1024                                            # LG_TUBE_RING_MAX: floats of output history per sequence (rollout_window)
 TUBE_ACT = {"relu": 0, "softplus": 1, "tanh": 2, "elu": 3}      # LG_TUBE_ACT_*
 TUBE_LOSS = {"scalar": 0, "vector": 1, "mse": 2}                # LG_TUBE_LOSS_*
@@ -229,6 +230,17 @@ def declare_tube_api(lib):
     lib.lg_tube_predict_windows.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp]
     lib.lg_tube_rollout.argtypes = [vp, vp, i64, i32, i32, vp, vp]
     lib.lg_tube_rollout_window.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp]
+    lib.lg_tube_sweep_create.argtypes = [C.POINTER(lg_tube_cfg), i32, C.POINTER(vp)]
+    lib.lg_tube_sweep_destroy.argtypes = [vp]
+    lib.lg_tube_sweep_set_stream.argtypes = [vp, vp]
+    lib.lg_tube_sweep_get_buffers.argtypes = [vp, i32, C.POINTER(lg_tube_buffers)]
+    lib.lg_tube_sweep_param_layout.argtypes = [vp, PI64, PI64, C.c_int]
+    lib.lg_tube_sweep_params_changed.argtypes = [vp, i32]
+    lib.lg_tube_sweep_set_step.argtypes = [vp, i64]
+    lib.lg_tube_sweep_set_data.argtypes = [vp, C.c_int, vp, vp, vp, i64, i32, i32, i32]
+    lib.lg_tube_sweep_begin_epoch.argtypes = [vp, i64]
+    lib.lg_tube_sweep_step.argtypes = [vp, vp, i64]
+    lib.lg_tube_sweep_eval.argtypes = [vp]
 
 
 RS_SLOT_ROOT, RS_SLOT_MASK, RS_SLOT_DIST, RS_SLOT_RAMP, RS_NRESET, RS_NOBS = 0, 4, 5, 7, 9, 8     # LG_RS_*

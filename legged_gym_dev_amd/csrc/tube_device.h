@@ -35,3 +35,9 @@ struct TubeDev {                        // passed by value to kernels
     int32_t *perm;
     int64_t log_cap;
 };
+
+struct TubeMember {                     // one model of a sweep (lg_tube_sweep); the kernels index a device array of these by blockIdx.y
+    TubeDev dev;                        // its own buffers, alpha / delta / activation / seed; the shape is the same in every member
+    double lr0, gamma;                  // its Adam rate and StepLR schedule
+    int64_t step_size;
+};

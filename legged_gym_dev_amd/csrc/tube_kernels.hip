@@ -1,6 +1,7 @@
 // Tube-model trainer kernels (deep_tube_learning's train_tube.py on the device).
 //
-// Model: the reference MLP -- Linear, activation, repeated num_layers times, then a final Linear.  One training step is two launches:
+// Model: the reference MLP -- Linear, activation, repeated num_layers times, then a final Linear.  One training step is two launches
+// (for a sweep of K models of one shape the same two, k_tube_rows_sweep / k_tube_adam_sweep, with the members along grid y):
 //   k_tube_rows<true>  every workgroup owns LG_TUBE_ROWS rows of the minibatch: gathers them (through the epoch permutation or an
 //                      explicit row list; for the horizon dataset it draws the window start and builds input / target in place),
 //                      runs the forward pass with every hidden activation kept in LDS, the loss and its gradient, the backward
@@ -48,7 +49,8 @@ __device__ __forceinline__ float tube_huber(float delta, float l, float *dh) {
 }
 
 // Window start of row `pos` of a draw: uniform over [H_rev, T - H_fwd - 1), Philox keyed by (seed, draw key, row position).
-__device__ __forceinline__ int tube_window(const TubeDev &D, uint64_t key, int64_t pos) {
+template <class Dev>                    // TubeDev, or a sweep kernel's TubeDevView
+__device__ __forceinline__ int tube_window(const Dev &D, uint64_t key, int64_t pos) {
     uint32_t c[4] = {(uint32_t)pos, (uint32_t)key, (uint32_t)(key >> 32), 0x7ab3e5u ^ (uint32_t)(pos >> 32)};
     philox4x32((uint32_t)D.seed, (uint32_t)(D.seed >> 32), c);
     const uint32_t range = (uint32_t)(D.T - D.H_fwd - 1 - D.H_rev);
@@ -57,175 +59,53 @@ __device__ __forceinline__ int tube_window(const TubeDev &D, uint64_t key, int64
 
 // One tile of rows: gather, forward, loss (+ backward into the slab row when TRAIN, eval partial sums otherwise).
 // rows: row ids of the batch (position base + r); count: rows in the batch; norm: the loss's divisor (elements or rows).
+// The body is tube_rows_tile.inl, included by k_tube_rows (D in the kernel arguments) and k_tube_rows_sweep (D in the member array):
+// as a device function it inlined into k_tube_rows with a different schedule, and the single kernel is to stay as it was.
 template <bool TRAIN>
 __global__ void __launch_bounds__(NT) k_tube_rows(TubeDev D, TubeSplit S, const int32_t *rows, int64_t count, uint64_t key, float norm) {
-    extern __shared__ float lds[];
-    const int tid = threadIdx.x, I = D.in_dim, O = D.out_dim, U = D.units, L = D.layers;
-    const int64_t base = (int64_t)blockIdx.x * R;
-    const int nr = (int)(count - base < R ? count - base : R);
-    float *X = lds;                     // (R, I) input
-    float *H = X + R * I;               // (L, R, U) hidden activations
-    float *F = H + L * R * U;           // (R, O) fw, then dLoss/dfw
-    float *Y = F + R * O;               // (R, O) target
-    float *D0 = Y + R * O, *D1 = D0 + R * U;   // (R, U) deltas, ping-pong
-    __shared__ float rowloss[R], rowpos[R], rowerr[R];
-    __shared__ int64_t src[R];
-    __shared__ int ind[R];
+#include "tube_rows_tile.inl"
+}
 
-    if (tid < R) {
-        const int64_t s = tid < nr ? (int64_t)rows[base + tid] : -1;
-        src[tid] = s >= 0 && s < S.rows ? s : -1;     // a row id outside the split reads nothing (zero input and target)
-        if (D.horizon && tid < nr) {
-            ind[tid] = tube_window(D, key, base + tid);
-            D.starts[base + tid] = ind[tid];
-        }
-    }
-    __syncthreads();
-    // ---- gather
-    for (int e = tid; e < R * I; e += NT) {
-        const int r = e / I, c = e - r * I;
-        const int64_t s = src[r];
-        float x = 0.f;
-        if (s >= 0) {
-            if (!D.horizon) x = S.x[s * I + c];
-            else {
-                const int t0 = ind[r];
-                if (c < D.H_rev) x = S.x[s * D.T + t0 - D.H_rev + c];
-                else if (c < D.H_rev + D.nz) x = S.y[(s * D.T + t0) * D.nz + (c - D.H_rev)];
-                else {
-                    const int q = c - D.H_rev - D.nz, tt = q / D.m;
-                    x = S.v[(s * D.T + t0 - D.H_rev + tt) * D.m + (q - tt * D.m)];
-                }
-            }
-        }
-        X[e] = x;
-    }
-    for (int e = tid; e < R * O; e += NT) {
-        const int r = e / O, j = e - r * O;
-        const int64_t s = src[r];
-        Y[e] = s < 0 ? 0.f : D.horizon ? S.x[s * D.T + ind[r] + 1 + j] : S.y[s * O + j];
-    }
-    __syncthreads();
-    // ---- forward: out[r][j] = b[j] + sum_k W[j][k] in[r][k]; lanes over j (coalesced reads of the transposed weights), RB rows each
-    for (int li = 0; li <= L; ++li) {
-        const int K = D.din[li], N = D.dout[li];
-        const float *in = li == 0 ? X : H + (li - 1) * R * U;
-        float *out = li == L ? F : H + li * R * U;
-        const float *wt = D.wt + D.off_w[li], *b = D.params + D.off_b[li];
-        for (int e = tid; e < N * (R / RB); e += NT) {
-            const int j = e % N, r0 = (e / N) * RB;
-            float acc[RB];
-#pragma unroll
-            for (int q = 0; q < RB; ++q) acc[q] = 0.f;
-            for (int k = 0; k < K; ++k) {
-                const float w = wt[(int64_t)k * N + j];
-#pragma unroll
-                for (int q = 0; q < RB; ++q) acc[q] = fmaf(in[(r0 + q) * K + k], w, acc[q]);
-            }
-            const float bj = b[j];
-#pragma unroll
-            for (int q = 0; q < RB; ++q) {
-                const float z = acc[q] + bj;
-                out[(r0 + q) * N + j] = li == L ? z : tube_act(D.act, z, D.sp_beta);
-            }
-        }
-        __syncthreads();
-    }
-    // ---- loss per row (fixed order inside the row), dLoss/dfw into F
-    if (tid < R) {
-        float ls = 0.f, pos = 0.f, err = 0.f;
-        if (tid < nr) {
-            float *f = F + tid * O;
-            const float *y = Y + tid * O;
-            if (D.loss == LG_TUBE_LOSS_MSE) {
-                for (int j = 0; j < O; ++j) {
-                    const float d = f[j] - y[j];
-                    ls += d * d;
-                    if (TRAIN) f[j] = 2.f * d / norm;
-                }
-            } else if (D.loss == LG_TUBE_LOSS_SCALAR) {
-                for (int j = 0; j < O; ++j) {
-                    float dl, dh;
-                    const float fw = f[j];
-                    if (fw > y[j]) { pos += 1.f; err += fabsf(y[j] - fw); }
-                    ls += tube_huber(D.delta, tube_pinball(D.alpha, y[j], fw, &dl), &dh);
-                    if (TRAIN) f[j] = dh * dl / norm;
-                }
-            } else {                    // VectorTubeLoss: the pinball residuals summed over the row, then Huber
-                float lsum = 0.f, dh;
-                for (int j = 0; j < O; ++j) {
-                    float dl;
-                    const float fw = f[j];
-                    if (fw > y[j]) { pos += 1.f; err += fabsf(y[j] - fw); }
-                    lsum += tube_pinball(D.alpha, y[j], fw, &dl);
-                }
-                ls = tube_huber(D.delta, lsum, &dh);
-                if (TRAIN)
-                    for (int j = 0; j < O; ++j) {
-                        float dl;
-                        tube_pinball(D.alpha, y[j], f[j], &dl);
-                        f[j] = dh * dl / norm;
-                    }
-            }
-        } else if (TRAIN) {
-            for (int j = 0; j < O; ++j) F[tid * O + j] = 0.f;   // rows past the batch contribute nothing
-        }
-        rowloss[tid] = ls; rowpos[tid] = pos; rowerr[tid] = err;
-    }
-    __syncthreads();
-    if (!TRAIN) {
-        if (tid == 0) {
-            float a = 0.f, b = 0.f, c = 0.f;
-            for (int r = 0; r < R; ++r) { a += rowloss[r]; b += rowpos[r]; c += rowerr[r]; }
-            float *p = D.evpart + (size_t)blockIdx.x * 4;
-            p[0] = a; p[1] = b; p[2] = c; p[3] = (float)nr;
-        }
-        return;
-    }
-    float *g = D.slab + (size_t)blockIdx.x * D.slab_ld;
-    if (tid == 0) {
-        float a = 0.f;
-        for (int r = 0; r < R; ++r) a += rowloss[r];
-        g[D.num_params] = a;
-    }
-    // ---- backward, output layer first
-    float *dcur = F, *dnext = D0;
-    for (int li = L; li >= 0; --li) {
-        const int K = D.din[li], N = D.dout[li];
-        const float *a = li == 0 ? X : H + (li - 1) * R * U;
-        // weight gradient dW[j][k] = sum_r d[r][j] a[r][k] (lanes over k), bias gradient db[j] = sum_r d[r][j]
-        for (int e = tid; e < N * K; e += NT) {
-            const int j = e / K, k = e - j * K;
-            float acc = 0.f;
-#pragma unroll 8
-            for (int r = 0; r < R; ++r) acc = fmaf(dcur[r * N + j], a[r * K + k], acc);
-            g[D.off_w[li] + e] = acc;
-        }
-        for (int j = tid; j < N; j += NT) {
-            float acc = 0.f;
-            for (int r = 0; r < R; ++r) acc += dcur[r * N + j];
-            g[D.off_b[li] + j] = acc;
-        }
-        if (li == 0) break;
-        // input gradient through the activation: dprev[r][k] = act'(a[r][k]) sum_j W[j][k] d[r][j] (lanes over k)
-        const float *W = D.params + D.off_w[li];
-        for (int e = tid; e < K * (R / RB); e += NT) {
-            const int k = e % K, r0 = (e / K) * RB;
-            float acc[RB];
-#pragma unroll
-            for (int q = 0; q < RB; ++q) acc[q] = 0.f;
-            for (int j = 0; j < N; ++j) {
-                const float w = W[(int64_t)j * K + k];
-#pragma unroll
-                for (int q = 0; q < RB; ++q) acc[q] = fmaf(dcur[(r0 + q) * N + j], w, acc[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < RB; ++q) dnext[(r0 + q) * K + k] = acc[q] * tube_act_grad(D.act, a[(r0 + q) * K + k], D.sp_beta);
-        }
-        __syncthreads();
-        dcur = dnext;
-        dnext = dnext == D0 ? D1 : D0;
-    }
+// Member blockIdx.y of a sweep's device array.  The array is read-only for the whole launch, and it is read through the constant
+// address space: the loads are scalar, and the compiler takes the pointers stored in it for global ones (global_load /
+// global_store), where pointers loaded from global memory are generic and every weight load and slab store would be a flat access.
+#define TUBE_CONST __attribute__((address_space(4)))
+__device__ __forceinline__ const TUBE_CONST TubeMember &tube_member(const TubeMember *M) { return ((const TUBE_CONST TubeMember *)M)[blockIdx.y]; }
+
+// What k_tube_rows_sweep / k_tube_adam_sweep hold of their member's TubeDev, under TubeDev's field names.  The single kernels get
+// their TubeDev in the kernel arguments: loads the compiler knows to be invariant, so a field read inside a loop (D.horizon in the
+// gather, D.act after every dot product, D.layers per parameter of the Adam loop) costs nothing there.  Read from the member array
+// in place, the same field was loaded again in every iteration, with a wait that also drains the loop's LDS reads.  So every scalar
+// and pointer is read once, at kernel entry, into registers; the per-layer tables stay in the array and are read per layer.
+struct TubeDevView {
+    int in_dim, out_dim, units, layers, act, loss, horizon;
+    int H_fwd, H_rev, T, nz, m;
+    float alpha, delta, sp_beta;
+    uint64_t seed;
+    int64_t num_params, slab_ld;
+    const TUBE_CONST int64_t *off_w, *off_b;
+    const TUBE_CONST int *din, *dout;
+    float *params, *wt, *grads, *adam_m, *adam_v, *slab, *evpart, *normpart;
+    uint32_t *done_ctr;
+    float *log, *eval;
+    int32_t *starts, *perm;
+    int64_t log_cap;
+    __device__ __forceinline__ TubeDevView(const TUBE_CONST TubeDev &d)
+        : in_dim(d.in_dim), out_dim(d.out_dim), units(d.units), layers(d.layers), act(d.act), loss(d.loss), horizon(d.horizon),
+          H_fwd(d.H_fwd), H_rev(d.H_rev), T(d.T), nz(d.nz), m(d.m), alpha(d.alpha), delta(d.delta), sp_beta(d.sp_beta), seed(d.seed),
+          num_params(d.num_params), slab_ld(d.slab_ld), off_w(d.off_w), off_b(d.off_b), din(d.din), dout(d.dout), params(d.params),
+          wt(d.wt), grads(d.grads), adam_m(d.adam_m), adam_v(d.adam_v), slab(d.slab), evpart(d.evpart), normpart(d.normpart),
+          done_ctr(d.done_ctr), log(d.log), eval(d.eval), starts(d.starts), perm(d.perm), log_cap(d.log_cap) {}
+};
+
+// The same tile for member blockIdx.y of a sweep (grid = (tiles, K)).  rows: a row list shared by all members, or null: the
+// member's own epoch permutation from position pos.
+template <bool TRAIN>
+__global__ void __launch_bounds__(NT) k_tube_rows_sweep(const TubeMember *__restrict__ M, TubeSplit S, const int32_t *rows, int64_t pos,
+                                                        int64_t count, uint64_t key, float norm) {
+    const TubeDevView D(tube_member(M).dev);
+    if (!rows) rows = D.perm + pos;
+#include "tube_rows_tile.inl"
 }
 
 // transposed copy of every weight matrix (after the host wrote params)
@@ -241,61 +121,23 @@ __global__ void k_tube_wt(TubeDev D) {
 
 // Reduce the nwg slab rows in order, torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8, no weight decay) at StepLR's rate,
 // log [loss, lr after the step, grad_norm, rows] at slot (t - 1) % log_cap.  t: Adam's step count after this step (>= 1).
+// The body is tube_adam_block.inl, for the same reason as tube_rows_tile.inl.
 __global__ void __launch_bounds__(256) k_tube_adam(TubeDev D, int nwg, int64_t t, double lr0, double gamma, int64_t step_size,
                                                    float norm, int64_t rows) {
-    __shared__ float red[256];
-    __shared__ bool last;
-    const int64_t P = D.num_params;
-    const double lr = lr0 * pow(gamma, (double)((t - 1) / step_size));
-    const double bc1 = 1.0 - pow(0.9, (double)t), bc2 = 1.0 - pow(0.999, (double)t);
-    const float neg_step = (float)(-(lr / bc1)), bc2s = (float)sqrt(bc2);
-    float sq = 0.f;
-    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < P; p += (int64_t)gridDim.x * blockDim.x) {
-        float g = 0.f;
-        for (int w = 0; w < nwg; ++w) g += D.slab[(size_t)w * D.slab_ld + p];
-        D.grads[p] = g;
-        sq = fmaf(g, g, sq);
-        float m = D.adam_m[p], v = D.adam_v[p];
-        m = m + 0.1f * (g - m);                       // exp_avg.lerp_(grad, 1 - beta1)
-        v = v * 0.999f + 0.001f * g * g;              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-        const float denom = sqrtf(v) / bc2s + 1e-8f;
-        const float np = D.params[p] + neg_step * (m / denom);
-        D.adam_m[p] = m; D.adam_v[p] = v; D.params[p] = np;
-        for (int li = 0; li <= D.layers; ++li) {      // keep the transposed weight copy current
-            const int64_t o = p - D.off_w[li];
-            if (o >= 0 && o < (int64_t)D.din[li] * D.dout[li]) {
-                const int K = D.din[li], N = D.dout[li], j = (int)(o / K), k = (int)(o - (int64_t)j * K);
-                D.wt[D.off_w[li] + (int64_t)k * N + j] = np;
-            }
-        }
-    }
-    red[threadIdx.x] = sq;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        D.normpart[blockIdx.x] = red[0];
-        __threadfence();
-        last = atomicAdd(D.done_ctr, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last || threadIdx.x != 0) return;
-    __threadfence();
-    float n2 = 0.f, ls = 0.f;
-    for (unsigned b = 0; b < gridDim.x; ++b) n2 += __hip_atomic_load(D.normpart + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int w = 0; w < nwg; ++w) ls += D.slab[(size_t)w * D.slab_ld + P];
-    float *lg = D.log + (size_t)((t - 1) % D.log_cap) * 4;
-    lg[0] = ls / norm;
-    lg[1] = (float)(lr0 * pow(gamma, (double)(t / step_size)));   // get_last_lr() after lr_scheduler.step()
-    lg[2] = sqrtf(n2);
-    lg[3] = (float)rows;
-    atomicExch(D.done_ctr, 0u);
+#include "tube_adam_block.inl"
+}
+
+// member blockIdx.y of a sweep: its own slab, moments, rate schedule, counter and log (grid = (blocks, K))
+__global__ void __launch_bounds__(256) k_tube_adam_sweep(const TubeMember *__restrict__ M, int nwg, int64_t t, float norm, int64_t rows) {
+    const TUBE_CONST TubeMember &m = tube_member(M);
+    const TubeDevView D(m.dev);
+    const double lr0 = m.lr0, gamma = m.gamma;
+    const int64_t step_size = m.step_size;
+#include "tube_adam_block.inl"
 }
 
 // the eval's per-workgroup sums, in workgroup order
-__global__ void __launch_bounds__(256) k_tube_eval_finish(TubeDev D, int nwg, float norm, float elems) {
+__device__ __forceinline__ void tube_eval_finish_block(const TubeDev &D, int nwg, float norm, float elems) {
     __shared__ float red[4][256];
     float a[4] = {0.f, 0.f, 0.f, 0.f};
     for (int w = threadIdx.x; w < nwg; w += 256)
@@ -315,10 +157,24 @@ __global__ void __launch_bounds__(256) k_tube_eval_finish(TubeDev D, int nwg, fl
     }
 }
 
-__global__ void __launch_bounds__(256) k_tube_perm(TubeDev D, int n, int half_bits, uint64_t epoch) {
+__global__ void __launch_bounds__(256) k_tube_eval_finish(TubeDev D, int nwg, float norm, float elems) {
+    tube_eval_finish_block(D, nwg, norm, elems);
+}
+
+__global__ void __launch_bounds__(256) k_tube_eval_finish_sweep(const TubeMember *__restrict__ M, int nwg, float norm, float elems) {
+    tube_eval_finish_block((const TubeDev &)tube_member(M).dev, nwg, norm, elems);
+}
+
+__device__ __forceinline__ void tube_perm_entry(const TubeDev &D, int n, int half_bits, uint64_t epoch) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     D.perm[i] = (int32_t)feistel_perm(D.seed, epoch ^ 0x7475626500000000ull, n, half_bits, (uint32_t)i);
+}
+
+__global__ void __launch_bounds__(256) k_tube_perm(TubeDev D, int n, int half_bits, uint64_t epoch) { tube_perm_entry(D, n, half_bits, epoch); }
+
+__global__ void __launch_bounds__(256) k_tube_perm_sweep(const TubeMember *__restrict__ M, int n, int half_bits, uint64_t epoch) {
+    tube_perm_entry((const TubeDev &)tube_member(M).dev, n, half_bits, epoch);
 }
 
 __global__ void k_tube_iota(int32_t *p, int64_t n) {
@@ -629,6 +485,8 @@ int tubek_init() {
     const int lim = (int)(sizeof(float) * R * (LG_TUBE_MAX_IN + 4 * LG_TUBE_MAX_UNITS + 2 * LG_TUBE_MAX_OUT + 2 * LG_TUBE_MAX_UNITS));
     if (hipFuncSetAttribute((const void *)k_tube_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
     if (hipFuncSetAttribute((const void *)k_tube_rows<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
+    if (hipFuncSetAttribute((const void *)k_tube_rows_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
+    if (hipFuncSetAttribute((const void *)k_tube_rows_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
     const int plim = (int)(sizeof(float) * R * (LG_TUBE_MAX_IN + 2 * LG_TUBE_MAX_UNITS));
     if (hipFuncSetAttribute((const void *)k_tube_predict, hipFuncAttributeMaxDynamicSharedMemorySize, plim) != hipSuccess) return -1;
     for (const void *f : {(const void *)k_tube_rollout<1, 64, true>, (const void *)k_tube_rollout<1, 64, false>,
@@ -654,6 +512,29 @@ void tubek_eval(const TubeDev *D, const TubeSplit *S, const int32_t *rows, uint6
     const int nwg = (int)((S->rows + R - 1) / R);
     hipLaunchKernelGGL(k_tube_rows<false>, dim3(nwg), dim3(NT), tubek_lds_bytes(D), s, *D, *S, rows, S->rows, key, norm);
     hipLaunchKernelGGL(k_tube_eval_finish, dim3(1), dim3(256), 0, s, *D, nwg, norm, (float)(S->rows * (int64_t)D->out_dim));
+}
+// ---- sweep: the same launches with the members along grid y.  M: device array of K members; D0: member 0's host copy (the shape).
+void tubek_step_sweep(const TubeMember *M, int K, const TubeDev *D0, const TubeSplit *S, const int32_t *rows, int64_t pos, int64_t count,
+                      uint64_t key, float norm, hipStream_t s) {
+    const int nwg = (int)((count + R - 1) / R);
+    hipLaunchKernelGGL(k_tube_rows_sweep<true>, dim3(nwg, K), dim3(NT), tubek_lds_bytes(D0), s, M, *S, rows, pos, count, key, norm);
+}
+void tubek_adam_sweep(const TubeMember *M, int K, const TubeDev *D0, int nwg, int64_t t, float norm, int64_t rows, hipStream_t s) {
+    int blocks = (int)((D0->num_params + 255) / 256);
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_tube_adam_sweep, dim3(blocks, K), dim3(256), 0, s, M, nwg, t, norm, rows);
+}
+void tubek_eval_sweep(const TubeMember *M, int K, const TubeDev *D0, const TubeSplit *S, const int32_t *rows, uint64_t key, float norm,
+                      hipStream_t s) {
+    const int nwg = (int)((S->rows + R - 1) / R);
+    hipLaunchKernelGGL(k_tube_rows_sweep<false>, dim3(nwg, K), dim3(NT), tubek_lds_bytes(D0), s, M, *S, rows, (int64_t)0, S->rows, key, norm);
+    hipLaunchKernelGGL(k_tube_eval_finish_sweep, dim3(1, K), dim3(256), 0, s, M, nwg, norm, (float)(S->rows * (int64_t)D0->out_dim));
+}
+void tubek_perm_sweep(const TubeMember *M, int K, int n, uint64_t epoch, hipStream_t s) {
+    int bits = 2;
+    while ((1ll << bits) < n) ++bits;
+    bits += bits & 1;
+    hipLaunchKernelGGL(k_tube_perm_sweep, dim3((n + 255) / 256, K), dim3(256), 0, s, M, n, bits / 2, epoch);
 }
 void tubek_wt(const TubeDev *D, hipStream_t s) { hipLaunchKernelGGL(k_tube_wt, dim3(64), dim3(256), 0, s, *D); }
 void tubek_perm(const TubeDev *D, int n, uint64_t epoch, hipStream_t s) {

@@ -1,1 +1,2 @@
-"""Tube learning: train a tube MLP on the ROM tracking data that scripts/collect_trajectory_data.py records."""
+"""Tube learning: train a tube MLP on the ROM tracking data that scripts/collect_trajectory_data.py records:
+trainer.HipTubeTrainer for one model, sweep.HipTubeSweep for K models of one shape in the same two launches per step."""
