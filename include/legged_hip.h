@@ -459,6 +459,7 @@ int lg_ppo_comm_wait_ms(lg_ppo *p, double *ms_total, int64_t *minibatches);
 #define LG_TUBE_LOSS_SCALAR 0                      /* ScalarTubeLoss / ScalarHorizonTubeLoss: Huber mean over rows x outputs */
 #define LG_TUBE_LOSS_VECTOR 1                      /* VectorTubeLoss: pinball residuals summed per row, Huber mean over rows */
 #define LG_TUBE_LOSS_MSE 2                         /* ErrorLoss */
+#define LG_TUBE_MAX_LEVELS 64                       /* levels of one lg_tube_predict_levels call */
 typedef struct lg_tube_cfg {
     int32_t input_dim, output_dim, num_units, num_layers;
     int32_t activation, loss, horizon /*0: flat (data, target) rows; 1: ScalarHorizonTubeDataset windows*/, batch_size;
@@ -466,6 +467,12 @@ typedef struct lg_tube_cfg {
     uint64_t seed;                                 /* epoch permutations and horizon window draws */
     float alpha, delta, softplus_beta, _padf;
     double lr, gamma;                              /* Adam lr0; StepLR: lr = lr0 * gamma^floor(step / step_size) */
+    /* Level-conditioned tube; 0 = off.  With level_input = 1 the LAST input column is the coverage level
+     * of the row: input_dim counts it, the data of lg_tube_set_data has input_dim - 1 columns, every step / eval draws one level
+     * per row, uniform over [level_lo, level_hi), and the row's pinball loss takes that level where it takes alpha otherwise
+     * (alpha is not read).  Needs a tube loss (not mse), horizon = 0, input_dim >= 2 and 0 <= level_lo < level_hi <= 1. */
+    int32_t level_input, _pad2;
+    float level_lo, level_hi;
 } lg_tube_cfg;
 
 typedef struct lg_tube_buffers {
@@ -476,6 +483,8 @@ typedef struct lg_tube_buffers {
     int32_t *starts;                               /* horizon dataset: window start drawn per row of the last step / eval */
     int32_t *perm;                                 /* the epoch's permutation of the training rows */
     int64_t num_params, log_cap, starts_cap, perm_cap, step;
+    float *levels;                                 /* level_input: the level of every row of the last step / eval (as starts) */
+    int64_t levels_cap;
 } lg_tube_buffers;
 
 typedef struct lg_tube lg_tube;
@@ -495,7 +504,11 @@ int lg_tube_set_data(lg_tube *t, int which, const float *x, const float *y, cons
 int lg_tube_begin_epoch(lg_tube *t, int64_t epoch);   /* a new permutation of the training rows, keyed by (seed, epoch) */
 /* One Adam step on `count` rows: rows (device, count) or NULL = the next count rows of the epoch's permutation. */
 int lg_tube_step(lg_tube *t, const int32_t *rows, int64_t count);
-int lg_tube_eval(lg_tube *t);                      /* metrics of the test split into lg_tube_buffers.eval (one window per row) */
+int lg_tube_eval(lg_tube *t);                      /* metrics of the test split into lg_tube_buffers.eval (one window per row;
+                                                      level_input: one drawn level per row) */
+/* level_input handles: lg_tube_eval with every test row at `level` (0..1) instead of a drawn one; eval[1] is then the coverage
+ * at that level.  -1 on an unconditioned handle. */
+int lg_tube_eval_level(lg_tube *t, float level);
 
 /* Inference.  The three entries read params / the transposed copy and change neither; all pointers are device pointers, everything
  * runs on the handle's stream and nothing waits for the device.  A row's result does not depend on the batch it is in.
@@ -504,6 +517,13 @@ int lg_tube_eval(lg_tube *t);                      /* metrics of the test split 
 /* out[i] = MLP(x[rows ? rows[i] : i]);  x (n, input_dim), out (count, output_dim).  Flat (non-horizon) handles.  The caller
  * guarantees 0 <= rows[i] < n. */
 int lg_tube_predict(lg_tube *t, const float *x, const int32_t *rows, int64_t count, float *out);
+/* level_input handles: out[i, l] = MLP([x[rows ? rows[i] : i], levels[l]]), one launch; x (n, input_dim - 1), levels (device,
+ * n_levels, 1 <= n_levels <= 64), out (count, n_levels, output_dim).  The part of the first layer that does not depend on the
+ * level is computed once per row.  Each out[i, l] equals, bit for bit, lg_tube_predict on that row with levels[l] appended.
+ * lg_tube_predict, lg_tube_rollout and lg_tube_rollout_window take rows of full input_dim on such a handle: the caller fills the
+ * level column, a teacher column like any other.  -1 on an unconditioned handle. */
+int lg_tube_predict_levels(lg_tube *t, const float *x, const int32_t *rows, int64_t count, const float *levels, int32_t n_levels,
+                           float *out);
 /* Horizon handles: item (env[i], start[i]) built as ScalarHorizonTubeDataset._get_item_helper does, out (count, H_fwd).
  * w (n, T), z (n, T, nz), v (n, T, m) padded in front by H_rev as for lg_tube_set_data.
  * Caller guarantees 0 <= env[i] < n, H_rev <= start[i] and start[i] + H_fwd <= T. */
@@ -527,7 +547,8 @@ int lg_tube_rollout_window(lg_tube *t, const float *x, int64_t n_seq, int32_t T,
 /* ------------------------------------------------------------------ sweep of tube trainers: K models
  * of one shape train on one dataset in the same two launches per step, the members along the grid's y axis.  Member k is, bit for
  * bit, the lg_tube built from cfgs[k] and given the same calls.  Members share input_dim, output_dim, num_units, num_layers, loss,
- * horizon, H_fwd, H_rev and batch_size; they may differ in alpha, delta, activation, softplus_beta, lr, gamma, step_size and seed.
+ * horizon, H_fwd, H_rev, batch_size and level_input; they may differ in alpha, delta, activation, softplus_beta, lr, gamma, step_size,
+ * seed, level_lo and level_hi.
  * Every member owns a full set of a single trainer's buffers (parameters, moments, gradient slab, log, eval, starts, perm), so a
  * sweep takes K times a single trainer's memory; the dataset is held once.  The members step together: one step count, one
  * position in the epoch (each member in its own permutation).  Every entry returns 0, or -1 / a negative code with the reason in
@@ -552,6 +573,7 @@ int lg_tube_sweep_begin_epoch(lg_tube_sweep *s, int64_t epoch);   /* every membe
  * each member's own permutation.  Two launches for all members. */
 int lg_tube_sweep_step(lg_tube_sweep *s, const int32_t *rows, int64_t count);
 int lg_tube_sweep_eval(lg_tube_sweep *s);          /* every member's test metrics into its lg_tube_buffers.eval; two launches */
+int lg_tube_sweep_eval_level(lg_tube_sweep *s, float level);   /* lg_tube_eval_level of every member; two launches */
 
 /* ------------------------------------------------------------------ ROM-on-ROM simulator (deep_tube_learning/custom_sim.py
  * CustomSim with the `custom` branch of data_collection_trajectory.py:87-90 and configs/data_generation/double_single_int.yaml;

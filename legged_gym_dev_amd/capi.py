@@ -192,6 +192,7 @@ TUBE_MAX_IN, TUBE_MAX_OUT, TUBE_MAX_UNITS = 256, 64, 128     # LG_TUBE_MAX_*; nu
 TUBE_SWEEP_MAX = 64                                             # LG_TUBE_SWEEP_MAX: members of one lg_tube_sweep
 TUBE_RING_MAX = 1024                                            # LG_TUBE_RING_MAX: floats of output history per sequence (rollout_window)
 TUBE_ACT = {"relu": 0, "softplus": 1, "tanh": 2, "elu": 3}      # LG_TUBE_ACT_*
+TUBE_MAX_LEVELS = 64                                            # levels of one lg_tube_predict_levels call
 TUBE_LOSS = {"scalar": 0, "vector": 1, "mse": 2}                # LG_TUBE_LOSS_*
 
 
@@ -202,14 +203,16 @@ class lg_tube_cfg(C.Structure):
         ("H_fwd", i32), ("H_rev", i32), ("step_size", i32), ("_pad", i32),
         ("seed", u64),
         ("alpha", f32), ("delta", f32), ("softplus_beta", f32), ("_padf", f32),
-        ("lr", C.c_double), ("gamma", C.c_double)]
+        ("lr", C.c_double), ("gamma", C.c_double),
+        ("level_input", i32), ("_pad2", i32), ("level_lo", f32), ("level_hi", f32)]
 
 
 class lg_tube_buffers(C.Structure):
     _fields_ = [
         ("params", PF), ("grads", PF), ("adam_m", PF), ("adam_v", PF), ("log", PF), ("eval", PF),
         ("starts", PI32), ("perm", PI32),
-        ("num_params", i64), ("log_cap", i64), ("starts_cap", i64), ("perm_cap", i64), ("step", i64)]
+        ("num_params", i64), ("log_cap", i64), ("starts_cap", i64), ("perm_cap", i64), ("step", i64),
+        ("levels", PF), ("levels_cap", i64)]
 
 
 def declare_tube_api(lib):
@@ -241,6 +244,9 @@ def declare_tube_api(lib):
     lib.lg_tube_sweep_begin_epoch.argtypes = [vp, i64]
     lib.lg_tube_sweep_step.argtypes = [vp, vp, i64]
     lib.lg_tube_sweep_eval.argtypes = [vp]
+    lib.lg_tube_eval_level.argtypes = [vp, f32]
+    lib.lg_tube_predict_levels.argtypes = [vp, vp, vp, i64, vp, i32, vp]
+    lib.lg_tube_sweep_eval_level.argtypes = [vp, f32]
 
 
 RS_SLOT_ROOT, RS_SLOT_MASK, RS_SLOT_DIST, RS_SLOT_RAMP, RS_NRESET, RS_NOBS = 0, 4, 5, 7, 9, 8     # LG_RS_*

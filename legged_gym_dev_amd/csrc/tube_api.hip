@@ -1,6 +1,6 @@
 // C-ABI (include/legged_hip.h, lg_tube_*) of the tube-model trainer: parameter / optimiser / slab allocation in HBM, epoch
 // permutation, the two launches of a training step, the eval launch, and the inference entries: predict, window prediction and
-// the closed-loop roll-outs, single-tap and windowed (tube_kernels.hip).  lg_tube_sweep_*: K such trainers of one shape on one
+// the closed-loop roll-outs, single-tap and windowed, and the level entries of a level-conditioned model (tube_kernels.hip).  lg_tube_sweep_*: K such trainers of one shape on one
 // dataset, stepped by the same two launches with the members along grid y.
 #include <cmath>
 #include <cstring>
@@ -18,7 +18,7 @@ int tubek_init();
 void tubek_step(const TubeDev *D, const TubeSplit *S, const int32_t *rows, int64_t count, uint64_t key, float norm, hipStream_t s);
 void tubek_adam(const TubeDev *D, int nwg, int64_t t, double lr0, double gamma, int64_t step_size, float norm, int64_t rows,
                 hipStream_t s);
-void tubek_eval(const TubeDev *D, const TubeSplit *S, const int32_t *rows, uint64_t key, float norm, hipStream_t s);
+void tubek_eval(const TubeDev *D, const TubeSplit *S, const int32_t *rows, uint64_t key, float norm, float level, hipStream_t s);
 void tubek_wt(const TubeDev *D, hipStream_t s);
 void tubek_perm(const TubeDev *D, int n, uint64_t epoch, hipStream_t s);
 void tubek_iota(int32_t *p, int64_t n, hipStream_t s);
@@ -26,7 +26,9 @@ void tubek_step_sweep(const TubeMember *M, int K, const TubeDev *D0, const TubeS
                       uint64_t key, float norm, hipStream_t s);
 void tubek_adam_sweep(const TubeMember *M, int K, const TubeDev *D0, int nwg, int64_t t, float norm, int64_t rows, hipStream_t s);
 void tubek_eval_sweep(const TubeMember *M, int K, const TubeDev *D0, const TubeSplit *S, const int32_t *rows, uint64_t key, float norm,
-                      hipStream_t s);
+                      float level, hipStream_t s);
+void tubek_predict_levels(const TubeDev *D, const float *x, const int32_t *rows, int64_t count, const float *levels, int n_levels,
+                          float *o, hipStream_t s);
 void tubek_perm_sweep(const TubeMember *M, int K, int n, uint64_t epoch, hipStream_t s);
 void tubek_predict(const TubeDev *D, const float *x, const float *y, const float *v, const int32_t *rows, const int32_t *env,
                    const int32_t *start, int T, int nz, int m, int64_t count, float *o, hipStream_t s);
@@ -36,7 +38,7 @@ void tubek_rollout_window(const TubeDev *D, const float *x, int64_t n_seq, int T
 }
 
 struct TubeCaps {                       // rows that a model's data-sized buffers hold
-    int64_t starts = 0, perm = 0, evpart = 0;
+    int64_t starts = 0, perm = 0, evpart = 0, levels = 0;
 };
 
 struct lg_tube {
@@ -86,6 +88,13 @@ static std::string cfg_reason(const lg_tube_cfg *c) {
     if (c->step_size < 1) return "step_size must be positive";
     if (c->horizon && (c->H_rev < 0 || c->H_fwd < 1 || c->output_dim != c->H_fwd)) return "horizon dataset: output_dim must equal H_fwd";
     if (c->activation == LG_TUBE_ACT_SOFTPLUS && !(c->softplus_beta > 0.f)) return "softplus_beta must be positive";
+    if (c->level_input != 0 && c->level_input != 1) return "level_input must be 0 or 1";
+    if (c->level_input) {
+        if (c->loss == LG_TUBE_LOSS_MSE) return "level_input needs a tube loss (scalar or vector): the mse loss has no level";
+        if (c->horizon) return "level_input with horizon = 1 is not supported: lg_tube_predict_windows has no place for a level";
+        if (c->input_dim < 2) return "level_input: input_dim counts the level column and must be at least 2";
+        if (!(c->level_lo >= 0.f && c->level_lo < c->level_hi && c->level_hi <= 1.f)) return "level range must satisfy 0 <= level_lo < level_hi <= 1";
+    }
     return "";
 }
 
@@ -96,6 +105,7 @@ static bool dev_init(const lg_tube_cfg *cfg, TubeDev &D) {
     D.act = cfg->activation; D.loss = cfg->loss; D.horizon = cfg->horizon; D.H_fwd = cfg->H_fwd; D.H_rev = cfg->H_rev;
     D.alpha = cfg->alpha; D.delta = cfg->delta; D.sp_beta = cfg->activation == LG_TUBE_ACT_SOFTPLUS ? cfg->softplus_beta : 1.f;
     D.seed = cfg->seed;
+    D.level_input = cfg->level_input; D.level_lo = cfg->level_lo; D.level_hi = cfg->level_hi;
     int64_t off = 0;
     for (int li = 0; li <= D.layers; ++li) {        // state-dict order: layers.{2 li}.weight (out, in), layers.{2 li}.bias
         D.din[li] = li == 0 ? D.in_dim : D.units;
@@ -116,7 +126,7 @@ static bool dev_init(const lg_tube_cfg *cfg, TubeDev &D) {
 static void dev_free(TubeDev &D) {
     for (void *q : {(void *)D.params, (void *)D.wt, (void *)D.grads, (void *)D.adam_m, (void *)D.adam_v, (void *)D.slab,
                     (void *)D.evpart, (void *)D.normpart, (void *)D.done_ctr, (void *)D.log, (void *)D.eval, (void *)D.starts,
-                    (void *)D.perm})
+                    (void *)D.perm, (void *)D.levels})
         if (q) (void)hipFree(q);
 }
 
@@ -142,6 +152,11 @@ static bool data_alloc(TubeDev &D, TubeCaps &c, int which, int64_t rows, int64_t
         if (D.starts) (void)hipFree(D.starts);
         if (!talloc((void **)&D.starts, need * 4)) { D.starts = nullptr; c.starts = 0; return false; }
         c.starts = need;
+    }
+    if (D.level_input && need > c.levels) {
+        if (D.levels) (void)hipFree(D.levels);
+        if (!talloc((void **)&D.levels, need * 4)) { D.levels = nullptr; c.levels = 0; return false; }
+        c.levels = need;
     }
     if (which == 0 && rows > c.perm) {
         if (D.perm) (void)hipFree(D.perm);
@@ -172,6 +187,7 @@ static void fill_buffers(const TubeDev &D, const TubeCaps &c, int64_t t, lg_tube
     out->log = D.log; out->eval = D.eval; out->starts = D.starts; out->perm = D.perm;
     out->num_params = D.num_params; out->log_cap = D.log_cap; out->starts_cap = c.starts; out->perm_cap = c.perm;
     out->step = t;
+    out->levels = D.levels; out->levels_cap = c.levels;
 }
 
 static int fill_layout(const TubeDev &D, int64_t *offsets, int64_t *shapes, int max_entries, const char *who) {
@@ -273,8 +289,17 @@ int lg_tube_eval(lg_tube *p) {
     const TubeSplit &S = p->split[1];
     if (!S.rows) { lg_set_error("lg_tube_eval: no test data (lg_tube_set_data with which = 1)"); return -1; }
     const uint64_t key = 0x8000000000000000ull | (uint64_t)p->eval_count++;
-    tubek_eval(&p->dev, &S, p->eval_rows, key, loss_norm(p->cfg, S.rows), p->stream);
+    tubek_eval(&p->dev, &S, p->eval_rows, key, loss_norm(p->cfg, S.rows), -1.f, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_eval: launch failed"), -3);
+}
+
+int lg_tube_eval_level(lg_tube *p, float level) {
+    const TubeSplit &S = p->split[1];
+    if (!p->dev.level_input) { lg_set_error("lg_tube_eval_level: the handle is not level-conditioned (lg_tube_cfg.level_input)"); return -1; }
+    if (!(level >= 0.f && level <= 1.f)) { lg_set_error("lg_tube_eval_level: level must lie in 0..1"); return -1; }
+    if (!S.rows) { lg_set_error("lg_tube_eval_level: no test data (lg_tube_set_data with which = 1)"); return -1; }
+    tubek_eval(&p->dev, &S, p->eval_rows, 0, loss_norm(p->cfg, S.rows), level, p->stream);     // nothing is drawn: no key
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_eval_level: launch failed"), -3);
 }
 
 // ---------------------------------------------------------------- inference: reads params / wt, changes neither
@@ -284,6 +309,16 @@ int lg_tube_predict(lg_tube *p, const float *x, const int32_t *rows, int64_t cou
     if (!x || !out) { lg_set_error("lg_tube_predict: missing array"); return -1; }
     tubek_predict(&p->dev, x, nullptr, nullptr, rows, nullptr, nullptr, 0, 0, 0, count, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict: launch failed"), -3);
+}
+
+int lg_tube_predict_levels(lg_tube *p, const float *x, const int32_t *rows, int64_t count, const float *levels, int32_t n_levels,
+                           float *out) {
+    if (!p->dev.level_input) { lg_set_error("lg_tube_predict_levels: the handle is not level-conditioned (lg_tube_cfg.level_input)"); return -1; }
+    if (count < 1) { lg_set_error("lg_tube_predict_levels: count must be positive"); return -1; }
+    if (n_levels < 1 || n_levels > LG_TUBE_MAX_LEVELS) { lg_set_error("lg_tube_predict_levels: n_levels must be 1..64"); return -1; }
+    if (!x || !levels || !out) { lg_set_error("lg_tube_predict_levels: missing array"); return -1; }
+    tubek_predict_levels(&p->dev, x, rows, count, levels, n_levels, out, p->stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict_levels: launch failed"), -3);
 }
 
 int lg_tube_predict_windows(lg_tube *p, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz, int32_t m,
@@ -358,7 +393,8 @@ int lg_tube_sweep_create(const lg_tube_cfg *cfgs, int32_t K, lg_tube_sweep **out
         const char *f = a.input_dim != b.input_dim ? "input_dim" : a.output_dim != b.output_dim ? "output_dim"
                       : a.num_units != b.num_units ? "num_units" : a.num_layers != b.num_layers ? "num_layers"
                       : a.loss != b.loss ? "loss" : a.horizon != b.horizon ? "horizon" : a.H_fwd != b.H_fwd ? "H_fwd"
-                      : a.H_rev != b.H_rev ? "H_rev" : a.batch_size != b.batch_size ? "batch_size" : nullptr;
+                      : a.H_rev != b.H_rev ? "H_rev" : a.batch_size != b.batch_size ? "batch_size"
+                      : a.level_input != b.level_input ? "level_input" : nullptr;
         if (f) {
             lg_set_error(std::string("lg_tube_sweep_create: ") + f + " differs between member 0 and member " + std::to_string(k) +
                          " (the members of a sweep share it)");
@@ -470,8 +506,17 @@ int lg_tube_sweep_eval(lg_tube_sweep *s) {
     const TubeSplit &S = s->split[1];
     if (!S.rows) { lg_set_error("lg_tube_sweep_eval: no test data (lg_tube_sweep_set_data with which = 1)"); return -1; }
     const uint64_t key = 0x8000000000000000ull | (uint64_t)s->eval_count++;
-    tubek_eval_sweep(s->dmem, (int)s->mem.size(), &s->mem[0].dev, &S, s->eval_rows, key, loss_norm(s->cfg[0], S.rows), s->stream);
+    tubek_eval_sweep(s->dmem, (int)s->mem.size(), &s->mem[0].dev, &S, s->eval_rows, key, loss_norm(s->cfg[0], S.rows), -1.f, s->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_sweep_eval: launch failed"), -3);
+}
+
+int lg_tube_sweep_eval_level(lg_tube_sweep *s, float level) {
+    const TubeSplit &S = s->split[1];
+    if (!s->mem[0].dev.level_input) { lg_set_error("lg_tube_sweep_eval_level: the sweep is not level-conditioned (lg_tube_cfg.level_input)"); return -1; }
+    if (!(level >= 0.f && level <= 1.f)) { lg_set_error("lg_tube_sweep_eval_level: level must lie in 0..1"); return -1; }
+    if (!S.rows) { lg_set_error("lg_tube_sweep_eval_level: no test data (lg_tube_sweep_set_data with which = 1)"); return -1; }
+    tubek_eval_sweep(s->dmem, (int)s->mem.size(), &s->mem[0].dev, &S, s->eval_rows, 0, loss_norm(s->cfg[0], S.rows), level, s->stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_sweep_eval_level: launch failed"), -3);
 }
 
 }  // extern "C"

@@ -34,10 +34,14 @@ struct TubeDev {                        // passed by value to kernels
     int32_t *starts;                    // horizon window start per row of the last step / eval
     int32_t *perm;
     int64_t log_cap;
+    // level-conditioned tube (lg_tube_cfg.level_input), appended: the fields above keep their offsets
+    int level_input;                    // 1: the last input column is the row's level, drawn per row in [level_lo, level_hi)
+    float level_lo, level_hi;
+    float *levels;                      // level per row of the last step / eval
 };
 
 struct TubeMember {                     // one model of a sweep (lg_tube_sweep); the kernels index a device array of these by blockIdx.y
-    TubeDev dev;                        // its own buffers, alpha / delta / activation / seed; the shape is the same in every member
+    TubeDev dev;                        // its own buffers, alpha / delta / activation / seed / level range; the shape is the same in every member
     double lr0, gamma;                  // its Adam rate and StepLR schedule
     int64_t step_size;
 };

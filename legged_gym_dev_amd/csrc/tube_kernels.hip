@@ -8,6 +8,8 @@
 //                      pass, and writes its partial weight / bias gradients and loss sum to its own slab row;
 //   k_tube_adam        sums the slab rows in workgroup order (fixed order: bit-reproducible without atomics), applies
 //                      torch.optim.Adam (defaults) at the StepLR rate of the step, and logs loss, lr and gradient norm on the device.
+// A level-conditioned model (lg_tube_cfg.level_input) runs the same two launches with the tile's LEVEL flag
+// set, and k_tube_predict_levels evaluates many levels of a row in one launch.
 // Plain fp32 FMA over LDS tiles: at 16..128 units the matrices are far too small for MFMA to matter.
 #include "tube_device.h"
 
@@ -57,12 +59,25 @@ __device__ __forceinline__ int tube_window(const Dev &D, uint64_t key, int64_t p
     return D.H_rev + (int)(((uint64_t)c[0] * range) >> 32);
 }
 
+// Level of row `pos` of a draw on a level-conditioned model: uniform over [level_lo, level_hi), from the same Philox key as
+// tube_window -- (seed, draw key, row position) -- under a domain constant of its own, so the two draws never coincide.  It depends
+// on (seed, key, pos) alone: not on the tile, the batch size or the sweep.  The one fp32 formula: u = 24 bits / 2^24, fmaf(hi - lo, u, lo).
+template <class Dev>
+__device__ __forceinline__ float tube_level(const Dev &D, uint64_t key, int64_t pos) {
+    uint32_t c[4] = {(uint32_t)pos, (uint32_t)key, (uint32_t)(key >> 32), 0x1e7e1c0du ^ (uint32_t)(pos >> 32)};
+    philox4x32((uint32_t)D.seed, (uint32_t)(D.seed >> 32), c);
+    const float u = (float)(c[0] >> 8) * (1.f / 16777216.f);
+    return fmaf(D.level_hi - D.level_lo, u, D.level_lo);
+}
+
 // One tile of rows: gather, forward, loss (+ backward into the slab row when TRAIN, eval partial sums otherwise).
 // rows: row ids of the batch (position base + r); count: rows in the batch; norm: the loss's divisor (elements or rows).
 // The body is tube_rows_tile.inl, included by k_tube_rows (D in the kernel arguments) and k_tube_rows_sweep (D in the member array):
 // as a device function it inlined into k_tube_rows with a different schedule, and the single kernel is to stay as it was.
-template <bool TRAIN>
-__global__ void __launch_bounds__(NT) k_tube_rows(TubeDev D, TubeSplit S, const int32_t *rows, int64_t count, uint64_t key, float norm) {
+// LEVEL: the level-conditioned tile (tube_rows_tile.inl); `level` >= 0 fixes every row's level, < 0 draws it.
+template <bool TRAIN, bool LEVEL>
+__global__ void __launch_bounds__(NT) k_tube_rows(TubeDev D, TubeSplit S, const int32_t *rows, int64_t count, uint64_t key, float norm,
+                                                  float level) {
 #include "tube_rows_tile.inl"
 }
 
@@ -90,19 +105,22 @@ struct TubeDevView {
     float *log, *eval;
     int32_t *starts, *perm;
     int64_t log_cap;
+    float level_lo, level_hi;
+    float *levels;
     __device__ __forceinline__ TubeDevView(const TUBE_CONST TubeDev &d)
         : in_dim(d.in_dim), out_dim(d.out_dim), units(d.units), layers(d.layers), act(d.act), loss(d.loss), horizon(d.horizon),
           H_fwd(d.H_fwd), H_rev(d.H_rev), T(d.T), nz(d.nz), m(d.m), alpha(d.alpha), delta(d.delta), sp_beta(d.sp_beta), seed(d.seed),
           num_params(d.num_params), slab_ld(d.slab_ld), off_w(d.off_w), off_b(d.off_b), din(d.din), dout(d.dout), params(d.params),
           wt(d.wt), grads(d.grads), adam_m(d.adam_m), adam_v(d.adam_v), slab(d.slab), evpart(d.evpart), normpart(d.normpart),
-          done_ctr(d.done_ctr), log(d.log), eval(d.eval), starts(d.starts), perm(d.perm), log_cap(d.log_cap) {}
+          done_ctr(d.done_ctr), log(d.log), eval(d.eval), starts(d.starts), perm(d.perm), log_cap(d.log_cap), level_lo(d.level_lo),
+          level_hi(d.level_hi), levels(d.levels) {}
 };
 
 // The same tile for member blockIdx.y of a sweep (grid = (tiles, K)).  rows: a row list shared by all members, or null: the
 // member's own epoch permutation from position pos.
-template <bool TRAIN>
+template <bool TRAIN, bool LEVEL>
 __global__ void __launch_bounds__(NT) k_tube_rows_sweep(const TubeMember *__restrict__ M, TubeSplit S, const int32_t *rows, int64_t pos,
-                                                        int64_t count, uint64_t key, float norm) {
+                                                        int64_t count, uint64_t key, float norm, float level) {
     const TubeDevView D(tube_member(M).dev);
     if (!rows) rows = D.perm + pos;
 #include "tube_rows_tile.inl"
@@ -258,6 +276,68 @@ __global__ void __launch_bounds__(NT) k_tube_predict(TubeDev D, TubeGather G, in
         in = out;
     }
     tube_layer<R, RB, NT, true>(tid, D.din[L], O, in, D.wt + D.off_w[L], D.params + D.off_b[L], D.act, D.sp_beta, nullptr, o + base * O, O, nr);
+}
+
+// out[i][l] = MLP([x row of item i, levels[l]]) for a level-conditioned model: R rows per workgroup, gathered as in k_tube_predict
+// from x (n, I - 1).  The first layer is split: per (row, unit) the chain over the I - 1 shared columns -- acc = 0, fmaf over k
+// ascending, tube_layer's order -- is computed once into A; per level the unit is finished with the chain's last link
+// fmaf(level, w[I-1][j], acc), the bias and the activation, and the remaining layers run through tube_layer.  The level is the
+// last k of the first layer, so every out[i][l] equals k_tube_predict on the row with the level appended, bit for bit.
+// Dynamic LDS: X (R, I - 1), A (R, U), H0, H1 (R, U).  o: (count, n_levels, O).
+__global__ void __launch_bounds__(NT) k_tube_predict_levels(TubeDev D, const float *x, const int32_t *rows, int64_t count,
+                                                            const float *levels, int n_levels, float *o) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, I = D.in_dim, Ix = I - 1, O = D.out_dim, U = D.units, L = D.layers;
+    const int64_t base = (int64_t)blockIdx.x * R;
+    const int nr = (int)(count - base < R ? count - base : R);
+    float *X = lds, *A = X + R * Ix, *H0 = A + R * U, *H1 = H0 + R * U;
+    for (int e = tid; e < R * Ix; e += NT) {
+        const int r = e / Ix, c = e - r * Ix;
+        float v = 0.f;
+        if (r < nr) {
+            const int64_t s = rows ? (int64_t)rows[base + r] : base + r;
+            v = x[s * Ix + c];
+        }
+        X[e] = v;
+    }
+    __syncthreads();
+    const float *w0 = D.wt + D.off_w[0], *b0 = D.params + D.off_b[0];
+    for (int e = tid; e < U * (R / RB); e += NT) {
+        const int j = e % U, r0 = (e / U) * RB;
+        float acc[RB];
+#pragma unroll
+        for (int q = 0; q < RB; ++q) acc[q] = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < Ix; ++k) {
+            const float wv = w0[k * U + j];
+#pragma unroll
+            for (int q = 0; q < RB; ++q) acc[q] = fmaf(X[(r0 + q) * Ix + k], wv, acc[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < RB; ++q) A[(r0 + q) * U + j] = acc[q];
+    }
+    __syncthreads();
+    for (int l = 0; l < n_levels; ++l) {
+        const float lv = levels[l];
+        for (int e = tid; e < R * U; e += NT) {
+            const int j = e % U;
+            const float z = fmaf(lv, w0[Ix * U + j], A[e]) + b0[j];
+            H0[e] = tube_act(D.act, z, D.sp_beta);
+        }
+        __syncthreads();
+        const float *in = H0;
+        int64_t ow = D.off_b[0] + U;    // off_w[1]; the hidden layers are U x U and packed weight, bias, weight, ... (dev_init)
+        for (int li = 1; li < L; ++li) {
+            float *out = li & 1 ? H1 : H0;
+            tube_layer<R, RB, NT, false>(tid, U, U, in, D.wt + ow, D.params + ow + U * U, D.act, D.sp_beta, out, nullptr, 0, 0);
+            __syncthreads();
+            in = out;
+            ow += U * U + U;
+        }
+        tube_layer<R, RB, NT, true>(tid, U, O, in, D.wt + ow, D.params + ow + U * O, D.act, D.sp_beta, nullptr,
+                                    o + (base * n_levels + l) * O, (int64_t)n_levels * O, nr);
+        __syncthreads();                // the next level rewrites H0, which the last layer may still read
+    }
 }
 
 // Closed loop over time: a workgroup owns RT sequences and walks t = 0..T-1 itself; the carried output of the tile stays in LDS.
@@ -478,17 +558,27 @@ void tubek_predict(const TubeDev *D, const float *x, const float *y, const float
     hipLaunchKernelGGL(k_tube_predict, dim3((unsigned)((count + R - 1) / R)), dim3(NT), bytes, s, *D, G, count, o);
 }
 
+void tubek_predict_levels(const TubeDev *D, const float *x, const int32_t *rows, int64_t count, const float *levels, int n_levels,
+                          float *o, hipStream_t s) {
+    const size_t bytes = sizeof(float) * (size_t)R * (D->in_dim - 1 + 3 * D->units);
+    hipLaunchKernelGGL(k_tube_predict_levels, dim3((unsigned)((count + R - 1) / R)), dim3(NT), bytes, s, *D, x, rows, count, levels,
+                       n_levels, o);
+}
+
 size_t tubek_lds_bytes(const TubeDev *D) {
     return sizeof(float) * (size_t)R * (D->in_dim + D->layers * D->units + 2 * D->out_dim + 2 * D->units);
 }
 int tubek_init() {
     const int lim = (int)(sizeof(float) * R * (LG_TUBE_MAX_IN + 4 * LG_TUBE_MAX_UNITS + 2 * LG_TUBE_MAX_OUT + 2 * LG_TUBE_MAX_UNITS));
-    if (hipFuncSetAttribute((const void *)k_tube_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_tube_rows<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_tube_rows_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_tube_rows_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
+    for (const void *f : {(const void *)k_tube_rows<true, false>, (const void *)k_tube_rows<false, false>,
+                          (const void *)k_tube_rows<true, true>, (const void *)k_tube_rows<false, true>,
+                          (const void *)k_tube_rows_sweep<true, false>, (const void *)k_tube_rows_sweep<false, false>,
+                          (const void *)k_tube_rows_sweep<true, true>, (const void *)k_tube_rows_sweep<false, true>})
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lim) != hipSuccess) return -1;
     const int plim = (int)(sizeof(float) * R * (LG_TUBE_MAX_IN + 2 * LG_TUBE_MAX_UNITS));
     if (hipFuncSetAttribute((const void *)k_tube_predict, hipFuncAttributeMaxDynamicSharedMemorySize, plim) != hipSuccess) return -1;
+    const int llim = (int)(sizeof(float) * R * (LG_TUBE_MAX_IN - 1 + 3 * LG_TUBE_MAX_UNITS));
+    if (hipFuncSetAttribute((const void *)k_tube_predict_levels, hipFuncAttributeMaxDynamicSharedMemorySize, llim) != hipSuccess) return -1;
     for (const void *f : {(const void *)k_tube_rollout<1, 64, true>, (const void *)k_tube_rollout<1, 64, false>,
                           (const void *)k_tube_rollout<4, 64, true>, (const void *)k_tube_rollout<4, 64, false>,
                           (const void *)k_tube_rollout<16, 256, true>, (const void *)k_tube_rollout<16, 256, false>,
@@ -500,7 +590,8 @@ int tubek_init() {
 }
 void tubek_step(const TubeDev *D, const TubeSplit *S, const int32_t *rows, int64_t count, uint64_t key, float norm, hipStream_t s) {
     const int nwg = (int)((count + R - 1) / R);
-    hipLaunchKernelGGL(k_tube_rows<true>, dim3(nwg), dim3(NT), tubek_lds_bytes(D), s, *D, *S, rows, count, key, norm);
+    if (D->level_input) hipLaunchKernelGGL((k_tube_rows<true, true>), dim3(nwg), dim3(NT), tubek_lds_bytes(D), s, *D, *S, rows, count, key, norm, -1.f);
+    else hipLaunchKernelGGL((k_tube_rows<true, false>), dim3(nwg), dim3(NT), tubek_lds_bytes(D), s, *D, *S, rows, count, key, norm, -1.f);
 }
 void tubek_adam(const TubeDev *D, int nwg, int64_t t, double lr0, double gamma, int64_t step_size, float norm, int64_t rows,
                 hipStream_t s) {
@@ -508,16 +599,19 @@ void tubek_adam(const TubeDev *D, int nwg, int64_t t, double lr0, double gamma, 
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(k_tube_adam, dim3(blocks), dim3(256), 0, s, *D, nwg, t, lr0, gamma, step_size, norm, rows);
 }
-void tubek_eval(const TubeDev *D, const TubeSplit *S, const int32_t *rows, uint64_t key, float norm, hipStream_t s) {
+// level: a level-conditioned model's fixed level (lg_tube_eval_level), or negative: one drawn per row
+void tubek_eval(const TubeDev *D, const TubeSplit *S, const int32_t *rows, uint64_t key, float norm, float level, hipStream_t s) {
     const int nwg = (int)((S->rows + R - 1) / R);
-    hipLaunchKernelGGL(k_tube_rows<false>, dim3(nwg), dim3(NT), tubek_lds_bytes(D), s, *D, *S, rows, S->rows, key, norm);
+    if (D->level_input) hipLaunchKernelGGL((k_tube_rows<false, true>), dim3(nwg), dim3(NT), tubek_lds_bytes(D), s, *D, *S, rows, S->rows, key, norm, level);
+    else hipLaunchKernelGGL((k_tube_rows<false, false>), dim3(nwg), dim3(NT), tubek_lds_bytes(D), s, *D, *S, rows, S->rows, key, norm, level);
     hipLaunchKernelGGL(k_tube_eval_finish, dim3(1), dim3(256), 0, s, *D, nwg, norm, (float)(S->rows * (int64_t)D->out_dim));
 }
 // ---- sweep: the same launches with the members along grid y.  M: device array of K members; D0: member 0's host copy (the shape).
 void tubek_step_sweep(const TubeMember *M, int K, const TubeDev *D0, const TubeSplit *S, const int32_t *rows, int64_t pos, int64_t count,
                       uint64_t key, float norm, hipStream_t s) {
     const int nwg = (int)((count + R - 1) / R);
-    hipLaunchKernelGGL(k_tube_rows_sweep<true>, dim3(nwg, K), dim3(NT), tubek_lds_bytes(D0), s, M, *S, rows, pos, count, key, norm);
+    if (D0->level_input) hipLaunchKernelGGL((k_tube_rows_sweep<true, true>), dim3(nwg, K), dim3(NT), tubek_lds_bytes(D0), s, M, *S, rows, pos, count, key, norm, -1.f);
+    else hipLaunchKernelGGL((k_tube_rows_sweep<true, false>), dim3(nwg, K), dim3(NT), tubek_lds_bytes(D0), s, M, *S, rows, pos, count, key, norm, -1.f);
 }
 void tubek_adam_sweep(const TubeMember *M, int K, const TubeDev *D0, int nwg, int64_t t, float norm, int64_t rows, hipStream_t s) {
     int blocks = (int)((D0->num_params + 255) / 256);
@@ -525,9 +619,10 @@ void tubek_adam_sweep(const TubeMember *M, int K, const TubeDev *D0, int nwg, in
     hipLaunchKernelGGL(k_tube_adam_sweep, dim3(blocks, K), dim3(256), 0, s, M, nwg, t, norm, rows);
 }
 void tubek_eval_sweep(const TubeMember *M, int K, const TubeDev *D0, const TubeSplit *S, const int32_t *rows, uint64_t key, float norm,
-                      hipStream_t s) {
+                      float level, hipStream_t s) {
     const int nwg = (int)((S->rows + R - 1) / R);
-    hipLaunchKernelGGL(k_tube_rows_sweep<false>, dim3(nwg, K), dim3(NT), tubek_lds_bytes(D0), s, M, *S, rows, (int64_t)0, S->rows, key, norm);
+    if (D0->level_input) hipLaunchKernelGGL((k_tube_rows_sweep<false, true>), dim3(nwg, K), dim3(NT), tubek_lds_bytes(D0), s, M, *S, rows, (int64_t)0, S->rows, key, norm, level);
+    else hipLaunchKernelGGL((k_tube_rows_sweep<false, false>), dim3(nwg, K), dim3(NT), tubek_lds_bytes(D0), s, M, *S, rows, (int64_t)0, S->rows, key, norm, level);
     hipLaunchKernelGGL(k_tube_eval_finish_sweep, dim3(1, K), dim3(256), 0, s, M, nwg, norm, (float)(S->rows * (int64_t)D0->out_dim));
 }
 void tubek_perm_sweep(const TubeMember *M, int K, int n, uint64_t epoch, hipStream_t s) {

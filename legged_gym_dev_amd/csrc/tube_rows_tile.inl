@@ -1,7 +1,11 @@
 // Body of k_tube_rows and k_tube_rows_sweep (tube_kernels.hip), included inside each kernel so that both compile the same
-// statements in kernel context.  Names it takes from the including kernel: TRAIN (template bool), D (the kernel's TubeDev argument, or a
-// sweep kernel's TubeDevView of its member: the same field names), S (TubeSplit), rows (const int32_t *), count (int64_t), key (uint64_t), norm (float).  The tile is
-// blockIdx.x.  It declares its own shared arrays and may return early, so it must be the last thing in the kernel.
+// statements in kernel context.  Names it takes from the including kernel: TRAIN, LEVEL (template bools), D (the kernel's TubeDev argument, or a
+// sweep kernel's TubeDevView of its member: the same field names), S (TubeSplit), rows (const int32_t *), count (int64_t), key (uint64_t), norm (float),
+// level (float; read only when LEVEL).  The tile is blockIdx.x.
+// LEVEL (lg_tube_cfg.level_input): the last input column is the row's coverage level -- `level` where it is >= 0 (lg_tube_eval_level),
+// else drawn per row position by tube_level -- and the row's pinball loss takes it in place of D.alpha.  The split then holds I - 1
+// columns.  Every LEVEL statement sits behind the compile-time flag: with LEVEL = false the fragment compiles what it compiled before.
+// It declares its own shared arrays and may return early, so it must be the last thing in the kernel.
 //
 // Why a fragment and not a function: as `template <bool TRAIN> __device__ __forceinline__ void tube_rows_tile(const TubeDev &D,
 // const TubeSplit &S, rows, count, key, norm)` the body inlined into k_tube_rows<true> / <false> with a different schedule
@@ -10,7 +14,8 @@
 // that is meant to leave k_tube_rows alone:
 //     hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 --cuda-device-only -S tube_kernels.hip -o new.s   (and old.s at the old commit)
 // then, per kernel symbol, the lines between `<symbol>:` and `.Lfunc_end`, comments stripped and the function number taken out
-// of the `.LBB<n>_<m>` labels, must be equal.  With the fragment all 20 kernels of the parent commit were.
+// of the `.LBB<n>_<m>` labels, must be equal.  With the fragment all 20 kernels of the parent commit were.  With the LEVEL flag they
+// were not all: TubeDev grew, which moved kernel-argument offsets (DESIGN.md section 10.4 lists every symbol); results are bit-identical.
     extern __shared__ float lds[];
     const int tid = threadIdx.x, I = D.in_dim, O = D.out_dim, U = D.units, L = D.layers;
     const int64_t base = (int64_t)blockIdx.x * R;
@@ -31,6 +36,14 @@
             ind[tid] = tube_window(D, key, base + tid);
             D.starts[base + tid] = ind[tid];
         }
+        if (LEVEL) {                    // column I - 1 of the row, written here; the gather below leaves it alone
+            float lv = 0.f;
+            if (tid < nr) {
+                lv = level >= 0.f ? level : tube_level(D, key, base + tid);
+                D.levels[base + tid] = lv;
+            }
+            X[tid * I + I - 1] = lv;
+        }
     }
     __syncthreads();
     // ---- gather
@@ -38,8 +51,9 @@
         const int r = e / I, c = e - r * I;
         const int64_t s = src[r];
         float x = 0.f;
+        if (LEVEL && c == I - 1) continue;
         if (s >= 0) {
-            if (!D.horizon) x = S.x[s * I + c];
+            if (!D.horizon) x = S.x[s * (LEVEL ? I - 1 : I) + c];
             else {
                 const int t0 = ind[r];
                 if (c < D.H_rev) x = S.x[s * D.T + t0 - D.H_rev + c];
@@ -89,6 +103,7 @@
         if (tid < nr) {
             float *f = F + tid * O;
             const float *y = Y + tid * O;
+            const float alpha = LEVEL ? X[tid * I + I - 1] : D.alpha;
             if (D.loss == LG_TUBE_LOSS_MSE) {
                 for (int j = 0; j < O; ++j) {
                     const float d = f[j] - y[j];
@@ -100,7 +115,7 @@
                     float dl, dh;
                     const float fw = f[j];
                     if (fw > y[j]) { pos += 1.f; err += fabsf(y[j] - fw); }
-                    ls += tube_huber(D.delta, tube_pinball(D.alpha, y[j], fw, &dl), &dh);
+                    ls += tube_huber(D.delta, tube_pinball(alpha, y[j], fw, &dl), &dh);
                     if (TRAIN) f[j] = dh * dl / norm;
                 }
             } else {                    // VectorTubeLoss: the pinball residuals summed over the row, then Huber
@@ -109,13 +124,13 @@
                     float dl;
                     const float fw = f[j];
                     if (fw > y[j]) { pos += 1.f; err += fabsf(y[j] - fw); }
-                    lsum += tube_pinball(D.alpha, y[j], fw, &dl);
+                    lsum += tube_pinball(alpha, y[j], fw, &dl);
                 }
                 ls = tube_huber(D.delta, lsum, &dh);
                 if (TRAIN)
                     for (int j = 0; j < O; ++j) {
                         float dl;
-                        tube_pinball(D.alpha, y[j], f[j], &dl);
+                        tube_pinball(alpha, y[j], f[j], &dl);
                         f[j] = dh * dl / norm;
                     }
             }

@@ -18,6 +18,11 @@ feedback_dN is that distance in rows, 1 for every dataset (tube/data.py feedback
 prediction at the window starts H_rev, H_rev + S, ... of every env, scored overall and per step ahead.  Writes eval.json to --out (default: the run folder) and prints the
 reference's "Total Success Rate" (and, for error_dynamics, "Mean Error" / "Mean One Step Error") lines.
 
+A level-conditioned run (config.json level_input; datasets scalar_level, vector_level) is scored per coverage level (--levels,
+default 0.5,0.8,0.9,0.95): eval.json's "levels" has one entry per level with the one-step metrics -- every level of every row from one
+predict_levels launch -- and the closed-loop roll-out with the level column filled.  The success rate rises with the level but need
+not equal it.
+
 Deliberate deviations from the reference scripts:
   * evaluate_tube.py:53 feeds the full z[t] to a model that ScalarTubeDataset trained on z[:, 2:] (the input widths differ).  The
     rows here are the dataset's own (tube/data.py sequences()): what the model was trained on.
@@ -39,7 +44,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch  # noqa: E402
 
 from legged_gym_dev_amd.tube import evaluate as ev  # noqa: E402
-from legged_gym_dev_amd.tube.data import DATASETS, construct_dataset, feedback_layout, sequences  # noqa: E402
+from legged_gym_dev_amd.tube.data import DATASETS, LEVEL_KINDS, construct_dataset, feedback_layout, sequences  # noqa: E402
 from legged_gym_dev_amd.tube.model import CONFIG_NAME, HipTubeModel, read_config  # noqa: E402
 
 DEFAULTS = {"N": 1, "dN": 1, "recursive": False, "H_fwd": 50, "H_rev": 10, "softplus_beta": 1.0}
@@ -52,6 +57,7 @@ def parse_args(argv=None):
     ap.add_argument("--checkpoint", choices=["best", "latest"], default="best")
     ap.add_argument("--horizon", type=int, default=None, help="flat datasets: reseed the roll-out every K steps")
     ap.add_argument("--window_stride", type=int, default=1, help="scalar_horizon: distance between window starts")
+    ap.add_argument("--levels", default=None, help="level-conditioned runs: comma-separated coverage levels (default 0.5,0.8,0.9,0.95)")
     ap.add_argument("--plot", action="store_true", help="save w / fw / fw_single PNGs per env to --out")
     ap.add_argument("--plot_envs", type=int, default=4)
     ap.add_argument("--out", default=None)
@@ -98,6 +104,33 @@ def evaluate_flat(model, cfg, raw, horizon, dev):
     res = {"one_step": ev.tube_metrics(fw_single, target, done, None, ed), "rollout": ev.tube_metrics(fw, target, done, reseed, ed),
            "feedback_width": fb, "feedback_taps": taps, "feedback_dN": lag, "feedback_stride": stride, "envs": E, "steps_per_env": T, "reseed_every": horizon}
     return res, {"w": target, "fw": fw, "fw_single": fw_single, "done": done}
+
+
+DEFAULT_LEVELS = (0.5, 0.8, 0.9, 0.95)
+
+
+def evaluate_levels(model, cfg, raw, horizon, dev, levels):
+    """evaluate_flat per level of a level-conditioned model: the one-step predictions of all levels from one predict_levels
+    launch, the roll-out per level on the rows with the column filled."""
+    kind = cfg["dataset"]
+    win = {"N": cfg["N"], "dN": cfg["dN"]}
+    if LEVEL_KINDS[kind] == "scalar":
+        win["recursive"] = cfg["recursive"]
+    data, target, done = (t.to(dev) for t in sequences(kind, raw, **win))
+    fb, taps, lag, stride = feedback_layout(kind, cfg["N"], cfg["dN"], cfg["recursive"], n=raw["z"].shape[-1], m=raw["v"].shape[-1])
+    E, T, I = data.shape
+    single = model.predict_levels(data.reshape(E * T, I), torch.tensor(levels, dtype=torch.float32))      # (E T, levels, out)
+    reseed = ev.reseed_mask(done, horizon)
+    per_level, series = [], None
+    for i, lv in enumerate(levels):
+        fw_single = single[:, i, :].reshape(E, T, -1)
+        fw = model.rollout_window(model.with_level(data, lv), fb, taps, lag, stride, reseed)
+        per_level.append({"level": lv, "one_step": ev.tube_metrics(fw_single, target, done), "rollout": ev.tube_metrics(fw, target, done, reseed)})
+        if i == len(levels) - 1:
+            series = {"w": target, "fw": fw, "fw_single": fw_single, "done": done}
+    res = {"levels": per_level, "feedback_width": fb, "feedback_taps": taps, "feedback_dN": lag, "feedback_stride": stride, "envs": E,
+           "steps_per_env": T, "reseed_every": horizon}
+    return res, series
 
 
 def evaluate_horizon(model, cfg, raw, stride, dev):
@@ -158,10 +191,15 @@ def main(argv=None):
     os.makedirs(out, exist_ok=True)
     horizon = (cfg["H_fwd"], cfg["H_rev"]) if cfg["dataset"] == "scalar_horizon" else None
     model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, activation=cfg["activation"], softplus_beta=cfg["softplus_beta"],
-                              horizon=horizon, device=a.device)
+                              horizon=horizon, device=a.device, level_input=cfg["dataset"] in LEVEL_KINDS)
     raw = construct_dataset(a.data)
+    levels = None
+    if model.level_input:
+        levels = [float(v) for v in a.levels.split(",")] if a.levels else list(DEFAULT_LEVELS)
     try:
-        if horizon is None:
+        if levels is not None:
+            res, series = evaluate_levels(model, cfg, raw, a.horizon, dev, levels)
+        elif horizon is None:
             res, series = evaluate_flat(model, cfg, raw, a.horizon, dev)
         else:
             res, series = evaluate_horizon(model, cfg, raw, a.window_stride, dev)
@@ -173,7 +211,10 @@ def main(argv=None):
         res["plots"] = plot(cfg["dataset"], series, out, a.plot_envs)
     with open(os.path.join(out, "eval.json"), "w") as f:
         json.dump(_json_safe(res), f, indent=1, allow_nan=False)
-    if horizon is None:
+    if levels is not None:
+        for r in res["levels"]:
+            print(f"level {r['level']}: Single Success Rate: {r['one_step']['success_rate']}  Total Success Rate: {r['rollout']['success_rate']}")
+    elif horizon is None:
         print(f"Single Success Rate: {res['one_step']['success_rate']}")
         print(f"Total Success Rate: {res['rollout']['success_rate']}")
         if cfg["dataset"] == "error_dynamics":

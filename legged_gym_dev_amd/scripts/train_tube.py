@@ -17,7 +17,12 @@ The host waits for the device only at checkpoints and once per epoch (to write t
 cartesian product of the flags' values as one HipTubeSweep: every member in the same two launches per step, on one dataset split.
 --out then holds one folder per member, <name>=<value>[,<name>=<value>...], with exactly what a single run writes (usable by
 evaluate_tube.py --run as it is and bit-identical to the single run with those flags on the same split), and sweep.json: per
-member its hyperparameters, final train loss and test metrics.  The split is drawn once, seeded by --seed, or by the first
+member its hyperparameters, final train loss and test metrics.
+
+--dataset scalar_level | vector_level trains a level-conditioned tube: the coverage level is the model's
+last input column, drawn per row and step from [--level_lo, --level_hi) on the device; --alpha is not read and the loss follows
+the dataset.  On evaluation steps metrics.jsonl also holds the test coverage at the levels 0.5, 0.8, 0.9 and 0.95.  --sweep works
+on top of it (over seed or lr, say).  The split is drawn once, seeded by --seed, or by the first
 value of a swept seed: the member with that seed matches its single run, the other seeds train on that split too.
 """
 import argparse
@@ -31,7 +36,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from legged_gym_dev_amd.tube.data import DATASETS, construct_dataset  # noqa: E402
+from legged_gym_dev_amd.tube.data import DATASETS, LEVEL_KINDS, construct_dataset  # noqa: E402
 from legged_gym_dev_amd.tube.trainer import HipTubeTrainer  # noqa: E402
 
 
@@ -44,7 +49,11 @@ def parse_args(argv=None):
     ap.add_argument("--recursive", action="store_true")
     ap.add_argument("--H_fwd", type=int, default=50)
     ap.add_argument("--H_rev", type=int, default=10)
-    ap.add_argument("--loss", choices=["scalar", "vector", "scalar_horizon", "error"], default="scalar")
+    ap.add_argument("--loss", choices=["scalar", "vector", "scalar_horizon", "error", "scalar_level", "vector_level"], default="scalar",
+                    help="a level dataset (scalar_level, vector_level) sets the loss of its own name")
+    ap.add_argument("--level_lo", type=float, default=argparse.SUPPRESS,
+                    help="level datasets: levels are drawn from [level_lo, level_hi) (default 0, 1)")
+    ap.add_argument("--level_hi", type=float, default=argparse.SUPPRESS)
     ap.add_argument("--alpha", type=float, default=0.8, help="tube quantile (default.yaml leaves it unset; tube_learning.yaml's)")
     ap.add_argument("--delta", type=float, default=1.0)
     ap.add_argument("--num_units", type=int, default=32)
@@ -65,6 +74,11 @@ def parse_args(argv=None):
     ap.add_argument("--sweep", action="append", default=None, metavar="NAME=v1,v2,...",
                     help="train every combination of the listed values in one sweep (repeatable); NAME: " + ", ".join(SWEEP_FIELDS))
     a = ap.parse_args(argv)
+    if a.dataset in LEVEL_KINDS:        # the level fields exist on a level-conditioned run only: every other run is as it was
+        a.level_input, a.loss = True, a.dataset
+        a.level_lo, a.level_hi = getattr(a, "level_lo", 0.0), getattr(a, "level_hi", 1.0)
+    elif a.loss in LEVEL_KINDS or hasattr(a, "level_lo") or hasattr(a, "level_hi"):
+        ap.error("--loss scalar_level / vector_level, --level_lo and --level_hi need --dataset scalar_level or vector_level")
     try:
         a.sweep = parse_sweep(a.sweep)
     except ValueError as e:
@@ -116,16 +130,22 @@ def sweep_members(axes):
 
 CONFIG_KEYS = ("dataset", "N", "dN", "recursive", "H_fwd", "H_rev", "loss", "alpha", "delta", "num_units", "num_layers", "activation",
                "softplus_beta", "seed", "validation_split")
+LEVEL_CONFIG_KEYS = ("level_input", "level_lo", "level_hi")     # a level-conditioned run records these too
+EVAL_LEVELS = (0.5, 0.8, 0.9, 0.95)     # a level-conditioned run logs its test coverage at these on every evaluation step
 
 
 def run_config(a):
     """The flags a later evaluation needs, as the dict written to config.json."""
-    return {k: getattr(a, k) for k in CONFIG_KEYS}
+    return {k: getattr(a, k) for k in CONFIG_KEYS + (LEVEL_CONFIG_KEYS if _level(a) else ())}
+
+
+def _level(a):
+    return getattr(a, "level_input", False)
 
 
 def make_dataset(a):
     ds = construct_dataset(a.data)
-    if a.dataset == "scalar":
+    if a.dataset in ("scalar", "scalar_level"):
         return DATASETS[a.dataset].from_folder(ds, N=a.N, dN=a.dN, recursive=a.recursive)
     if a.dataset == "scalar_horizon":
         return DATASETS[a.dataset].from_folder(ds, H_fwd=a.H_fwd, H_rev=a.H_rev)
@@ -135,6 +155,11 @@ def make_dataset(a):
 def eval_metrics(a, ev):
     if a.loss == "error":
         return {"Test Loss": float(ev[0])}
+    if _level(a):                       # ev: the drawn-level evaluation, then one fixed-level evaluation per EVAL_LEVELS entry
+        out = {"Test Loss (level drawn)": float(ev[0])}
+        for i, lv in enumerate(EVAL_LEVELS):
+            out[f"Proportion Correct, fw > w (level={lv:.2f})"] = float(ev[4 * (i + 1) + 1])
+        return out
     t = f"(alpha={a.alpha:.1f})"
     return {f"Test Loss {t}": float(ev[0]), f"Proportion Correct, fw > w {t}": float(ev[1]),
             f"Mean Error when Correct, fw > w {t}": float(ev[2])}
@@ -153,6 +178,8 @@ def main(argv=None):
     shared = dict(num_units=a.num_units, num_layers=a.num_layers, activation=a.activation, softplus_beta=a.softplus_beta, loss=a.loss,
                   alpha=a.alpha, delta=a.delta, lr=a.lr, gamma=a.gamma, step_size=a.step_size, batch_size=a.batch_size, seed=a.seed,
                   horizon=horizon, device=a.device)
+    if _level(a):
+        shared.update(level_lo=a.level_lo, level_hi=a.level_hi)
     if members is None:
         tr = HipTubeTrainer(dataset.input_dim, dataset.output_dim, **shared)
         runs = [(a, tr, a.out)]                                    # (flags, what answers read_log / state_dict, folder)
@@ -206,7 +233,10 @@ def main(argv=None):
                             best[k] = loss
                             torch.save(sd, os.path.join(out, "model_best.pth"))
                 if step % a.steps_per_model_evaluation == 0:
-                    pending[step] = _LazyRows(tr.evaluate(), K)
+                    ev = tr.evaluate().reshape(K, 4)
+                    if _level(a):
+                        ev = torch.cat([ev] + [tr.eval_level(lv).reshape(K, 4) for lv in EVAL_LEVELS], dim=1)
+                    pending[step] = _LazyRows(ev, K)
                 if step - first + 1 == tr.log_cap:
                     flush(step)
             flush(step)
@@ -240,14 +270,14 @@ def main(argv=None):
 
 
 class _LazyRows:
-    """An evaluation's device result, (4,) of one trainer or (K, 4) of a sweep, read back once when the log is written."""
+    """An evaluation's device result, (K, 4) -- (K, 4 + 4 levels) on a level-conditioned run --, read back once when the log is written."""
 
     def __init__(self, ev, K):
         self.ev, self.K, self.host = ev, K, None
 
     def __getitem__(self, k):
         if self.host is None:
-            self.host = self.ev.cpu().reshape(self.K, 4)
+            self.host = self.ev.cpu().reshape(self.K, -1)
         return self.host[k]
 
 

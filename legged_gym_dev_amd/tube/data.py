@@ -68,6 +68,7 @@ def _load(src):
 
 class TubeDataset:
     """Rows of (data, target): float32 torch tensors (rows, input_dim), (rows, output_dim)."""
+    conditioned = False                 # True: the model takes one more, last, input column that the data does not hold (the level)
 
     def __init__(self, data, target, input_dim, output_dim):
         self.data, self.target = data, target
@@ -224,15 +225,43 @@ class AlphaVectorTubeDataset(TubeDataset):
         raise NotImplementedError("AlphaVectorTubeDataset " + _ALPHA_REASON)
 
 
+class LevelScalarTubeDataset(ScalarTubeDataset):
+    """ScalarTubeDataset's rows and targets for a level-conditioned tube: the model's input is the row
+    plus one last column, the coverage level, so input_dim is the data width + 1.  The data holds no level: the trainer draws one
+    per row at every step on the device, and the row's pinball loss takes it in place of alpha -- one level per row, where the
+    reference's AlphaScalarTubeLoss broadcasts (B,) against (B, 1) to B x B."""
+    conditioned = True
+
+    @classmethod
+    def from_folder(cls, src, N=1, dN=1, recursive=False):
+        ds = _load(src)
+        x, y = cls._rows(*cls._sequences(ds, N, dN, recursive), ds["done"])
+        return cls(x, y, x.shape[1] + 1, 1)
+
+
+class LevelVectorTubeDataset(VectorTubeDataset):
+    """VectorTubeDataset's rows and targets for a level-conditioned tube; see LevelScalarTubeDataset."""
+    conditioned = True
+
+    @classmethod
+    def from_folder(cls, src, N=1, dN=1):
+        ds = _load(src)
+        x, y = cls._rows(*cls._sequences(ds, N, dN), ds["done"])
+        return cls(x, y, x.shape[1] + 1, y.shape[1])
+
+
 DATASETS = {"scalar": ScalarTubeDataset, "vector": VectorTubeDataset, "error_dynamics": ErrorDynamicsDataset,
-            "scalar_horizon": ScalarHorizonTubeDataset}
+            "scalar_horizon": ScalarHorizonTubeDataset, "scalar_level": LevelScalarTubeDataset,
+            "vector_level": LevelVectorTubeDataset}
+LEVEL_KINDS = {"scalar_level": "scalar", "vector_level": "vector"}     # conditioned kind -> the kind whose rows it has
 
 
 def sequences(kind, src, **window_args):
     """The per-env, time-ordered rows that ``DATASETS[kind].from_folder(src, **window_args)`` builds before it drops the done
     rows: float32 tensors data (E, T, input_dim) and target (E, T, output_dim), and done (E, T) bool.  Row (e, t) holds the
     model's input at step t and its target, the quantity one step ahead; a done row's target belongs to the next episode.
-    Flat kinds only: the horizon dataset has no rows."""
+    Flat kinds only: the horizon dataset has no rows.  A level kind returns its base kind's rows (input_dim - 1 columns: the
+    level column is the caller's to append, HipTubeModel.with_level)."""
     if kind not in DATASETS or kind == "scalar_horizon":
         raise ValueError(f"sequences: kind {kind!r} has no per-step rows; one of {[k for k in DATASETS if k != 'scalar_horizon']}")
     ds = _load(src)
@@ -245,7 +274,9 @@ def feedback_width(kind, N=1, dN=1, recursive=False, n=None):
     """How many leading input columns of a `kind` row are the model's own previous output, i.e. what a closed-loop roll-out
     feeds back: 1 (the error norm w) for scalar, n (the ROM state width) for vector and error_dynamics.  Raises
     NotImplementedError where the fed-back quantity also sits in delayed window taps (N > 1 with vector, error_dynamics or
-    recursive=True): those taps would have to come from the roll-out's own past, and the reference rolls out N = 1 only."""
+    recursive=True): those taps would have to come from the roll-out's own past, and the reference rolls out N = 1 only.
+    A level kind has its base kind's width: the level column is the last one."""
+    kind = LEVEL_KINDS.get(kind, kind)
     if kind == "scalar":
         if N > 1 and recursive:
             raise NotImplementedError("roll-out of a recursive scalar window (N > 1): the delayed taps hold w too")
@@ -270,7 +301,12 @@ def feedback_layout(kind, N=1, dN=1, recursive=False, n=None, m=None):
     The lag is 1 row whatever dN is: get_slice keeps every dN-th sample counted back from the end of the episode in EVERY
     block, block 0 included, so the rows of a dN > 1 dataset are a subsampled series (padded in front) in which block i still
     trails block 0 by i rows.  That is the window the model was trained on, so it is the one a roll-out over these rows feeds.
-    Unlike feedback_width it refuses no window: the delayed taps come from the roll-out's own past."""
+    Unlike feedback_width it refuses no window: the delayed taps come from the roll-out's own past.
+    A level kind (scalar_level, vector_level) has its base kind's layout; its row carries the level as one more, last, column, which
+    no block reaches ((taps - 1) * stride + fb <= input_dim holds as before), so only the non-recursive scalar stride, which
+    counts the whole row, grows by one: 1 + N (n - 2 + m) + 1."""
+    level = kind in LEVEL_KINDS
+    kind = LEVEL_KINDS.get(kind, kind)
     if N < 1 or dN < 1:
         raise ValueError(f"feedback_layout: N={N} and dN={dN} must be at least 1")
     if kind not in ("scalar", "vector", "error_dynamics"):
@@ -280,6 +316,6 @@ def feedback_layout(kind, N=1, dN=1, recursive=False, n=None, m=None):
     n, m = int(n), int(m)
     if kind == "scalar":
         if not recursive:
-            return 1, 1, 1, 1 + N * (n - 2 + m)
+            return 1, 1, 1, 1 + N * (n - 2 + m) + int(level)
         return 1, int(N), 1, 1 + (n - 2) + m
     return n, int(N), 1, 2 * n + m

@@ -1,5 +1,5 @@
 """HipTubeModel: a trained tube MLP for inference only -- ``predict``, ``predict_windows``, ``rollout`` and
-``rollout_window`` on the HIP kernels.
+``rollout_window`` on the HIP kernels, and ``predict_levels`` / ``with_level`` for a level-conditioned model.
 
 It wraps the same ``lg_tube`` handle the trainer uses; the model's shape comes from the state dict, and what the state dict
 cannot say (activation, Softplus beta, the horizon) from the run's ``config.json`` (train_tube.py writes it) or from keywords.
@@ -34,20 +34,22 @@ def read_config(run_dir):
 
 
 class HipTubeModel:
-    def __init__(self, state_dict, activation="relu", softplus_beta=1.0, horizon=None, device="cuda:0"):
-        """horizon: None, or (H_fwd, H_rev) for a ScalarHorizonTubeDataset model."""
+    def __init__(self, state_dict, activation="relu", softplus_beta=1.0, horizon=None, device="cuda:0", level_input=False):
+        """horizon: None, or (H_fwd, H_rev) for a ScalarHorizonTubeDataset model.  level_input: a level-conditioned model, whose
+        last input column is the coverage level (predict_levels, with_level)."""
         I, O, U, L = shape_from_state_dict(state_dict)
         self._tr = HipTubeTrainer(I, O, num_units=U, num_layers=L, activation=activation, softplus_beta=softplus_beta,
-                                  loss="scalar", alpha=0.5, batch_size=32, horizon=tuple(horizon) if horizon else None,
-                                  device=device)
+                                  loss="scalar_level" if level_input else "scalar", alpha=0.5, batch_size=32,
+                                  horizon=tuple(horizon) if horizon else None, device=device)
         self._tr.load_state_dict(state_dict)
+        self.level_input = bool(level_input)
         self.input_dim, self.output_dim, self.num_units, self.num_layers = I, O, U, L
         self.activation, self.softplus_beta, self.horizon, self.device = activation, softplus_beta, self._tr.horizon, self._tr.device
 
     @classmethod
-    def load(cls, src, checkpoint="latest", activation=None, softplus_beta=None, horizon=None, device="cuda:0"):
-        """src: a train_tube.py run folder (its config.json supplies activation, softplus_beta and the horizon; keywords
-        replace them) or a state dict (keywords, defaults relu / 1.0 / flat)."""
+    def load(cls, src, checkpoint="latest", activation=None, softplus_beta=None, horizon=None, device="cuda:0", level_input=None):
+        """src: a train_tube.py run folder (its config.json supplies activation, softplus_beta, the horizon and level_input;
+        keywords replace them) or a state dict (keywords, defaults relu / 1.0 / flat / unconditioned)."""
         cfg = {}
         if isinstance(src, (str, os.PathLike)):
             if checkpoint not in CHECKPOINTS:
@@ -61,10 +63,20 @@ class HipTubeModel:
             horizon = (cfg["H_fwd"], cfg["H_rev"])
         return cls(sd, activation=activation or cfg.get("activation", "relu"),
                    softplus_beta=softplus_beta if softplus_beta is not None else cfg.get("softplus_beta", 1.0),
-                   horizon=horizon, device=device)
+                   horizon=horizon, device=device,
+                   level_input=bool(cfg.get("level_input", False)) if level_input is None else level_input)
 
     def predict(self, x, rows=None):
         return self._tr.predict(x, rows)
+
+    def predict_levels(self, x, levels, rows=None):
+        return self._tr.predict_levels(x, levels, rows)
+
+    @staticmethod
+    def with_level(x, level):
+        """x (..., input_dim - 1) with the level column appended: the rows predict / rollout / rollout_window take on a
+        level-conditioned model."""
+        return torch.cat((x, torch.full_like(x[..., :1], float(level))), dim=-1)
 
     def predict_windows(self, ds, env, start):
         return self._tr.predict_windows(ds, env, start)

@@ -12,11 +12,12 @@ import torch
 
 from .. import capi
 from ..lib import LeggedHipError, device_tensor, load
-from .trainer import LOSSES, _numel, initial_params, param_shapes
+from .trainer import LEVEL_LOSSES, LOSSES, _numel, initial_params, param_shapes
 
-MEMBER_FIELDS = ("alpha", "delta", "activation", "softplus_beta", "lr", "gamma", "step_size", "seed")   # what members may differ in
+MEMBER_FIELDS = ("alpha", "delta", "activation", "softplus_beta", "lr", "gamma", "step_size", "seed",
+                 "level_lo", "level_hi")                                                 # what members may differ in
 DEFAULTS = dict(num_units=32, num_layers=2, activation="relu", softplus_beta=1.0, loss="scalar", alpha=0.8, delta=1.0, lr=1e-3,
-                gamma=0.1, step_size=10000, batch_size=2048, seed=42, horizon=None)       # HipTubeTrainer's
+                gamma=0.1, step_size=10000, batch_size=2048, seed=42, horizon=None, level_lo=0.0, level_hi=1.0)   # HipTubeTrainer's
 
 
 class _Member:
@@ -63,15 +64,16 @@ class HipTubeSweep:
                 raise ValueError(f"member {k}: activation {c['activation']!r}: one of {tuple(capi.TUBE_ACT)}")
             if c["loss"] not in LOSSES:
                 raise ValueError(f"member {k}: loss {c['loss']!r}: one of {tuple(LOSSES)}")
-            if c["loss"] != "error" and c["alpha"] is None:
+            if c["loss"] != "error" and c["loss"] not in LEVEL_LOSSES and c["alpha"] is None:
                 raise ValueError(f"member {k}: loss {c['loss']!r} needs alpha")
-            hz = c["horizon"]
+            hz, lv = c["horizon"], c["loss"] in LEVEL_LOSSES
             cfgs[k] = capi.lg_tube_cfg(input_dim=input_dim, output_dim=output_dim, num_units=c["num_units"], num_layers=c["num_layers"],
                                        activation=capi.TUBE_ACT[c["activation"]], loss=capi.TUBE_LOSS[LOSSES[c["loss"]]],
                                        horizon=int(hz is not None), batch_size=c["batch_size"], H_fwd=hz[0] if hz else 0,
                                        H_rev=hz[1] if hz else 0, step_size=c["step_size"], seed=c["seed"],
                                        alpha=c["alpha"] if c["alpha"] is not None else 0.0, delta=c["delta"],
-                                       softplus_beta=c["softplus_beta"], lr=c["lr"], gamma=c["gamma"])
+                                       softplus_beta=c["softplus_beta"], lr=c["lr"], gamma=c["gamma"], level_input=int(lv),
+                                       level_lo=c["level_lo"] if lv else 0.0, level_hi=c["level_hi"] if lv else 0.0)
         torch.cuda.set_device(self.device)
         h = C.c_void_p()
         self._call("create", cfgs, self.K, C.byref(h), obj=False)
@@ -79,6 +81,8 @@ class HipTubeSweep:
         c0 = self.configs[0]
         self.dims = (input_dim, output_dim, c0["num_units"], c0["num_layers"])
         self.loss, self.horizon, self.batch_size = c0["loss"], c0["horizon"], c0["batch_size"]
+        self.level_input = c0["loss"] in LEVEL_LOSSES
+        self.data_dim = input_dim - int(self.level_input)
         self.use_current_stream()
         self._views()
         for k, c in enumerate(self.configs):
@@ -97,7 +101,7 @@ class HipTubeSweep:
     def _views(self):
         """Per member, torch views of its buffers under the trainer's attribute names: self.params[k], self.adam_m[k], ..."""
         ptr = lambda p: C.cast(p, C.c_void_p).value
-        names = ("params", "grads", "adam_m", "adam_v", "log", "eval_buf", "starts", "perm")
+        names = ("params", "grads", "adam_m", "adam_v", "log", "eval_buf", "starts", "perm", "levels")
         for n in names:
             setattr(self, n, [])
         for k in range(self.K):
@@ -111,6 +115,7 @@ class HipTubeSweep:
             self.eval_buf.append(device_tensor(ptr(b.eval), (4,), "f4", self, self.device))
             self.starts.append(device_tensor(ptr(b.starts), (int(b.starts_cap),), "i4", self, self.device) if b.starts_cap else None)
             self.perm.append(device_tensor(ptr(b.perm), (int(b.perm_cap),), "i4", self, self.device) if b.perm_cap else None)
+            self.levels.append(device_tensor(ptr(b.levels), (int(b.levels_cap),), "f4", self, self.device) if b.levels_cap else None)
         offs, shp = (C.c_int64 * 16)(), (C.c_int64 * 32)()
         n = self.lib.lg_tube_sweep_param_layout(self.h, offs, shp, 16)
         self.layout = [(key, int(offs[i]), shape) for (key, shape), i in zip(param_shapes(*self.dims), range(n))]
@@ -155,8 +160,8 @@ class HipTubeSweep:
                            w.shape[0], w.shape[1], z.shape[2], v.shape[2])
             else:
                 x, y = (t.to(self.device, torch.float32).contiguous() for t in (ds.data, ds.target))
-                if x.shape[1] != self.dims[0] or y.shape[1] != self.dims[1]:
-                    raise ValueError(f"dataset dims {(x.shape[1], y.shape[1])} != model dims {self.dims[:2]}")
+                if x.shape[1] != self.data_dim or y.shape[1] != self.dims[1]:
+                    raise ValueError(f"dataset dims {(x.shape[1], y.shape[1])} != model dims {(self.data_dim, self.dims[1])}")
                 self._data[which] = (x, y)
                 self._call("set_data", which, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), None, x.shape[0], 0, 0, 0)
         self._views()
@@ -196,9 +201,22 @@ class HipTubeSweep:
         self._call("eval")
         return torch.stack(self.eval_buf)
 
+    def eval_level(self, level):
+        """Level-conditioned sweeps: evaluate() with every test row of every member at `level`; (K, 4), column 1 the coverage."""
+        if not self.level_input:
+            raise ValueError("eval_level: the sweep is not level-conditioned (loss scalar_level / vector_level)")
+        self._call("eval_level", C.c_float(float(level)))
+        return torch.stack(self.eval_buf)
+
+    def read_levels(self, k, count):
+        """Host copy of the levels member k drew for the first `count` rows of the last step or evaluation."""
+        if not self.level_input:
+            raise ValueError("read_levels: the sweep is not level-conditioned (loss scalar_level / vector_level)")
+        return self.levels[self._index(k)][:count].cpu()
+
     def close(self):
         if getattr(self, "h", None):
-            self.params = self.grads = self.adam_m = self.adam_v = self.log = self.eval_buf = self.starts = self.perm = None
+            self.params = self.grads = self.adam_m = self.adam_v = self.log = self.eval_buf = self.starts = self.perm = self.levels = None
             self.lib.lg_tube_sweep_destroy(self.h)
             self.h = None
 

@@ -3,7 +3,8 @@ include/legged_hip.h).
 
 A step is two launches on the current stream -- fused forward / loss / backward over the minibatch, then the fixed-order gradient
 reduction, Adam and StepLR -- and nothing in it waits for the device.  Loss, lr and gradient norm of every step stay in a device
-log until ``read_log``.  ``predict``, ``predict_windows``, ``rollout`` and ``rollout_window`` run the model as it stands (one launch
+log until ``read_log``.  A level-conditioned model (loss ``scalar_level`` / ``vector_level``) takes the
+coverage level as its last input column: ``eval_level``, ``predict_levels`` and ``read_levels`` are its own.  ``predict``, ``predict_windows``, ``rollout`` and ``rollout_window`` run the model as it stands (one launch
 each, the roll-outs included) and return device tensors.  There is no CPU fallback: without the library or a GPU the constructor raises.
 """
 import ctypes as C
@@ -15,11 +16,24 @@ from .. import capi
 from ..lib import LeggedHipError, device_tensor, load
 
 ACTIVATIONS = tuple(capi.TUBE_ACT)
-LOSSES = {"scalar": "scalar", "scalar_horizon": "scalar", "vector": "vector", "error": "mse"}   # reference loss -> kernel loss
+LOSSES = {"scalar": "scalar", "scalar_horizon": "scalar", "vector": "vector", "error": "mse",
+          "scalar_level": "scalar", "vector_level": "vector"}                                   # reference loss -> kernel loss
+LEVEL_LOSSES = ("scalar_level", "vector_level")     # level-conditioned: lg_tube_cfg.level_input, the last input column is the level
 
 
-def check_envelope(input_dim, output_dim, num_units, num_layers, activation="relu", final_activation=None):
-    """The supported model envelope (the C side refuses the same); raises ValueError / NotImplementedError outside it."""
+def check_envelope(input_dim, output_dim, num_units, num_layers, activation="relu", final_activation=None, loss=None,
+                   horizon=None, level_input=False, level_lo=0.0, level_hi=1.0):
+    """The supported model envelope (the C side refuses the same); raises ValueError / NotImplementedError outside it.
+    level_input: the level-conditioned tube, with the loss, the horizon and the level range it is asked with."""
+    if level_input:
+        if loss is not None and LOSSES.get(loss) == "mse":
+            raise ValueError("level_input needs a tube loss (scalar or vector): the mse loss has no level")
+        if horizon is not None:
+            raise NotImplementedError("level_input with a horizon dataset is not supported: predict_windows has no place for a level")
+        if input_dim < 2:
+            raise ValueError(f"input_dim={input_dim}: with level_input it counts the level column and must be at least 2")
+        if not 0.0 <= level_lo < level_hi <= 1.0:
+            raise ValueError(f"level range [{level_lo}, {level_hi}): 0 <= level_lo < level_hi <= 1")
     if final_activation is not None:
         raise NotImplementedError("final_activation other than None is not supported (no reference configuration uses one)")
     if activation not in ACTIVATIONS:
@@ -58,11 +72,15 @@ def initial_params(input_dim, output_dim, num_units, num_layers, seed):
 class HipTubeTrainer:
     def __init__(self, input_dim, output_dim, num_units=32, num_layers=2, activation="relu", softplus_beta=1.0,
                  loss="scalar", alpha=0.8, delta=1.0, lr=1e-3, gamma=0.1, step_size=10000, batch_size=2048, seed=42,
-                 horizon=None, final_activation=None, device="cuda:0"):
-        """horizon: None for the row datasets, (H_fwd, H_rev) for ScalarHorizonTubeDataset."""
-        check_envelope(input_dim, output_dim, num_units, num_layers, activation, final_activation)
+                 horizon=None, final_activation=None, device="cuda:0", level_lo=0.0, level_hi=1.0):
+        """horizon: None for the row datasets, (H_fwd, H_rev) for ScalarHorizonTubeDataset.  loss "scalar_level" /
+        "vector_level": the level-conditioned tube -- input_dim counts the level column (the last one), the data has
+        input_dim - 1 columns, every row of a step draws its level uniformly from [level_lo, level_hi), alpha is not read."""
         if loss not in LOSSES:
             raise ValueError(f"loss {loss!r}: one of {tuple(LOSSES)}")
+        self.level_input = loss in LEVEL_LOSSES
+        check_envelope(input_dim, output_dim, num_units, num_layers, activation, final_activation, loss=loss, horizon=horizon,
+                       level_input=self.level_input, level_lo=level_lo, level_hi=level_hi)
         if loss in ("scalar", "scalar_horizon", "vector") and alpha is None:
             raise ValueError(f"loss {loss!r} needs alpha")
         self.device = torch.device(device)
@@ -77,8 +95,10 @@ class HipTubeTrainer:
                                horizon=int(horizon is not None), batch_size=batch_size,
                                H_fwd=horizon[0] if horizon else 0, H_rev=horizon[1] if horizon else 0, step_size=step_size,
                                seed=seed, alpha=alpha if alpha is not None else 0.0, delta=delta, softplus_beta=softplus_beta,
-                               lr=lr, gamma=gamma)
+                               lr=lr, gamma=gamma, level_input=int(self.level_input),
+                               level_lo=level_lo if self.level_input else 0.0, level_hi=level_hi if self.level_input else 0.0)
         self.batch_size = batch_size
+        self.data_dim = input_dim - int(self.level_input)          # columns of the data: the level column is not in it
         torch.cuda.set_device(self.device)
         self.h = C.c_void_p()
         self._call("create", C.byref(cfg), C.byref(self.h), obj=False)
@@ -110,6 +130,7 @@ class HipTubeTrainer:
         self.eval_buf = device_tensor(ptr(b.eval), (4,), "f4", self, self.device)
         self.starts = device_tensor(ptr(b.starts), (int(b.starts_cap),), "i4", self, self.device) if b.starts_cap else None
         self.perm = device_tensor(ptr(b.perm), (int(b.perm_cap),), "i4", self, self.device) if b.perm_cap else None
+        self.levels = device_tensor(ptr(b.levels), (int(b.levels_cap),), "f4", self, self.device) if b.levels_cap else None
         self.step_count = int(b.step)
         offs, shp = (C.c_int64 * 16)(), (C.c_int64 * 32)()
         n = self.lib.lg_tube_param_layout(self.h, offs, shp, 16)
@@ -148,8 +169,8 @@ class HipTubeTrainer:
                            w.shape[0], w.shape[1], z.shape[2], v.shape[2])
             else:
                 x, y = (t.to(self.device, torch.float32).contiguous() for t in (ds.data, ds.target))
-                if x.shape[1] != self.dims[0] or y.shape[1] != self.dims[1]:
-                    raise ValueError(f"dataset dims {(x.shape[1], y.shape[1])} != model dims {self.dims[:2]}")
+                if x.shape[1] != self.data_dim or y.shape[1] != self.dims[1]:
+                    raise ValueError(f"dataset dims {(x.shape[1], y.shape[1])} != model dims {(self.data_dim, self.dims[1])}")
                 self._data[which] = (x, y)
                 self._call("set_data", which, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), None, x.shape[0], 0, 0, 0)
         self._views()
@@ -188,7 +209,51 @@ class HipTubeTrainer:
         self._call("eval")
         return self.eval_buf.clone()
 
+    def eval_level(self, level):
+        """Level-conditioned models: evaluate() with every test row at `level` (0..1) instead of a drawn one; entry 1 is then
+        the coverage at that level."""
+        self._need_level("eval_level")
+        self._call("eval_level", C.c_float(float(level)))
+        return self.eval_buf.clone()
+
+    def read_levels(self, count):
+        """Host copy of the levels of the first `count` rows of the last step or evaluation (row order of that batch)."""
+        self._need_level("read_levels")
+        if self.levels is None or not 0 <= count <= self.levels.numel():
+            raise ValueError(f"count={count}: 0..{0 if self.levels is None else self.levels.numel()} (set_data sizes the buffer)")
+        return self.levels[:count].cpu()
+
+    def _need_level(self, what):
+        if not self.level_input:
+            raise ValueError(f"{what}: the model is not level-conditioned (loss scalar_level / vector_level)")
+
     # ---------------------------------------------------------------- inference (reads the parameters, changes nothing)
+    def predict_levels(self, x, levels, rows=None):
+        """Level-conditioned models: MLP([x[rows], level]) for every level of `levels` (1..64 values) in one launch, as a device
+        tensor (count, n_levels, output_dim); x (n, input_dim - 1) holds no level column.  Entry [i, l] equals, bit for bit,
+        predict() on row i with levels[l] appended."""
+        self._need_level("predict_levels")
+        x = self._f32(x)
+        if x.dim() != 2 or x.shape[1] != self.data_dim or x.shape[0] < 1:
+            raise ValueError(f"x must be (n >= 1, {self.data_dim}); got {tuple(x.shape)}")
+        levels = self._f32(torch.as_tensor(levels)).reshape(-1)
+        if not 1 <= levels.numel() <= capi.TUBE_MAX_LEVELS:
+            raise ValueError(f"{levels.numel()} levels: 1..{capi.TUBE_MAX_LEVELS}")
+        count, rp = x.shape[0], None
+        if rows is not None:
+            rows = rows.to(self.device, torch.int32).contiguous().reshape(-1)
+            count = rows.numel()
+            if count < 1:
+                raise ValueError("rows is empty")
+            if int(rows.min()) < 0 or int(rows.max()) >= x.shape[0]:
+                raise IndexError(f"rows must lie in 0..{x.shape[0] - 1}")
+            rp = C.c_void_p(rows.data_ptr())
+        out = torch.empty(count, levels.numel(), self.dims[1], device=self.device, dtype=torch.float32)
+        self._call("predict_levels", C.c_void_p(x.data_ptr()), rp, count, C.c_void_p(levels.data_ptr()), levels.numel(),
+                   C.c_void_p(out.data_ptr()))
+        self._keep = (x, rows, levels)
+        return out
+
     def predict(self, x, rows=None):
         """MLP(x[rows]) (every row of x in order when rows is None) as a device tensor (count, output_dim); flat models."""
         if self.horizon is not None:
@@ -300,7 +365,7 @@ class HipTubeTrainer:
 
     def close(self):
         if getattr(self, "h", None):
-            self.params = self.grads = self.adam_m = self.adam_v = self.log = self.eval_buf = self.starts = self.perm = None
+            self.params = self.grads = self.adam_m = self.adam_v = self.log = self.eval_buf = self.starts = self.perm = self.levels = None
             self.lib.lg_tube_destroy(self.h)
             self.h = None
 

@@ -13,6 +13,12 @@ loss, backward, Adam, StepLR, gradient norm -- with no .item() in the loop.
 against K HipTubeTrainer runs with the same member configurations executed one after the other (their timed stretches summed),
 same warm-up, same steps, each timing closed by a device synchronise.
     python tools/bench_tube.py --steps 300 --sweep 1,4,16
+
+--level adds the level-conditioned leg: the time per step of a level-conditioned trainer (loss
+scalar_level: data of 3 columns, the level drawn on the device as the 4th input) against the unconditioned trainer of the same
+shape whose data holds one more column (4 inputs), default model and batch.  Median of --repeats after a warm-up, every timing
+closed by a device synchronise.
+    python tools/bench_tube.py --steps 400 --level
 """
 import argparse
 import json
@@ -56,6 +62,16 @@ def make(cfg, g):
     return dict(kw=dict(input_dim=Hr + 2 * (Hr + Hf), output_dim=Hf, num_units=128, num_layers=2, activation="softplus",
                         softplus_beta=5.0, loss="vector", alpha=0.9, step_size=1000, gamma=0.75, horizon=(Hf, Hr)),
                 data=_Horizon(w.to(DEV), z.to(DEV), v.to(DEV), Hf, Hr), rows=E, horizon=(Hf, Hr))
+
+
+def make_level(g):
+    """The default config's rows; `plain` carries a 4th data column where `level` draws its level column on the device."""
+    n = 8192 * 200
+    x = torch.rand(n, 4, generator=g)
+    y = (x[:, :1] + 0.1 * torch.rand(n, 1, generator=g)).to(DEV)
+    kw = dict(input_dim=4, output_dim=1, num_units=32, num_layers=2, activation="relu", step_size=2000)
+    return {"level": dict(kw=dict(loss="scalar_level", **kw), data=_Flat(x[:, :3].contiguous().to(DEV), y), rows=n, horizon=None),
+            "plain": dict(kw=dict(loss="scalar", alpha=0.8, **kw), data=_Flat(x.to(DEV), y), rows=n, horizon=None)}
 
 
 def sweep_members(K):
@@ -141,8 +157,19 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--configs", default="default,oneshot")
     ap.add_argument("--sweep", default=None, help="member counts of the sweep leg, e.g. 1,4,16 (replaces the torch comparison)")
+    ap.add_argument("--level", action="store_true", help="the level-conditioned step against the unconditioned step (replaces the torch comparison)")
     a = ap.parse_args()
     B = 2048
+    if a.level:
+        cs = make_level(torch.Generator().manual_seed(0))
+        res = {"config": "level_step", "steps": a.steps, "batch": B, "repeats": a.repeats, "device": torch.cuda.get_device_name(0)}
+        for who in ("plain", "level", "plain_again"):            # the unconditioned leg twice: the run-to-run spread
+            ts = sorted(time_hip(cs[who.split("_")[0]], a.steps, B) for _ in range(a.repeats))
+            res[who] = {"us_per_step_median": round(1e6 * ts[len(ts) // 2] / a.steps, 1),
+                        "us_per_step_all": [round(1e6 * t / a.steps, 1) for t in ts]}
+        res["level_over_plain"] = round(res["level"]["us_per_step_median"] / res["plain"]["us_per_step_median"], 3)
+        print(json.dumps(res), flush=True)
+        return
     if a.sweep:
         for cfg in a.configs.split(","):
             c = make(cfg, torch.Generator().manual_seed(0))

@@ -11,6 +11,10 @@
     window_error_64 / _4096      the same for error-dynamics rows, N = 10 taps of (e, z, v): 60 inputs, 2 outputs, 2 columns fed
                                  back per tap, 128 units x 2 layers Softplus(beta 5)
                                  Both also time rollout() -- one tap fed back -- on the same model and rows: the ring's cost.
+    levels_4096 / _389120        predict_levels with 8 levels on that many rows of the 128 units x 2 layers Softplus model (5 data
+                                 columns + the level), against the way without it: 8 predict() calls on the rows with the level
+                                 column appended by torch (torch.cat per level; the appended rows are built inside the timing).  Times are per call,
+                                 from windows of several calls
 Torch eager is the literal loop: T times (write the fed-back columns -- for the windowed configs those of every tap, from the
 loop's own past outputs, as the reference's evaluate_error_dyn_simple.py gathers them -- and run the nn.Sequential on the batch);
 for the one-shot config the gather of every window by advanced indexing, then one forward.  Each timing ends in a device synchronise; median of
@@ -38,7 +42,7 @@ MODELS = {"default": dict(I=3, O=1, U=32, L=2, act="relu", beta=1.0, fb=1),
 WINDOWS = {"scalar": dict(I=30, O=1, U=32, L=2, act="relu", beta=1.0, fb=1, taps=10, dN=1, stride=3),
            "error": dict(I=60, O=2, U=128, L=2, act="softplus", beta=5.0, fb=2, taps=10, dN=1, stride=6)}
 CONFIGS = ["rollout_default_64", "rollout_default_4096", "rollout_vector_64", "rollout_vector_4096", "oneshot",
-           "window_scalar_64", "window_scalar_4096", "window_error_64", "window_error_4096"]
+           "window_scalar_64", "window_scalar_4096", "window_error_64", "window_error_4096", "levels_4096", "levels_389120"]
 
 
 class _Horizon:
@@ -123,6 +127,34 @@ def bench_window(name, n_seq, T, repeats):
             "hip_single_tap_us_per_step": one_t * 1e6 / T, "max_abs_diff": diff}
 
 
+def bench_levels(n, repeats):
+    Ix, O, U, L, n_levels = 5, 2, 128, 2, 8
+    g = torch.Generator().manual_seed(0)
+    x = (torch.rand(n, Ix, generator=g) * 0.8).to(DEV)
+    levels = torch.linspace(0.5, 0.99, n_levels).to(DEV)
+    m = HipTubeModel(initial_params(Ix + 1, O, U, L, 1), activation="softplus", softplus_beta=5.0, level_input=True, device=DEV)
+    lv = [float(v) for v in levels.cpu()]
+
+    iters = max(2, 1600000 // n)        # calls per timed window: a window of one small call would time the clock
+
+    def one_by_one():
+        return torch.stack([m.predict(m.with_level(x, v)) for v in lv], dim=1)
+
+    def loop(fn):
+        def run():
+            for _ in range(iters):
+                fn()
+        return run
+    hip_t, hip_all = (v if i == 0 else [t / iters for t in v] for i, v in enumerate(timed(loop(lambda: m.predict_levels(x, levels)), repeats)))
+    ref_t, ref_all = (v if i == 0 else [t / iters for t in v] for i, v in enumerate(timed(loop(one_by_one), repeats)))
+    hip_t, ref_t = hip_t / iters, ref_t / iters
+    same = bool(torch.equal(m.predict_levels(x, levels), one_by_one()))
+    m.close()
+    return {"rows": n, "levels": n_levels, "calls_per_timing": iters, "predict_levels_ms": hip_t * 1e3, "predict_per_level_ms": ref_t * 1e3,
+            "per_level_over_predict_levels": ref_t / hip_t, "predict_levels_ms_all": [t * 1e3 for t in hip_all],
+            "predict_per_level_ms_all": [t * 1e3 for t in ref_all], "bit_identical": same}
+
+
 def bench_oneshot(repeats):
     E, T, Hf, Hr, nz, mv = 4096, 1000, 50, 10, 2, 2
     g = torch.Generator().manual_seed(0)
@@ -160,6 +192,8 @@ def main():
     for cfg in a.configs.split(","):
         if cfg == "oneshot":
             res = bench_oneshot(a.repeats)
+        elif cfg.startswith("levels_"):
+            res = bench_levels(int(cfg.split("_")[1]), a.repeats)
         else:
             kind, name, n = cfg.split("_")
             res = (bench_window if kind == "window" else bench_rollout)(name, int(n), a.steps, a.repeats)
