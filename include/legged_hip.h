@@ -651,6 +651,42 @@ int lg_romsim_policy(lg_romsim *s, const float *obs, float *out, int64_t rows);
  * done (N, T) u8, x (N, T+1, 4) or NULL.  An env's records equal, bit for bit, lg_romsim_reset + repeated lg_romsim_step(NULL). */
 int lg_romsim_collect(lg_romsim *s, int32_t T, float *z, float *v, float *pz_x, uint8_t *done, float *x);
 
+/* ------------------------------------------------------------------ tube datasets built on the device:
+ * the rows of deep_tube_learning/datasets.py (tube/data.py) from records laid out as lg_romsim_collect or an epoch pickle has them:
+ * z, pz_x (n_env, T+1, n) f32, v (n_env, T, m) f32, done (n_env, T) u8.  Per (env e, step t < T) a base row b[e, t]:
+ *     scalar, recursive      (w, z[2:], v)      w = |pz_x - z|, sqrtf of the squares summed in column order, one rounding per op
+ *     scalar, not recursive  (z[2:], v)         and the single column w[e, t] in front of the whole window
+ *     vector                 (|pz_x - z|, z, v)
+ *     error dynamics         (pz_x - z, z, v)
+ * Block i < N of row (e, t) is b[e, src], src = (T-1 - i dN) - (T-1 - t) dN, when src >= 0, else b[e, 0] with its m v columns zeroed.
+ * The target is the leading quantity at t + 1 (1 column for scalar, n otherwise).
+ * compact = 1 drops the rows with done[e, t] != 0 -- and, with mark_last_env = 1, every row of the envs e with
+ * e % epoch_envs == epoch_envs - 1 (construct_dataset's done[-1, :] = True per epoch) -- keeping (env, time) order; the order and
+ * the bytes do not depend on the run (no atomics).  compact = 0 writes all n_env T rows in order.
+ * Envelope: n 2..6, m 1..4, N >= 1, dN >= 1, T >= 1, input_dim <= LG_TUBE_MAX_IN, epoch_envs divides n_env.
+ * Every entry returns 0, or -1 with the reason (the field named) in lg_last_error.  Every array is a DEVICE pointer; the builds
+ * queue their launches on `stream` and wait for nothing. */
+#define LG_TUBE_ROWS_SCALAR 0
+#define LG_TUBE_ROWS_VECTOR 1
+#define LG_TUBE_ROWS_ERROR 2
+typedef struct lg_tube_rows_spec {
+    int32_t kind /*LG_TUBE_ROWS_**/, N, dN, recursive;
+    int32_t n, m, T, n_env;
+    int32_t compact, mark_last_env, epoch_envs, _pad;
+} lg_tube_rows_spec;
+int lg_tube_rows_check(const lg_tube_rows_spec *spec);                  /* host code: needs no GPU */
+int lg_tube_rows_dims(const lg_tube_rows_spec *spec, int32_t *input_dim, int32_t *output_dim);   /* host code */
+int64_t lg_tube_rows_workspace(const lg_tube_rows_spec *spec);          /* bytes (0 for compact = 0); -1 outside the envelope */
+/* data (rows, input_dim), target (rows, output_dim) with room for n_env T rows; n_rows: one int64, the rows written.  workspace:
+ * lg_tube_rows_workspace bytes, 8-byte aligned; done and workspace may be NULL for compact = 0.  Rows past n_rows are not touched. */
+int lg_tube_rows_build(const lg_tube_rows_spec *spec, const float *z, const float *pz_x, const float *v, const uint8_t *done,
+                       float *data, float *target, int64_t *n_rows, void *workspace, void *stream);
+/* ScalarHorizonTubeDataset's arrays, padded in front by H_rev steps (w and z with their first sample, v with zeros):
+ * w (n_env, T + H_rev), z_no_pos (n_env, T + H_rev, n - 2) (no columns, and may be NULL, for n = 2), v_pad (n_env, T + H_rev, m).
+ * Uses steps 0..T-1 of z and pz_x.  No compaction. */
+int lg_tube_horizon_build(const float *z, const float *pz_x, const float *v, int64_t n_env, int32_t T, int32_t n, int32_t m,
+                          int32_t H_rev, float *w, float *z_no_pos, float *v_pad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

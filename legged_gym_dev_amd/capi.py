@@ -291,6 +291,28 @@ def declare_romsim_api(lib):
     lib.lg_romsim_collect.argtypes = [vp, i32, vp, vp, vp, vp, vp]
 
 
+TUBE_ROWS_KIND = {"scalar": 0, "vector": 1, "error_dynamics": 2}     # LG_TUBE_ROWS_*
+
+
+class lg_tube_rows_spec(C.Structure):
+    _fields_ = [
+        ("kind", i32), ("N", i32), ("dN", i32), ("recursive", i32),
+        ("n", i32), ("m", i32), ("T", i32), ("n_env", i32),
+        ("compact", i32), ("mark_last_env", i32), ("epoch_envs", i32), ("_pad", i32)]
+
+
+def declare_tube_data_api(lib):
+    vp, ps = C.c_void_p, C.POINTER(lg_tube_rows_spec)
+    if not hasattr(lib, "lg_tube_rows_build"):     # an A/B library (LG_HIP_LIB) built before the device builder
+        return
+    lib.lg_tube_rows_check.argtypes = [ps]
+    lib.lg_tube_rows_dims.argtypes = [ps, PI32, PI32]
+    lib.lg_tube_rows_workspace.argtypes = [ps]
+    lib.lg_tube_rows_workspace.restype = i64
+    lib.lg_tube_rows_build.argtypes = [ps, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.lg_tube_horizon_build.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp]
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p

@@ -41,6 +41,7 @@ def load():
         _declare_ppo(_lib)
         capi.declare_tube_api(_lib)
         capi.declare_romsim_api(_lib)
+        capi.declare_tube_data_api(_lib)
     return _lib
 
 

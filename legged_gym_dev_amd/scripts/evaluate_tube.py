@@ -1,9 +1,9 @@
 """Evaluate a trained tube model on recorded ROM tracking data: the numerical content of the reference's
 deep_tube_learning/evaluation/evaluate_tube.py, evaluate_error_dyn.py, evaluate_tube_oneshot.py, evaluate_tube_simple.py and
 evaluate_error_dyn_simple.py on the HIP kernels, without
-wandb or hydra and on recorded data instead of a fresh simulation.
+wandb or hydra, on recorded data (--data) or on a fresh simulation (--sim).
 
-    python legged_gym_dev_amd/scripts/evaluate_tube.py --run tube_runs/run0 --data rom_tracking_data/run1 \\
+    python legged_gym_dev_amd/scripts/evaluate_tube.py --run tube_runs/run0 (--data rom_tracking_data/run1 | --sim) \\
         [--checkpoint best|latest] [--horizon K] [--window_stride S] [--plot] [--out DIR]
 
 The run's config.json (train_tube.py writes it) says how the model and its inputs are built; for a run without one, give
@@ -22,6 +22,12 @@ A level-conditioned run (config.json level_input; datasets scalar_level, vector_
 default 0.5,0.8,0.9,0.95): eval.json's "levels" has one entry per level with the one-step metrics -- every level of every row from one
 predict_levels launch -- and the closed-loop roll-out with the level column filled.  The success rate rises with the level but need
 not equal it.
+
+--sim in place of --data scores the model on fresh robots, as the reference's evaluation scripts do: --sim_resident epochs (default 1)
+of --sim_envs envs x --sim_T steps are simulated then and there by the ROM-on-ROM simulator (tube/rom_sim.py HipRomSim) with
+--sim_seed, whose default differs from the run's training seeds, and the rows are built on the device (tube/device_data.py); every
+env is scored (the simulator never sets done).  --sim_envs and --sim_T default to the run's own sim flags, if it has them, then to the
+simulator's 8192 x 200.  eval.json then holds "source": "sim" and the sim flags instead of "data".
 
 Deliberate deviations from the reference scripts:
   * evaluate_tube.py:53 feeds the full z[t] to a model that ScalarTubeDataset trained on z[:, 2:] (the input widths differ).  The
@@ -53,7 +59,14 @@ DEFAULTS = {"N": 1, "dN": 1, "recursive": False, "H_fwd": 50, "H_rev": 10, "soft
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--run", required=True, help="folder train_tube.py wrote (model.pth, model_best.pth, config.json)")
-    ap.add_argument("--data", required=True, help="folder of epoch_<k>.pickle files")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--data", help="folder of epoch_<k>.pickle files")
+    src.add_argument("--sim", action="store_true", help="score fresh robots simulated on the device (HipRomSim)")
+    ap.add_argument("--sim_envs", type=int, default=None)
+    ap.add_argument("--sim_T", type=int, default=None)
+    ap.add_argument("--sim_seed", type=int, default=None, help="default: the smallest seed >= 1 the run did not train with")
+    ap.add_argument("--sim_resident", type=int, default=None, help="epochs to simulate (default 1)")
+    ap.add_argument("--sim_refresh", type=int, default=None, help="accepted for symmetry with train_tube.py; not read")
     ap.add_argument("--checkpoint", choices=["best", "latest"], default="best")
     ap.add_argument("--horizon", type=int, default=None, help="flat datasets: reseed the roll-out every K steps")
     ap.add_argument("--window_stride", type=int, default=1, help="scalar_horizon: distance between window starts")
@@ -89,12 +102,45 @@ def resolve_config(a):
     return {**DEFAULTS, **cfg}
 
 
+def sim_flags(a, cfg):
+    """The sim flags of an evaluation: what is given here, else the run's own (config.json of a --sim run), else the defaults."""
+    used = {cfg.get("seed"), cfg.get("sim_seed")}
+    f = {"sim_envs": a.sim_envs or cfg.get("sim_envs") or 8192, "sim_T": a.sim_T or cfg.get("sim_T"), "sim_resident": a.sim_resident or 1,
+         "sim_seed": a.sim_seed if a.sim_seed is not None else min(s for s in range(1, 4) if s not in used)}
+    if f["sim_envs"] < 1 or f["sim_resident"] < 1 or (f["sim_T"] is not None and f["sim_T"] < 1):
+        raise ValueError(f"--sim_envs, --sim_T and --sim_resident must be at least 1; got {f}")
+    return f
+
+
+def sim_records(f, device):
+    """Fresh robots: f["sim_resident"] epochs of the ROM-on-ROM simulator as one record dict of device tensors."""
+    from legged_gym_dev_amd.tube.rom_sim import HipRomSim, RomSimCfg
+    rc = RomSimCfg()
+    rc.env.num_envs = f["sim_envs"]
+    sim = HipRomSim(rc, seed=f["sim_seed"], device=device)
+    try:
+        recs = [sim.collect_epoch(f["sim_T"]) for _ in range(f["sim_resident"])]
+        torch.cuda.synchronize(sim.device)
+    finally:
+        sim.close()
+    return recs[0] if len(recs) == 1 else {k: torch.cat([r[k] for r in recs], dim=0) for k in ("z", "pz_x", "v", "done")}
+
+
+def rows(kind, raw, win, dev):
+    """sequences(kind, raw, **win) on `dev`: built there when the records already live on a device, on the host otherwise."""
+    if isinstance(raw["z"], torch.Tensor) and raw["z"].is_cuda:
+        from legged_gym_dev_amd.tube.device_data import build_rows
+        data, target = build_rows(raw, kind, compact=False, **win)
+        return data, target, raw["done"].ne(0)
+    return tuple(t.to(dev) for t in sequences(kind, raw, **win))
+
+
 def evaluate_flat(model, cfg, raw, horizon, dev):
     kind = cfg["dataset"]
     win = {"N": cfg["N"], "dN": cfg["dN"]}
     if kind == "scalar":
         win["recursive"] = cfg["recursive"]
-    data, target, done = (t.to(dev) for t in sequences(kind, raw, **win))
+    data, target, done = rows(kind, raw, win, dev)
     fb, taps, lag, stride = feedback_layout(kind, cfg["N"], cfg["dN"], cfg["recursive"], n=raw["z"].shape[-1], m=raw["v"].shape[-1])
     E, T, I = data.shape
     fw_single = model.predict(data.reshape(E * T, I)).reshape(E, T, -1)
@@ -116,7 +162,7 @@ def evaluate_levels(model, cfg, raw, horizon, dev, levels):
     win = {"N": cfg["N"], "dN": cfg["dN"]}
     if LEVEL_KINDS[kind] == "scalar":
         win["recursive"] = cfg["recursive"]
-    data, target, done = (t.to(dev) for t in sequences(kind, raw, **win))
+    data, target, done = rows(kind, raw, win, dev)
     fb, taps, lag, stride = feedback_layout(kind, cfg["N"], cfg["dN"], cfg["recursive"], n=raw["z"].shape[-1], m=raw["v"].shape[-1])
     E, T, I = data.shape
     single = model.predict_levels(data.reshape(E * T, I), torch.tensor(levels, dtype=torch.float32))      # (E T, levels, out)
@@ -134,7 +180,11 @@ def evaluate_levels(model, cfg, raw, horizon, dev, levels):
 
 
 def evaluate_horizon(model, cfg, raw, stride, dev):
-    ds = DATASETS["scalar_horizon"].from_folder(raw, H_fwd=cfg["H_fwd"], H_rev=cfg["H_rev"])
+    if isinstance(raw["z"], torch.Tensor) and raw["z"].is_cuda:
+        from legged_gym_dev_amd.tube.device_data import from_records
+        ds = from_records(DATASETS["scalar_horizon"], raw, H_fwd=cfg["H_fwd"], H_rev=cfg["H_rev"])
+    else:
+        ds = DATASETS["scalar_horizon"].from_folder(raw, H_fwd=cfg["H_fwd"], H_rev=cfg["H_rev"])
     Hf, Hr = ds.H_fwd, ds.H_rev
     E, T = ds.w.shape
     starts = torch.arange(Hr, T - Hf, max(1, stride), dtype=torch.int32)        # targets reach w[start + H_fwd] <= w[T - 1]
@@ -192,7 +242,8 @@ def main(argv=None):
     horizon = (cfg["H_fwd"], cfg["H_rev"]) if cfg["dataset"] == "scalar_horizon" else None
     model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, activation=cfg["activation"], softplus_beta=cfg["softplus_beta"],
                               horizon=horizon, device=a.device, level_input=cfg["dataset"] in LEVEL_KINDS)
-    raw = construct_dataset(a.data)
+    sim = sim_flags(a, cfg) if a.sim else None
+    raw = sim_records(sim, a.device) if a.sim else construct_dataset(a.data)
     levels = None
     if model.level_input:
         levels = [float(v) for v in a.levels.split(",")] if a.levels else list(DEFAULT_LEVELS)
@@ -206,7 +257,8 @@ def main(argv=None):
         torch.cuda.synchronize(dev)
     finally:
         model.close()
-    res.update({"run": os.path.abspath(a.run), "data": os.path.abspath(a.data), "checkpoint": a.checkpoint, "dataset": cfg["dataset"]})
+    res.update({"run": os.path.abspath(a.run), **({"source": "sim", **sim} if a.sim else {"data": os.path.abspath(a.data)}),
+                "checkpoint": a.checkpoint, "dataset": cfg["dataset"]})
     if a.plot:
         res["plots"] = plot(cfg["dataset"], series, out, a.plot_envs)
     with open(os.path.join(out, "eval.json"), "w") as f:

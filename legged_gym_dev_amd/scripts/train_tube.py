@@ -24,6 +24,13 @@ last input column, drawn per row and step from [--level_lo, --level_hi) on the d
 the dataset.  On evaluation steps metrics.jsonl also holds the test coverage at the levels 0.5, 0.8, 0.9 and 0.95.  --sweep works
 on top of it (over seed or lr, say).  The split is drawn once, seeded by --seed, or by the first
 value of a swept seed: the member with that seed matches its single run, the other seeds train on that split too.
+
+--sim in place of --data trains straight from the ROM-on-ROM simulator (tube/rom_sim.py HipRomSim): the epochs
+are collected, and the rows built, on the device; nothing is written to disk or copied to the host.  --sim_envs, --sim_T and --sim_seed
+set the simulator (defaults: its own 8192 envs and 200 steps, seed 0); the data set holds the last --sim_resident epochs and after
+every training epoch --sim_refresh new ones replace the oldest (the loop's dataset.update()), --sim_refresh 0 keeps it static: then
+the run equals, bit for bit, collect_rom_sim_data.py with those flags followed by --data.  It composes with --sweep and the level
+datasets; config.json records the sim flags.
 """
 import argparse
 import itertools
@@ -42,7 +49,11 @@ from legged_gym_dev_amd.tube.trainer import HipTubeTrainer  # noqa: E402
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--data", required=True, help="folder of epoch_<k>.pickle files")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--data", help="folder of epoch_<k>.pickle files")
+    src.add_argument("--sim", action="store_true", default=argparse.SUPPRESS, help="train on epochs simulated on the device (HipRomSim)")
+    for name, (tp, _, hlp) in SIM_FLAGS.items():
+        ap.add_argument("--" + name, type=tp, default=argparse.SUPPRESS, help="--sim: " + hlp)
     ap.add_argument("--dataset", choices=sorted(DATASETS), default="scalar")
     ap.add_argument("--N", type=int, default=1)
     ap.add_argument("--dN", type=int, default=1)
@@ -79,12 +90,24 @@ def parse_args(argv=None):
         a.level_lo, a.level_hi = getattr(a, "level_lo", 0.0), getattr(a, "level_hi", 1.0)
     elif a.loss in LEVEL_KINDS or hasattr(a, "level_lo") or hasattr(a, "level_hi"):
         ap.error("--loss scalar_level / vector_level, --level_lo and --level_hi need --dataset scalar_level or vector_level")
+    if getattr(a, "sim", False):        # the sim fields exist on a --sim run only: a --data run is as it was
+        for name, (_, default, _) in SIM_FLAGS.items():
+            setattr(a, name, getattr(a, name, default))
+        if a.sim_envs < 2 or a.sim_resident < 1 or a.sim_refresh < 0 or (a.sim_T is not None and a.sim_T < 1):
+            ap.error("--sim_envs must be at least 2 (every epoch's last env is dropped), --sim_resident and --sim_T at least 1, --sim_refresh at least 0")
+    elif any(hasattr(a, name) for name in SIM_FLAGS):
+        ap.error("--" + ", --".join(SIM_FLAGS) + " need --sim")
     try:
         a.sweep = parse_sweep(a.sweep)
     except ValueError as e:
         ap.error(str(e))
     return a
 
+
+# --sim's sub-flags: name -> (type, default, help)
+SIM_FLAGS = {"sim_envs": (int, 8192, "envs per epoch"), "sim_T": (int, None, "records per env and epoch (default: the simulator's 200)"),
+             "sim_seed": (int, 0, "the simulator's seed"), "sim_resident": (int, 1, "epochs the data set holds"),
+             "sim_refresh": (int, 1, "new epochs after every training epoch; 0: a static data set")}
 
 # the per-member fields of a sweep (tube/sweep.py MEMBER_FIELDS) and how their values parse; every other flag is shared
 SWEEP_FIELDS = {"alpha": float, "delta": float, "activation": str, "softplus_beta": float, "lr": float, "gamma": float,
@@ -131,19 +154,37 @@ def sweep_members(axes):
 CONFIG_KEYS = ("dataset", "N", "dN", "recursive", "H_fwd", "H_rev", "loss", "alpha", "delta", "num_units", "num_layers", "activation",
                "softplus_beta", "seed", "validation_split")
 LEVEL_CONFIG_KEYS = ("level_input", "level_lo", "level_hi")     # a level-conditioned run records these too
+SIM_CONFIG_KEYS = ("sim",) + tuple(SIM_FLAGS)                  # a --sim run records these too
 EVAL_LEVELS = (0.5, 0.8, 0.9, 0.95)     # a level-conditioned run logs its test coverage at these on every evaluation step
 
 
 def run_config(a):
     """The flags a later evaluation needs, as the dict written to config.json."""
-    return {k: getattr(a, k) for k in CONFIG_KEYS + (LEVEL_CONFIG_KEYS if _level(a) else ())}
+    return {k: getattr(a, k) for k in CONFIG_KEYS + (LEVEL_CONFIG_KEYS if _level(a) else ()) + (SIM_CONFIG_KEYS if _sim(a) else ())}
 
 
 def _level(a):
     return getattr(a, "level_input", False)
 
 
+def _sim(a):
+    return getattr(a, "sim", False)
+
+
+def make_sim_dataset(a):
+    """--sim: a HipRomSim of the reference's double_single_int configuration and the data set that lives on the device with it."""
+    from legged_gym_dev_amd.tube.device_data import SimTubeDataset
+    from legged_gym_dev_amd.tube.rom_sim import HipRomSim, RomSimCfg
+    cfg = RomSimCfg()
+    cfg.env.num_envs = a.sim_envs
+    sim = HipRomSim(cfg, seed=a.sim_seed, device=a.device)
+    return SimTubeDataset(sim, a.dataset, N=a.N, dN=a.dN, recursive=a.recursive, H_fwd=a.H_fwd, H_rev=a.H_rev, T=a.sim_T,
+                          resident_epochs=a.sim_resident, refresh=a.sim_refresh)
+
+
 def make_dataset(a):
+    if _sim(a):
+        return make_sim_dataset(a)
     ds = construct_dataset(a.data)
     if a.dataset in ("scalar", "scalar_level"):
         return DATASETS[a.dataset].from_folder(ds, N=a.N, dN=a.dN, recursive=a.recursive)
@@ -247,6 +288,9 @@ def main(argv=None):
                 tag = "" if members is None else f" [{members[k][0]}]"
                 print(f"epoch {epoch}{tag}: loss {total[k] / steps_per_epoch:.6f} lr {lr_epoch:.3g} ({steps_per_epoch} steps)", flush=True)
             dataset.update()
+            if getattr(dataset, "changed", False) and epoch + 1 < a.num_epochs:      # fresh rows, the same split: n_train is as it was
+                tr.set_data(*dataset.split())
+                dataset.changed = False
     finally:
         for mf in mfs:
             mf.close()
@@ -266,6 +310,8 @@ def main(argv=None):
         with open(os.path.join(a.out, "sweep.json"), "w") as f:
             json.dump(_nan_to_none(summary), f, indent=1, allow_nan=False)
     tr.close()
+    if _sim(a):
+        dataset.sim.close()
     return a.out
 
 
