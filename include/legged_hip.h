@@ -687,6 +687,21 @@ int lg_tube_rows_build(const lg_tube_rows_spec *spec, const float *z, const floa
 int lg_tube_horizon_build(const float *z, const float *pz_x, const float *v, int64_t n_env, int32_t T, int32_t n, int32_t m,
                           int32_t H_rev, float *w, float *z_no_pos, float *v_pad, void *stream);
 
+/* ------------------------------------------------------------------ batched exact k-th smallest: the order
+ * statistic of conformal calibration.  values (B, ld) f32, batch row b = values[b ld .. b ld + n), ld >= n, no alignment or padding
+ * asked of the rows; keep NULL or (n) u8 shared by every batch row, element i takes part iff keep[i] != 0; ranks (B, R) int64,
+ * 1-based; out (B, R) f32; n_kept one int64, the number of kept elements.  out[b, r] is the ranks[b, r]-th smallest kept element
+ * of row b in IEEE order: -0.0 counts and comes back as +0.0; every NaN sorts above +inf (torch.sort's place for it) and comes back
+ * as the canonical quiet NaN; a rank below 1 or above n_kept gives +inf.  Exact, and the same bits on every run: four passes of a
+ * most-significant-digit radix select over the order-preserving key, integer counting only.
+ * Envelope: 1 <= B <= 4096, 1 <= R <= 8, 1 <= n < 2^31.  Every array is a DEVICE pointer; workspace: lg_select_workspace(B, R)
+ * bytes, 8-byte aligned, contents arbitrary (the call clears it).  The call queues its work on `stream` and waits for nothing.
+ * 0, or -1 with the reason (the field named) in lg_last_error. */
+int64_t lg_select_workspace(int32_t B, int32_t R);     /* host code; bytes, -1 outside the envelope */
+int32_t lg_select_chunk(void);                         /* host code; elements per step of a workgroup's walk over its row */
+int lg_select_kth(const float *values, int64_t ld, int32_t B, int64_t n, const uint8_t *keep, const int64_t *ranks, int32_t R,
+                  float *out, int64_t *n_kept, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -313,6 +313,17 @@ def declare_tube_data_api(lib):
     lib.lg_tube_horizon_build.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp]
 
 
+def declare_select_api(lib):
+    vp = C.c_void_p
+    if not hasattr(lib, "lg_select_kth"):          # an A/B library (LG_HIP_LIB) built before the selection
+        return
+    lib.lg_select_workspace.argtypes = [i32, i32]
+    lib.lg_select_workspace.restype = i64
+    lib.lg_select_chunk.argtypes = []
+    lib.lg_select_chunk.restype = i32
+    lib.lg_select_kth.argtypes = [vp, i64, i32, i64, vp, vp, i32, vp, vp, vp, vp]
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p

@@ -42,6 +42,7 @@ def load():
         capi.declare_tube_api(_lib)
         capi.declare_romsim_api(_lib)
         capi.declare_tube_data_api(_lib)
+        capi.declare_select_api(_lib)
     return _lib
 
 

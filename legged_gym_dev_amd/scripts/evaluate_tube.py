@@ -4,7 +4,7 @@ evaluate_error_dyn_simple.py on the HIP kernels, without
 wandb or hydra, on recorded data (--data) or on a fresh simulation (--sim).
 
     python legged_gym_dev_amd/scripts/evaluate_tube.py --run tube_runs/run0 (--data rom_tracking_data/run1 | --sim) \\
-        [--checkpoint best|latest] [--horizon K] [--window_stride S] [--plot] [--out DIR]
+        [--checkpoint best|latest] [--horizon K] [--window_stride S] [--plot] [--out DIR] [--calibration [PATH]]
 
 The run's config.json (train_tube.py writes it) says how the model and its inputs are built; for a run without one, give
 --dataset, --activation and the other train_tube.py flags here (a flag given here replaces the file's value).
@@ -28,6 +28,12 @@ of --sim_envs envs x --sim_T steps are simulated then and there by the ROM-on-RO
 --sim_seed, whose default differs from the run's training seeds, and the rows are built on the device (tube/device_data.py); every
 env is scored (the simulator never sets done).  --sim_envs and --sim_T default to the run's own sim flags, if it has them, then to the
 simulator's 8192 x 200.  eval.json then holds "source": "sim" and the sim flags instead of "data".
+
+--calibration [PATH] (default PATH: the run's calibration.json, which calibrate_tube.py writes) scores the conformally calibrated
+tube as well: beside every metrics dict eval.json gains a "calibrated" dict with the same metrics on Calibration.apply'd
+predictions (prediction + offset), the offsets used and "covered", the count of scored elements with w - fw <= offset (the exact
+form of the comparison).  Evaluating on the calibration's own --sim_seed or --data folder is refused: coverage measured on the rows
+the offsets were fitted on says nothing.  Without the flag eval.json and the printed lines are what they were.
 
 Deliberate deviations from the reference scripts:
   * evaluate_tube.py:53 feeds the full z[t] to a model that ScalarTubeDataset trained on z[:, 2:] (the input widths differ).  The
@@ -71,6 +77,8 @@ def parse_args(argv=None):
     ap.add_argument("--horizon", type=int, default=None, help="flat datasets: reseed the roll-out every K steps")
     ap.add_argument("--window_stride", type=int, default=1, help="scalar_horizon: distance between window starts")
     ap.add_argument("--levels", default=None, help="level-conditioned runs: comma-separated coverage levels (default 0.5,0.8,0.9,0.95)")
+    ap.add_argument("--calibration", nargs="?", const="", default=None, metavar="PATH",
+                    help="also score the calibrated tube; PATH defaults to the run's calibration.json")
     ap.add_argument("--plot", action="store_true", help="save w / fw / fw_single PNGs per env to --out")
     ap.add_argument("--plot_envs", type=int, default=4)
     ap.add_argument("--out", default=None)
@@ -135,7 +143,46 @@ def rows(kind, raw, win, dev):
     return tuple(t.to(dev) for t in sequences(kind, raw, **win))
 
 
-def evaluate_flat(model, cfg, raw, horizon, dev):
+def load_calibration(a, cfg, sim):
+    """The Calibration --calibration names, or None without the flag.  Refuses, with the reason, a calibration of another kind of
+    model and an evaluation on the calibration's own robots."""
+    if a.calibration is None:
+        return None
+    from legged_gym_dev_amd.tube.calibrate import Calibration, default_path
+    path = a.calibration or default_path(a.run)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path} is missing: calibrate_tube.py --run {a.run} writes it")
+    c = Calibration.load(path)
+    kind = "levels" if cfg["dataset"] in LEVEL_KINDS else "horizon" if cfg["dataset"] == "scalar_horizon" else "flat"
+    if c.kind != kind or c.provenance.get("dataset", cfg["dataset"]) != cfg["dataset"]:
+        raise ValueError(f"{path} calibrates a {c.provenance.get('dataset', c.kind)} model; the run is {cfg['dataset']}")
+    if sim is not None and c.provenance.get("source") == "sim" and c.provenance.get("sim_seed") == sim["sim_seed"]:
+        raise ValueError(f"--sim_seed {sim['sim_seed']} is the seed {path} was calibrated on: coverage on the calibration's own robots "
+                         "says nothing about fresh ones; give another --sim_seed")
+    if a.data is not None and c.provenance.get("data") == os.path.abspath(a.data):
+        raise ValueError(f"--data {a.data} is the folder {path} was calibrated on: coverage on the calibration's own rows says nothing "
+                         "about fresh ones; give another folder")
+    return c
+
+
+def _cal_safe(o):
+    """inf (the offset of a set with too few calibration rows, and what it does to a mean) becomes the string "inf"."""
+    if isinstance(o, dict):
+        return {k: _cal_safe(v) for k, v in o.items()}
+    if isinstance(o, (list, tuple)):
+        return [_cal_safe(v) for v in o]
+    return ("inf" if o > 0 else "-inf") if isinstance(o, float) and o in (float("inf"), float("-inf")) else o
+
+
+def calibrated_tube(c, fw, target, done, reseed, coverage, part, level=None):
+    """tube_metrics of the calibrated prediction, the offsets, and the exact count of covered scored elements."""
+    m = ev.tube_metrics(c.apply(fw, coverage, level, part), target, done, reseed)
+    m["offset"] = c.offset(coverage, level, part).tolist()
+    m["covered"] = int((c.covers(fw, target, coverage, level, part) & ~done.bool()[:, :, None]).sum())
+    return _cal_safe(m)
+
+
+def evaluate_flat(model, cfg, raw, horizon, dev, calib=None):
     kind = cfg["dataset"]
     win = {"N": cfg["N"], "dN": cfg["dN"]}
     if kind == "scalar":
@@ -149,13 +196,17 @@ def evaluate_flat(model, cfg, raw, horizon, dev):
     ed = kind == "error_dynamics"
     res = {"one_step": ev.tube_metrics(fw_single, target, done, None, ed), "rollout": ev.tube_metrics(fw, target, done, reseed, ed),
            "feedback_width": fb, "feedback_taps": taps, "feedback_dN": lag, "feedback_stride": stride, "envs": E, "steps_per_env": T, "reseed_every": horizon}
+    if calib is not None:
+        res["calibrated"] = {"n": calib.n, "coverages": calib.coverages, "ranks": calib.ranks,
+                             "one_step": [calibrated_tube(calib, fw_single, target, done, None, cv, "one_step") for cv in calib.coverages],
+                             "rollout": [calibrated_tube(calib, fw, target, done, reseed, cv, "rollout") for cv in calib.coverages]}
     return res, {"w": target, "fw": fw, "fw_single": fw_single, "done": done}
 
 
 DEFAULT_LEVELS = (0.5, 0.8, 0.9, 0.95)
 
 
-def evaluate_levels(model, cfg, raw, horizon, dev, levels):
+def evaluate_levels(model, cfg, raw, horizon, dev, levels, calib=None):
     """evaluate_flat per level of a level-conditioned model: the one-step predictions of all levels from one predict_levels
     launch, the roll-out per level on the rows with the column filled."""
     kind = cfg["dataset"]
@@ -172,6 +223,10 @@ def evaluate_levels(model, cfg, raw, horizon, dev, levels):
         fw_single = single[:, i, :].reshape(E, T, -1)
         fw = model.rollout_window(model.with_level(data, lv), fb, taps, lag, stride, reseed)
         per_level.append({"level": lv, "one_step": ev.tube_metrics(fw_single, target, done), "rollout": ev.tube_metrics(fw, target, done, reseed)})
+        if calib is not None:
+            per_level[-1]["calibrated"] = {"n": calib.n, "rank": calib.ranks[calib.index(lv)],
+                                           "one_step": calibrated_tube(calib, fw_single, target, done, None, lv, "one_step"),
+                                           "rollout": calibrated_tube(calib, fw, target, done, reseed, lv, "rollout")}
         if i == len(levels) - 1:
             series = {"w": target, "fw": fw, "fw_single": fw_single, "done": done}
     res = {"levels": per_level, "feedback_width": fb, "feedback_taps": taps, "feedback_dN": lag, "feedback_stride": stride, "envs": E,
@@ -179,7 +234,7 @@ def evaluate_levels(model, cfg, raw, horizon, dev, levels):
     return res, series
 
 
-def evaluate_horizon(model, cfg, raw, stride, dev):
+def evaluate_horizon(model, cfg, raw, stride, dev, calib=None):
     if isinstance(raw["z"], torch.Tensor) and raw["z"].is_cuda:
         from legged_gym_dev_amd.tube.device_data import from_records
         ds = from_records(DATASETS["scalar_horizon"], raw, H_fwd=cfg["H_fwd"], H_rev=cfg["H_rev"])
@@ -197,6 +252,10 @@ def evaluate_horizon(model, cfg, raw, stride, dev):
     idx = start.to(dev).long()[:, None] + torch.arange(1, Hf + 1, device=dev)[None, :]
     target = w[env.to(dev).long()[:, None], idx]
     res = {"one_shot": ev.window_metrics(fw, target), "envs": E, "windows_per_env": int(starts.numel()), "window_stride": stride}
+    if calib is not None:
+        res["calibrated"] = {"n": calib.n, "coverages": calib.coverages, "ranks": calib.ranks, "one_shot": [_cal_safe(
+            {**ev.window_metrics(calib.apply(fw, cv), target), "offset": calib.offset(cv).tolist(),
+             "covered_by_step": calib.covers(fw, target, cv).sum(dim=0).tolist()}) for cv in calib.coverages]}
     return res, {"w": target.reshape(E, -1, Hf), "fw": fw.reshape(E, -1, Hf), "starts": starts}
 
 
@@ -240,23 +299,27 @@ def main(argv=None):
     out = a.out or a.run
     os.makedirs(out, exist_ok=True)
     horizon = (cfg["H_fwd"], cfg["H_rev"]) if cfg["dataset"] == "scalar_horizon" else None
+    sim = sim_flags(a, cfg) if a.sim else None
+    calib = load_calibration(a, cfg, sim)
+    extra = {} if calib is None else {"calib": calib}
     model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, activation=cfg["activation"], softplus_beta=cfg["softplus_beta"],
                               horizon=horizon, device=a.device, level_input=cfg["dataset"] in LEVEL_KINDS)
-    sim = sim_flags(a, cfg) if a.sim else None
     raw = sim_records(sim, a.device) if a.sim else construct_dataset(a.data)
     levels = None
     if model.level_input:
         levels = [float(v) for v in a.levels.split(",")] if a.levels else list(DEFAULT_LEVELS)
     try:
         if levels is not None:
-            res, series = evaluate_levels(model, cfg, raw, a.horizon, dev, levels)
+            res, series = evaluate_levels(model, cfg, raw, a.horizon, dev, levels, **extra)
         elif horizon is None:
-            res, series = evaluate_flat(model, cfg, raw, a.horizon, dev)
+            res, series = evaluate_flat(model, cfg, raw, a.horizon, dev, **extra)
         else:
-            res, series = evaluate_horizon(model, cfg, raw, a.window_stride, dev)
+            res, series = evaluate_horizon(model, cfg, raw, a.window_stride, dev, **extra)
         torch.cuda.synchronize(dev)
     finally:
         model.close()
+    if calib is not None:
+        res["calibration"] = os.path.abspath(a.calibration or os.path.join(a.run, "calibration.json"))
     res.update({"run": os.path.abspath(a.run), **({"source": "sim", **sim} if a.sim else {"data": os.path.abspath(a.data)}),
                 "checkpoint": a.checkpoint, "dataset": cfg["dataset"]})
     if a.plot:
@@ -274,6 +337,15 @@ def main(argv=None):
             print(f"Mean One Step Error: {res['one_step']['mse']}")
     else:
         print(f"Total Success Rate: {res['one_shot']['success_rate']}")
+    if calib is not None:
+        if levels is not None:
+            for r in res["levels"]:
+                print(f"calibrated level {r['level']}: Single Success Rate: {r['calibrated']['one_step']['success_rate']}  "
+                      f"Total Success Rate: {r['calibrated']['rollout']['success_rate']}")
+        else:
+            for part in ("one_step", "rollout", "one_shot"):
+                for cv, m in zip(calib.coverages, res["calibrated"].get(part, [])):
+                    print(f"calibrated coverage {cv} {part}: Success Rate: {m['success_rate']}")
     return res
 
 
