@@ -702,6 +702,26 @@ int32_t lg_select_chunk(void);                         /* host code; elements pe
 int lg_select_kth(const float *values, int64_t ld, int32_t B, int64_t n, const uint8_t *keep, const int64_t *ranks, int32_t R,
                   float *out, int64_t *n_kept, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------ grouped exact k-th smallest: one
+ * conformal offset per group -- per age of a roll-out, say -- from one call.  values (B, ld) f32 as for lg_select_kth; group (n)
+ * int32 shared by every batch row, 4-byte aligned: element i belongs to group group[i] when 0 <= group[i] < G and takes no part
+ * otherwise; cov_num, cov_den: R coverages as fractions, HOST arrays read by the call, 1 <= num < den <= 2^31 - 1.
+ * Written by the call: counts (G) int64, the members of each group (the same for every batch row); ranks (G, R) int64,
+ * ranks[g, r] = ceil((counts[g] + 1) cov_num[r] / cov_den[r]), computed on the device in 64-bit integers, no host round trip
+ * between the count and the selection; out (B, G, R) f32, out[b, g, r] = the ranks[g, r]-th smallest member of group g in row b,
+ * in lg_select_kth's order and with its special values (-0.0 counts and returns +0.0, NaNs above +inf returning the canonical
+ * quiet NaN); a rank above counts[g] -- an empty group included -- gives +inf, and ranks[g, r] is still written.
+ * Envelope: 1 <= B <= 4096, 1 <= G <= LG_SELECT_MAX_GROUPS, 1 <= R <= 8, B G R <= 65536 (1 KiB of bins per (row, group, rank)),
+ * 1 <= n < 2^31.  values, group, out, counts and ranks are DEVICE pointers; workspace: lg_select_grouped_workspace(B, G, R) bytes,
+ * 8-byte aligned, contents arbitrary (the call clears it).  The call queues its work on `stream` and waits for nothing; the same
+ * bits on every run.  0, or -1 with the reason (the field named) in lg_last_error. */
+#define LG_SELECT_MAX_GROUPS 1024
+int64_t lg_select_grouped_workspace(int32_t B, int32_t G, int32_t R);   /* host code; bytes, -1 outside the envelope */
+int32_t lg_select_group_tile(int32_t R);                                /* host code; groups one workgroup counts at a time */
+int lg_select_kth_grouped(const float *values, int64_t ld, int32_t B, int64_t n, const int32_t *group, int32_t G,
+                          const int64_t *cov_num, const int64_t *cov_den, int32_t R, float *out, int64_t *counts, int64_t *ranks,
+                          void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

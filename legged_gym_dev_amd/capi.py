@@ -322,6 +322,13 @@ def declare_select_api(lib):
     lib.lg_select_chunk.argtypes = []
     lib.lg_select_chunk.restype = i32
     lib.lg_select_kth.argtypes = [vp, i64, i32, i64, vp, vp, i32, vp, vp, vp, vp]
+    if not hasattr(lib, "lg_select_kth_grouped"):  # an A/B library built before the grouped selection
+        return
+    lib.lg_select_grouped_workspace.argtypes = [i32, i32, i32]
+    lib.lg_select_grouped_workspace.restype = i64
+    lib.lg_select_group_tile.argtypes = [i32]
+    lib.lg_select_group_tile.restype = i32
+    lib.lg_select_kth_grouped.argtypes = [vp, i64, i32, i64, vp, i32, C.POINTER(i64), C.POINTER(i64), i32, vp, vp, vp, vp, vp]
 
 
 def declare_env_api(lib, prefix="lg_"):

@@ -21,18 +21,6 @@
 // order in which workgroups arrive, and no float is ever added.
 #include "select_device.h"
 
-__device__ __forceinline__ uint32_t sel_key(float f) {
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u ^ 0x80000000u);
-}
-
-__device__ __forceinline__ float sel_value(uint32_t key) {
-    if (key == 0xffffffffu) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-}
-
 template <bool FIRST>
 __global__ __launch_bounds__(SEL_THREADS) void k_select_pass(SelectP P, int shift) {
     constexpr int NL = FIRST ? SEL_COPIES * 256 : SEL_MAX_R * 256;

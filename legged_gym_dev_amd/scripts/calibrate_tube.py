@@ -1,7 +1,8 @@
 """Calibrate a trained tube model: split conformal offsets on a held-out calibration set.
 
     python legged_gym_dev_amd/scripts/calibrate_tube.py --run tube_runs/run0 (--data rom_tracking_data/cal | --sim) \\
-        [--coverage 0.9,0.95 | --levels 0.5,0.8,0.9,0.95] [--checkpoint best|latest] [--horizon K] [--window_stride S] [--out DIR]
+        [--coverage 0.9,0.95 | --levels 0.5,0.8,0.9,0.95] [--checkpoint best|latest] [--horizon K] [--window_stride S] [--out DIR] \\
+        [--by_age [--max_age A] [--trajectory]]
 
 Every calibration row is scored with s = w - fw on the predictions evaluate_tube.py scores -- the one-step prediction and the
 closed-loop roll-out (same reseed mask, pooled over ages) for the flat datasets scalar and vector, per level for a
@@ -20,6 +21,20 @@ evaluate_tube.py refuses a --sim_seed or a --data folder equal to the calibratio
 The guarantee is the split conformal one: on calibration and test rows that are exchangeable, P(w <= fw + q) >= c.  Envs are
 exchangeable; the steps of one env are correlated, so the effective sample is smaller than n and the margin over c on fresh
 robots is not promised (section 10.6).
+
+--by_age (flat datasets scalar and vector) also writes calibration_age.json next to calibration.json, which
+is written exactly as without the flag: one roll-out offset per age of the fed-back state (steps since the last reseed; with
+--horizon K that is K ages) instead of one pooled over ages, every age's ceil((count + 1) c)-th smallest score from one grouped
+selection on the device (lg_select_kth_grouped).  --max_age A pools the ages >= A - 1 into the last group; the default is one
+group per age that occurs, at most 1024.  Prints one line per (coverage, age, column): rank, count, offset.  Level-conditioned
+runs, scalar_horizon (which already has one offset per step ahead) and error_dynamics are refused.
+
+--trajectory (with --by_age) fits the per-age offsets on the envs of even index only and, on the envs of odd index, a margin
+delta per coverage and column: the conformal_rank(E_margin, c)-th smallest, over those envs, of the env's largest score
+w - fw - q[age] over its kept steps.  What that buys, per output column: P(every kept step of a fresh env lies inside
+fw + q[age] + delta) >= c.  That is exact split conformal over envs, which are exchangeable (independent draws of the simulator's
+seed stream), unlike the steps of one env.  It is per column, not joint over the columns of a vector tube, and it covers the env's
+whole recorded length: for the statement over one planning horizon of K steps, simulate with --sim_T K.
 """
 import argparse
 import os
@@ -55,6 +70,9 @@ def parse_args(argv=None):
     ap.add_argument("--checkpoint", choices=["best", "latest"], default="best")
     ap.add_argument("--horizon", type=int, default=None, help="flat datasets: reseed the roll-out every K steps")
     ap.add_argument("--window_stride", type=int, default=1, help="scalar_horizon: distance between window starts")
+    ap.add_argument("--by_age", action="store_true", help="flat datasets: also write calibration_age.json, one roll-out offset per age")
+    ap.add_argument("--max_age", type=int, default=None, help="--by_age: number of age groups; ages >= A - 1 share the last (default: every age, at most 1024)")
+    ap.add_argument("--trajectory", action="store_true", help="--by_age: offsets from the even envs, a per-env margin from the odd envs")
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
     for name, kw in (("dataset", dict(choices=sorted(et.DATASETS))), ("N", dict(type=int)), ("dN", dict(type=int)),
@@ -91,6 +109,40 @@ def check_kind(cfg, a):
     return [float(c) for c in wanted]
 
 
+def check_by_age(cfg, a):
+    """--by_age, --max_age and --trajectory: flat kinds only."""
+    if not a.by_age:
+        if a.trajectory:
+            raise ValueError("--trajectory needs --by_age: the margin is fitted on top of the per-age offsets")
+        if a.max_age is not None:
+            raise ValueError("--max_age needs --by_age: it is the number of age groups")
+        return
+    kind = cfg["dataset"]
+    if kind in LEVEL_KINDS:
+        raise ValueError(f"--by_age: {kind} is level-conditioned; per-age and trajectory calibration of conditioned tubes is not built "
+                         f"(flat kinds only: {', '.join(cal.FLAT_KINDS)})")
+    if kind == "scalar_horizon":
+        raise ValueError("--by_age: scalar_horizon predicts all steps ahead in one shot and already has one offset per step ahead")
+    if kind not in cal.FLAT_KINDS:
+        raise ValueError(f"--by_age: {kind} predicts a signed error, not a bound, and is not calibrated")
+    if a.max_age is not None and not 1 <= a.max_age <= cal.MAX_GROUPS:
+        raise ValueError(f"--max_age must be 1..{cal.MAX_GROUPS}; got {a.max_age}")
+
+
+def calibrate_age(model, cfg, raw, a, wanted, dev):
+    """The AgeCalibration of --by_age [--trajectory] on the rows calibrate() scores."""
+    kind = cfg["dataset"]
+    win = {"N": cfg["N"], "dN": cfg["dN"]}
+    if kind == "scalar":
+        win["recursive"] = cfg["recursive"]
+    data, target, done = et.rows(kind, raw, win, dev)
+    layout = feedback_layout(kind, cfg["N"], cfg["dN"], cfg["recursive"], n=raw["z"].shape[-1], m=raw["v"].shape[-1])
+    reseed = ev.reseed_mask(done, a.horizon)
+    if a.trajectory:
+        return cal.calibrate_trajectory(model, data, target, done, layout, reseed, wanted, kind, a.max_age)
+    return cal.AgeCalibration(wanted, *cal.calibrate_by_age(model, data, target, done, layout, reseed, wanted, kind, a.max_age))
+
+
 def calibrate(model, cfg, raw, a, wanted, dev):
     kind = cfg["dataset"]
     if kind == "scalar_horizon":
@@ -112,6 +164,7 @@ def calibrate(model, cfg, raw, a, wanted, dev):
 def main(argv=None):
     a = parse_args(argv)
     cfg = et.resolve_config(a)
+    check_by_age(cfg, a)
     wanted = check_kind(cfg, a)
     dev = torch.device(a.device)
     out = a.out or a.run
@@ -123,6 +176,7 @@ def main(argv=None):
     try:
         raw = et.sim_records(sim, a.device) if a.sim else construct_dataset(a.data)
         c = calibrate(model, cfg, raw, a, wanted, dev)
+        by_age = calibrate_age(model, cfg, raw, a, wanted, dev) if a.by_age else None
         torch.cuda.synchronize(dev)
     finally:
         model.close()
@@ -131,6 +185,11 @@ def main(argv=None):
     c.save(os.path.join(out, cal.CALIBRATION_NAME))
     for line in c.lines():
         print(line)
+    if by_age is not None:
+        by_age.provenance = dict(c.provenance)
+        by_age.save(os.path.join(out, cal.AGE_CALIBRATION_NAME))
+        for line in by_age.lines():
+            print(line)
     return c
 
 

@@ -4,7 +4,8 @@ evaluate_error_dyn_simple.py on the HIP kernels, without
 wandb or hydra, on recorded data (--data) or on a fresh simulation (--sim).
 
     python legged_gym_dev_amd/scripts/evaluate_tube.py --run tube_runs/run0 (--data rom_tracking_data/run1 | --sim) \\
-        [--checkpoint best|latest] [--horizon K] [--window_stride S] [--plot] [--out DIR] [--calibration [PATH]]
+        [--checkpoint best|latest] [--horizon K] [--window_stride S] [--plot] [--out DIR] [--calibration [PATH]] \\
+        [--age_calibration [PATH]]
 
 The run's config.json (train_tube.py writes it) says how the model and its inputs are built; for a run without one, give
 --dataset, --activation and the other train_tube.py flags here (a flag given here replaces the file's value).
@@ -34,6 +35,13 @@ tube as well: beside every metrics dict eval.json gains a "calibrated" dict with
 predictions (prediction + offset), the offsets used and "covered", the count of scored elements with w - fw <= offset (the exact
 form of the comparison).  Evaluating on the calibration's own --sim_seed or --data folder is refused: coverage measured on the rows
 the offsets were fitted on says nothing.  Without the flag eval.json and the printed lines are what they were.
+
+--age_calibration [PATH] (flat datasets; default PATH: the run's calibration_age.json, which calibrate_tube.py --by_age writes) scores
+the roll-out with one offset per age of the fed-back state: eval.json gains "calibrated_by_age" with, per
+coverage, the roll-out metrics on prediction + offset[age], the exact count "covered" and its curve over ages, and "trajectory": the
+fraction of envs whose every kept step is covered (tube/evaluate.py trajectory_metrics), per column, for the raw roll-out, for the
+per-age tube and, when the calibration holds a trajectory margin, for the per-age + margin tube.  The calibration's own --sim_seed or
+--data folder is refused as for --calibration.  Without the flag eval.json and the printed lines are what they were.
 
 Deliberate deviations from the reference scripts:
   * evaluate_tube.py:53 feeds the full z[t] to a model that ScalarTubeDataset trained on z[:, 2:] (the input widths differ).  The
@@ -79,6 +87,8 @@ def parse_args(argv=None):
     ap.add_argument("--levels", default=None, help="level-conditioned runs: comma-separated coverage levels (default 0.5,0.8,0.9,0.95)")
     ap.add_argument("--calibration", nargs="?", const="", default=None, metavar="PATH",
                     help="also score the calibrated tube; PATH defaults to the run's calibration.json")
+    ap.add_argument("--age_calibration", nargs="?", const="", default=None, metavar="PATH",
+                    help="flat datasets: also score the per-age calibrated roll-out; PATH defaults to the run's calibration_age.json")
     ap.add_argument("--plot", action="store_true", help="save w / fw / fw_single PNGs per env to --out")
     ap.add_argument("--plot_envs", type=int, default=4)
     ap.add_argument("--out", default=None)
@@ -156,13 +166,61 @@ def load_calibration(a, cfg, sim):
     kind = "levels" if cfg["dataset"] in LEVEL_KINDS else "horizon" if cfg["dataset"] == "scalar_horizon" else "flat"
     if c.kind != kind or c.provenance.get("dataset", cfg["dataset"]) != cfg["dataset"]:
         raise ValueError(f"{path} calibrates a {c.provenance.get('dataset', c.kind)} model; the run is {cfg['dataset']}")
+    refuse_own_rows(c, path, a, sim)
+    return c
+
+
+def refuse_own_rows(c, path, a, sim):
+    """An evaluation on the robots or rows the calibration c (read from path) was fitted on is refused."""
     if sim is not None and c.provenance.get("source") == "sim" and c.provenance.get("sim_seed") == sim["sim_seed"]:
         raise ValueError(f"--sim_seed {sim['sim_seed']} is the seed {path} was calibrated on: coverage on the calibration's own robots "
                          "says nothing about fresh ones; give another --sim_seed")
     if a.data is not None and c.provenance.get("data") == os.path.abspath(a.data):
         raise ValueError(f"--data {a.data} is the folder {path} was calibrated on: coverage on the calibration's own rows says nothing "
                          "about fresh ones; give another folder")
+
+
+def load_age_calibration(a, cfg, sim):
+    """The AgeCalibration --age_calibration names, or None without the flag; load_calibration's refusals."""
+    if a.age_calibration is None:
+        return None
+    from legged_gym_dev_amd.tube.calibrate import FLAT_KINDS, AgeCalibration, default_age_path
+    if cfg["dataset"] not in FLAT_KINDS:
+        raise ValueError(f"--age_calibration: per-age offsets exist for the roll-out of the flat kinds ({', '.join(FLAT_KINDS)}); the run is {cfg['dataset']}")
+    path = a.age_calibration or default_age_path(a.run)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path} is missing: calibrate_tube.py --run {a.run} --by_age writes it")
+    c = AgeCalibration.load(path)
+    if c.provenance.get("dataset", cfg["dataset"]) != cfg["dataset"]:
+        raise ValueError(f"{path} calibrates a {c.provenance['dataset']} model; the run is {cfg['dataset']}")
+    refuse_own_rows(c, path, a, sim)
     return c
+
+
+def calibrated_by_age(c, fw, target, done, reseed):
+    """eval.json's "calibrated_by_age": per coverage the roll-out metrics on the per-age tube, and the trajectory rates of the raw
+    roll-out, the per-age tube and (with a stored margin) the per-age + margin tube."""
+    age = ev.steps_since(reseed)
+    keep = ~done.bool()[:, :, None]
+    n_age = int(age[keep[:, :, 0]].max()) + 1 if bool(keep.any()) else 1
+    res = {"max_age": c.max_age, "coverages": c.coverages, "counts": c.counts, "ranks": c.ranks, "rollout": [],
+           "trajectory": {"raw": ev.trajectory_metrics(fw >= target, done), "by_age": []}}
+    if c.margin is not None:
+        res.update({"margin": c.margin.tolist(), "margin_n": c.margin_n, "margin_ranks": c.margin_ranks})
+        res["trajectory"]["by_age_margin"] = []
+    for cv in c.coverages:
+        cov = c.covers(fw, target, age, cv)
+        m = ev.tube_metrics(c.apply(fw, age, cv), target, done, reseed)
+        m["offset_by_age"] = c.offsets[c.index(cv)].tolist()
+        m["covered"] = int((cov & keep).sum())
+        by_age = torch.zeros(n_age, dtype=torch.int64, device=fw.device).index_add_(0, age.reshape(-1).clamp(max=n_age - 1),
+                                                                                   (cov & keep).sum(dim=2).reshape(-1))
+        m["covered_by_age"] = by_age.tolist()
+        res["rollout"].append(m)
+        res["trajectory"]["by_age"].append(ev.trajectory_metrics(cov, done))
+        if c.margin is not None:
+            res["trajectory"]["by_age_margin"].append(ev.trajectory_metrics(c.covers(fw, target, age, cv, trajectory=True), done))
+    return _cal_safe(res)
 
 
 def _cal_safe(o):
@@ -182,7 +240,7 @@ def calibrated_tube(c, fw, target, done, reseed, coverage, part, level=None):
     return _cal_safe(m)
 
 
-def evaluate_flat(model, cfg, raw, horizon, dev, calib=None):
+def evaluate_flat(model, cfg, raw, horizon, dev, calib=None, age_calib=None):
     kind = cfg["dataset"]
     win = {"N": cfg["N"], "dN": cfg["dN"]}
     if kind == "scalar":
@@ -200,6 +258,8 @@ def evaluate_flat(model, cfg, raw, horizon, dev, calib=None):
         res["calibrated"] = {"n": calib.n, "coverages": calib.coverages, "ranks": calib.ranks,
                              "one_step": [calibrated_tube(calib, fw_single, target, done, None, cv, "one_step") for cv in calib.coverages],
                              "rollout": [calibrated_tube(calib, fw, target, done, reseed, cv, "rollout") for cv in calib.coverages]}
+    if age_calib is not None:
+        res["calibrated_by_age"] = calibrated_by_age(age_calib, fw, target, done, reseed)
     return res, {"w": target, "fw": fw, "fw_single": fw_single, "done": done}
 
 
@@ -302,6 +362,9 @@ def main(argv=None):
     sim = sim_flags(a, cfg) if a.sim else None
     calib = load_calibration(a, cfg, sim)
     extra = {} if calib is None else {"calib": calib}
+    age_calib = load_age_calibration(a, cfg, sim)
+    if age_calib is not None:
+        extra["age_calib"] = age_calib
     model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, activation=cfg["activation"], softplus_beta=cfg["softplus_beta"],
                               horizon=horizon, device=a.device, level_input=cfg["dataset"] in LEVEL_KINDS)
     raw = sim_records(sim, a.device) if a.sim else construct_dataset(a.data)
@@ -320,6 +383,8 @@ def main(argv=None):
         model.close()
     if calib is not None:
         res["calibration"] = os.path.abspath(a.calibration or os.path.join(a.run, "calibration.json"))
+    if age_calib is not None:
+        res["age_calibration"] = os.path.abspath(a.age_calibration or os.path.join(a.run, "calibration_age.json"))
     res.update({"run": os.path.abspath(a.run), **({"source": "sim", **sim} if a.sim else {"data": os.path.abspath(a.data)}),
                 "checkpoint": a.checkpoint, "dataset": cfg["dataset"]})
     if a.plot:
@@ -346,6 +411,13 @@ def main(argv=None):
             for part in ("one_step", "rollout", "one_shot"):
                 for cv, m in zip(calib.coverages, res["calibrated"].get(part, [])):
                     print(f"calibrated coverage {cv} {part}: Success Rate: {m['success_rate']}")
+    if age_calib is not None:
+        ba = res["calibrated_by_age"]
+        print(f"Trajectory Success Rate: {ba['trajectory']['raw']['trajectory_success_rate']}")
+        for i, cv in enumerate(age_calib.coverages):
+            print(f"calibrated by age, coverage {cv} rollout: Success Rate: {ba['rollout'][i]['success_rate']}  Trajectory Success Rate: "
+                  f"{ba['trajectory']['by_age'][i]['trajectory_success_rate']}" + (
+                      f"  with the margin: {ba['trajectory']['by_age_margin'][i]['trajectory_success_rate']}" if age_calib.margin is not None else ""))
     return res
 
 

@@ -10,6 +10,12 @@ output column, per level and per step ahead.
     Calibration                               offsets, ranks, provenance; save / load (calibration.json); apply / covers
     calibrate_flat / calibrate_levels / calibrate_horizon      the three score layouts
 
+Per age and per trajectory, for the closed-loop roll-out of the flat kinds:
+
+    select_kth_grouped(values, group, G, coverages)      the conformal order statistic of every group, ranks computed on the device
+    calibrate_by_age / calibrate_trajectory              one offset per age of the fed-back state; a margin from a score per env
+    AgeCalibration                                       per-age offsets and the margin; save / load (calibration_age.json)
+
 There is no CPU fallback for the selection: without the library or a GPU it raises.
 """
 import ctypes as C
@@ -21,6 +27,8 @@ from fractions import Fraction
 import torch
 
 CALIBRATION_NAME = "calibration.json"
+AGE_CALIBRATION_NAME = "calibration_age.json"
+MAX_GROUPS = 1024                                       # LG_SELECT_MAX_GROUPS
 FLAT_KINDS = ("scalar", "vector")
 PARTS = ("one_step", "rollout")
 
@@ -64,6 +72,59 @@ def select_kth(values, ranks, keep=None):
     if rc != 0:
         raise (ValueError if rc == -1 else LeggedHipError)(f"lg_select_kth failed ({rc}): {lib.lg_last_error().decode()}")
     return out, n_kept
+
+
+def coverage_fractions(coverages):
+    """[(num, den)] of the decimals the caller wrote, Fraction(str(c)) as in conformal_rank: what lg_select_kth_grouped takes."""
+    out = []
+    for c in coverages:
+        f = Fraction(str(c).strip())
+        if not 0 < f < 1:
+            raise ValueError(f"coverage must lie inside (0, 1); got {c}")
+        if f.denominator > 2 ** 31 - 1:
+            raise ValueError(f"coverage {c} has the denominator {f.denominator}, above 2^31 - 1: write it with fewer digits")
+        out.append((f.numerator, f.denominator))
+    return out
+
+
+def select_kth_grouped(values, group, G, coverages):
+    """values (B, n) float32 on the device, handled as in select_kth; group (n) integers shared by the rows, element i belongs to
+    group[i] when 0 <= group[i] < G and takes no part otherwise; coverages: decimals inside (0, 1).  Returns (out (B, G, R) float32,
+    counts (G) int64, ranks (G, R) int64), all on the device: out[b, g, r] is the ceil((counts[g] + 1) c_r)-th smallest member of
+    group g in row b, +inf where the group has fewer members (lg_select_kth_grouped, include/legged_hip.h).  Queues on the current
+    stream, waits for nothing."""
+    from ..lib import LeggedHipError, load
+    lib = load()
+    if not (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float32 and values.dim() == 2):
+        raise LeggedHipError(f"select_kth_grouped needs a (B, n) float32 tensor on a GPU device (no CPU fallback); got "
+                             f"{type(values).__name__} {tuple(getattr(values, 'shape', ()))} on {getattr(values, 'device', None)}")
+    B, n = values.shape
+    if n >= 1 and not (values.stride(1) == 1 and (B == 1 or values.stride(0) >= n)):
+        values = values.contiguous()
+    ld = n if B == 1 else values.stride(0)
+    dev = values.device
+    fr = coverage_fractions(coverages)
+    R, G = len(fr), int(G)
+    group = torch.as_tensor(group).to(dev).reshape(-1)
+    if group.dtype != torch.int32 or group.stride(0) != 1:
+        group = group.to(torch.int32).contiguous()
+    if group.numel() != n:
+        raise ValueError(f"group must have n = {n} elements; got {group.numel()}")
+    nbytes = lib.lg_select_grouped_workspace(B, G, R)
+    if nbytes < 0:
+        raise ValueError(lib.lg_last_error().decode())
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    out = torch.empty((B, G, R), dtype=torch.float32, device=dev)
+    counts = torch.empty(G, dtype=torch.int64, device=dev)
+    ranks = torch.empty((G, R), dtype=torch.int64, device=dev)
+    num, den = (C.c_int64 * R)(*[f[0] for f in fr]), (C.c_int64 * R)(*[f[1] for f in fr])
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        rc = lib.lg_select_kth_grouped(p(values), ld, B, n, p(group), G, num, den, R, p(out), p(counts), p(ranks), p(ws),
+                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise (ValueError if rc == -1 else LeggedHipError)(f"lg_select_kth_grouped failed ({rc}): {lib.lg_last_error().decode()}")
+    return out, counts, ranks
 
 
 def conformal_rank(n, coverage):
@@ -225,3 +286,173 @@ def calibrate_horizon(fw, target, coverages):
 
 def default_path(run):
     return os.path.join(run, CALIBRATION_NAME)
+
+
+class AgeCalibration:
+    """Roll-out offsets per age of the fed-back state (steps since the last reseed), and optionally a trajectory margin.
+
+    offsets (n_coverages, max_age, out): offsets[c, a] is the conformal offset of the steps of age a; ages >= max_age - 1 share
+    the last group.  counts (max_age): calibration steps per group; ranks (max_age, n_coverages).  margin (n_coverages, out), with
+    margin_n envs and margin_ranks (n_coverages): delta of calibrate_trajectory, or None.  provenance as for Calibration."""
+
+    def __init__(self, coverages, offsets, counts, ranks, margin=None, margin_n=None, margin_ranks=None, provenance=None):
+        self.coverages = [float(c) for c in coverages]
+        self.offsets = torch.as_tensor(offsets, dtype=torch.float32).cpu()
+        self.counts = [int(v) for v in torch.as_tensor(counts).reshape(-1).tolist()]
+        self.ranks = [[int(v) for v in row] for row in torch.as_tensor(ranks).tolist()]
+        self.provenance = dict(provenance or {})
+        C_ = len(self.coverages)
+        if self.offsets.dim() != 3 or self.offsets.shape[0] != C_ or self.offsets.shape[1] != len(self.counts) \
+                or len(self.ranks) != len(self.counts) or any(len(r) != C_ for r in self.ranks):
+            raise ValueError(f"offsets {tuple(self.offsets.shape)} do not fit {C_} coverages and {len(self.counts)} ages")
+        self.max_age = self.offsets.shape[1]
+        self.margin = None if margin is None else torch.as_tensor(margin, dtype=torch.float32).cpu()
+        self.margin_n = None if margin is None else int(margin_n)
+        self.margin_ranks = None if margin is None else [int(r) for r in margin_ranks]
+        if self.margin is not None and (tuple(self.margin.shape) != (C_, self.offsets.shape[2]) or len(self.margin_ranks) != C_):
+            raise ValueError(f"margin {tuple(self.margin.shape)} does not fit offsets {tuple(self.offsets.shape)}")
+        if bool(torch.isnan(self.offsets).any()):
+            c, a, o = torch.isnan(self.offsets).nonzero()[0].tolist()
+            raise ValueError(f"NaN offset at coverage {self.coverages[c]}, age {a}, column {o}: a NaN score reached the rank")
+        if self.margin is not None and bool(torch.isnan(self.margin).any()):
+            c, o = torch.isnan(self.margin).nonzero()[0].tolist()
+            raise ValueError(f"NaN margin at coverage {self.coverages[c]}, column {o}: a NaN score reached the rank")
+
+    def index(self, coverage):
+        for i, c in enumerate(self.coverages):
+            if abs(c - float(coverage)) <= 1e-9:
+                return i
+        raise KeyError(f"coverage {coverage} was not calibrated; have {self.coverages}")
+
+    def _gather(self, age, coverage, dev):
+        age = torch.as_tensor(age).long().clamp(0, self.max_age - 1)
+        return self.offsets[self.index(coverage)].to(dev)[age.to(dev)]
+
+    def _margin(self, coverage, dev):
+        if self.margin is None:
+            raise ValueError("this calibration holds no trajectory margin: calibrate_tube.py --by_age --trajectory writes one")
+        return self.margin[self.index(coverage)].to(dev)
+
+    def offset_at(self, age, coverage, trajectory=False):
+        """(..., out) for ages (...): the offset of each age, clamped to max_age - 1; with trajectory the margin added."""
+        dev = age.device if torch.is_tensor(age) else "cpu"
+        q = self._gather(age, coverage, dev)
+        return q + self._margin(coverage, dev) if trajectory else q
+
+    def apply(self, fw, age, coverage, trajectory=False):
+        """fw + offset_at(age): fw (..., out), age (...)."""
+        return fw + self.offset_at(torch.as_tensor(age).to(fw.device), coverage, trajectory)
+
+    def covers(self, fw, w, age, coverage, trajectory=False):
+        """(w - fw) <= offset, the exact form of apply(fw) >= w.  With trajectory: ((w - fw) - offset) <= margin, the arithmetic of
+        the score the margin was selected from, so that the count on the margin envs is exact."""
+        q = self._gather(age, coverage, fw.device)
+        if trajectory:
+            return ((w - fw) - q) <= self._margin(coverage, fw.device)
+        return (w - fw) <= q
+
+    def to_json(self):
+        return {"kind": "age", "coverages": self.coverages, "max_age": self.max_age, "counts": self.counts, "ranks": self.ranks,
+                "offsets": _enc(self.offsets.tolist()), "margin": None if self.margin is None else _enc(self.margin.tolist()),
+                "margin_n": self.margin_n, "margin_ranks": self.margin_ranks, **self.provenance}
+
+    def save(self, path):
+        with open(path, "w") as f:
+            json.dump(self.to_json(), f, indent=1, allow_nan=False)
+
+    @classmethod
+    def load(cls, path):
+        with open(path) as f:
+            d = json.load(f)
+        if d.get("kind") != "age":
+            raise ValueError(f"{path} holds a {d.get('kind')!r} calibration, not a per-age one ({AGE_CALIBRATION_NAME})")
+        core = ("kind", "coverages", "max_age", "counts", "ranks", "offsets", "margin", "margin_n", "margin_ranks")
+        return cls(d["coverages"], _dec(d["offsets"]), d["counts"], d["ranks"], None if d["margin"] is None else _dec(d["margin"]),
+                   d["margin_n"], d["margin_ranks"], {k: v for k, v in d.items() if k not in core})
+
+    def lines(self):
+        """One printed line per (coverage, age, column): rank, count, offset; then the margin lines."""
+        out = []
+        for c, cv in enumerate(self.coverages):
+            for a in range(self.max_age):
+                for o in range(self.offsets.shape[2]):
+                    out.append(f"rollout, coverage {cv}, age {a}{'+' if a == self.max_age - 1 else ''}, column {o}: rank {self.ranks[a][c]} of "
+                               f"count {self.counts[a]}, offset {float(self.offsets[c, a, o])}")
+        if self.margin is not None:
+            for c, cv in enumerate(self.coverages):
+                for o in range(self.margin.shape[1]):
+                    out.append(f"trajectory margin, coverage {cv}, column {o}: rank {self.margin_ranks[c]} of {self.margin_n} envs, "
+                               f"margin {float(self.margin[c, o])}")
+        return out
+
+
+def age_groups(done, reseed, max_age=None):
+    """(group (E, T) int32, G): group = min(steps since the last reseed, G - 1) where the step is kept (~done), else -1.  G = max_age
+    if given, otherwise min(oldest kept age + 1, MAX_GROUPS); ages past the last group share it."""
+    from .evaluate import steps_since
+    keep = ~done.bool()
+    age = steps_since(reseed.to(keep.device))
+    if max_age is None:
+        G = min(int(age[keep].max()) + 1, MAX_GROUPS) if bool(keep.any()) else 1
+    else:
+        G = int(max_age)
+        if not 1 <= G <= MAX_GROUPS:
+            raise ValueError(f"max_age must be 1..{MAX_GROUPS}; got {max_age}")
+    return torch.where(keep, age.clamp(max=G - 1), torch.full_like(age, -1)).to(torch.int32), G
+
+
+def _take_envs(envs, *tensors):
+    if envs is None:
+        return tensors
+    envs = torch.as_tensor(envs).long()
+    return tuple(t[envs.to(t.device)] for t in tensors)
+
+
+def calibrate_by_age(model, data, target, done, layout, reseed, coverages, kind="scalar", max_age=None, envs=None):
+    """Flat kinds: the roll-out scores target - rollout_window(...) of calibrate_flat, one conformal offset per age of the fed-back
+    state instead of one for all -- one lg_select_kth_grouped call, the batch rows the output columns, the groups the ages
+    (age_groups).  envs: an index tensor, the envs to calibrate on (default all).
+    Returns (offsets (n_coverages, G, out), counts (G), ranks (G, n_coverages)), on the device."""
+    if kind not in FLAT_KINDS:
+        raise ValueError(f"{kind}: per-age offsets are for the roll-out of the flat kinds ({', '.join(FLAT_KINDS)})")
+    data, target, done, reseed = _take_envs(envs, data, target, done, reseed)
+    E, T, _ = data.shape
+    O = target.shape[2]
+    fw = model.rollout_window(data, *layout, reseed)
+    group, G = age_groups(done, reseed, max_age)
+    scores = (target - fw).reshape(E * T, O).t()
+    q, counts, ranks = select_kth_grouped(scores, group.reshape(-1), G, coverages)          # (out, G, n_coverages)
+    return q.permute(2, 1, 0).contiguous(), counts, ranks
+
+
+def calibrate_trajectory(model, data, target, done, layout, reseed, coverages, kind="scalar", max_age=None, envs=None, split=None):
+    """calibrate_by_age on one half of the envs, and on the other half a margin from one score per env, so that
+    P(every kept step of a fresh env is covered) >= c per output column: exact split conformal over envs, which are exchangeable
+    (DESIGN.md section 10.7).  split: (shape envs, margin envs) index tensors; default the even and the odd entries of envs (of
+    all envs).  The score of margin env e is s[c, o, e] = max over its kept steps t of (target - fw - q[c, group(e, t), o]), an
+    infinite q contributing -inf; delta[c, o] is the conformal_rank(E_margin, c)-th smallest of s[c, o, :] (select_kth).
+    Returns an AgeCalibration with offsets q and margin delta."""
+    if split is None:
+        idx = torch.arange(data.shape[0]) if envs is None else torch.as_tensor(envs).long().cpu()
+        split = (idx[0::2], idx[1::2])
+    shape_envs, margin_envs = split
+    if len(margin_envs) < 1 or len(shape_envs) < 1:
+        raise ValueError("a trajectory margin needs at least two envs: one for the offsets and one for the margin")
+    q, counts, ranks = calibrate_by_age(model, data, target, done, layout, reseed, coverages, kind, max_age, shape_envs)
+    data, target, done, reseed = _take_envs(margin_envs, data, target, done, reseed)
+    Em, T, _ = data.shape
+    O, G, nc = target.shape[2], q.shape[1], q.shape[0]
+    fw = model.rollout_window(data, *layout, reseed)
+    group, _ = age_groups(done, reseed, G)
+    keep = group.ge(0)
+    qs = q[:, group.clamp(min=0).long()]                                                   # (n_coverages, E_margin, T, out)
+    s = (target - fw)[None] - qs
+    s = torch.where(keep[None, :, :, None], s, torch.full_like(s, -math.inf)).amax(dim=2)   # (n_coverages, E_margin, out)
+    m_ranks = _ranks(Em, coverages)
+    per_row = torch.tensor(m_ranks).repeat_interleave(O)[:, None]                           # row (coverage, column)
+    delta, _ = select_kth(s.permute(0, 2, 1).reshape(nc * O, Em), per_row)
+    return AgeCalibration(coverages, q, counts, ranks, delta.reshape(nc, O), Em, m_ranks)
+
+
+def default_age_path(run):
+    return os.path.join(run, AGE_CALIBRATION_NAME)

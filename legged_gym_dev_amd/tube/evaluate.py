@@ -80,3 +80,12 @@ def window_metrics(pred, target):
     return {"windows": int(pred.shape[0]), "success_rate": float(cover.mean()),
             "mean_excess": float((diff * cover).sum() / cover.sum()),
             "success_rate_by_step": cover.mean(dim=0).tolist()}
+
+
+def trajectory_metrics(covered, done):
+    """covered (E, T, out) bool, done (E, T): the fraction of envs whose every kept step is covered, per output column --
+    the quantity a trajectory margin (tube/calibrate.py calibrate_trajectory) bounds.  An env without a kept step counts as covered."""
+    if covered.dim() != 3 or done.shape != covered.shape[:2]:
+        raise ValueError(f"shapes: covered {tuple(covered.shape)}, done {tuple(done.shape)}")
+    whole = (covered.bool() | done.bool()[:, :, None]).all(dim=1)                            # (E, out)
+    return {"envs": int(covered.shape[0]), "trajectory_success_rate": whole.double().mean(dim=0).tolist()}

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Timing of the grouped k-th selection (csrc/select_grouped_kernels.hip, tube/calibrate.py select_kth_grouped; DESIGN.md section
+10.7) on resident data against the two routes that existed before it:
+
+    masked    G calls of select_kth, each with the keep mask of one group and a host read of the group's count in front (the rank
+              ceil((count + 1) c) needs it): what a per-age calibration cost without the grouped entry
+    sort      per group, torch.sort of the group's members (an index gather, a sort along the row, a gather of the ranks)
+
+Shapes (B, n, G), R coverages, group = element index mod G (the age of a step reseeded every G steps):
+    (2, 12 800, 50)       R = 2   a test-sized set
+    (2, 409 600, 50)      R = 2   8192 envs x 50 steps, two output columns
+    (4, 4 096 000, 1000)  R = 2   many groups: 63 tiles
+
+Values are |N(0, 1)|, like tube scores.  Median of 3 after a warm-up run, every timing closed by a device synchronise.  "bytes" is
+what one grouped call reads: 4 passes x tiles x B x n x (4 bytes of value + 4 bytes of group id); "of HBM" is that over the time as
+a fraction of the 6.29 TB/s a float4 copy reaches on this part.  A set that fits the last-level cache can exceed what HBM alone would
+give: the column is a rate, not a claim about where the bytes came from.
+
+    python tools/bench_select_grouped.py        # prints, and writes profiles/select_grouped_bench.txt
+"""
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+from legged_gym_dev_amd.lib import load  # noqa: E402
+from legged_gym_dev_amd.tube.calibrate import conformal_rank, select_kth, select_kth_grouped  # noqa: E402
+
+HBM_RATE = 6.29e12
+SHAPES = [(2, 12800, 50), (2, 409600, 50), (4, 4096000, 1000)]
+COVERAGES = ("0.9", "0.95")
+
+
+def timed(fn, reps=3):
+    fn()                                               # warm-up
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append(time.perf_counter() - t0)
+    return statistics.median(out), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "select_grouped_bench.txt"))
+    a = ap.parse_args()
+    dev = "cuda:0"
+    lib = load()
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+    R = len(COVERAGES)
+    gt = lib.lg_select_group_tile(R)
+    say(f"grouped k-th selection, {torch.cuda.get_device_name(0)}; R = {R} coverages {COVERAGES}, tile {gt} groups; median of 3 after a warm-up "
+        "run, each timing closed by a device synchronise")
+    say(f"{'shape (B, n, G)':>22s} {'tiles':>5s} {'grouped ms':>10s} {'masked ms':>10s} {'ratio':>7s} {'sort ms':>9s} {'ratio':>7s} {'bytes':>9s} "
+        f"{'rate':>10s} {'of HBM':>7s}   runs (grouped ms)")
+    ms = lambda r: " ".join(f"{x * 1e3:.3f}" for x in r)
+    for B, n, G in SHAPES:
+        g = torch.Generator(device=dev).manual_seed(B + n)
+        v = torch.randn(B, n, device=dev, generator=g).abs_()
+        group = (torch.arange(n, device=dev) % G).to(torch.int32)
+
+        def grouped():
+            return select_kth_grouped(v, group, G, COVERAGES)[0]
+
+        def masked():
+            out = torch.empty(B, G, R, device=dev)
+            for a_ in range(G):
+                keep = group == a_
+                count = int(keep.sum())                # the host round trip the rank needs
+                ranks = torch.tensor([conformal_rank(count, c) for c in COVERAGES])
+                out[:, a_] = select_kth(v, ranks, keep)[0]
+            return out
+
+        def srt():
+            out = torch.empty(B, G, R, device=dev)
+            for a_ in range(G):
+                idx = (group == a_).nonzero()[:, 0]
+                ranks = torch.tensor([conformal_rank(idx.numel(), c) for c in COVERAGES], device=dev)      # all within the count here
+                out[:, a_] = torch.sort(v[:, idx], dim=1).values[:, ranks - 1]
+            return out
+
+        want = grouped()
+        assert bool(torch.isfinite(want).all()) and torch.equal(masked(), want) and torch.equal(srt(), want)
+        del want
+        tg, rg = timed(grouped)
+        tm, _ = timed(masked)
+        ts, _ = timed(srt)
+        tiles = -(-G // gt)
+        nbytes = 4 * tiles * B * n * 8
+        say(f"{f'({B}, {n}, {G})':>22s} {tiles:5d} {tg * 1e3:10.3f} {tm * 1e3:10.3f} {tm / tg:7.2f} {ts * 1e3:9.3f} {ts / tg:7.2f} {nbytes / 1e6:6.0f} MB "
+            f"{nbytes / tg / 1e12:5.2f} TB/s {nbytes / tg / HBM_RATE:7.2f}   [{ms(rg)}]")
+        del v, group
+        torch.cuda.empty_cache()
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "k_select"], capture_output=True, text=True).stdout
+    say("\n" + res)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
