@@ -33,20 +33,42 @@ FLAT_KINDS = ("scalar", "vector")
 PARTS = ("one_step", "rollout")
 
 
-def select_kth(values, ranks, keep=None):
-    """values (B, n) float32 on the device, rows n apart or further (a row stride becomes ld; anything else is copied); ranks (B, R)
-    or (R,) for every row, 1-based; keep None or (n) bool / uint8 shared by the rows.  Returns (out (B, R) float32, n_kept a device
-    int64 tensor of one element): lg_select_kth's semantics (include/legged_hip.h).  Queues on the current stream, waits for nothing."""
-    from ..lib import LeggedHipError, load
-    lib = load()
+def _device_rows(values, who):
+    """(values, B, n, ld, dev) of a (B, n) float32 device tensor for lg_select_*: a row stride becomes ld, anything else is copied."""
+    from ..lib import LeggedHipError
     if not (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float32 and values.dim() == 2):
-        raise LeggedHipError(f"select_kth needs a (B, n) float32 tensor on a GPU device (no CPU fallback); got {type(values).__name__} "
+        raise LeggedHipError(f"{who} needs a (B, n) float32 tensor on a GPU device (no CPU fallback); got {type(values).__name__} "
                              f"{tuple(getattr(values, 'shape', ()))} on {getattr(values, 'device', None)}")
     B, n = values.shape
     if n >= 1 and not (values.stride(1) == 1 and (B == 1 or values.stride(0) >= n)):
         values = values.contiguous()
-    ld = n if B == 1 else values.stride(0)
-    dev = values.device
+    return values, B, n, (n if B == 1 else values.stride(0)), values.device
+
+
+def _workspace(lib, nbytes, dev):
+    """The workspace a size query asked for; a refused query (-1) raises with the library's reason."""
+    if nbytes < 0:
+        raise ValueError(lib.lg_last_error().decode())
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+
+
+def _call(lib, entry, dev, *args):
+    """lib.<entry>(*args, dev's current stream), tensors as their pointers; -1 raises ValueError, another failure LeggedHipError."""
+    from ..lib import LeggedHipError
+    args = [C.c_void_p(a.data_ptr()) if torch.is_tensor(a) else a for a in args]
+    with torch.cuda.device(dev):
+        rc = getattr(lib, entry)(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise (ValueError if rc == -1 else LeggedHipError)(f"{entry} failed ({rc}): {lib.lg_last_error().decode()}")
+
+
+def select_kth(values, ranks, keep=None):
+    """values (B, n) float32 on the device, rows n apart or further (a row stride becomes ld; anything else is copied); ranks (B, R)
+    or (R,) for every row, 1-based; keep None or (n) bool / uint8 shared by the rows.  Returns (out (B, R) float32, n_kept a device
+    int64 tensor of one element): lg_select_kth's semantics (include/legged_hip.h).  Queues on the current stream, waits for nothing."""
+    from ..lib import load
+    lib = load()
+    values, B, n, ld, dev = _device_rows(values, "select_kth")
     ranks = torch.as_tensor(ranks, dtype=torch.int64)
     if ranks.dim() == 1:
         ranks = ranks[None, :].expand(B, -1)
@@ -59,18 +81,10 @@ def select_kth(values, ranks, keep=None):
         keep = (keep.view(torch.uint8) if keep.dtype == torch.bool else keep.ne(0).to(torch.uint8)).contiguous()
         if keep.numel() != n:
             raise ValueError(f"keep must have n = {n} elements; got {keep.numel()}")
-    nbytes = lib.lg_select_workspace(B, R)
-    if nbytes < 0:
-        raise ValueError(lib.lg_last_error().decode())
-    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    ws = _workspace(lib, lib.lg_select_workspace(B, R), dev)
     out = torch.empty((B, R), dtype=torch.float32, device=dev)
     n_kept = torch.empty(1, dtype=torch.int64, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = lib.lg_select_kth(p(values), ld, B, n, p(keep) if keep is not None else None, p(ranks), R, p(out), p(n_kept), p(ws),
-                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise (ValueError if rc == -1 else LeggedHipError)(f"lg_select_kth failed ({rc}): {lib.lg_last_error().decode()}")
+    _call(lib, "lg_select_kth", dev, values, ld, B, n, keep, ranks, R, out, n_kept, ws)
     return out, n_kept
 
 
@@ -93,16 +107,9 @@ def select_kth_grouped(values, group, G, coverages):
     counts (G) int64, ranks (G, R) int64), all on the device: out[b, g, r] is the ceil((counts[g] + 1) c_r)-th smallest member of
     group g in row b, +inf where the group has fewer members (lg_select_kth_grouped, include/legged_hip.h).  Queues on the current
     stream, waits for nothing."""
-    from ..lib import LeggedHipError, load
+    from ..lib import load
     lib = load()
-    if not (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float32 and values.dim() == 2):
-        raise LeggedHipError(f"select_kth_grouped needs a (B, n) float32 tensor on a GPU device (no CPU fallback); got "
-                             f"{type(values).__name__} {tuple(getattr(values, 'shape', ()))} on {getattr(values, 'device', None)}")
-    B, n = values.shape
-    if n >= 1 and not (values.stride(1) == 1 and (B == 1 or values.stride(0) >= n)):
-        values = values.contiguous()
-    ld = n if B == 1 else values.stride(0)
-    dev = values.device
+    values, B, n, ld, dev = _device_rows(values, "select_kth_grouped")
     fr = coverage_fractions(coverages)
     R, G = len(fr), int(G)
     group = torch.as_tensor(group).to(dev).reshape(-1)
@@ -110,20 +117,12 @@ def select_kth_grouped(values, group, G, coverages):
         group = group.to(torch.int32).contiguous()
     if group.numel() != n:
         raise ValueError(f"group must have n = {n} elements; got {group.numel()}")
-    nbytes = lib.lg_select_grouped_workspace(B, G, R)
-    if nbytes < 0:
-        raise ValueError(lib.lg_last_error().decode())
-    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    ws = _workspace(lib, lib.lg_select_grouped_workspace(B, G, R), dev)
     out = torch.empty((B, G, R), dtype=torch.float32, device=dev)
     counts = torch.empty(G, dtype=torch.int64, device=dev)
     ranks = torch.empty((G, R), dtype=torch.int64, device=dev)
     num, den = (C.c_int64 * R)(*[f[0] for f in fr]), (C.c_int64 * R)(*[f[1] for f in fr])
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = lib.lg_select_kth_grouped(p(values), ld, B, n, p(group), G, num, den, R, p(out), p(counts), p(ranks), p(ws),
-                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise (ValueError if rc == -1 else LeggedHipError)(f"lg_select_kth_grouped failed ({rc}): {lib.lg_last_error().decode()}")
+    _call(lib, "lg_select_kth_grouped", dev, values, ld, B, n, group, G, num, den, R, out, counts, ranks, ws)
     return out, counts, ranks
 
 
@@ -150,6 +149,13 @@ def _dec(o):
     if isinstance(o, list):
         return [_dec(v) for v in o]
     return float(o) if isinstance(o, str) else o
+
+
+def _coverage_index(coverages, coverage):
+    for i, c in enumerate(coverages):
+        if abs(c - float(coverage)) <= 1e-9:
+            return i
+    raise KeyError(f"coverage {coverage} was not calibrated; have {coverages}")
 
 
 class Calibration:
@@ -189,10 +195,7 @@ class Calibration:
                 raise ValueError(f"level {level} is calibrated to coverage {level}, not {coverage}: a level-conditioned model's level is its coverage")
         elif level is not None:
             raise ValueError(f"a {self.kind} calibration has no levels")
-        for i, c in enumerate(self.coverages):
-            if abs(c - float(coverage)) <= 1e-9:
-                return i
-        raise KeyError(f"coverage {coverage} was not calibrated; have {self.coverages}")
+        return _coverage_index(self.coverages, coverage)
 
     def offset(self, coverage, level=None, part="one_step"):
         """The offsets of one set: (out) for flat and levels, (H_fwd) for horizon."""
@@ -217,7 +220,7 @@ class Calibration:
 
     def save(self, path):
         with open(path, "w") as f:
-            json.dump(self.to_json(), f, indent=1, allow_nan=False)
+            json.dump(self.to_json(), f, indent=1, allow_nan=False)       # strict JSON: to_json's _enc has named the infinities
 
     @classmethod
     def load(cls, path):
@@ -319,10 +322,7 @@ class AgeCalibration:
             raise ValueError(f"NaN margin at coverage {self.coverages[c]}, column {o}: a NaN score reached the rank")
 
     def index(self, coverage):
-        for i, c in enumerate(self.coverages):
-            if abs(c - float(coverage)) <= 1e-9:
-                return i
-        raise KeyError(f"coverage {coverage} was not calibrated; have {self.coverages}")
+        return _coverage_index(self.coverages, coverage)
 
     def _gather(self, age, coverage, dev):
         age = torch.as_tensor(age).long().clamp(0, self.max_age - 1)
@@ -356,9 +356,7 @@ class AgeCalibration:
                 "offsets": _enc(self.offsets.tolist()), "margin": None if self.margin is None else _enc(self.margin.tolist()),
                 "margin_n": self.margin_n, "margin_ranks": self.margin_ranks, **self.provenance}
 
-    def save(self, path):
-        with open(path, "w") as f:
-            json.dump(self.to_json(), f, indent=1, allow_nan=False)
+    save = Calibration.save                                # the same strict-JSON writer, on this class's to_json
 
     @classmethod
     def load(cls, path):

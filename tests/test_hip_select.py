@@ -6,6 +6,8 @@ import ctypes as C
 import pytest
 import torch
 
+from tests.select_ref import _assert_same, _bit_patterns
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 INF = float("inf")
@@ -31,18 +33,6 @@ def _reference(values, ranks, keep=None):
     return out, (values.shape[1] if keep is None else int(keep.bool().sum()))
 
 
-def _assert_same(got, want, what=""):
-    got = got.cpu()
-    assert got.shape == want.shape and got.dtype == torch.float32, what
-    nan = torch.isnan(want)
-    assert torch.equal(torch.isnan(got), nan), what
-    g0 = torch.where(got == 0, torch.zeros_like(got), got)
-    assert torch.equal(g0[~nan], want[~nan]), what
-    bits = got.view(torch.int32)
-    assert bool((bits[got == 0] == 0).all()), what + ": a zero must come back as +0.0"
-    assert bool((bits[nan] == 0x7FC00000).all()), what + ": a NaN must come back as the canonical quiet NaN"
-
-
 def _check(values, ranks, keep=None, what=""):
     """values: a CPU (B, n) tensor, or a device view whose CPU copy is the reference's input."""
     from legged_gym_dev_amd.tube.calibrate import select_kth
@@ -55,16 +45,6 @@ def _check(values, ranks, keep=None, what=""):
     _assert_same(got, want, what)
     assert int(n_kept) == n_want, what
     return got
-
-
-def _bit_patterns(B, n, seed):
-    """Uniformly random 32-bit patterns viewed as fp32, with every special planted once per row for good measure."""
-    g = torch.Generator().manual_seed(seed)
-    v = torch.randint(-2 ** 31, 2 ** 31, (B, n), generator=g, dtype=torch.int64).to(torch.int32)
-    if n >= 8:
-        v[:, :8] = torch.tensor([0x7F800000, -0x00800000, 0x7FC00001, -0x00000001, -0x80000000, 0, 1, -0x7FFFFFFF], dtype=torch.int32)
-        v = v[:, torch.randperm(n, generator=g)]
-    return v.view(torch.float32)
 
 
 def _middle_ranks(n_kept, B):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the grouped k-th selection (csrc/select_grouped_kernels.hip, tube/calibrate.py select_kth_grouped; DESIGN.md section
+"""Timing of the grouped k-th selection (k_select_grouped_pass in csrc/select_kernels.hip, tube/calibrate.py select_kth_grouped; DESIGN.md section
 10.7) on resident data against the two routes that existed before it:
 
     masked    G calls of select_kth, each with the keep mask of one group and a host read of the group's count in front (the rank

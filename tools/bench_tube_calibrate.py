@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the batched k-th selection (csrc/select_kernels.hip, tube/calibrate.py select_kth) against torch.kthvalue and against
+"""Timing of the batched k-th selection (k_select_pass in csrc/select_kernels.hip, tube/calibrate.py select_kth) against torch.kthvalue and against
 torch.sort + gather on the device, on resident data, and of calibrate_tube.py --sim end to end on the default model.
 
 Shapes (B, n), R ranks per row:
