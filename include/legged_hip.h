@@ -459,7 +459,7 @@ int lg_ppo_comm_wait_ms(lg_ppo *p, double *ms_total, int64_t *minibatches);
 #define LG_TUBE_LOSS_SCALAR 0                      /* ScalarTubeLoss / ScalarHorizonTubeLoss: Huber mean over rows x outputs */
 #define LG_TUBE_LOSS_VECTOR 1                      /* VectorTubeLoss: pinball residuals summed per row, Huber mean over rows */
 #define LG_TUBE_LOSS_MSE 2                         /* ErrorLoss */
-#define LG_TUBE_MAX_LEVELS 64                       /* levels of one lg_tube_predict_levels call */
+#define LG_TUBE_MAX_LEVELS 64                       /* levels of one lg_tube_predict_levels / lg_tube_predict_windows_levels call */
 typedef struct lg_tube_cfg {
     int32_t input_dim, output_dim, num_units, num_layers;
     int32_t activation, loss, horizon /*0: flat (data, target) rows; 1: ScalarHorizonTubeDataset windows*/, batch_size;
@@ -470,7 +470,11 @@ typedef struct lg_tube_cfg {
     /* Level-conditioned tube; 0 = off.  With level_input = 1 the LAST input column is the coverage level
      * of the row: input_dim counts it, the data of lg_tube_set_data has input_dim - 1 columns, every step / eval draws one level
      * per row, uniform over [level_lo, level_hi), and the row's pinball loss takes that level where it takes alpha otherwise
-     * (alpha is not read).  Needs a tube loss (not mse), horizon = 0, input_dim >= 2 and 0 <= level_lo < level_hi <= 1. */
+     * (alpha is not read).  Needs a tube loss (not mse), input_dim >= 2 and 0 <= level_lo < level_hi <= 1.
+     * With horizon = 1 the window item gains the level as its last column: [w[t0-H_rev : t0], z[t0],
+     * v[t0-H_rev : t0+H_fwd], level], input_dim = H_rev + nz + (H_rev + H_fwd) m + 1; one level per row, shared by the row's H_fwd
+     * outputs in the loss; starts and levels both record the draw.  Chosen edge of the envelope: a conditioned horizon handle needs
+     * H_rev >= 1 -- an item without a past error carries no error history; the conditioned flat kinds serve that case. */
     int32_t level_input, _pad2;
     float level_lo, level_hi;
 } lg_tube_cfg;
@@ -498,7 +502,8 @@ int lg_tube_param_layout(lg_tube *t, int64_t *offsets, int64_t *shapes, int max_
 int lg_tube_params_changed(lg_tube *t);            /* after the caller wrote params (initialisation, checkpoint load) */
 int lg_tube_set_step(lg_tube *t, int64_t step);    /* Adam / StepLR step count (resume) */
 /* which: 0 train, 1 test.  Device pointers the caller keeps alive.  Flat: x = data (rows, input_dim), y = target
- * (rows, output_dim), v unused.  Horizon: x = w (rows, T), y = z (rows, T, nz), v = v (rows, T, m), padded in front by H_rev. */
+ * (rows, output_dim), v unused.  Horizon: x = w (rows, T), y = z (rows, T, nz), v = v (rows, T, m), padded in front by H_rev;
+ * -1 unless input_dim == H_rev + nz + (H_rev + H_fwd) m (+ 1 on a level_input handle). */
 int lg_tube_set_data(lg_tube *t, int which, const float *x, const float *y, const float *v, int64_t rows, int32_t T, int32_t nz,
                      int32_t m);
 int lg_tube_begin_epoch(lg_tube *t, int64_t epoch);   /* a new permutation of the training rows, keyed by (seed, epoch) */
@@ -526,9 +531,18 @@ int lg_tube_predict_levels(lg_tube *t, const float *x, const int32_t *rows, int6
                            float *out);
 /* Horizon handles: item (env[i], start[i]) built as ScalarHorizonTubeDataset._get_item_helper does, out (count, H_fwd).
  * w (n, T), z (n, T, nz), v (n, T, m) padded in front by H_rev as for lg_tube_set_data.
- * Caller guarantees 0 <= env[i] < n, H_rev <= start[i] and start[i] + H_fwd <= T. */
+ * Caller guarantees 0 <= env[i] < n, H_rev <= start[i] and start[i] + H_fwd <= T.  -1 on a level_input handle: a window holds no
+ * level, lg_tube_predict_windows_levels takes them. */
 int lg_tube_predict_windows(lg_tube *t, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz,
                             int32_t m, const int32_t *env, const int32_t *start, int64_t count, float *out);
+/* level_input horizon handles: out[i, l] = MLP([item (env[i], start[i]), levels[l]]), one launch; the arrays and the caller's
+ * guarantees are lg_tube_predict_windows', input_dim = H_rev + nz + (H_rev + H_fwd) m + 1, levels (device, n_levels,
+ * 1 <= n_levels <= 64), out (count, n_levels, H_fwd).  The first layer's chain over the shared columns is computed once per window.
+ * Each out[i, l] equals, bit for bit, lg_tube_predict of a flat level_input handle with the same parameters on the item with
+ * levels[l] appended.  -1 on an unconditioned handle and on a flat handle. */
+int lg_tube_predict_windows_levels(lg_tube *t, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz,
+                                   int32_t m, const int32_t *env, const int32_t *start, int64_t count, const float *levels,
+                                   int32_t n_levels, float *out);
 /* Closed loop over time, one launch.  x (n_seq, T, input_dim): the teacher rows in time order.  out (n_seq, T, output_dim).
  * out[s, t] = MLP(xt) where xt = x[s, t] with its leading fb columns replaced by out[s, t-1, 0:fb],
  * except at t == 0 and where reseed[s, t] != 0 (reseed (n_seq, T) may be NULL): there xt = x[s, t] unchanged.

@@ -246,6 +246,7 @@ def declare_tube_api(lib):
     lib.lg_tube_sweep_eval.argtypes = [vp]
     lib.lg_tube_eval_level.argtypes = [vp, f32]
     lib.lg_tube_predict_levels.argtypes = [vp, vp, vp, i64, vp, i32, vp]
+    lib.lg_tube_predict_windows_levels.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp, i32, vp]
     lib.lg_tube_sweep_eval_level.argtypes = [vp, f32]
 
 

@@ -1,6 +1,6 @@
 // C-ABI (include/legged_hip.h, lg_tube_*) of the tube-model trainer: parameter / optimiser / slab allocation in HBM, epoch
 // permutation, the two launches of a training step, the eval launch, and the inference entries: predict, window prediction and
-// the closed-loop roll-outs, single-tap and windowed, and the level entries of a level-conditioned model (tube_kernels.hip).  lg_tube_sweep_*: K such trainers of one shape on one
+// the closed-loop roll-outs, single-tap and windowed, and the level entries of a level-conditioned model, flat or horizon (tube_kernels.hip).  lg_tube_sweep_*: K such trainers of one shape on one
 // dataset, stepped by the same two launches with the members along grid y.
 #include <cmath>
 #include <cstring>
@@ -29,6 +29,9 @@ void tubek_eval_sweep(const TubeMember *M, int K, const TubeDev *D0, const TubeS
                       float level, hipStream_t s);
 void tubek_predict_levels(const TubeDev *D, const float *x, const int32_t *rows, int64_t count, const float *levels, int n_levels,
                           float *o, hipStream_t s);
+void tubek_predict_windows_levels(const TubeDev *D, const float *w, const float *z, const float *v, const int32_t *env,
+                                  const int32_t *start, int T, int nz, int m, int64_t count, const float *levels, int n_levels,
+                                  float *o, hipStream_t s);
 void tubek_perm_sweep(const TubeMember *M, int K, int n, uint64_t epoch, hipStream_t s);
 void tubek_predict(const TubeDev *D, const float *x, const float *y, const float *v, const int32_t *rows, const int32_t *env,
                    const int32_t *start, int T, int nz, int m, int64_t count, float *o, hipStream_t s);
@@ -91,7 +94,7 @@ static std::string cfg_reason(const lg_tube_cfg *c) {
     if (c->level_input != 0 && c->level_input != 1) return "level_input must be 0 or 1";
     if (c->level_input) {
         if (c->loss == LG_TUBE_LOSS_MSE) return "level_input needs a tube loss (scalar or vector): the mse loss has no level";
-        if (c->horizon) return "level_input with horizon = 1 is not supported: lg_tube_predict_windows has no place for a level";
+        if (c->horizon && c->H_rev < 1) return "level_input with horizon = 1 needs H_rev >= 1: an item without a past error has no error history (use a flat level kind)";
         if (c->input_dim < 2) return "level_input: input_dim counts the level column and must be at least 2";
         if (!(c->level_lo >= 0.f && c->level_lo < c->level_hi && c->level_hi <= 1.f)) return "level range must satisfy 0 <= level_lo < level_hi <= 1";
     }
@@ -130,6 +133,11 @@ static void dev_free(TubeDev &D) {
         if (q) (void)hipFree(q);
 }
 
+// columns of a horizon handle's item built from z of width nz and v of width m; a conditioned handle's last column is the level
+static int64_t window_dim(const TubeDev &D, int32_t nz, int32_t m) {
+    return D.H_rev + (int64_t)nz + (int64_t)(D.H_rev + D.H_fwd) * m + (D.level_input ? 1 : 0);
+}
+
 // what is wrong with a split handed to set_data (null: nothing); a horizon split's T, nz, m are taken into D
 static const char *data_reason(TubeDev &D, int which, const float *x, const float *y, const float *v, int64_t rows, int32_t T, int32_t nz,
                                int32_t m) {
@@ -137,7 +145,8 @@ static const char *data_reason(TubeDev &D, int which, const float *x, const floa
     if (rows < 1 || rows > INT32_MAX) return "rows must be 1..2^31-1";
     if (!x || (!D.horizon && !y) || (D.horizon && ((nz && !y) || (m && !v)))) return "missing array";
     if (D.horizon) {
-        if (D.H_rev + nz + (D.H_rev + D.H_fwd) * m != D.in_dim) return "input_dim != H_rev + nz + (H_rev + H_fwd) * m";
+        if (nz < 0 || m < 0 || window_dim(D, nz, m) != D.in_dim)
+            return D.level_input ? "input_dim != H_rev + nz + (H_rev + H_fwd) * m + 1 (the level column)" : "input_dim != H_rev + nz + (H_rev + H_fwd) * m";
         if (T - D.H_fwd - 1 <= D.H_rev) return "T - H_fwd - 1 must exceed H_rev";
         if ((D.T && D.T != T) || (D.nz && D.nz != nz) || (D.m && D.m != m)) return "train and test splits differ in T, nz or m";
         D.T = T; D.nz = nz; D.m = m;
@@ -321,18 +330,46 @@ int lg_tube_predict_levels(lg_tube *p, const float *x, const int32_t *rows, int6
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict_levels: launch failed"), -3);
 }
 
+// what is wrong with a window query on a horizon handle (null: nothing)
+static const char *windows_reason(const TubeDev &D, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz,
+                                  int32_t m, const int32_t *env, const int32_t *start, int64_t count, const float *out) {
+    if (count < 1 || n < 1) return "n and count must be positive";
+    if (nz < 0 || m < 0 || window_dim(D, nz, m) != D.in_dim)
+        return D.level_input ? "input_dim != H_rev + nz + (H_rev + H_fwd) * m + 1 (the level column)" : "input_dim != H_rev + nz + (H_rev + H_fwd) * m";
+    if (T < D.H_rev + D.H_fwd) return "T is shorter than H_rev + H_fwd";
+    if (!w || (nz && !z) || (m && !v) || !env || !start || !out) return "missing array";
+    return nullptr;
+}
+
 int lg_tube_predict_windows(lg_tube *p, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz, int32_t m,
                             const int32_t *env, const int32_t *start, int64_t count, float *out) {
     const TubeDev &D = p->dev;
     if (!D.horizon) { lg_set_error("lg_tube_predict_windows: a flat handle predicts rows (lg_tube_predict)"); return -1; }
-    if (count < 1 || n < 1) { lg_set_error("lg_tube_predict_windows: n and count must be positive"); return -1; }
-    if (nz < 0 || m < 0 || D.H_rev + nz + (D.H_rev + D.H_fwd) * m != D.in_dim) {
-        lg_set_error("lg_tube_predict_windows: input_dim != H_rev + nz + (H_rev + H_fwd) * m"); return -1;
+    if (D.level_input) {
+        lg_set_error("lg_tube_predict_windows: the handle is level-conditioned (lg_tube_cfg.level_input): a window has no level, use "
+                     "lg_tube_predict_windows_levels");
+        return -1;
     }
-    if (T < D.H_rev + D.H_fwd) { lg_set_error("lg_tube_predict_windows: T is shorter than H_rev + H_fwd"); return -1; }
-    if (!w || (nz && !z) || (m && !v) || !env || !start || !out) { lg_set_error("lg_tube_predict_windows: missing array"); return -1; }
+    if (const char *e = windows_reason(D, w, z, v, n, T, nz, m, env, start, count, out)) {
+        lg_set_error(std::string("lg_tube_predict_windows: ") + e); return -1;
+    }
     tubek_predict(&p->dev, w, z, v, nullptr, env, start, T, nz, m, count, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict_windows: launch failed"), -3);
+}
+
+int lg_tube_predict_windows_levels(lg_tube *p, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz,
+                                   int32_t m, const int32_t *env, const int32_t *start, int64_t count, const float *levels,
+                                   int32_t n_levels, float *out) {
+    const TubeDev &D = p->dev;
+    const char *e = nullptr;
+    if (!D.level_input) e = "the handle is not level-conditioned (lg_tube_cfg.level_input)";
+    else if (!D.horizon) e = "not a horizon handle (lg_tube_cfg.horizon): a flat handle predicts rows (lg_tube_predict_levels)";
+    else if (n_levels < 1 || n_levels > LG_TUBE_MAX_LEVELS) e = "n_levels must be 1..64";
+    else if (!levels) e = "missing array";
+    else e = windows_reason(D, w, z, v, n, T, nz, m, env, start, count, out);
+    if (e) { lg_set_error(std::string("lg_tube_predict_windows_levels: ") + e); return -1; }
+    tubek_predict_windows_levels(&p->dev, w, z, v, env, start, T, nz, m, count, levels, n_levels, out, p->stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict_windows_levels: launch failed"), -3);
 }
 
 int lg_tube_rollout(lg_tube *p, const float *x, int64_t n_seq, int32_t T, int32_t fb, const uint8_t *reseed, float *out) {

@@ -9,7 +9,8 @@
 //   k_tube_adam        sums the slab rows in workgroup order (fixed order: bit-reproducible without atomics), applies
 //                      torch.optim.Adam (defaults) at the StepLR rate of the step, and logs loss, lr and gradient norm on the device.
 // A level-conditioned model (lg_tube_cfg.level_input) runs the same two launches with the tile's LEVEL flag
-// set, and k_tube_predict_levels evaluates many levels of a row in one launch.
+// set -- on flat rows and on horizon windows alike (section 10.8) -- and k_tube_predict_levels evaluates many levels of a row, or
+// of a window, in one launch.
 // Plain fp32 FMA over LDS tiles: at 16..128 units the matrices are far too small for MFMA to matter.
 #include "tube_device.h"
 
@@ -279,13 +280,16 @@ __global__ void __launch_bounds__(NT) k_tube_predict(TubeDev D, TubeGather G, in
 }
 
 // out[i][l] = MLP([x row of item i, levels[l]]) for a level-conditioned model: R rows per workgroup, gathered as in k_tube_predict
-// from x (n, I - 1).  The first layer is split: per (row, unit) the chain over the I - 1 shared columns -- acc = 0, fmaf over k
+// from x (n, I - 1) -- or, WINDOW, as k_tube_predict's horizon branch gathers the item at (env[i], start[i]) of w, z, v: the I - 1
+// shared columns [w[t0-H_rev : t0], z[t0], v[t0-H_rev : t0+H_fwd]] (k_tube_predict_windows_levels is that instantiation).
+// The first layer is split: per (row, unit) the chain over the I - 1 shared columns -- acc = 0, fmaf over k
 // ascending, tube_layer's order -- is computed once into A; per level the unit is finished with the chain's last link
 // fmaf(level, w[I-1][j], acc), the bias and the activation, and the remaining layers run through tube_layer.  The level is the
 // last k of the first layer, so every out[i][l] equals k_tube_predict on the row with the level appended, bit for bit.
 // Dynamic LDS: X (R, I - 1), A (R, U), H0, H1 (R, U).  o: (count, n_levels, O).
-__global__ void __launch_bounds__(NT) k_tube_predict_levels(TubeDev D, const float *x, const int32_t *rows, int64_t count,
-                                                            const float *levels, int n_levels, float *o) {
+template <bool WINDOW>
+__global__ void __launch_bounds__(NT) k_tube_predict_levels(TubeDev D, TubeGather G, int64_t count, const float *levels, int n_levels,
+                                                            float *o) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, I = D.in_dim, Ix = I - 1, O = D.out_dim, U = D.units, L = D.layers;
     const int64_t base = (int64_t)blockIdx.x * R;
@@ -293,12 +297,23 @@ __global__ void __launch_bounds__(NT) k_tube_predict_levels(TubeDev D, const flo
     float *X = lds, *A = X + R * Ix, *H0 = A + R * U, *H1 = H0 + R * U;
     for (int e = tid; e < R * Ix; e += NT) {
         const int r = e / Ix, c = e - r * Ix;
-        float v = 0.f;
+        float x = 0.f;
         if (r < nr) {
-            const int64_t s = rows ? (int64_t)rows[base + r] : base + r;
-            v = x[s * Ix + c];
+            if (!WINDOW) {
+                const int64_t s = G.rows ? (int64_t)G.rows[base + r] : base + r;
+                x = G.x[s * Ix + c];
+            } else {
+                const int64_t s = G.env[base + r];
+                const int t0 = G.start[base + r];
+                if (c < D.H_rev) x = G.x[s * G.T + t0 - D.H_rev + c];
+                else if (c < D.H_rev + G.nz) x = G.y[(s * G.T + t0) * G.nz + (c - D.H_rev)];
+                else {
+                    const int q = c - D.H_rev - G.nz, tt = q / G.m;
+                    x = G.v[(s * G.T + t0 - D.H_rev + tt) * G.m + (q - tt * G.m)];
+                }
+            }
         }
-        X[e] = v;
+        X[e] = x;
     }
     __syncthreads();
     const float *w0 = D.wt + D.off_w[0], *b0 = D.params + D.off_b[0];
@@ -560,8 +575,18 @@ void tubek_predict(const TubeDev *D, const float *x, const float *y, const float
 
 void tubek_predict_levels(const TubeDev *D, const float *x, const int32_t *rows, int64_t count, const float *levels, int n_levels,
                           float *o, hipStream_t s) {
+    const TubeGather G{x, nullptr, nullptr, rows, nullptr, nullptr, 0, 0, 0};
     const size_t bytes = sizeof(float) * (size_t)R * (D->in_dim - 1 + 3 * D->units);
-    hipLaunchKernelGGL(k_tube_predict_levels, dim3((unsigned)((count + R - 1) / R)), dim3(NT), bytes, s, *D, x, rows, count, levels,
+    hipLaunchKernelGGL(k_tube_predict_levels<false>, dim3((unsigned)((count + R - 1) / R)), dim3(NT), bytes, s, *D, G, count, levels,
+                       n_levels, o);
+}
+// k_tube_predict_windows_levels: the same tile with the window gather
+void tubek_predict_windows_levels(const TubeDev *D, const float *w, const float *z, const float *v, const int32_t *env,
+                                  const int32_t *start, int T, int nz, int m, int64_t count, const float *levels, int n_levels,
+                                  float *o, hipStream_t s) {
+    const TubeGather G{w, z, v, nullptr, env, start, T, nz, m};
+    const size_t bytes = sizeof(float) * (size_t)R * (D->in_dim - 1 + 3 * D->units);
+    hipLaunchKernelGGL(k_tube_predict_levels<true>, dim3((unsigned)((count + R - 1) / R)), dim3(NT), bytes, s, *D, G, count, levels,
                        n_levels, o);
 }
 
@@ -578,7 +603,8 @@ int tubek_init() {
     const int plim = (int)(sizeof(float) * R * (LG_TUBE_MAX_IN + 2 * LG_TUBE_MAX_UNITS));
     if (hipFuncSetAttribute((const void *)k_tube_predict, hipFuncAttributeMaxDynamicSharedMemorySize, plim) != hipSuccess) return -1;
     const int llim = (int)(sizeof(float) * R * (LG_TUBE_MAX_IN - 1 + 3 * LG_TUBE_MAX_UNITS));
-    if (hipFuncSetAttribute((const void *)k_tube_predict_levels, hipFuncAttributeMaxDynamicSharedMemorySize, llim) != hipSuccess) return -1;
+    for (const void *f : {(const void *)k_tube_predict_levels<false>, (const void *)k_tube_predict_levels<true>})
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, llim) != hipSuccess) return -1;
     for (const void *f : {(const void *)k_tube_rollout<1, 64, true>, (const void *)k_tube_rollout<1, 64, false>,
                           (const void *)k_tube_rollout<4, 64, true>, (const void *)k_tube_rollout<4, 64, false>,
                           (const void *)k_tube_rollout<16, 256, true>, (const void *)k_tube_rollout<16, 256, false>,

@@ -4,7 +4,9 @@
 // level (float; read only when LEVEL).  The tile is blockIdx.x.
 // LEVEL (lg_tube_cfg.level_input): the last input column is the row's coverage level -- `level` where it is >= 0 (lg_tube_eval_level),
 // else drawn per row position by tube_level -- and the row's pinball loss takes it in place of D.alpha.  The split then holds I - 1
-// columns.  Every LEVEL statement sits behind the compile-time flag: with LEVEL = false the fragment compiles what it compiled before.
+// columns; on a horizon handle the window item holds I - 1 columns, the gather's window branch runs for
+// c < I - 1 only, and the row's H_fwd outputs share the level.  Every LEVEL statement sits behind the compile-time flag: with
+// LEVEL = false the fragment compiles what it compiled before.
 // It declares its own shared arrays and may return early, so it must be the last thing in the kernel.
 //
 // Why a fragment and not a function: as `template <bool TRAIN> __device__ __forceinline__ void tube_rows_tile(const TubeDev &D,

@@ -7,7 +7,8 @@
 Every calibration row is scored with s = w - fw on the predictions evaluate_tube.py scores -- the one-step prediction and the
 closed-loop roll-out (same reseed mask, pooled over ages) for the flat datasets scalar and vector, per level for a
 level-conditioned run (level l is calibrated to coverage l, which makes "the level is the coverage" true), per step ahead for
-scalar_horizon -- and the ceil((n + 1) c)-th smallest score of every set, taken exactly on the device (lg_select_kth), is the
+scalar_horizon, per level and step ahead for scalar_horizon_level (--levels; every level of every window from one launch) -- and
+the ceil((n + 1) c)-th smallest score of every set, taken exactly on the device (lg_select_kth), is the
 offset that evaluate_tube.py --calibration adds to the prediction.  error_dynamics is refused: it predicts a signed error, not a
 bound.  Rows after a done are left out, as in the evaluation.
 
@@ -47,7 +48,7 @@ import torch  # noqa: E402
 import evaluate_tube as et  # noqa: E402
 from legged_gym_dev_amd.tube import calibrate as cal  # noqa: E402
 from legged_gym_dev_amd.tube import evaluate as ev  # noqa: E402
-from legged_gym_dev_amd.tube.data import LEVEL_KINDS, construct_dataset, feedback_layout  # noqa: E402
+from legged_gym_dev_amd.tube.data import HORIZON_KINDS, HORIZON_LEVEL_KIND, LEVEL_KINDS, construct_dataset, feedback_layout  # noqa: E402
 from legged_gym_dev_amd.tube.model import HipTubeModel  # noqa: E402
 
 DEFAULT_COVERAGE = (0.9, 0.95)
@@ -93,10 +94,10 @@ def sim_flags(a, cfg):
 def check_kind(cfg, a):
     """The dataset kinds that are bounds; the coverages or levels asked for, as the decimals written."""
     kind = cfg["dataset"]
-    if LEVEL_KINDS.get(kind, kind) not in cal.FLAT_KINDS + ("scalar_horizon",):
+    if LEVEL_KINDS.get(kind, kind) not in cal.FLAT_KINDS + HORIZON_KINDS:
         raise ValueError(f"--run was trained on {kind}: it predicts a signed error, not a bound, and is not calibrated "
-                         f"(bounds: {', '.join(cal.FLAT_KINDS)}, their level kinds and scalar_horizon)")
-    if kind in LEVEL_KINDS:
+                         f"(bounds: {', '.join(cal.FLAT_KINDS)}, their level kinds, scalar_horizon and scalar_horizon_level)")
+    if et.DATASETS[kind].conditioned:
         if a.coverage is not None:
             raise ValueError("a level-conditioned run is calibrated per level: give --levels, not --coverage")
         wanted = a.levels.split(",") if a.levels else [str(v) for v in et.DEFAULT_LEVELS]
@@ -121,8 +122,8 @@ def check_by_age(cfg, a):
     if kind in LEVEL_KINDS:
         raise ValueError(f"--by_age: {kind} is level-conditioned; per-age and trajectory calibration of conditioned tubes is not built "
                          f"(flat kinds only: {', '.join(cal.FLAT_KINDS)})")
-    if kind == "scalar_horizon":
-        raise ValueError("--by_age: scalar_horizon predicts all steps ahead in one shot and already has one offset per step ahead")
+    if kind in HORIZON_KINDS:
+        raise ValueError(f"--by_age: {kind} predicts all steps ahead in one shot and already has one offset per step ahead")
     if kind not in cal.FLAT_KINDS:
         raise ValueError(f"--by_age: {kind} predicts a signed error, not a bound, and is not calibrated")
     if a.max_age is not None and not 1 <= a.max_age <= cal.MAX_GROUPS:
@@ -145,6 +146,9 @@ def calibrate_age(model, cfg, raw, a, wanted, dev):
 
 def calibrate(model, cfg, raw, a, wanted, dev):
     kind = cfg["dataset"]
+    if kind == HORIZON_LEVEL_KIND:                          # one launch scores every level of every window
+        _, series = et.evaluate_horizon_levels(model, cfg, raw, a.window_stride, dev, wanted)
+        return cal.calibrate_horizon_levels(series["fw_levels"], series["target"], wanted)
     if kind == "scalar_horizon":
         _, series = et.evaluate_horizon(model, cfg, raw, a.window_stride, dev)
         Hf = series["fw"].shape[-1]
@@ -169,10 +173,10 @@ def main(argv=None):
     dev = torch.device(a.device)
     out = a.out or a.run
     os.makedirs(out, exist_ok=True)
-    horizon = (cfg["H_fwd"], cfg["H_rev"]) if cfg["dataset"] == "scalar_horizon" else None
+    horizon = (cfg["H_fwd"], cfg["H_rev"]) if cfg["dataset"] in HORIZON_KINDS else None
     sim = sim_flags(a, cfg) if a.sim else None
     model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, activation=cfg["activation"], softplus_beta=cfg["softplus_beta"],
-                              horizon=horizon, device=a.device, level_input=cfg["dataset"] in LEVEL_KINDS)
+                              horizon=horizon, device=a.device, level_input=et.DATASETS[cfg["dataset"]].conditioned)
     try:
         raw = et.sim_records(sim, a.device) if a.sim else construct_dataset(a.data)
         c = calibrate(model, cfg, raw, a, wanted, dev)

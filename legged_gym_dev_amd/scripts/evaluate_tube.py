@@ -22,7 +22,10 @@ reference's "Total Success Rate" (and, for error_dynamics, "Mean Error" / "Mean 
 A level-conditioned run (config.json level_input; datasets scalar_level, vector_level) is scored per coverage level (--levels,
 default 0.5,0.8,0.9,0.95): eval.json's "levels" has one entry per level with the one-step metrics -- every level of every row from one
 predict_levels launch -- and the closed-loop roll-out with the level column filled.  The success rate rises with the level but need
-not equal it.
+not equal it.  A level-conditioned one-shot run (dataset scalar_horizon_level; section 10.8) is scored per level
+on the windows scalar_horizon scores: "levels" has one entry per level with the one-shot metrics -- every level of every window from
+one predict_windows_levels launch -- and "level_crossings" is the share of (window, step ahead, pair of adjacent levels) where the
+prediction falls as the level rises.
 
 --sim in place of --data scores the model on fresh robots, as the reference's evaluation scripts do: --sim_resident epochs (default 1)
 of --sim_envs envs x --sim_T steps are simulated then and there by the ROM-on-ROM simulator (tube/rom_sim.py HipRomSim) with
@@ -64,7 +67,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch  # noqa: E402
 
 from legged_gym_dev_amd.tube import evaluate as ev  # noqa: E402
-from legged_gym_dev_amd.tube.data import DATASETS, LEVEL_KINDS, construct_dataset, feedback_layout, sequences  # noqa: E402
+from legged_gym_dev_amd.tube.data import (DATASETS, HORIZON_KINDS, HORIZON_LEVEL_KIND, LEVEL_KINDS, construct_dataset,  # noqa: E402
+                                          feedback_layout, sequences)
 from legged_gym_dev_amd.tube.model import CONFIG_NAME, HipTubeModel, read_config  # noqa: E402
 
 DEFAULTS = {"N": 1, "dN": 1, "recursive": False, "H_fwd": 50, "H_rev": 10, "softplus_beta": 1.0}
@@ -163,7 +167,8 @@ def load_calibration(a, cfg, sim):
     if not os.path.isfile(path):
         raise FileNotFoundError(f"{path} is missing: calibrate_tube.py --run {a.run} writes it")
     c = Calibration.load(path)
-    kind = "levels" if cfg["dataset"] in LEVEL_KINDS else "horizon" if cfg["dataset"] == "scalar_horizon" else "flat"
+    kind = "levels" if cfg["dataset"] in LEVEL_KINDS else "horizon_levels" if cfg["dataset"] == HORIZON_LEVEL_KIND \
+        else "horizon" if cfg["dataset"] == "scalar_horizon" else "flat"
     if c.kind != kind or c.provenance.get("dataset", cfg["dataset"]) != cfg["dataset"]:
         raise ValueError(f"{path} calibrates a {c.provenance.get('dataset', c.kind)} model; the run is {cfg['dataset']}")
     refuse_own_rows(c, path, a, sim)
@@ -294,12 +299,14 @@ def evaluate_levels(model, cfg, raw, horizon, dev, levels, calib=None):
     return res, series
 
 
-def evaluate_horizon(model, cfg, raw, stride, dev, calib=None):
+def horizon_windows(cfg, raw, stride, dev, kind="scalar_horizon"):
+    """The windows a one-shot evaluation scores: (ds, env, start, target (windows, H_fwd), starts) with the starts H_rev,
+    H_rev + stride, ... of every env, env-major."""
     if isinstance(raw["z"], torch.Tensor) and raw["z"].is_cuda:
         from legged_gym_dev_amd.tube.device_data import from_records
-        ds = from_records(DATASETS["scalar_horizon"], raw, H_fwd=cfg["H_fwd"], H_rev=cfg["H_rev"])
+        ds = from_records(DATASETS[kind], raw, H_fwd=cfg["H_fwd"], H_rev=cfg["H_rev"])
     else:
-        ds = DATASETS["scalar_horizon"].from_folder(raw, H_fwd=cfg["H_fwd"], H_rev=cfg["H_rev"])
+        ds = DATASETS[kind].from_folder(raw, H_fwd=cfg["H_fwd"], H_rev=cfg["H_rev"])
     Hf, Hr = ds.H_fwd, ds.H_rev
     E, T = ds.w.shape
     starts = torch.arange(Hr, T - Hf, max(1, stride), dtype=torch.int32)        # targets reach w[start + H_fwd] <= w[T - 1]
@@ -307,10 +314,33 @@ def evaluate_horizon(model, cfg, raw, stride, dev, calib=None):
         raise ValueError(f"episodes of {T - Hr} steps are shorter than H_fwd + 1 = {Hf + 1}")
     env = torch.arange(E, dtype=torch.int32).repeat_interleave(starts.numel())
     start = starts.repeat(E)
-    fw = model.predict_windows(ds, env, start)
     w = ds.w.to(dev)
     idx = start.to(dev).long()[:, None] + torch.arange(1, Hf + 1, device=dev)[None, :]
-    target = w[env.to(dev).long()[:, None], idx]
+    return ds, env, start, w[env.to(dev).long()[:, None], idx], starts
+
+
+def evaluate_horizon_levels(model, cfg, raw, stride, dev, levels, calib=None):
+    """evaluate_horizon per level of a level-conditioned one-shot model: every level of every window from
+    one predict_windows_levels launch, one window_metrics entry per level, and level_crossings over the adjacent levels."""
+    ds, env, start, target, starts = horizon_windows(cfg, raw, stride, dev, HORIZON_LEVEL_KIND)
+    E, Hf = ds.w.shape[0], ds.H_fwd
+    fw = model.predict_windows_levels(ds, env, start, torch.tensor(levels, dtype=torch.float32))          # (windows, levels, H_fwd)
+    per_level = []
+    for i, lv in enumerate(levels):
+        per_level.append({"level": lv, "one_shot": ev.window_metrics(fw[:, i, :], target)})
+        if calib is not None:
+            per_level[-1]["calibrated"] = {"n": calib.n, "rank": calib.ranks[calib.index(level=lv)], "one_shot": _cal_safe(
+                {**ev.window_metrics(calib.apply(fw[:, i, :], level=lv), target), "offset": calib.offset(level=lv).tolist(),
+                 "covered_by_step": calib.covers(fw[:, i, :], target, level=lv).sum(dim=0).tolist()})}
+    res = {"levels": per_level, "level_crossings": ev.level_crossings(fw, levels), "envs": E, "windows_per_env": int(starts.numel()),
+           "window_stride": stride}
+    return res, {"w": target.reshape(E, -1, Hf), "fw": fw[:, -1, :].reshape(E, -1, Hf), "fw_levels": fw, "target": target, "starts": starts}
+
+
+def evaluate_horizon(model, cfg, raw, stride, dev, calib=None):
+    ds, env, start, target, starts = horizon_windows(cfg, raw, stride, dev)
+    E, Hf = ds.w.shape[0], ds.H_fwd
+    fw = model.predict_windows(ds, env, start)
     res = {"one_shot": ev.window_metrics(fw, target), "envs": E, "windows_per_env": int(starts.numel()), "window_stride": stride}
     if calib is not None:
         res["calibrated"] = {"n": calib.n, "coverages": calib.coverages, "ranks": calib.ranks, "one_shot": [_cal_safe(
@@ -326,7 +356,7 @@ def plot(kind, series, out, n_envs):
     files = []
     for e in range(min(n_envs, series["w"].shape[0])):
         fig, ax = plt.subplots(figsize=(9, 4))
-        if kind == "scalar_horizon":
+        if kind in HORIZON_KINDS:
             for k in range(0, series["w"].shape[1], max(1, series["w"].shape[1] // 8)):
                 t = int(series["starts"][k]) + 1 + torch.arange(series["w"].shape[2])
                 ax.plot(t, series["w"][e, k].cpu(), "b", label="w" if k == 0 else None)
@@ -358,7 +388,7 @@ def main(argv=None):
     dev = torch.device(a.device)
     out = a.out or a.run
     os.makedirs(out, exist_ok=True)
-    horizon = (cfg["H_fwd"], cfg["H_rev"]) if cfg["dataset"] == "scalar_horizon" else None
+    horizon = (cfg["H_fwd"], cfg["H_rev"]) if cfg["dataset"] in HORIZON_KINDS else None
     sim = sim_flags(a, cfg) if a.sim else None
     calib = load_calibration(a, cfg, sim)
     extra = {} if calib is None else {"calib": calib}
@@ -366,13 +396,15 @@ def main(argv=None):
     if age_calib is not None:
         extra["age_calib"] = age_calib
     model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, activation=cfg["activation"], softplus_beta=cfg["softplus_beta"],
-                              horizon=horizon, device=a.device, level_input=cfg["dataset"] in LEVEL_KINDS)
+                              horizon=horizon, device=a.device, level_input=DATASETS[cfg["dataset"]].conditioned)
     raw = sim_records(sim, a.device) if a.sim else construct_dataset(a.data)
     levels = None
     if model.level_input:
         levels = [float(v) for v in a.levels.split(",")] if a.levels else list(DEFAULT_LEVELS)
     try:
-        if levels is not None:
+        if levels is not None and horizon is not None:
+            res, series = evaluate_horizon_levels(model, cfg, raw, a.window_stride, dev, levels, **extra)
+        elif levels is not None:
             res, series = evaluate_levels(model, cfg, raw, a.horizon, dev, levels, **extra)
         elif horizon is None:
             res, series = evaluate_flat(model, cfg, raw, a.horizon, dev, **extra)
@@ -391,7 +423,11 @@ def main(argv=None):
         res["plots"] = plot(cfg["dataset"], series, out, a.plot_envs)
     with open(os.path.join(out, "eval.json"), "w") as f:
         json.dump(_json_safe(res), f, indent=1, allow_nan=False)
-    if levels is not None:
+    if levels is not None and horizon is not None:
+        for r in res["levels"]:
+            print(f"level {r['level']}: Total Success Rate: {r['one_shot']['success_rate']}")
+        print(f"Level crossings: {res['level_crossings']}")
+    elif levels is not None:
         for r in res["levels"]:
             print(f"level {r['level']}: Single Success Rate: {r['one_step']['success_rate']}  Total Success Rate: {r['rollout']['success_rate']}")
     elif horizon is None:
@@ -403,7 +439,10 @@ def main(argv=None):
     else:
         print(f"Total Success Rate: {res['one_shot']['success_rate']}")
     if calib is not None:
-        if levels is not None:
+        if levels is not None and horizon is not None:
+            for r in res["levels"]:
+                print(f"calibrated level {r['level']} one_shot: Success Rate: {r['calibrated']['one_shot']['success_rate']}")
+        elif levels is not None:
             for r in res["levels"]:
                 print(f"calibrated level {r['level']}: Single Success Rate: {r['calibrated']['one_step']['success_rate']}  "
                       f"Total Success Rate: {r['calibrated']['rollout']['success_rate']}")

@@ -25,6 +25,11 @@ the dataset.  On evaluation steps metrics.jsonl also holds the test coverage at 
 on top of it (over seed or lr, say).  The split is drawn once, seeded by --seed, or by the first
 value of a swept seed: the member with that seed matches its single run, the other seeds train on that split too.
 
+--dataset scalar_horizon_level --H_fwd F --H_rev R [--level_lo --level_hi] trains the level-conditioned one-shot tube (DESIGN.md
+section 10.8): the scalar_horizon window item with the level appended, one level drawn per window and shared by its H_fwd outputs;
+the loss is scalar_level (Huber per element), or vector_level with --loss vector_level (summed over the H_fwd outputs, then Huber).
+H_rev must be at least 1.  It logs the same coverages and composes with --sweep and --sim like the flat level datasets.
+
 --sim in place of --data trains straight from the ROM-on-ROM simulator (tube/rom_sim.py HipRomSim): the epochs
 are collected, and the rows built, on the device; nothing is written to disk or copied to the host.  --sim_envs, --sim_T and --sim_seed
 set the simulator (defaults: its own 8192 envs and 200 steps, seed 0); the data set holds the last --sim_resident epochs and after
@@ -43,7 +48,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from legged_gym_dev_amd.tube.data import DATASETS, LEVEL_KINDS, construct_dataset  # noqa: E402
+from legged_gym_dev_amd.tube.data import DATASETS, HORIZON_KINDS, HORIZON_LEVEL_KIND, LEVEL_KINDS, construct_dataset  # noqa: E402
 from legged_gym_dev_amd.tube.trainer import HipTubeTrainer  # noqa: E402
 
 
@@ -88,8 +93,13 @@ def parse_args(argv=None):
     if a.dataset in LEVEL_KINDS:        # the level fields exist on a level-conditioned run only: every other run is as it was
         a.level_input, a.loss = True, a.dataset
         a.level_lo, a.level_hi = getattr(a, "level_lo", 0.0), getattr(a, "level_hi", 1.0)
+    elif a.dataset == HORIZON_LEVEL_KIND:   # one level per window for its H_fwd outputs: Huber per element, or per window (vector_level)
+        if a.loss not in ("scalar", "scalar_level", "vector_level"):
+            ap.error("--dataset scalar_horizon_level takes --loss scalar_level (the default) or vector_level")
+        a.level_input, a.loss = True, "vector_level" if a.loss == "vector_level" else "scalar_level"
+        a.level_lo, a.level_hi = getattr(a, "level_lo", 0.0), getattr(a, "level_hi", 1.0)
     elif a.loss in LEVEL_KINDS or hasattr(a, "level_lo") or hasattr(a, "level_hi"):
-        ap.error("--loss scalar_level / vector_level, --level_lo and --level_hi need --dataset scalar_level or vector_level")
+        ap.error("--loss scalar_level / vector_level, --level_lo and --level_hi need --dataset scalar_level, vector_level or scalar_horizon_level")
     if getattr(a, "sim", False):        # the sim fields exist on a --sim run only: a --data run is as it was
         for name, (_, default, _) in SIM_FLAGS.items():
             setattr(a, name, getattr(a, name, default))
@@ -188,7 +198,7 @@ def make_dataset(a):
     ds = construct_dataset(a.data)
     if a.dataset in ("scalar", "scalar_level"):
         return DATASETS[a.dataset].from_folder(ds, N=a.N, dN=a.dN, recursive=a.recursive)
-    if a.dataset == "scalar_horizon":
+    if a.dataset in HORIZON_KINDS:
         return DATASETS[a.dataset].from_folder(ds, H_fwd=a.H_fwd, H_rev=a.H_rev)
     return DATASETS[a.dataset].from_folder(ds, N=a.N, dN=a.dN)
 
@@ -215,7 +225,7 @@ def main(argv=None):
     np.random.seed(split_seed)
     dataset = make_dataset(a)
     train, test = dataset.random_split(a.validation_split)
-    horizon = (a.H_fwd, a.H_rev) if a.dataset == "scalar_horizon" else None
+    horizon = (a.H_fwd, a.H_rev) if a.dataset in HORIZON_KINDS else None
     shared = dict(num_units=a.num_units, num_layers=a.num_layers, activation=a.activation, softplus_beta=a.softplus_beta, loss=a.loss,
                   alpha=a.alpha, delta=a.delta, lr=a.lr, gamma=a.gamma, step_size=a.step_size, batch_size=a.batch_size, seed=a.seed,
                   horizon=horizon, device=a.device)

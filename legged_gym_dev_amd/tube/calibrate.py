@@ -2,13 +2,13 @@
 
 Score every row of a held-out calibration set with s = w - fw, take the ceil((n + 1) c)-th smallest score as an offset q, and use
 fw + q as the tube: on exchangeable data it covers with probability >= c, whatever the model learned.  The scores come from the
-entries that exist (predict, predict_levels, predict_windows, rollout_window); the order statistic is lg_select_kth, exact, per
+entries that exist (predict, predict_levels, predict_windows, predict_windows_levels, rollout_window); the order statistic is lg_select_kth, exact, per
 output column, per level and per step ahead.
 
     select_kth(values, ranks, keep=None)      the k-th smallest per batch row, on the device
     conformal_rank(n, coverage)               ceil((n + 1) c) in exact rational arithmetic
     Calibration                               offsets, ranks, provenance; save / load (calibration.json); apply / covers
-    calibrate_flat / calibrate_levels / calibrate_horizon      the three score layouts
+    calibrate_flat / calibrate_levels / calibrate_horizon / calibrate_horizon_levels      the four score layouts
 
 Per age and per trajectory, for the closed-loop roll-out of the flat kinds:
 
@@ -164,8 +164,12 @@ class Calibration:
     kind "flat":    parts one_step and rollout; offsets (2, n_coverages, out)
     kind "levels":  a level-conditioned model, level l calibrated to coverage l; offsets (2, n_levels, out); coverages are the levels
     kind "horizon": one offset per coverage and step ahead; offsets (n_coverages, H_fwd)
+    kind "horizon_levels": a level-conditioned one-shot model, level l calibrated to coverage l, one offset
+                    per level and step ahead; offsets (n_levels, H_fwd); coverages are the levels
     n: kept calibration rows; ranks[i] = conformal_rank(n, coverages[i]); provenance: run, checkpoint, dataset, data or the sim flags."""
-    KINDS = ("flat", "levels", "horizon")
+    KINDS = ("flat", "levels", "horizon", "horizon_levels")
+    WINDOW_KINDS = ("horizon", "horizon_levels")            # offsets (sets, H_fwd), no parts
+    LEVEL_KINDS = ("levels", "horizon_levels")              # the sets are levels, each calibrated to itself
 
     def __init__(self, kind, coverages, offsets, n, ranks, provenance=None):
         if kind not in self.KINDS:
@@ -175,9 +179,10 @@ class Calibration:
         self.offsets = torch.as_tensor(offsets, dtype=torch.float32).cpu()
         self.n, self.ranks = int(n), [int(r) for r in ranks]
         self.provenance = dict(provenance or {})
-        want = 2 if kind == "horizon" else 3
+        self.windowed = kind in self.WINDOW_KINDS
+        want = 2 if self.windowed else 3
         if self.offsets.dim() != want or self.offsets.shape[want - 2] != len(self.coverages) or len(self.ranks) != len(self.coverages) \
-                or (kind != "horizon" and self.offsets.shape[0] != len(PARTS)):
+                or (not self.windowed and self.offsets.shape[0] != len(PARTS)):
             raise ValueError(f"{kind}: offsets {tuple(self.offsets.shape)} do not fit {len(self.coverages)} coverages")
         if bool(torch.isnan(self.offsets).any()):
             bad = torch.isnan(self.offsets).nonzero()[0].tolist()
@@ -185,38 +190,47 @@ class Calibration:
 
     def set_name(self, idx):
         """The name of offsets[idx] for messages and printed lines."""
-        if self.kind == "horizon":
-            return f"coverage {self.coverages[idx[0]]}, step ahead {idx[1] + 1}"
-        return f"{PARTS[idx[0]]}, {'level' if self.kind == 'levels' else 'coverage'} {self.coverages[idx[1]]}, column {idx[2]}"
+        word = "level" if self.kind in self.LEVEL_KINDS else "coverage"
+        if self.windowed:
+            return f"{word} {self.coverages[idx[0]]}, step ahead {idx[1] + 1}"
+        return f"{PARTS[idx[0]]}, {word} {self.coverages[idx[1]]}, column {idx[2]}"
 
-    def index(self, coverage, level=None):
-        if self.kind == "levels":
+    def index(self, coverage=None, level=None):
+        """The set of `coverage`; on the level kinds `level` alone names it too (a level is its own coverage).  KeyError for a set
+        that was not calibrated."""
+        if self.kind in self.LEVEL_KINDS:
+            if coverage is None:
+                coverage = level
+            if coverage is None:
+                raise ValueError(f"a {self.kind} calibration needs the level (or its coverage)")
             if level is not None and abs(float(level) - float(coverage)) > 1e-9:
                 raise ValueError(f"level {level} is calibrated to coverage {level}, not {coverage}: a level-conditioned model's level is its coverage")
         elif level is not None:
             raise ValueError(f"a {self.kind} calibration has no levels")
+        elif coverage is None:
+            raise ValueError(f"a {self.kind} calibration needs the coverage")
         return _coverage_index(self.coverages, coverage)
 
-    def offset(self, coverage, level=None, part="one_step"):
-        """The offsets of one set: (out) for flat and levels, (H_fwd) for horizon."""
+    def offset(self, coverage=None, level=None, part="one_step"):
+        """The offsets of one set: (out) for flat and levels, (H_fwd) for horizon and horizon_levels."""
         i = self.index(coverage, level)
-        if self.kind == "horizon":
+        if self.windowed:
             return self.offsets[i]
         if part not in PARTS:
             raise ValueError(f"part {part!r}: one of {PARTS}")
         return self.offsets[PARTS.index(part), i]
 
-    def apply(self, fw, coverage, level=None, part="one_step"):
+    def apply(self, fw, coverage=None, level=None, part="one_step"):
         """fw + offset, the offset broadcast over the rows (fw (..., out), or (..., H_fwd) for horizon)."""
         return fw + self.offset(coverage, level, part).to(fw.device)
 
-    def covers(self, fw, w, coverage, level=None, part="one_step"):
+    def covers(self, fw, w, coverage=None, level=None, part="one_step"):
         """(w - fw) <= offset: the exact form of apply(fw) >= w, which can differ from it by an ulp of the sum."""
         return (w - fw) <= self.offset(coverage, level, part).to(fw.device)
 
     def to_json(self):
         return {"kind": self.kind, "coverages": self.coverages, "n": self.n, "ranks": self.ranks,
-                "offsets": _enc(self.offsets.tolist()), "parts": list(PARTS) if self.kind != "horizon" else None, **self.provenance}
+                "offsets": _enc(self.offsets.tolist()), "parts": None if self.windowed else list(PARTS), **self.provenance}
 
     def save(self, path):
         with open(path, "w") as f:
@@ -233,7 +247,7 @@ class Calibration:
         """One printed line per set: rank, n, offset."""
         out = []
         for idx in torch.cartesian_prod(*[torch.arange(s) for s in self.offsets.shape]).reshape(-1, self.offsets.dim()).tolist():
-            ci = idx[0] if self.kind == "horizon" else idx[1]
+            ci = idx[0] if self.windowed else idx[1]
             out.append(f"{self.set_name(idx)}: rank {self.ranks[ci]} of n {self.n}, offset {float(self.offsets[tuple(idx)])}")
         return out
 
@@ -285,6 +299,21 @@ def calibrate_horizon(fw, target, coverages):
     ranks = _ranks(W, coverages)
     q, _ = select_kth((target - fw).t(), torch.tensor(ranks))                  # (H_fwd, n_coverages)
     return Calibration("horizon", coverages, q.t(), W, ranks)
+
+
+def calibrate_horizon_levels(fw, target, levels):
+    """scalar_horizon_level: fw (windows, n_levels, H_fwd) from ONE predict_windows_levels launch on the window starts, target
+    (windows, H_fwd).  The scores target - fw are laid out (n_levels * H_fwd, windows), row (level, step) taking its level's rank:
+    one offset per level and step ahead, level l calibrated to coverage l."""
+    W, L, H = fw.shape
+    if len(levels) != L or tuple(target.shape) != (W, H):
+        raise ValueError(f"fw {tuple(fw.shape)} does not fit {len(levels)} levels and target {tuple(target.shape)}")
+    if L * H > 4096:
+        raise ValueError(f"{L} levels x {H} steps ahead = {L * H} score rows exceed the selection's 4096 batch rows: calibrate fewer levels at once")
+    ranks = _ranks(W, levels)
+    scores = (target[:, None, :] - fw).permute(1, 2, 0).reshape(L * H, W)
+    q, _ = select_kth(scores, torch.tensor(ranks).repeat_interleave(H)[:, None])
+    return Calibration("horizon_levels", levels, q.reshape(L, H), W, ranks)
 
 
 def default_path(run):

@@ -159,6 +159,7 @@ class ScalarHorizonTubeDataset:
     (w and z with their first sample, v with zeros).  Item (env, ind) -- ind drawn uniformly from [H_rev, T' - H_fwd - 1) -- is
     input [w[ind-H_rev:ind], z[ind], v[ind-H_rev:ind+H_fwd].flatten()] and target w[ind+1:ind+H_fwd+1].  As in the reference,
     the input does not hold the current error w[ind]."""
+    conditioned = False
 
     def __init__(self, w, z, v, H_fwd, H_rev, input_dim, output_dim):
         self.w, self.z, self.v = w, z, v
@@ -250,10 +251,24 @@ class LevelVectorTubeDataset(VectorTubeDataset):
         return cls(x, y, x.shape[1] + 1, y.shape[1])
 
 
+class LevelScalarHorizonTubeDataset(ScalarHorizonTubeDataset):
+    """ScalarHorizonTubeDataset's arrays for a level-conditioned one-shot tube: the model's item is the
+    window item plus one last column, the coverage level, so input_dim is the item width + 1.  The arrays hold no level: the trainer
+    draws one per row at every step, and the row's H_fwd outputs share it in the pinball loss."""
+    conditioned = True
+
+    @classmethod
+    def from_folder(cls, src, H_fwd=50, H_rev=10):
+        ds = ScalarHorizonTubeDataset.from_folder(src, H_fwd, H_rev)
+        return cls(ds.w, ds.z, ds.v, H_fwd, H_rev, ds.input_dim + 1, H_fwd)
+
+
 DATASETS = {"scalar": ScalarTubeDataset, "vector": VectorTubeDataset, "error_dynamics": ErrorDynamicsDataset,
             "scalar_horizon": ScalarHorizonTubeDataset, "scalar_level": LevelScalarTubeDataset,
-            "vector_level": LevelVectorTubeDataset}
-LEVEL_KINDS = {"scalar_level": "scalar", "vector_level": "vector"}     # conditioned kind -> the kind whose rows it has
+            "vector_level": LevelVectorTubeDataset, "scalar_horizon_level": LevelScalarHorizonTubeDataset}
+LEVEL_KINDS = {"scalar_level": "scalar", "vector_level": "vector"}     # conditioned flat kind -> the kind whose rows it has
+HORIZON_KINDS = ("scalar_horizon", "scalar_horizon_level")             # window kinds: no per-step rows, no closed loop
+HORIZON_LEVEL_KIND = "scalar_horizon_level"                            # the conditioned window kind (section 10.8)
 
 
 def sequences(kind, src, **window_args):
@@ -262,8 +277,8 @@ def sequences(kind, src, **window_args):
     model's input at step t and its target, the quantity one step ahead; a done row's target belongs to the next episode.
     Flat kinds only: the horizon dataset has no rows.  A level kind returns its base kind's rows (input_dim - 1 columns: the
     level column is the caller's to append, HipTubeModel.with_level)."""
-    if kind not in DATASETS or kind == "scalar_horizon":
-        raise ValueError(f"sequences: kind {kind!r} has no per-step rows; one of {[k for k in DATASETS if k != 'scalar_horizon']}")
+    if kind not in DATASETS or kind in HORIZON_KINDS:
+        raise ValueError(f"sequences: kind {kind!r} has no per-step rows; one of {[k for k in DATASETS if k not in HORIZON_KINDS]}")
     ds = _load(src)
     data, target = DATASETS[kind]._sequences(ds, **window_args)
     return (torch.from_numpy(np.ascontiguousarray(data)).float(), torch.from_numpy(np.ascontiguousarray(target)).float(),

@@ -125,9 +125,9 @@ def build_horizon(records, H_rev, device=None):
 def from_records(cls, records, N=1, dN=1, recursive=False, H_fwd=50, H_rev=10, mark_last_env=True, epoch_envs=None, device=None):
     """cls.from_folder's dataset from a record dict, holding device tensors: random_split, HipTubeTrainer.set_data and
     HipTubeSweep.set_data take it as it is (set_data passes device tensors through without a copy)."""
-    if cls is td.ScalarHorizonTubeDataset:
+    if cls in (td.ScalarHorizonTubeDataset, td.LevelScalarHorizonTubeDataset):
         w, z, v = build_horizon(records, H_rev, device)
-        return cls(w, z, v, H_fwd, H_rev, H_rev + z.shape[-1] + (H_rev + H_fwd) * v.shape[-1], H_fwd)
+        return cls(w, z, v, H_fwd, H_rev, H_rev + z.shape[-1] + (H_rev + H_fwd) * v.shape[-1] + int(cls.conditioned), H_fwd)
     if cls not in _KIND_OF:
         raise ValueError(f"from_records: {cls.__name__} has no device builder")
     x, y = build_rows(records, _KIND_OF[cls], N, dN, recursive and _KIND_OF[cls] == "scalar", True, mark_last_env, epoch_envs, device)

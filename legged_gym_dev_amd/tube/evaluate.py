@@ -82,6 +82,17 @@ def window_metrics(pred, target):
             "success_rate_by_step": cover.mean(dim=0).tolist()}
 
 
+def level_crossings(pred, levels):
+    """pred (count, n_levels, H_fwd) of a level-conditioned one-shot model, levels in any order: the share of (window, step ahead,
+    pair of adjacent levels in ascending order) where the prediction FALLS as the level rises -- 0 for a model whose bounds are
+    nested.  nan with fewer than two levels."""
+    order = torch.argsort(torch.as_tensor(levels, dtype=torch.float64))
+    p = pred[:, order.to(pred.device), :]
+    if p.shape[1] < 2:
+        return float("nan")
+    return float((p[:, 1:, :] < p[:, :-1, :]).double().mean())
+
+
 def trajectory_metrics(covered, done):
     """covered (E, T, out) bool, done (E, T): the fraction of envs whose every kept step is covered, per output column --
     the quantity a trajectory margin (tube/calibrate.py calibrate_trajectory) bounds.  An env without a kept step counts as covered."""

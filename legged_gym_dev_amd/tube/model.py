@@ -1,5 +1,6 @@
 """HipTubeModel: a trained tube MLP for inference only -- ``predict``, ``predict_windows``, ``rollout`` and
-``rollout_window`` on the HIP kernels, and ``predict_levels`` / ``with_level`` for a level-conditioned model.
+``rollout_window`` on the HIP kernels, and ``predict_levels`` / ``with_level`` for a level-conditioned model
+(``predict_windows_levels`` where it is a horizon model).
 
 It wraps the same ``lg_tube`` handle the trainer uses; the model's shape comes from the state dict, and what the state dict
 cannot say (activation, Softplus beta, the horizon) from the run's ``config.json`` (train_tube.py writes it) or from keywords.
@@ -10,6 +11,7 @@ import os
 
 import torch
 
+from .data import HORIZON_KINDS
 from .trainer import HipTubeTrainer
 
 CONFIG_NAME = "config.json"
@@ -36,7 +38,7 @@ def read_config(run_dir):
 class HipTubeModel:
     def __init__(self, state_dict, activation="relu", softplus_beta=1.0, horizon=None, device="cuda:0", level_input=False):
         """horizon: None, or (H_fwd, H_rev) for a ScalarHorizonTubeDataset model.  level_input: a level-conditioned model, whose
-        last input column is the coverage level (predict_levels, with_level)."""
+        last input column is the coverage level (predict_levels, with_level; with a horizon predict_windows_levels)."""
         I, O, U, L = shape_from_state_dict(state_dict)
         self._tr = HipTubeTrainer(I, O, num_units=U, num_layers=L, activation=activation, softplus_beta=softplus_beta,
                                   loss="scalar_level" if level_input else "scalar", alpha=0.5, batch_size=32,
@@ -59,7 +61,7 @@ class HipTubeModel:
             sd = torch.load(os.path.join(src, CHECKPOINTS[checkpoint]), map_location="cpu")
         else:
             sd = src
-        if horizon is None and cfg.get("dataset") == "scalar_horizon":
+        if horizon is None and cfg.get("dataset") in HORIZON_KINDS:
             horizon = (cfg["H_fwd"], cfg["H_rev"])
         return cls(sd, activation=activation or cfg.get("activation", "relu"),
                    softplus_beta=softplus_beta if softplus_beta is not None else cfg.get("softplus_beta", 1.0),
@@ -80,6 +82,9 @@ class HipTubeModel:
 
     def predict_windows(self, ds, env, start):
         return self._tr.predict_windows(ds, env, start)
+
+    def predict_windows_levels(self, ds, env, start, levels):
+        return self._tr.predict_windows_levels(ds, env, start, levels)
 
     def rollout(self, x, fb, reseed=None):
         return self._tr.rollout(x, fb, reseed)

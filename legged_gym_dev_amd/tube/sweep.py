@@ -12,7 +12,7 @@ import torch
 
 from .. import capi
 from ..lib import LeggedHipError, device_tensor, load
-from .trainer import LEVEL_LOSSES, LOSSES, _numel, initial_params, param_shapes
+from .trainer import LEVEL_LOSSES, LOSSES, _numel, check_window_dims, initial_params, param_shapes
 
 MEMBER_FIELDS = ("alpha", "delta", "activation", "softplus_beta", "lr", "gamma", "step_size", "seed",
                  "level_lo", "level_hi")                                                 # what members may differ in
@@ -155,6 +155,7 @@ class HipTubeSweep:
                 w, z, v = (t.to(self.device, torch.float32).contiguous() for t in (ds.w, ds.z, ds.v))
                 if (ds.H_fwd, ds.H_rev) != tuple(self.horizon):
                     raise ValueError("dataset horizon != sweep horizon")
+                check_window_dims(self.dims[0], self.horizon, z.shape[2], v.shape[2], self.level_input)
                 self._data[which] = (w, z, v)
                 self._call("set_data", which, C.c_void_p(w.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(v.data_ptr()),
                            w.shape[0], w.shape[1], z.shape[2], v.shape[2])

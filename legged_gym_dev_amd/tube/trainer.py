@@ -4,7 +4,8 @@ include/legged_hip.h).
 A step is two launches on the current stream -- fused forward / loss / backward over the minibatch, then the fixed-order gradient
 reduction, Adam and StepLR -- and nothing in it waits for the device.  Loss, lr and gradient norm of every step stay in a device
 log until ``read_log``.  A level-conditioned model (loss ``scalar_level`` / ``vector_level``) takes the
-coverage level as its last input column: ``eval_level``, ``predict_levels`` and ``read_levels`` are its own.  ``predict``, ``predict_windows``, ``rollout`` and ``rollout_window`` run the model as it stands (one launch
+coverage level as its last input column: ``eval_level``, ``predict_levels`` and ``read_levels`` are its own, and on a horizon
+dataset (section 10.8) ``predict_windows_levels``.  ``predict``, ``predict_windows``, ``rollout`` and ``rollout_window`` run the model as it stands (one launch
 each, the roll-outs included) and return device tensors.  There is no CPU fallback: without the library or a GPU the constructor raises.
 """
 import ctypes as C
@@ -24,12 +25,14 @@ LEVEL_LOSSES = ("scalar_level", "vector_level")     # level-conditioned: lg_tube
 def check_envelope(input_dim, output_dim, num_units, num_layers, activation="relu", final_activation=None, loss=None,
                    horizon=None, level_input=False, level_lo=0.0, level_hi=1.0):
     """The supported model envelope (the C side refuses the same); raises ValueError / NotImplementedError outside it.
-    level_input: the level-conditioned tube, with the loss, the horizon and the level range it is asked with."""
+    level_input: the level-conditioned tube, with the loss, the horizon and the level range it is asked with.  A conditioned
+    horizon model needs H_rev >= 1: the chosen edge of the envelope."""
     if level_input:
         if loss is not None and LOSSES.get(loss) == "mse":
             raise ValueError("level_input needs a tube loss (scalar or vector): the mse loss has no level")
-        if horizon is not None:
-            raise NotImplementedError("level_input with a horizon dataset is not supported: predict_windows has no place for a level")
+        if horizon is not None and horizon[1] < 1:
+            raise ValueError(f"level_input with a horizon dataset needs H_rev >= 1 (got {horizon[1]}): an item without a past error "
+                             "carries no error history; the flat level kinds serve that case")
         if input_dim < 2:
             raise ValueError(f"input_dim={input_dim}: with level_input it counts the level column and must be at least 2")
         if not 0.0 <= level_lo < level_hi <= 1.0:
@@ -46,6 +49,19 @@ def check_envelope(input_dim, output_dim, num_units, num_layers, activation="rel
         raise ValueError(f"input_dim={input_dim}: 1..{capi.TUBE_MAX_IN}")
     if not 1 <= output_dim <= capi.TUBE_MAX_OUT:
         raise ValueError(f"output_dim={output_dim}: 1..{capi.TUBE_MAX_OUT}")
+
+
+def window_input_dim(horizon, nz, m, level_input=False):
+    """Columns of a horizon model's item: H_rev + nz + (H_rev + H_fwd) m, plus the level column of a conditioned model."""
+    Hf, Hr = horizon
+    return Hr + nz + (Hr + Hf) * m + int(bool(level_input))
+
+
+def check_window_dims(input_dim, horizon, nz, m, level_input=False):
+    """ValueError unless arrays z (.., nz) and v (.., m) build items of the model's input_dim (the C side refuses the same)."""
+    if input_dim != window_input_dim(horizon, nz, m, level_input):
+        raise ValueError(f"input_dim {input_dim} != H_rev + nz + (H_rev + H_fwd) * m{' + 1 (the level column)' if level_input else ''} = "
+                         f"{window_input_dim(horizon, nz, m, level_input)} for H_fwd, H_rev = {tuple(horizon)}, nz = {nz}, m = {m}")
 
 
 def param_shapes(input_dim, output_dim, num_units, num_layers):
@@ -75,7 +91,8 @@ class HipTubeTrainer:
                  horizon=None, final_activation=None, device="cuda:0", level_lo=0.0, level_hi=1.0):
         """horizon: None for the row datasets, (H_fwd, H_rev) for ScalarHorizonTubeDataset.  loss "scalar_level" /
         "vector_level": the level-conditioned tube -- input_dim counts the level column (the last one), the data has
-        input_dim - 1 columns, every row of a step draws its level uniformly from [level_lo, level_hi), alpha is not read."""
+        input_dim - 1 columns, every row of a step draws its level uniformly from [level_lo, level_hi), alpha is not read.
+        With a horizon the window item gains the level as its last column and the row's H_fwd outputs share it in the loss."""
         if loss not in LOSSES:
             raise ValueError(f"loss {loss!r}: one of {tuple(LOSSES)}")
         self.level_input = loss in LEVEL_LOSSES
@@ -164,6 +181,7 @@ class HipTubeTrainer:
                 w, z, v = (t.to(self.device, torch.float32).contiguous() for t in (ds.w, ds.z, ds.v))
                 if (ds.H_fwd, ds.H_rev) != tuple(self.horizon):
                     raise ValueError("dataset horizon != trainer horizon")
+                check_window_dims(self.dims[0], self.horizon, z.shape[2], v.shape[2], self.level_input)
                 self._data[which] = (w, z, v)
                 self._call("set_data", which, C.c_void_p(w.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(v.data_ptr()),
                            w.shape[0], w.shape[1], z.shape[2], v.shape[2])
@@ -275,11 +293,8 @@ class HipTubeTrainer:
         self._keep = (x, rows)
         return out
 
-    def predict_windows(self, ds, env, start):
-        """The H_fwd predictions of the ScalarHorizonTubeDataset items (env[i], start[i]) of `ds` (w, z, v padded in front by
-        H_rev): a device tensor (count, H_fwd).  Every start must satisfy H_rev <= start and start + H_fwd <= T."""
-        if self.horizon is None:
-            raise ValueError("a flat model predicts rows: predict(x, rows)")
+    def _windows(self, ds, env, start):
+        """The checked arguments of a window query: (w, z, v, n, T, env, start) on the device."""
         Hf, Hr = self.horizon
         if (ds.H_fwd, ds.H_rev) != (Hf, Hr):
             raise ValueError("dataset horizon != model horizon")
@@ -287,8 +302,7 @@ class HipTubeTrainer:
         n, T = w.shape
         if z.shape[:2] != (n, T) or v.shape[:2] != (n, T):
             raise ValueError("w, z and v differ in envs or time steps")
-        if Hr + z.shape[2] + (Hr + Hf) * v.shape[2] != self.dims[0]:
-            raise ValueError(f"H_rev + nz + (H_rev + H_fwd) * m != input_dim {self.dims[0]}")
+        check_window_dims(self.dims[0], self.horizon, z.shape[2], v.shape[2], self.level_input)
         env = torch.as_tensor(env).to(self.device, torch.int32).contiguous().reshape(-1)
         start = torch.as_tensor(start).to(self.device, torch.int32).contiguous().reshape(-1)
         if env.numel() != start.numel() or env.numel() < 1:
@@ -297,11 +311,40 @@ class HipTubeTrainer:
             raise IndexError(f"env must lie in 0..{n - 1}")
         if int(start.min()) < Hr or int(start.max()) + Hf > T:
             raise IndexError(f"window out of range: need {Hr} <= start and start + {Hf} <= {T}")
-        out = torch.empty(env.numel(), Hf, device=self.device, dtype=torch.float32)
+        return w, z, v, n, T, env, start
+
+    def predict_windows(self, ds, env, start):
+        """The H_fwd predictions of the ScalarHorizonTubeDataset items (env[i], start[i]) of `ds` (w, z, v padded in front by
+        H_rev): a device tensor (count, H_fwd).  Every start must satisfy H_rev <= start and start + H_fwd <= T."""
+        if self.horizon is None:
+            raise ValueError("a flat model predicts rows: predict(x, rows)")
+        if self.level_input:
+            raise ValueError("predict_windows: the model is level-conditioned, a window holds no level: "
+                             "predict_windows_levels(ds, env, start, levels)")
+        w, z, v, n, T, env, start = self._windows(ds, env, start)
+        out = torch.empty(env.numel(), self.horizon[0], device=self.device, dtype=torch.float32)
         self._call("predict_windows", C.c_void_p(w.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(v.data_ptr()), n, T,
                    z.shape[2], v.shape[2], C.c_void_p(env.data_ptr()), C.c_void_p(start.data_ptr()), env.numel(),
                    C.c_void_p(out.data_ptr()))
         self._keep = (w, z, v, env, start)
+        return out
+
+    def predict_windows_levels(self, ds, env, start, levels):
+        """Level-conditioned horizon models: the H_fwd predictions of the items (env[i], start[i]) of `ds` at every level of
+        `levels` (1..64 values) in one launch, a device tensor (count, n_levels, H_fwd).  Entry [i, l] equals, bit for bit,
+        predict() of a flat conditioned model with these parameters on the item with levels[l] appended."""
+        self._need_level("predict_windows_levels")
+        if self.horizon is None:
+            raise ValueError("predict_windows_levels: not a horizon model; a flat model predicts rows: predict_levels(x, levels)")
+        levels = self._f32(torch.as_tensor(levels)).reshape(-1)
+        if not 1 <= levels.numel() <= capi.TUBE_MAX_LEVELS:
+            raise ValueError(f"{levels.numel()} levels: 1..{capi.TUBE_MAX_LEVELS}")
+        w, z, v, n, T, env, start = self._windows(ds, env, start)
+        out = torch.empty(env.numel(), levels.numel(), self.horizon[0], device=self.device, dtype=torch.float32)
+        self._call("predict_windows_levels", C.c_void_p(w.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(v.data_ptr()), n, T,
+                   z.shape[2], v.shape[2], C.c_void_p(env.data_ptr()), C.c_void_p(start.data_ptr()), env.numel(),
+                   C.c_void_p(levels.data_ptr()), levels.numel(), C.c_void_p(out.data_ptr()))
+        self._keep = (w, z, v, env, start, levels)
         return out
 
     def rollout(self, x, fb, reseed=None):
