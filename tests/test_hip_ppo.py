@@ -1,6 +1,11 @@
 """GPU parity of the HIP PPO learner (through the lg_ppo_* C-ABI) against the fp32 torch restatement
 of rsl_rl (oracle/ppo_torch.py): act/log-prob, GAE returns, minibatch gradients (MFMA GEMM
-forward/backward vs autograd), KL-adaptive lr + grad clip + Adam, full update."""
+forward/backward vs autograd), KL-adaptive lr + grad clip + Adam, full update.
+
+The gradient tests here update on the rollout's own parameters with 12 actions: importance ratio 1 and v_new = v_old, so every row is
+inside the surrogate clip and on the tie branch of the clipped value loss.  The other branches of the loss, value_loss_coef != 1,
+use_clipped_value_loss = False, 1 .. 16 actions and the second trip of the head kernels' tile loops are checked against float64, per
+head kernel, in tests/test_hip_ppo_loss.py (inputs: tests/ppo_loss_ref.py, their conditions: tests/test_ppo_loss_host.py)."""
 import numpy as np
 import pytest
 import torch
@@ -733,7 +738,8 @@ def test_clipped_surrogate_and_kl_known_answers_through_the_library(sign, expect
     """The known-answer cases that pin the torch restatement (tests/test_ppo_oracle.py) through the LIBRARY's loss path: three rows whose
     importance ratios are 0.7, 1.0, 1.3 (the stored log-prob shifted by -ln r), advantages +1 (then -1), clip 0.2:
     mean surrogate = mean max(-A r, -A clip(r, 0.8, 1.2)); the KL of a policy with itself = sum_a ln(1 + 1e-5) (rsl_rl's epsilon inside the
-    log); value loss 0 when returns = values."""
+    log); value loss 0 when returns = values.  Three loss statistics on the k_head_fused<32> path; the gradients of these branches, on
+    every head kernel, are in tests/test_hip_ppo_loss.py."""
     N, O, A, T = 3, 48, 12, 1
     alg = dict(ALG, num_mini_batches=1, num_learning_epochs=1)
     pol = dict(POLICY, actor_hidden_dims=[64, 32], critic_hidden_dims=[64, 32])

@@ -1,0 +1,89 @@
+"""The PPO minibatch loss of the HIP learner against float64, on every head kernel, clip regime and action count.
+
+The loss exists four times in legged_gym_dev_amd/csrc/ppo_kernels.hip (k_loss after the head GEMMs, k_head_fused<32>,
+k_head_fused<64>, k_head_net<128, 12 | 16> + k_head_finish<128>); lg_ppo_minibatch_backward picks one by activation, depth and
+last hidden widths (tests/ppo_loss_ref.py: PATHS / CASES name the path each case takes).  The gradient tests of
+tests/test_hip_ppo.py update on the rollout's own parameters -- ratio 1, v_new = v_old, A = 12 -- so they sit on the tie branch
+of the clipped value loss and inside the surrogate clip.  Here the storage is written directly with rows steered to a table of
+(ratio, advantage, v_new - v_old, v_new - return) targets, which tests/test_ppo_loss_host.py shows to keep every row off every
+branch boundary and to cover all six (surrogate, value) regime pairs; value_loss_coef = 0.5; num_actions 1 .. 16; row counts on
+both sides of the 64-row tile, of k_loss's 256-row block and of a full trip of the capped persistent grids (192 / 384 workgroups).
+
+Compared against oracle.ppo_torch.PPO.minibatch_loss on a float64 model and bit-identical inputs: every parameter gradient
+(the bands of tests/test_hip_ppo.py on the whole vector, and the relative-norm bound again on each head / last-hidden-bias /
+first-layer block and on std), the KL sum, and the loss statistics after the optimiser step.  N = 1 (R = 1, one minibatch) is
+accepted by lg_ppo_create, so the matrix runs as listed."""
+import pytest
+import torch
+
+from tests import ppo_loss_ref as plr
+
+pytestmark = pytest.mark.gpu
+
+_STORAGE = ("obs", "actions", "values", "advantages", "returns", "log_prob", "mu")
+
+
+def _run(case, alg, R, mb):
+    """One lg_ppo_minibatch_backward + lg_ppo_minibatch_step on the case's storage -> (what the library computed, in the shape
+    ppo_loss_ref.reference() returns it; the storage rows of the minibatch)."""
+    from legged_gym_dev_amd.rl.ppo import HipPPO
+    m = case["meta"]
+    N = R * alg["num_mini_batches"]
+    policy = {"actor_hidden_dims": m["hidden"], "critic_hidden_dims": m["critic_hidden"], "activation": m["activation"],
+              "init_noise_std": 1.0}
+    hip = HipPPO(N, m["O"], None, m["A"], policy, alg, 1, device="cuda:0", seed=3)
+    try:
+        assert set(hip.param_views) == set(case["params"])
+        for k, v in case["params"].items():
+            hip.param_views[k].copy_(v)
+        hip.params_changed()
+        for k in _STORAGE:
+            hip.t[k].copy_(case[k].reshape(hip.t[k].shape))
+        hip.t["sigma"].copy_(case["sigma"])
+        hip._call("begin_update")
+        hip._call("minibatch_backward", 0, mb)
+        torch.cuda.synchronize()
+        rows = hip.t["perm"][mb * R:(mb + 1) * R].long().cpu()
+        got = {"grads": {k: v.detach().cpu().clone() for k, v in hip.grad_views.items()},
+               "kl": float(hip.t["grads"][hip.num_params]) / R}
+        hip._call("minibatch_step")
+        torch.cuda.synchronize()
+        st = hip.stats()
+        assert st["n_updates"] == 1.0
+        got["value_loss"] = st["value_loss_sum"] / st["n_updates"]
+        got["surrogate_loss"] = st["surrogate_loss_sum"] / st["n_updates"]
+        return got, rows
+    finally:
+        hip.close()
+
+
+@pytest.mark.parametrize("c", plr.CASES, ids=plr.case_id)
+def test_loss_gradients_kl_and_statistics_match_float64(c):
+    case, alg = plr.build_for(c), plr.alg_for(c)
+    R, mb = c[6], c[8]
+    got, rows = _run(case, alg, R, mb)
+    assert sorted(rows.tolist()) == list(range(R)) or alg["num_mini_batches"] > 1
+    ref = plr.reference(case, alg, rows)
+    assert list(got["grads"]) == list(ref["grads"])
+    for k, g in got["grads"].items():
+        assert bool(torch.isfinite(g).all()), k
+    errs = plr.band_errors(got, ref, case)
+    print("ppo_loss_errors", plr.case_id(c), {k: "%.3g/%.3g" % v for k, v in errs.items()})
+    over = {k: v for k, v in errs.items() if not v[0] <= v[1]}
+    assert not over, over
+
+
+@pytest.mark.parametrize("label", plr.LABELS)
+def test_known_answers_when_neither_loss_has_a_gradient(label):
+    """Every row surrogate-clipped, with a value loss that is clipped, outside the clip range and the larger: d loss / d log-prob
+    is 0 * ratio / R and d loss / d value is 0, so every actor and critic weight and bias gradient is EXACTLY zero, and
+    d loss / d std[a] = -entropy_coef / std[a] (a sum of R equal terms entropy_coef / (R std))."""
+    hidden, critic, act = plr.PATHS[label]
+    A, R = (16 if label == "net128_16" else 12), 193
+    case = plr.single_regime_case(8, A, hidden, act, R, 11, critic)
+    got, _ = _run(case, plr.ALG, R, 0)
+    for k, g in got["grads"].items():
+        if k == "std":
+            torch.testing.assert_close(g.double(), -plr.ALG["entropy_coef"] / case["params"]["std"].double(), rtol=1e-5, atol=0)
+        else:
+            assert torch.equal(g, torch.zeros_like(g)), (k, float(g.abs().max()))
