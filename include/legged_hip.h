@@ -736,6 +736,58 @@ int lg_select_kth_grouped(const float *values, int64_t ld, int32_t B, int64_t n,
                           const int64_t *cov_num, const int64_t *cov_den, int32_t R, float *out, int64_t *counts, int64_t *ranks,
                           void *workspace, void *stream);
 
+/* ------------------------------------------------------------------ plans against a tube: score B plans
+ * -- a start z0 and N inputs of the SingleInt2D ROM -- against a one-shot horizon tube, and track B plans on the ROM-on-ROM model, one
+ * launch each.  The evaluation step of a planner; no optimiser is part of it.  Reference lines: trajopt/tube_trajopt.py ("TT"),
+ * deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.py ("MT"), trajopt/rom_dynamics.py ("RD"). */
+#define LG_PLAN_MAX_N 64
+#define LG_PLAN_MAX_OBS 8
+#define LG_PLAN_TUBE_NN 0                          /* the one-shot MLP of a horizon lg_tube handle (TT:561-568, tube_dyn "NN_oneshot") */
+#define LG_PLAN_TUBE_L1 1                          /* scaling (|vx| + |vy|)                                      (TT:489-499) */
+#define LG_PLAN_TUBE_L2 2                          /* scaling (vx^2 + vy^2)                                      (TT:502-512) */
+#define LG_PLAN_TUBE_L1_ROLLING 3                  /* mean of the last min(window_size, k + 1) l1 values         (TT:515-526) */
+#define LG_PLAN_TUBE_L2_ROLLING 4                  /* the same of the l2 values                                  (TT:529-540) */
+typedef struct lg_plan_problem {                   /* one problem for every plan of a call (TT:11-21 problem_dict, TT:460 solve_tube) */
+    int32_t N /*nodes after the start: 1..LG_PLAN_MAX_N*/, H_rev /*past steps of the tube item*/, n_obs /*0..LG_PLAN_MAX_OBS*/;
+    int32_t tube_kind /*LG_PLAN_TUBE_**/, window_size /*rolling kinds: >= 1*/, _pad;
+    float dt /*ROM step, > 0*/, scaling /*analytic kinds*/, w_max, Qw;
+    float obs_c[LG_PLAN_MAX_OBS][2], obs_r[LG_PLAN_MAX_OBS], goal[2];
+    float Q[4], Qf[4], R[4];                       /* 2 x 2, row-major; each quadratic is sum((d @ M) * d) (TT:41-56) */
+    float rom_z_min[2], rom_z_max[2], rom_v_min[2], rom_v_max[2];
+} lg_plan_problem;
+/* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error: N outside 1..64, n_obs outside 0..8, dt <= 0, a negative
+ * radius, an unknown tube_kind, window_size < 1 on a rolling kind, the NN kind without a handle, a handle that is not a horizon
+ * handle or whose H_fwd != N, nz != 0 (input_dim != H_rev + 2 (H_rev + N) [+ 1]) or H_rev differs from the problem's, has_level
+ * given on an unconditioned handle or missing on a conditioned one.  tube may be NULL for the analytic kinds (it is then not read). */
+int lg_plan_check(const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level);
+/* Score B plans in one launch (k_plan_score, 32 plans per 256-thread workgroup).  DEVICE pointers: z0 (B, 2), v (B, N, 2); e
+ * (B, H_rev) past error norms, v_prev (B, H_rev, 2), w0 (B) the tube at node 0 -- each may be NULL = zeros; offset (N) a calibration
+ * offset per step ahead or NULL.  level is read on a level_input handle only (has_level must say so).
+ * Tube: fw (N) = MLP([e, v_prev.flatten(), v.flatten(), (level)]) -- the ScalarHorizonTubeDataset item at start = H_rev of w = e,
+ * v = cat(v_prev, v), gathered on chip; it equals lg_tube_predict_windows (lg_tube_predict_windows_levels) on those arrays bit for
+ * bit -- or the analytic kind.  The reference flattens v column-major (TT:563), not the order its dataset trained on; the dataset's
+ * order is used here.  Nodes: w[0] = w0, w[k+1] = fw[k] + offset[k]; z[0] = z0, z[k+1] = z[k] + dt v[k] (RD:192, one rounding per
+ * op).  g[i, k] = |z_k - c_i|^2 - (r_i + w_k)^2 (TT:59-62,73).  cost = sum_k<N (z_k - goal) Q (z_k - goal)' + the same with Qf at
+ * node N + sum v_k R v_k' + Qw sum w_k^2 (TT:206-212), one chain: nodes ascending, state, input, tube term per node.
+ * Outputs (DEVICE): cost (B); min_clear (B) = min g, +inf without obstacles; worst_node (B) int32, the first node that attains it
+ * (-1 without obstacles); n_viol (B, 4) int32: nodes with some g < 0, steps with v outside rom_v_min/max, nodes with z outside
+ * rom_z_min/max, nodes with w > w_max; fw (B, N), z (B, N+1, 2), w (B, N+1) optional (NULL = not written).
+ * A plan's outputs do not depend on B or on its place in the batch; no atomics.  -1 as lg_plan_check, for B < 1 or a missing array.
+ * Every shape of the envelope fits the kernel's dynamic LDS (checked where the kernel is compiled). */
+int lg_plan_score(lg_tube *tube, const lg_plan_problem *prob, const float *z0, const float *v, const float *e, const float *v_prev,
+                  const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *cost, float *min_clear,
+                  int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, void *stream);
+/* Track B prescribed plans on the simulator's DoubleInt2D model under its DoubleSingleTracking law in one launch (k_plan_track, one
+ * lane per plan; the loop of MT:75-88 at S = 1).  Kp, Kd, the velocity / acceleration bounds and the model dt are the handle's; its
+ * generator state and buffers are neither read nor written.  DEVICE: z (B, N+1, 2), v (B, N, 2), x0 (B, 4) or NULL = (z[0], 0, 0).
+ * S model steps per node, 1..8, refused unless |S model_dt - rom_dt| <= 1e-6 rom_dt.  Per node t and substep s the reference point
+ * is z[t] + (z[t+1] - z[t]) ((s model_dt) / rom_dt) (get_trajectory's interpolation, RD:607-612; z[t] at S = 1), the feed-forward
+ * v[min(t+1, N-1)] (MT:80), the action the controller's on (x, ref, ff) (MT:81, controllers.py:87-92), then x = f(x, a) (RD:224-225).
+ * Outputs (DEVICE): pz_x (B, N+1, 2); w_true (B, N+1) = |pz_x - z| as lg_tube_rows_build takes it; x (B, N+1, 4) and
+ * u (B, N S, 2) optional.  A plan's outputs equal, bit for bit, the same steps made one at a time with lg_romsim_policy. */
+int lg_plan_track(lg_romsim *sim, const float *z, const float *v, const float *x0, int64_t B, int32_t N, int32_t S, float rom_dt,
+                  float *pz_x, float *w_true, float *x, float *u);
+
 #ifdef __cplusplus
 }
 #endif

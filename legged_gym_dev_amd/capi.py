@@ -332,6 +332,28 @@ def declare_select_api(lib):
     lib.lg_select_kth_grouped.argtypes = [vp, i64, i32, i64, vp, i32, C.POINTER(i64), C.POINTER(i64), i32, vp, vp, vp, vp, vp]
 
 
+PLAN_MAX_N, PLAN_MAX_OBS = 64, 8                                # LG_PLAN_MAX_*
+PLAN_TUBE = {"nn": 0, "l1": 1, "l2": 2, "l1_rolling": 3, "l2_rolling": 4}     # LG_PLAN_TUBE_*
+
+
+class lg_plan_problem(C.Structure):
+    _fields_ = [
+        ("N", i32), ("H_rev", i32), ("n_obs", i32), ("tube_kind", i32), ("window_size", i32), ("_pad", i32),
+        ("dt", f32), ("scaling", f32), ("w_max", f32), ("Qw", f32),
+        ("obs_c", (f32 * 2) * 8), ("obs_r", f32 * 8), ("goal", f32 * 2),
+        ("Q", f32 * 4), ("Qf", f32 * 4), ("R", f32 * 4),
+        ("rom_z_min", f32 * 2), ("rom_z_max", f32 * 2), ("rom_v_min", f32 * 2), ("rom_v_max", f32 * 2)]
+
+
+def declare_plan_api(lib):
+    vp = C.c_void_p
+    if not hasattr(lib, "lg_plan_score"):          # an A/B library (LG_HIP_LIB) built before the plan entries
+        return
+    lib.lg_plan_check.argtypes = [C.POINTER(lg_plan_problem), vp, i32]
+    lib.lg_plan_score.argtypes = [vp, C.POINTER(lg_plan_problem), vp, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.lg_plan_track.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp]
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p

@@ -1,6 +1,7 @@
 // C-ABI (include/legged_hip.h, lg_romsim_*) of the ROM-on-ROM simulator: buffers in HBM, the DevParams the generator laws of
 // lg_traj.h read, the Philox epoch, and the launches of romsim_kernels.hip.  Nothing here waits for the device except
 // lg_romsim_inject_status and lg_romsim_destroy.
+// lg_plan_track: prescribed plans tracked under the handle's law and bounds (k_plan_track).
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -15,6 +16,8 @@ void romsimk_step(const RomSimDev *D, int64_t epoch, const float *actions, hipSt
 void romsimk_policy(const RomSimDev *D, const float *obs, float *out, int64_t rows, hipStream_t st);
 void romsimk_collect(const RomSimDev *D, int64_t epoch, int construct, int T, int max_sub, float *z, float *v, float *pz,
                      uint8_t *done, float *x, hipStream_t st);
+void romsimk_plan_track(const RomSimDev *D, const float *z, const float *v, const float *x0, int64_t B, int N, int S, float rom_dt,
+                        float *pz, float *wt, float *x, float *u, hipStream_t st);
 }
 
 struct lg_romsim {
@@ -208,6 +211,22 @@ int lg_romsim_collect(lg_romsim *p, int32_t T, float *z, float *v, float *pz_x, 
     romsimk_collect(&p->dev, p->epoch, !p->constructed, T, p->max_sub, z, v, pz_x, done, x, p->stream);
     p->constructed = 1;
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_romsim_collect: launch failed"), -3);
+}
+
+// DESIGN.md section 10.9.  The handle's epoch, generator state and buffers are not touched.
+int lg_plan_track(lg_romsim *p, const float *z, const float *v, const float *x0, int64_t B, int32_t N, int32_t S, float rom_dt,
+                  float *pz_x, float *w_true, float *x, float *u) {
+    if (B < 1 || B > INT32_MAX) { lg_set_error("lg_plan_track: B must be 1..2^31-1"); return -1; }
+    if (N < 1 || N > LG_PLAN_MAX_N) { lg_set_error("lg_plan_track: N must be 1.." + std::to_string(LG_PLAN_MAX_N)); return -1; }
+    if (S < 1 || S > 8) { lg_set_error("lg_plan_track: S must be 1..8"); return -1; }
+    if (!(rom_dt > 0.f) || !(std::fabs((double)S * (double)p->cfg.model_dt - (double)rom_dt) <= 1e-6 * (double)rom_dt)) {
+        lg_set_error("lg_plan_track: S * model_dt = " + std::to_string(S) + " * " + std::to_string(p->cfg.model_dt) +
+                     " differs from rom_dt = " + std::to_string(rom_dt) + " (the ROM step must be a whole number S of model steps)");
+        return -1;
+    }
+    if (!z || !v || !pz_x || !w_true) { lg_set_error("lg_plan_track: missing array (z, v, pz_x and w_true are required)"); return -1; }
+    romsimk_plan_track(&p->dev, z, v, x0, B, N, S, rom_dt, pz_x, w_true, x, u, p->stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_track: launch failed"), -3);
 }
 
 }  // extern "C"

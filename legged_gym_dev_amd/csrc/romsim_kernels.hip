@@ -228,7 +228,60 @@ __global__ __launch_bounds__(LG_RS_LANES) void k_romsim_collect(RomSimDev D, int
     rs_store(D, i, w, vw, x, a, o);
 }
 
+// Track B prescribed plans: the loop of deep_tube_learning/evaluation/
+// evaluate_tube_simple_oneshot_on_mpc_traj.py:75-88 ("MT") with S model steps per node.  One lane per plan, as k_romsim_collect has
+// one per env; the law is rs_controller and the model the DoubleInt2D.f lines of rs_env_step, one rounding per op.  Nothing of the
+// simulator's own state is read or written: D supplies Kp, Kd, the bounds and the model dt.
+__global__ __launch_bounds__(LG_RS_LANES) void k_plan_track(RomSimDev D, const float *__restrict__ z, const float *__restrict__ v,
+                                                            const float *__restrict__ x0, int64_t B, int N, int S, float rom_dt,
+                                                            float *__restrict__ pz, float *__restrict__ wt, float *__restrict__ xo,
+                                                            float *__restrict__ uo) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * LG_RS_LANES + threadIdx.x;
+    if (i >= B) return;
+    const float *zi = z + i * (N + 1) * 2, *vi = v + i * N * 2;
+    float x[4], o[LG_RS_NOBS], a[2];
+    if (x0) {
+#pragma unroll
+        for (int d = 0; d < 4; ++d) x[d] = x0[i * 4 + d];
+    } else { x[0] = zi[0]; x[1] = zi[1]; x[2] = 0.0f; x[3] = 0.0f; }
+    const int64_t r1 = i * (N + 1);
+    for (int t = 0; t <= N; ++t) {
+        // the record of node t: proj_z (MT:88) and the error norm (MT:90), sqrtf of the squares summed in column order
+        const float ex = x[0] - zi[2 * t], ey = x[1] - zi[2 * t + 1];
+        float s2 = 0.0f;
+        s2 = s2 + ex * ex; s2 = s2 + ey * ey;
+        pz[(r1 + t) * 2] = x[0]; pz[(r1 + t) * 2 + 1] = x[1];
+        wt[r1 + t] = sqrtf(s2);
+        if (xo) {
+#pragma unroll
+            for (int d = 0; d < 4; ++d) xo[(r1 + t) * 4 + d] = x[d];
+        }
+        if (t == N) break;
+        const int tf = t + 1 < N ? t + 1 : N - 1;                   // MT:80
+        const float za[2] = {zi[2 * t], zi[2 * t + 1]}, zb[2] = {zi[2 * t + 2], zi[2 * t + 3]};
+        for (int s = 0; s < S; ++s) {
+            const float frac = ((float)s * D.dt) / rom_dt;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) o[d] = x[d];
+            o[4] = za[0] + (zb[0] - za[0]) * frac; o[5] = za[1] + (zb[1] - za[1]) * frac;
+            o[6] = vi[2 * tf]; o[7] = vi[2 * tf + 1];
+            rs_controller(D, o, a);                                 // MT:81
+            // DoubleInt2D.f (RD:224-225), as rs_env_step writes it out
+            const float px = x[0] + D.dt * x[2], py = x[1] + D.dt * x[3];
+            x[2] = x[2] + D.dt * a[0]; x[3] = x[3] + D.dt * a[1];
+            x[0] = px; x[1] = py;
+            if (uo) { uo[(i * N * S + (int64_t)t * S + s) * 2] = a[0]; uo[(i * N * S + (int64_t)t * S + s) * 2 + 1] = a[1]; }
+        }
+    }
+}
+
 extern "C" {
+void romsimk_plan_track(const RomSimDev *D, const float *z, const float *v, const float *x0, int64_t B, int N, int S, float rom_dt,
+                        float *pz, float *wt, float *x, float *u, hipStream_t st) {
+    hipLaunchKernelGGL(k_plan_track, dim3((unsigned)((B + LG_RS_LANES - 1) / LG_RS_LANES)), dim3(LG_RS_LANES), 0, st, *D, z, v, x0, B, N,
+                       S, rom_dt, pz, wt, x, u);
+}
 void romsimk_reset(const RomSimDev *D, int64_t epoch, int construct, hipStream_t st) {
     hipLaunchKernelGGL(k_romsim_reset, dim3((D->n + LG_RS_LANES - 1) / LG_RS_LANES), dim3(LG_RS_LANES), 0, st, *D, epoch, construct);
 }

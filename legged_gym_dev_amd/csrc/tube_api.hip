@@ -2,6 +2,7 @@
 // permutation, the two launches of a training step, the eval launch, and the inference entries: predict, window prediction and
 // the closed-loop roll-outs, single-tap and windowed, and the level entries of a level-conditioned model, flat or horizon (tube_kernels.hip).  lg_tube_sweep_*: K such trainers of one shape on one
 // dataset, stepped by the same two launches with the members along grid y.
+// lg_plan_check / lg_plan_score: plans scored against a one-shot horizon handle or an analytic tube (k_plan_score).
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -38,6 +39,9 @@ void tubek_predict(const TubeDev *D, const float *x, const float *y, const float
 void tubek_rollout(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed, float *o, hipStream_t s);
 void tubek_rollout_window(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, int taps, int dN, int stride,
                           const uint8_t *reseed, float *o, hipStream_t s);
+int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
+                         const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
+                         float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, hipStream_t s);
 }
 
 struct TubeCaps {                       // rows that a model's data-sized buffers hold
@@ -399,6 +403,52 @@ int lg_tube_rollout_window(lg_tube *p, const float *x, int64_t n_seq, int32_t T,
     if (e) { lg_set_error(std::string("lg_tube_rollout_window: ") + e); return -1; }
     tubek_rollout_window(&p->dev, x, n_seq, T, fb, taps, dN, taps > 1 ? stride : D.in_dim, reseed, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_rollout_window: launch failed"), -3);
+}
+
+// ---------------------------------------------------------------- plans against a tube
+// why a problem, with the handle it is asked with, lies outside the envelope; empty inside it
+static std::string plan_reason(const lg_plan_problem *q, const lg_tube *t, int32_t has_level) {
+    if (q->N < 1 || q->N > LG_PLAN_MAX_N) return "N = " + std::to_string(q->N) + " must be 1.." + std::to_string(LG_PLAN_MAX_N);
+    if (q->n_obs < 0 || q->n_obs > LG_PLAN_MAX_OBS) return "n_obs = " + std::to_string(q->n_obs) + " must be 0.." + std::to_string(LG_PLAN_MAX_OBS);
+    if (!(q->dt > 0.f)) return "dt must be positive";
+    for (int i = 0; i < q->n_obs; ++i)
+        if (!(q->obs_r[i] >= 0.f)) return "obs_r[" + std::to_string(i) + "] is negative";
+    if (q->tube_kind < LG_PLAN_TUBE_NN || q->tube_kind > LG_PLAN_TUBE_L2_ROLLING) return "tube_kind must be nn (0), l1, l2, l1_rolling or l2_rolling (1..4)";
+    if ((q->tube_kind == LG_PLAN_TUBE_L1_ROLLING || q->tube_kind == LG_PLAN_TUBE_L2_ROLLING) && q->window_size < 1)
+        return "window_size must be at least 1 for a rolling tube_kind";
+    if (q->tube_kind != LG_PLAN_TUBE_NN) return has_level ? "level is given, but an analytic tube_kind has none" : "";
+    if (!t) return "tube_kind nn needs a tube handle";
+    const TubeDev &D = t->dev;
+    if (!D.horizon) return "the tube handle is not a horizon handle (lg_tube_cfg.horizon): a plan is scored by a one-shot tube";
+    if (D.H_fwd != q->N) return "the handle's H_fwd = " + std::to_string(D.H_fwd) + " differs from N = " + std::to_string(q->N);
+    if (D.H_rev != q->H_rev) return "the handle's H_rev = " + std::to_string(D.H_rev) + " differs from the problem's H_rev = " + std::to_string(q->H_rev);
+    if (window_dim(D, 0, 2) != D.in_dim)
+        return "nz must be 0: the handle's input_dim = " + std::to_string(D.in_dim) + " is not H_rev + 2 (H_rev + H_fwd)" +
+               (D.level_input ? " + 1" : "") + " (the ROM is SingleInt2D: no state columns past the position)";
+    if (has_level && !D.level_input) return "level is given, but the handle is not level-conditioned (lg_tube_cfg.level_input)";
+    if (!has_level && D.level_input) return "level is missing: the handle is level-conditioned (lg_tube_cfg.level_input)";
+    return "";
+}
+
+int lg_plan_check(const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level) {
+    const std::string e = plan_reason(prob, tube, has_level);
+    if (!e.empty()) { lg_set_error("lg_plan: " + e); return -1; }
+    return 0;
+}
+
+int lg_plan_score(lg_tube *tube, const lg_plan_problem *prob, const float *z0, const float *v, const float *e, const float *v_prev,
+                  const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *cost, float *min_clear,
+                  int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, void *stream) {
+    if (lg_plan_check(prob, tube, has_level)) return -1;
+    if (B < 1 || B > INT32_MAX) { lg_set_error("lg_plan_score: B must be 1..2^31-1"); return -1; }
+    if (!z0 || !v || !cost || !min_clear || !worst_node || !n_viol) {
+        lg_set_error("lg_plan_score: missing array (z0, v, cost, min_clear, worst_node and n_viol are required)"); return -1;
+    }
+    const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
+    const int64_t rc = tubek_plan_score(nn ? &tube->dev : nullptr, prob, z0, v, e, v_prev, w0, offset, has_level ? level : 0.f, B, cost,
+                                        min_clear, worst_node, n_viol, fw, z, w, (hipStream_t)stream);
+    if (rc < 0) { lg_set_error("lg_plan_score: hipFuncSetAttribute failed"); return -2; }
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_score: launch failed"), -3);
 }
 
 // ---------------------------------------------------------------- sweep: K trainers of one shape on one dataset

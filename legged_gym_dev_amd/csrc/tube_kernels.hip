@@ -12,7 +12,12 @@
 // set -- on flat rows and on horizon windows alike (section 10.8) -- and k_tube_predict_levels evaluates many levels of a row, or
 // of a window, in one launch.
 // Plain fp32 FMA over LDS tiles: at 16..128 units the matrices are far too small for MFMA to matter.
+#include <cstring>
+
 #include "tube_device.h"
+
+// lg_plan_problem.R, read before R becomes the tile's row count below
+__device__ __forceinline__ const float *plan_input_cost(const lg_plan_problem &p) { return p.R; }
 
 #define R LG_TUBE_ROWS
 #define NT LG_TUBE_THREADS
@@ -355,6 +360,129 @@ __global__ void __launch_bounds__(NT) k_tube_predict_levels(TubeDev D, TubeGathe
     }
 }
 
+// ------------------------------------------------------------------ plans against a tube
+// Score R plans per workgroup: the one-shot tube of every plan through tube_layer (or an analytic tube), then one lane per plan
+// walks the plan's nodes -- ROM state, tube, clearance, cost, counts -- in one fixed-order chain.  The reference's definitions:
+// trajopt/tube_trajopt.py ("TT") oneshot_nn_tube_dyn :561-568, the analytic tubes :489-540, the obstacle constraint :59-97, the
+// objective :41-56,206-212; SingleInt2D.f is trajopt/rom_dynamics.py:192.
+struct PlanDev {                        // passed by value
+    lg_plan_problem p;
+    const float *z0, *v, *e, *v_prev, *w0, *offset;
+    float *cost, *min_clear, *fw, *z, *w;
+    int32_t *worst_node, *n_viol;
+    float level;
+    int Hr, I;                          // columns of the tile's item: Hr past errors, 2 (Hr + N) inputs, (level); analytic kinds: Hr = 0
+};
+
+#define PLAN_ZS(N) ((((N) + 1) * 3) | 1)    // floats of a plan's (z, w) nodes in LDS: odd, so that the lanes' rows fall on different banks
+
+// sum((d @ M) * d) of a 2-vector, M row-major (TT:56)
+__device__ __forceinline__ float plan_quad(const float *M, float d0, float d1) {
+#pragma clang fp contract(off)
+    return (d0 * M[0] + d1 * M[2]) * d0 + (d0 * M[1] + d1 * M[3]) * d1;
+}
+
+// Dynamic LDS: X (R, I) the items -- for an analytic kind the plan's inputs alone --, H0, H1 (R, U) (NN kind), FW (R, N), ZW (R, PLAN_ZS).
+__global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t count) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
+    const bool nn = P.p.tube_kind == LG_PLAN_TUBE_NN;
+    const int U = nn ? D.units : 0, L = D.layers, ZS = PLAN_ZS(N);
+    const int64_t base = (int64_t)blockIdx.x * R;
+    const int nr = (int)(count - base < R ? count - base : R);
+    float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N;
+    // the ScalarHorizonTubeDataset item at start = H_rev of w = e, z = none, v = cat(v_prev, v), straight into the tile
+    for (int e = tid; e < R * I; e += NT) {
+        const int r = e / I, c = e - r * I;
+        float x = 0.f;
+        if (r < nr) {
+            const int64_t b = base + r;
+            if (c < Hr) x = P.e ? P.e[b * Hr + c] : 0.f;
+            else if (c < Hr + 2 * (Hr + N)) {
+                const int q = c - Hr, tt = q >> 1, d = q & 1;
+                if (tt < Hr) x = P.v_prev ? P.v_prev[(b * Hr + tt) * 2 + d] : 0.f;
+                else x = P.v[(b * N + (tt - Hr)) * 2 + d];
+            } else x = P.level;
+        }
+        X[e] = x;
+    }
+    __syncthreads();
+    if (nn) {
+        const float *in = X;
+        for (int li = 0; li < L; ++li) {
+            float *out = li & 1 ? H1 : H0;
+            tube_layer<R, RB, NT, false>(tid, D.din[li], U, in, D.wt + D.off_w[li], D.params + D.off_b[li], D.act, D.sp_beta, out, nullptr, 0, 0);
+            __syncthreads();
+            in = out;
+        }
+        tube_layer<R, RB, NT, true>(tid, D.din[L], N, in, D.wt + D.off_w[L], D.params + D.off_b[L], D.act, D.sp_beta, FW,
+                                    P.fw ? P.fw + base * N : nullptr, N, P.fw ? nr : 0);
+        __syncthreads();
+    }
+    if (tid < nr) {
+#pragma clang fp contract(off)
+        const lg_plan_problem &p = P.p;
+        const int64_t b = base + tid;
+        const float *vr = X + tid * I + 3 * Hr;     // the plan's inputs in its item
+        float *fw = FW + tid * N, *zw = ZW + tid * ZS;
+        if (!nn) {
+            const bool l1 = p.tube_kind == LG_PLAN_TUBE_L1 || p.tube_kind == LG_PLAN_TUBE_L1_ROLLING;
+            for (int k = 0; k < N; ++k) {
+                const float vx = vr[2 * k], vy = vr[2 * k + 1];
+                fw[k] = p.scaling * (l1 ? fabsf(vx) + fabsf(vy) : vx * vx + vy * vy);
+            }
+            if (p.tube_kind == LG_PLAN_TUBE_L1_ROLLING || p.tube_kind == LG_PLAN_TUBE_L2_ROLLING) {
+                for (int k = N - 1; k >= 0; --k) {  // descending: fw[k] reads the plain values at and before k only
+                    const int k0 = k - p.window_size + 1 > 0 ? k - p.window_size + 1 : 0;
+                    float s = 0.f;
+                    for (int i = k0; i <= k; ++i) s = s + fw[i];
+                    fw[k] = s / (float)(k - k0 + 1);
+                }
+            }
+        }
+        float zx = P.z0[b * 2], zy = P.z0[b * 2 + 1], wk = P.w0 ? P.w0[b] : 0.f;
+        float cost = 0.f, minc = INFINITY;
+        int worst = -1, nv_g = 0, nv_v = 0, nv_z = 0, nv_w = 0;
+        for (int k = 0; k <= N; ++k) {
+            zw[3 * k] = zx; zw[3 * k + 1] = zy; zw[3 * k + 2] = wk;
+            bool hit = false;
+            for (int i = 0; i < p.n_obs; ++i) {
+                const float dx = zx - p.obs_c[i][0], dy = zy - p.obs_c[i][1], rr = p.obs_r[i] + wk;
+                const float g = (dx * dx + dy * dy) - rr * rr;
+                if (g < minc) { minc = g; worst = k; }
+                hit = hit || g < 0.f;
+            }
+            nv_g += hit;
+            nv_z += zx < p.rom_z_min[0] || zx > p.rom_z_max[0] || zy < p.rom_z_min[1] || zy > p.rom_z_max[1];
+            nv_w += wk > p.w_max;
+            cost = cost + plan_quad(k < N ? p.Q : p.Qf, zx - p.goal[0], zy - p.goal[1]);
+            const float vx = k < N ? vr[2 * k] : 0.f, vy = k < N ? vr[2 * k + 1] : 0.f;
+            if (k < N) {
+                nv_v += vx < p.rom_v_min[0] || vx > p.rom_v_max[0] || vy < p.rom_v_min[1] || vy > p.rom_v_max[1];
+                cost = cost + plan_quad(plan_input_cost(p), vx, vy);
+            }
+            cost = cost + (wk * p.Qw) * wk;
+            if (k < N) {
+                zx = zx + p.dt * vx; zy = zy + p.dt * vy;          // SingleInt2D.f
+                wk = P.offset ? fw[k] + P.offset[k] : fw[k];
+            }
+        }
+        P.cost[b] = cost; P.min_clear[b] = minc; P.worst_node[b] = worst;
+        P.n_viol[b * 4] = nv_g; P.n_viol[b * 4 + 1] = nv_v; P.n_viol[b * 4 + 2] = nv_z; P.n_viol[b * 4 + 3] = nv_w;
+    }
+    if (!P.z && !P.w && (nn || !P.fw)) return;
+    __syncthreads();
+    for (int e = tid; e < nr * (N + 1); e += NT) {
+        const int r = e / (N + 1), k = e - r * (N + 1);
+        const float *zw = ZW + r * ZS + 3 * k;
+        const int64_t o = (base + r) * (N + 1) + k;
+        if (P.z) { P.z[o * 2] = zw[0]; P.z[o * 2 + 1] = zw[1]; }
+        if (P.w) P.w[o] = zw[2];
+    }
+    if (!nn && P.fw)
+        for (int e = tid; e < nr * N; e += NT) P.fw[base * N + e] = FW[e];
+}
+
 // Closed loop over time: a workgroup owns RT sequences and walks t = 0..T-1 itself; the carried output of the tile stays in LDS.
 // Step t: X = x[s, t] with its leading fb columns replaced by the previous output unless t == 0 or reseed[s, t]; forward; store.
 // The teacher row and the reseed flag of step t + 1 are loaded into registers before step t's layers run, so their latency
@@ -588,6 +716,38 @@ void tubek_predict_windows_levels(const TubeDev *D, const float *w, const float 
     const size_t bytes = sizeof(float) * (size_t)R * (D->in_dim - 1 + 3 * D->units);
     hipLaunchKernelGGL(k_tube_predict_levels<true>, dim3((unsigned)((count + R - 1) / R)), dim3(NT), bytes, s, *D, G, count, levels,
                        n_levels, o);
+}
+
+// k_plan_score.  D: the horizon handle's TubeDev, or null for an analytic kind.  Returns the dynamic LDS of the launch in bytes, or
+// -1 where the kernel's ceiling cannot be set.  The reference shape (130 inputs, 128 units, N = 50) takes 74 KiB, past k_tube_predict's
+// own 64 KiB, so the ceiling is the roll-out kernels'; the largest shape of the envelope stays below it:
+static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + 2 * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N)) <= LG_TUBE_ROLLOUT_LDS,
+              "k_plan_score: the envelope's largest tile set must fit the dynamic LDS ceiling");
+int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
+                         const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
+                         float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, hipStream_t s) {
+    PlanDev P;
+    memset(&P, 0, sizeof(P));
+    TubeDev T;
+    memset(&T, 0, sizeof(T));
+    if (D) T = *D;
+    const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
+    P.p = *prob;
+    P.z0 = z0; P.v = v; P.e = nn ? e : nullptr; P.v_prev = nn ? v_prev : nullptr; P.w0 = w0; P.offset = offset;
+    P.cost = cost; P.min_clear = min_clear; P.worst_node = worst_node; P.n_viol = n_viol; P.fw = fw; P.z = z; P.w = w;
+    P.level = level;
+    P.Hr = nn ? prob->H_rev : 0;
+    P.I = nn ? T.in_dim : 2 * prob->N;
+    const size_t bytes = sizeof(float) * (size_t)R * (P.I + (nn ? 2 * T.units : 0) + prob->N + PLAN_ZS(prob->N));
+    static bool ceiling_set[64];        // per device: the attribute is set once, not per launch
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    if (dev < 0 || dev >= 64 || !ceiling_set[dev]) {
+        if (hipFuncSetAttribute((const void *)k_plan_score, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
+        if (dev >= 0 && dev < 64) ceiling_set[dev] = true;
+    }
+    hipLaunchKernelGGL(k_plan_score, dim3((unsigned)((B + R - 1) / R)), dim3(NT), bytes, s, T, P, B);
+    return (int64_t)bytes;
 }
 
 size_t tubek_lds_bytes(const TubeDev *D) {

@@ -43,6 +43,7 @@ def load():
         capi.declare_romsim_api(_lib)
         capi.declare_tube_data_api(_lib)
         capi.declare_select_api(_lib)
+        capi.declare_plan_api(_lib)
     return _lib
 
 

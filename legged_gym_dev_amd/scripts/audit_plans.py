@@ -1,0 +1,187 @@
+"""Score plans against a tube, track them on the ROM-on-ROM model and audit whether the tube held: the question the reference's
+deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.py asks of one solved plan, asked of a batch of plans from any
+source, on the HIP kernels (legged_gym_dev_amd/tube/plan.py), without CasADi, IPOPT, wandb or hydra.
+
+    python legged_gym_dev_amd/scripts/audit_plans.py (--run tube_runs/run0 | --tube l1|l2|l1_rolling|l2_rolling [--scaling s] [--window_size n]) \\
+        (--problem gap|right|right_wide | --problem_json F) \\
+        (--plans F.npz | --warm_start start|goal|interpolate [--perturb K --sigma s --seed n]) \\
+        [--calibration [PATH]] [--coverage c] [--level l] [--checkpoint best|latest] [--sim_cfg KEY=VALUE ...] [--out DIR]
+
+--run: a train_tube.py run of a one-shot tube (dataset scalar_horizon or scalar_horizon_level; any other is refused): the plans have
+N = the run's H_fwd nodes, and the tube item's past (H_rev error norms and inputs) is zero, as the reference's solve_tube starts.
+--tube: an analytic baseline tube instead (trajopt/tube_trajopt.py:489-540); N is --N (default 50).
+--plans: an .npz with z0 (B, 2) and v (B, N, 2).  --warm_start: the reference's warm start of the problem and, with --perturb K, K
+clipped Gaussian perturbations of it beside it (sigma in the input's units, clipped to the problem's input bounds).
+--calibration [PATH] (default PATH: the run's calibration.json) adds the conformal offset per step ahead: --coverage picks the set of a
+scalar_horizon calibration, --level that of a scalar_horizon_level one (the level also conditions the model).
+--sim_cfg: fields of the tracking model's configuration (RomSimCfg: env.model.dt=0.05 controller.Kp=10 ...); rom.dt is the problem's dt.
+
+Writes audit.json to --out (default: the run folder, or the working directory) and prints the reference script's
+"Total Success Rate" line: the share of (plan, node) pairs with tube >= realised error.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import numpy as np  # noqa: E402
+
+from legged_gym_dev_amd.tube import plan as pl  # noqa: E402
+
+ONE_SHOT = ("scalar_horizon", "scalar_horizon_level")
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    tube = ap.add_mutually_exclusive_group(required=True)
+    tube.add_argument("--run", help="folder train_tube.py wrote for a one-shot tube")
+    tube.add_argument("--tube", choices=[k for k in pl.TUBE_KINDS if k != "nn"], help="an analytic tube")
+    ap.add_argument("--scaling", type=float, default=0.5)
+    ap.add_argument("--window_size", type=int, default=10)
+    ap.add_argument("--N", type=int, default=None, help="nodes of an analytic-tube problem (default 50); a run fixes it to its H_fwd")
+    prob = ap.add_mutually_exclusive_group(required=True)
+    prob.add_argument("--problem", choices=sorted(pl.PROBLEMS))
+    prob.add_argument("--problem_json", help="a PlanProblem as JSON")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--plans", help=".npz with z0 (B, 2) and v (B, N, 2)")
+    src.add_argument("--warm_start", choices=["start", "goal", "interpolate", "nominal"])
+    ap.add_argument("--perturb", type=int, default=0)
+    ap.add_argument("--sigma", type=float, default=0.05)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--calibration", nargs="?", const="", default=None, metavar="PATH")
+    ap.add_argument("--coverage", type=float, default=None)
+    ap.add_argument("--level", type=float, default=None)
+    ap.add_argument("--checkpoint", choices=["best", "latest"], default="best")
+    ap.add_argument("--sim_cfg", nargs="*", default=[], metavar="KEY=VALUE")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if a.perturb and a.plans:
+        ap.error("--perturb belongs to --warm_start; --plans are taken as they are")
+    if a.perturb < 0 or a.sigma < 0:
+        ap.error("--perturb and --sigma must not be negative")
+    if a.calibration is not None and not a.run:
+        ap.error("--calibration belongs to --run: an analytic tube has none")
+    if a.tube and a.level is not None:
+        ap.error("--level belongs to a level-conditioned --run")
+    return a
+
+
+def run_config(run):
+    """config.json of the run; ValueError unless it trained a one-shot tube."""
+    from legged_gym_dev_amd.tube.model import read_config
+    cfg = read_config(run)
+    if cfg.get("dataset") not in ONE_SHOT:
+        raise ValueError(f"{run} trained a {cfg.get('dataset')!r} model; plans are scored by a one-shot tube: dataset {' or '.join(ONE_SHOT)}")
+    return cfg
+
+
+def build_problem(a, cfg):
+    kw = {"tube_kind": "nn", "N": cfg["H_fwd"], "H_rev": cfg["H_rev"]} if cfg else \
+        {"tube_kind": a.tube, "scaling": a.scaling, "window_size": a.window_size, **({"N": a.N} if a.N else {})}
+    if a.problem:
+        return pl.PlanProblem.named(a.problem, **kw)
+    with open(a.problem_json) as f:
+        given = json.load(f)
+    p = pl.PlanProblem.from_json(a.problem_json)
+    for k, v in kw.items():
+        if k in ("N", "H_rev") and cfg and k in given and given[k] != v:
+            raise ValueError(f"{a.problem_json}: {k}={given[k]} differs from the run's {v}")
+        setattr(p, k, v)
+    return p
+
+
+def build_plans(a, p):
+    """(z0 (B, 2), v (B, N, 2)) float32 tensors and a description of where they come from."""
+    import torch
+    if a.plans:
+        d = np.load(a.plans)
+        missing = [k for k in ("z0", "v") if k not in d]
+        if missing:
+            raise ValueError(f"{a.plans}: array(s) {missing} missing; a plan file holds z0 (B, 2) and v (B, N, 2)")
+        return torch.as_tensor(d["z0"], dtype=torch.float32), torch.as_tensor(d["v"], dtype=torch.float32), {"plans_file": a.plans}
+    _, v = pl.warm_start(a.warm_start, p.start, p.goal, p.N, p.dt)
+    v = torch.as_tensor(v, dtype=torch.float32)[None]
+    if a.perturb:
+        v = torch.cat([v, pl.perturb(v[0], a.sigma, a.perturb, a.seed, p.rom_v_min, p.rom_v_max)])
+    z0 = torch.tensor(p.start, dtype=torch.float32).repeat(v.shape[0], 1)
+    return z0, v, {"warm_start": a.warm_start, "perturb": a.perturb, "sigma": a.sigma, "seed": a.seed}
+
+
+def sim_config(a, p):
+    from legged_gym_dev_amd.tube.rom_sim import RomSimCfg
+    rc = RomSimCfg()
+    rc.env.num_envs = 1
+    rc.rom.dt = p.dt
+    for item in a.sim_cfg:
+        key, eq, val = item.partition("=")
+        node, parts = rc, key.split(".")
+        try:
+            for part in parts[:-1]:
+                node = getattr(node, part)
+            old = getattr(node, parts[-1])
+        except AttributeError:
+            raise ValueError(f"--sim_cfg {item}: RomSimCfg has no field {key!r}") from None
+        if not eq:
+            raise ValueError(f"--sim_cfg {item}: KEY=VALUE")
+        setattr(node, parts[-1], val if isinstance(old, str) else json.loads(val))
+    return rc
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    cfg = run_config(a.run) if a.run else None
+    p = build_problem(a, cfg)
+    if a.warm_start == "nominal":
+        pl.warm_start("nominal", p.start, p.goal, p.N, p.dt)          # raises, naming the missing solver
+    import torch
+    from legged_gym_dev_amd.tube.rom_sim import HipRomSim
+    model = calib = sim = None
+    level = a.level
+    if a.run:
+        from legged_gym_dev_amd.tube.calibrate import Calibration, default_path
+        from legged_gym_dev_amd.tube.model import HipTubeModel
+        if cfg["dataset"] == "scalar_horizon_level" and level is None:
+            raise ValueError("--level is required: the run is level-conditioned (scalar_horizon_level)")
+        if a.calibration is not None:
+            path = a.calibration or default_path(a.run)
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"{path} is missing: calibrate_tube.py --run {a.run} writes it")
+            calib = Calibration.load(path)
+    else:
+        pl.check_envelope(p)
+    z0, v, source = build_plans(a, p)
+    try:
+        if a.run:
+            model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, device=a.device)
+        scorer = pl.HipPlanScorer(model, p, calibration=calib, level=level, coverage=a.coverage, device=a.device)
+        sim = HipRomSim(sim_config(a, p), device=a.device)
+        s = scorer.score(z0, v)
+        t = pl.track(sim, s["z"], v)
+        torch.cuda.synchronize()
+        res = pl.audit(s, t, p)
+        cost, clear = s["cost"].cpu().double(), s["min_clear"].cpu().double()
+        extra = {"cost_mean": float(cost.mean()), "cost_min": float(cost.min()), "best_plan": int(cost.argmin()),
+                 "min_clear_min": float(clear.min()) if p.n_obs else None, "n_viol_plans": [int(x) for x in (s["n_viol"] > 0).sum(dim=0).cpu()],
+                 "problem": p.to_json(), "run": a.run, "tube": a.tube or "nn", "level": level,
+                 "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), "source": source}
+        assert not set(extra) & set(res), "a key of the audit would be overwritten"
+        res.update(extra)
+    finally:
+        if sim is not None:
+            sim.close()
+        if model is not None:
+            model.close()
+    out = a.out or a.run or "."
+    os.makedirs(out, exist_ok=True)
+    with open(os.path.join(out, "audit.json"), "w") as f:
+        json.dump(res, f, indent=1, allow_nan=False)
+    print(f"{res['plans']} plans x {res['nodes']} nodes: predicted safe {res['predicted_safe']:.4f}, actually safe {res['actually_safe']:.4f}, "
+          f"covered at every node {res['covered_plans']:.4f}; realised error mean {res['w_true_mean']:.4f} max {res['w_true_max']:.4f}")
+    print(f"Total Success Rate: {res['coverage']}")
+    return res
+
+
+if __name__ == "__main__":
+    main()
