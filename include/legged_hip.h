@@ -788,6 +788,50 @@ int lg_plan_score(lg_tube *tube, const lg_plan_problem *prob, const float *z0, c
 int lg_plan_track(lg_romsim *sim, const float *z, const float *v, const float *x0, int64_t B, int32_t N, int32_t S, float rom_dt,
                   float *pz_x, float *w_true, float *x, float *u);
 
+/* ------------------------------------------------------------------ sampling planner on a tube: MPPI for P
+ * problem instances at once, in place of the reference's NLP solve -- trajopt/tube_trajopt.py:460 solve_tube ("TT") -- and of the
+ * re-solve at every control step of trajopt/tube_planning_closed_loop.py:82-168 ("TPCL").  The instances share one lg_plan_problem;
+ * each has its own z0 (P, 2), e (P, H_rev), v_prev (P, H_rev, 2), w0 (P) and mean plan vbar (P, N, 2).  One iteration is two
+ * launches: k_plan_sample_score (K candidates per instance drawn around vbar and scored by k_plan_score's own code, no candidate
+ * stored) and k_plan_mppi_update (softmin-weighted mean, elite, history). */
+#define LG_MPPI_MAX_K 4096
+typedef struct lg_mppi_cfg {                       /* the sampler that stands in for TT:460's solver options */
+    int32_t K /*candidates per instance: a multiple of 32 in 32..LG_MPPI_MAX_K*/, iters /*>= 1*/;
+    uint64_t seed;                                 /* Philox key of the call */
+    int32_t instance_offset /*instance p draws as instance id instance_offset + p*/, _pad;
+    float sigma /*> 0*/, sigma_decay /*(0, 1]: sigma_it = sigma * sigma_decay^it, `it` float32 products*/, lambda /*> 0*/;
+    float rho_g, rho_w, rho_z;                     /* >= 0: weights of the obstacle, tube and state hinge sums */
+} lg_mppi_cfg;
+/* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error: whatever lg_plan_check refuses, K outside 32..4096 or no
+ * multiple of 32, iters < 1, sigma <= 0, sigma_decay outside (0, 1], lambda <= 0, a negative rho, P < 1, P * K past int32. */
+int lg_mppi_check(const lg_mppi_cfg *cfg, const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level, int64_t P);
+/* For tests and tools: out (P, K, N, 2) (DEVICE), the candidates of iteration `it` around vbar (P, N, 2), through the device function
+ * both kernels draw with.  Candidate j of instance p: clip(vbar[p] + sigma_it eps, rom_v_min, rom_v_max) with eps from one
+ * Philox4x32-10 block per (instance_offset + p, it, j, node), keyed by seed: Box-Muller, cosine branch x, sine branch y.  Candidate 0
+ * is the mean plan (eps = 0).  The tube handle is not read. */
+int lg_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int32_t it, const float *vbar, int64_t P, float *out,
+                            void *stream);
+/* One iteration `it` (cfg->iters is not read): what & 1 launches k_plan_sample_score, what & 2 k_plan_mppi_update.  DEVICE pointers;
+ * e, v_prev, w0, offset, level as lg_plan_score takes them, per instance.
+ * Score: J (P, K) = ((cost + rho_g pen_g) + rho_w pen_w) + rho_z pen_z, one rounding per operation, where cost and the nodes are
+ * lg_plan_score's of the candidate and pen_g = sum_k sum_i max(0, -g[i, k]), pen_w = sum_k max(0, w_k - w_max), pen_z = sum_k sum_d
+ * max(0, z_d - z_max_d) + max(0, z_min_d - z_d), nodes 0..N ascending.  Optional (NULL = not written): cost (P, K), min_clear (P, K),
+ * pen (P, K, 3).  A candidate's outputs do not depend on P, K or its place in a tile.
+ * Update (reads J, so J may be given): weights expf(-(J_j - Jmin) / lambda), 0 for a non-finite J; vbar[p] becomes the weighted mean
+ * of the candidates, drawn again; sums in an order fixed by K alone, no float atomics.  With no finite J vbar[p] stays and n_bad[p]
+ * (int32) counts the iteration.  best_J (P), best_v (P, N, 2): the first arg-min candidate wherever Jmin < best_J; reset_best != 0
+ * starts them (and n_bad) afresh, so they need no initial value.  hist_row (P, 2) optional: (J of candidate 0, Jmin). */
+int lg_plan_mppi_step(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int32_t it, int32_t what, int32_t reset_best,
+                      const float *z0, const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level,
+                      float level, int64_t P, float *vbar, float *J, float *cost, float *min_clear, float *pen, float *best_J,
+                      float *best_v, float *hist_row, int32_t *n_bad, void *stream);
+/* The plan of TT:460 by cfg->iters iterations of lg_plan_mppi_step from the mean plans in vbar (in-out): 2 iters launches on the
+ * stream, no host synchronisation.  J_scratch (P, K); best_J (P), best_v (P, N, 2), n_bad (P) int32 are started by the call;
+ * hist (iters, P, 2) optional. */
+int lg_plan_mppi(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, const float *z0, const float *e,
+                 const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t P, float *vbar,
+                 float *J_scratch, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -345,6 +345,15 @@ class lg_plan_problem(C.Structure):
         ("rom_z_min", f32 * 2), ("rom_z_max", f32 * 2), ("rom_v_min", f32 * 2), ("rom_v_max", f32 * 2)]
 
 
+MPPI_MAX_K = 4096                                               # LG_MPPI_MAX_K
+
+
+class lg_mppi_cfg(C.Structure):
+    _fields_ = [
+        ("K", i32), ("iters", i32), ("seed", u64), ("instance_offset", i32), ("_pad", i32),
+        ("sigma", f32), ("sigma_decay", f32), ("lambda_", f32), ("rho_g", f32), ("rho_w", f32), ("rho_z", f32)]
+
+
 def declare_plan_api(lib):
     vp = C.c_void_p
     if not hasattr(lib, "lg_plan_score"):          # an A/B library (LG_HIP_LIB) built before the plan entries
@@ -352,6 +361,13 @@ def declare_plan_api(lib):
     lib.lg_plan_check.argtypes = [C.POINTER(lg_plan_problem), vp, i32]
     lib.lg_plan_score.argtypes = [vp, C.POINTER(lg_plan_problem), vp, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.lg_plan_track.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp]
+    if not hasattr(lib, "lg_plan_mppi"):           # an A/B library built before the sampling planner
+        return
+    pp, pc = C.POINTER(lg_plan_problem), C.POINTER(lg_mppi_cfg)
+    lib.lg_mppi_check.argtypes = [pc, pp, vp, i32, i64]
+    lib.lg_plan_mppi_candidates.argtypes = [pp, pc, i32, vp, i64, vp, vp]
+    lib.lg_plan_mppi_step.argtypes = [vp, pp, pc, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.lg_plan_mppi.argtypes = [vp, pp, pc, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp, vp]
 
 
 def declare_env_api(lib, prefix="lg_"):

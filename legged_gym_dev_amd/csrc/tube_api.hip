@@ -3,6 +3,7 @@
 // the closed-loop roll-outs, single-tap and windowed, and the level entries of a level-conditioned model, flat or horizon (tube_kernels.hip).  lg_tube_sweep_*: K such trainers of one shape on one
 // dataset, stepped by the same two launches with the members along grid y.
 // lg_plan_check / lg_plan_score: plans scored against a one-shot horizon handle or an analytic tube (k_plan_score).
+// lg_mppi_check / lg_plan_mppi*: the sampling planner on top of it (k_plan_sample_score, k_plan_mppi_update).
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -42,6 +43,13 @@ void tubek_rollout_window(const TubeDev *D, const float *x, int64_t n_seq, int T
 int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
                          const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
                          float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, hipStream_t s);
+void tubek_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *vbar, int64_t P_, float *out,
+                                hipStream_t s);
+int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
+                                const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
+                                const float *vbar, float *J, float *cost, float *min_clear, float *pen, hipStream_t s);
+void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,
+                            const float *J, float *best_J, float *best_v, float *hist, int32_t *n_bad, hipStream_t s);
 }
 
 struct TubeCaps {                       // rows that a model's data-sized buffers hold
@@ -449,6 +457,72 @@ int lg_plan_score(lg_tube *tube, const lg_plan_problem *prob, const float *z0, c
                                         min_clear, worst_node, n_viol, fw, z, w, (hipStream_t)stream);
     if (rc < 0) { lg_set_error("lg_plan_score: hipFuncSetAttribute failed"); return -2; }
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_score: launch failed"), -3);
+}
+
+// ---------------------------------------------------------------- sampling planner on a tube
+static std::string mppi_reason(const lg_mppi_cfg *c, int64_t P) {
+    if (c->K < 32 || c->K > LG_MPPI_MAX_K || c->K % 32) return "K = " + std::to_string(c->K) + " must be a multiple of 32 in 32.." + std::to_string(LG_MPPI_MAX_K);
+    if (c->iters < 1) return "iters = " + std::to_string(c->iters) + " must be at least 1";
+    if (!(c->sigma > 0.f)) return "sigma must be positive";
+    if (!(c->sigma_decay > 0.f && c->sigma_decay <= 1.f)) return "sigma_decay must lie in (0, 1]";
+    if (!(c->lambda > 0.f)) return "lambda must be positive";
+    if (!(c->rho_g >= 0.f)) return "rho_g must not be negative";
+    if (!(c->rho_w >= 0.f)) return "rho_w must not be negative";
+    if (!(c->rho_z >= 0.f)) return "rho_z must not be negative";
+    if (P < 1) return "P = " + std::to_string(P) + " must be at least 1";
+    if (P * c->K > INT32_MAX) return "P * K = " + std::to_string(P * c->K) + " must not exceed 2^31 - 1";
+    return "";
+}
+
+int lg_mppi_check(const lg_mppi_cfg *cfg, const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level, int64_t P) {
+    if (lg_plan_check(prob, tube, has_level)) return -1;
+    const std::string e = mppi_reason(cfg, P);
+    if (!e.empty()) { lg_set_error("lg_mppi: " + e); return -1; }
+    return 0;
+}
+
+int lg_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int32_t it, const float *vbar, int64_t P, float *out,
+                            void *stream) {
+    lg_plan_problem q = *prob;          // the tube is not read: the analytic envelope of the problem is what counts here
+    q.tube_kind = LG_PLAN_TUBE_L1;
+    if (lg_mppi_check(cfg, &q, nullptr, 0, P)) return -1;
+    if (it < 0) { lg_set_error("lg_plan_mppi_candidates: it must not be negative"); return -1; }
+    if (P * cfg->K * (int64_t)prob->N > INT32_MAX) { lg_set_error("lg_plan_mppi_candidates: P * K * N must not exceed 2^31 - 1"); return -1; }
+    if (!vbar || !out) { lg_set_error("lg_plan_mppi_candidates: missing array"); return -1; }
+    tubek_plan_mppi_candidates(prob, cfg, it, vbar, P, out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_mppi_candidates: launch failed"), -3);
+}
+
+int lg_plan_mppi_step(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int32_t it, int32_t what, int32_t reset_best,
+                      const float *z0, const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level,
+                      float level, int64_t P, float *vbar, float *J, float *cost, float *min_clear, float *pen, float *best_J,
+                      float *best_v, float *hist_row, int32_t *n_bad, void *stream) {
+    if (lg_mppi_check(cfg, prob, tube, has_level, P)) return -1;
+    if (it < 0) { lg_set_error("lg_plan_mppi_step: it must not be negative"); return -1; }
+    if (!(what & 3)) { lg_set_error("lg_plan_mppi_step: what must name the score (1), the update (2) or both (3)"); return -1; }
+    if (!vbar || !J || ((what & 1) && !z0) || ((what & 2) && (!best_J || !best_v || !n_bad))) {
+        lg_set_error("lg_plan_mppi_step: missing array (vbar and J; z0 for the score; best_J, best_v and n_bad for the update)"); return -1;
+    }
+    const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
+    if (what & 1) {
+        const int64_t rc = tubek_plan_sample_score(nn ? &tube->dev : nullptr, prob, cfg, it, z0, e, v_prev, w0, offset, has_level ? level : 0.f,
+                                                   P, vbar, J, cost, min_clear, pen, (hipStream_t)stream);
+        if (rc < 0) { lg_set_error("lg_plan_mppi_step: hipFuncSetAttribute failed"); return -2; }
+    }
+    if (what & 2) tubek_plan_mppi_update(prob, cfg, it, reset_best, P, vbar, J, best_J, best_v, hist_row, n_bad, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_mppi_step: launch failed"), -3);
+}
+
+int lg_plan_mppi(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, const float *z0, const float *e,
+                 const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t P, float *vbar,
+                 float *J_scratch, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream) {
+    if (lg_mppi_check(cfg, prob, tube, has_level, P)) return -1;
+    for (int32_t it = 0; it < cfg->iters; ++it) {
+        const int rc = lg_plan_mppi_step(tube, prob, cfg, it, 3, it == 0, z0, e, v_prev, w0, offset, has_level, level, P, vbar, J_scratch,
+                                         nullptr, nullptr, nullptr, best_J, best_v, hist ? hist + (int64_t)it * P * 2 : nullptr, n_bad, stream);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 // ---------------------------------------------------------------- sweep: K trainers of one shape on one dataset

@@ -382,6 +382,71 @@ __device__ __forceinline__ float plan_quad(const float *M, float d0, float d1) {
     return (d0 * M[0] + d1 * M[2]) * d0 + (d0 * M[1] + d1 * M[3]) * d1;
 }
 
+// One lane's walk over a plan's nodes, shared by k_plan_score and k_plan_sample_score: the analytic tube (where the kind is one), the
+// ROM nodes, the tube nodes, clearance, cost and counts in one fixed-order chain, every operation rounded on its own.  vr: the plan's
+// inputs (N, 2) in the lane's item; fw (N): the MLP's tube values, or written here for an analytic kind; zw: PLAN_ZS floats of nodes.
+// PEN adds the three hinge sums of the sampling planner (section 10.10), each its own chain over the nodes in ascending order:
+// pen_g += max(0, -g) per obstacle, pen_w += max(0, w - w_max), pen_z += max(0, z_d - z_max_d) + max(0, z_min_d - z_d) per axis d.
+struct PlanWalk {
+    float cost, minc, pen_g, pen_w, pen_z;
+    int worst, nv_g, nv_v, nv_z, nv_w;
+};
+template <bool PEN>
+__device__ __forceinline__ PlanWalk plan_walk(const lg_plan_problem &p, bool nn, const float *vr, float *fw, float *zw, float zx, float zy,
+                                              float wk, const float *offset) {
+#pragma clang fp contract(off)
+    const int N = p.N;
+    if (!nn) {
+        const bool l1 = p.tube_kind == LG_PLAN_TUBE_L1 || p.tube_kind == LG_PLAN_TUBE_L1_ROLLING;
+        for (int k = 0; k < N; ++k) {
+            const float vx = vr[2 * k], vy = vr[2 * k + 1];
+            fw[k] = p.scaling * (l1 ? fabsf(vx) + fabsf(vy) : vx * vx + vy * vy);
+        }
+        if (p.tube_kind == LG_PLAN_TUBE_L1_ROLLING || p.tube_kind == LG_PLAN_TUBE_L2_ROLLING) {
+            for (int k = N - 1; k >= 0; --k) {  // descending: fw[k] reads the plain values at and before k only
+                const int k0 = k - p.window_size + 1 > 0 ? k - p.window_size + 1 : 0;
+                float s = 0.f;
+                for (int i = k0; i <= k; ++i) s = s + fw[i];
+                fw[k] = s / (float)(k - k0 + 1);
+            }
+        }
+    }
+    PlanWalk W;
+    W.cost = 0.f; W.minc = INFINITY; W.pen_g = 0.f; W.pen_w = 0.f; W.pen_z = 0.f;
+    W.worst = -1; W.nv_g = 0; W.nv_v = 0; W.nv_z = 0; W.nv_w = 0;
+    for (int k = 0; k <= N; ++k) {
+        zw[3 * k] = zx; zw[3 * k + 1] = zy; zw[3 * k + 2] = wk;
+        bool hit = false;
+        for (int i = 0; i < p.n_obs; ++i) {
+            const float dx = zx - p.obs_c[i][0], dy = zy - p.obs_c[i][1], rr = p.obs_r[i] + wk;
+            const float g = (dx * dx + dy * dy) - rr * rr;
+            if (g < W.minc) { W.minc = g; W.worst = k; }
+            hit = hit || g < 0.f;
+            if (PEN) W.pen_g = W.pen_g + fmaxf(0.f, -g);
+        }
+        W.nv_g += hit;
+        W.nv_z += zx < p.rom_z_min[0] || zx > p.rom_z_max[0] || zy < p.rom_z_min[1] || zy > p.rom_z_max[1];
+        W.nv_w += wk > p.w_max;
+        if (PEN) {
+            W.pen_w = W.pen_w + fmaxf(0.f, wk - p.w_max);
+            W.pen_z = W.pen_z + (fmaxf(0.f, zx - p.rom_z_max[0]) + fmaxf(0.f, p.rom_z_min[0] - zx));
+            W.pen_z = W.pen_z + (fmaxf(0.f, zy - p.rom_z_max[1]) + fmaxf(0.f, p.rom_z_min[1] - zy));
+        }
+        W.cost = W.cost + plan_quad(k < N ? p.Q : p.Qf, zx - p.goal[0], zy - p.goal[1]);
+        const float vx = k < N ? vr[2 * k] : 0.f, vy = k < N ? vr[2 * k + 1] : 0.f;
+        if (k < N) {
+            W.nv_v += vx < p.rom_v_min[0] || vx > p.rom_v_max[0] || vy < p.rom_v_min[1] || vy > p.rom_v_max[1];
+            W.cost = W.cost + plan_quad(plan_input_cost(p), vx, vy);
+        }
+        W.cost = W.cost + (wk * p.Qw) * wk;
+        if (k < N) {
+            zx = zx + p.dt * vx; zy = zy + p.dt * vy;          // SingleInt2D.f
+            wk = offset ? fw[k] + offset[k] : fw[k];
+        }
+    }
+    return W;
+}
+
 // Dynamic LDS: X (R, I) the items -- for an analytic kind the plan's inputs alone --, H0, H1 (R, U) (NN kind), FW (R, N), ZW (R, PLAN_ZS).
 __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t count) {
     extern __shared__ float lds[];
@@ -420,55 +485,11 @@ __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t
         __syncthreads();
     }
     if (tid < nr) {
-#pragma clang fp contract(off)
-        const lg_plan_problem &p = P.p;
         const int64_t b = base + tid;
-        const float *vr = X + tid * I + 3 * Hr;     // the plan's inputs in its item
-        float *fw = FW + tid * N, *zw = ZW + tid * ZS;
-        if (!nn) {
-            const bool l1 = p.tube_kind == LG_PLAN_TUBE_L1 || p.tube_kind == LG_PLAN_TUBE_L1_ROLLING;
-            for (int k = 0; k < N; ++k) {
-                const float vx = vr[2 * k], vy = vr[2 * k + 1];
-                fw[k] = p.scaling * (l1 ? fabsf(vx) + fabsf(vy) : vx * vx + vy * vy);
-            }
-            if (p.tube_kind == LG_PLAN_TUBE_L1_ROLLING || p.tube_kind == LG_PLAN_TUBE_L2_ROLLING) {
-                for (int k = N - 1; k >= 0; --k) {  // descending: fw[k] reads the plain values at and before k only
-                    const int k0 = k - p.window_size + 1 > 0 ? k - p.window_size + 1 : 0;
-                    float s = 0.f;
-                    for (int i = k0; i <= k; ++i) s = s + fw[i];
-                    fw[k] = s / (float)(k - k0 + 1);
-                }
-            }
-        }
-        float zx = P.z0[b * 2], zy = P.z0[b * 2 + 1], wk = P.w0 ? P.w0[b] : 0.f;
-        float cost = 0.f, minc = INFINITY;
-        int worst = -1, nv_g = 0, nv_v = 0, nv_z = 0, nv_w = 0;
-        for (int k = 0; k <= N; ++k) {
-            zw[3 * k] = zx; zw[3 * k + 1] = zy; zw[3 * k + 2] = wk;
-            bool hit = false;
-            for (int i = 0; i < p.n_obs; ++i) {
-                const float dx = zx - p.obs_c[i][0], dy = zy - p.obs_c[i][1], rr = p.obs_r[i] + wk;
-                const float g = (dx * dx + dy * dy) - rr * rr;
-                if (g < minc) { minc = g; worst = k; }
-                hit = hit || g < 0.f;
-            }
-            nv_g += hit;
-            nv_z += zx < p.rom_z_min[0] || zx > p.rom_z_max[0] || zy < p.rom_z_min[1] || zy > p.rom_z_max[1];
-            nv_w += wk > p.w_max;
-            cost = cost + plan_quad(k < N ? p.Q : p.Qf, zx - p.goal[0], zy - p.goal[1]);
-            const float vx = k < N ? vr[2 * k] : 0.f, vy = k < N ? vr[2 * k + 1] : 0.f;
-            if (k < N) {
-                nv_v += vx < p.rom_v_min[0] || vx > p.rom_v_max[0] || vy < p.rom_v_min[1] || vy > p.rom_v_max[1];
-                cost = cost + plan_quad(plan_input_cost(p), vx, vy);
-            }
-            cost = cost + (wk * p.Qw) * wk;
-            if (k < N) {
-                zx = zx + p.dt * vx; zy = zy + p.dt * vy;          // SingleInt2D.f
-                wk = P.offset ? fw[k] + P.offset[k] : fw[k];
-            }
-        }
-        P.cost[b] = cost; P.min_clear[b] = minc; P.worst_node[b] = worst;
-        P.n_viol[b * 4] = nv_g; P.n_viol[b * 4 + 1] = nv_v; P.n_viol[b * 4 + 2] = nv_z; P.n_viol[b * 4 + 3] = nv_w;
+        const PlanWalk W = plan_walk<false>(P.p, nn, X + tid * I + 3 * Hr, FW + tid * N, ZW + tid * ZS, P.z0[b * 2], P.z0[b * 2 + 1],
+                                            P.w0 ? P.w0[b] : 0.f, P.offset);
+        P.cost[b] = W.cost; P.min_clear[b] = W.minc; P.worst_node[b] = W.worst;
+        P.n_viol[b * 4] = W.nv_g; P.n_viol[b * 4 + 1] = W.nv_v; P.n_viol[b * 4 + 2] = W.nv_z; P.n_viol[b * 4 + 3] = W.nv_w;
     }
     if (!P.z && !P.w && (nn || !P.fw)) return;
     __syncthreads();
@@ -481,6 +502,206 @@ __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t
     }
     if (!nn && P.fw)
         for (int e = tid; e < nr * N; e += NT) P.fw[base * N + e] = FW[e];
+}
+
+// ------------------------------------------------------------------ sampling planner on a tube (MPPI)
+// One iteration is two launches: k_plan_sample_score draws K candidates around every instance's mean plan and scores them with
+// k_plan_score's own tile; k_plan_mppi_update folds them into the new mean by softmin weights.  No candidate is stored: both kernels
+// regenerate it from Philox through mppi_candidate.
+struct MppiDev {                        // passed by value
+    const float *vbar_in;               // (P, N, 2) mean plans read by the launch
+    float *vbar;                        // the same array, written by the update
+    float *J, *pen, *best_J, *best_v, *hist;
+    int32_t *n_bad;
+    uint64_t seed;
+    uint32_t inst0, it;                 // instance id of instance 0, iteration
+    int K, N, reset;
+    float sigma_it, lambda, rho_g, rho_w, rho_z;
+    float v_min[2], v_max[2];
+};
+
+// Candidate j of instance id `inst` at iteration `it`, node k: clip(vbar + sigma_it eps, v_min, v_max), every operation rounded on its
+// own.  eps = one Philox4x32-10 block keyed by the call's seed at counter (inst, it, j, node | tag): Box-Muller on its first two words,
+// the cosine branch for x and the sine branch for y; u1 in (0, 1], the angle 2 pi u2 taken as sincospi(2 u2).  Candidate 0 is the
+// mean plan itself.  The only place a candidate is made: k_plan_sample_score, k_plan_mppi_update and k_plan_mppi_candidates call it.
+__device__ __forceinline__ void mppi_candidate(const MppiDev &M, uint32_t inst, int j, int k, float bx, float by, float *vx, float *vy) {
+#pragma clang fp contract(off)
+    float x = bx, y = by;
+    if (j != 0) {
+        uint32_t c[4] = {inst, M.it, (uint32_t)j, 0x4d500000u | (uint32_t)k};
+        philox4x32((uint32_t)M.seed, (uint32_t)(M.seed >> 32), c);
+        const float u1 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f), u2 = (float)(c[1] >> 8) * (1.0f / 16777216.0f);
+        const float r = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincospif(2.0f * u2, &sn, &cs);
+        x = bx + M.sigma_it * (r * cs);
+        y = by + M.sigma_it * (r * sn);
+    }
+    *vx = fminf(fmaxf(x, M.v_min[0]), M.v_max[0]);
+    *vy = fminf(fmaxf(y, M.v_min[1]), M.v_max[1]);
+}
+
+// for tests and tools: the (P, K, N, 2) candidates of one iteration, one thread per (instance, candidate, node)
+__global__ void __launch_bounds__(NT) k_plan_mppi_candidates(MppiDev M, int64_t count, float *out) {
+    const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= count) return;
+    const int k = (int)(i % M.N);
+    const int64_t g = i / M.N;
+    const int p = (int)(g / M.K), j = (int)(g - (int64_t)p * M.K);
+    const float *vb = M.vbar_in + ((int64_t)p * M.N + k) * 2;
+    mppi_candidate(M, M.inst0 + (uint32_t)p, j, k, vb[0], vb[1], out + i * 2, out + i * 2 + 1);
+}
+
+// k_plan_score's tile -- R candidates per workgroup, the same LDS layout -- with the plan columns of the item drawn in place instead
+// of gathered: tile t holds candidates 32 (t mod K/32) .. + 31 of instance t / (K/32) (K is a multiple of R), so one z0, e, v_prev,
+// w0 serves the tile.  The layers and the lane's walk are k_plan_score's.  J = ((cost + rho_g pen_g) + rho_w pen_w) + rho_z pen_z.
+// P.cost, P.min_clear and M.pen (P, K, 3) are optional here.  No atomics; a candidate depends on (seed, instance id, it, j) alone.
+__global__ void __launch_bounds__(NT) k_plan_sample_score(TubeDev D, PlanDev P, MppiDev M) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
+    const bool nn = P.p.tube_kind == LG_PLAN_TUBE_NN;
+    const int U = nn ? D.units : 0, L = D.layers, ZS = PLAN_ZS(N);
+    const int64_t base = (int64_t)blockIdx.x * R;
+    const int pi = (int)(base / M.K), j0 = (int)(base - (int64_t)pi * M.K);
+    float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N;
+    for (int e = tid; e < R * I; e += NT) {         // the columns beside the plan: the instance's e, v_prev and the level
+        const int r = e / I, c = e - r * I;
+        if (c < Hr) X[e] = P.e ? P.e[(int64_t)pi * Hr + c] : 0.f;
+        else if (c < 3 * Hr) X[e] = P.v_prev ? P.v_prev[(int64_t)pi * Hr * 2 + (c - Hr)] : 0.f;
+        else if (c >= Hr + 2 * (Hr + N)) X[e] = P.level;
+    }
+    for (int q = tid; q < R * N; q += NT) {         // the plan: one Philox block per (candidate, node)
+        const int r = q / N, k = q - r * N;
+        const float *vb = M.vbar_in + ((int64_t)pi * N + k) * 2;
+        float *x = X + r * I + 3 * Hr + 2 * k;
+        mppi_candidate(M, M.inst0 + (uint32_t)pi, j0 + r, k, vb[0], vb[1], x, x + 1);
+    }
+    __syncthreads();
+    if (nn) {
+        const float *in = X;
+        for (int li = 0; li < L; ++li) {
+            float *out = li & 1 ? H1 : H0;
+            tube_layer<R, RB, NT, false>(tid, D.din[li], U, in, D.wt + D.off_w[li], D.params + D.off_b[li], D.act, D.sp_beta, out, nullptr, 0, 0);
+            __syncthreads();
+            in = out;
+        }
+        tube_layer<R, RB, NT, true>(tid, D.din[L], N, in, D.wt + D.off_w[L], D.params + D.off_b[L], D.act, D.sp_beta, FW, nullptr, N, 0);
+        __syncthreads();
+    }
+    if (tid < R) {
+#pragma clang fp contract(off)
+        const int64_t b = base + tid;
+        const PlanWalk W = plan_walk<true>(P.p, nn, X + tid * I + 3 * Hr, FW + tid * N, ZW + tid * ZS, P.z0[pi * 2], P.z0[pi * 2 + 1],
+                                           P.w0 ? P.w0[pi] : 0.f, P.offset);
+        M.J[b] = ((W.cost + M.rho_g * W.pen_g) + M.rho_w * W.pen_w) + M.rho_z * W.pen_z;
+        if (P.cost) P.cost[b] = W.cost;
+        if (P.min_clear) P.min_clear[b] = W.minc;
+        if (M.pen) { M.pen[b * 3] = W.pen_g; M.pen[b * 3 + 1] = W.pen_w; M.pen[b * 3 + 2] = W.pen_z; }
+    }
+}
+
+// The softmin update, one workgroup per instance.  Dynamic LDS: K floats, J then the weights.
+//   1. Jmin and its first index over the finite J: thread t scans j = t, t + 256, .. ascending, then a halving tree over the threads
+//      that prefers the smaller value and, on a tie, the smaller index.
+//   2. weight_j = expf(-(J_j - Jmin) / lambda), 0 for a non-finite J.
+//   3. Every sum over the candidates has one order, fixed by K alone: MPPI_CH = 64 chunks, chunk c adding j = c, c + 64, .. ascending
+//      from 0, then a halving tree over the chunks (c += c + 32, 16, .. 1).  The weights' sum S takes it on threads 0..63; the
+//      weighted sums take it MPPI_NB = 4 nodes at a time -- thread t is chunk t / 4 of node k0 + t % 4 and accumulates x and y of its
+//      candidates, regenerated by mppi_candidate -- so a thread makes K / 64 Philox blocks per pass and ceil(N / 4) passes, at P = 1 too.
+//      A candidate of weight 0 is skipped: it adds +0 to a sum that is not -0.
+//   4. vbar[k] = sum / S.  With no finite J the mean stays and n_bad counts the iteration.  The elite: where Jmin < best_J (or at a
+//      reset) best_J and best_v take the arg-min candidate; a reset without a finite J leaves best_J = inf and best_v = the mean.
+//      hist = (J of candidate 0, Jmin).
+#define MPPI_CH 64
+#define MPPI_NB (NT / MPPI_CH)
+__device__ __forceinline__ bool mppi_finite(float x) { return fabsf(x) < INFINITY; }
+__global__ void __launch_bounds__(NT) k_plan_mppi_update(MppiDev M) {
+#pragma clang fp contract(off)
+    extern __shared__ float wl[];
+    __shared__ float red[NT * 2];
+    __shared__ int redi[NT];
+    const int tid = threadIdx.x, p = blockIdx.x, K = M.K, N = M.N;
+    const float *J = M.J + (int64_t)p * K;
+    float m = INFINITY;
+    int mi = -1;
+    for (int j = tid; j < K; j += NT) {
+        const float x = J[j];
+        wl[j] = x;
+        if (mppi_finite(x) && (mi < 0 || x < m)) { m = x; mi = j; }
+    }
+    red[tid] = m; redi[tid] = mi;
+    __syncthreads();
+    for (int h = NT / 2; h > 0; h >>= 1) {
+        if (tid < h) {
+            const float b = red[tid + h];
+            const int bi = redi[tid + h], ai = redi[tid];
+            if (bi >= 0 && (ai < 0 || b < red[tid] || (b == red[tid] && bi < ai))) { red[tid] = b; redi[tid] = bi; }
+        }
+        __syncthreads();
+    }
+    const float Jmin = red[0];
+    const int best = redi[0];
+    const float J0 = wl[0], bJ = M.best_J[p];
+    const bool improved = best >= 0 && (M.reset || Jmin < bJ);
+    __syncthreads();
+    for (int j = tid; j < K; j += NT) {
+        const float x = wl[j];
+        wl[j] = mppi_finite(x) ? expf(-(x - Jmin) / M.lambda) : 0.f;
+    }
+    __syncthreads();
+    const int c = tid / MPPI_NB, n = tid - c * MPPI_NB;
+    if (tid < MPPI_CH) {
+        float s = 0.f;
+        for (int j = tid; j < K; j += MPPI_CH) s = s + wl[j];
+        red[tid] = s;
+    }
+    __syncthreads();
+    for (int h = MPPI_CH / 2; h > 0; h >>= 1) {
+        if (tid < h) red[tid] = red[tid] + red[tid + h];
+        __syncthreads();
+    }
+    const float S = red[0];
+    __syncthreads();
+    const uint32_t inst = M.inst0 + (uint32_t)p;
+    for (int k0 = 0; k0 < N; k0 += MPPI_NB) {
+        const int k = k0 + n;
+        const bool on = k < N;
+        float bx = 0.f, by = 0.f, ax = 0.f, ay = 0.f;
+        if (on) {
+            const float *vb = M.vbar_in + ((int64_t)p * N + k) * 2;
+            bx = vb[0]; by = vb[1];
+            for (int j = c; j < K; j += MPPI_CH) {
+                const float w = wl[j];
+                if (w == 0.f) continue;
+                float vx, vy;
+                mppi_candidate(M, inst, j, k, bx, by, &vx, &vy);
+                ax = ax + w * vx; ay = ay + w * vy;
+            }
+        }
+        red[tid * 2] = ax; red[tid * 2 + 1] = ay;
+        __syncthreads();
+        for (int h = MPPI_CH / 2; h > 0; h >>= 1) {
+            if (c < h) {
+                red[tid * 2] = red[tid * 2] + red[(tid + h * MPPI_NB) * 2];
+                red[tid * 2 + 1] = red[tid * 2 + 1] + red[(tid + h * MPPI_NB) * 2 + 1];
+            }
+            __syncthreads();
+        }
+        if (c == 0 && on) {
+            const int64_t o = ((int64_t)p * N + k) * 2;
+            if (improved) mppi_candidate(M, inst, best, k, bx, by, M.best_v + o, M.best_v + o + 1);
+            else if (M.reset) { M.best_v[o] = bx; M.best_v[o + 1] = by; }
+            if (best >= 0) { M.vbar[o] = red[tid * 2] / S; M.vbar[o + 1] = red[tid * 2 + 1] / S; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (improved) M.best_J[p] = Jmin;
+        else if (M.reset) M.best_J[p] = INFINITY;
+        if (M.hist) { M.hist[p * 2] = J0; M.hist[p * 2 + 1] = Jmin; }
+        const int bad = best < 0;
+        M.n_bad[p] = M.reset ? bad : M.n_bad[p] + bad;
+    }
 }
 
 // Closed loop over time: a workgroup owns RT sequences and walks t = 0..T-1 itself; the carried output of the tile stays in LDS.
@@ -748,6 +969,66 @@ int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const fl
     }
     hipLaunchKernelGGL(k_plan_score, dim3((unsigned)((B + R - 1) / R)), dim3(NT), bytes, s, T, P, B);
     return (int64_t)bytes;
+}
+
+// The sampling planner's launches.  k_plan_sample_score's tile is k_plan_score's, so the assert above
+// covers it; the update's dynamic LDS is the K weights:
+static_assert(sizeof(float) * LG_MPPI_MAX_K <= 16 * 1024, "k_plan_mppi_update: K weights take at most 16 KiB of LDS");
+static_assert(sizeof(float) * (LG_MPPI_MAX_K + 3 * NT) <= LG_TUBE_ROLLOUT_LDS, "k_plan_mppi_update: weights and reduction rows fit the LDS ceiling");
+static_assert(LG_MPPI_MAX_K % R == 0 && NT % MPPI_CH == 0, "a tile of candidates belongs to one instance; whole nodes per pass");
+static MppiDev mppi_dev(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it) {
+    MppiDev M;
+    memset(&M, 0, sizeof(M));
+    M.seed = cfg->seed; M.inst0 = (uint32_t)cfg->instance_offset; M.it = (uint32_t)it;
+    M.K = cfg->K; M.N = prob->N;
+    float s = cfg->sigma;               // sigma_it = sigma * sigma_decay^it as `it` float32 products
+    for (int i = 0; i < it; ++i) s = s * cfg->sigma_decay;
+    M.sigma_it = s; M.lambda = cfg->lambda; M.rho_g = cfg->rho_g; M.rho_w = cfg->rho_w; M.rho_z = cfg->rho_z;
+    for (int d = 0; d < 2; ++d) { M.v_min[d] = prob->rom_v_min[d]; M.v_max[d] = prob->rom_v_max[d]; }
+    return M;
+}
+void tubek_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *vbar, int64_t P_, float *out,
+                                hipStream_t s) {
+    MppiDev M = mppi_dev(prob, cfg, it);
+    M.vbar_in = vbar;
+    const int64_t count = P_ * cfg->K * prob->N;
+    hipLaunchKernelGGL(k_plan_mppi_candidates, dim3((unsigned)((count + NT - 1) / NT)), dim3(NT), 0, s, M, count, out);
+}
+// returns the dynamic LDS of the launch in bytes, or -1 where the kernel's ceiling cannot be set
+int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
+                                const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
+                                const float *vbar, float *J, float *cost, float *min_clear, float *pen, hipStream_t s) {
+    PlanDev P;
+    memset(&P, 0, sizeof(P));
+    TubeDev T;
+    memset(&T, 0, sizeof(T));
+    if (D) T = *D;
+    const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
+    P.p = *prob;
+    P.z0 = z0; P.e = nn ? e : nullptr; P.v_prev = nn ? v_prev : nullptr; P.w0 = w0; P.offset = offset;
+    P.cost = cost; P.min_clear = min_clear;
+    P.level = level;
+    P.Hr = nn ? prob->H_rev : 0;
+    P.I = nn ? T.in_dim : 2 * prob->N;
+    MppiDev M = mppi_dev(prob, cfg, it);
+    M.vbar_in = vbar; M.J = J; M.pen = pen;
+    const size_t bytes = sizeof(float) * (size_t)R * (P.I + (nn ? 2 * T.units : 0) + prob->N + PLAN_ZS(prob->N));
+    static bool ceiling_set[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    if (dev < 0 || dev >= 64 || !ceiling_set[dev]) {
+        if (hipFuncSetAttribute((const void *)k_plan_sample_score, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
+        if (dev >= 0 && dev < 64) ceiling_set[dev] = true;
+    }
+    hipLaunchKernelGGL(k_plan_sample_score, dim3((unsigned)(P_ * cfg->K / R)), dim3(NT), bytes, s, T, P, M);
+    return (int64_t)bytes;
+}
+void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,
+                            const float *J, float *best_J, float *best_v, float *hist, int32_t *n_bad, hipStream_t s) {
+    MppiDev M = mppi_dev(prob, cfg, it);
+    M.vbar_in = vbar; M.vbar = vbar; M.J = const_cast<float *>(J); M.best_J = best_J; M.best_v = best_v; M.hist = hist; M.n_bad = n_bad;
+    M.reset = reset;
+    hipLaunchKernelGGL(k_plan_mppi_update, dim3((unsigned)P_), dim3(NT), sizeof(float) * (size_t)cfg->K, s, M);
 }
 
 size_t tubek_lds_bytes(const TubeDev *D) {

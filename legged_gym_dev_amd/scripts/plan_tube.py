@@ -1,0 +1,166 @@
+"""Plan through a problem with a tube: the reference's trajopt/tube_trajopt.py (one plan) and trajopt/tube_planning_closed_loop.py
+(replanning at every step) with a sampling planner -- batched MPPI on the HIP kernels (legged_gym_dev_amd/tube/plan.py; DESIGN.md
+section 10.10) -- in place of CasADi / IPOPT, for many starts at once.
+
+    python legged_gym_dev_amd/scripts/plan_tube.py (--run tube_runs/run0 | --tube l1|l2|l1_rolling|l2_rolling [--scaling s] [--window_size n]) \\
+        --problem gap|right|right_wide|F.json [--level l] [--calibration [PATH]] [--coverage c] \\
+        [--K 256] [--iters 20] [--sigma 0.3] [--sigma_decay 1] [--lambda 1] [--rho_g 1e4] [--rho_w 0] [--rho_z 0] [--seed 0] \\
+        [--starts P --start_noise s] [--closed_loop H] [--sim_cfg KEY=VALUE ...] [--out DIR]
+
+--run, --tube, --calibration, --coverage, --level, --checkpoint, --sim_cfg: as audit_plans.py takes them; a run that audit_plans.py
+refuses (not a one-shot tube) is refused here.  --problem: one of the reference's problems, or a PlanProblem as JSON (a path ending
+in .json).  --starts P: P instances; the first starts at the problem's start, the others at start + start_noise * standard normal.
+Without --closed_loop every start gets one plan, which is scored, tracked and audited as audit_plans.py does.  With --closed_loop H
+every robot replans at each of H control steps (closed_loop) and the audit is audit_closed_loop's.
+
+Writes plan.json -- the audit, the history of the (first) plan, the settings -- and plans.npz with z0 (B, 2), v (B, N, 2): the final
+mean plans, or with --closed_loop every plan in force, step by step; audit_plans.py --plans reads it.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np  # noqa: E402
+
+import audit_plans  # noqa: E402
+from legged_gym_dev_amd.tube import plan as pl  # noqa: E402
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    tube = ap.add_mutually_exclusive_group(required=True)
+    tube.add_argument("--run", help="folder train_tube.py wrote for a one-shot tube")
+    tube.add_argument("--tube", choices=[k for k in pl.TUBE_KINDS if k != "nn"], help="an analytic tube")
+    ap.add_argument("--scaling", type=float, default=0.5)
+    ap.add_argument("--window_size", type=int, default=10)
+    ap.add_argument("--N", type=int, default=None, help="nodes of an analytic-tube problem (default 50); a run fixes it to its H_fwd")
+    ap.add_argument("--problem", required=True, help="gap, right, right_wide, or a PlanProblem as JSON (F.json)")
+    ap.add_argument("--calibration", nargs="?", const="", default=None, metavar="PATH")
+    ap.add_argument("--coverage", type=float, default=None)
+    ap.add_argument("--level", type=float, default=None)
+    ap.add_argument("--checkpoint", choices=["best", "latest"], default="best")
+    d = pl.MppiCfg()
+    ap.add_argument("--K", type=int, default=d.K)
+    ap.add_argument("--iters", type=int, default=d.iters)
+    ap.add_argument("--sigma", type=float, default=d.sigma)
+    ap.add_argument("--sigma_decay", type=float, default=d.sigma_decay)
+    ap.add_argument("--lambda", dest="lambda_", type=float, default=d.lambda_)
+    ap.add_argument("--rho_g", type=float, default=d.rho_g)
+    ap.add_argument("--rho_w", type=float, default=d.rho_w)
+    ap.add_argument("--rho_z", type=float, default=d.rho_z)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--starts", type=int, default=1)
+    ap.add_argument("--start_noise", type=float, default=0.0)
+    ap.add_argument("--closed_loop", type=int, default=None, metavar="H")
+    ap.add_argument("--goal_tol", type=float, default=0.1)
+    ap.add_argument("--sim_cfg", nargs="*", default=[], metavar="KEY=VALUE")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if a.problem not in pl.PROBLEMS and not a.problem.endswith(".json"):
+        ap.error(f"--problem {a.problem}: one of {sorted(pl.PROBLEMS)} or a .json file")
+    if a.calibration is not None and not a.run:
+        ap.error("--calibration belongs to --run: an analytic tube has none")
+    if a.tube and a.level is not None:
+        ap.error("--level belongs to a level-conditioned --run")
+    if a.starts < 1 or a.start_noise < 0:
+        ap.error("--starts must be at least 1 and --start_noise not negative")
+    if a.closed_loop is not None and a.closed_loop < 1:
+        ap.error("--closed_loop H: at least 1 step")
+    try:
+        mppi_cfg(a).check(a.starts)
+    except ValueError as e:
+        ap.error(str(e))
+    return a
+
+
+def mppi_cfg(a):
+    return pl.MppiCfg(K=a.K, iters=a.iters, seed=a.seed, sigma=a.sigma, sigma_decay=a.sigma_decay, lambda_=a.lambda_, rho_g=a.rho_g,
+                      rho_w=a.rho_w, rho_z=a.rho_z)
+
+
+def build_problem(a, cfg):
+    named = a.problem in pl.PROBLEMS
+    return audit_plans.build_problem(argparse.Namespace(tube=a.tube, scaling=a.scaling, window_size=a.window_size, N=a.N,
+                                                        problem=a.problem if named else None, problem_json=None if named else a.problem), cfg)
+
+
+def starts(a, p):
+    """(P, 2) float32: the problem's start, then start + start_noise * standard normal from a torch generator on the host."""
+    import torch
+    s = torch.tensor(p.start, dtype=torch.float32).repeat(a.starts, 1)
+    if a.starts > 1 and a.start_noise > 0:
+        g = torch.Generator().manual_seed(int(a.seed))
+        s[1:] += float(a.start_noise) * torch.randn(a.starts - 1, 2, generator=g)
+    return s
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    cfg = audit_plans.run_config(a.run) if a.run else None
+    p = build_problem(a, cfg)
+    import torch
+    from legged_gym_dev_amd.tube.rom_sim import HipRomSim
+    model = calib = sim = None
+    if a.run:
+        from legged_gym_dev_amd.tube.calibrate import Calibration, default_path
+        from legged_gym_dev_amd.tube.model import HipTubeModel
+        if cfg["dataset"] == "scalar_horizon_level" and a.level is None:
+            raise ValueError("--level is required: the run is level-conditioned (scalar_horizon_level)")
+        if a.calibration is not None:
+            path = a.calibration or default_path(a.run)
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"{path} is missing: calibrate_tube.py --run {a.run} writes it")
+            calib = Calibration.load(path)
+    else:
+        pl.check_envelope(p)
+    z0 = starts(a, p)
+    try:
+        if a.run:
+            model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, device=a.device)
+        planner = pl.HipMppiPlanner(model, p, mppi_cfg(a), calibration=calib, level=a.level, coverage=a.coverage, device=a.device)
+        sim = HipRomSim(audit_plans.sim_config(a, p), device=a.device)
+        if a.closed_loop is None:
+            sol = planner.plan(z0)
+            t = pl.track(sim, sol["score"]["z"], sol["v"])
+            torch.cuda.synchronize()
+            audit = pl.audit(sol["score"], t, p)
+            hist, plans_z0, plans_v = sol["hist"], z0, sol["v"]
+            extra = {"best_J": [float(x) for x in sol["best_J"].cpu()], "n_bad": [int(x) for x in sol["n_bad"].cpu()],
+                     "cost": [float(x) for x in sol["score"]["cost"].cpu()]}
+        else:
+            first = planner.plan(z0)                                     # the history of the first plan; closed_loop makes it again
+            res = pl.closed_loop(planner, sim, a.closed_loop, z0, keep_plans=True)
+            torch.cuda.synchronize()
+            audit = pl.audit_closed_loop(res, p, goal_tol=a.goal_tol)
+            hist = first["hist"]
+            plans_z0, plans_v = res["plans_z"][:, :, 0].reshape(-1, 2), res["plans_v"].reshape(-1, p.N, 2)
+            extra = {"n_bad": [int(x) for x in res["n_bad"].sum(dim=1).cpu()], "cost": res["cost"].cpu().double().tolist(),
+                     "min_clear": res["min_clear"].cpu().double().tolist() if p.n_obs else None}
+    finally:
+        if sim is not None:
+            sim.close()
+        if model is not None:
+            model.close()
+    out = {"audit": audit, "hist": hist.cpu().double().tolist(), "closed_loop": a.closed_loop, "starts": z0.double().tolist(),
+           "mppi": {**{k: v for k, v in vars(mppi_cfg(a)).items() if k != "lambda_"}, "lambda": a.lambda_}, "problem": p.to_json(),
+           "run": a.run, "tube": a.tube or "nn", "level": a.level, "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), **extra}
+    folder = a.out or a.run or "."
+    os.makedirs(folder, exist_ok=True)
+    with open(os.path.join(folder, "plan.json"), "w") as f:
+        json.dump(out, f, indent=1, allow_nan=False)
+    np.savez(os.path.join(folder, "plans.npz"), z0=plans_z0.cpu().numpy(), v=plans_v.cpu().numpy())
+    if a.closed_loop is None:
+        print(f"{audit['plans']} plans x {audit['nodes']} nodes: predicted safe {audit['predicted_safe']:.4f}, actually safe "
+              f"{audit['actually_safe']:.4f}, covered at every node {audit['covered_plans']:.4f}")
+    else:
+        print(f"{audit['robots']} robots x {audit['steps']} steps: coverage {audit['coverage']:.4f}, covered at every step "
+              f"{audit['covered_robots']:.4f}, actually safe {audit['actually_safe']:.4f}, reached the goal {audit['reached_goal']:.4f}")
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -4,8 +4,9 @@ model, and audit whether the tube held -- lg_plan_score / lg_plan_track in inclu
 A plan is a start ``z0`` (2) and ``N`` inputs ``v`` (N, 2) of the SingleInt2D ROM.  The definitions are the reference planner's
 (trajopt/tube_trajopt.py, "TT"): the one-shot tube query :561-568, the obstacle constraint inflated by the tube :59-97, the quadratic
 objective :41-56,206-212, the analytic baseline tubes :489-540 and the problems ``gap``, ``right``, ``right_wide`` :11-21; the tracking
-loop is deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.py:75-88.  No optimiser is part of this: the plans come
-from any solver, or from ``warm_start`` and ``perturb``.  There is no CPU fallback: scoring and tracking need the library and a GPU.
+loop is deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.py:75-88.  The plans come from any solver, from
+``warm_start`` and ``perturb``, or from the sampling planner below (``HipMppiPlanner``, ``closed_loop``; section 10.10), which stands in
+for the reference's NLP solve.  There is no CPU fallback: scoring, planning and tracking need the library and a GPU.
 """
 import ctypes as C
 import dataclasses
@@ -307,3 +308,250 @@ def audit(score, track, problem):
             "table": {"safe_safe": share(pred & act), "safe_unsafe": share(pred & ~act), "unsafe_safe": share(~pred & act),
                       "unsafe_unsafe": share(~pred & ~act)},
             "w_true_mean": float(wt.mean()), "w_true_max": float(wt.max())}
+
+
+# ---------------------------------------------------------------- the sampling planner
+@dataclasses.dataclass
+class MppiCfg:
+    """lg_mppi_cfg, field for field: MPPI in place of the reference's NLP solve (trajopt/tube_trajopt.py:460 solve_tube).
+    K candidates per instance and iteration, drawn as clip(mean + sigma_it * standard normal) with sigma_it = sigma * sigma_decay^it;
+    weights exp(-(J - Jmin) / lambda) on J = cost + rho_g pen_g + rho_w pen_w + rho_z pen_z (the hinge sums of the obstacle, tube and
+    state constraints).  instance_offset: instance p draws as instance id instance_offset + p."""
+    K: int = 256
+    iters: int = 20
+    seed: int = 0
+    instance_offset: int = 0
+    sigma: float = 0.3
+    sigma_decay: float = 1.0
+    lambda_: float = 1.0
+    rho_g: float = 1e4
+    rho_w: float = 0.0
+    rho_z: float = 0.0
+
+    def check(self, P=1):
+        """ValueError in lg_mppi_check's words, the field named."""
+        if self.K < 32 or self.K > capi.MPPI_MAX_K or self.K % 32:
+            raise ValueError(f"K = {self.K} must be a multiple of 32 in 32..{capi.MPPI_MAX_K}")
+        if self.iters < 1:
+            raise ValueError(f"iters = {self.iters} must be at least 1")
+        if not self.sigma > 0:
+            raise ValueError("sigma must be positive")
+        if not 0 < self.sigma_decay <= 1:
+            raise ValueError("sigma_decay must lie in (0, 1]")
+        if not self.lambda_ > 0:
+            raise ValueError("lambda must be positive")
+        for name in ("rho_g", "rho_w", "rho_z"):
+            if not getattr(self, name) >= 0:
+                raise ValueError(f"{name} must not be negative")
+        if P < 1:
+            raise ValueError(f"P = {P} must be at least 1")
+        if P * self.K > 2 ** 31 - 1:
+            raise ValueError(f"P * K = {P * self.K} must not exceed 2^31 - 1")
+
+    def to_struct(self, iters=None):
+        c = capi.lg_mppi_cfg()
+        c.K, c.iters, c.seed, c.instance_offset = int(self.K), int(self.iters if iters is None else iters), int(self.seed), int(self.instance_offset)
+        c.sigma, c.sigma_decay, c.lambda_ = float(self.sigma), float(self.sigma_decay), float(self.lambda_)
+        c.rho_g, c.rho_w, c.rho_z = float(self.rho_g), float(self.rho_w), float(self.rho_z)
+        return c
+
+    def sigma_it(self, it):
+        """sigma * sigma_decay^it as the library takes it: `it` float32 products."""
+        s, d = np.float32(self.sigma), np.float32(self.sigma_decay)
+        for _ in range(int(it)):
+            s = np.float32(s * d)
+        return s
+
+
+class HipMppiPlanner:
+    """lg_plan_mppi on one problem for P instances at once, built on a HipPlanScorer: the handle, offset, level and envelope checks
+    are the scorer's.  The arguments after cfg are HipPlanScorer's."""
+
+    def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None):
+        cfg.check()
+        self.scorer = HipPlanScorer(model, problem, calibration=calibration, level=level, coverage=coverage, device=device)
+        self.problem, self.cfg, self.device, self.lib = problem, cfg, self.scorer.device, self.scorer.lib
+        self._err = self.scorer._err
+
+    def _fail(self, name, rc):
+        raise self._err(f"{name} failed ({rc}): {self.lib.lg_last_error().decode()}")
+
+    def _stream(self):
+        import torch
+        torch.cuda.set_device(self.device)
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def state(self, z0, vbar, e=None, v_prev=None, w0=None, want=()):
+        """The device arrays of a run: the instances' z0 (P, 2), e, v_prev, w0 (None = zeros), the mean plans vbar (P, N, 2) (copied),
+        J (P, K), best_J, best_v, n_bad and whatever of cost, min_clear (P, K), pen (P, K, 3) `want` names."""
+        import torch
+        p, dev, K = self.problem, self.device, self.cfg.K
+        f32 = lambda t: None if t is None else torch.as_tensor(t).to(dev, torch.float32).contiguous()
+        z0, e, v_prev, w0 = f32(z0), f32(e), f32(v_prev), f32(w0)
+        vbar = torch.as_tensor(vbar).to(dev, torch.float32).clone().contiguous()
+        if z0.dim() != 2 or z0.shape[1] != 2 or z0.shape[0] < 1:
+            raise ValueError(f"z0 must be (P >= 1, 2); got {tuple(z0.shape)}")
+        P = z0.shape[0]
+        self.cfg.check(P)
+        for name, t, shape in (("vbar", vbar, (P, p.N, 2)), ("e", e, (P, p.H_rev)), ("v_prev", v_prev, (P, p.H_rev, 2)), ("w0", w0, (P,))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {shape}; got {tuple(t.shape)}")
+        bad = [k for k in want if k not in ("cost", "min_clear", "pen")]
+        if bad:
+            raise ValueError(f"want {bad}: of cost, min_clear, pen")
+        st = {"P": P, "z0": z0, "e": e, "v_prev": v_prev, "w0": w0, "vbar": vbar, "J": torch.empty(P, K, device=dev),
+              "best_J": torch.empty(P, device=dev), "best_v": torch.empty(P, p.N, 2, device=dev),
+              "n_bad": torch.zeros(P, device=dev, dtype=torch.int32)}
+        opt = {"cost": (P, K), "min_clear": (P, K), "pen": (P, K, 3)}
+        for k in want:
+            st[k] = torch.empty(opt[k], device=dev)
+        return st
+
+    def candidates(self, vbar, it=0):
+        """lg_plan_mppi_candidates: the (P, K, N, 2) candidates of iteration `it` around vbar (P, N, 2) (tests and tools)."""
+        import torch
+        p = self.problem
+        vbar = torch.as_tensor(vbar).to(self.device, torch.float32).contiguous()
+        if vbar.dim() != 3 or tuple(vbar.shape[1:]) != (p.N, 2) or vbar.shape[0] < 1:
+            raise ValueError(f"vbar must be (P >= 1, {p.N}, 2); got {tuple(vbar.shape)}")
+        out = torch.empty(vbar.shape[0], self.cfg.K, p.N, 2, device=self.device)
+        rc = self.lib.lg_plan_mppi_candidates(C.byref(self.scorer.struct), C.byref(self.cfg.to_struct()), int(it), _ptr(vbar), vbar.shape[0],
+                                              _ptr(out), self._stream())
+        if rc != 0:
+            self._fail("lg_plan_mppi_candidates", rc)
+        return out
+
+    def step(self, st, it, what=3, reset=False, hist_row=None):
+        """lg_plan_mppi_step on a state(): what & 1 the score (writes J and the optional outputs), what & 2 the update (reads J;
+        writes vbar, best_J, best_v, n_bad and hist_row (P, 2) where given)."""
+        sc = self.scorer
+        rc = self.lib.lg_plan_mppi_step(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), int(it), int(what), int(bool(reset)),
+                                        _ptr(st["z0"]), _ptr(st["e"]), _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset),
+                                        int(sc.level is not None), float(sc.level if sc.level is not None else 0.0), st["P"],
+                                        _ptr(st["vbar"]), _ptr(st["J"]), _ptr(st.get("cost")), _ptr(st.get("min_clear")), _ptr(st.get("pen")),
+                                        _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]), self._stream())
+        if rc != 0:
+            self._fail("lg_plan_mppi_step", rc)
+        return st
+
+    def warm_start(self, z0):
+        """The `interpolate` warm start (TT:415-432) from every instance's z0 to the goal, clipped to the input bounds: (P, N, 2)."""
+        p = self.problem
+        z0 = np.asarray(z0, np.float64).reshape(-1, 2)
+        z = np.linspace(0, 1, p.N + 1)[None, :, None] * (np.asarray(p.goal, np.float64) - z0)[:, None, :] + z0[:, None, :]
+        v = np.diff(z, axis=1) / p.dt                                    # warm_start's arithmetic, every instance at once
+        return np.clip(v, np.asarray(p.rom_v_min, np.float64), np.asarray(p.rom_v_max, np.float64)).astype(np.float32)
+
+    def plan(self, z0, v_init=None, e=None, v_prev=None, w0=None, iters=None):
+        """lg_plan_mppi from z0 (P, 2): cfg.iters (or `iters`) iterations from the mean plans v_init (P, N, 2) or (N, 2); None = the
+        clipped `interpolate` warm start.  Returns device tensors: v (P, N, 2) the final mean plan, best_v, best_J (P), hist
+        (iters, P, 2) = (J of the mean plan, smallest J) per iteration, n_bad (P) int32, and score / best_score: both plans through
+        HipPlanScorer.score (with z and w)."""
+        import torch
+        z0 = torch.as_tensor(z0, dtype=torch.float32).reshape(-1, 2)
+        if v_init is None:
+            v_init = self.warm_start(z0.cpu().numpy())
+        v_init = torch.as_tensor(v_init, dtype=torch.float32)
+        if v_init.dim() == 2:
+            v_init = v_init[None].repeat(z0.shape[0], 1, 1)
+        iters = self.cfg.iters if iters is None else int(iters)
+        if iters < 1:
+            raise ValueError(f"iters = {iters} must be at least 1")
+        st = self.state(z0, v_init, e, v_prev, w0)
+        hist = torch.empty(iters, st["P"], 2, device=self.device)
+        sc = self.scorer
+        rc = self.lib.lg_plan_mppi(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), _ptr(st["z0"]), _ptr(st["e"]),
+                                   _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset), int(sc.level is not None),
+                                   float(sc.level if sc.level is not None else 0.0), st["P"], _ptr(st["vbar"]), _ptr(st["J"]),
+                                   _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist), _ptr(st["n_bad"]), self._stream())
+        if rc != 0:
+            self._fail("lg_plan_mppi", rc)
+        want = ("z", "w")
+        return {"v": st["vbar"], "best_v": st["best_v"], "best_J": st["best_J"], "hist": hist, "n_bad": st["n_bad"],
+                "score": sc.score(st["z0"], st["vbar"], st["e"], st["v_prev"], st["w0"], want=want),
+                "best_score": sc.score(st["z0"], st["best_v"], st["e"], st["v_prev"], st["w0"], want=want)}
+
+
+def shift_plan(v):
+    """The receding-horizon shift of mean plans (P, N, 2): one step on, the last row repeated."""
+    import torch
+    return torch.cat([v[:, 1:], v[:, -1:]], dim=1)
+
+
+def shift_past(e, v_prev, err, v_k):
+    """The tube item's past one step on (TPCL:160-163, as a true shift): e (P, H_rev) drops its oldest value and takes err (P),
+    v_prev (P, H_rev, 2) takes v_k (P, 2).  With H_rev = 0 both stay empty."""
+    import torch
+    if e.shape[1] == 0:
+        return e, v_prev
+    return torch.cat([e[:, 1:], err[:, None]], dim=1), torch.cat([v_prev[:, 1:], v_k[:, None]], dim=1)
+
+
+def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=False, track_fn=None):
+    """trajopt/tube_planning_closed_loop.py:82-168 ("TPCL") for P robots at once: plan, apply the first action, replan, H times.
+    start (P, 2); x0 (P, 4) the robots' states, None = (start, 0, 0).  The first plan runs iters_first iterations (None = cfg.iters)
+    from the warm start, every later one cfg.iters from the previous mean plan shifted by one step.
+    Step k: the action comes from track() on the first two nodes of the plan in force (the final mean plan) -- reference point
+    z_sol[0], feed-forward v_sol[1] (TPCL:91-96), from the robot's state; x[:, 1] and its actions are kept.  Recorded: v_k = v_sol[0],
+    z_{k+1} = z_sol[1], w_{k+1} = w_sol[1], pz_x_{k+1}; then e and v_prev shift by one and take |z_k - pz_x_k| and v_k, and the next
+    plan starts from the ROM's z_{k+1} (TPCL:159).  No plan is made after the last step.
+    Returns device tensors z (P, H+1, 2), v (P, H, 2), w (P, H+1), pz_x (P, H+1, 2), x (P, H+1, 4), u (P, H S, 2), cost, min_clear,
+    best_J (P, H) of the plan in force, n_bad (P, H) and, with keep_plans, plans_v (H, P, N, 2), plans_z (H, P, N+1, 2), plans_w."""
+    import torch
+    p = planner.problem
+    track_fn = track if track_fn is None else track_fn
+    dev = planner.device
+    start = torch.as_tensor(start, dtype=torch.float32).reshape(-1, 2).to(dev)
+    P = start.shape[0]
+    if H < 1:
+        raise ValueError(f"H = {H} must be at least 1")
+    xk = torch.cat([start, torch.zeros(P, 2, device=dev)], dim=1) if x0 is None else torch.as_tensor(x0, dtype=torch.float32).to(dev)
+    if tuple(xk.shape) != (P, 4):
+        raise ValueError(f"x0 must be {(P, 4)}; got {tuple(xk.shape)}")
+    e, v_prev = torch.zeros(P, p.H_rev, device=dev), torch.zeros(P, p.H_rev, 2, device=dev)
+    zk = start
+    z, v, w, pz, x, u = [zk], [], [torch.zeros(P, device=dev)], [xk[:, :2]], [xk], []
+    cost, clear, bestJ, nbad, plans = [], [], [], [], {"v": [], "z": [], "w": []}
+    sol = planner.plan(zk, None, e, v_prev, None, iters=iters_first)
+    for k in range(H):
+        v_sol, z_sol, w_sol = sol["v"], sol["score"]["z"], sol["score"]["w"]
+        ff = v_sol[:, min(1, p.N - 1)][:, None]
+        t = track_fn(sim, z_sol[:, :2], ff, xk, rom_dt=p.dt)
+        xk = t["x"][:, 1]
+        v_k = v_sol[:, 0]
+        err = torch.linalg.vector_norm(z[-1] - pz[-1], dim=1)
+        v.append(v_k), z.append(z_sol[:, 1]), w.append(w_sol[:, 1]), pz.append(xk[:, :2]), x.append(xk), u.append(t["u"])
+        cost.append(sol["score"]["cost"]), clear.append(sol["score"]["min_clear"]), bestJ.append(sol["best_J"]), nbad.append(sol["n_bad"])
+        if keep_plans:
+            plans["v"].append(v_sol), plans["z"].append(z_sol), plans["w"].append(w_sol)
+        e, v_prev = shift_past(e, v_prev, err, v_k)
+        if k + 1 < H:
+            sol = planner.plan(z[-1], shift_plan(v_sol), e, v_prev, None)
+    out = {"z": torch.stack(z, 1), "v": torch.stack(v, 1), "w": torch.stack(w, 1), "pz_x": torch.stack(pz, 1), "x": torch.stack(x, 1),
+           "u": torch.cat(u, 1), "cost": torch.stack(cost, 1), "min_clear": torch.stack(clear, 1), "best_J": torch.stack(bestJ, 1),
+           "n_bad": torch.stack(nbad, 1)}
+    if keep_plans:
+        out.update({"plans_" + k: torch.stack(t, 0) for k, t in plans.items()})
+    return out
+
+
+def audit_closed_loop(result, problem, goal_tol=0.1):
+    """Did the tube hold in closed loop?  Plain Python numbers (strict JSON).  coverage_by_step[k]: share of robots with
+    w_k >= |z_k - pz_x_k|; coverage: its mean; covered_robots: share covered at every step; actually_safe: share whose realised path
+    pz_x enters no obstacle; predicted_safe: share whose plans in force all had min_clear >= 0; reached_goal: share whose ROM path
+    ends within goal_tol of the goal; goal_distance_mean: the mean of that distance."""
+    import torch
+    f64 = lambda t: t.detach().cpu().double()
+    z, w, pz = f64(result["z"]), f64(result["w"]), f64(result["pz_x"])
+    err = torch.linalg.vector_norm(z - pz, dim=-1)
+    cov = w >= err
+    act = torch.ones(z.shape[0], dtype=torch.bool)
+    for c, r in zip(problem.obs_c, problem.obs_r):
+        act &= ~(torch.linalg.vector_norm(pz - torch.tensor(c, dtype=torch.float64), dim=-1) < float(r)).any(dim=1)
+    pred = (f64(result["min_clear"]) >= 0).all(dim=1)
+    dist = torch.linalg.vector_norm(z[:, -1] - torch.tensor(problem.goal, dtype=torch.float64), dim=-1)
+    share = lambda m: float(m.double().mean())
+    return {"robots": int(z.shape[0]), "steps": int(z.shape[1] - 1), "coverage_by_step": [float(v) for v in cov.double().mean(dim=0)],
+            "coverage": share(cov), "covered_robots": share(cov.all(dim=1)), "actually_safe": share(act), "predicted_safe": share(pred),
+            "goal_tol": float(goal_tol), "reached_goal": share(dist <= goal_tol), "goal_distance_mean": float(dist.mean()),
+            "error_mean": float(err.mean()), "error_max": float(err.max())}
