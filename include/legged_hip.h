@@ -832,6 +832,45 @@ int lg_plan_mppi(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *
                  const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t P, float *vbar,
                  float *J_scratch, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream);
 
+/* ------------------------------------------------------------------ gradient planner on a tube: the
+ * objective of lg_plan_mppi_step, J = ((cost + rho_g pen_g) + rho_w pen_w) + rho_z pen_z, of B plans and its gradient dJ/dv by a
+ * reverse sweep in the scoring tile (k_plan_grad, 32 plans per 256-thread workgroup, one launch), with projected Adam and an elite
+ * fused behind it: a first-order stand-in for the NLP solve of trajopt/tube_trajopt.py:460.  Plain fp32 FMA arithmetic; the forward
+ * half is lg_plan_mppi_step's code, so J, cost, min_clear and pen carry its bits.  A hinge max(0, a) has derivative 1 where a > 0
+ * strictly, else 0; |v| has derivative 0 at 0; ReLU'(0) = 0.  w0, z0, e, v_prev and the level get no gradient. */
+typedef struct lg_grad_cfg {
+    int32_t iters;                                 /* >= 1: stepping launches of lg_plan_descend */
+    float lr /*> 0*/, beta1, beta2 /*[0, 1)*/, eps /*> 0*/;   /* Adam, bias-corrected */
+    float rho_g, rho_w, rho_z;                     /* >= 0: weights of the obstacle, tube and state hinge sums */
+} lg_grad_cfg;
+/* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error: whatever lg_plan_check refuses, iters < 1, lr <= 0, a
+ * beta outside [0, 1), eps <= 0, a negative rho, B < 1 or past int32. */
+int lg_plan_grad_check(const lg_grad_cfg *cfg, const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level, int64_t B);
+/* One evaluation.  DEVICE pointers; z0 (B, 2), v (B, N, 2) required, e, v_prev, w0, offset, level as lg_plan_score takes them, per
+ * plan.  Outputs: J (B), grad (B, N, 2) = dJ/dv; cost (B), min_clear (B), pen (B, 3) optional (NULL = not written).  Of cfg only the
+ * rho are read (the rest is still checked).  A plan's outputs do not depend on B or on its place in a tile; no atomics. */
+int lg_plan_grad(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *v, const float *e,
+                 const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *J,
+                 float *grad, float *cost, float *min_clear, float *pen, void *stream);
+/* One iteration `it` (cfg->iters is not read) in one launch: what = 1 evaluates the plans in v (B, N, 2); what = 3 also steps them
+ * in place (the step is fused into the launch that makes the gradient, so 2 alone is refused).  Evaluation: J (B) required; grad,
+ * cost, min_clear, pen optional as above; the elite best_J (B), best_v (B, N, 2) takes the plan evaluated wherever J is finite and
+ * J < best_J; hist_row (B, 2) optional = (J, max |dJ/dv|).  Step, per element, every operation rounded on its own, with t = it + 1:
+ * m = beta1 m + (1 - beta1) g; s = beta2 s + ((1 - beta2) g) g; v = clip(v - lr (m / (1 - beta1^t)) / (sqrt(s / (1 - beta2^t)) + eps),
+ * rom_v_min, rom_v_max), the two bias corrections rounded once from double.  A plan whose J or gradient is not finite keeps v, m
+ * and s, and n_bad[b] (int32) counts the step.  reset != 0 starts m, s (B, N, 2), the elite and n_bad afresh, so they need no
+ * initial value; a reset without a finite J leaves best_J = inf and best_v = the plan. */
+int lg_plan_descend_step(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, int32_t it, int32_t what, int32_t reset,
+                         const float *z0, const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level,
+                         float level, int64_t B, float *v, float *J, float *grad, float *cost, float *min_clear, float *pen, float *m,
+                         float *s, float *best_J, float *best_v, float *hist_row, int32_t *n_bad, void *stream);
+/* cfg->iters stepping launches from the plans in v (in-out), then one evaluation-only launch, so that the elite also covers the
+ * last iterate: iters + 1 launches on the stream, no host synchronisation.  J_scratch (B); m, s (B, N, 2), best_J, best_v and n_bad
+ * are started by the call; hist (iters + 1, B, 2) optional. */
+int lg_plan_descend(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *e,
+                    const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *v,
+                    float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

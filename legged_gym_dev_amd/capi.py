@@ -354,6 +354,11 @@ class lg_mppi_cfg(C.Structure):
         ("sigma", f32), ("sigma_decay", f32), ("lambda_", f32), ("rho_g", f32), ("rho_w", f32), ("rho_z", f32)]
 
 
+class lg_grad_cfg(C.Structure):
+    _fields_ = [
+        ("iters", i32), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("rho_g", f32), ("rho_w", f32), ("rho_z", f32)]
+
+
 def declare_plan_api(lib):
     vp = C.c_void_p
     if not hasattr(lib, "lg_plan_score"):          # an A/B library (LG_HIP_LIB) built before the plan entries
@@ -368,6 +373,13 @@ def declare_plan_api(lib):
     lib.lg_plan_mppi_candidates.argtypes = [pp, pc, i32, vp, i64, vp, vp]
     lib.lg_plan_mppi_step.argtypes = [vp, pp, pc, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.lg_plan_mppi.argtypes = [vp, pp, pc, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp, vp]
+    if not hasattr(lib, "lg_plan_grad"):           # an A/B library built before the gradient planner
+        return
+    pg = C.POINTER(lg_grad_cfg)
+    lib.lg_plan_grad_check.argtypes = [pg, pp, vp, i32, i64]
+    lib.lg_plan_grad.argtypes = [vp, pp, pg, vp, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp]
+    lib.lg_plan_descend_step.argtypes = [vp, pp, pg, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, i64] + [vp] * 13
+    lib.lg_plan_descend.argtypes = [vp, pp, pg, vp, vp, vp, vp, vp, i32, f32, i64] + [vp] * 9
 
 
 def declare_env_api(lib, prefix="lg_"):

@@ -4,6 +4,7 @@
 // dataset, stepped by the same two launches with the members along grid y.
 // lg_plan_check / lg_plan_score: plans scored against a one-shot horizon handle or an analytic tube (k_plan_score).
 // lg_mppi_check / lg_plan_mppi*: the sampling planner on top of it (k_plan_sample_score, k_plan_mppi_update).
+// lg_plan_grad_check / lg_plan_grad / lg_plan_descend*: the gradient planner (k_plan_grad).
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -50,6 +51,7 @@ int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, c
                                 const float *vbar, float *J, float *cost, float *min_clear, float *pen, hipStream_t s);
 void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,
                             const float *J, float *best_J, float *best_v, float *hist, int32_t *n_bad, hipStream_t s);
+int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, hipStream_t s);
 }
 
 struct TubeCaps {                       // rows that a model's data-sized buffers hold
@@ -520,6 +522,94 @@ int lg_plan_mppi(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *
     for (int32_t it = 0; it < cfg->iters; ++it) {
         const int rc = lg_plan_mppi_step(tube, prob, cfg, it, 3, it == 0, z0, e, v_prev, w0, offset, has_level, level, P, vbar, J_scratch,
                                          nullptr, nullptr, nullptr, best_J, best_v, hist ? hist + (int64_t)it * P * 2 : nullptr, n_bad, stream);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- gradient planner on a tube
+static std::string grad_reason(const lg_grad_cfg *c, int64_t B) {
+    if (c->iters < 1) return "iters = " + std::to_string(c->iters) + " must be at least 1";
+    if (!(c->lr > 0.f)) return "lr must be positive";
+    if (!(c->beta1 >= 0.f && c->beta1 < 1.f)) return "beta1 must lie in [0, 1)";
+    if (!(c->beta2 >= 0.f && c->beta2 < 1.f)) return "beta2 must lie in [0, 1)";
+    if (!(c->eps > 0.f)) return "eps must be positive";
+    if (!(c->rho_g >= 0.f)) return "rho_g must not be negative";
+    if (!(c->rho_w >= 0.f)) return "rho_w must not be negative";
+    if (!(c->rho_z >= 0.f)) return "rho_z must not be negative";
+    if (B < 1) return "B = " + std::to_string(B) + " must be at least 1";
+    if (B > INT32_MAX) return "B = " + std::to_string(B) + " must not exceed 2^31 - 1";
+    return "";
+}
+
+int lg_plan_grad_check(const lg_grad_cfg *cfg, const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level, int64_t B) {
+    if (lg_plan_check(prob, tube, has_level)) return -1;
+    const std::string e = grad_reason(cfg, B);
+    if (!e.empty()) { lg_set_error("lg_plan_grad: " + e); return -1; }
+    return 0;
+}
+
+static void grad_args(PlanGradArgs *A, const lg_grad_cfg *cfg, const float *z0, const float *e, const float *v_prev, const float *w0,
+                      const float *offset, int32_t has_level, float level) {
+    memset(A, 0, sizeof(*A));
+    A->z0 = z0; A->e = e; A->v_prev = v_prev; A->w0 = w0; A->offset = offset;
+    A->level = has_level ? level : 0.f;
+    A->lr = cfg->lr; A->beta1 = cfg->beta1; A->beta2 = cfg->beta2; A->eps = cfg->eps; A->bc1 = 1.f; A->bc2 = 1.f;
+    A->rho_g = cfg->rho_g; A->rho_w = cfg->rho_w; A->rho_z = cfg->rho_z;
+}
+
+int lg_plan_grad(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *v, const float *e,
+                 const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *J,
+                 float *grad, float *cost, float *min_clear, float *pen, void *stream) {
+    if (lg_plan_grad_check(cfg, prob, tube, has_level, B)) return -1;
+    if (!z0 || !v || !J || !grad) { lg_set_error("lg_plan_grad: missing array (z0, v, J and grad are required)"); return -1; }
+    PlanGradArgs A;
+    grad_args(&A, cfg, z0, e, v_prev, w0, offset, has_level, level);
+    A.v = const_cast<float *>(v);       // read only: no step in this launch
+    A.J = J; A.grad = grad; A.cost = cost; A.min_clear = min_clear; A.pen = pen;
+    const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
+    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, (hipStream_t)stream) < 0) {
+        lg_set_error("lg_plan_grad: hipFuncSetAttribute failed"); return -2;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_grad: launch failed"), -3);
+}
+
+int lg_plan_descend_step(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, int32_t it, int32_t what, int32_t reset,
+                         const float *z0, const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level,
+                         float level, int64_t B, float *v, float *J, float *grad, float *cost, float *min_clear, float *pen, float *m,
+                         float *s, float *best_J, float *best_v, float *hist_row, int32_t *n_bad, void *stream) {
+    if (lg_plan_grad_check(cfg, prob, tube, has_level, B)) return -1;
+    if (it < 0) { lg_set_error("lg_plan_descend_step: it must not be negative"); return -1; }
+    if (what != 1 && what != 3) {
+        lg_set_error("lg_plan_descend_step: what must be the evaluation (1) or the evaluation and the step (3): the step is fused into "
+                     "the launch that makes the gradient");
+        return -1;
+    }
+    if (!z0 || !v || !J || !best_J || !best_v || !n_bad || ((what & 2) && (!m || !s))) {
+        lg_set_error("lg_plan_descend_step: missing array (z0, v, J, best_J, best_v and n_bad; m and s for the step)"); return -1;
+    }
+    PlanGradArgs A;
+    grad_args(&A, cfg, z0, e, v_prev, w0, offset, has_level, level);
+    A.v = v; A.J = J; A.grad = grad; A.cost = cost; A.min_clear = min_clear; A.pen = pen;
+    A.m = m; A.s = s; A.best_J = best_J; A.best_v = best_v; A.hist = hist_row; A.n_bad = n_bad;
+    A.step = (what & 2) != 0; A.reset = reset != 0;
+    A.bc1 = (float)(1.0 - std::pow((double)cfg->beta1, (double)it + 1.0));     // step index t = it + 1
+    A.bc2 = (float)(1.0 - std::pow((double)cfg->beta2, (double)it + 1.0));
+    const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
+    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, (hipStream_t)stream) < 0) {
+        lg_set_error("lg_plan_descend_step: hipFuncSetAttribute failed"); return -2;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_descend_step: launch failed"), -3);
+}
+
+int lg_plan_descend(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *e,
+                    const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *v,
+                    float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream) {
+    if (lg_plan_grad_check(cfg, prob, tube, has_level, B)) return -1;
+    for (int32_t it = 0; it <= cfg->iters; ++it) {  // iters stepping launches, then the evaluation of the last iterate
+        const int rc = lg_plan_descend_step(tube, prob, cfg, it, it < cfg->iters ? 3 : 1, it == 0, z0, e, v_prev, w0, offset, has_level,
+                                            level, B, v, J_scratch, nullptr, nullptr, nullptr, nullptr, m, s, best_J, best_v,
+                                            hist ? hist + (int64_t)it * B * 2 : nullptr, n_bad, stream);
         if (rc) return rc;
     }
     return 0;

@@ -447,16 +447,10 @@ __device__ __forceinline__ PlanWalk plan_walk(const lg_plan_problem &p, bool nn,
     return W;
 }
 
-// Dynamic LDS: X (R, I) the items -- for an analytic kind the plan's inputs alone --, H0, H1 (R, U) (NN kind), FW (R, N), ZW (R, PLAN_ZS).
-__global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t count) {
-    extern __shared__ float lds[];
-    const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
-    const bool nn = P.p.tube_kind == LG_PLAN_TUBE_NN;
-    const int U = nn ? D.units : 0, L = D.layers, ZS = PLAN_ZS(N);
-    const int64_t base = (int64_t)blockIdx.x * R;
-    const int nr = (int)(count - base < R ? count - base : R);
-    float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N;
-    // the ScalarHorizonTubeDataset item at start = H_rev of w = e, z = none, v = cat(v_prev, v), straight into the tile
+// The tile's items: the ScalarHorizonTubeDataset item at start = H_rev of w = e, z = none, v = cat(v_prev, v) of plans base .. base + nr - 1,
+// straight into X (R, I); rows past nr are zeros.  Shared by k_plan_score and k_plan_grad.
+__device__ __forceinline__ void plan_gather(const PlanDev &P, float *X, int64_t base, int nr, int tid) {
+    const int N = P.p.N, I = P.I, Hr = P.Hr;
     for (int e = tid; e < R * I; e += NT) {
         const int r = e / I, c = e - r * I;
         float x = 0.f;
@@ -471,6 +465,18 @@ __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t
         }
         X[e] = x;
     }
+}
+
+// Dynamic LDS: X (R, I) the items -- for an analytic kind the plan's inputs alone --, H0, H1 (R, U) (NN kind), FW (R, N), ZW (R, PLAN_ZS).
+__global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t count) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
+    const bool nn = P.p.tube_kind == LG_PLAN_TUBE_NN;
+    const int U = nn ? D.units : 0, L = D.layers, ZS = PLAN_ZS(N);
+    const int64_t base = (int64_t)blockIdx.x * R;
+    const int nr = (int)(count - base < R ? count - base : R);
+    float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N;
+    plan_gather(P, X, base, nr, tid);
     __syncthreads();
     if (nn) {
         const float *in = X;
@@ -701,6 +707,225 @@ __global__ void __launch_bounds__(NT) k_plan_mppi_update(MppiDev M) {
         if (M.hist) { M.hist[p * 2] = J0; M.hist[p * 2 + 1] = Jmin; }
         const int bad = best < 0;
         M.n_bad[p] = M.reset ? bad : M.n_bad[p] + bad;
+    }
+}
+
+// ------------------------------------------------------------------ gradient planner on a tube
+// J = ((cost + rho_g pen_g) + rho_w pen_w) + rho_z pen_z of R plans per workgroup and dJ/dv of every plan by a reverse sweep in the
+// same workgroup, with projected Adam and the elite fused behind it.  No atomics; a plan's outputs depend on its own row alone.
+//
+// One Linear layer backwards for a tile of R rows, in place: h (R, K) holds the layer's activated input and takes
+// dIn[r][k] = act'(h[r][k]) * sum_j delta[r][j] W[j][k], W = the layer's weights as the parameters keep them ([j][k], lanes across k),
+// each sum one fmaf chain from 0 with j ascending.  No thread reads another's h, so in place needs no second buffer.
+__device__ __forceinline__ void tube_layer_back(int tid, int K, int No, const float *delta, const float *w, float *h, int act, float beta) {
+    for (int e = tid; e < K * (R / RB); e += NT) {
+        const int k = e % K, r0 = (e / K) * RB;
+        float acc[RB];
+#pragma unroll
+        for (int q = 0; q < RB; ++q) acc[q] = 0.f;
+#pragma unroll 8
+        for (int j = 0; j < No; ++j) {
+            const float wv = w[j * K + k];
+#pragma unroll
+            for (int q = 0; q < RB; ++q) acc[q] = fmaf(delta[(r0 + q) * No + j], wv, acc[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < RB; ++q) h[(r0 + q) * K + k] = tube_act_grad(act, h[(r0 + q) * K + k], beta) * acc[q];
+    }
+}
+
+// plan_walk in reverse, one lane per plan, every operation rounded on its own.  zw: the nodes plan_walk left; vr: the plan's inputs.
+// Nodes k = N..1 (z0 and w0 get no gradient).  Per node the local adjoints, each one chain in this order: the state (goal) term
+// d (M + M'), then per obstacle i ascending where g < 0 strictly (the hinge max(0, -g); g recomputed by plan_walk's own expression)
+// -rho_g 2 (z - c_i) for z and +rho_g 2 (r_i + w) for w, then +-rho_z where a state bound is passed strictly; for w: 2 Qw w first,
+// rho_w where w > w_max last.  a = sum_{j >= k} dJ/dz_j, nodes descending.  Left behind: dfw[k-1] = dJ/dw_k = dJ/dfw[k-1] (the
+// offset is a constant), and in the slots of node k, zw[3k + d], dJ/dv[k-1][d] = v (R + R') + dt a, without the tube's part.
+// Analytic kinds then add the tube's part in the same lane, steps i ascending: db = dJ/dfw[i], or for a rolling kind the window's
+// transposed mean sum_{k = i..min(i + window - 1, N - 1)} dJ/dfw[k] / (k - k0(k) + 1), k ascending from 0; times scaling sign(v)
+// (l1, 0 at 0) or (2 scaling) v (l2).
+__device__ __forceinline__ void plan_walk_back(const lg_plan_problem &p, bool nn, const float *vr, float *dfw, float *zw, float rho_g,
+                                               float rho_w, float rho_z) {
+#pragma clang fp contract(off)
+    const int N = p.N;
+    const float *Ri = plan_input_cost(p);
+    float ax = 0.f, ay = 0.f;
+    for (int k = N; k >= 1; --k) {
+        const float zx = zw[3 * k], zy = zw[3 * k + 1], wk = zw[3 * k + 2];
+        const float *M = k < N ? p.Q : p.Qf;
+        const float d0 = zx - p.goal[0], d1 = zy - p.goal[1];
+        float lx = (M[0] + M[0]) * d0 + (M[1] + M[2]) * d1;
+        float ly = (M[1] + M[2]) * d0 + (M[3] + M[3]) * d1;
+        float lw = (2.f * p.Qw) * wk;
+        for (int i = 0; i < p.n_obs; ++i) {
+            const float dx = zx - p.obs_c[i][0], dy = zy - p.obs_c[i][1], rr = p.obs_r[i] + wk;
+            const float g = (dx * dx + dy * dy) - rr * rr;
+            if (g < 0.f) {
+                lx = lx - rho_g * (2.f * dx);
+                ly = ly - rho_g * (2.f * dy);
+                lw = lw + rho_g * (2.f * rr);
+            }
+        }
+        if (zx - p.rom_z_max[0] > 0.f) lx = lx + rho_z;
+        if (p.rom_z_min[0] - zx > 0.f) lx = lx - rho_z;
+        if (zy - p.rom_z_max[1] > 0.f) ly = ly + rho_z;
+        if (p.rom_z_min[1] - zy > 0.f) ly = ly - rho_z;
+        if (wk - p.w_max > 0.f) lw = lw + rho_w;
+        ax = ax + lx; ay = ay + ly;
+        dfw[k - 1] = lw;
+        const float vx = vr[2 * (k - 1)], vy = vr[2 * (k - 1) + 1];
+        zw[3 * k] = ((Ri[0] + Ri[0]) * vx + (Ri[1] + Ri[2]) * vy) + p.dt * ax;
+        zw[3 * k + 1] = ((Ri[1] + Ri[2]) * vx + (Ri[3] + Ri[3]) * vy) + p.dt * ay;
+    }
+    if (nn) return;
+    const bool l1 = p.tube_kind == LG_PLAN_TUBE_L1 || p.tube_kind == LG_PLAN_TUBE_L1_ROLLING;
+    const bool rolling = p.tube_kind == LG_PLAN_TUBE_L1_ROLLING || p.tube_kind == LG_PLAN_TUBE_L2_ROLLING;
+    const int ws = p.window_size < N ? p.window_size : N;
+    for (int i = 0; i < N; ++i) {
+        float db = dfw[i];
+        if (rolling) {
+            const int k1 = i + ws - 1 < N - 1 ? i + ws - 1 : N - 1;
+            db = 0.f;
+            for (int k = i; k <= k1; ++k) {
+                const int k0 = k - ws + 1 > 0 ? k - ws + 1 : 0;
+                db = db + dfw[k] / (float)(k - k0 + 1);
+            }
+        }
+        const float vx = vr[2 * i], vy = vr[2 * i + 1];
+        const float tx = l1 ? p.scaling * (float)((vx > 0.f) - (vx < 0.f)) : (2.f * p.scaling) * vx;
+        const float ty = l1 ? p.scaling * (float)((vy > 0.f) - (vy < 0.f)) : (2.f * p.scaling) * vy;
+        zw[3 * (i + 1)] = zw[3 * (i + 1)] + db * tx;
+        zw[3 * (i + 1) + 1] = zw[3 * (i + 1) + 1] + db * ty;
+    }
+}
+
+// Dynamic LDS: X (R, I) the items as in k_plan_score, H_l (R, U) per hidden layer l (every activated output is kept for the reverse
+// sweep), FW (R, N): the tube values, then dJ/dfw in place, ZW (R, PLAN_ZS): the nodes, then per row [J, elite flag, bad flag] in node
+// 0's slots and dJ/dv[k][d] in slot 3 (k + 1) + d.
+//   1. gather, tube_layer per layer, plan_walk<true>: k_plan_sample_score's forward, so J and its parts are that kernel's bits.
+//   2. plan_walk_back in the lane that walked the plan.
+//   3. NN kind: delta of the output layer = dJ/dfw; tube_layer_back per hidden layer, last to first, in place over H_l; of the first
+//      layer's input gradient only the 2 N plan columns are formed -- sum_j delta_0[r][j] W_0[j][3 H_rev + c], one fmaf chain from 0,
+//      j ascending -- and dJ/dv = (the lane's term) + (that sum).
+//   4. the lane: bad = J or some dJ/dv not finite; hist = (J, max |dJ/dv|); the elite takes the plan evaluated where J is finite and
+//      (reset or J < best_J), before any step; n_bad counts the steps refused.
+//   5. per plan element, coalesced: grad out, best_v, and with `step` Adam on (m, s) and the projection clip(v, v_min, v_max),
+//      every operation rounded on its own: m = beta1 m + (1 - beta1) g; s = beta2 s + ((1 - beta2) g) g;
+//      v = clip(v - lr (m / bc1) / (sqrt(s / bc2) + eps)).  A bad plan keeps v, m and s.
+struct GradDev {                        // passed by value
+    float *v, *J, *grad, *pen, *m, *s, *best_J, *best_v, *hist;
+    int32_t *n_bad;
+    int step, reset;
+    float lr, beta1, beta2, eps, bc1, bc2, rho_g, rho_w, rho_z;
+    float v_min[2], v_max[2];
+};
+
+__global__ void __launch_bounds__(NT) k_plan_grad(TubeDev D, PlanDev P, GradDev G, int64_t count) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
+    const bool nn = P.p.tube_kind == LG_PLAN_TUBE_NN;
+    const int U = nn ? D.units : 0, L = nn ? D.layers : 0, ZS = PLAN_ZS(N);
+    const int64_t base = (int64_t)blockIdx.x * R;
+    const int nr = (int)(count - base < R ? count - base : R);
+    float *X = lds, *H = X + R * I, *FW = H + R * U * L, *ZW = FW + R * N;
+    plan_gather(P, X, base, nr, tid);
+    __syncthreads();
+    if (nn) {
+        const float *in = X;
+        for (int li = 0; li < L; ++li) {
+            float *out = H + li * R * U;
+            tube_layer<R, RB, NT, false>(tid, D.din[li], U, in, D.wt + D.off_w[li], D.params + D.off_b[li], D.act, D.sp_beta, out, nullptr, 0, 0);
+            __syncthreads();
+            in = out;
+        }
+        tube_layer<R, RB, NT, true>(tid, D.din[L], N, in, D.wt + D.off_w[L], D.params + D.off_b[L], D.act, D.sp_beta, FW, nullptr, N, 0);
+        __syncthreads();
+    }
+    if (tid < nr) {
+#pragma clang fp contract(off)
+        const int64_t b = base + tid;
+        float *zw = ZW + tid * ZS;
+        const float *vr = X + tid * I + 3 * Hr;
+        const PlanWalk W = plan_walk<true>(P.p, nn, vr, FW + tid * N, zw, P.z0[b * 2], P.z0[b * 2 + 1], P.w0 ? P.w0[b] : 0.f, P.offset);
+        const float J = ((W.cost + G.rho_g * W.pen_g) + G.rho_w * W.pen_w) + G.rho_z * W.pen_z;
+        G.J[b] = J;
+        if (P.cost) P.cost[b] = W.cost;
+        if (P.min_clear) P.min_clear[b] = W.minc;
+        if (G.pen) { G.pen[b * 3] = W.pen_g; G.pen[b * 3 + 1] = W.pen_w; G.pen[b * 3 + 2] = W.pen_z; }
+        plan_walk_back(P.p, nn, vr, FW + tid * N, zw, G.rho_g, G.rho_w, G.rho_z);
+        zw[0] = J;
+    }
+    __syncthreads();
+    if (nn) {
+        const float *delta = FW;
+        int No = N;
+        for (int li = L; li >= 1; --li) {           // layer li: U inputs (hidden layer li - 1's output), No outputs
+            float *h = H + (li - 1) * R * U;
+            tube_layer_back(tid, U, No, delta, D.params + D.off_w[li], h, D.act, D.sp_beta);
+            __syncthreads();
+            delta = h; No = U;
+        }
+        const float *w0 = D.params + D.off_w[0] + 3 * Hr;
+        for (int e = tid; e < 2 * N * (R / RB); e += NT) {
+            const int c = e % (2 * N), r0 = (e / (2 * N)) * RB;
+            float acc[RB];
+#pragma unroll
+            for (int q = 0; q < RB; ++q) acc[q] = 0.f;
+#pragma unroll 8
+            for (int j = 0; j < No; ++j) {
+                const float wv = w0[j * I + c];
+#pragma unroll
+                for (int q = 0; q < RB; ++q) acc[q] = fmaf(delta[(r0 + q) * No + j], wv, acc[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < RB; ++q) {
+                float *g = ZW + (r0 + q) * ZS + 3 * ((c >> 1) + 1) + (c & 1);
+                if (r0 + q < nr) *g = *g + acc[q];
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < nr) {
+        const int64_t b = base + tid;
+        float *zw = ZW + tid * ZS;
+        const float J = zw[0];
+        bool fin = mppi_finite(J);
+        float gmax = 0.f;
+        for (int k = 1; k <= N; ++k) {
+            const float gx = zw[3 * k], gy = zw[3 * k + 1];
+            fin = fin && mppi_finite(gx) && mppi_finite(gy);
+            gmax = fmaxf(gmax, fmaxf(fabsf(gx), fabsf(gy)));
+        }
+        bool improved = false;
+        if (G.best_J) {
+            improved = mppi_finite(J) && (G.reset || J < G.best_J[b]);
+            if (improved) G.best_J[b] = J;
+            else if (G.reset) G.best_J[b] = INFINITY;
+        }
+        if (G.n_bad) G.n_bad[b] = (G.reset ? 0 : G.n_bad[b]) + (G.step && !fin ? 1 : 0);
+        if (G.hist) { G.hist[b * 2] = J; G.hist[b * 2 + 1] = gmax; }
+        zw[1] = improved ? 1.f : 0.f;
+        zw[2] = fin ? 0.f : 1.f;
+    }
+    __syncthreads();
+    for (int e = tid; e < nr * 2 * N; e += NT) {
+#pragma clang fp contract(off)
+        const int r = e / (2 * N), c = e - r * 2 * N, d = c & 1;
+        const float *zw = ZW + r * ZS;
+        const float g = zw[3 * ((c >> 1) + 1) + d], v = X[r * I + 3 * Hr + c];
+        const bool bad = zw[2] != 0.f;
+        const int64_t o = base * 2 * N + e;
+        if (G.grad) G.grad[o] = g;
+        if (G.best_v && (G.reset || zw[1] != 0.f)) G.best_v[o] = v;     // a reset without a finite J: best_J = inf, best_v = the plan
+        if (G.step) {
+            float m = G.reset ? 0.f : G.m[o], s = G.reset ? 0.f : G.s[o];
+            if (!bad) {
+                m = G.beta1 * m + (1.f - G.beta1) * g;
+                s = G.beta2 * s + ((1.f - G.beta2) * g) * g;
+                const float x = v - (G.lr * (m / G.bc1)) / (sqrtf(s / G.bc2) + G.eps);
+                G.v[o] = fminf(fmaxf(x, G.v_min[d]), G.v_max[d]);
+            }
+            if (G.reset || !bad) { G.m[o] = m; G.s[o] = s; }
+        }
     }
 }
 
@@ -1029,6 +1254,46 @@ void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg,
     M.vbar_in = vbar; M.vbar = vbar; M.J = const_cast<float *>(J); M.best_J = best_J; M.best_v = best_v; M.hist = hist; M.n_bad = n_bad;
     M.reset = reset;
     hipLaunchKernelGGL(k_plan_mppi_update, dim3((unsigned)P_), dim3(NT), sizeof(float) * (size_t)cfg->K, s, M);
+}
+
+// k_plan_grad.  Its tile keeps every hidden layer's output, so the largest shape of the envelope -- 256
+// inputs, 4 x 128 units, N = 64 -- takes 128.4 KiB at R = 32 rows and stays below the ceiling; no smaller tile is needed:
+static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + (LG_TUBE_MAX_LIN - 1) * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N)) <=
+                  LG_TUBE_ROLLOUT_LDS,
+              "k_plan_grad: the envelope's largest tile set must fit the dynamic LDS ceiling");
+static_assert(PLAN_ZS(1) >= 6, "k_plan_grad keeps J, two flags and dJ/dv of step 0 in a row of nodes at N = 1 too");
+// returns the dynamic LDS of the launch in bytes, or -1 where the kernel's ceiling cannot be set
+int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, hipStream_t s) {
+    PlanDev P;
+    memset(&P, 0, sizeof(P));
+    TubeDev T;
+    memset(&T, 0, sizeof(T));
+    if (D) T = *D;
+    const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
+    P.p = *prob;
+    P.z0 = A->z0; P.v = A->v; P.e = nn ? A->e : nullptr; P.v_prev = nn ? A->v_prev : nullptr; P.w0 = A->w0; P.offset = A->offset;
+    P.cost = A->cost; P.min_clear = A->min_clear;
+    P.level = A->level;
+    P.Hr = nn ? prob->H_rev : 0;
+    P.I = nn ? T.in_dim : 2 * prob->N;
+    GradDev G;
+    memset(&G, 0, sizeof(G));
+    G.v = A->v; G.J = A->J; G.grad = A->grad; G.pen = A->pen; G.m = A->m; G.s = A->s; G.best_J = A->best_J; G.best_v = A->best_v;
+    G.hist = A->hist; G.n_bad = A->n_bad;
+    G.step = A->step; G.reset = A->reset;
+    G.lr = A->lr; G.beta1 = A->beta1; G.beta2 = A->beta2; G.eps = A->eps; G.bc1 = A->bc1; G.bc2 = A->bc2;
+    G.rho_g = A->rho_g; G.rho_w = A->rho_w; G.rho_z = A->rho_z;
+    for (int d = 0; d < 2; ++d) { G.v_min[d] = prob->rom_v_min[d]; G.v_max[d] = prob->rom_v_max[d]; }
+    const size_t bytes = sizeof(float) * (size_t)R * (P.I + (nn ? T.layers * T.units : 0) + prob->N + PLAN_ZS(prob->N));
+    static bool ceiling_set[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    if (dev < 0 || dev >= 64 || !ceiling_set[dev]) {
+        if (hipFuncSetAttribute((const void *)k_plan_grad, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
+        if (dev >= 0 && dev < 64) ceiling_set[dev] = true;
+    }
+    hipLaunchKernelGGL(k_plan_grad, dim3((unsigned)((B + R - 1) / R)), dim3(NT), bytes, s, T, P, G, B);
+    return (int64_t)bytes;
 }
 
 size_t tubek_lds_bytes(const TubeDev *D) {

@@ -1,14 +1,17 @@
 """Plan through a problem with a tube: the reference's trajopt/tube_trajopt.py (one plan) and trajopt/tube_planning_closed_loop.py
 (replanning at every step) with a sampling planner -- batched MPPI on the HIP kernels (legged_gym_dev_amd/tube/plan.py; DESIGN.md
-section 10.10) -- in place of CasADi / IPOPT, for many starts at once.
+section 10.10) --, a first-order one -- projected Adam on the HIP plan gradient (section 10.11) -- or the second after the first, in
+place of CasADi / IPOPT, for many starts at once.
 
     python legged_gym_dev_amd/scripts/plan_tube.py (--run tube_runs/run0 | --tube l1|l2|l1_rolling|l2_rolling [--scaling s] [--window_size n]) \\
         --problem gap|right|right_wide|F.json [--level l] [--calibration [PATH]] [--coverage c] \\
         [--K 256] [--iters 20] [--sigma 0.3] [--sigma_decay 1] [--lambda 1] [--rho_g 1e4] [--rho_w 0] [--rho_z 0] [--seed 0] \\
+        [--planner mppi|grad|mppi+grad] [--lr 0.05] [--grad_iters 100] \\
         [--starts P --start_noise s] [--closed_loop H] [--sim_cfg KEY=VALUE ...] [--out DIR]
 
 --run, --tube, --calibration, --coverage, --level, --checkpoint, --sim_cfg: as audit_plans.py takes them; a run that audit_plans.py
-refuses (not a one-shot tube) is refused here.  --problem: one of the reference's problems, or a PlanProblem as JSON (a path ending
+refuses (not a one-shot tube) is refused here.  --planner: mppi (the default), grad (--grad_iters steps of rate --lr from the warm start; the rho are shared) or mppi+grad (MPPI,
+then the gradient planner from MPPI's best plan).  --problem: one of the reference's problems, or a PlanProblem as JSON (a path ending
 in .json).  --starts P: P instances; the first starts at the problem's start, the others at start + start_noise * standard normal.
 Without --closed_loop every start gets one plan, which is scored, tracked and audited as audit_plans.py does.  With --closed_loop H
 every robot replans at each of H control steps (closed_loop) and the audit is audit_closed_loop's.
@@ -52,6 +55,10 @@ def parse_args(argv=None):
     ap.add_argument("--rho_w", type=float, default=d.rho_w)
     ap.add_argument("--rho_z", type=float, default=d.rho_z)
     ap.add_argument("--seed", type=int, default=0)
+    g = pl.GradCfg()
+    ap.add_argument("--planner", choices=PLANNERS, default="mppi")
+    ap.add_argument("--lr", type=float, default=g.lr)
+    ap.add_argument("--grad_iters", type=int, default=g.iters)
     ap.add_argument("--starts", type=int, default=1)
     ap.add_argument("--start_noise", type=float, default=0.0)
     ap.add_argument("--closed_loop", type=int, default=None, metavar="H")
@@ -71,15 +78,35 @@ def parse_args(argv=None):
     if a.closed_loop is not None and a.closed_loop < 1:
         ap.error("--closed_loop H: at least 1 step")
     try:
-        mppi_cfg(a).check(a.starts)
+        if "mppi" in a.planner:
+            mppi_cfg(a).check(a.starts)
+        if "grad" in a.planner:
+            grad_cfg(a).check(a.starts)
     except ValueError as e:
         ap.error(str(e))
     return a
 
 
+PLANNERS = ("mppi", "grad", "mppi+grad")
+
+
 def mppi_cfg(a):
     return pl.MppiCfg(K=a.K, iters=a.iters, seed=a.seed, sigma=a.sigma, sigma_decay=a.sigma_decay, lambda_=a.lambda_, rho_g=a.rho_g,
                       rho_w=a.rho_w, rho_z=a.rho_z)
+
+
+def grad_cfg(a):
+    return pl.GradCfg(iters=a.grad_iters, lr=a.lr, rho_g=a.rho_g, rho_w=a.rho_w, rho_z=a.rho_z)
+
+
+def make_planner(a, model, p, calib):
+    """The planner --planner names, on one scorer's arguments."""
+    kw = dict(calibration=calib, level=a.level, coverage=a.coverage, device=a.device)
+    if a.planner == "mppi":
+        return pl.HipMppiPlanner(model, p, mppi_cfg(a), **kw)
+    if a.planner == "grad":
+        return pl.HipGradPlanner(model, p, grad_cfg(a), **kw)
+    return pl.ChainedPlanner(pl.HipMppiPlanner(model, p, mppi_cfg(a), **kw), pl.HipGradPlanner(model, p, grad_cfg(a), **kw))
 
 
 def build_problem(a, cfg):
@@ -121,7 +148,7 @@ def main(argv=None):
     try:
         if a.run:
             model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, device=a.device)
-        planner = pl.HipMppiPlanner(model, p, mppi_cfg(a), calibration=calib, level=a.level, coverage=a.coverage, device=a.device)
+        planner = make_planner(a, model, p, calib)
         sim = HipRomSim(audit_plans.sim_config(a, p), device=a.device)
         if a.closed_loop is None:
             sol = planner.plan(z0)
@@ -148,6 +175,8 @@ def main(argv=None):
     out = {"audit": audit, "hist": hist.cpu().double().tolist(), "closed_loop": a.closed_loop, "starts": z0.double().tolist(),
            "mppi": {**{k: v for k, v in vars(mppi_cfg(a)).items() if k != "lambda_"}, "lambda": a.lambda_}, "problem": p.to_json(),
            "run": a.run, "tube": a.tube or "nn", "level": a.level, "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), **extra}
+    if a.planner != "mppi":
+        out.update({"planner": a.planner, "grad": vars(grad_cfg(a))})
     folder = a.out or a.run or "."
     os.makedirs(folder, exist_ok=True)
     with open(os.path.join(folder, "plan.json"), "w") as f:

@@ -5,7 +5,8 @@ A plan is a start ``z0`` (2) and ``N`` inputs ``v`` (N, 2) of the SingleInt2D RO
 (trajopt/tube_trajopt.py, "TT"): the one-shot tube query :561-568, the obstacle constraint inflated by the tube :59-97, the quadratic
 objective :41-56,206-212, the analytic baseline tubes :489-540 and the problems ``gap``, ``right``, ``right_wide`` :11-21; the tracking
 loop is deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.py:75-88.  The plans come from any solver, from
-``warm_start`` and ``perturb``, or from the sampling planner below (``HipMppiPlanner``, ``closed_loop``; section 10.10), which stands in
+``warm_start`` and ``perturb``, or from the planners below -- the sampling ``HipMppiPlanner`` (section 10.10), the first-order
+``HipGradPlanner`` (section 10.11), or one after the other (``ChainedPlanner``) -- in ``closed_loop`` or alone, which stand in
 for the reference's NLP solve.  There is no CPU fallback: scoring, planning and tracking need the library and a GPU.
 """
 import ctypes as C
@@ -470,6 +471,165 @@ class HipMppiPlanner:
         return {"v": st["vbar"], "best_v": st["best_v"], "best_J": st["best_J"], "hist": hist, "n_bad": st["n_bad"],
                 "score": sc.score(st["z0"], st["vbar"], st["e"], st["v_prev"], st["w0"], want=want),
                 "best_score": sc.score(st["z0"], st["best_v"], st["e"], st["v_prev"], st["w0"], want=want)}
+
+
+# ---------------------------------------------------------------- the gradient planner
+@dataclasses.dataclass
+class GradCfg:
+    """lg_grad_cfg, field for field: projected Adam on J = cost + rho_g pen_g + rho_w pen_w + rho_z pen_z (MppiCfg's objective),
+    whose gradient k_plan_grad makes by a reverse sweep in the scoring tile.  iters stepping launches; the projection is the clip
+    to rom_v_min / rom_v_max."""
+    iters: int = 100
+    lr: float = 0.05
+    beta1: float = 0.9
+    beta2: float = 0.999
+    eps: float = 1e-8
+    rho_g: float = 1e4
+    rho_w: float = 0.0
+    rho_z: float = 0.0
+
+    def check(self, B=1):
+        """ValueError in lg_plan_grad_check's words, the field named."""
+        if self.iters < 1:
+            raise ValueError(f"iters = {self.iters} must be at least 1")
+        if not self.lr > 0:
+            raise ValueError("lr must be positive")
+        for name in ("beta1", "beta2"):
+            if not 0 <= getattr(self, name) < 1:
+                raise ValueError(f"{name} must lie in [0, 1)")
+        if not self.eps > 0:
+            raise ValueError("eps must be positive")
+        for name in ("rho_g", "rho_w", "rho_z"):
+            if not getattr(self, name) >= 0:
+                raise ValueError(f"{name} must not be negative")
+        if B < 1:
+            raise ValueError(f"B = {B} must be at least 1")
+        if B > 2 ** 31 - 1:
+            raise ValueError(f"B = {B} must not exceed 2^31 - 1")
+
+    def to_struct(self, iters=None):
+        c = capi.lg_grad_cfg()
+        c.iters = int(self.iters if iters is None else iters)
+        c.lr, c.beta1, c.beta2, c.eps = float(self.lr), float(self.beta1), float(self.beta2), float(self.eps)
+        c.rho_g, c.rho_w, c.rho_z = float(self.rho_g), float(self.rho_w), float(self.rho_z)
+        return c
+
+
+class HipGradPlanner:
+    """lg_plan_grad / lg_plan_descend on one problem for P plans at once, built on a HipPlanScorer the way HipMppiPlanner is: the
+    handle, offset, level and envelope checks are the scorer's.  The arguments after cfg are HipPlanScorer's."""
+
+    warm_start = HipMppiPlanner.warm_start
+    _fail = HipMppiPlanner._fail
+    _stream = HipMppiPlanner._stream
+
+    def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None):
+        cfg.check()
+        self.scorer = HipPlanScorer(model, problem, calibration=calibration, level=level, coverage=coverage, device=device)
+        self.problem, self.cfg, self.device, self.lib = problem, cfg, self.scorer.device, self.scorer.lib
+        self._err = self.scorer._err
+
+    def state(self, z0, v, e=None, v_prev=None, w0=None, want=()):
+        """The device arrays of a run: z0 (P, 2), e, v_prev, w0 (None = zeros), the plans v (P, N, 2) (copied), J (P), the Adam
+        moments m, s, best_J, best_v, n_bad and whatever of grad (P, N, 2), cost, min_clear (P), pen (P, 3) `want` names."""
+        import torch
+        p, dev = self.problem, self.device
+        f32 = lambda t: None if t is None else torch.as_tensor(t).to(dev, torch.float32).contiguous()
+        z0, e, v_prev, w0 = f32(z0), f32(e), f32(v_prev), f32(w0)
+        v = torch.as_tensor(v).to(dev, torch.float32).clone().contiguous()
+        if z0.dim() != 2 or z0.shape[1] != 2 or z0.shape[0] < 1:
+            raise ValueError(f"z0 must be (P >= 1, 2); got {tuple(z0.shape)}")
+        P = z0.shape[0]
+        self.cfg.check(P)
+        for name, t, shape in (("v", v, (P, p.N, 2)), ("e", e, (P, p.H_rev)), ("v_prev", v_prev, (P, p.H_rev, 2)), ("w0", w0, (P,))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {shape}; got {tuple(t.shape)}")
+        opt = {"grad": (P, p.N, 2), "cost": (P,), "min_clear": (P,), "pen": (P, 3)}
+        bad = [k for k in want if k not in opt]
+        if bad:
+            raise ValueError(f"want {bad}: of grad, cost, min_clear, pen")
+        st = {"P": P, "z0": z0, "e": e, "v_prev": v_prev, "w0": w0, "v": v, "J": torch.empty(P, device=dev),
+              "m": torch.empty(P, p.N, 2, device=dev), "s": torch.empty(P, p.N, 2, device=dev), "best_J": torch.empty(P, device=dev),
+              "best_v": torch.empty(P, p.N, 2, device=dev), "n_bad": torch.zeros(P, device=dev, dtype=torch.int32)}
+        for k in want:
+            st[k] = torch.empty(opt[k], device=dev)
+        return st
+
+    def _common(self, st):
+        sc = self.scorer
+        return (_ptr(st["e"]), _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset), int(sc.level is not None),
+                float(sc.level if sc.level is not None else 0.0), st["P"])
+
+    def gradient(self, z0, v, e=None, v_prev=None, w0=None, want=("cost", "min_clear", "pen")):
+        """lg_plan_grad: J (B) and grad (B, N, 2) = dJ/dv of the plans v from z0 (B, 2), and whatever of cost, min_clear, pen
+        (B, 3) `want` names, as device tensors."""
+        st = self.state(z0, v, e, v_prev, w0, want=("grad",) + tuple(k for k in want if k != "grad"))
+        sc = self.scorer
+        rc = self.lib.lg_plan_grad(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), _ptr(st["z0"]), _ptr(st["v"]),
+                                   *self._common(st), _ptr(st["J"]), _ptr(st["grad"]), _ptr(st.get("cost")), _ptr(st.get("min_clear")),
+                                   _ptr(st.get("pen")), self._stream())
+        if rc != 0:
+            self._fail("lg_plan_grad", rc)
+        self._keep = st
+        return {k: st[k] for k in ("J", "grad", "cost", "min_clear", "pen") if k in st}
+
+    def step(self, st, it, what=3, reset=False, hist_row=None):
+        """lg_plan_descend_step on a state(): what = 1 evaluates (J, the optional outputs, the elite, hist_row (P, 2)); what = 3
+        also steps v, m and s in place."""
+        sc = self.scorer
+        rc = self.lib.lg_plan_descend_step(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), int(it), int(what), int(bool(reset)),
+                                           _ptr(st["z0"]), *self._common(st), _ptr(st["v"]), _ptr(st["J"]), _ptr(st.get("grad")),
+                                           _ptr(st.get("cost")), _ptr(st.get("min_clear")), _ptr(st.get("pen")), _ptr(st["m"]), _ptr(st["s"]),
+                                           _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]), self._stream())
+        if rc != 0:
+            self._fail("lg_plan_descend_step", rc)
+        return st
+
+    def plan(self, z0, v_init=None, e=None, v_prev=None, w0=None, iters=None):
+        """lg_plan_descend from z0 (P, 2): cfg.iters (or `iters`) steps from the plans v_init (P, N, 2) or (N, 2); None = the clipped
+        `interpolate` warm start.  HipMppiPlanner.plan's keys: v (P, N, 2) the last iterate, best_v, best_J (P) the elite over every
+        iterate, hist (iters + 1, P, 2) = (J, max |dJ/dv|) per evaluation, n_bad (P) int32, score / best_score."""
+        import torch
+        z0 = torch.as_tensor(z0, dtype=torch.float32).reshape(-1, 2)
+        if v_init is None:
+            v_init = self.warm_start(z0.cpu().numpy())
+        v_init = torch.as_tensor(v_init, dtype=torch.float32)
+        if v_init.dim() == 2:
+            v_init = v_init[None].repeat(z0.shape[0], 1, 1)
+        iters = self.cfg.iters if iters is None else int(iters)
+        if iters < 1:
+            raise ValueError(f"iters = {iters} must be at least 1")
+        st = self.state(z0, v_init, e, v_prev, w0)
+        hist = torch.empty(iters + 1, st["P"], 2, device=self.device)
+        sc = self.scorer
+        rc = self.lib.lg_plan_descend(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), _ptr(st["z0"]), *self._common(st),
+                                      _ptr(st["v"]), _ptr(st["J"]), _ptr(st["m"]), _ptr(st["s"]), _ptr(st["best_J"]), _ptr(st["best_v"]),
+                                      _ptr(hist), _ptr(st["n_bad"]), self._stream())
+        if rc != 0:
+            self._fail("lg_plan_descend", rc)
+        want = ("z", "w")
+        return {"v": st["v"], "best_v": st["best_v"], "best_J": st["best_J"], "hist": hist, "n_bad": st["n_bad"],
+                "score": sc.score(st["z0"], st["v"], st["e"], st["v_prev"], st["w0"], want=want),
+                "best_score": sc.score(st["z0"], st["best_v"], st["e"], st["v_prev"], st["w0"], want=want)}
+
+
+class ChainedPlanner:
+    """Two planners on one problem, one after the other: `plan` runs `first` (say MPPI, which finds the homotopy class), then
+    `second` (say the gradient planner, which polishes) from `first`'s best_v.  The result is `second`'s, with `first`'s under
+    the key "first"; closed_loop takes it like either planner."""
+
+    def __init__(self, first, second):
+        if first.problem is not second.problem and first.problem != second.problem:
+            raise ValueError("the two planners of a chain must share one problem")
+        self.first, self.second = first, second
+        self.problem, self.device = first.problem, first.device
+
+    def plan(self, z0, v_init=None, e=None, v_prev=None, w0=None, iters=None):
+        """`iters` goes to `first` (closed_loop's iters_first); `second` always runs its own."""
+        a = self.first.plan(z0, v_init, e, v_prev, w0, iters=iters)
+        b = dict(self.second.plan(z0, a["best_v"], e, v_prev, w0))
+        b["first"] = a
+        return b
 
 
 def shift_plan(v):
