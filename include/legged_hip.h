@@ -138,11 +138,20 @@ typedef struct lg_xterm {
 /* generator classes (trajectory_generator.cls; rom_dynamics.py:441-699) and weight samplers (weight_samp_cls; deep_tube_learning/
  * utils.py:27-79), chosen per context by lg_set_traj_generator.  RANDOM is TrajectoryGenerator, the training generator; ZERO,
  * SQUARE and CIRCLE are the fixed evaluation paths (no draws: their resample never samples).  The weight sampler only matters for
- * RANDOM: NO_RAMP zeroes the ramp weight before normalising. */
+ * RANDOM: NO_RAMP zeroes the ramp weight before normalising.
+ * PLAN (trajectory_generator.cls = 'PlanTrajectoryGenerator') is THIS PROJECT'S OWN class, not one of rom_dynamics.py: every env
+ * follows a plan of its own -- n_nodes ROM inputs handed in by lg_traj_set_plans, piecewise constant per ROM step and indexed by the
+ * env's ROM step counter LG_TG_K: the ROM step that takes k to k + 1 advances the window with v_plan[env][k] for 0 <= k < n_nodes and
+ * with 0 otherwise (the reset's pre-roll at k < 0, past the plan's end, before any plan was set).  It draws nothing, is never
+ * stationary, uses the inputs as given (bounds are the host's business) and leaves LG_TG_V = the input last applied to the window
+ * (the ROM interval in force).  A reset env replays its plan from node 0 at its new root position.  It is what lets the env track
+ * the plans of tube/plan.py the way deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.py:75-132 lets its ROM
+ * stand-in track them (legged_gym_dev_amd/tube/plan_env.py). */
 #define LG_TG_KIND_RANDOM 0
 #define LG_TG_KIND_ZERO 1
 #define LG_TG_KIND_SQUARE 2
 #define LG_TG_KIND_CIRCLE 3
+#define LG_TG_KIND_PLAN 4
 #define LG_TG_WSAMP_UNIFORM 0
 #define LG_TG_WSAMP_NO_RAMP 1
 typedef struct lg_traj_cfg {
@@ -318,6 +327,31 @@ int lg_set_traj_generator(lg_ctx *ctx, int kind, int weight_sampler);
  * -N rom_dt, and N ROM steps fill the window -- without touching the rest of the env (the observed trajectory follows at the next
  * step callback).  z: DEVICE f32 (N, 2).  RANDOM draws its resample from the reset slots at the current step counter. */
 int lg_traj_reset(lg_ctx *ctx, const float *z);
+/* Trajectory env of kind LG_TG_KIND_PLAN: the plans of every env, v DEVICE f32 (num_envs, n_nodes, 2), 0 <= n_nodes <= LG_PLAN_MAX_N
+ * (v may be NULL when n_nodes is 0).  A stream-ordered copy into the context's own (num_envs, LG_PLAN_MAX_N, 2) buffer: the
+ * caller's array need not outlive the call.  The ROM step counters are not touched: lg_traj_reset / a reset restart the plans.
+ * Refused (lg_last_error) for a non-trajectory env, a kind other than PLAN, n_nodes out of range, a null v with n_nodes > 0. */
+int lg_traj_set_plans(lg_ctx *ctx, const float *v, int32_t n_nodes);
+/* ROM-rate recorder of the trajectory env (any generator kind), per env and on the device: one small launch per env step, one
+ * lane per env, no host read.  The caller owns the (device) buffers.  lg_traj_rec_begin writes row 0 -- z = trajectory[:, 0] (the
+ * point the robot tracks), pz_x = root xy, x = the state vector in get_state()'s layout (base pose 7, joint positions, base twist
+ * 6, joint velocities) -- and sets rows = 1, dead = 0, k_mark = LG_TG_K.  lg_traj_rec_step, called after an env step, does for
+ * each env: (1) nothing if it is dead; (2) if its reset flag (lg_buffers.reset, the step's dones) is set: dead = 1, rows kept;
+ * (3) otherwise, if LG_TG_K != k_mark and rows < rows_max: row `rows` of z, pz_x (and x), v[rows - 1] = LG_TG_V, rows += 1,
+ * k_mark = LG_TG_K.  So row r of an env is what it was right after its own r-th ROM step since begin. */
+typedef struct lg_traj_rec {
+    int32_t rows_max, x_n;                /* rows per env (>= 2); floats per row of x: 13 + 2 num_actions, or 0 without x */
+    float *z, *pz_x;                      /* (N, rows_max, 2) */
+    float *v;                             /* (N, rows_max - 1, 2) */
+    int32_t *rows;                        /* (N) rows written */
+    uint8_t *dead;                        /* (N) the env reset (termination or time-out) while recording */
+    float *k_mark;                        /* (N) LG_TG_K at the last row */
+    float *x;                             /* (N, rows_max, x_n) or NULL */
+} lg_traj_rec;
+/* host: refuses, the field named in lg_last_error, rows_max < 2, a null required buffer, an x_n that is not env_x_n */
+int lg_traj_rec_check(const lg_traj_rec *rec, int64_t N, int32_t env_x_n);
+int lg_traj_rec_begin(lg_ctx *ctx, const lg_traj_rec *rec);
+int lg_traj_rec_step(lg_ctx *ctx, const lg_traj_rec *rec);
 /* Runs the step's single-workgroup epilogue (extras["episode"], extras["time_outs"], counters) if a learner attached with
  * lg_ppo_attach_env left it pending; a no-op otherwise.  Every env entry point does this itself before it touches the env. */
 int lg_finalize(lg_ctx *ctx);

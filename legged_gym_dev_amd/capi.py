@@ -28,7 +28,8 @@ SIGNALS = {"zero": (0, 8), "base_lin_vel": (1, 3), "base_ang_vel": (2, 3), "proj
 TRAJ_MAX_PTS, TG_NDRAW, TG_STRIDE = 17, 20, 30
 TG_CENTER = 28                                                   # LG_TG_CENTER: 2 floats, CircleTrajectoryGenerator.center
 TG_KINDS = {"TrajectoryGenerator": 0, "ZeroTrajectoryGenerator": 1, "SquareTrajectoryGenerator": 2,
-            "CircleTrajectoryGenerator": 3}                      # LG_TG_KIND_*
+            "CircleTrajectoryGenerator": 3,
+            "PlanTrajectoryGenerator": 4}                        # LG_TG_KIND_*; the last is this project's own class (tube/plan_env.py)
 TG_WEIGHT_SAMPLERS = {"UniformWeightSampler": 0, "UniformWeightSamplerNoRamp": 1}    # LG_TG_WSAMP_*
 TG_FIELDS = {"weights": (0, 4), "t_final": (4, 1), "t": (5, 1), "k": (6, 1), "const": (7, 2), "extreme": (9, 2),
              "ramp_t_start": (11, 1), "ramp_v_start": (12, 2), "ramp_v_end": (14, 2), "sin_mag": (16, 2), "sin_freq": (18, 2),
@@ -382,6 +383,12 @@ def declare_plan_api(lib):
     lib.lg_plan_descend.argtypes = [vp, pp, pg, vp, vp, vp, vp, vp, i32, f32, i64] + [vp] * 9
 
 
+class lg_traj_rec(C.Structure):
+    """The ROM-rate recorder's caller-owned device buffers (include/legged_hip.h lg_traj_rec)."""
+    _fields_ = [("rows_max", i32), ("x_n", i32), ("z", C.c_void_p), ("pz_x", C.c_void_p), ("v", C.c_void_p), ("rows", C.c_void_p),
+                ("dead", C.c_void_p), ("k_mark", C.c_void_p), ("x", C.c_void_p)]
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p
@@ -405,6 +412,13 @@ def declare_env_api(lib, prefix="lg_"):
     g("get_stage").argtypes = [vp, C.POINTER(lg_stage)]
     g("set_curriculum_stage").argtypes = [vp, C.POINTER(lg_stage), C.c_int]
     if prefix == "lg_":
+        g("set_traj_generator").argtypes = [vp, C.c_int, C.c_int]
+        g("traj_reset").argtypes = [vp, vp]
+        if hasattr(lib, "lg_traj_set_plans"):          # an A/B library (LG_HIP_LIB) built before the plan-following generator
+            g("traj_set_plans").argtypes = [vp, vp, i32]
+            g("traj_rec_check").argtypes = [C.POINTER(lg_traj_rec), i64, i32]
+            g("traj_rec_begin").argtypes = [vp, C.POINTER(lg_traj_rec)]
+            g("traj_rec_step").argtypes = [vp, C.POINTER(lg_traj_rec)]
         g("set_stream").argtypes = [vp, vp]
         lib.lg_version.restype = C.c_int
 

@@ -1,6 +1,7 @@
 // C-ABI (include/legged_hip.h) for the environment step: context, HBM allocation, launches.
 #include <cmath>
 #include <cstdio>
+#include <cstddef>
 #include <cstring>
 #include <string>
 
@@ -17,6 +18,8 @@ extern "C" void lgk_finalize(const DevParams *P, int accumulate, hipStream_t s);
 extern "C" void lgk_set_stage(DevParams *P, const lg_stage *st, int what, hipStream_t s);
 extern "C" void lgk_reset_all(const DevParams *P, int N, int64_t counter, int inject, int init_done, hipStream_t s);
 extern "C" void lgk_traj_reset(const DevParams *P, const float *z, int N, int64_t counter, int inject, hipStream_t s);
+extern "C" void lgk_traj_set_plans(DevParams *P, const float *v, int N, int n, hipStream_t s);
+extern "C" void lgk_traj_record(const DevParams *P, const lg_traj_rec *rec, int N, int begin, hipStream_t s);
 extern "C" void lgk_reset_ids(const DevParams *P, const int32_t *ids, int n, int N, int64_t counter, int inject, int init_done, int traj,
                               hipStream_t s);
 
@@ -245,19 +248,67 @@ int lg_set_stream(lg_ctx *c, void *stream) { c->stream = (hipStream_t)stream; re
 int lg_set_step_counter(lg_ctx *c, int64_t v) { c->step_counter = v; return 0; }
 int64_t lg_get_step_counter(lg_ctx *c) { return c->step_counter; }
 int lg_set_init_done(lg_ctx *c, int v) { c->init_done = v; return 0; }
+static int chk_launch();
+static void flush_finalize(lg_ctx *c);
 int lg_set_traj_generator(lg_ctx *c, int kind, int weight_sampler) {
     if (!c) { g_err = "null argument"; return -1; }
     if (!c->h.cfg.traj.enabled) { g_err = "lg_set_traj_generator: not a trajectory env"; return -1; }
-    if (kind < LG_TG_KIND_RANDOM || kind > LG_TG_KIND_CIRCLE) { g_err = "lg_set_traj_generator: unknown generator kind"; return -1; }
+    if (kind < LG_TG_KIND_RANDOM || kind > LG_TG_KIND_PLAN) { g_err = "lg_set_traj_generator: unknown generator kind"; return -1; }
     if (weight_sampler != LG_TG_WSAMP_UNIFORM && weight_sampler != LG_TG_WSAMP_NO_RAMP) {
         g_err = "lg_set_traj_generator: unknown weight sampler"; return -1;
     }
+    if (kind == LG_TG_KIND_PLAN && !c->h.tg_plan) {             // every env's plan: zeroed, no node yet (the input is 0 until lg_traj_set_plans)
+        int rc = dalloc(c, &c->h.tg_plan, (size_t)c->h.cfg.num_envs * LG_PLAN_MAX_N * 2);
+        if (rc) return rc;
+    }
     c->h.tg_kind = kind;
     c->h.tg_wsamp = weight_sampler;
-    HIPCHK(hipStreamSynchronize(c->stream));                    // kernels read the pair from the device copy of DevParams
-    HIPCHK(hipMemcpy(&c->d->tg_kind, &c->h.tg_kind, 2 * sizeof(int), hipMemcpyHostToDevice));
+    c->h.tg_plan_n = 0;
+    HIPCHK(hipStreamSynchronize(c->stream));                    // kernels read these from the device copy of DevParams: its tail
+    HIPCHK(hipMemcpy(&c->d->tg_kind, &c->h.tg_kind, sizeof(DevParams) - offsetof(DevParams, tg_kind), hipMemcpyHostToDevice));
     return 0;
 }
+int lg_traj_set_plans(lg_ctx *c, const float *v, int32_t n_nodes) {
+    if (!c) { g_err = "null argument"; return -1; }
+    if (!c->h.cfg.traj.enabled) { g_err = "lg_traj_set_plans: not a trajectory env"; return -1; }
+    if (c->h.tg_kind != LG_TG_KIND_PLAN || !c->h.tg_plan) {
+        g_err = "lg_traj_set_plans: the generator is not PlanTrajectoryGenerator (lg_set_traj_generator with LG_TG_KIND_PLAN)"; return -1;
+    }
+    if (n_nodes < 0 || n_nodes > LG_PLAN_MAX_N) {
+        g_err = "lg_traj_set_plans: n_nodes = " + std::to_string(n_nodes) + " must lie in 0.." + std::to_string(LG_PLAN_MAX_N); return -1;
+    }
+    if (n_nodes > 0 && !v) { g_err = "lg_traj_set_plans: v is null with n_nodes > 0"; return -1; }
+    flush_finalize(c);
+    c->h.tg_plan_n = n_nodes;
+    lgk_traj_set_plans(c->d, v, c->h.cfg.num_envs, n_nodes, c->stream);
+    return chk_launch();
+}
+int lg_traj_rec_check(const lg_traj_rec *r, int64_t N, int32_t env_x_n) {
+    std::string e;
+    if (!r) e = "rec is null";
+    else if (N < 1) e = "N = " + std::to_string((long long)N) + " must be at least 1";
+    else if (r->rows_max < 2) e = "rows_max = " + std::to_string(r->rows_max) + " must be at least 2";
+    else if (!r->z) e = "z is null";
+    else if (!r->pz_x) e = "pz_x is null";
+    else if (!r->v) e = "v is null";
+    else if (!r->rows) e = "rows is null";
+    else if (!r->dead) e = "dead is null";
+    else if (!r->k_mark) e = "k_mark is null";
+    else if (r->x && r->x_n != env_x_n) e = "x_n = " + std::to_string(r->x_n) + " must be the env's " + std::to_string(env_x_n);
+    else if (!r->x && r->x_n != 0) e = "x_n = " + std::to_string(r->x_n) + " must be 0 without x";
+    if (e.empty()) return 0;
+    g_err = "lg_traj_rec: " + e;
+    return -1;
+}
+static int traj_record(lg_ctx *c, const lg_traj_rec *rec, int begin) {
+    if (!c) { g_err = "null argument"; return -1; }
+    if (!c->h.cfg.traj.enabled) { g_err = "lg_traj_rec: not a trajectory env"; return -1; }
+    if (lg_traj_rec_check(rec, c->h.cfg.num_envs, 13 + 2 * c->h.cfg.num_actions)) return -1;
+    lgk_traj_record(c->d, rec, c->h.cfg.num_envs, begin, c->stream);
+    return chk_launch();
+}
+int lg_traj_rec_begin(lg_ctx *c, const lg_traj_rec *rec) { return traj_record(c, rec, 1); }
+int lg_traj_rec_step(lg_ctx *c, const lg_traj_rec *rec) { return traj_record(c, rec, 0); }
 int lg_inject_uniforms(lg_ctx *c, int enable) { c->inject = enable; return 0; }
 
 static int chk_launch() {

@@ -1093,7 +1093,67 @@ __global__ void __launch_bounds__(64) k_traj_reset(const DevParams *__restrict__
     tg_reset(P, i, z[2 * i], z[2 * i + 1], counter, inject, s_win[threadIdx.x]);
 }
 
+// lg_traj_set_plans: the caller's (N, n, 2) plans into the context's (N, LG_PLAN_MAX_N, 2) buffer, and the node count -- one launch
+// on the env's stream, so the step kernels that follow see both and the caller's array is free once the call returns
+__global__ void __launch_bounds__(256) k_traj_set_plans(DevParams *__restrict__ P, const float *__restrict__ v, int n) {
+    const int N = P->cfg.num_envs;
+    const size_t total = (size_t)N * n * 2;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t i = e / ((size_t)n * 2), r = e % ((size_t)n * 2);
+        P->tg_plan[i * (LG_PLAN_MAX_N * 2) + r] = v[e];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) P->tg_plan_n = n;
+}
+
+// The ROM-rate recorder (legged_hip.h lg_traj_rec): one lane per env; every write lands in the env's own rows, so there are no
+// atomics and no scratch.  begin: row 0 and the marks.  Otherwise the three rules: dead -> nothing; reset on this step -> dead;
+// the env's ROM step counter moved and a row is free -> one row.
+__device__ __forceinline__ void traj_rec_row(const DevParams *P, const lg_traj_rec &R, int i, int r) {
+    const lg_cfg &c = P->cfg;
+    const float *root = P->buf.root_states + (size_t)i * 13;
+    const size_t o = ((size_t)i * R.rows_max + r) * 2;
+    R.z[o] = P->buf.trajectory[(size_t)i * c.traj.N * 2]; R.z[o + 1] = P->buf.trajectory[(size_t)i * c.traj.N * 2 + 1];
+    R.pz_x[o] = root[0]; R.pz_x[o + 1] = root[1];
+    if (R.x) {                                                     // get_state(): base pose 7, joint positions, base twist 6, joint velocities
+        const int A = c.num_actions;
+        float *x = R.x + ((size_t)i * R.rows_max + r) * R.x_n;
+        const float *d = P->buf.dof_state + (size_t)i * A * 2;
+        for (int k = 0; k < 7; ++k) x[k] = root[k];
+        for (int a = 0; a < A; ++a) x[7 + a] = d[2 * a];
+        for (int k = 0; k < 6; ++k) x[7 + A + k] = root[7 + k];
+        for (int a = 0; a < A; ++a) x[13 + A + a] = d[2 * a + 1];
+    }
+}
+__global__ void __launch_bounds__(256) k_traj_record(const DevParams *__restrict__ P, lg_traj_rec R, int begin) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P->cfg.num_envs) return;
+    const float *s = P->buf.tg_state + (size_t)i * LG_TG_STRIDE;
+    if (begin) {
+        traj_rec_row(P, R, i, 0);
+        R.rows[i] = 1; R.dead[i] = 0; R.k_mark[i] = s[LG_TG_K];
+        return;
+    }
+    if (R.dead[i]) return;
+    if (P->buf.reset[i]) { R.dead[i] = 1; return; }
+    const int r = R.rows[i];
+    const float k = s[LG_TG_K];
+    if (k != R.k_mark[i] && r < R.rows_max) {
+        traj_rec_row(P, R, i, r);
+        const size_t o = ((size_t)i * (R.rows_max - 1) + (r - 1)) * 2;
+        R.v[o] = s[LG_TG_V]; R.v[o + 1] = s[LG_TG_V + 1];
+        R.rows[i] = r + 1; R.k_mark[i] = k;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
+extern "C" void lgk_traj_set_plans(DevParams *P, const float *v, int N, int n, hipStream_t s) {
+    const size_t total = (size_t)N * n * 2;
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_traj_set_plans, dim3(blocks < 1 ? 1 : blocks > 1024 ? 1024 : (int)blocks), dim3(256), 0, s, P, v, n);
+}
+extern "C" void lgk_traj_record(const DevParams *P, const lg_traj_rec *rec, int N, int begin, hipStream_t s) {
+    hipLaunchKernelGGL(k_traj_record, dim3((N + 255) / 256), dim3(256), 0, s, P, *rec, begin);
+}
 extern "C" void lgk_set_actions(const DevParams *P, const float *a, int n, hipStream_t s) {
     int blocks = (n + 255) / 256;
     hipLaunchKernelGGL(k_set_actions, dim3(blocks > 1024 ? 1024 : blocks), dim3(256), 0, s, P, a);

@@ -92,6 +92,10 @@ struct DevParams {
     // trajectory env: generator class / weight sampler (LG_TG_KIND_*, LG_TG_WSAMP_*; lg_set_traj_generator).  Last, so that no
     // member the other kernels read moves.
     int tg_kind, tg_wsamp;
+    // LG_TG_KIND_PLAN: every env's plan, (num_envs, LG_PLAN_MAX_N, 2) inputs of which the first tg_plan_n count (lg_traj_set_plans);
+    // allocated and zeroed when the kind is selected, null before.  After tg_kind / tg_wsamp for the same reason.
+    float *tg_plan;
+    int tg_plan_n;
 };
 
 struct lg_ctx {

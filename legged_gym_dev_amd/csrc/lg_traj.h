@@ -116,6 +116,17 @@ __device__ __forceinline__ void tg_input_circle(const TgPar &b, const float *s, 
     v[0] = vx / n1 * m;
     v[1] = vy / n1 * m;
 }
+// PlanTrajectoryGenerator -- this project's own class, not one of rom_dynamics.py (legged_hip.h LG_TG_KIND_PLAN): the env's own plan,
+// piecewise constant per ROM step and indexed by the ROM step counter k (a whole number held in a float), not by comparing
+// accumulated fp32 time against corners as Square does.  0 outside 0 <= k < n_nodes; the inputs are used as given.
+__device__ __forceinline__ void tg_input_plan(const DevParams *P, int i, float k, float v[2]) {
+    const int j = (int)k;
+    v[0] = 0.0f; v[1] = 0.0f;
+    if (k >= 0.0f && j < P->tg_plan_n) {
+        const float *p = P->tg_plan + ((size_t)i * LG_PLAN_MAX_N + j) * 2;
+        v[0] = p[0]; v[1] = p[1];
+    }
+}
 // get_input_t of the configured class + the stationary mask of step_rom_idx (RD:579-580).  kind is kernel-uniform (DevParams):
 // TrajectoryGenerator takes the first branch and never reads z.  z: the window's last point (LDS or HBM).
 __device__ __forceinline__ void tg_input_kind(const DevParams *P, const TgPar &b, int i, float tt, const float *z, float v[2]) {
@@ -125,6 +136,7 @@ __device__ __forceinline__ void tg_input_kind(const DevParams *P, const TgPar &b
     v[0] = 0.0f; v[1] = 0.0f;                                      // ZeroTrajectoryGenerator (RD:618-625)
     if (kind == LG_TG_KIND_SQUARE) tg_input_square(b, tt, v);
     else if (kind == LG_TG_KIND_CIRCLE) tg_input_circle(b, s, z[0], z[1], v);
+    else if (kind == LG_TG_KIND_PLAN) tg_input_plan(P, i, s[LG_TG_K], v);       // the counter BEFORE this step's ROM step
     if (s[LG_TG_STATIONARY] != 0.0f) { v[0] = 0.0f; v[1] = 0.0f; }
 }
 
@@ -184,7 +196,8 @@ __device__ inline void tg_callback_step(const DevParams *P, int i, int64_t count
     const bool rom = tt >= k * t.rom_dt - 1e-5f;
     if (rom) { tg_window_step(P, w, v); k += 1.0f; }
     const float tn = tt + P->cfg.dt;
-    s[LG_TG_V] = v[0]; s[LG_TG_V + 1] = v[1];                      // self.v (RD:579-580)
+    // self.v (RD:579-580); PLAN keeps the input of the ROM interval in force: the one last applied to the window
+    if (!GEN || P->tg_kind != LG_TG_KIND_PLAN || rom) { s[LG_TG_V] = v[0]; s[LG_TG_V + 1] = v[1]; }
     s[LG_TG_K] = k;
     s[LG_TG_T] = tn;
     if (rom) tg_window_store(P, i, w);
@@ -207,6 +220,7 @@ __device__ inline void tg_reset(const DevParams *P, int i, float z0x, float z0y,
     if (kind == LG_TG_KIND_RANDOM) tg_resample<GEN>(P, tg_par_cfg(P), i, LG_TSLOT_RTG(A), counter, inject);
     else if (kind == LG_TG_KIND_ZERO) s[LG_TG_STATIONARY] = 1.0f;              // RD:620-621
     else if (kind == LG_TG_KIND_CIRCLE) { s[LG_TG_CENTER] = z0x - 0.5f; s[LG_TG_CENTER + 1] = z0y; }   // RD:679-681
+    else if (kind == LG_TG_KIND_PLAN) s[LG_TG_STATIONARY] = 0.0f;              // never stationary: tg_input_kind zeroes a stationary env
     float tt = s[LG_TG_T], k = s[LG_TG_K], v[2] = {0.0f, 0.0f};
     for (int it = 0; it < t.N * t.dN; ++it) {
         if (kind == LG_TG_KIND_RANDOM) tg_input(P, i, tt, v);
@@ -225,6 +239,7 @@ __device__ inline void tg_reset(const DevParams *P, int i, float z0x, float z0y,
 __device__ inline void tg_late_resample(const DevParams *P, int i, int64_t counter, int inject) {
 #pragma clang fp contract(off)      // one rounding per torch op: the event comparisons below must agree with the reference
     float *s = P->buf.tg_state + (size_t)i * LG_TG_STRIDE;
+    if (P->tg_kind == LG_TG_KIND_PLAN) return;                     // nothing to resample; v stays the input of the interval in force
     float v[2];                                                    // and leaves self.v evaluated at the env's new time
     if (P->tg_kind == LG_TG_KIND_RANDOM) {
         if (s[LG_TG_T] > s[LG_TG_T_FINAL]) tg_resample(P, tg_par_cfg(P), i, LG_TSLOT_RTG(P->cfg.num_actions), counter, inject);

@@ -111,8 +111,9 @@ CONTRACT = [
     ("rom.v_max", CONSUMED, "setup"),
     ("rom.*", INERT, "state bounds / curricula of other reduced-order models: SingleInt2D.clip_v_z returns v unchanged (rom_dynamics.py:201-202) "
      "and legged_robot_trajectory.py:89-103 passes nothing else"),
-    ("trajectory_generator.cls", CONSUMED, "setup: lg_set_traj_generator (TrajectoryGenerator and the Zero / Square / Circle "
-     "evaluation generators; env_setup._parse_trajectory refuses any other name)"),
+    ("trajectory_generator.cls", CONSUMED, "setup: lg_set_traj_generator (TrajectoryGenerator, the Zero / Square / Circle "
+     "evaluation generators, and PlanTrajectoryGenerator -- this project's own class, not one of rom_dynamics.py: every env follows the "
+     "plan traj_gen.set_plans gave it (tube/plan_env.py); env_setup._parse_trajectory refuses any other name)"),
     ("trajectory_generator.t_samp_cls", FIXED, "UniformSampleHoldDT is the implemented hold-time sampler", ("UniformSampleHoldDT",)),
     ("trajectory_generator.weight_samp_cls", CONSUMED, "setup: lg_set_traj_generator (UniformWeightSampler, UniformWeightSamplerNoRamp; "
      "env_setup._parse_trajectory refuses UniformWeightSamplerNoExtreme, which raises in the reference, and unknown names)"),

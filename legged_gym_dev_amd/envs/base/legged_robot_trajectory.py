@@ -16,11 +16,13 @@ from .reward_terms import ExpNegWeightedSqErr, SlopedErrChange
 
 class _TrajGenView:
     """Read-only face of the device-side generator state under the reference's TrajectoryGenerator attribute names
-    (rom_dynamics.py:484-505); ``center`` for CircleTrajectoryGenerator (:679-681), ``reset(z)`` (:592-593).  The class name
+    (rom_dynamics.py:484-505); ``center`` for CircleTrajectoryGenerator (:679-681), ``reset(z)`` (:592-593), ``set_plans(v)`` for this
+    project's own PlanTrajectoryGenerator.  The class name
     is the configured generator's (trajectory_generator.cls)."""
 
     def __init__(self, env):
         self._core, self._t, self.N, self.dN = env.core, env.core.t, env.setup.traj["N"], env.setup.traj["dN"]
+        self._kind = env.setup.traj["kind"]
         for name, (off, n) in capi.TG_FIELDS.items():
             v = self._t["tg_state"][:, off:off + n]
             setattr(self, {"const": "sample_hold_input", "extreme": "extreme_input", "stationary": "stationary_inds"}.get(name, name),
@@ -40,6 +42,22 @@ class _TrajGenView:
             raise ValueError(f"reset(z): z has {zc.shape[0]} rows, the generator {self._t['tg_traj'].shape[0]} envs")
         self._z = zc                                     # kept alive until the next call (the launch is asynchronous)
         self._core.call("traj_reset", C.c_void_p(zc.data_ptr()))
+
+    def set_plans(self, v):
+        """PlanTrajectoryGenerator (this project's own class: csrc/lg_traj.h, LG_TG_KIND_PLAN): every env's plan from v
+        (num_envs, n_nodes, 2), 0 <= n_nodes <= LG_PLAN_MAX_N -- the ROM step k -> k + 1 of env i advances its window with v[i, k],
+        and with 0 outside the plan (lg_traj_set_plans: a stream-ordered copy).  reset(z) / an env reset restart the plans."""
+        import ctypes as C
+        if self._kind != capi.TG_KINDS["PlanTrajectoryGenerator"]:
+            raise ValueError("set_plans(v): trajectory_generator.cls is not 'PlanTrajectoryGenerator'")
+        vc = torch.as_tensor(v, device=self._t["tg_traj"].device, dtype=torch.float32).contiguous()
+        n_env = self._t["tg_traj"].shape[0]
+        if vc.dim() != 3 or vc.shape[0] != n_env or vc.shape[2] != 2:
+            raise ValueError(f"set_plans(v): v must be ({n_env}, n_nodes, 2); got {tuple(vc.shape)}")
+        if vc.shape[1] > capi.PLAN_MAX_N:
+            raise ValueError(f"set_plans(v): n_nodes = {vc.shape[1]} exceeds LG_PLAN_MAX_N = {capi.PLAN_MAX_N}")
+        self._plans = vc
+        self._core.call("traj_set_plans", C.c_void_p(vc.data_ptr()) if vc.shape[1] else None, int(vc.shape[1]))
 
 
 class _RomView:

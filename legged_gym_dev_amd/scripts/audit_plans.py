@@ -5,7 +5,8 @@ source, on the HIP kernels (legged_gym_dev_amd/tube/plan.py; DESIGN.md section 1
     python legged_gym_dev_amd/scripts/audit_plans.py (--run tube_runs/run0 | --tube l1|l2|l1_rolling|l2_rolling [--scaling s] [--window_size n]) \\
         (--problem gap|right|right_wide | --problem_json F) \\
         (--plans F.npz | --warm_start start|goal|interpolate [--perturb K --sigma s --seed n]) \\
-        [--calibration [PATH]] [--coverage c] [--level l] [--checkpoint best|latest] [--sim_cfg KEY=VALUE ...] [--out DIR]
+        [--calibration [PATH]] [--coverage c] [--level l] [--checkpoint best|latest] [--sim_cfg KEY=VALUE ...] [--out DIR] \\
+        [--robot [--task anymal_c_flat_trajectory] [--load_run R] [--policy_checkpoint K] [--push_robots] [--allow_fast]]
 
 --run: a train_tube.py run of a one-shot tube (dataset scalar_horizon or scalar_horizon_level; any other is refused): the plans have
 N = the run's H_fwd nodes, and the tube item's past (H_rev error norms and inputs) is zero, as the reference's solve_tube starts.
@@ -15,6 +16,13 @@ clipped Gaussian perturbations of it beside it (sigma in the input's units, clip
 --calibration [PATH] (default PATH: the run's calibration.json) adds the conformal offset per step ahead: --coverage picks the set of a
 scalar_horizon calibration, --level that of a scalar_horizon_level one (the level also conditions the model).
 --sim_cfg: fields of the tracking model's configuration (RomSimCfg: env.model.dt=0.05 controller.Kp=10 ...); rom.dt is the problem's dt.
+
+--robot: the plans are tracked by the legged robot instead -- one simulated robot of --task per plan under the task's trained policy
+(the latest checkpoint of its experiment as play.py finds it, or --load_run / --policy_checkpoint; without one, a fresh policy), on
+the HIP env with PlanTrajectoryGenerator (legged_gym_dev_amd/tube/plan_env.py): track_env, then the score
+with the robot's own history as the tube item's past, then audit_env, which adds completed / terminated / covered_plans_of_all and
+a "tracker": "robot" field.  The policy's checkpoint has its own flag because --checkpoint already names the tube's.  The problem's
+dt must be the task's rom.dt and the inputs must lie inside its rom.v_min / v_max (--allow_fast lifts the latter).
 
 Writes audit.json to --out (default: the run folder, or the working directory) and prints the reference script's
 "Total Success Rate" line: the share of (plan, node) pairs with tube >= realised error.
@@ -56,7 +64,19 @@ def parse_args(argv=None):
     ap.add_argument("--sim_cfg", nargs="*", default=[], metavar="KEY=VALUE")
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--robot", action="store_true", help="track the plans on the legged robot (one env per plan) instead of the ROM-on-ROM model")
+    ap.add_argument("--task", default=None, help="with --robot: a trajectory-tracking task (default anymal_c_flat_trajectory)")
+    ap.add_argument("--load_run", default=None, help="with --robot: the policy's run folder (default: the latest)")
+    ap.add_argument("--policy_checkpoint", type=int, default=None, help="with --robot: the policy's checkpoint number (default: the latest)")
+    ap.add_argument("--push_robots", action="store_true", help="with --robot: push the robots on the task's timers")
+    ap.add_argument("--allow_fast", action="store_true", help="with --robot: accept inputs beyond the task's rom.v_min / v_max")
     a = ap.parse_args(argv)
+    if not a.robot:
+        for flag in ("task", "load_run", "policy_checkpoint", "push_robots", "allow_fast"):
+            if getattr(a, flag) not in (None, False):
+                ap.error(f"--{flag} belongs to --robot")
+    elif a.sim_cfg:
+        ap.error("--sim_cfg configures the ROM-on-ROM tracking model; --robot tracks on the legged env")
     if a.perturb and a.plans:
         ap.error("--perturb belongs to --warm_start; --plans are taken as they are")
     if a.perturb < 0 or a.sigma < 0:
@@ -129,6 +149,48 @@ def sim_config(a, p):
     return rc
 
 
+def robot_env(a, B):
+    """The env of --robot with one robot per plan and its inference policy: plan_env_cfg's configuration, the checkpoint chosen as
+    evaluate_tracking.py chooses it."""
+    import evaluate_tracking
+    from legged_gym_dev_amd.envs import task_registry
+    from legged_gym_dev_amd.tube.plan_env import plan_env_cfg
+    from legged_gym_dev_amd.utils import get_args
+    task = a.task or "anymal_c_flat_trajectory"
+    env_cfg, train_cfg = plan_env_cfg(task, B, push_robots=a.push_robots)
+    args = get_args(["--task", task, "--num_envs", str(B), "--headless"])
+    args.sim_device = args.rl_device = a.device
+    args.load_run, args.checkpoint = a.load_run, a.policy_checkpoint
+    env, env_cfg = task_registry.make_env(name=task, args=args, env_cfg=env_cfg)
+    train_cfg.runner.resume = False
+    runner, train_cfg = task_registry.make_alg_runner(env=env, name=task, args=args, train_cfg=train_cfg, log_root=None)
+    path = evaluate_tracking._checkpoint(train_cfg, args)
+    if path is not None:
+        print(f"Loading model from: {path}")
+        runner.load(path)
+    else:
+        print("No checkpoint found: tracking with a freshly initialised policy")
+    return env, runner, runner.get_inference_policy(device=env.device), path
+
+
+def main_robot(a, p, scorer, z0, v):
+    """--robot: track_env, score with the robot's own history, audit_env."""
+    import torch
+    from legged_gym_dev_amd.tube.plan_env import audit_env, track_env
+    env, runner, policy, path = robot_env(a, v.shape[0])
+    try:
+        if abs(float(env.rom.dt) - float(p.dt)) > 1e-9:
+            raise ValueError(f"the problem's dt = {p.dt} differs from the task's rom.dt = {env.rom.dt}")
+        t = track_env(env, policy, v, z0, H_rev=p.H_rev, allow_fast=a.allow_fast)
+        s = scorer.score(z0, v, e=t["e_past"], v_prev=t["v_prev"], w0=t["w0"])
+        torch.cuda.synchronize()
+        res = audit_env(s, t, p)
+    finally:
+        runner.ppo.close()
+        env.close()
+    return s, res, {"tracker": "robot", "task": a.task or "anymal_c_flat_trajectory", "policy": path, "push_robots": bool(a.push_robots)}
+
+
 def main(argv=None):
     a = parse_args(argv)
     cfg = run_config(a.run) if a.run else None
@@ -156,16 +218,20 @@ def main(argv=None):
         if a.run:
             model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, device=a.device)
         scorer = pl.HipPlanScorer(model, p, calibration=calib, level=level, coverage=a.coverage, device=a.device)
-        sim = HipRomSim(sim_config(a, p), device=a.device)
-        s = scorer.score(z0, v)
-        t = pl.track(sim, s["z"], v)
-        torch.cuda.synchronize()
-        res = pl.audit(s, t, p)
+        robot = {}
+        if a.robot:
+            s, res, robot = main_robot(a, p, scorer, z0, v)
+        else:
+            sim = HipRomSim(sim_config(a, p), device=a.device)
+            s = scorer.score(z0, v)
+            t = pl.track(sim, s["z"], v)
+            torch.cuda.synchronize()
+            res = pl.audit(s, t, p)
         cost, clear = s["cost"].cpu().double(), s["min_clear"].cpu().double()
         extra = {"cost_mean": float(cost.mean()), "cost_min": float(cost.min()), "best_plan": int(cost.argmin()),
                  "min_clear_min": float(clear.min()) if p.n_obs else None, "n_viol_plans": [int(x) for x in (s["n_viol"] > 0).sum(dim=0).cpu()],
                  "problem": p.to_json(), "run": a.run, "tube": a.tube or "nn", "level": level,
-                 "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), "source": source}
+                 "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), "source": source, **robot}
         assert not set(extra) & set(res), "a key of the audit would be overwritten"
         res.update(extra)
     finally:
@@ -177,6 +243,12 @@ def main(argv=None):
     os.makedirs(out, exist_ok=True)
     with open(os.path.join(out, "audit.json"), "w") as f:
         json.dump(res, f, indent=1, allow_nan=False)
+    if a.robot:
+        print(f"{res['plans']} plans x {res['nodes']} nodes on the robot: completed {res['completed']}, terminated {res['terminated']}, "
+              f"covered at every node (of all) {res['covered_plans_of_all']:.4f}")
+        if not res["completed"]:
+            print("Total Success Rate: None (no robot completed its plan)")
+            return res
     print(f"{res['plans']} plans x {res['nodes']} nodes: predicted safe {res['predicted_safe']:.4f}, actually safe {res['actually_safe']:.4f}, "
           f"covered at every node {res['covered_plans']:.4f}; realised error mean {res['w_true_mean']:.4f} max {res['w_true_max']:.4f}")
     print(f"Total Success Rate: {res['coverage']}")
