@@ -776,14 +776,16 @@ int lg_select_kth_grouped(const float *values, int64_t ld, int32_t B, int64_t n,
  * deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.py ("MT"), trajopt/rom_dynamics.py ("RD"). */
 #define LG_PLAN_MAX_N 64
 #define LG_PLAN_MAX_OBS 8
+#define LG_PLAN_STEP_MAX_HREV 64                   /* LG_PLAN_TUBE_NN_STEP: the caller's history, 0..64 steps */
 #define LG_PLAN_TUBE_NN 0                          /* the one-shot MLP of a horizon lg_tube handle (TT:561-568, tube_dyn "NN_oneshot") */
 #define LG_PLAN_TUBE_L1 1                          /* scaling (|vx| + |vy|)                                      (TT:489-499) */
 #define LG_PLAN_TUBE_L2 2                          /* scaling (vx^2 + vy^2)                                      (TT:502-512) */
 #define LG_PLAN_TUBE_L1_ROLLING 3                  /* mean of the last min(window_size, k + 1) l1 values         (TT:515-526) */
 #define LG_PLAN_TUBE_L2_ROLLING 4                  /* the same of the l2 values                                  (TT:529-540) */
+#define LG_PLAN_TUBE_NN_STEP 5                     /* the one-step MLP of a flat scalar lg_tube handle, fed back node by node (section 10.13) */
 typedef struct lg_plan_problem {                   /* one problem for every plan of a call (TT:11-21 problem_dict, TT:460 solve_tube) */
     int32_t N /*nodes after the start: 1..LG_PLAN_MAX_N*/, H_rev /*past steps of the tube item*/, n_obs /*0..LG_PLAN_MAX_OBS*/;
-    int32_t tube_kind /*LG_PLAN_TUBE_**/, window_size /*rolling kinds: >= 1*/, _pad;
+    int32_t tube_kind /*LG_PLAN_TUBE_**/, window_size /*rolling kinds: >= 1*/, recursive /*nn_step: 0 / 1, the row layout*/;
     float dt /*ROM step, > 0*/, scaling /*analytic kinds*/, w_max, Qw;
     float obs_c[LG_PLAN_MAX_OBS][2], obs_r[LG_PLAN_MAX_OBS], goal[2];
     float Q[4], Qf[4], R[4];                       /* 2 x 2, row-major; each quadratic is sum((d @ M) * d) (TT:41-56) */
@@ -792,7 +794,16 @@ typedef struct lg_plan_problem {                   /* one problem for every plan
 /* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error: N outside 1..64, n_obs outside 0..8, dt <= 0, a negative
  * radius, an unknown tube_kind, window_size < 1 on a rolling kind, the NN kind without a handle, a handle that is not a horizon
  * handle or whose H_fwd != N, nz != 0 (input_dim != H_rev + 2 (H_rev + N) [+ 1]) or H_rev differs from the problem's, has_level
- * given on an unconditioned handle or missing on a conditioned one.  tube may be NULL for the analytic kinds (it is then not read). */
+ * given on an unconditioned handle or missing on a conditioned one.  tube may be NULL for the analytic kinds (it is then not read).
+ * LG_PLAN_TUBE_NN_STEP (the recursion of trajopt/old/rom_tube_planning.py:106-107): the handle is a FLAT one
+ * (a horizon handle is refused) with output_dim 1.  The taps T come from the handle: with I' = input_dim minus the level column,
+ * I' = 1 + 2 T (recursive = 0) or I' = 3 T (recursive = 1); any other I' is refused, and so are recursive outside 0 / 1, H_rev
+ * outside 0..64 or below T - 1 (the delayed taps of node 0 come from e and v_prev) and the level rules above.
+ * Row of node k: [ww(k), vv(k), vv(k-1), .., vv(k-T+1), (level)] or, recursive, [ww(k), vv(k), ww(k-1), vv(k-1), .., (level)] with
+ * vv(j) = v[j] (j >= 0) or v_prev[H_rev + j], ww(j) = fw[j-1] (j >= 1), w0 (j = 0) or e[H_rev + j]; fw[k] = MLP(row_k), the raw value
+ * fed back, never the calibrated one.  fw equals lg_tube_rollout_window on such rows (fb = 1, taps 1 or T with stride 3, no reseed)
+ * bit for bit.  lg_plan_score, lg_plan_mppi_step and lg_plan_mppi take the kind (k_plan_score_step, k_plan_sample_score_step);
+ * lg_plan_grad* and lg_plan_descend* refuse it: reverse mode through N chained MLP passes is not built. */
 int lg_plan_check(const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level);
 /* Score B plans in one launch (k_plan_score, 32 plans per 256-thread workgroup).  DEVICE pointers: z0 (B, 2), v (B, N, 2); e
  * (B, H_rev) past error norms, v_prev (B, H_rev, 2), w0 (B) the tube at node 0 -- each may be NULL = zeros; offset (N) a calibration

@@ -334,12 +334,13 @@ def declare_select_api(lib):
 
 
 PLAN_MAX_N, PLAN_MAX_OBS = 64, 8                                # LG_PLAN_MAX_*
-PLAN_TUBE = {"nn": 0, "l1": 1, "l2": 2, "l1_rolling": 3, "l2_rolling": 4}     # LG_PLAN_TUBE_*
+PLAN_STEP_MAX_HREV = 64                                         # LG_PLAN_STEP_MAX_HREV
+PLAN_TUBE = {"nn": 0, "l1": 1, "l2": 2, "l1_rolling": 3, "l2_rolling": 4, "nn_step": 5}     # LG_PLAN_TUBE_*
 
 
 class lg_plan_problem(C.Structure):
     _fields_ = [
-        ("N", i32), ("H_rev", i32), ("n_obs", i32), ("tube_kind", i32), ("window_size", i32), ("_pad", i32),
+        ("N", i32), ("H_rev", i32), ("n_obs", i32), ("tube_kind", i32), ("window_size", i32), ("recursive", i32),
         ("dt", f32), ("scaling", f32), ("w_max", f32), ("Qw", f32),
         ("obs_c", (f32 * 2) * 8), ("obs_r", f32 * 8), ("goal", f32 * 2),
         ("Q", f32 * 4), ("Qf", f32 * 4), ("R", f32 * 4),

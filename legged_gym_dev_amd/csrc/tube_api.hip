@@ -3,6 +3,7 @@
 // the closed-loop roll-outs, single-tap and windowed, and the level entries of a level-conditioned model, flat or horizon (tube_kernels.hip).  lg_tube_sweep_*: K such trainers of one shape on one
 // dataset, stepped by the same two launches with the members along grid y.
 // lg_plan_check / lg_plan_score: plans scored against a one-shot horizon handle or an analytic tube (k_plan_score).
+// The same entry points take the one-step kind LG_PLAN_TUBE_NN_STEP (k_plan_score_step, k_plan_sample_score_step; section 10.13).
 // lg_mppi_check / lg_plan_mppi*: the sampling planner on top of it (k_plan_sample_score, k_plan_mppi_update).
 // lg_plan_grad_check / lg_plan_grad / lg_plan_descend*: the gradient planner (k_plan_grad).
 #include <cmath>
@@ -52,6 +53,13 @@ int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, c
 void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,
                             const float *J, float *best_J, float *best_v, float *hist, int32_t *n_bad, hipStream_t s);
 int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, hipStream_t s);
+int64_t tubek_plan_step_bytes(const TubeDev *D, const lg_plan_problem *prob);
+int64_t tubek_plan_score_step(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
+                              const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
+                              float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, hipStream_t s);
+int64_t tubek_plan_sample_score_step(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
+                                     const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
+                                     const float *vbar, float *J, float *cost, float *min_clear, float *pen, hipStream_t s);
 }
 
 struct TubeCaps {                       // rows that a model's data-sized buffers hold
@@ -416,6 +424,36 @@ int lg_tube_rollout_window(lg_tube *p, const float *x, int64_t n_seq, int32_t T,
 }
 
 // ---------------------------------------------------------------- plans against a tube
+// Taps of a one-step handle: with I' = input_dim minus the level column, I' = 1 + 2 T (not recursive) or
+// 3 T (recursive); 0 where I' fits the form asked for in no T >= 1.
+static int plan_step_taps(const TubeDev &D, int recursive) {
+    const int Ip = D.in_dim - (D.level_input ? 1 : 0);
+    if (recursive) return Ip >= 3 && Ip % 3 == 0 ? Ip / 3 : 0;
+    return Ip >= 3 && (Ip - 1) % 2 == 0 ? (Ip - 1) / 2 : 0;
+}
+// the envelope of LG_PLAN_TUBE_NN_STEP beyond the problem's own fields
+static std::string plan_step_reason(const lg_plan_problem *q, const lg_tube *t, int32_t has_level) {
+    if (!t) return "tube_kind nn_step needs a tube handle";
+    const TubeDev &D = t->dev;
+    if (D.horizon) return "the tube handle is a horizon handle (lg_tube_cfg.horizon): nn_step rolls a flat one-step tube along the plan";
+    if (D.out_dim != 1) return "the handle's output_dim = " + std::to_string(D.out_dim) + " must be 1: nn_step rolls a scalar tube";
+    if (q->recursive != 0 && q->recursive != 1) return "recursive = " + std::to_string(q->recursive) + " must be 0 or 1";
+    const int T = plan_step_taps(D, q->recursive);
+    if (!T)
+        return "the handle's input_dim = " + std::to_string(D.in_dim) + (D.level_input ? " (one of them the level)" : "") + " with recursive = " +
+               std::to_string(q->recursive) + " is not " + (q->recursive ? "3 T" : "1 + 2 T") + (D.level_input ? " + 1" : "") +
+               " for any T >= 1 (the ROM is SingleInt2D: no state columns past the position)";
+    if (q->H_rev < 0 || q->H_rev > LG_PLAN_STEP_MAX_HREV || q->H_rev < T - 1)
+        return "H_rev = " + std::to_string(q->H_rev) + " must be 0.." + std::to_string(LG_PLAN_STEP_MAX_HREV) + " and at least T - 1 = " +
+               std::to_string(T - 1) + ": the delayed taps of node 0 come from e and v_prev";
+    if (tubek_plan_step_bytes(&D, q) > (int64_t)LG_TUBE_ROLLOUT_LDS)
+        return "the tile of input_dim = " + std::to_string(D.in_dim) + ", " + std::to_string(D.units) + " units, H_rev = " +
+               std::to_string(q->H_rev) + " and N = " + std::to_string(q->N) + " does not fit the dynamic LDS ceiling";
+    if (has_level && !D.level_input) return "level is given, but the handle is not level-conditioned (lg_tube_cfg.level_input)";
+    if (!has_level && D.level_input) return "level is missing: the handle is level-conditioned (lg_tube_cfg.level_input)";
+    return "";
+}
+
 // why a problem, with the handle it is asked with, lies outside the envelope; empty inside it
 static std::string plan_reason(const lg_plan_problem *q, const lg_tube *t, int32_t has_level) {
     if (q->N < 1 || q->N > LG_PLAN_MAX_N) return "N = " + std::to_string(q->N) + " must be 1.." + std::to_string(LG_PLAN_MAX_N);
@@ -423,9 +461,11 @@ static std::string plan_reason(const lg_plan_problem *q, const lg_tube *t, int32
     if (!(q->dt > 0.f)) return "dt must be positive";
     for (int i = 0; i < q->n_obs; ++i)
         if (!(q->obs_r[i] >= 0.f)) return "obs_r[" + std::to_string(i) + "] is negative";
-    if (q->tube_kind < LG_PLAN_TUBE_NN || q->tube_kind > LG_PLAN_TUBE_L2_ROLLING) return "tube_kind must be nn (0), l1, l2, l1_rolling or l2_rolling (1..4)";
+    if (q->tube_kind < LG_PLAN_TUBE_NN || q->tube_kind > LG_PLAN_TUBE_NN_STEP)
+        return "tube_kind must be nn (0), l1, l2, l1_rolling, l2_rolling (1..4) or nn_step (5)";
     if ((q->tube_kind == LG_PLAN_TUBE_L1_ROLLING || q->tube_kind == LG_PLAN_TUBE_L2_ROLLING) && q->window_size < 1)
         return "window_size must be at least 1 for a rolling tube_kind";
+    if (q->tube_kind == LG_PLAN_TUBE_NN_STEP) return plan_step_reason(q, t, has_level);
     if (q->tube_kind != LG_PLAN_TUBE_NN) return has_level ? "level is given, but an analytic tube_kind has none" : "";
     if (!t) return "tube_kind nn needs a tube handle";
     const TubeDev &D = t->dev;
@@ -455,8 +495,11 @@ int lg_plan_score(lg_tube *tube, const lg_plan_problem *prob, const float *z0, c
         lg_set_error("lg_plan_score: missing array (z0, v, cost, min_clear, worst_node and n_viol are required)"); return -1;
     }
     const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
-    const int64_t rc = tubek_plan_score(nn ? &tube->dev : nullptr, prob, z0, v, e, v_prev, w0, offset, has_level ? level : 0.f, B, cost,
-                                        min_clear, worst_node, n_viol, fw, z, w, (hipStream_t)stream);
+    const int64_t rc = prob->tube_kind == LG_PLAN_TUBE_NN_STEP
+        ? tubek_plan_score_step(&tube->dev, prob, z0, v, e, v_prev, w0, offset, has_level ? level : 0.f, B, cost, min_clear, worst_node,
+                                n_viol, fw, z, w, (hipStream_t)stream)
+        : tubek_plan_score(nn ? &tube->dev : nullptr, prob, z0, v, e, v_prev, w0, offset, has_level ? level : 0.f, B, cost,
+                           min_clear, worst_node, n_viol, fw, z, w, (hipStream_t)stream);
     if (rc < 0) { lg_set_error("lg_plan_score: hipFuncSetAttribute failed"); return -2; }
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_score: launch failed"), -3);
 }
@@ -507,8 +550,11 @@ int lg_plan_mppi_step(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_
     }
     const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
     if (what & 1) {
-        const int64_t rc = tubek_plan_sample_score(nn ? &tube->dev : nullptr, prob, cfg, it, z0, e, v_prev, w0, offset, has_level ? level : 0.f,
-                                                   P, vbar, J, cost, min_clear, pen, (hipStream_t)stream);
+        const int64_t rc = prob->tube_kind == LG_PLAN_TUBE_NN_STEP
+            ? tubek_plan_sample_score_step(&tube->dev, prob, cfg, it, z0, e, v_prev, w0, offset, has_level ? level : 0.f, P, vbar, J, cost,
+                                           min_clear, pen, (hipStream_t)stream)
+            : tubek_plan_sample_score(nn ? &tube->dev : nullptr, prob, cfg, it, z0, e, v_prev, w0, offset, has_level ? level : 0.f,
+                                      P, vbar, J, cost, min_clear, pen, (hipStream_t)stream);
         if (rc < 0) { lg_set_error("lg_plan_mppi_step: hipFuncSetAttribute failed"); return -2; }
     }
     if (what & 2) tubek_plan_mppi_update(prob, cfg, it, reset_best, P, vbar, J, best_J, best_v, hist_row, n_bad, (hipStream_t)stream);
@@ -543,6 +589,11 @@ static std::string grad_reason(const lg_grad_cfg *c, int64_t B) {
 }
 
 int lg_plan_grad_check(const lg_grad_cfg *cfg, const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level, int64_t B) {
+    if (prob->tube_kind == LG_PLAN_TUBE_NN_STEP) {
+        lg_set_error("lg_plan_grad: tube_kind nn_step has no gradient planner: reverse mode through N chained MLP passes is not built "
+                     "(plan with lg_plan_mppi)");
+        return -1;
+    }
     if (lg_plan_check(prob, tube, has_level)) return -1;
     const std::string e = grad_reason(cfg, B);
     if (!e.empty()) { lg_set_error("lg_plan_grad: " + e); return -1; }

@@ -710,6 +710,174 @@ __global__ void __launch_bounds__(NT) k_plan_mppi_update(MppiDev M) {
     }
 }
 
+// ------------------------------------------------------------------ plans against a one-step tube
+// LG_PLAN_TUBE_NN_STEP: the flat scalar tube MLP rolled node by node along the plan, w[k+1] = fw(w[k], v[k], ..) (the reference's
+// trajopt/old/rom_tube_planning.py:106-107), inside the scoring tile.  A workgroup owns R plans as k_plan_score does and keeps their
+// history in LDS: per plan a line of inputs -- v_prev, then the plan, so the lane's walk still reads (N, 2) contiguous inputs -- and
+// a line of tube values e, w0, fw[0..N-1].  Per node it builds the (R, I) rows from the two lines, runs the L + 1 layers through
+// tube_layer -- the chains of k_tube_rollout, so fw carries that kernel's bits -- and the last layer appends fw[k] to the w lines.
+// The lines' strides are odd, so the 32 walking lanes fall on different banks.
+#define PLAN_STEP_VS(Hr, N) ((2 * ((Hr) + (N))) | 1)
+#define PLAN_STEP_WS(Hr, N) (((Hr) + (N) + 1) | 1)
+#define PLAN_STEP_PRE 4                 // row elements whose source a thread keeps in registers: R * 32 columns / NT
+constexpr size_t plan_step_floats(int I, int U, int Hr, int N) {   // the tile without the weights
+    return (size_t)R * (PLAN_STEP_VS(Hr, N) + PLAN_STEP_WS(Hr, N) + I + 2 * U + PLAN_ZS(N));
+}
+struct PlanStepTile {
+    float *W, *V, *WL, *X, *H0, *H1, *ZW;
+    int VS, WS;
+};
+__device__ __forceinline__ PlanStepTile plan_step_tile(float *lds, const TubeDev &D, const PlanDev &P, bool wlds) {
+    PlanStepTile S;
+    S.VS = PLAN_STEP_VS(P.Hr, P.p.N); S.WS = PLAN_STEP_WS(P.Hr, P.p.N);
+    S.W = lds;
+    S.V = lds + (wlds ? D.num_params : 0);
+    S.WL = S.V + R * S.VS; S.X = S.WL + R * S.WS; S.H0 = S.X + R * P.I; S.H1 = S.H0 + R * D.units; S.ZW = S.H1 + R * D.units;
+    return S;
+}
+// Element (r, c) of the row tile: where node 0 reads it, as a float offset from the V lines (the w lines follow them) with bit 30
+// set where the source advances 2 floats per node (an input column) instead of 1 (a tube column); -1 for the level column, which
+// is written once.  Tap i of node k is step k - i: the input at V[2 (Hr + k - i)], the tube value at WL[Hr + k - i] (Hr >= T - 1).
+__device__ __forceinline__ int plan_step_src(int r, int c, int Ix, bool rec, int Hr, int VS, int WS) {
+    if (c >= Ix) return -1;
+    int tap, col;                       // col 0: the tube value; 1, 2: the input's x, y
+    if (rec) { tap = c / 3; col = c - tap * 3; }
+    else if (c == 0) { tap = 0; col = 0; }
+    else { tap = (c - 1) >> 1; col = 1 + ((c - 1) & 1); }
+    return col == 0 ? R * VS + r * WS + Hr - tap : (1 << 30) | (r * VS + 2 * (Hr - tap) + col - 1);
+}
+// The node loop of a tile whose V and w lines are filled up to node 0 (no barrier needed before the call): fw[k] of every row lands
+// in its w line at Hr + 1 + k.  WLDS: the transposed weights and the biases are staged to LDS once, as in k_tube_rollout.
+template <bool WLDS>
+__device__ __forceinline__ void plan_step_roll(const TubeDev &D, const PlanDev &P, const PlanStepTile &S, int tid) {
+    const int N = P.p.N, I = P.I, Hr = P.Hr, U = D.units, L = D.layers, Ix = I - (D.level_input ? 1 : 0);
+    const bool rec = P.p.recursive != 0;
+    if (WLDS) {
+        for (int64_t p = tid; p < D.num_params; p += NT) S.W[p] = D.wt[p];
+        __syncthreads();
+        for (int li = 0; li <= L; ++li)
+            for (int j = tid; j < D.dout[li]; j += NT) S.W[D.off_b[li] + j] = D.params[D.off_b[li] + j];
+    }
+    const float *wsrc = WLDS ? S.W : D.wt, *bsrc = WLDS ? S.W : D.params;
+    int src[PLAN_STEP_PRE];
+#pragma unroll
+    for (int q = 0; q < PLAN_STEP_PRE; ++q) {
+        const int e = tid + q * NT;
+        src[q] = e < R * I ? plan_step_src(e / I, e % I, Ix, rec, Hr, S.VS, S.WS) : -1;
+    }
+    if (D.level_input)
+        for (int r = tid; r < R; r += NT) S.X[r * I + I - 1] = P.level;
+    __syncthreads();
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int q = 0; q < PLAN_STEP_PRE; ++q)
+            if (src[q] >= 0) S.X[tid + q * NT] = S.V[(src[q] & 0x3fffffff) + k * (1 + (src[q] >> 30))];
+        for (int e = tid + PLAN_STEP_PRE * NT; e < R * I; e += NT) {     // rows wider than 32 columns: the source per element
+            const int sc = plan_step_src(e / I, e % I, Ix, rec, Hr, S.VS, S.WS);
+            if (sc >= 0) S.X[e] = S.V[(sc & 0x3fffffff) + k * (1 + (sc >> 30))];
+        }
+        __syncthreads();
+        const float *in = S.X;
+        for (int li = 0; li < L; ++li) {
+            float *out = li & 1 ? S.H1 : S.H0;
+            tube_layer<R, RB, NT, false>(tid, D.din[li], U, in, wsrc + D.off_w[li], bsrc + D.off_b[li], D.act, D.sp_beta, out, nullptr, 0, 0);
+            __syncthreads();
+            in = out;
+        }
+        tube_layer<R, RB, NT, true>(tid, D.din[L], 1, in, wsrc + D.off_w[L], bsrc + D.off_b[L], D.act, D.sp_beta, nullptr,
+                                    S.WL + Hr + 1 + k, S.WS, R);
+        __syncthreads();
+    }
+}
+
+// k_plan_score for the one-step kind.  Dynamic LDS: (W the parameters), V (R, VS), WL (R, WS), X (R, I), H0, H1 (R, U), ZW (R, PLAN_ZS).
+template <bool WLDS>
+__global__ void __launch_bounds__(NT) k_plan_score_step(TubeDev D, PlanDev P, int64_t count) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, N = P.p.N, Hr = P.Hr, ZS = PLAN_ZS(N), VC = 2 * (Hr + N);
+    const int64_t base = (int64_t)blockIdx.x * R;
+    const int nr = (int)(count - base < R ? count - base : R);
+    const PlanStepTile S = plan_step_tile(lds, D, P, WLDS);
+    for (int e = tid; e < R * VC; e += NT) {            // rows past nr are zeros
+        const int r = e / VC, c = e - r * VC;
+        float x = 0.f;
+        if (r < nr) {
+            const int64_t b = base + r;
+            if (c < 2 * Hr) x = P.v_prev ? P.v_prev[b * 2 * Hr + c] : 0.f;
+            else x = P.v[b * 2 * N + (c - 2 * Hr)];
+        }
+        S.V[r * S.VS + c] = x;
+    }
+    for (int e = tid; e < R * (Hr + 1); e += NT) {
+        const int r = e / (Hr + 1), c = e - r * (Hr + 1);
+        float x = 0.f;
+        if (r < nr) {
+            const int64_t b = base + r;
+            if (c < Hr) x = P.e ? P.e[b * Hr + c] : 0.f;
+            else x = P.w0 ? P.w0[b] : 0.f;
+        }
+        S.WL[r * S.WS + c] = x;
+    }
+    plan_step_roll<WLDS>(D, P, S, tid);
+    if (tid < nr) {
+        const int64_t b = base + tid;
+        const PlanWalk W = plan_walk<false>(P.p, true, S.V + tid * S.VS + 2 * Hr, S.WL + tid * S.WS + Hr + 1, S.ZW + tid * ZS, P.z0[b * 2],
+                                            P.z0[b * 2 + 1], S.WL[tid * S.WS + Hr], P.offset);
+        P.cost[b] = W.cost; P.min_clear[b] = W.minc; P.worst_node[b] = W.worst;
+        P.n_viol[b * 4] = W.nv_g; P.n_viol[b * 4 + 1] = W.nv_v; P.n_viol[b * 4 + 2] = W.nv_z; P.n_viol[b * 4 + 3] = W.nv_w;
+    }
+    if (P.fw)
+        for (int e = tid; e < nr * N; e += NT) {
+            const int r = e / N, k = e - r * N;
+            P.fw[base * N + e] = S.WL[r * S.WS + Hr + 1 + k];
+        }
+    if (!P.z && !P.w) return;
+    __syncthreads();
+    for (int e = tid; e < nr * (N + 1); e += NT) {
+        const int r = e / (N + 1), k = e - r * (N + 1);
+        const float *zw = S.ZW + r * ZS + 3 * k;
+        const int64_t o = (base + r) * (N + 1) + k;
+        if (P.z) { P.z[o * 2] = zw[0]; P.z[o * 2 + 1] = zw[1]; }
+        if (P.w) P.w[o] = zw[2];
+    }
+}
+
+// k_plan_sample_score for the one-step kind: the same tile with the plan columns drawn in place; tile t holds candidates of one
+// instance, whose v_prev, e and w0 every row shares.  J is formed by k_plan_sample_score's expression.
+template <bool WLDS>
+__global__ void __launch_bounds__(NT) k_plan_sample_score_step(TubeDev D, PlanDev P, MppiDev M) {
+    extern __shared__ float lds[];
+    const int tid = threadIdx.x, N = P.p.N, Hr = P.Hr, ZS = PLAN_ZS(N);
+    const int64_t base = (int64_t)blockIdx.x * R;
+    const int pi = (int)(base / M.K), j0 = (int)(base - (int64_t)pi * M.K);
+    const PlanStepTile S = plan_step_tile(lds, D, P, WLDS);
+    for (int e = tid; e < R * 2 * Hr; e += NT) {
+        const int r = e / (2 * Hr), c = e - r * (2 * Hr);
+        S.V[r * S.VS + c] = P.v_prev ? P.v_prev[(int64_t)pi * Hr * 2 + c] : 0.f;
+    }
+    for (int q = tid; q < R * N; q += NT) {         // the plan: one Philox block per (candidate, node)
+        const int r = q / N, k = q - r * N;
+        const float *vb = M.vbar_in + ((int64_t)pi * N + k) * 2;
+        float *x = S.V + r * S.VS + 2 * Hr + 2 * k;
+        mppi_candidate(M, M.inst0 + (uint32_t)pi, j0 + r, k, vb[0], vb[1], x, x + 1);
+    }
+    for (int e = tid; e < R * (Hr + 1); e += NT) {
+        const int r = e / (Hr + 1), c = e - r * (Hr + 1);
+        S.WL[r * S.WS + c] = c < Hr ? (P.e ? P.e[(int64_t)pi * Hr + c] : 0.f) : (P.w0 ? P.w0[pi] : 0.f);
+    }
+    plan_step_roll<WLDS>(D, P, S, tid);
+    if (tid < R) {
+#pragma clang fp contract(off)
+        const int64_t b = base + tid;
+        const PlanWalk W = plan_walk<true>(P.p, true, S.V + tid * S.VS + 2 * Hr, S.WL + tid * S.WS + Hr + 1, S.ZW + tid * ZS, P.z0[pi * 2],
+                                           P.z0[pi * 2 + 1], P.w0 ? P.w0[pi] : 0.f, P.offset);
+        M.J[b] = ((W.cost + M.rho_g * W.pen_g) + M.rho_w * W.pen_w) + M.rho_z * W.pen_z;
+        if (P.cost) P.cost[b] = W.cost;
+        if (P.min_clear) P.min_clear[b] = W.minc;
+        if (M.pen) { M.pen[b * 3] = W.pen_g; M.pen[b * 3 + 1] = W.pen_w; M.pen[b * 3 + 2] = W.pen_z; }
+    }
+}
+
 // ------------------------------------------------------------------ gradient planner on a tube
 // J = ((cost + rho_g pen_g) + rho_w pen_w) + rho_z pen_z of R plans per workgroup and dJ/dv of every plan by a reverse sweep in the
 // same workgroup, with projected Adam and the elite fused behind it.  No atomics; a plan's outputs depend on its own row alone.
@@ -1246,6 +1414,75 @@ int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, c
         if (dev >= 0 && dev < 64) ceiling_set[dev] = true;
     }
     hipLaunchKernelGGL(k_plan_sample_score, dim3((unsigned)(P_ * cfg->K / R)), dim3(NT), bytes, s, T, P, M);
+    return (int64_t)bytes;
+}
+// The one-step kind.  Every shape of the envelope fits the ceiling without the weights -- the reference
+// configurations (T <= 10, units <= 128, N <= 64) with room to spare --; lg_plan_check asks tubek_plan_step_bytes all the same.
+static_assert(sizeof(float) * plan_step_floats(LG_TUBE_MAX_IN, LG_TUBE_MAX_UNITS, LG_PLAN_STEP_MAX_HREV, LG_PLAN_MAX_N) <= LG_TUBE_ROLLOUT_LDS,
+              "k_plan_score_step: the envelope's largest tile set must fit the dynamic LDS ceiling");
+static_assert(sizeof(float) * plan_step_floats(31, 128, LG_PLAN_STEP_MAX_HREV, 64) <= LG_TUBE_ROLLOUT_LDS, "the reference one-step shapes fit");
+// dynamic LDS of the one-step tile in bytes, without the weights
+int64_t tubek_plan_step_bytes(const TubeDev *D, const lg_plan_problem *prob) {
+    return (int64_t)(sizeof(float) * plan_step_floats(D->in_dim, D->units, prob->H_rev, prob->N));
+}
+static PlanDev plan_step_dev(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *e, const float *v_prev,
+                             const float *w0, const float *offset, float level) {
+    PlanDev P;
+    memset(&P, 0, sizeof(P));
+    P.p = *prob;
+    P.z0 = z0; P.e = e; P.v_prev = v_prev; P.w0 = w0; P.offset = offset;
+    P.level = level;
+    P.Hr = prob->H_rev;
+    P.I = D->in_dim;
+    return P;
+}
+// weights go to LDS where weights + tile fit the ceiling; *bytes: the launch's dynamic LDS
+static bool plan_step_wlds(const TubeDev *D, const lg_plan_problem *prob, size_t *bytes) {
+    const size_t tile = (size_t)tubek_plan_step_bytes(D, prob), all = tile + sizeof(float) * (size_t)D->num_params;
+    const bool wl = all <= LG_TUBE_ROLLOUT_LDS;
+    *bytes = wl ? all : tile;
+    return wl;
+}
+static int plan_step_ceiling(const void *f, bool *set) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    if (dev < 0 || dev >= 64 || !set[dev]) {
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
+        if (dev >= 0 && dev < 64) set[dev] = true;
+    }
+    return 0;
+}
+// returns the dynamic LDS of the launch in bytes, or -1 where the kernel's ceiling cannot be set
+int64_t tubek_plan_score_step(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
+                              const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
+                              float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, hipStream_t s) {
+    PlanDev P = plan_step_dev(D, prob, z0, e, v_prev, w0, offset, level);
+    P.v = v; P.cost = cost; P.min_clear = min_clear; P.worst_node = worst_node; P.n_viol = n_viol; P.fw = fw; P.z = z; P.w = w;
+    size_t bytes;
+    const bool wl = plan_step_wlds(D, prob, &bytes);
+    static bool ceiling_set[2][64];
+    const void *f = wl ? (const void *)k_plan_score_step<true> : (const void *)k_plan_score_step<false>;
+    if (plan_step_ceiling(f, ceiling_set[wl])) return -1;
+    const dim3 grid((unsigned)((B + R - 1) / R));
+    if (wl) hipLaunchKernelGGL(k_plan_score_step<true>, grid, dim3(NT), bytes, s, *D, P, B);
+    else hipLaunchKernelGGL(k_plan_score_step<false>, grid, dim3(NT), bytes, s, *D, P, B);
+    return (int64_t)bytes;
+}
+int64_t tubek_plan_sample_score_step(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
+                                     const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
+                                     const float *vbar, float *J, float *cost, float *min_clear, float *pen, hipStream_t s) {
+    PlanDev P = plan_step_dev(D, prob, z0, e, v_prev, w0, offset, level);
+    P.cost = cost; P.min_clear = min_clear;
+    MppiDev M = mppi_dev(prob, cfg, it);
+    M.vbar_in = vbar; M.J = J; M.pen = pen;
+    size_t bytes;
+    const bool wl = plan_step_wlds(D, prob, &bytes);
+    static bool ceiling_set[2][64];
+    const void *f = wl ? (const void *)k_plan_sample_score_step<true> : (const void *)k_plan_sample_score_step<false>;
+    if (plan_step_ceiling(f, ceiling_set[wl])) return -1;
+    const dim3 grid((unsigned)(P_ * cfg->K / R));
+    if (wl) hipLaunchKernelGGL(k_plan_sample_score_step<true>, grid, dim3(NT), bytes, s, *D, P, M);
+    else hipLaunchKernelGGL(k_plan_sample_score_step<false>, grid, dim3(NT), bytes, s, *D, P, M);
     return (int64_t)bytes;
 }
 void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,

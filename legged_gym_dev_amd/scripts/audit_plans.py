@@ -5,11 +5,16 @@ source, on the HIP kernels (legged_gym_dev_amd/tube/plan.py; DESIGN.md section 1
     python legged_gym_dev_amd/scripts/audit_plans.py (--run tube_runs/run0 | --tube l1|l2|l1_rolling|l2_rolling [--scaling s] [--window_size n]) \\
         (--problem gap|right|right_wide | --problem_json F) \\
         (--plans F.npz | --warm_start start|goal|interpolate [--perturb K --sigma s --seed n]) \\
-        [--calibration [PATH]] [--coverage c] [--level l] [--checkpoint best|latest] [--sim_cfg KEY=VALUE ...] [--out DIR] \\
+        [--calibration [PATH] | --age_calibration [PATH] [--trajectory_margin]] [--H_rev h] [--coverage c] [--level l] \\
+        [--checkpoint best|latest] [--sim_cfg KEY=VALUE ...] [--out DIR] \\
         [--robot [--task anymal_c_flat_trajectory] [--load_run R] [--policy_checkpoint K] [--push_robots] [--allow_fast]]
 
---run: a train_tube.py run of a one-shot tube (dataset scalar_horizon or scalar_horizon_level; any other is refused): the plans have
-N = the run's H_fwd nodes, and the tube item's past (H_rev error norms and inputs) is zero, as the reference's solve_tube starts.
+--run: a train_tube.py run of a one-shot tube (dataset scalar_horizon or scalar_horizon_level): the plans have N = the run's H_fwd
+nodes, and the tube item's past (H_rev error norms and inputs) is zero, as the reference's solve_tube starts.  Or a run of a flat
+scalar tube (dataset scalar or scalar_level, dN = 1), which is rolled node by node along the plan: N is --N
+(default 50), the window and --recursive come from its config.json, the history is --H_rev steps (default: the taps - 1), and
+--age_calibration [PATH] [--coverage c] [--trajectory_margin] (calibrate_tube.py --by_age) or --calibration pick the offsets.  Vector,
+error-dynamics and Alpha runs are refused.
 --tube: an analytic baseline tube instead (trajopt/tube_trajopt.py:489-540); N is --N (default 50).
 --plans: an .npz with z0 (B, 2) and v (B, N, 2).  --warm_start: the reference's warm start of the problem and, with --perturb K, K
 clipped Gaussian perturbations of it beside it (sigma in the input's units, clipped to the problem's input bounds).
@@ -38,13 +43,16 @@ import numpy as np  # noqa: E402
 from legged_gym_dev_amd.tube import plan as pl  # noqa: E402
 
 ONE_SHOT = ("scalar_horizon", "scalar_horizon_level")
+STEP = ("scalar", "scalar_level")                   # the flat scalar tubes, rolled node by node along the plan (tube_kind nn_step)
+LEVEL_RUNS = ("scalar_horizon_level", "scalar_level")
+ANALYTIC = ("l1", "l2", "l1_rolling", "l2_rolling")
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     tube = ap.add_mutually_exclusive_group(required=True)
     tube.add_argument("--run", help="folder train_tube.py wrote for a one-shot tube")
-    tube.add_argument("--tube", choices=[k for k in pl.TUBE_KINDS if k != "nn"], help="an analytic tube")
+    tube.add_argument("--tube", choices=list(ANALYTIC), help="an analytic tube")
     ap.add_argument("--scaling", type=float, default=0.5)
     ap.add_argument("--window_size", type=int, default=10)
     ap.add_argument("--N", type=int, default=None, help="nodes of an analytic-tube problem (default 50); a run fixes it to its H_fwd")
@@ -58,6 +66,7 @@ def parse_args(argv=None):
     ap.add_argument("--sigma", type=float, default=0.05)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--calibration", nargs="?", const="", default=None, metavar="PATH")
+    add_step_flags(ap)
     ap.add_argument("--coverage", type=float, default=None)
     ap.add_argument("--level", type=float, default=None)
     ap.add_argument("--checkpoint", choices=["best", "latest"], default="best")
@@ -85,28 +94,85 @@ def parse_args(argv=None):
         ap.error("--calibration belongs to --run: an analytic tube has none")
     if a.tube and a.level is not None:
         ap.error("--level belongs to a level-conditioned --run")
+    check_step_flags(ap, a)
     return a
 
 
+def add_step_flags(ap):
+    """The flags of a step run (dataset scalar / scalar_level), shared with plan_tube.py."""
+    ap.add_argument("--age_calibration", nargs="?", const="", default=None, metavar="PATH",
+                    help="a step run: the per-age offsets calibrate_tube.py --by_age wrote (default PATH: the run's calibration_age.json)")
+    ap.add_argument("--trajectory_margin", action="store_true", help="--age_calibration: add its trajectory margin")
+    ap.add_argument("--H_rev", type=int, default=None, help="a step run: past steps of the plan's history (default: the model's taps - 1)")
+
+
+def check_step_flags(ap, a):
+    if a.age_calibration is not None and not a.run:
+        ap.error("--age_calibration belongs to --run: an analytic tube has none")
+    if a.age_calibration is not None and a.calibration is not None:
+        ap.error("--age_calibration and --calibration both name the offsets: give one")
+    if a.trajectory_margin and a.age_calibration is None:
+        ap.error("--trajectory_margin belongs to --age_calibration")
+    if a.H_rev is not None and (not a.run or a.H_rev < 0):
+        ap.error("--H_rev belongs to a step --run and is not negative")
+
+
 def run_config(run):
-    """config.json of the run; ValueError unless it trained a one-shot tube."""
+    """config.json of the run; ValueError unless it trained a one-shot tube or a flat scalar tube with dN = 1."""
     from legged_gym_dev_amd.tube.model import read_config
     cfg = read_config(run)
-    if cfg.get("dataset") not in ONE_SHOT:
-        raise ValueError(f"{run} trained a {cfg.get('dataset')!r} model; plans are scored by a one-shot tube: dataset {' or '.join(ONE_SHOT)}")
+    kind = cfg.get("dataset")
+    if kind in STEP:
+        missing = [k for k in ("N", "dN", "recursive") if k not in cfg]
+        if missing:
+            raise ValueError(f"{run}: config.json of the {kind!r} run holds no {', '.join(missing)}, so its rows cannot be rebuilt along a plan; "
+                             f"plans are scored by such a step run or by a one-shot tube (dataset {' or '.join(ONE_SHOT)})")
+        if cfg["dN"] != 1:
+            raise ValueError(f"{run} trained with dN = {cfg['dN']}; a tube is rolled along a plan node by node: dN must be 1")
+        return cfg
+    if kind not in ONE_SHOT:
+        raise ValueError(f"{run} trained a {kind!r} model; plans are scored by a one-shot tube (dataset {' or '.join(ONE_SHOT)}) or by a "
+                         f"flat scalar tube rolled along the plan (dataset {' or '.join(STEP)}); vector, error-dynamics and Alpha tubes are not")
     return cfg
 
 
+def is_step(cfg):
+    return bool(cfg) and cfg.get("dataset") in STEP
+
+
+def load_calibration(a, cfg):
+    """The calibration --calibration / --age_calibration names, or None.  A step run takes either; a one-shot run --calibration."""
+    from legged_gym_dev_amd.tube.calibrate import AgeCalibration, Calibration, default_age_path, default_path
+    if a.age_calibration is not None:
+        if not is_step(cfg):
+            raise ValueError(f"--age_calibration belongs to a step run (dataset {' or '.join(STEP)}); {a.run} trained {cfg.get('dataset')!r}")
+        path = a.age_calibration or default_age_path(a.run)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{path} is missing: calibrate_tube.py --run {a.run} --by_age writes it")
+        return AgeCalibration.load(path)
+    if a.calibration is None:
+        return None
+    path = a.calibration or default_path(a.run)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path} is missing: calibrate_tube.py --run {a.run} writes it")
+    return Calibration.load(path)
+
+
 def build_problem(a, cfg):
-    kw = {"tube_kind": "nn", "N": cfg["H_fwd"], "H_rev": cfg["H_rev"]} if cfg else \
-        {"tube_kind": a.tube, "scaling": a.scaling, "window_size": a.window_size, **({"N": a.N} if a.N else {})}
+    if is_step(cfg):
+        kw = {"tube_kind": "nn_step", "recursive": bool(cfg["recursive"]), **({"N": a.N} if a.N else {}),
+              "H_rev": max(int(cfg["N"]) - 1, 0) if getattr(a, "H_rev", None) is None else a.H_rev}
+    elif cfg:
+        kw = {"tube_kind": "nn", "N": cfg["H_fwd"], "H_rev": cfg["H_rev"]}
+    else:
+        kw = {"tube_kind": a.tube, "scaling": a.scaling, "window_size": a.window_size, **({"N": a.N} if a.N else {})}
     if a.problem:
         return pl.PlanProblem.named(a.problem, **kw)
     with open(a.problem_json) as f:
         given = json.load(f)
     p = pl.PlanProblem.from_json(a.problem_json)
     for k, v in kw.items():
-        if k in ("N", "H_rev") and cfg and k in given and given[k] != v:
+        if k in ("N", "H_rev") and cfg and not is_step(cfg) and k in given and given[k] != v:
             raise ValueError(f"{a.problem_json}: {k}={given[k]} differs from the run's {v}")
         setattr(p, k, v)
     return p
@@ -202,22 +268,18 @@ def main(argv=None):
     model = calib = sim = None
     level = a.level
     if a.run:
-        from legged_gym_dev_amd.tube.calibrate import Calibration, default_path
         from legged_gym_dev_amd.tube.model import HipTubeModel
-        if cfg["dataset"] == "scalar_horizon_level" and level is None:
-            raise ValueError("--level is required: the run is level-conditioned (scalar_horizon_level)")
-        if a.calibration is not None:
-            path = a.calibration or default_path(a.run)
-            if not os.path.isfile(path):
-                raise FileNotFoundError(f"{path} is missing: calibrate_tube.py --run {a.run} writes it")
-            calib = Calibration.load(path)
+        if cfg["dataset"] in LEVEL_RUNS and level is None:
+            raise ValueError(f"--level is required: the run is level-conditioned ({cfg['dataset']})")
+        calib = load_calibration(a, cfg)
     else:
         pl.check_envelope(p)
     z0, v, source = build_plans(a, p)
     try:
         if a.run:
             model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, device=a.device)
-        scorer = pl.HipPlanScorer(model, p, calibration=calib, level=level, coverage=a.coverage, device=a.device)
+        scorer = pl.HipPlanScorer(model, p, calibration=calib, level=level, coverage=a.coverage, device=a.device,
+                                  trajectory=a.trajectory_margin)
         robot = {}
         if a.robot:
             s, res, robot = main_robot(a, p, scorer, z0, v)
@@ -230,7 +292,7 @@ def main(argv=None):
         cost, clear = s["cost"].cpu().double(), s["min_clear"].cpu().double()
         extra = {"cost_mean": float(cost.mean()), "cost_min": float(cost.min()), "best_plan": int(cost.argmin()),
                  "min_clear_min": float(clear.min()) if p.n_obs else None, "n_viol_plans": [int(x) for x in (s["n_viol"] > 0).sum(dim=0).cpu()],
-                 "problem": p.to_json(), "run": a.run, "tube": a.tube or "nn", "level": level,
+                 "problem": p.to_json(), "run": a.run, "tube": a.tube or p.tube_kind, "level": level,
                  "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), "source": source, **robot}
         assert not set(extra) & set(res), "a key of the audit would be overwritten"
         res.update(extra)

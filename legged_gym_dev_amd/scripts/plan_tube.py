@@ -4,13 +4,16 @@ section 10.10) --, a first-order one -- projected Adam on the HIP plan gradient 
 place of CasADi / IPOPT, for many starts at once.
 
     python legged_gym_dev_amd/scripts/plan_tube.py (--run tube_runs/run0 | --tube l1|l2|l1_rolling|l2_rolling [--scaling s] [--window_size n]) \\
-        --problem gap|right|right_wide|F.json [--level l] [--calibration [PATH]] [--coverage c] \\
+        --problem gap|right|right_wide|F.json [--level l] [--calibration [PATH] | --age_calibration [PATH] [--trajectory_margin]] \\
+        [--H_rev h] [--coverage c] [--w0 zero|error] \\
         [--K 256] [--iters 20] [--sigma 0.3] [--sigma_decay 1] [--lambda 1] [--rho_g 1e4] [--rho_w 0] [--rho_z 0] [--seed 0] \\
         [--planner mppi|grad|mppi+grad] [--lr 0.05] [--grad_iters 100] \\
         [--starts P --start_noise s] [--closed_loop H] [--sim_cfg KEY=VALUE ...] [--out DIR]
 
 --run, --tube, --calibration, --coverage, --level, --checkpoint, --sim_cfg: as audit_plans.py takes them; a run that audit_plans.py
-refuses (not a one-shot tube) is refused here.  --planner: mppi (the default), grad (--grad_iters steps of rate --lr from the warm start; the rho are shared) or mppi+grad (MPPI,
+refuses is refused here; a step run (dataset scalar / scalar_level, rolled along the plan: DESIGN.md section 10.13) plans with
+--planner mppi only, and --w0 error starts each replanning of --closed_loop at the tracking error, the quantity its first column was
+trained on.  --planner: mppi (the default), grad (--grad_iters steps of rate --lr from the warm start; the rho are shared) or mppi+grad (MPPI,
 then the gradient planner from MPPI's best plan).  --problem: one of the reference's problems, or a PlanProblem as JSON (a path ending
 in .json).  --starts P: P instances; the first starts at the problem's start, the others at start + start_noise * standard normal.
 Without --closed_loop every start gets one plan, which is scored, tracked and audited as audit_plans.py does.  With --closed_loop H
@@ -36,12 +39,15 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     tube = ap.add_mutually_exclusive_group(required=True)
     tube.add_argument("--run", help="folder train_tube.py wrote for a one-shot tube")
-    tube.add_argument("--tube", choices=[k for k in pl.TUBE_KINDS if k != "nn"], help="an analytic tube")
+    tube.add_argument("--tube", choices=list(audit_plans.ANALYTIC), help="an analytic tube")
     ap.add_argument("--scaling", type=float, default=0.5)
     ap.add_argument("--window_size", type=int, default=10)
     ap.add_argument("--N", type=int, default=None, help="nodes of an analytic-tube problem (default 50); a run fixes it to its H_fwd")
     ap.add_argument("--problem", required=True, help="gap, right, right_wide, or a PlanProblem as JSON (F.json)")
     ap.add_argument("--calibration", nargs="?", const="", default=None, metavar="PATH")
+    audit_plans.add_step_flags(ap)
+    ap.add_argument("--w0", choices=["zero", "error"], default="zero",
+                    help="--closed_loop: start every replanning's tube at 0 or at the tracking error |z_k - pz_x_k|")
     ap.add_argument("--coverage", type=float, default=None)
     ap.add_argument("--level", type=float, default=None)
     ap.add_argument("--checkpoint", choices=["best", "latest"], default="best")
@@ -77,6 +83,9 @@ def parse_args(argv=None):
         ap.error("--starts must be at least 1 and --start_noise not negative")
     if a.closed_loop is not None and a.closed_loop < 1:
         ap.error("--closed_loop H: at least 1 step")
+    if a.w0 != "zero" and a.closed_loop is None:
+        ap.error("--w0 belongs to --closed_loop")
+    audit_plans.check_step_flags(ap, a)
     try:
         if "mppi" in a.planner:
             mppi_cfg(a).check(a.starts)
@@ -103,7 +112,9 @@ def make_planner(a, model, p, calib):
     """The planner --planner names, on one scorer's arguments."""
     kw = dict(calibration=calib, level=a.level, coverage=a.coverage, device=a.device)
     if a.planner == "mppi":
-        return pl.HipMppiPlanner(model, p, mppi_cfg(a), **kw)
+        return pl.HipMppiPlanner(model, p, mppi_cfg(a), trajectory=a.trajectory_margin, **kw)
+    if p.tube_kind == "nn_step":
+        raise ValueError(pl.NO_GRADIENT)
     if a.planner == "grad":
         return pl.HipGradPlanner(model, p, grad_cfg(a), **kw)
     return pl.ChainedPlanner(pl.HipMppiPlanner(model, p, mppi_cfg(a), **kw), pl.HipGradPlanner(model, p, grad_cfg(a), **kw))
@@ -111,7 +122,7 @@ def make_planner(a, model, p, calib):
 
 def build_problem(a, cfg):
     named = a.problem in pl.PROBLEMS
-    return audit_plans.build_problem(argparse.Namespace(tube=a.tube, scaling=a.scaling, window_size=a.window_size, N=a.N,
+    return audit_plans.build_problem(argparse.Namespace(tube=a.tube, scaling=a.scaling, window_size=a.window_size, N=a.N, H_rev=a.H_rev,
                                                         problem=a.problem if named else None, problem_json=None if named else a.problem), cfg)
 
 
@@ -133,15 +144,10 @@ def main(argv=None):
     from legged_gym_dev_amd.tube.rom_sim import HipRomSim
     model = calib = sim = None
     if a.run:
-        from legged_gym_dev_amd.tube.calibrate import Calibration, default_path
         from legged_gym_dev_amd.tube.model import HipTubeModel
-        if cfg["dataset"] == "scalar_horizon_level" and a.level is None:
-            raise ValueError("--level is required: the run is level-conditioned (scalar_horizon_level)")
-        if a.calibration is not None:
-            path = a.calibration or default_path(a.run)
-            if not os.path.isfile(path):
-                raise FileNotFoundError(f"{path} is missing: calibrate_tube.py --run {a.run} writes it")
-            calib = Calibration.load(path)
+        if cfg["dataset"] in audit_plans.LEVEL_RUNS and a.level is None:
+            raise ValueError(f"--level is required: the run is level-conditioned ({cfg['dataset']})")
+        calib = audit_plans.load_calibration(a, cfg)
     else:
         pl.check_envelope(p)
     z0 = starts(a, p)
@@ -160,7 +166,7 @@ def main(argv=None):
                      "cost": [float(x) for x in sol["score"]["cost"].cpu()]}
         else:
             first = planner.plan(z0)                                     # the history of the first plan; closed_loop makes it again
-            res = pl.closed_loop(planner, sim, a.closed_loop, z0, keep_plans=True)
+            res = pl.closed_loop(planner, sim, a.closed_loop, z0, keep_plans=True, w0=a.w0)
             torch.cuda.synchronize()
             audit = pl.audit_closed_loop(res, p, goal_tol=a.goal_tol)
             hist = first["hist"]
@@ -174,7 +180,9 @@ def main(argv=None):
             model.close()
     out = {"audit": audit, "hist": hist.cpu().double().tolist(), "closed_loop": a.closed_loop, "starts": z0.double().tolist(),
            "mppi": {**{k: v for k, v in vars(mppi_cfg(a)).items() if k != "lambda_"}, "lambda": a.lambda_}, "problem": p.to_json(),
-           "run": a.run, "tube": a.tube or "nn", "level": a.level, "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), **extra}
+           "run": a.run, "tube": a.tube or p.tube_kind, "level": a.level, "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), **extra}
+    if a.w0 != "zero":
+        out["w0"] = a.w0
     if a.planner != "mppi":
         out.update({"planner": a.planner, "grad": vars(grad_cfg(a))})
     folder = a.out or a.run or "."

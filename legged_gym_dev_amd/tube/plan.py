@@ -7,7 +7,9 @@ objective :41-56,206-212, the analytic baseline tubes :489-540 and the problems 
 loop is deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.py:75-88.  The plans come from any solver, from
 ``warm_start`` and ``perturb``, or from the planners below -- the sampling ``HipMppiPlanner`` (section 10.10), the first-order
 ``HipGradPlanner`` (section 10.11), or one after the other (``ChainedPlanner``) -- in ``closed_loop`` or alone, which stand in
-for the reference's NLP solve.  There is no CPU fallback: scoring, planning and tracking need the library and a GPU.
+for the reference's NLP solve.  tube_kind "nn_step" (section 10.13) scores and plans with a flat one-step tube instead, rolled node
+by node along the plan inside the kernels (w[k+1] = fw(w[k], v[k], ..), trajopt/old/rom_tube_planning.py:106-107).
+There is no CPU fallback: scoring, planning and tracking need the library and a GPU.
 """
 import ctypes as C
 import dataclasses
@@ -29,6 +31,9 @@ PROBLEMS = {
 }
 TUBE_KINDS = tuple(capi.PLAN_TUBE)
 ROLLING = ("l1_rolling", "l2_rolling")
+MODEL_KINDS = ("nn", "nn_step")                     # the kinds that query a tube model; the others are analytic
+NO_GRADIENT = ("tube_kind 'nn_step' has no gradient planner: reverse mode through N chained MLP passes is not built "
+               "(plan with HipMppiPlanner)")
 
 
 def _eye(s):
@@ -38,7 +43,7 @@ def _eye(s):
 @dataclasses.dataclass
 class PlanProblem:
     """lg_plan_problem, field for field, plus the start the warm starts leave from.  Q, Qf, R: 2 x 2 row-major (4 numbers);
-    Qf None = Q (TT:200-201).  The defaults are the reference script's: N = 50, Q = R = 10 I, Qw = 0, w_max = 1."""
+    Qf None = Q (TT:200-201).  recursive: the row layout of an nn_step model (train_tube.py --recursive).  The defaults are the reference script's: N = 50, Q = R = 10 I, Qw = 0, w_max = 1."""
     N: int = 50
     dt: float = 0.1
     start: List[float] = dataclasses.field(default_factory=lambda: [0.0, 0.0])
@@ -49,6 +54,7 @@ class PlanProblem:
     tube_kind: str = "nn"
     scaling: float = 0.5
     window_size: int = 10
+    recursive: bool = False
     w_max: float = 1.0
     Qw: float = 0.0
     Q: List[float] = dataclasses.field(default_factory=lambda: _eye(10))
@@ -91,6 +97,7 @@ class PlanProblem:
         q = capi.lg_plan_problem()
         q.N, q.H_rev, q.n_obs, q.window_size = int(self.N), int(self.H_rev), int(self.n_obs), int(self.window_size)
         q.tube_kind = capi.PLAN_TUBE.get(self.tube_kind, -1)
+        q.recursive = int(bool(self.recursive))
         q.dt, q.scaling, q.w_max, q.Qw = float(self.dt), float(self.scaling), float(self.w_max), float(self.Qw)
         for i in range(min(self.n_obs, capi.PLAN_MAX_OBS)):
             q.obs_c[i][0], q.obs_c[i][1], q.obs_r[i] = float(self.obs_c[i][0]), float(self.obs_c[i][1]), float(self.obs_r[i])
@@ -124,14 +131,16 @@ def check_envelope(problem, model=None, level=None):
     for name in ("Q", "R") + (("Qf",) if p.Qf is not None else ()):
         if len(getattr(p, name)) != 4:
             raise ValueError(f"{name}: a 2 x 2 matrix as 4 numbers, row-major")
-    if p.tube_kind != "nn":
+    if p.tube_kind not in MODEL_KINDS:
         if level is not None:
             raise ValueError("level is given, but an analytic tube_kind has none")
         return
     if model is None:
-        raise ValueError("tube_kind 'nn' needs a tube model (a handle)")
+        raise ValueError(f"tube_kind {p.tube_kind!r} needs a tube model (a handle)")
     dims = getattr(model, "dims", None)
     input_dim = dims[0] if dims else model.input_dim
+    if p.tube_kind == "nn_step":
+        return _check_step(p, model, input_dim, dims[1] if dims else model.output_dim, level)
     if model.horizon is None:
         raise ValueError("the tube model is not a horizon model: a plan is scored by a one-shot tube (dataset scalar_horizon)")
     Hf, Hr = model.horizon
@@ -147,6 +156,74 @@ def check_envelope(problem, model=None, level=None):
         raise ValueError("level is given, but the model is not level-conditioned")
     if level is None and model.level_input:
         raise ValueError("level is missing: the model is level-conditioned")
+
+
+def step_taps(input_dim, level_input, recursive):
+    """Taps T of a flat scalar tube model: with I' = input_dim minus the level column, I' = 1 + 2 T (not
+    recursive) or 3 T (recursive).  ValueError naming input_dim and recursive where I' fits the form in no T >= 1."""
+    Ip = int(input_dim) - int(bool(level_input))
+    T = Ip // 3 if recursive else (Ip - 1) // 2
+    if Ip < 3 or (Ip % 3 if recursive else (Ip - 1) % 2):
+        raise ValueError(f"the model's input_dim={input_dim}{' (one of them the level)' if level_input else ''} with recursive={bool(recursive)} "
+                         f"is not {'3 T' if recursive else '1 + 2 T'}{' + 1' if level_input else ''} for any T >= 1 (the ROM is SingleInt2D: "
+                         "no state columns past the position)")
+    return T
+
+
+_STEP_ROWS, _STEP_LDS = 32, 144 * 1024               # LG_TUBE_ROWS, LG_TUBE_ROLLOUT_LDS (csrc/tube_device.h)
+
+
+def step_tile_bytes(input_dim, units, H_rev, N):
+    """Dynamic LDS of k_plan_score_step's tile without the weights (tube_kernels.hip plan_step_floats)."""
+    return 4 * _STEP_ROWS * (((2 * (H_rev + N)) | 1) + ((H_rev + N + 1) | 1) + input_dim + 2 * units + (((N + 1) * 3) | 1))
+
+
+def _check_step(p, model, input_dim, output_dim, level):
+    """check_envelope for tube_kind 'nn_step' (lg_plan_check refuses the same)."""
+    if model.horizon is not None:
+        raise ValueError("the tube model is a horizon model: nn_step rolls a flat one-step tube along the plan (dataset scalar)")
+    if output_dim != 1:
+        raise ValueError(f"the model's output_dim={output_dim} must be 1: nn_step rolls a scalar tube")
+    T = step_taps(input_dim, model.level_input, p.recursive)
+    if not 0 <= p.H_rev <= capi.PLAN_STEP_MAX_HREV or p.H_rev < T - 1:
+        raise ValueError(f"H_rev={p.H_rev}: 0..{capi.PLAN_STEP_MAX_HREV} and at least T - 1 = {T - 1} (the delayed taps of node 0 come from "
+                         "e and v_prev)")
+    units = getattr(model, "dims", (0, 0, getattr(model, "num_units", 0)))[2]
+    if step_tile_bytes(input_dim, units, p.H_rev, p.N) > _STEP_LDS:
+        raise ValueError(f"the tile of input_dim={input_dim}, {units} units, H_rev={p.H_rev} and N={p.N} does not fit the dynamic LDS ceiling")
+    if level is not None and not model.level_input:
+        raise ValueError("level is given, but the model is not level-conditioned")
+    if level is None and model.level_input:
+        raise ValueError("level is missing: the model is level-conditioned")
+
+
+def step_offsets(calibration, N, coverage=None, level=None, trajectory=False):
+    """The offsets (N) float32 an nn_step plan adds to fw[0..N-1].  fw[k] is k fed-back steps after the seed w0, so an
+    AgeCalibration gives offset_at(age = k, coverage) (ages past max_age - 1 share the last group; trajectory adds the margin), and
+    a Calibration of kind 'flat' or 'levels' its one_step offset at k = 0 and its rollout offset at k >= 1."""
+    import torch
+    from .calibrate import AgeCalibration
+    if isinstance(calibration, AgeCalibration):
+        if coverage is None and len(calibration.coverages) == 1:
+            coverage = calibration.coverages[0]
+        if coverage is None:
+            raise ValueError(f"a per-age calibration needs the coverage: one of {calibration.coverages}")
+        off = calibration.offset_at(torch.arange(N), coverage, trajectory=trajectory)
+        if off.shape[-1] != 1:
+            raise ValueError(f"the per-age calibration holds {off.shape[-1]} columns; nn_step rolls a scalar tube")
+        return off[:, 0].float().contiguous()
+    if trajectory:
+        raise ValueError("the trajectory margin belongs to a per-age calibration (calibrate_tube.py --by_age --trajectory)")
+    if calibration.kind not in ("flat", "levels"):
+        raise ValueError(f"a {calibration.kind!r} calibration holds offsets per step ahead of a one-shot tube; nn_step takes kind 'flat' or "
+                         "'levels' (calibrate_tube.py on a scalar / scalar_level run) or a per-age one (--by_age)")
+    if calibration.kind == "flat" and coverage is None and len(calibration.coverages) == 1:
+        coverage = calibration.coverages[0]
+    kw = dict(level=level) if calibration.kind == "levels" else dict(coverage=coverage)
+    one, roll = calibration.offset(part="one_step", **kw), calibration.offset(part="rollout", **kw)
+    if one.numel() != 1:
+        raise ValueError(f"the calibration holds {one.numel()} columns; nn_step rolls a scalar tube")
+    return torch.cat([one.reshape(1), roll.reshape(1).repeat(N - 1)]).float().contiguous()
 
 
 def warm_start(kind, start, goal, N, dt):
@@ -185,19 +262,27 @@ def _ptr(t):
 
 
 class HipPlanScorer:
-    """lg_plan_score on one problem.  model: a HipTubeModel / HipTubeTrainer of a one-shot horizon tube, or None for the analytic
-    kinds.  calibration: a Calibration of kind 'horizon' (pick the set with `coverage`; a single set needs none) or
-    'horizon_levels' (the set of `level`); its offsets are added per step ahead.  level: a level-conditioned model's level."""
+    """lg_plan_score on one problem.  model: a HipTubeModel / HipTubeTrainer of a one-shot horizon tube ('nn'), of a flat scalar
+    tube ('nn_step'), or None for the analytic kinds.  calibration: a Calibration of kind 'horizon' (pick
+    the set with `coverage`; a single set needs none) or 'horizon_levels' (the set of `level`); its offsets are added per step
+    ahead.  For 'nn_step': an AgeCalibration (`coverage`; `trajectory` adds its margin) or a Calibration of kind 'flat' / 'levels'
+    (step_offsets).  level: a level-conditioned model's level."""
 
-    def __init__(self, model, problem, calibration=None, level=None, coverage=None, device=None):
+    def __init__(self, model, problem, calibration=None, level=None, coverage=None, device=None, trajectory=False):
         import torch
         from ..lib import LeggedHipError, load
         check_envelope(problem, model, level)
         self.problem, self.level = problem, level
-        self.model = model if problem.tube_kind == "nn" else None
+        self.model = model if problem.tube_kind in MODEL_KINDS else None
         self._err = LeggedHipError
         self.offset = None
-        if calibration is not None:
+        if calibration is not None and problem.tube_kind == "nn_step":
+            self.offset = step_offsets(calibration, problem.N, coverage=coverage, level=level, trajectory=trajectory)
+        elif calibration is not None:
+            if trajectory:
+                raise ValueError("the trajectory margin belongs to a per-age calibration on tube_kind 'nn_step'")
+            if not hasattr(calibration, "kind"):
+                raise ValueError("a per-age calibration does not fit a one-shot tube: it belongs to tube_kind 'nn_step'")
             if calibration.kind not in ("horizon", "horizon_levels"):
                 raise ValueError(f"a {calibration.kind!r} calibration does not fit a plan: offsets per step ahead come from kind "
                                  "'horizon' or 'horizon_levels' (calibrate_tube.py on a scalar_horizon / scalar_horizon_level run)")
@@ -368,9 +453,10 @@ class HipMppiPlanner:
     """lg_plan_mppi on one problem for P instances at once, built on a HipPlanScorer: the handle, offset, level and envelope checks
     are the scorer's.  The arguments after cfg are HipPlanScorer's."""
 
-    def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None):
+    def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None, trajectory=False):
         cfg.check()
-        self.scorer = HipPlanScorer(model, problem, calibration=calibration, level=level, coverage=coverage, device=device)
+        self.scorer = HipPlanScorer(model, problem, calibration=calibration, level=level, coverage=coverage, device=device,
+                                    trajectory=trajectory)
         self.problem, self.cfg, self.device, self.lib = problem, cfg, self.scorer.device, self.scorer.lib
         self._err = self.scorer._err
 
@@ -522,9 +608,12 @@ class HipGradPlanner:
     warm_start = HipMppiPlanner.warm_start
     _fail = HipMppiPlanner._fail
     _stream = HipMppiPlanner._stream
+    needs_gradient = True
 
     def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None):
         cfg.check()
+        if problem.tube_kind == "nn_step":
+            raise ValueError(NO_GRADIENT)
         self.scorer = HipPlanScorer(model, problem, calibration=calibration, level=level, coverage=coverage, device=device)
         self.problem, self.cfg, self.device, self.lib = problem, cfg, self.scorer.device, self.scorer.lib
         self._err = self.scorer._err
@@ -621,6 +710,8 @@ class ChainedPlanner:
     def __init__(self, first, second):
         if first.problem is not second.problem and first.problem != second.problem:
             raise ValueError("the two planners of a chain must share one problem")
+        if getattr(first.problem, "tube_kind", None) == "nn_step" and any(getattr(pln, "needs_gradient", False) for pln in (first, second)):
+            raise ValueError(NO_GRADIENT)
         self.first, self.second = first, second
         self.problem, self.device = first.problem, first.device
 
@@ -647,7 +738,7 @@ def shift_past(e, v_prev, err, v_k):
     return torch.cat([e[:, 1:], err[:, None]], dim=1), torch.cat([v_prev[:, 1:], v_k[:, None]], dim=1)
 
 
-def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=False, track_fn=None):
+def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=False, track_fn=None, w0="zero"):
     """trajopt/tube_planning_closed_loop.py:82-168 ("TPCL") for P robots at once: plan, apply the first action, replan, H times.
     start (P, 2); x0 (P, 4) the robots' states, None = (start, 0, 0).  The first plan runs iters_first iterations (None = cfg.iters)
     from the warm start, every later one cfg.iters from the previous mean plan shifted by one step.
@@ -655,6 +746,8 @@ def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=Fa
     z_sol[0], feed-forward v_sol[1] (TPCL:91-96), from the robot's state; x[:, 1] and its actions are kept.  Recorded: v_k = v_sol[0],
     z_{k+1} = z_sol[1], w_{k+1} = w_sol[1], pz_x_{k+1}; then e and v_prev shift by one and take |z_k - pz_x_k| and v_k, and the next
     plan starts from the ROM's z_{k+1} (TPCL:159).  No plan is made after the last step.
+    w0: "zero" starts every plan's tube at 0 (w0 = None); "error" at |z_k - pz_x_k|, the tracking error at the replanning instant --
+    the quantity the first column of a one-step tube model (tube_kind 'nn_step') was trained on.
     Returns device tensors z (P, H+1, 2), v (P, H, 2), w (P, H+1), pz_x (P, H+1, 2), x (P, H+1, 4), u (P, H S, 2), cost, min_clear,
     best_J (P, H) of the plan in force, n_bad (P, H) and, with keep_plans, plans_v (H, P, N, 2), plans_z (H, P, N+1, 2), plans_w."""
     import torch
@@ -665,6 +758,8 @@ def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=Fa
     P = start.shape[0]
     if H < 1:
         raise ValueError(f"H = {H} must be at least 1")
+    if w0 not in ("zero", "error"):
+        raise ValueError(f"w0 = {w0!r}: 'zero' or 'error'")
     xk = torch.cat([start, torch.zeros(P, 2, device=dev)], dim=1) if x0 is None else torch.as_tensor(x0, dtype=torch.float32).to(dev)
     if tuple(xk.shape) != (P, 4):
         raise ValueError(f"x0 must be {(P, 4)}; got {tuple(xk.shape)}")
@@ -672,7 +767,8 @@ def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=Fa
     zk = start
     z, v, w, pz, x, u = [zk], [], [torch.zeros(P, device=dev)], [xk[:, :2]], [xk], []
     cost, clear, bestJ, nbad, plans = [], [], [], [], {"v": [], "z": [], "w": []}
-    sol = planner.plan(zk, None, e, v_prev, None, iters=iters_first)
+    w_start = (lambda: None) if w0 == "zero" else (lambda: torch.linalg.vector_norm(z[-1] - pz[-1], dim=1))
+    sol = planner.plan(zk, None, e, v_prev, w_start(), iters=iters_first)
     for k in range(H):
         v_sol, z_sol, w_sol = sol["v"], sol["score"]["z"], sol["score"]["w"]
         ff = v_sol[:, min(1, p.N - 1)][:, None]
@@ -686,7 +782,7 @@ def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=Fa
             plans["v"].append(v_sol), plans["z"].append(z_sol), plans["w"].append(w_sol)
         e, v_prev = shift_past(e, v_prev, err, v_k)
         if k + 1 < H:
-            sol = planner.plan(z[-1], shift_plan(v_sol), e, v_prev, None)
+            sol = planner.plan(z[-1], shift_plan(v_sol), e, v_prev, w_start())
     out = {"z": torch.stack(z, 1), "v": torch.stack(v, 1), "w": torch.stack(w, 1), "pz_x": torch.stack(pz, 1), "x": torch.stack(x, 1),
            "u": torch.cat(u, 1), "cost": torch.stack(cost, 1), "min_clear": torch.stack(clear, 1), "best_J": torch.stack(bestJ, 1),
            "n_bad": torch.stack(nbad, 1)}
