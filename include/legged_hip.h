@@ -783,7 +783,8 @@ int lg_select_kth_grouped(const float *values, int64_t ld, int32_t B, int64_t n,
 #define LG_PLAN_TUBE_L1_ROLLING 3                  /* mean of the last min(window_size, k + 1) l1 values         (TT:515-526) */
 #define LG_PLAN_TUBE_L2_ROLLING 4                  /* the same of the l2 values                                  (TT:529-540) */
 #define LG_PLAN_TUBE_NN_STEP 5                     /* the one-step MLP of a flat scalar lg_tube handle, fed back node by node (section 10.13) */
-typedef struct lg_plan_problem {                   /* one problem for every plan of a call (TT:11-21 problem_dict, TT:460 solve_tube) */
+typedef struct lg_plan_problem {                   /* one problem for every plan of a call (TT:11-21 problem_dict, TT:460 solve_tube);
+                                                    * a goal and obstacles per plan: lg_plan_scenes below (section 10.14) */
     int32_t N /*nodes after the start: 1..LG_PLAN_MAX_N*/, H_rev /*past steps of the tube item*/, n_obs /*0..LG_PLAN_MAX_OBS*/;
     int32_t tube_kind /*LG_PLAN_TUBE_**/, window_size /*rolling kinds: >= 1*/, recursive /*nn_step: 0 / 1, the row layout*/;
     float dt /*ROM step, > 0*/, scaling /*analytic kinds*/, w_max, Qw;
@@ -835,7 +836,8 @@ int lg_plan_track(lg_romsim *sim, const float *z, const float *v, const float *x
 
 /* ------------------------------------------------------------------ sampling planner on a tube: MPPI for P
  * problem instances at once, in place of the reference's NLP solve -- trajopt/tube_trajopt.py:460 solve_tube ("TT") -- and of the
- * re-solve at every control step of trajopt/tube_planning_closed_loop.py:82-168 ("TPCL").  The instances share one lg_plan_problem;
+ * re-solve at every control step of trajopt/tube_planning_closed_loop.py:82-168 ("TPCL").  The instances share one lg_plan_problem
+ * (its goal and obstacles can be each instance's own: lg_plan_mppi_step_scenes, section 10.14);
  * each has its own z0 (P, 2), e (P, H_rev), v_prev (P, H_rev, 2), w0 (P) and mean plan vbar (P, N, 2).  One iteration is two
  * launches: k_plan_sample_score (K candidates per instance drawn around vbar and scored by k_plan_score's own code, no candidate
  * stored) and k_plan_mppi_update (softmin-weighted mean, elite, history). */
@@ -915,6 +917,56 @@ int lg_plan_descend_step(lg_tube *tube, const lg_plan_problem *prob, const lg_gr
 int lg_plan_descend(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *e,
                     const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *v,
                     float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream);
+
+/* ------------------------------------------------------------------ per-plan scenes: a goal and an
+ * obstacle list of its own for every plan of a scoring or gradient launch, or for every instance of an MPPI launch, in place of the
+ * one goal and list of lg_plan_problem.  Everything else of the problem -- N, dt, the tube, the weights, the bounds -- stays shared.
+ * Row r of a tile reads scene base + r from a row of 27 floats in LDS (2 goal, 24 obstacles, the count), staged once per tile; a
+ * tile of candidates reads its instance's one row.  The walk and the reverse walk are the arithmetic of the entries above, operation
+ * for operation, so plan b of a call with scenes equals, bit for bit, a call of B = 1 without scenes on a problem that carries
+ * scene b (an MPPI instance p: a P = 1 call with instance_offset + p). */
+typedef struct lg_plan_scenes {                    /* DEVICE pointers; one scene per plan (scoring, gradient) or per instance (MPPI) */
+    int64_t S;                                     /* must equal the call's B (or P) */
+    const float *goal;                             /* (S, 2), or NULL = prob->goal for every scene */
+    const float *obs;                              /* (S, LG_PLAN_MAX_OBS, 3): cx, cy, r; slots past n_obs[s] are not read */
+    const int32_t *n_obs;                          /* (S); obs and n_obs are both given or both NULL (= the problem's obstacles) */
+} lg_plan_scenes;
+/* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error: S < 1, S != count, one of obs / n_obs without the other,
+ * or all three pointers NULL (the struct then says nothing: pass NULL scenes).  The arrays are not read: n_obs[s] is clamped into
+ * 0..LG_PLAN_MAX_OBS on the device, and a scene without obstacles gives min_clear = +inf and worst_node = -1 as n_obs = 0 does.
+ * Radii, centres and goals are the caller's to validate before upload (tube/plan.py Scenes does). */
+int lg_plan_scenes_check(const lg_plan_scenes *scenes, int64_t count);
+/* The entries above with scenes: each takes its parent's arguments and `scenes` before `stream`.  scenes == NULL is the parent's
+ * behaviour -- the parents are these entries called with NULL, and launch the kernels' instantiations without a scene row.  With
+ * scenes, prob->goal, obs_c, obs_r and n_obs are still checked by lg_plan_check but not read by the kernel for the parts the scenes
+ * supply.  All six tube kinds are taken by the scoring and MPPI entries; the gradient entries refuse nn_step as their parents do.
+ * lg_plan_track reads no obstacle and needs no scenes. */
+int lg_plan_score_scenes(lg_tube *tube, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
+                         const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B,
+                         float *cost, float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w,
+                         const lg_plan_scenes *scenes, void *stream);
+int lg_plan_mppi_step_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int32_t it, int32_t what,
+                             int32_t reset_best, const float *z0, const float *e, const float *v_prev, const float *w0,
+                             const float *offset, int32_t has_level, float level, int64_t P, float *vbar, float *J, float *cost,
+                             float *min_clear, float *pen, float *best_J, float *best_v, float *hist_row, int32_t *n_bad,
+                             const lg_plan_scenes *scenes, void *stream);
+int lg_plan_mppi_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, const float *z0, const float *e,
+                        const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t P,
+                        float *vbar, float *J_scratch, float *best_J, float *best_v, float *hist, int32_t *n_bad,
+                        const lg_plan_scenes *scenes, void *stream);
+int lg_plan_grad_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *v,
+                        const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level,
+                        int64_t B, float *J, float *grad, float *cost, float *min_clear, float *pen, const lg_plan_scenes *scenes,
+                        void *stream);
+int lg_plan_descend_step_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, int32_t it, int32_t what,
+                                int32_t reset, const float *z0, const float *e, const float *v_prev, const float *w0,
+                                const float *offset, int32_t has_level, float level, int64_t B, float *v, float *J, float *grad,
+                                float *cost, float *min_clear, float *pen, float *m, float *s, float *best_J, float *best_v,
+                                float *hist_row, int32_t *n_bad, const lg_plan_scenes *scenes, void *stream);
+int lg_plan_descend_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *e,
+                           const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B,
+                           float *v, float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad,
+                           const lg_plan_scenes *scenes, void *stream);
 
 #ifdef __cplusplus
 }

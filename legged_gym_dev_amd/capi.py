@@ -361,6 +361,11 @@ class lg_grad_cfg(C.Structure):
         ("iters", i32), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("rho_g", f32), ("rho_w", f32), ("rho_z", f32)]
 
 
+class lg_plan_scenes(C.Structure):
+    """One goal and obstacle list per plan or MPPI instance (include/legged_hip.h lg_plan_scenes); device pointers."""
+    _fields_ = [("S", i64), ("goal", C.c_void_p), ("obs", C.c_void_p), ("n_obs", C.c_void_p)]
+
+
 def declare_plan_api(lib):
     vp = C.c_void_p
     if not hasattr(lib, "lg_plan_score"):          # an A/B library (LG_HIP_LIB) built before the plan entries
@@ -382,6 +387,13 @@ def declare_plan_api(lib):
     lib.lg_plan_grad.argtypes = [vp, pp, pg, vp, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp]
     lib.lg_plan_descend_step.argtypes = [vp, pp, pg, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, i64] + [vp] * 13
     lib.lg_plan_descend.argtypes = [vp, pp, pg, vp, vp, vp, vp, vp, i32, f32, i64] + [vp] * 9
+    if not hasattr(lib, "lg_plan_score_scenes"):   # an A/B library built before the per-plan scenes
+        return
+    ps = C.POINTER(lg_plan_scenes)                 # each *_scenes entry: its parent's arguments with the scenes before the stream
+    lib.lg_plan_scenes_check.argtypes = [ps, i64]
+    for name in ("lg_plan_score", "lg_plan_mppi_step", "lg_plan_mppi", "lg_plan_grad", "lg_plan_descend_step", "lg_plan_descend"):
+        a = list(getattr(lib, name).argtypes)
+        getattr(lib, name + "_scenes").argtypes = a[:-1] + [ps, a[-1]]
 
 
 class lg_traj_rec(C.Structure):

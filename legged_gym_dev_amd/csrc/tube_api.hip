@@ -44,22 +44,27 @@ void tubek_rollout_window(const TubeDev *D, const float *x, int64_t n_seq, int T
                           const uint8_t *reseed, float *o, hipStream_t s);
 int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
                          const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
-                         float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, hipStream_t s);
+                         float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w,
+                         const lg_plan_scenes *sc, hipStream_t s);
 void tubek_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *vbar, int64_t P_, float *out,
                                 hipStream_t s);
 int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
                                 const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
-                                const float *vbar, float *J, float *cost, float *min_clear, float *pen, hipStream_t s);
+                                const float *vbar, float *J, float *cost, float *min_clear, float *pen, const lg_plan_scenes *sc,
+                                hipStream_t s);
 void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,
                             const float *J, float *best_J, float *best_v, float *hist, int32_t *n_bad, hipStream_t s);
-int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, hipStream_t s);
+int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, const lg_plan_scenes *sc,
+                        hipStream_t s);
 int64_t tubek_plan_step_bytes(const TubeDev *D, const lg_plan_problem *prob);
 int64_t tubek_plan_score_step(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
                               const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
-                              float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, hipStream_t s);
+                              float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w,
+                              const lg_plan_scenes *sc, hipStream_t s);
 int64_t tubek_plan_sample_score_step(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
                                      const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
-                                     const float *vbar, float *J, float *cost, float *min_clear, float *pen, hipStream_t s);
+                                     const float *vbar, float *J, float *cost, float *min_clear, float *pen, const lg_plan_scenes *sc,
+                                     hipStream_t s);
 }
 
 struct TubeCaps {                       // rows that a model's data-sized buffers hold
@@ -486,20 +491,42 @@ int lg_plan_check(const lg_plan_problem *prob, const lg_tube *tube, int32_t has_
     return 0;
 }
 
+// Per-plan scenes.  Every planning entry is its *_scenes entry with NULL scenes.
+int lg_plan_scenes_check(const lg_plan_scenes *sc, int64_t count) {
+    std::string e;
+    if (sc->S < 1) e = "S = " + std::to_string(sc->S) + " must be at least 1";
+    else if (sc->S != count)
+        e = "S = " + std::to_string(sc->S) + " differs from the call's count of plans or instances = " + std::to_string(count);
+    else if (sc->obs && !sc->n_obs) e = "obs is given without n_obs";
+    else if (!sc->obs && sc->n_obs) e = "n_obs is given without obs";
+    else if (!sc->goal && !sc->obs) e = "goal, obs and n_obs are all NULL: the scenes say nothing (pass NULL scenes)";
+    if (!e.empty()) { lg_set_error("lg_plan_scenes: " + e); return -1; }
+    return 0;
+}
+
 int lg_plan_score(lg_tube *tube, const lg_plan_problem *prob, const float *z0, const float *v, const float *e, const float *v_prev,
                   const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *cost, float *min_clear,
                   int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, void *stream) {
+    return lg_plan_score_scenes(tube, prob, z0, v, e, v_prev, w0, offset, has_level, level, B, cost, min_clear, worst_node, n_viol, fw, z,
+                                w, nullptr, stream);
+}
+
+int lg_plan_score_scenes(lg_tube *tube, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
+                         const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B,
+                         float *cost, float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w,
+                         const lg_plan_scenes *scenes, void *stream) {
     if (lg_plan_check(prob, tube, has_level)) return -1;
     if (B < 1 || B > INT32_MAX) { lg_set_error("lg_plan_score: B must be 1..2^31-1"); return -1; }
+    if (scenes && lg_plan_scenes_check(scenes, B)) return -1;
     if (!z0 || !v || !cost || !min_clear || !worst_node || !n_viol) {
         lg_set_error("lg_plan_score: missing array (z0, v, cost, min_clear, worst_node and n_viol are required)"); return -1;
     }
     const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
     const int64_t rc = prob->tube_kind == LG_PLAN_TUBE_NN_STEP
         ? tubek_plan_score_step(&tube->dev, prob, z0, v, e, v_prev, w0, offset, has_level ? level : 0.f, B, cost, min_clear, worst_node,
-                                n_viol, fw, z, w, (hipStream_t)stream)
+                                n_viol, fw, z, w, scenes, (hipStream_t)stream)
         : tubek_plan_score(nn ? &tube->dev : nullptr, prob, z0, v, e, v_prev, w0, offset, has_level ? level : 0.f, B, cost,
-                           min_clear, worst_node, n_viol, fw, z, w, (hipStream_t)stream);
+                           min_clear, worst_node, n_viol, fw, z, w, scenes, (hipStream_t)stream);
     if (rc < 0) { lg_set_error("lg_plan_score: hipFuncSetAttribute failed"); return -2; }
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_score: launch failed"), -3);
 }
@@ -542,7 +569,17 @@ int lg_plan_mppi_step(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_
                       const float *z0, const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level,
                       float level, int64_t P, float *vbar, float *J, float *cost, float *min_clear, float *pen, float *best_J,
                       float *best_v, float *hist_row, int32_t *n_bad, void *stream) {
+    return lg_plan_mppi_step_scenes(tube, prob, cfg, it, what, reset_best, z0, e, v_prev, w0, offset, has_level, level, P, vbar, J, cost,
+                                    min_clear, pen, best_J, best_v, hist_row, n_bad, nullptr, stream);
+}
+
+int lg_plan_mppi_step_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int32_t it, int32_t what,
+                             int32_t reset_best, const float *z0, const float *e, const float *v_prev, const float *w0,
+                             const float *offset, int32_t has_level, float level, int64_t P, float *vbar, float *J, float *cost,
+                             float *min_clear, float *pen, float *best_J, float *best_v, float *hist_row, int32_t *n_bad,
+                             const lg_plan_scenes *scenes, void *stream) {
     if (lg_mppi_check(cfg, prob, tube, has_level, P)) return -1;
+    if (scenes && lg_plan_scenes_check(scenes, P)) return -1;
     if (it < 0) { lg_set_error("lg_plan_mppi_step: it must not be negative"); return -1; }
     if (!(what & 3)) { lg_set_error("lg_plan_mppi_step: what must name the score (1), the update (2) or both (3)"); return -1; }
     if (!vbar || !J || ((what & 1) && !z0) || ((what & 2) && (!best_J || !best_v || !n_bad))) {
@@ -552,9 +589,9 @@ int lg_plan_mppi_step(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_
     if (what & 1) {
         const int64_t rc = prob->tube_kind == LG_PLAN_TUBE_NN_STEP
             ? tubek_plan_sample_score_step(&tube->dev, prob, cfg, it, z0, e, v_prev, w0, offset, has_level ? level : 0.f, P, vbar, J, cost,
-                                           min_clear, pen, (hipStream_t)stream)
+                                           min_clear, pen, scenes, (hipStream_t)stream)
             : tubek_plan_sample_score(nn ? &tube->dev : nullptr, prob, cfg, it, z0, e, v_prev, w0, offset, has_level ? level : 0.f,
-                                      P, vbar, J, cost, min_clear, pen, (hipStream_t)stream);
+                                      P, vbar, J, cost, min_clear, pen, scenes, (hipStream_t)stream);
         if (rc < 0) { lg_set_error("lg_plan_mppi_step: hipFuncSetAttribute failed"); return -2; }
     }
     if (what & 2) tubek_plan_mppi_update(prob, cfg, it, reset_best, P, vbar, J, best_J, best_v, hist_row, n_bad, (hipStream_t)stream);
@@ -564,10 +601,20 @@ int lg_plan_mppi_step(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_
 int lg_plan_mppi(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, const float *z0, const float *e,
                  const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t P, float *vbar,
                  float *J_scratch, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream) {
+    return lg_plan_mppi_scenes(tube, prob, cfg, z0, e, v_prev, w0, offset, has_level, level, P, vbar, J_scratch, best_J, best_v, hist,
+                               n_bad, nullptr, stream);
+}
+
+int lg_plan_mppi_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, const float *z0, const float *e,
+                        const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t P,
+                        float *vbar, float *J_scratch, float *best_J, float *best_v, float *hist, int32_t *n_bad,
+                        const lg_plan_scenes *scenes, void *stream) {
     if (lg_mppi_check(cfg, prob, tube, has_level, P)) return -1;
+    if (scenes && lg_plan_scenes_check(scenes, P)) return -1;
     for (int32_t it = 0; it < cfg->iters; ++it) {
-        const int rc = lg_plan_mppi_step(tube, prob, cfg, it, 3, it == 0, z0, e, v_prev, w0, offset, has_level, level, P, vbar, J_scratch,
-                                         nullptr, nullptr, nullptr, best_J, best_v, hist ? hist + (int64_t)it * P * 2 : nullptr, n_bad, stream);
+        const int rc = lg_plan_mppi_step_scenes(tube, prob, cfg, it, 3, it == 0, z0, e, v_prev, w0, offset, has_level, level, P, vbar,
+                                                J_scratch, nullptr, nullptr, nullptr, best_J, best_v,
+                                                hist ? hist + (int64_t)it * P * 2 : nullptr, n_bad, scenes, stream);
         if (rc) return rc;
     }
     return 0;
@@ -612,14 +659,23 @@ static void grad_args(PlanGradArgs *A, const lg_grad_cfg *cfg, const float *z0, 
 int lg_plan_grad(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *v, const float *e,
                  const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *J,
                  float *grad, float *cost, float *min_clear, float *pen, void *stream) {
+    return lg_plan_grad_scenes(tube, prob, cfg, z0, v, e, v_prev, w0, offset, has_level, level, B, J, grad, cost, min_clear, pen, nullptr,
+                               stream);
+}
+
+int lg_plan_grad_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *v,
+                        const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level,
+                        int64_t B, float *J, float *grad, float *cost, float *min_clear, float *pen, const lg_plan_scenes *scenes,
+                        void *stream) {
     if (lg_plan_grad_check(cfg, prob, tube, has_level, B)) return -1;
+    if (scenes && lg_plan_scenes_check(scenes, B)) return -1;
     if (!z0 || !v || !J || !grad) { lg_set_error("lg_plan_grad: missing array (z0, v, J and grad are required)"); return -1; }
     PlanGradArgs A;
     grad_args(&A, cfg, z0, e, v_prev, w0, offset, has_level, level);
     A.v = const_cast<float *>(v);       // read only: no step in this launch
     A.J = J; A.grad = grad; A.cost = cost; A.min_clear = min_clear; A.pen = pen;
     const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
-    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, (hipStream_t)stream) < 0) {
+    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, scenes, (hipStream_t)stream) < 0) {
         lg_set_error("lg_plan_grad: hipFuncSetAttribute failed"); return -2;
     }
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_grad: launch failed"), -3);
@@ -629,7 +685,17 @@ int lg_plan_descend_step(lg_tube *tube, const lg_plan_problem *prob, const lg_gr
                          const float *z0, const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level,
                          float level, int64_t B, float *v, float *J, float *grad, float *cost, float *min_clear, float *pen, float *m,
                          float *s, float *best_J, float *best_v, float *hist_row, int32_t *n_bad, void *stream) {
+    return lg_plan_descend_step_scenes(tube, prob, cfg, it, what, reset, z0, e, v_prev, w0, offset, has_level, level, B, v, J, grad, cost,
+                                       min_clear, pen, m, s, best_J, best_v, hist_row, n_bad, nullptr, stream);
+}
+
+int lg_plan_descend_step_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, int32_t it, int32_t what,
+                                int32_t reset, const float *z0, const float *e, const float *v_prev, const float *w0,
+                                const float *offset, int32_t has_level, float level, int64_t B, float *v, float *J, float *grad,
+                                float *cost, float *min_clear, float *pen, float *m, float *s, float *best_J, float *best_v,
+                                float *hist_row, int32_t *n_bad, const lg_plan_scenes *scenes, void *stream) {
     if (lg_plan_grad_check(cfg, prob, tube, has_level, B)) return -1;
+    if (scenes && lg_plan_scenes_check(scenes, B)) return -1;
     if (it < 0) { lg_set_error("lg_plan_descend_step: it must not be negative"); return -1; }
     if (what != 1 && what != 3) {
         lg_set_error("lg_plan_descend_step: what must be the evaluation (1) or the evaluation and the step (3): the step is fused into "
@@ -647,7 +713,7 @@ int lg_plan_descend_step(lg_tube *tube, const lg_plan_problem *prob, const lg_gr
     A.bc1 = (float)(1.0 - std::pow((double)cfg->beta1, (double)it + 1.0));     // step index t = it + 1
     A.bc2 = (float)(1.0 - std::pow((double)cfg->beta2, (double)it + 1.0));
     const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
-    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, (hipStream_t)stream) < 0) {
+    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, scenes, (hipStream_t)stream) < 0) {
         lg_set_error("lg_plan_descend_step: hipFuncSetAttribute failed"); return -2;
     }
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_descend_step: launch failed"), -3);
@@ -656,11 +722,20 @@ int lg_plan_descend_step(lg_tube *tube, const lg_plan_problem *prob, const lg_gr
 int lg_plan_descend(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *e,
                     const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *v,
                     float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream) {
+    return lg_plan_descend_scenes(tube, prob, cfg, z0, e, v_prev, w0, offset, has_level, level, B, v, J_scratch, m, s, best_J, best_v, hist,
+                                  n_bad, nullptr, stream);
+}
+
+int lg_plan_descend_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *e,
+                           const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B,
+                           float *v, float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad,
+                           const lg_plan_scenes *scenes, void *stream) {
     if (lg_plan_grad_check(cfg, prob, tube, has_level, B)) return -1;
+    if (scenes && lg_plan_scenes_check(scenes, B)) return -1;
     for (int32_t it = 0; it <= cfg->iters; ++it) {  // iters stepping launches, then the evaluation of the last iterate
-        const int rc = lg_plan_descend_step(tube, prob, cfg, it, it < cfg->iters ? 3 : 1, it == 0, z0, e, v_prev, w0, offset, has_level,
-                                            level, B, v, J_scratch, nullptr, nullptr, nullptr, nullptr, m, s, best_J, best_v,
-                                            hist ? hist + (int64_t)it * B * 2 : nullptr, n_bad, stream);
+        const int rc = lg_plan_descend_step_scenes(tube, prob, cfg, it, it < cfg->iters ? 3 : 1, it == 0, z0, e, v_prev, w0, offset,
+                                                   has_level, level, B, v, J_scratch, nullptr, nullptr, nullptr, nullptr, m, s, best_J,
+                                                   best_v, hist ? hist + (int64_t)it * B * 2 : nullptr, n_bad, scenes, stream);
         if (rc) return rc;
     }
     return 0;

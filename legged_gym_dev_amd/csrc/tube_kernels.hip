@@ -372,6 +372,8 @@ struct PlanDev {                        // passed by value
     int32_t *worst_node, *n_viol;
     float level;
     int Hr, I;                          // columns of the tile's item: Hr past errors, 2 (Hr + N) inputs, (level); analytic kinds: Hr = 0
+    const float *sc_goal, *sc_obs;      // lg_plan_scenes (section 10.14): read by the <SC = true> kernels alone
+    const int32_t *sc_n;
 };
 
 #define PLAN_ZS(N) ((((N) + 1) * 3) | 1)    // floats of a plan's (z, w) nodes in LDS: odd, so that the lanes' rows fall on different banks
@@ -380,6 +382,51 @@ struct PlanDev {                        // passed by value
 __device__ __forceinline__ float plan_quad(const float *M, float d0, float d1) {
 #pragma clang fp contract(off)
     return (d0 * M[0] + d1 * M[2]) * d0 + (d0 * M[1] + d1 * M[3]) * d1;
+}
+
+// The scene a walk runs against: the goal, the obstacle list and its length, read through one accessor.
+// PlanSceneProb: the call's one scene in the by-value problem -- uniform reads, the code of the entries without scenes.
+// PlanSceneRow: a row of PLAN_SCN floats in LDS, [goal x, y, (cx, cy, r) x LG_PLAN_MAX_OBS, count]; the stride is odd, so the 32
+// walking lanes read different banks.  plan_scene_stage fills the rows of a tile before its first barrier.
+#define PLAN_SCN (3 + 3 * LG_PLAN_MAX_OBS)
+static_assert(PLAN_SCN == 27 && (PLAN_SCN & 1), "a scene row: 2 + 24 + 1 floats, an odd stride");
+struct PlanSceneProb {
+    const lg_plan_problem &p;
+    __device__ __forceinline__ int n() const { return p.n_obs; }
+    __device__ __forceinline__ float cx(int i) const { return p.obs_c[i][0]; }
+    __device__ __forceinline__ float cy(int i) const { return p.obs_c[i][1]; }
+    __device__ __forceinline__ float r(int i) const { return p.obs_r[i]; }
+    __device__ __forceinline__ float gx() const { return p.goal[0]; }
+    __device__ __forceinline__ float gy() const { return p.goal[1]; }
+};
+struct PlanSceneRow {
+    const float *s;
+    __device__ __forceinline__ int n() const { return (int)s[PLAN_SCN - 1]; }
+    __device__ __forceinline__ float cx(int i) const { return s[2 + 3 * i]; }
+    __device__ __forceinline__ float cy(int i) const { return s[3 + 3 * i]; }
+    __device__ __forceinline__ float r(int i) const { return s[4 + 3 * i]; }
+    __device__ __forceinline__ float gx() const { return s[0]; }
+    __device__ __forceinline__ float gy() const { return s[1]; }
+};
+// Rows 0 .. rows - 1 of SCN take scenes s0, s0 + 1, ..; rows at and past nr are zeros with a zero count.  A part the scenes leave
+// out (goal, or obs and n_obs) comes from the problem; n_obs[s] is clamped into 0 .. LG_PLAN_MAX_OBS and slots past it are not read.
+__device__ __forceinline__ void plan_scene_stage(const PlanDev &P, float *SCN, int64_t s0, int rows, int nr, int tid) {
+    for (int e = tid; e < rows * PLAN_SCN; e += NT) {
+        const int r = e / PLAN_SCN, c = e - r * PLAN_SCN;
+        float x = 0.f;
+        if (r < nr) {
+            const int64_t s = s0 + r;
+            if (c < 2) x = P.sc_goal ? P.sc_goal[s * 2 + c] : P.p.goal[c];
+            else {
+                int n = P.sc_n ? P.sc_n[s] : P.p.n_obs;
+                n = n < 0 ? 0 : (n > LG_PLAN_MAX_OBS ? LG_PLAN_MAX_OBS : n);
+                const int q = c - 2, i = q / 3, k = q - 3 * i;
+                if (c == PLAN_SCN - 1) x = (float)n;
+                else if (i < n) x = P.sc_obs ? P.sc_obs[s * (3 * LG_PLAN_MAX_OBS) + q] : (k < 2 ? P.p.obs_c[i][k] : P.p.obs_r[i]);
+            }
+        }
+        SCN[e] = x;
+    }
 }
 
 // One lane's walk over a plan's nodes, shared by k_plan_score and k_plan_sample_score: the analytic tube (where the kind is one), the
@@ -391,8 +438,8 @@ struct PlanWalk {
     float cost, minc, pen_g, pen_w, pen_z;
     int worst, nv_g, nv_v, nv_z, nv_w;
 };
-template <bool PEN>
-__device__ __forceinline__ PlanWalk plan_walk(const lg_plan_problem &p, bool nn, const float *vr, float *fw, float *zw, float zx, float zy,
+template <bool PEN, class SN>
+__device__ __forceinline__ PlanWalk plan_walk(const lg_plan_problem &p, const SN &sn, bool nn, const float *vr, float *fw, float *zw, float zx, float zy,
                                               float wk, const float *offset) {
 #pragma clang fp contract(off)
     const int N = p.N;
@@ -414,11 +461,13 @@ __device__ __forceinline__ PlanWalk plan_walk(const lg_plan_problem &p, bool nn,
     PlanWalk W;
     W.cost = 0.f; W.minc = INFINITY; W.pen_g = 0.f; W.pen_w = 0.f; W.pen_z = 0.f;
     W.worst = -1; W.nv_g = 0; W.nv_v = 0; W.nv_z = 0; W.nv_w = 0;
+    const int n_obs = sn.n();
+    const float gx = sn.gx(), gy = sn.gy();
     for (int k = 0; k <= N; ++k) {
         zw[3 * k] = zx; zw[3 * k + 1] = zy; zw[3 * k + 2] = wk;
         bool hit = false;
-        for (int i = 0; i < p.n_obs; ++i) {
-            const float dx = zx - p.obs_c[i][0], dy = zy - p.obs_c[i][1], rr = p.obs_r[i] + wk;
+        for (int i = 0; i < n_obs; ++i) {
+            const float dx = zx - sn.cx(i), dy = zy - sn.cy(i), rr = sn.r(i) + wk;
             const float g = (dx * dx + dy * dy) - rr * rr;
             if (g < W.minc) { W.minc = g; W.worst = k; }
             hit = hit || g < 0.f;
@@ -432,7 +481,7 @@ __device__ __forceinline__ PlanWalk plan_walk(const lg_plan_problem &p, bool nn,
             W.pen_z = W.pen_z + (fmaxf(0.f, zx - p.rom_z_max[0]) + fmaxf(0.f, p.rom_z_min[0] - zx));
             W.pen_z = W.pen_z + (fmaxf(0.f, zy - p.rom_z_max[1]) + fmaxf(0.f, p.rom_z_min[1] - zy));
         }
-        W.cost = W.cost + plan_quad(k < N ? p.Q : p.Qf, zx - p.goal[0], zy - p.goal[1]);
+        W.cost = W.cost + plan_quad(k < N ? p.Q : p.Qf, zx - gx, zy - gy);
         const float vx = k < N ? vr[2 * k] : 0.f, vy = k < N ? vr[2 * k + 1] : 0.f;
         if (k < N) {
             W.nv_v += vx < p.rom_v_min[0] || vx > p.rom_v_max[0] || vy < p.rom_v_min[1] || vy > p.rom_v_max[1];
@@ -467,7 +516,9 @@ __device__ __forceinline__ void plan_gather(const PlanDev &P, float *X, int64_t 
     }
 }
 
-// Dynamic LDS: X (R, I) the items -- for an analytic kind the plan's inputs alone --, H0, H1 (R, U) (NN kind), FW (R, N), ZW (R, PLAN_ZS).
+// Dynamic LDS: X (R, I) the items -- for an analytic kind the plan's inputs alone --, H0, H1 (R, U) (NN kind), FW (R, N), ZW (R, PLAN_ZS),
+// and with SC the scenes SCN (R, PLAN_SCN): row r walks against scene base + r.
+template <bool SC>
 __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t count) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
@@ -475,8 +526,9 @@ __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t
     const int U = nn ? D.units : 0, L = D.layers, ZS = PLAN_ZS(N);
     const int64_t base = (int64_t)blockIdx.x * R;
     const int nr = (int)(count - base < R ? count - base : R);
-    float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N;
+    float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N, *SCN = ZW + R * ZS;
     plan_gather(P, X, base, nr, tid);
+    if (SC) plan_scene_stage(P, SCN, base, R, nr, tid);
     __syncthreads();
     if (nn) {
         const float *in = X;
@@ -492,8 +544,12 @@ __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t
     }
     if (tid < nr) {
         const int64_t b = base + tid;
-        const PlanWalk W = plan_walk<false>(P.p, nn, X + tid * I + 3 * Hr, FW + tid * N, ZW + tid * ZS, P.z0[b * 2], P.z0[b * 2 + 1],
-                                            P.w0 ? P.w0[b] : 0.f, P.offset);
+        const float *vr = X + tid * I + 3 * Hr;
+        const float w0 = P.w0 ? P.w0[b] : 0.f;
+        const PlanWalk W = SC ? plan_walk<false>(P.p, PlanSceneRow{SCN + tid * PLAN_SCN}, nn, vr, FW + tid * N, ZW + tid * ZS, P.z0[b * 2],
+                                                 P.z0[b * 2 + 1], w0, P.offset)
+                              : plan_walk<false>(P.p, PlanSceneProb{P.p}, nn, vr, FW + tid * N, ZW + tid * ZS, P.z0[b * 2], P.z0[b * 2 + 1],
+                                                 w0, P.offset);
         P.cost[b] = W.cost; P.min_clear[b] = W.minc; P.worst_node[b] = W.worst;
         P.n_viol[b * 4] = W.nv_g; P.n_viol[b * 4 + 1] = W.nv_v; P.n_viol[b * 4 + 2] = W.nv_z; P.n_viol[b * 4 + 3] = W.nv_w;
     }
@@ -562,6 +618,8 @@ __global__ void __launch_bounds__(NT) k_plan_mppi_candidates(MppiDev M, int64_t 
 // of gathered: tile t holds candidates 32 (t mod K/32) .. + 31 of instance t / (K/32) (K is a multiple of R), so one z0, e, v_prev,
 // w0 serves the tile.  The layers and the lane's walk are k_plan_score's.  J = ((cost + rho_g pen_g) + rho_w pen_w) + rho_z pen_z.
 // P.cost, P.min_clear and M.pen (P, K, 3) are optional here.  No atomics; a candidate depends on (seed, instance id, it, j) alone.
+// With SC the tile's instance has a scene of its own: one row SCN (PLAN_SCN) behind ZW, which every walking lane reads.
+template <bool SC>
 __global__ void __launch_bounds__(NT) k_plan_sample_score(TubeDev D, PlanDev P, MppiDev M) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
@@ -569,7 +627,8 @@ __global__ void __launch_bounds__(NT) k_plan_sample_score(TubeDev D, PlanDev P, 
     const int U = nn ? D.units : 0, L = D.layers, ZS = PLAN_ZS(N);
     const int64_t base = (int64_t)blockIdx.x * R;
     const int pi = (int)(base / M.K), j0 = (int)(base - (int64_t)pi * M.K);
-    float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N;
+    float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N, *SCN = ZW + R * ZS;
+    if (SC) plan_scene_stage(P, SCN, pi, 1, 1, tid);
     for (int e = tid; e < R * I; e += NT) {         // the columns beside the plan: the instance's e, v_prev and the level
         const int r = e / I, c = e - r * I;
         if (c < Hr) X[e] = P.e ? P.e[(int64_t)pi * Hr + c] : 0.f;
@@ -597,8 +656,12 @@ __global__ void __launch_bounds__(NT) k_plan_sample_score(TubeDev D, PlanDev P, 
     if (tid < R) {
 #pragma clang fp contract(off)
         const int64_t b = base + tid;
-        const PlanWalk W = plan_walk<true>(P.p, nn, X + tid * I + 3 * Hr, FW + tid * N, ZW + tid * ZS, P.z0[pi * 2], P.z0[pi * 2 + 1],
-                                           P.w0 ? P.w0[pi] : 0.f, P.offset);
+        const float *vr = X + tid * I + 3 * Hr;
+        const float w0 = P.w0 ? P.w0[pi] : 0.f;
+        const PlanWalk W = SC ? plan_walk<true>(P.p, PlanSceneRow{SCN}, nn, vr, FW + tid * N, ZW + tid * ZS, P.z0[pi * 2], P.z0[pi * 2 + 1],
+                                                w0, P.offset)
+                              : plan_walk<true>(P.p, PlanSceneProb{P.p}, nn, vr, FW + tid * N, ZW + tid * ZS, P.z0[pi * 2],
+                                                P.z0[pi * 2 + 1], w0, P.offset);
         M.J[b] = ((W.cost + M.rho_g * W.pen_g) + M.rho_w * W.pen_w) + M.rho_z * W.pen_z;
         if (P.cost) P.cost[b] = W.cost;
         if (P.min_clear) P.min_clear[b] = W.minc;
@@ -720,11 +783,11 @@ __global__ void __launch_bounds__(NT) k_plan_mppi_update(MppiDev M) {
 #define PLAN_STEP_VS(Hr, N) ((2 * ((Hr) + (N))) | 1)
 #define PLAN_STEP_WS(Hr, N) (((Hr) + (N) + 1) | 1)
 #define PLAN_STEP_PRE 4                 // row elements whose source a thread keeps in registers: R * 32 columns / NT
-constexpr size_t plan_step_floats(int I, int U, int Hr, int N) {   // the tile without the weights
-    return (size_t)R * (PLAN_STEP_VS(Hr, N) + PLAN_STEP_WS(Hr, N) + I + 2 * U + PLAN_ZS(N));
+constexpr size_t plan_step_floats(int I, int U, int Hr, int N, bool scenes) {   // the tile without the weights
+    return (size_t)R * (PLAN_STEP_VS(Hr, N) + PLAN_STEP_WS(Hr, N) + I + 2 * U + PLAN_ZS(N) + (scenes ? PLAN_SCN : 0));
 }
 struct PlanStepTile {
-    float *W, *V, *WL, *X, *H0, *H1, *ZW;
+    float *W, *V, *WL, *X, *H0, *H1, *ZW, *SCN;         // SCN (R, PLAN_SCN): the tile's scenes, kernels with SC alone
     int VS, WS;
 };
 __device__ __forceinline__ PlanStepTile plan_step_tile(float *lds, const TubeDev &D, const PlanDev &P, bool wlds) {
@@ -733,6 +796,7 @@ __device__ __forceinline__ PlanStepTile plan_step_tile(float *lds, const TubeDev
     S.W = lds;
     S.V = lds + (wlds ? D.num_params : 0);
     S.WL = S.V + R * S.VS; S.X = S.WL + R * S.WS; S.H0 = S.X + R * P.I; S.H1 = S.H0 + R * D.units; S.ZW = S.H1 + R * D.units;
+    S.SCN = S.ZW + R * PLAN_ZS(P.p.N);
     return S;
 }
 // Element (r, c) of the row tile: where node 0 reads it, as a float offset from the V lines (the w lines follow them) with bit 30
@@ -790,8 +854,9 @@ __device__ __forceinline__ void plan_step_roll(const TubeDev &D, const PlanDev &
     }
 }
 
-// k_plan_score for the one-step kind.  Dynamic LDS: (W the parameters), V (R, VS), WL (R, WS), X (R, I), H0, H1 (R, U), ZW (R, PLAN_ZS).
-template <bool WLDS>
+// k_plan_score for the one-step kind.  Dynamic LDS: (W the parameters), V (R, VS), WL (R, WS), X (R, I), H0, H1 (R, U), ZW (R, PLAN_ZS),
+// (SCN (R, PLAN_SCN) the scenes).
+template <bool WLDS, bool SC>
 __global__ void __launch_bounds__(NT) k_plan_score_step(TubeDev D, PlanDev P, int64_t count) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, Hr = P.Hr, ZS = PLAN_ZS(N), VC = 2 * (Hr + N);
@@ -818,11 +883,16 @@ __global__ void __launch_bounds__(NT) k_plan_score_step(TubeDev D, PlanDev P, in
         }
         S.WL[r * S.WS + c] = x;
     }
+    if (SC) plan_scene_stage(P, S.SCN, base, R, nr, tid);
     plan_step_roll<WLDS>(D, P, S, tid);
     if (tid < nr) {
         const int64_t b = base + tid;
-        const PlanWalk W = plan_walk<false>(P.p, true, S.V + tid * S.VS + 2 * Hr, S.WL + tid * S.WS + Hr + 1, S.ZW + tid * ZS, P.z0[b * 2],
-                                            P.z0[b * 2 + 1], S.WL[tid * S.WS + Hr], P.offset);
+        const float *vr = S.V + tid * S.VS + 2 * Hr;
+        float *fw = S.WL + tid * S.WS + Hr + 1;
+        const PlanWalk W = SC ? plan_walk<false>(P.p, PlanSceneRow{S.SCN + tid * PLAN_SCN}, true, vr, fw, S.ZW + tid * ZS, P.z0[b * 2],
+                                                 P.z0[b * 2 + 1], S.WL[tid * S.WS + Hr], P.offset)
+                              : plan_walk<false>(P.p, PlanSceneProb{P.p}, true, vr, fw, S.ZW + tid * ZS, P.z0[b * 2], P.z0[b * 2 + 1],
+                                                 S.WL[tid * S.WS + Hr], P.offset);
         P.cost[b] = W.cost; P.min_clear[b] = W.minc; P.worst_node[b] = W.worst;
         P.n_viol[b * 4] = W.nv_g; P.n_viol[b * 4 + 1] = W.nv_v; P.n_viol[b * 4 + 2] = W.nv_z; P.n_viol[b * 4 + 3] = W.nv_w;
     }
@@ -844,7 +914,7 @@ __global__ void __launch_bounds__(NT) k_plan_score_step(TubeDev D, PlanDev P, in
 
 // k_plan_sample_score for the one-step kind: the same tile with the plan columns drawn in place; tile t holds candidates of one
 // instance, whose v_prev, e and w0 every row shares.  J is formed by k_plan_sample_score's expression.
-template <bool WLDS>
+template <bool WLDS, bool SC>
 __global__ void __launch_bounds__(NT) k_plan_sample_score_step(TubeDev D, PlanDev P, MppiDev M) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, Hr = P.Hr, ZS = PLAN_ZS(N);
@@ -865,12 +935,18 @@ __global__ void __launch_bounds__(NT) k_plan_sample_score_step(TubeDev D, PlanDe
         const int r = e / (Hr + 1), c = e - r * (Hr + 1);
         S.WL[r * S.WS + c] = c < Hr ? (P.e ? P.e[(int64_t)pi * Hr + c] : 0.f) : (P.w0 ? P.w0[pi] : 0.f);
     }
+    if (SC) plan_scene_stage(P, S.SCN, pi, 1, 1, tid);
     plan_step_roll<WLDS>(D, P, S, tid);
     if (tid < R) {
 #pragma clang fp contract(off)
         const int64_t b = base + tid;
-        const PlanWalk W = plan_walk<true>(P.p, true, S.V + tid * S.VS + 2 * Hr, S.WL + tid * S.WS + Hr + 1, S.ZW + tid * ZS, P.z0[pi * 2],
-                                           P.z0[pi * 2 + 1], P.w0 ? P.w0[pi] : 0.f, P.offset);
+        const float *vr = S.V + tid * S.VS + 2 * Hr;
+        float *fw = S.WL + tid * S.WS + Hr + 1;
+        const float w0 = P.w0 ? P.w0[pi] : 0.f;
+        const PlanWalk W = SC ? plan_walk<true>(P.p, PlanSceneRow{S.SCN}, true, vr, fw, S.ZW + tid * ZS, P.z0[pi * 2], P.z0[pi * 2 + 1], w0,
+                                                P.offset)
+                              : plan_walk<true>(P.p, PlanSceneProb{P.p}, true, vr, fw, S.ZW + tid * ZS, P.z0[pi * 2], P.z0[pi * 2 + 1], w0,
+                                                P.offset);
         M.J[b] = ((W.cost + M.rho_g * W.pen_g) + M.rho_w * W.pen_w) + M.rho_z * W.pen_z;
         if (P.cost) P.cost[b] = W.cost;
         if (P.min_clear) P.min_clear[b] = W.minc;
@@ -911,21 +987,24 @@ __device__ __forceinline__ void tube_layer_back(int tid, int K, int No, const fl
 // Analytic kinds then add the tube's part in the same lane, steps i ascending: db = dJ/dfw[i], or for a rolling kind the window's
 // transposed mean sum_{k = i..min(i + window - 1, N - 1)} dJ/dfw[k] / (k - k0(k) + 1), k ascending from 0; times scaling sign(v)
 // (l1, 0 at 0) or (2 scaling) v (l2).
-__device__ __forceinline__ void plan_walk_back(const lg_plan_problem &p, bool nn, const float *vr, float *dfw, float *zw, float rho_g,
+template <class SN>
+__device__ __forceinline__ void plan_walk_back(const lg_plan_problem &p, const SN &sn, bool nn, const float *vr, float *dfw, float *zw, float rho_g,
                                                float rho_w, float rho_z) {
 #pragma clang fp contract(off)
     const int N = p.N;
     const float *Ri = plan_input_cost(p);
+    const int n_obs = sn.n();
+    const float gx = sn.gx(), gy = sn.gy();
     float ax = 0.f, ay = 0.f;
     for (int k = N; k >= 1; --k) {
         const float zx = zw[3 * k], zy = zw[3 * k + 1], wk = zw[3 * k + 2];
         const float *M = k < N ? p.Q : p.Qf;
-        const float d0 = zx - p.goal[0], d1 = zy - p.goal[1];
+        const float d0 = zx - gx, d1 = zy - gy;
         float lx = (M[0] + M[0]) * d0 + (M[1] + M[2]) * d1;
         float ly = (M[1] + M[2]) * d0 + (M[3] + M[3]) * d1;
         float lw = (2.f * p.Qw) * wk;
-        for (int i = 0; i < p.n_obs; ++i) {
-            const float dx = zx - p.obs_c[i][0], dy = zy - p.obs_c[i][1], rr = p.obs_r[i] + wk;
+        for (int i = 0; i < n_obs; ++i) {
+            const float dx = zx - sn.cx(i), dy = zy - sn.cy(i), rr = sn.r(i) + wk;
             const float g = (dx * dx + dy * dy) - rr * rr;
             if (g < 0.f) {
                 lx = lx - rho_g * (2.f * dx);
@@ -987,6 +1066,7 @@ struct GradDev {                        // passed by value
     float v_min[2], v_max[2];
 };
 
+template <bool SC>                      // SC: the scenes SCN (R, PLAN_SCN) follow ZW; both walks of row r read scene base + r
 __global__ void __launch_bounds__(NT) k_plan_grad(TubeDev D, PlanDev P, GradDev G, int64_t count) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
@@ -994,8 +1074,9 @@ __global__ void __launch_bounds__(NT) k_plan_grad(TubeDev D, PlanDev P, GradDev 
     const int U = nn ? D.units : 0, L = nn ? D.layers : 0, ZS = PLAN_ZS(N);
     const int64_t base = (int64_t)blockIdx.x * R;
     const int nr = (int)(count - base < R ? count - base : R);
-    float *X = lds, *H = X + R * I, *FW = H + R * U * L, *ZW = FW + R * N;
+    float *X = lds, *H = X + R * I, *FW = H + R * U * L, *ZW = FW + R * N, *SCN = ZW + R * ZS;
     plan_gather(P, X, base, nr, tid);
+    if (SC) plan_scene_stage(P, SCN, base, R, nr, tid);
     __syncthreads();
     if (nn) {
         const float *in = X;
@@ -1013,13 +1094,17 @@ __global__ void __launch_bounds__(NT) k_plan_grad(TubeDev D, PlanDev P, GradDev 
         const int64_t b = base + tid;
         float *zw = ZW + tid * ZS;
         const float *vr = X + tid * I + 3 * Hr;
-        const PlanWalk W = plan_walk<true>(P.p, nn, vr, FW + tid * N, zw, P.z0[b * 2], P.z0[b * 2 + 1], P.w0 ? P.w0[b] : 0.f, P.offset);
+        const float w0 = P.w0 ? P.w0[b] : 0.f;
+        const PlanSceneRow row{SCN + tid * PLAN_SCN};
+        const PlanWalk W = SC ? plan_walk<true>(P.p, row, nn, vr, FW + tid * N, zw, P.z0[b * 2], P.z0[b * 2 + 1], w0, P.offset)
+                              : plan_walk<true>(P.p, PlanSceneProb{P.p}, nn, vr, FW + tid * N, zw, P.z0[b * 2], P.z0[b * 2 + 1], w0, P.offset);
         const float J = ((W.cost + G.rho_g * W.pen_g) + G.rho_w * W.pen_w) + G.rho_z * W.pen_z;
         G.J[b] = J;
         if (P.cost) P.cost[b] = W.cost;
         if (P.min_clear) P.min_clear[b] = W.minc;
         if (G.pen) { G.pen[b * 3] = W.pen_g; G.pen[b * 3 + 1] = W.pen_w; G.pen[b * 3 + 2] = W.pen_z; }
-        plan_walk_back(P.p, nn, vr, FW + tid * N, zw, G.rho_g, G.rho_w, G.rho_z);
+        if (SC) plan_walk_back(P.p, row, nn, vr, FW + tid * N, zw, G.rho_g, G.rho_w, G.rho_z);
+        else plan_walk_back(P.p, PlanSceneProb{P.p}, nn, vr, FW + tid * N, zw, G.rho_g, G.rho_w, G.rho_z);
         zw[0] = J;
     }
     __syncthreads();
@@ -1332,16 +1417,36 @@ void tubek_predict_windows_levels(const TubeDev *D, const float *w, const float 
                        n_levels, o);
 }
 
+// Per-plan scenes: sc = null launches the instantiation without them, the code of the entries before
+// scenes; otherwise the <SC = true> one, whose tile carries R scene rows (one row in the sampling kernels, within the same budget).
+constexpr size_t PLAN_SCN_BYTES = sizeof(float) * (size_t)R * PLAN_SCN;
+static void plan_scenes_dev(PlanDev *P, const lg_plan_scenes *sc) {
+    if (!sc) return;
+    P->sc_goal = sc->goal; P->sc_obs = sc->obs; P->sc_n = sc->n_obs;
+}
+// the dynamic LDS ceiling of kernel f, set once per device, not per launch
+static int plan_ceiling(const void *f, bool *set) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    if (dev < 0 || dev >= 64 || !set[dev]) {
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
+        if (dev >= 0 && dev < 64) set[dev] = true;
+    }
+    return 0;
+}
+
 // k_plan_score.  D: the horizon handle's TubeDev, or null for an analytic kind.  Returns the dynamic LDS of the launch in bytes, or
 // -1 where the kernel's ceiling cannot be set.  The reference shape (130 inputs, 128 units, N = 50) takes 74 KiB, past k_tube_predict's
 // own 64 KiB, so the ceiling is the roll-out kernels'; the largest shape of the envelope stays below it:
-static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + 2 * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N)) <= LG_TUBE_ROLLOUT_LDS,
+static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + 2 * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N) + PLAN_SCN) <= LG_TUBE_ROLLOUT_LDS,
               "k_plan_score: the envelope's largest tile set must fit the dynamic LDS ceiling");
 int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
                          const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
-                         float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, hipStream_t s) {
+                         float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w,
+                         const lg_plan_scenes *sc, hipStream_t s) {
     PlanDev P;
     memset(&P, 0, sizeof(P));
+    plan_scenes_dev(&P, sc);
     TubeDev T;
     memset(&T, 0, sizeof(T));
     if (D) T = *D;
@@ -1352,15 +1457,13 @@ int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const fl
     P.level = level;
     P.Hr = nn ? prob->H_rev : 0;
     P.I = nn ? T.in_dim : 2 * prob->N;
-    const size_t bytes = sizeof(float) * (size_t)R * (P.I + (nn ? 2 * T.units : 0) + prob->N + PLAN_ZS(prob->N));
-    static bool ceiling_set[64];        // per device: the attribute is set once, not per launch
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
-    if (dev < 0 || dev >= 64 || !ceiling_set[dev]) {
-        if (hipFuncSetAttribute((const void *)k_plan_score, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
-        if (dev >= 0 && dev < 64) ceiling_set[dev] = true;
-    }
-    hipLaunchKernelGGL(k_plan_score, dim3((unsigned)((B + R - 1) / R)), dim3(NT), bytes, s, T, P, B);
+    const size_t bytes = sizeof(float) * (size_t)R * (P.I + (nn ? 2 * T.units : 0) + prob->N + PLAN_ZS(prob->N)) + (sc ? PLAN_SCN_BYTES : 0);
+    static bool ceiling_set[2][64];
+    const void *f = sc ? (const void *)k_plan_score<true> : (const void *)k_plan_score<false>;
+    if (plan_ceiling(f, ceiling_set[sc != nullptr])) return -1;
+    const dim3 grid((unsigned)((B + R - 1) / R));
+    if (sc) hipLaunchKernelGGL(k_plan_score<true>, grid, dim3(NT), bytes, s, T, P, B);
+    else hipLaunchKernelGGL(k_plan_score<false>, grid, dim3(NT), bytes, s, T, P, B);
     return (int64_t)bytes;
 }
 
@@ -1390,9 +1493,11 @@ void tubek_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *
 // returns the dynamic LDS of the launch in bytes, or -1 where the kernel's ceiling cannot be set
 int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
                                 const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
-                                const float *vbar, float *J, float *cost, float *min_clear, float *pen, hipStream_t s) {
+                                const float *vbar, float *J, float *cost, float *min_clear, float *pen, const lg_plan_scenes *sc,
+                                hipStream_t s) {
     PlanDev P;
     memset(&P, 0, sizeof(P));
+    plan_scenes_dev(&P, sc);
     TubeDev T;
     memset(&T, 0, sizeof(T));
     if (D) T = *D;
@@ -1405,30 +1510,29 @@ int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, c
     P.I = nn ? T.in_dim : 2 * prob->N;
     MppiDev M = mppi_dev(prob, cfg, it);
     M.vbar_in = vbar; M.J = J; M.pen = pen;
-    const size_t bytes = sizeof(float) * (size_t)R * (P.I + (nn ? 2 * T.units : 0) + prob->N + PLAN_ZS(prob->N));
-    static bool ceiling_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
-    if (dev < 0 || dev >= 64 || !ceiling_set[dev]) {
-        if (hipFuncSetAttribute((const void *)k_plan_sample_score, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
-        if (dev >= 0 && dev < 64) ceiling_set[dev] = true;
-    }
-    hipLaunchKernelGGL(k_plan_sample_score, dim3((unsigned)(P_ * cfg->K / R)), dim3(NT), bytes, s, T, P, M);
+    const size_t bytes = sizeof(float) * ((size_t)R * (P.I + (nn ? 2 * T.units : 0) + prob->N + PLAN_ZS(prob->N)) + (sc ? PLAN_SCN : 0));
+    static bool ceiling_set[2][64];
+    const void *f = sc ? (const void *)k_plan_sample_score<true> : (const void *)k_plan_sample_score<false>;
+    if (plan_ceiling(f, ceiling_set[sc != nullptr])) return -1;
+    const dim3 grid((unsigned)(P_ * cfg->K / R));
+    if (sc) hipLaunchKernelGGL(k_plan_sample_score<true>, grid, dim3(NT), bytes, s, T, P, M);
+    else hipLaunchKernelGGL(k_plan_sample_score<false>, grid, dim3(NT), bytes, s, T, P, M);
     return (int64_t)bytes;
 }
 // The one-step kind.  Every shape of the envelope fits the ceiling without the weights -- the reference
 // configurations (T <= 10, units <= 128, N <= 64) with room to spare --; lg_plan_check asks tubek_plan_step_bytes all the same.
-static_assert(sizeof(float) * plan_step_floats(LG_TUBE_MAX_IN, LG_TUBE_MAX_UNITS, LG_PLAN_STEP_MAX_HREV, LG_PLAN_MAX_N) <= LG_TUBE_ROLLOUT_LDS,
+static_assert(sizeof(float) * plan_step_floats(LG_TUBE_MAX_IN, LG_TUBE_MAX_UNITS, LG_PLAN_STEP_MAX_HREV, LG_PLAN_MAX_N, true) <= LG_TUBE_ROLLOUT_LDS,
               "k_plan_score_step: the envelope's largest tile set must fit the dynamic LDS ceiling");
-static_assert(sizeof(float) * plan_step_floats(31, 128, LG_PLAN_STEP_MAX_HREV, 64) <= LG_TUBE_ROLLOUT_LDS, "the reference one-step shapes fit");
-// dynamic LDS of the one-step tile in bytes, without the weights
+static_assert(sizeof(float) * plan_step_floats(31, 128, LG_PLAN_STEP_MAX_HREV, 64, true) <= LG_TUBE_ROLLOUT_LDS, "the reference one-step shapes fit");
+// dynamic LDS of the one-step tile in bytes, without the weights and without the scene rows
 int64_t tubek_plan_step_bytes(const TubeDev *D, const lg_plan_problem *prob) {
-    return (int64_t)(sizeof(float) * plan_step_floats(D->in_dim, D->units, prob->H_rev, prob->N));
+    return (int64_t)(sizeof(float) * plan_step_floats(D->in_dim, D->units, prob->H_rev, prob->N, false));
 }
 static PlanDev plan_step_dev(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *e, const float *v_prev,
-                             const float *w0, const float *offset, float level) {
+                             const float *w0, const float *offset, float level, const lg_plan_scenes *sc) {
     PlanDev P;
     memset(&P, 0, sizeof(P));
+    plan_scenes_dev(&P, sc);
     P.p = *prob;
     P.z0 = z0; P.e = e; P.v_prev = v_prev; P.w0 = w0; P.offset = offset;
     P.level = level;
@@ -1437,52 +1541,52 @@ static PlanDev plan_step_dev(const TubeDev *D, const lg_plan_problem *prob, cons
     return P;
 }
 // weights go to LDS where weights + tile fit the ceiling; *bytes: the launch's dynamic LDS
-static bool plan_step_wlds(const TubeDev *D, const lg_plan_problem *prob, size_t *bytes) {
-    const size_t tile = (size_t)tubek_plan_step_bytes(D, prob), all = tile + sizeof(float) * (size_t)D->num_params;
+static bool plan_step_wlds(const TubeDev *D, const lg_plan_problem *prob, bool scenes, size_t *bytes) {
+    const size_t tile = (size_t)tubek_plan_step_bytes(D, prob) + (scenes ? PLAN_SCN_BYTES : 0);
+    const size_t all = tile + sizeof(float) * (size_t)D->num_params;
     const bool wl = all <= LG_TUBE_ROLLOUT_LDS;
     *bytes = wl ? all : tile;
     return wl;
 }
-static int plan_step_ceiling(const void *f, bool *set) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
-    if (dev < 0 || dev >= 64 || !set[dev]) {
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
-        if (dev >= 0 && dev < 64) set[dev] = true;
-    }
-    return 0;
-}
+// the four instantiations of a one-step kernel, by (weights in LDS, scenes)
+#define PLAN_STEP_PICK(K, wl, sc) \
+    ((wl) ? ((sc) ? (const void *)K<true, true> : (const void *)K<true, false>) : ((sc) ? (const void *)K<false, true> : (const void *)K<false, false>))
+#define PLAN_STEP_LAUNCH(K, wl, sc, grid, bytes, s, ...)                                         \
+    do {                                                                                         \
+        if ((wl) && (sc)) hipLaunchKernelGGL((K<true, true>), grid, dim3(NT), bytes, s, __VA_ARGS__);       \
+        else if (wl) hipLaunchKernelGGL((K<true, false>), grid, dim3(NT), bytes, s, __VA_ARGS__);           \
+        else if (sc) hipLaunchKernelGGL((K<false, true>), grid, dim3(NT), bytes, s, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((K<false, false>), grid, dim3(NT), bytes, s, __VA_ARGS__);                  \
+    } while (0)
 // returns the dynamic LDS of the launch in bytes, or -1 where the kernel's ceiling cannot be set
 int64_t tubek_plan_score_step(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
                               const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
-                              float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, hipStream_t s) {
-    PlanDev P = plan_step_dev(D, prob, z0, e, v_prev, w0, offset, level);
+                              float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w,
+                              const lg_plan_scenes *sc, hipStream_t s) {
+    PlanDev P = plan_step_dev(D, prob, z0, e, v_prev, w0, offset, level, sc);
     P.v = v; P.cost = cost; P.min_clear = min_clear; P.worst_node = worst_node; P.n_viol = n_viol; P.fw = fw; P.z = z; P.w = w;
     size_t bytes;
-    const bool wl = plan_step_wlds(D, prob, &bytes);
-    static bool ceiling_set[2][64];
-    const void *f = wl ? (const void *)k_plan_score_step<true> : (const void *)k_plan_score_step<false>;
-    if (plan_step_ceiling(f, ceiling_set[wl])) return -1;
+    const bool wl = plan_step_wlds(D, prob, sc != nullptr, &bytes);
+    static bool ceiling_set[4][64];
+    if (plan_ceiling(PLAN_STEP_PICK(k_plan_score_step, wl, sc), ceiling_set[2 * wl + (sc != nullptr)])) return -1;
     const dim3 grid((unsigned)((B + R - 1) / R));
-    if (wl) hipLaunchKernelGGL(k_plan_score_step<true>, grid, dim3(NT), bytes, s, *D, P, B);
-    else hipLaunchKernelGGL(k_plan_score_step<false>, grid, dim3(NT), bytes, s, *D, P, B);
+    PLAN_STEP_LAUNCH(k_plan_score_step, wl, sc, grid, bytes, s, *D, P, B);
     return (int64_t)bytes;
 }
 int64_t tubek_plan_sample_score_step(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
                                      const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
-                                     const float *vbar, float *J, float *cost, float *min_clear, float *pen, hipStream_t s) {
-    PlanDev P = plan_step_dev(D, prob, z0, e, v_prev, w0, offset, level);
+                                     const float *vbar, float *J, float *cost, float *min_clear, float *pen, const lg_plan_scenes *sc,
+                                     hipStream_t s) {
+    PlanDev P = plan_step_dev(D, prob, z0, e, v_prev, w0, offset, level, sc);
     P.cost = cost; P.min_clear = min_clear;
     MppiDev M = mppi_dev(prob, cfg, it);
     M.vbar_in = vbar; M.J = J; M.pen = pen;
     size_t bytes;
-    const bool wl = plan_step_wlds(D, prob, &bytes);
-    static bool ceiling_set[2][64];
-    const void *f = wl ? (const void *)k_plan_sample_score_step<true> : (const void *)k_plan_sample_score_step<false>;
-    if (plan_step_ceiling(f, ceiling_set[wl])) return -1;
+    const bool wl = plan_step_wlds(D, prob, sc != nullptr, &bytes);   // one scene row is read; the tile's budget is k_plan_score_step's
+    static bool ceiling_set[4][64];
+    if (plan_ceiling(PLAN_STEP_PICK(k_plan_sample_score_step, wl, sc), ceiling_set[2 * wl + (sc != nullptr)])) return -1;
     const dim3 grid((unsigned)(P_ * cfg->K / R));
-    if (wl) hipLaunchKernelGGL(k_plan_sample_score_step<true>, grid, dim3(NT), bytes, s, *D, P, M);
-    else hipLaunchKernelGGL(k_plan_sample_score_step<false>, grid, dim3(NT), bytes, s, *D, P, M);
+    PLAN_STEP_LAUNCH(k_plan_sample_score_step, wl, sc, grid, bytes, s, *D, P, M);
     return (int64_t)bytes;
 }
 void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,
@@ -1495,14 +1599,16 @@ void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg,
 
 // k_plan_grad.  Its tile keeps every hidden layer's output, so the largest shape of the envelope -- 256
 // inputs, 4 x 128 units, N = 64 -- takes 128.4 KiB at R = 32 rows and stays below the ceiling; no smaller tile is needed:
-static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + (LG_TUBE_MAX_LIN - 1) * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N)) <=
+static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + (LG_TUBE_MAX_LIN - 1) * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N) + PLAN_SCN) <=
                   LG_TUBE_ROLLOUT_LDS,
               "k_plan_grad: the envelope's largest tile set must fit the dynamic LDS ceiling");
 static_assert(PLAN_ZS(1) >= 6, "k_plan_grad keeps J, two flags and dJ/dv of step 0 in a row of nodes at N = 1 too");
 // returns the dynamic LDS of the launch in bytes, or -1 where the kernel's ceiling cannot be set
-int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, hipStream_t s) {
+int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, const lg_plan_scenes *sc,
+                        hipStream_t s) {
     PlanDev P;
     memset(&P, 0, sizeof(P));
+    plan_scenes_dev(&P, sc);
     TubeDev T;
     memset(&T, 0, sizeof(T));
     if (D) T = *D;
@@ -1521,15 +1627,13 @@ int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const Pla
     G.lr = A->lr; G.beta1 = A->beta1; G.beta2 = A->beta2; G.eps = A->eps; G.bc1 = A->bc1; G.bc2 = A->bc2;
     G.rho_g = A->rho_g; G.rho_w = A->rho_w; G.rho_z = A->rho_z;
     for (int d = 0; d < 2; ++d) { G.v_min[d] = prob->rom_v_min[d]; G.v_max[d] = prob->rom_v_max[d]; }
-    const size_t bytes = sizeof(float) * (size_t)R * (P.I + (nn ? T.layers * T.units : 0) + prob->N + PLAN_ZS(prob->N));
-    static bool ceiling_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
-    if (dev < 0 || dev >= 64 || !ceiling_set[dev]) {
-        if (hipFuncSetAttribute((const void *)k_plan_grad, hipFuncAttributeMaxDynamicSharedMemorySize, LG_TUBE_ROLLOUT_LDS) != hipSuccess) return -1;
-        if (dev >= 0 && dev < 64) ceiling_set[dev] = true;
-    }
-    hipLaunchKernelGGL(k_plan_grad, dim3((unsigned)((B + R - 1) / R)), dim3(NT), bytes, s, T, P, G, B);
+    const size_t bytes = sizeof(float) * (size_t)R * (P.I + (nn ? T.layers * T.units : 0) + prob->N + PLAN_ZS(prob->N)) + (sc ? PLAN_SCN_BYTES : 0);
+    static bool ceiling_set[2][64];
+    const void *f = sc ? (const void *)k_plan_grad<true> : (const void *)k_plan_grad<false>;
+    if (plan_ceiling(f, ceiling_set[sc != nullptr])) return -1;
+    const dim3 grid((unsigned)((B + R - 1) / R));
+    if (sc) hipLaunchKernelGGL(k_plan_grad<true>, grid, dim3(NT), bytes, s, T, P, G, B);
+    else hipLaunchKernelGGL(k_plan_grad<false>, grid, dim3(NT), bytes, s, T, P, G, B);
     return (int64_t)bytes;
 }
 

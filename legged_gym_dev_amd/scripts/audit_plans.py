@@ -6,7 +6,7 @@ source, on the HIP kernels (legged_gym_dev_amd/tube/plan.py; DESIGN.md section 1
         (--problem gap|right|right_wide | --problem_json F) \\
         (--plans F.npz | --warm_start start|goal|interpolate [--perturb K --sigma s --seed n]) \\
         [--calibration [PATH] | --age_calibration [PATH] [--trajectory_margin]] [--H_rev h] [--coverage c] [--level l] \\
-        [--checkpoint best|latest] [--sim_cfg KEY=VALUE ...] [--out DIR] \\
+        [--checkpoint best|latest] [--sim_cfg KEY=VALUE ...] [--out DIR] [--scenes F.npz] \\
         [--robot [--task anymal_c_flat_trajectory] [--load_run R] [--policy_checkpoint K] [--push_robots] [--allow_fast]]
 
 --run: a train_tube.py run of a one-shot tube (dataset scalar_horizon or scalar_horizon_level): the plans have N = the run's H_fwd
@@ -28,6 +28,11 @@ the HIP env with PlanTrajectoryGenerator (legged_gym_dev_amd/tube/plan_env.py; D
 with the robot's own history as the tube item's past, then audit_env, which adds completed / terminated / covered_plans_of_all and
 a "tracker": "robot" field.  The policy's checkpoint has its own flag because --checkpoint already names the tube's.  The problem's
 dt must be the task's rom.dt and the inputs must lie inside its rom.v_min / v_max (--allow_fast lifts the latter).
+
+--scenes F.npz: a Scenes file (plan_tube.py --scenes writes scenes.npz beside plans.npz): plan b is scored
+and audited against scene b's own goal and obstacles, so the file holds as many scenes as --plans holds plans.  With --warm_start
+every scene gets the warm start to its own goal and, with --perturb K, K perturbations of it (seed + the scene's number): S (K + 1)
+plans, scene by scene, each scene repeated K + 1 times on the host.  The audit gains its per-plan lists (by_plan).
 
 Writes audit.json to --out (default: the run folder, or the working directory) and prints the reference script's
 "Total Success Rate" line: the share of (plan, node) pairs with tube >= realised error.
@@ -79,7 +84,10 @@ def parse_args(argv=None):
     ap.add_argument("--policy_checkpoint", type=int, default=None, help="with --robot: the policy's checkpoint number (default: the latest)")
     ap.add_argument("--push_robots", action="store_true", help="with --robot: push the robots on the task's timers")
     ap.add_argument("--allow_fast", action="store_true", help="with --robot: accept inputs beyond the task's rom.v_min / v_max")
+    ap.add_argument("--scenes", default=None, metavar="F.npz", help="a Scenes file: plan b against scene b's own goal and obstacles")
     a = ap.parse_args(argv)
+    if a.scenes is not None and not a.scenes.endswith(".npz"):
+        ap.error(f"--scenes {a.scenes}: a .npz file (plan_tube.py --scenes writes scenes.npz)")
     if not a.robot:
         for flag in ("task", "load_run", "policy_checkpoint", "push_robots", "allow_fast"):
             if getattr(a, flag) not in (None, False):
@@ -178,6 +186,28 @@ def build_problem(a, cfg):
     return p
 
 
+def build_scene_plans(a, p):
+    """--scenes: (z0, v, source, Scenes of S = B).  --plans: one scene per plan.  --warm_start: per scene the warm start to its own
+    goal and its --perturb K perturbations, the scene repeated K + 1 times."""
+    import torch
+    scenes = pl.Scenes.load(a.scenes)
+    if a.plans:
+        z0, v, source = build_plans(a, p)
+        if scenes.S != v.shape[0]:
+            raise ValueError(f"--scenes {a.scenes} holds {scenes.S} scenes and --plans {a.plans} {v.shape[0]} plans: one scene per plan")
+        return z0, v, {**source, "scenes_file": a.scenes}, scenes
+    vs = []
+    for s, goal in enumerate(scenes.goals(p)):
+        v = torch.as_tensor(pl.warm_start(a.warm_start, p.start, goal, p.N, p.dt)[1], dtype=torch.float32)[None]
+        if a.perturb:
+            v = torch.cat([v, pl.perturb(v[0], a.sigma, a.perturb, a.seed + s, p.rom_v_min, p.rom_v_max)])
+        vs.append(v)
+    v = torch.cat(vs)
+    z0 = torch.tensor(p.start, dtype=torch.float32).repeat(v.shape[0], 1)
+    source = {"warm_start": a.warm_start, "perturb": a.perturb, "sigma": a.sigma, "seed": a.seed, "scenes_file": a.scenes}
+    return z0, v, source, scenes.take(np.repeat(np.arange(scenes.S), a.perturb + 1))
+
+
 def build_plans(a, p):
     """(z0 (B, 2), v (B, N, 2)) float32 tensors and a description of where they come from."""
     import torch
@@ -239,7 +269,7 @@ def robot_env(a, B):
     return env, runner, runner.get_inference_policy(device=env.device), path
 
 
-def main_robot(a, p, scorer, z0, v):
+def main_robot(a, p, scorer, z0, v, scenes=None):
     """--robot: track_env, score with the robot's own history, audit_env."""
     import torch
     from legged_gym_dev_amd.tube.plan_env import audit_env, track_env
@@ -248,9 +278,10 @@ def main_robot(a, p, scorer, z0, v):
         if abs(float(env.rom.dt) - float(p.dt)) > 1e-9:
             raise ValueError(f"the problem's dt = {p.dt} differs from the task's rom.dt = {env.rom.dt}")
         t = track_env(env, policy, v, z0, H_rev=p.H_rev, allow_fast=a.allow_fast)
-        s = scorer.score(z0, v, e=t["e_past"], v_prev=t["v_prev"], w0=t["w0"])
+        skw = {} if scenes is None else {"scenes": scenes}
+        s = scorer.score(z0, v, e=t["e_past"], v_prev=t["v_prev"], w0=t["w0"], **skw)
         torch.cuda.synchronize()
-        res = audit_env(s, t, p)
+        res = audit_env(s, t, p, **skw)
     finally:
         runner.ppo.close()
         env.close()
@@ -274,7 +305,12 @@ def main(argv=None):
         calib = load_calibration(a, cfg)
     else:
         pl.check_envelope(p)
-    z0, v, source = build_plans(a, p)
+    scenes = None
+    if a.scenes is not None:
+        z0, v, source, scenes = build_scene_plans(a, p)
+    else:
+        z0, v, source = build_plans(a, p)
+    skw = {} if scenes is None else {"scenes": scenes}
     try:
         if a.run:
             model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, device=a.device)
@@ -282,16 +318,16 @@ def main(argv=None):
                                   trajectory=a.trajectory_margin)
         robot = {}
         if a.robot:
-            s, res, robot = main_robot(a, p, scorer, z0, v)
+            s, res, robot = main_robot(a, p, scorer, z0, v, **skw)
         else:
             sim = HipRomSim(sim_config(a, p), device=a.device)
-            s = scorer.score(z0, v)
+            s = scorer.score(z0, v, **skw)
             t = pl.track(sim, s["z"], v)
             torch.cuda.synchronize()
-            res = pl.audit(s, t, p)
+            res = pl.audit(s, t, p, **skw)
         cost, clear = s["cost"].cpu().double(), s["min_clear"].cpu().double()
         extra = {"cost_mean": float(cost.mean()), "cost_min": float(cost.min()), "best_plan": int(cost.argmin()),
-                 "min_clear_min": float(clear.min()) if p.n_obs else None, "n_viol_plans": [int(x) for x in (s["n_viol"] > 0).sum(dim=0).cpu()],
+                 "min_clear_min": float(clear.min()) if p.n_obs or (scenes is not None and bool(np.isfinite(clear.numpy()).any())) else None, "n_viol_plans": [int(x) for x in (s["n_viol"] > 0).sum(dim=0).cpu()],
                  "problem": p.to_json(), "run": a.run, "tube": a.tube or p.tube_kind, "level": level,
                  "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), "source": source, **robot}
         assert not set(extra) & set(res), "a key of the audit would be overwritten"

@@ -8,7 +8,8 @@ place of CasADi / IPOPT, for many starts at once.
         [--H_rev h] [--coverage c] [--w0 zero|error] \\
         [--K 256] [--iters 20] [--sigma 0.3] [--sigma_decay 1] [--lambda 1] [--rho_g 1e4] [--rho_w 0] [--rho_z 0] [--seed 0] \\
         [--planner mppi|grad|mppi+grad] [--lr 0.05] [--grad_iters 100] \\
-        [--starts P --start_noise s] [--closed_loop H] [--sim_cfg KEY=VALUE ...] [--out DIR]
+        [--starts P --start_noise s] [--closed_loop H] [--sim_cfg KEY=VALUE ...] [--out DIR] \\
+        [--scenes random|FILE.npz [--scene_seed n] [--scene_obs LO,HI] [--scene_radius LO,HI] [--scene_margin M]]
 
 --run, --tube, --calibration, --coverage, --level, --checkpoint, --sim_cfg: as audit_plans.py takes them; a run that audit_plans.py
 refuses is refused here; a step run (dataset scalar / scalar_level, rolled along the plan: DESIGN.md section 10.13) plans with
@@ -18,6 +19,14 @@ then the gradient planner from MPPI's best plan).  --problem: one of the referen
 in .json).  --starts P: P instances; the first starts at the problem's start, the others at start + start_noise * standard normal.
 Without --closed_loop every start gets one plan, which is scored, tracked and audited as audit_plans.py does.  With --closed_loop H
 every robot replans at each of H control steps (closed_loop) and the audit is audit_closed_loop's.
+
+--scenes: every start plans in a scene of its own -- its own goal and obstacles -- in the same launches.
+FILE.npz: a Scenes file (goal (S, 2), obs_c, obs_r, n_obs) of S = --starts scenes.  random: random_scenes(--starts, --scene_seed, the
+problem's start) with --scene_obs LO,HI obstacles (default 1,3) of radius in --scene_radius LO,HI (default 0.1,0.4), centres in the box
+the problem's start and goal span (padded by 0.25), goals within 0.5 of the problem's goal, the start and the goal at least
+--scene_margin (default 0.05) outside every obstacle.  scenes.npz is written beside plans.npz, one scene per row of it (with
+--closed_loop the starts' scenes once per step), so audit_plans.py --plans plans.npz --scenes scenes.npz reads both; plan.json gains
+"scenes" (the source) and the audit its per-scene lists (by_plan / by_robot).  Without --scenes the output is what it was.
 
 Writes plan.json -- the audit, the history of the (first) plan, the settings -- and plans.npz with z0 (B, 2), v (B, N, 2): the final
 mean plans, or with --closed_loop every plan in force, step by step; audit_plans.py --plans reads it.
@@ -72,7 +81,9 @@ def parse_args(argv=None):
     ap.add_argument("--sim_cfg", nargs="*", default=[], metavar="KEY=VALUE")
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
+    add_scene_flags(ap)
     a = ap.parse_args(argv)
+    check_scene_flags(ap, a)
     if a.problem not in pl.PROBLEMS and not a.problem.endswith(".json"):
         ap.error(f"--problem {a.problem}: one of {sorted(pl.PROBLEMS)} or a .json file")
     if a.calibration is not None and not a.run:
@@ -97,6 +108,62 @@ def parse_args(argv=None):
 
 
 PLANNERS = ("mppi", "grad", "mppi+grad")
+SCENE_DEFAULTS = {"scene_seed": 0, "scene_obs": (1, 3), "scene_radius": (0.1, 0.4), "scene_margin": 0.05}
+
+
+def add_scene_flags(ap):
+    ap.add_argument("--scenes", default=None, metavar="random|FILE.npz", help="a scene of its own per start: random, or a Scenes file")
+    ap.add_argument("--scene_seed", type=int, default=None)
+    ap.add_argument("--scene_obs", default=None, metavar="LO,HI", help="obstacles per random scene (default 1,3)")
+    ap.add_argument("--scene_radius", default=None, metavar="LO,HI", help="radius of a random obstacle (default 0.1,0.4)")
+    ap.add_argument("--scene_margin", type=float, default=None, help="start and goal stay this far outside every random obstacle")
+
+
+def check_scene_flags(ap, a):
+    """Refuse what does not fit, parse the LO,HI pairs and fill the defaults of --scenes random."""
+    given = [k for k in SCENE_DEFAULTS if getattr(a, k) is not None]
+    if a.scenes is None:
+        if given:
+            ap.error(f"--{given[0]} belongs to --scenes random")
+        return
+    if a.scenes != "random":
+        if not a.scenes.endswith(".npz"):
+            ap.error(f"--scenes {a.scenes}: random or a .npz file")
+        if given:
+            ap.error(f"--{given[0]} belongs to --scenes random; {a.scenes} is taken as it is")
+        return
+    for k, kind in (("scene_obs", int), ("scene_radius", float)):
+        v = getattr(a, k)
+        if v is None:
+            continue
+        try:
+            lo, hi = (kind(x) for x in v.split(","))
+        except ValueError:
+            ap.error(f"--{k} {v}: LO,HI")
+        if not 0 <= lo <= hi or (k == "scene_obs" and hi > 8):
+            ap.error(f"--{k} {v}: 0 <= LO <= HI" + (" <= 8" if k == "scene_obs" else ""))
+        setattr(a, k, (lo, hi))
+    for k, v in SCENE_DEFAULTS.items():
+        if getattr(a, k) is None:
+            setattr(a, k, v)
+    if a.scene_margin < 0:
+        ap.error("--scene_margin must not be negative")
+
+
+def build_scenes(a, p):
+    """(Scenes of S = --starts, what plan.json says of them), or (None, None) without --scenes."""
+    if a.scenes is None:
+        return None, None
+    if a.scenes != "random":
+        sc = pl.Scenes.load(a.scenes)
+        if sc.S != a.starts:
+            raise ValueError(f"--scenes {a.scenes} holds {sc.S} scenes; --starts is {a.starts} (one scene per start)")
+        return sc, {"file": a.scenes, "S": sc.S}
+    s, g = np.asarray(p.start, np.float64), np.asarray(p.goal, np.float64)
+    kw = dict(n_obs=a.scene_obs, radius=a.scene_radius, margin=a.scene_margin,
+              centre_box=((np.minimum(s, g) - 0.25).tolist(), (np.maximum(s, g) + 0.25).tolist()),
+              goal_box=((g - 0.5).tolist(), (g + 0.5).tolist()))
+    return pl.random_scenes(a.starts, a.scene_seed, p.start, **kw), {"random": {"seed": a.scene_seed, **{k: list(v) if isinstance(v, tuple) else v for k, v in kw.items()}}, "S": a.starts}
 
 
 def mppi_cfg(a):
@@ -108,9 +175,11 @@ def grad_cfg(a):
     return pl.GradCfg(iters=a.grad_iters, lr=a.lr, rho_g=a.rho_g, rho_w=a.rho_w, rho_z=a.rho_z)
 
 
-def make_planner(a, model, p, calib):
+def make_planner(a, model, p, calib, scenes=None):
     """The planner --planner names, on one scorer's arguments."""
     kw = dict(calibration=calib, level=a.level, coverage=a.coverage, device=a.device)
+    if scenes is not None:
+        kw["scenes"] = scenes
     if a.planner == "mppi":
         return pl.HipMppiPlanner(model, p, mppi_cfg(a), trajectory=a.trajectory_margin, **kw)
     if p.tube_kind == "nn_step":
@@ -151,16 +220,18 @@ def main(argv=None):
     else:
         pl.check_envelope(p)
     z0 = starts(a, p)
+    scenes, scenes_src = build_scenes(a, p)
+    plan_scenes = scenes
     try:
         if a.run:
             model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, device=a.device)
-        planner = make_planner(a, model, p, calib)
+        planner = make_planner(a, model, p, calib, scenes)
         sim = HipRomSim(audit_plans.sim_config(a, p), device=a.device)
         if a.closed_loop is None:
             sol = planner.plan(z0)
             t = pl.track(sim, sol["score"]["z"], sol["v"])
             torch.cuda.synchronize()
-            audit = pl.audit(sol["score"], t, p)
+            audit = pl.audit(sol["score"], t, p) if scenes is None else pl.audit(sol["score"], t, p, scenes=scenes)
             hist, plans_z0, plans_v = sol["hist"], z0, sol["v"]
             extra = {"best_J": [float(x) for x in sol["best_J"].cpu()], "n_bad": [int(x) for x in sol["n_bad"].cpu()],
                      "cost": [float(x) for x in sol["score"]["cost"].cpu()]}
@@ -168,11 +239,16 @@ def main(argv=None):
             first = planner.plan(z0)                                     # the history of the first plan; closed_loop makes it again
             res = pl.closed_loop(planner, sim, a.closed_loop, z0, keep_plans=True, w0=a.w0)
             torch.cuda.synchronize()
-            audit = pl.audit_closed_loop(res, p, goal_tol=a.goal_tol)
+            audit = pl.audit_closed_loop(res, p, goal_tol=a.goal_tol, **({} if scenes is None else {"scenes": scenes}))
+            if scenes is not None:                                      # plans.npz holds (H, P) plans: the starts' scenes once per step
+                plan_scenes = scenes.take(np.tile(np.arange(scenes.S), a.closed_loop))
             hist = first["hist"]
             plans_z0, plans_v = res["plans_z"][:, :, 0].reshape(-1, 2), res["plans_v"].reshape(-1, p.N, 2)
             extra = {"n_bad": [int(x) for x in res["n_bad"].sum(dim=1).cpu()], "cost": res["cost"].cpu().double().tolist(),
                      "min_clear": res["min_clear"].cpu().double().tolist() if p.n_obs else None}
+            if scenes is not None:                                      # a scene without obstacles has min_clear = +inf: null in JSON
+                clear = res["min_clear"].cpu().double()
+                extra["min_clear"] = [[float(x) if np.isfinite(x) else None for x in row] for row in clear.tolist()]
     finally:
         if sim is not None:
             sim.close()
@@ -185,11 +261,15 @@ def main(argv=None):
         out["w0"] = a.w0
     if a.planner != "mppi":
         out.update({"planner": a.planner, "grad": vars(grad_cfg(a))})
+    if scenes is not None:
+        out["scenes"] = scenes_src
     folder = a.out or a.run or "."
     os.makedirs(folder, exist_ok=True)
     with open(os.path.join(folder, "plan.json"), "w") as f:
         json.dump(out, f, indent=1, allow_nan=False)
     np.savez(os.path.join(folder, "plans.npz"), z0=plans_z0.cpu().numpy(), v=plans_v.cpu().numpy())
+    if plan_scenes is not None:
+        plan_scenes.save(os.path.join(folder, "scenes.npz"))
     if a.closed_loop is None:
         print(f"{audit['plans']} plans x {audit['nodes']} nodes: predicted safe {audit['predicted_safe']:.4f}, actually safe "
               f"{audit['actually_safe']:.4f}, covered at every node {audit['covered_plans']:.4f}")

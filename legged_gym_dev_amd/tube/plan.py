@@ -9,6 +9,7 @@ loop is deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.p
 ``HipGradPlanner`` (section 10.11), or one after the other (``ChainedPlanner``) -- in ``closed_loop`` or alone, which stand in
 for the reference's NLP solve.  tube_kind "nn_step" (section 10.13) scores and plans with a flat one-step tube instead, rolled node
 by node along the plan inside the kernels (w[k+1] = fw(w[k], v[k], ..), trajopt/old/rom_tube_planning.py:106-107).
+`Scenes` (section 10.14) gives every plan of a launch, or every MPPI instance, a goal and obstacles of its own; `random_scenes` draws them.
 There is no CPU fallback: scoring, planning and tracking need the library and a GPU.
 """
 import ctypes as C
@@ -261,6 +262,185 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+# ---------------------------------------------------------------- per-plan scenes
+SCENES_ERR = "lg_plan_scenes: "                     # the prefix of lg_plan_scenes_check's refusals
+
+
+class Scenes:
+    """lg_plan_scenes: a goal and an obstacle list of its own for each of S plans (scoring, gradient) or S instances (MPPI); the
+    rest of the problem stays the PlanProblem's.  Host arrays, validated here: goal (S, 2) or None = the problem's goal; obs_c
+    (S, M <= 8, 2), obs_r (S, M) and n_obs (S) in 0..M -- scene s has the first n_obs[s] obstacles; n_obs None = M each -- or all
+    three None = the problem's obstacles.  Radii are finite and not negative; centres and goals finite."""
+
+    def __init__(self, goal=None, obs_c=None, obs_r=None, n_obs=None):
+        if goal is None and obs_c is None and obs_r is None and n_obs is None:
+            raise ValueError("goal, obs_c, obs_r and n_obs are all None: the scenes say nothing (pass scenes=None)")
+        if (obs_c is None) != (obs_r is None):
+            raise ValueError("obs_c and obs_r are given together or not at all")
+        if n_obs is not None and obs_c is None:
+            raise ValueError("n_obs is given without obs_c and obs_r")
+        self.goal = None if goal is None else np.ascontiguousarray(goal, np.float32)
+        self.obs_c = None if obs_c is None else np.ascontiguousarray(obs_c, np.float32)
+        self.obs_r = None if obs_r is None else np.ascontiguousarray(obs_r, np.float32)
+        if self.goal is not None and (self.goal.ndim != 2 or self.goal.shape[1] != 2 or self.goal.shape[0] < 1):
+            raise ValueError(f"goal must be (S >= 1, 2); got {self.goal.shape}")
+        self.n_obs = None
+        if self.obs_c is not None:
+            c, r = self.obs_c, self.obs_r
+            if c.ndim != 3 or c.shape[2] != 2 or c.shape[0] < 1 or c.shape[1] > capi.PLAN_MAX_OBS:
+                raise ValueError(f"obs_c must be (S >= 1, M <= {capi.PLAN_MAX_OBS}, 2); got {c.shape}")
+            if r.shape != c.shape[:2]:
+                raise ValueError(f"obs_r must be {c.shape[:2]}, one radius per centre; got {r.shape}")
+            n = np.full(c.shape[0], c.shape[1], np.int64) if n_obs is None else np.asarray(n_obs)
+            if n.shape != (c.shape[0],) or not np.issubdtype(n.dtype, np.integer):
+                raise ValueError(f"n_obs must be ({c.shape[0]},) integers; got {n.shape} {n.dtype}")
+            if n.min() < 0 or n.max() > c.shape[1]:
+                raise ValueError(f"n_obs must lie in 0..{c.shape[1]} (the slots of obs_c); got {int(n.min())}..{int(n.max())}")
+            self.n_obs = np.ascontiguousarray(n, np.int32)
+            live = np.arange(c.shape[1])[None, :] < self.n_obs[:, None]
+            if not np.isfinite(r[live]).all() or (r[live] < 0).any():
+                raise ValueError("obs_r: a radius is finite and not negative")
+            if not np.isfinite(c[live]).all():
+                raise ValueError("obs_c: a centre is finite")
+            if self.goal is not None and self.goal.shape[0] != c.shape[0]:
+                raise ValueError(f"goal holds {self.goal.shape[0]} scenes and obs_c {c.shape[0]}")
+        if self.goal is not None and not np.isfinite(self.goal).all():
+            raise ValueError("goal: a goal is finite")
+        self._dev = {}
+
+    @property
+    def S(self):
+        return int((self.goal if self.goal is not None else self.obs_c).shape[0])
+
+    def __len__(self):
+        return self.S
+
+    @classmethod
+    def repeat(cls, problem, S):
+        """S copies of the problem's own scene."""
+        M = problem.n_obs
+        return cls(goal=np.tile(np.asarray(problem.goal, np.float32), (int(S), 1)),
+                   obs_c=np.tile(np.asarray(problem.obs_c, np.float32).reshape(1, M, 2), (int(S), 1, 1)),
+                   obs_r=np.tile(np.asarray(problem.obs_r, np.float32).reshape(1, M), (int(S), 1)))
+
+    def take(self, idx):
+        """The scenes idx (an index array or slice) as Scenes of their own; repeats are allowed (there is no plan-to-scene map)."""
+        g = lambda a: None if a is None else a[idx]
+        return Scenes(g(self.goal), g(self.obs_c), g(self.obs_r), g(self.n_obs))
+
+    def problem(self, s, base):
+        """Scene s as a plain PlanProblem: `base` with the scene's goal and obstacles (float32 values, as the kernels read them)."""
+        kw = {}
+        if self.goal is not None:
+            kw["goal"] = [float(x) for x in self.goal[s]]
+        if self.obs_c is not None:
+            n = int(self.n_obs[s])
+            kw["obs_c"] = [[float(x) for x in c] for c in self.obs_c[s, :n]]
+            kw["obs_r"] = [float(x) for x in self.obs_r[s, :n]]
+        return dataclasses.replace(base, **kw)
+
+    def goals(self, problem):
+        """(S, 2) float64: every scene's goal (the problem's where the scenes carry none)."""
+        if self.goal is None:
+            return np.tile(np.asarray(problem.goal, np.float64), (self.S, 1))
+        return self.goal.astype(np.float64)
+
+    def obstacles(self, problem):
+        """(c (S, M, 2), r (S, M), live (S, M) bool) float64: every scene's obstacles (the problem's where the scenes carry none)."""
+        if self.obs_c is None:
+            M = problem.n_obs
+            return (np.tile(np.asarray(problem.obs_c, np.float64).reshape(1, M, 2), (self.S, 1, 1)),
+                    np.tile(np.asarray(problem.obs_r, np.float64).reshape(1, M), (self.S, 1)), np.ones((self.S, M), bool))
+        live = np.arange(self.obs_c.shape[1])[None, :] < self.n_obs[:, None]
+        return self.obs_c.astype(np.float64), self.obs_r.astype(np.float64), live
+
+    def packed(self):
+        """obs (S, 8, 3) float32 [cx, cy, r], zeros past n_obs, as the library reads it; None without obstacles of their own."""
+        if self.obs_c is None:
+            return None
+        M = self.obs_c.shape[1]
+        live = (np.arange(M)[None, :] < self.n_obs[:, None])[..., None]
+        obs = np.zeros((self.S, capi.PLAN_MAX_OBS, 3), np.float32)
+        obs[:, :M] = np.where(live, np.concatenate([self.obs_c, self.obs_r[..., None]], axis=2), np.float32(0))
+        return obs
+
+    def to(self, device):
+        """The device copy: (lg_plan_scenes, the tensors it points to), kept per device."""
+        import torch
+        key = str(torch.device(device))
+        if key not in self._dev:
+            up = lambda a: None if a is None else torch.as_tensor(a).to(device).contiguous()
+            t = (up(self.goal), up(self.packed()), up(self.n_obs))
+            st = capi.lg_plan_scenes()
+            st.S = self.S
+            st.goal, st.obs, st.n_obs = (None if x is None else x.data_ptr() for x in t)
+            self._dev[key] = (st, t)
+        return self._dev[key]
+
+    def save(self, path):
+        np.savez(path, **{k: getattr(self, k) for k in ("goal", "obs_c", "obs_r", "n_obs") if getattr(self, k) is not None})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as d:
+            bad = sorted(set(d.files) - {"goal", "obs_c", "obs_r", "n_obs"})
+            if bad:
+                raise ValueError(f"{path}: unknown scene array(s) {bad}; the arrays are goal, obs_c, obs_r, n_obs")
+            return cls(**{k: d[k] for k in d.files})
+
+
+def scenes_check(scenes, count):
+    """lg_plan_scenes_check on the host arrays' S, in its words: ValueError where S differs from the call's count."""
+    if scenes is not None and scenes.S != count:
+        raise ValueError(f"{SCENES_ERR}S = {scenes.S} differs from the call's count of plans or instances = {count}")
+
+
+RANDOM_SCENES_TRIES = 1000                          # rejections per scene before random_scenes gives up
+
+
+def random_scenes(S, seed, start, n_obs=(1, 3), centre_box=((0.0, 0.0), (2.0, 2.0)), radius=(0.1, 0.4),
+                  goal_box=((1.5, 1.5), (2.5, 2.5)), margin=0.05):
+    """S random scenes from numpy's default_rng(seed): per scene n in n_obs = (lo, hi) inclusive, a goal uniform in goal_box
+    ((x_lo, y_lo), (x_hi, y_hi)), n centres uniform in centre_box and radii uniform in radius = (lo, hi).  A draw is rejected
+    unless `start` -- (2,) or (S, 2) -- and the goal lie at least `margin` outside every obstacle, taken in float64 on the float32
+    values kept; after RANDOM_SCENES_TRIES rejections of one scene a ValueError names it."""
+    lo, hi = int(n_obs[0]), int(n_obs[1])
+    if S < 1 or not 0 <= lo <= hi <= capi.PLAN_MAX_OBS:
+        raise ValueError(f"S = {S} must be at least 1 and n_obs = {tuple(n_obs)} lie in 0..{capi.PLAN_MAX_OBS}, lo <= hi")
+    if not 0 <= radius[0] <= radius[1]:
+        raise ValueError(f"radius = {tuple(radius)}: 0 <= lo <= hi")
+    start = np.broadcast_to(np.asarray(start, np.float32).astype(np.float64), (S, 2))
+    rng = np.random.default_rng(int(seed))
+    cb, gb = np.asarray(centre_box, np.float64), np.asarray(goal_box, np.float64)
+    goal, c, r, cnt = np.zeros((S, 2), np.float32), np.zeros((S, hi, 2), np.float32), np.zeros((S, hi), np.float32), np.zeros(S, np.int32)
+    for s in range(S):
+        for _ in range(RANDOM_SCENES_TRIES):
+            n = int(rng.integers(lo, hi + 1))
+            g = rng.uniform(gb[0], gb[1]).astype(np.float32)
+            cs = rng.uniform(cb[0], cb[1], (n, 2)).astype(np.float32)
+            rs = rng.uniform(radius[0], radius[1], n).astype(np.float32)
+            far = lambda q: (np.linalg.norm(q[None, :] - cs.astype(np.float64), axis=1) >= rs.astype(np.float64) + margin).all()
+            if far(start[s]) and far(g.astype(np.float64)):
+                goal[s], c[s, :n], r[s, :n], cnt[s] = g, cs, rs, n
+                break
+        else:
+            raise ValueError(f"random_scenes: scene {s} was rejected {RANDOM_SCENES_TRIES} times: no draw keeps the start and the goal "
+                             f"{margin} outside every obstacle (n_obs={tuple(n_obs)}, radius={tuple(radius)}, centre_box={cb.tolist()})")
+    return Scenes(goal=goal, obs_c=c, obs_r=r, n_obs=cnt)
+
+
+def _scene_safe(pz, problem, scenes):
+    """actually_safe per plan: no node of pz (B, T, 2) float64 inside an obstacle of the plan's own scene."""
+    import torch
+    scenes_check(scenes, pz.shape[0])
+    c, r, live = (torch.as_tensor(a) for a in scenes.obstacles(problem))
+    if c.shape[1] == 0:
+        return torch.ones(pz.shape[0], dtype=torch.bool)
+    d = torch.linalg.vector_norm(pz[:, :, None, :] - c[:, None, :, :], dim=-1)
+    return ~((d < r[:, None, :]) & live[:, None, :]).any(dim=2).any(dim=1)
+
+
+
 class HipPlanScorer:
     """lg_plan_score on one problem.  model: a HipTubeModel / HipTubeTrainer of a one-shot horizon tube ('nn'), of a flat scalar
     tube ('nn_step'), or None for the analytic kinds.  calibration: a Calibration of kind 'horizon' (pick
@@ -304,8 +484,16 @@ class HipPlanScorer:
             self.offset = self.offset.to(self.device, torch.float32).contiguous()
         self._handle = getattr(self.model, "_tr", self.model).h if self.model is not None else None
 
-    def score(self, z0, v, e=None, v_prev=None, w0=None, want=("fw", "z", "w")):
-        """z0 (B, 2), v (B, N, 2); e (B, H_rev), v_prev (B, H_rev, 2), w0 (B) or None = zeros.  Returns device tensors: cost (B),
+    def _scenes(self, scenes, count):
+        """(entry suffix, trailing arguments) of a call with `scenes` (a Scenes or None): None calls the entry without scenes."""
+        if scenes is None:
+            return "", ()
+        scenes_check(scenes, count)
+        return "_scenes", (C.byref(scenes.to(self.device)[0]),)
+
+    def score(self, z0, v, e=None, v_prev=None, w0=None, want=("fw", "z", "w"), scenes=None):
+        """z0 (B, 2), v (B, N, 2); e (B, H_rev), v_prev (B, H_rev, 2), w0 (B) or None = zeros.  scenes: a Scenes of S = B, plan b
+        scored against its own goal and obstacles (lg_plan_score_scenes).  Returns device tensors: cost (B),
         min_clear (B), worst_node (B) int32, n_viol (B, 4) int32 [obstacle nodes, input steps, state nodes, tube nodes] and
         whatever of fw (B, N), z (B, N+1, 2), w (B, N+1) `want` names."""
         import torch
@@ -327,13 +515,15 @@ class HipPlanScorer:
         for k in want:
             out[k] = torch.empty(opt[k], device=dev)
         torch.cuda.set_device(dev)
-        rc = self.lib.lg_plan_score(self._handle, C.byref(self.struct), _ptr(z0), _ptr(v), _ptr(e), _ptr(v_prev), _ptr(w0), _ptr(self.offset),
-                                    int(self.level is not None), float(self.level if self.level is not None else 0.0), B,
-                                    _ptr(out["cost"]), _ptr(out["min_clear"]), _ptr(out["worst_node"]), _ptr(out["n_viol"]),
-                                    _ptr(out.get("fw")), _ptr(out.get("z")), _ptr(out.get("w")),
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        sfx, sargs = self._scenes(scenes, B)
+        rc = getattr(self.lib, "lg_plan_score" + sfx)(
+            self._handle, C.byref(self.struct), _ptr(z0), _ptr(v), _ptr(e), _ptr(v_prev), _ptr(w0), _ptr(self.offset),
+            int(self.level is not None), float(self.level if self.level is not None else 0.0), B,
+            _ptr(out["cost"]), _ptr(out["min_clear"]), _ptr(out["worst_node"]), _ptr(out["n_viol"]),
+            _ptr(out.get("fw")), _ptr(out.get("z")), _ptr(out.get("w")), *sargs,
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         if rc != 0:
-            raise self._err(f"lg_plan_score failed ({rc}): {self.lib.lg_last_error().decode()}")
+            raise self._err(f"lg_plan_score{sfx} failed ({rc}): {self.lib.lg_last_error().decode()}")
         self._keep = (z0, v, e, v_prev, w0)
         return out
 
@@ -369,9 +559,10 @@ def track(sim, z, v, x0=None, rom_dt=None, want=("x", "u")):
     return out
 
 
-def audit(score, track, problem):
+def audit(score, track, problem, scenes=None):
     """Did the tube hold?  score: HipPlanScorer.score's dict with 'w'; track: track()'s dict.  Plain Python numbers throughout, so
-    that json.dumps(..., allow_nan=False) takes the result as it is.
+    that json.dumps(..., allow_nan=False) takes the result as it is.  scenes: a Scenes of S = the plans (the one the plans were
+    scored with); actually_safe is then taken against each plan's own obstacles.
     coverage_by_node[k]: share of plans with w[k] >= w_true[k]; coverage: its mean (the reference script's "Total Success Rate");
     covered_plans: share covered at every node; predicted_safe: min_clear >= 0; actually_safe: no node of the realised path inside
     an obstacle (|pz_x - c_i| < r_i); table: the shares of (predicted, actual) in {safe, unsafe}^2."""
@@ -384,16 +575,23 @@ def audit(score, track, problem):
     cov = w >= wt
     pred = score["min_clear"].detach().cpu().double() >= 0
     act = torch.ones(B, dtype=torch.bool)
-    for c, r in zip(problem.obs_c, problem.obs_r):
-        d = torch.linalg.vector_norm(pz - torch.tensor(c, dtype=torch.float64), dim=-1)
-        act &= ~(d < float(r)).any(dim=1)
+    if scenes is not None:
+        act = _scene_safe(pz, problem, scenes)
+    else:
+        for c, r in zip(problem.obs_c, problem.obs_r):
+            d = torch.linalg.vector_norm(pz - torch.tensor(c, dtype=torch.float64), dim=-1)
+            act &= ~(d < float(r)).any(dim=1)
     share = lambda m: float(m.double().mean())
-    return {"plans": int(B), "nodes": int(w.shape[1]),
-            "coverage_by_node": [float(x) for x in cov.double().mean(dim=0)], "coverage": share(cov),
-            "covered_plans": share(cov.all(dim=1)), "predicted_safe": share(pred), "actually_safe": share(act),
-            "table": {"safe_safe": share(pred & act), "safe_unsafe": share(pred & ~act), "unsafe_safe": share(~pred & act),
-                      "unsafe_unsafe": share(~pred & ~act)},
-            "w_true_mean": float(wt.mean()), "w_true_max": float(wt.max())}
+    res = {"plans": int(B), "nodes": int(w.shape[1]),
+           "coverage_by_node": [float(x) for x in cov.double().mean(dim=0)], "coverage": share(cov),
+           "covered_plans": share(cov.all(dim=1)), "predicted_safe": share(pred), "actually_safe": share(act),
+           "table": {"safe_safe": share(pred & act), "safe_unsafe": share(pred & ~act), "unsafe_safe": share(~pred & act),
+                     "unsafe_unsafe": share(~pred & ~act)},
+           "w_true_mean": float(wt.mean()), "w_true_max": float(wt.max())}
+    if scenes is not None:                              # the audit per scene: plan b lives in scene b
+        res["by_plan"] = {"covered": [bool(x) for x in cov.all(dim=1)], "predicted_safe": [bool(x) for x in pred],
+                          "actually_safe": [bool(x) for x in act]}
+    return res
 
 
 # ---------------------------------------------------------------- the sampling planner
@@ -453,12 +651,13 @@ class HipMppiPlanner:
     """lg_plan_mppi on one problem for P instances at once, built on a HipPlanScorer: the handle, offset, level and envelope checks
     are the scorer's.  The arguments after cfg are HipPlanScorer's."""
 
-    def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None, trajectory=False):
+    def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None, trajectory=False, scenes=None):
         cfg.check()
         self.scorer = HipPlanScorer(model, problem, calibration=calibration, level=level, coverage=coverage, device=device,
                                     trajectory=trajectory)
         self.problem, self.cfg, self.device, self.lib = problem, cfg, self.scorer.device, self.scorer.lib
         self._err = self.scorer._err
+        self.scenes = scenes                            # a Scenes of S = the P of every call: instance p plans in scene p
 
     def _fail(self, name, rc):
         raise self._err(f"{name} failed ({rc}): {self.lib.lg_last_error().decode()}")
@@ -512,20 +711,27 @@ class HipMppiPlanner:
         """lg_plan_mppi_step on a state(): what & 1 the score (writes J and the optional outputs), what & 2 the update (reads J;
         writes vbar, best_J, best_v, n_bad and hist_row (P, 2) where given)."""
         sc = self.scorer
-        rc = self.lib.lg_plan_mppi_step(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), int(it), int(what), int(bool(reset)),
-                                        _ptr(st["z0"]), _ptr(st["e"]), _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset),
-                                        int(sc.level is not None), float(sc.level if sc.level is not None else 0.0), st["P"],
-                                        _ptr(st["vbar"]), _ptr(st["J"]), _ptr(st.get("cost")), _ptr(st.get("min_clear")), _ptr(st.get("pen")),
-                                        _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]), self._stream())
+        sfx, sargs = sc._scenes(self.scenes, st["P"])
+        rc = getattr(self.lib, "lg_plan_mppi_step" + sfx)(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), int(it), int(what), int(bool(reset)),
+            _ptr(st["z0"]), _ptr(st["e"]), _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset),
+            int(sc.level is not None), float(sc.level if sc.level is not None else 0.0), st["P"],
+            _ptr(st["vbar"]), _ptr(st["J"]), _ptr(st.get("cost")), _ptr(st.get("min_clear")), _ptr(st.get("pen")),
+            _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]), *sargs, self._stream())
         if rc != 0:
-            self._fail("lg_plan_mppi_step", rc)
+            self._fail("lg_plan_mppi_step" + sfx, rc)
         return st
 
     def warm_start(self, z0):
-        """The `interpolate` warm start (TT:415-432) from every instance's z0 to the goal, clipped to the input bounds: (P, N, 2)."""
+        """The `interpolate` warm start (TT:415-432) from every instance's z0 to the goal -- with scenes, to its own scene's goal --,
+        clipped to the input bounds: (P, N, 2)."""
         p = self.problem
         z0 = np.asarray(z0, np.float64).reshape(-1, 2)
-        z = np.linspace(0, 1, p.N + 1)[None, :, None] * (np.asarray(p.goal, np.float64) - z0)[:, None, :] + z0[:, None, :]
+        goal = np.asarray(p.goal, np.float64)
+        if getattr(self, "scenes", None) is not None and self.scenes.goal is not None:
+            scenes_check(self.scenes, z0.shape[0])
+            goal = self.scenes.goals(p)
+        z = np.linspace(0, 1, p.N + 1)[None, :, None] * (goal - z0)[:, None, :] + z0[:, None, :]
         v = np.diff(z, axis=1) / p.dt                                    # warm_start's arithmetic, every instance at once
         return np.clip(v, np.asarray(p.rom_v_min, np.float64), np.asarray(p.rom_v_max, np.float64)).astype(np.float32)
 
@@ -547,16 +753,18 @@ class HipMppiPlanner:
         st = self.state(z0, v_init, e, v_prev, w0)
         hist = torch.empty(iters, st["P"], 2, device=self.device)
         sc = self.scorer
-        rc = self.lib.lg_plan_mppi(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), _ptr(st["z0"]), _ptr(st["e"]),
-                                   _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset), int(sc.level is not None),
-                                   float(sc.level if sc.level is not None else 0.0), st["P"], _ptr(st["vbar"]), _ptr(st["J"]),
-                                   _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist), _ptr(st["n_bad"]), self._stream())
+        sfx, sargs = sc._scenes(self.scenes, st["P"])
+        rc = getattr(self.lib, "lg_plan_mppi" + sfx)(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), _ptr(st["z0"]), _ptr(st["e"]),
+            _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset), int(sc.level is not None),
+            float(sc.level if sc.level is not None else 0.0), st["P"], _ptr(st["vbar"]), _ptr(st["J"]),
+            _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist), _ptr(st["n_bad"]), *sargs, self._stream())
         if rc != 0:
-            self._fail("lg_plan_mppi", rc)
+            self._fail("lg_plan_mppi" + sfx, rc)
         want = ("z", "w")
         return {"v": st["vbar"], "best_v": st["best_v"], "best_J": st["best_J"], "hist": hist, "n_bad": st["n_bad"],
-                "score": sc.score(st["z0"], st["vbar"], st["e"], st["v_prev"], st["w0"], want=want),
-                "best_score": sc.score(st["z0"], st["best_v"], st["e"], st["v_prev"], st["w0"], want=want)}
+                "score": sc.score(st["z0"], st["vbar"], st["e"], st["v_prev"], st["w0"], want=want, scenes=self.scenes),
+                "best_score": sc.score(st["z0"], st["best_v"], st["e"], st["v_prev"], st["w0"], want=want, scenes=self.scenes)}
 
 
 # ---------------------------------------------------------------- the gradient planner
@@ -610,13 +818,14 @@ class HipGradPlanner:
     _stream = HipMppiPlanner._stream
     needs_gradient = True
 
-    def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None):
+    def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None, scenes=None):
         cfg.check()
         if problem.tube_kind == "nn_step":
             raise ValueError(NO_GRADIENT)
         self.scorer = HipPlanScorer(model, problem, calibration=calibration, level=level, coverage=coverage, device=device)
         self.problem, self.cfg, self.device, self.lib = problem, cfg, self.scorer.device, self.scorer.lib
         self._err = self.scorer._err
+        self.scenes = scenes                            # a Scenes of S = the B of every call: plan b descends in scene b
 
     def state(self, z0, v, e=None, v_prev=None, w0=None, want=()):
         """The device arrays of a run: z0 (P, 2), e, v_prev, w0 (None = zeros), the plans v (P, N, 2) (copied), J (P), the Adam
@@ -654,11 +863,13 @@ class HipGradPlanner:
         (B, 3) `want` names, as device tensors."""
         st = self.state(z0, v, e, v_prev, w0, want=("grad",) + tuple(k for k in want if k != "grad"))
         sc = self.scorer
-        rc = self.lib.lg_plan_grad(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), _ptr(st["z0"]), _ptr(st["v"]),
-                                   *self._common(st), _ptr(st["J"]), _ptr(st["grad"]), _ptr(st.get("cost")), _ptr(st.get("min_clear")),
-                                   _ptr(st.get("pen")), self._stream())
+        sfx, sargs = sc._scenes(self.scenes, st["P"])
+        rc = getattr(self.lib, "lg_plan_grad" + sfx)(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), _ptr(st["z0"]), _ptr(st["v"]),
+            *self._common(st), _ptr(st["J"]), _ptr(st["grad"]), _ptr(st.get("cost")), _ptr(st.get("min_clear")),
+            _ptr(st.get("pen")), *sargs, self._stream())
         if rc != 0:
-            self._fail("lg_plan_grad", rc)
+            self._fail("lg_plan_grad" + sfx, rc)
         self._keep = st
         return {k: st[k] for k in ("J", "grad", "cost", "min_clear", "pen") if k in st}
 
@@ -666,12 +877,14 @@ class HipGradPlanner:
         """lg_plan_descend_step on a state(): what = 1 evaluates (J, the optional outputs, the elite, hist_row (P, 2)); what = 3
         also steps v, m and s in place."""
         sc = self.scorer
-        rc = self.lib.lg_plan_descend_step(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), int(it), int(what), int(bool(reset)),
-                                           _ptr(st["z0"]), *self._common(st), _ptr(st["v"]), _ptr(st["J"]), _ptr(st.get("grad")),
-                                           _ptr(st.get("cost")), _ptr(st.get("min_clear")), _ptr(st.get("pen")), _ptr(st["m"]), _ptr(st["s"]),
-                                           _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]), self._stream())
+        sfx, sargs = sc._scenes(self.scenes, st["P"])
+        rc = getattr(self.lib, "lg_plan_descend_step" + sfx)(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), int(it), int(what), int(bool(reset)),
+            _ptr(st["z0"]), *self._common(st), _ptr(st["v"]), _ptr(st["J"]), _ptr(st.get("grad")),
+            _ptr(st.get("cost")), _ptr(st.get("min_clear")), _ptr(st.get("pen")), _ptr(st["m"]), _ptr(st["s"]),
+            _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]), *sargs, self._stream())
         if rc != 0:
-            self._fail("lg_plan_descend_step", rc)
+            self._fail("lg_plan_descend_step" + sfx, rc)
         return st
 
     def plan(self, z0, v_init=None, e=None, v_prev=None, w0=None, iters=None):
@@ -691,15 +904,17 @@ class HipGradPlanner:
         st = self.state(z0, v_init, e, v_prev, w0)
         hist = torch.empty(iters + 1, st["P"], 2, device=self.device)
         sc = self.scorer
-        rc = self.lib.lg_plan_descend(sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), _ptr(st["z0"]), *self._common(st),
-                                      _ptr(st["v"]), _ptr(st["J"]), _ptr(st["m"]), _ptr(st["s"]), _ptr(st["best_J"]), _ptr(st["best_v"]),
-                                      _ptr(hist), _ptr(st["n_bad"]), self._stream())
+        sfx, sargs = sc._scenes(self.scenes, st["P"])
+        rc = getattr(self.lib, "lg_plan_descend" + sfx)(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), _ptr(st["z0"]), *self._common(st),
+            _ptr(st["v"]), _ptr(st["J"]), _ptr(st["m"]), _ptr(st["s"]), _ptr(st["best_J"]), _ptr(st["best_v"]),
+            _ptr(hist), _ptr(st["n_bad"]), *sargs, self._stream())
         if rc != 0:
-            self._fail("lg_plan_descend", rc)
+            self._fail("lg_plan_descend" + sfx, rc)
         want = ("z", "w")
         return {"v": st["v"], "best_v": st["best_v"], "best_J": st["best_J"], "hist": hist, "n_bad": st["n_bad"],
-                "score": sc.score(st["z0"], st["v"], st["e"], st["v_prev"], st["w0"], want=want),
-                "best_score": sc.score(st["z0"], st["best_v"], st["e"], st["v_prev"], st["w0"], want=want)}
+                "score": sc.score(st["z0"], st["v"], st["e"], st["v_prev"], st["w0"], want=want, scenes=self.scenes),
+                "best_score": sc.score(st["z0"], st["best_v"], st["e"], st["v_prev"], st["w0"], want=want, scenes=self.scenes)}
 
 
 class ChainedPlanner:
@@ -712,8 +927,10 @@ class ChainedPlanner:
             raise ValueError("the two planners of a chain must share one problem")
         if getattr(first.problem, "tube_kind", None) == "nn_step" and any(getattr(pln, "needs_gradient", False) for pln in (first, second)):
             raise ValueError(NO_GRADIENT)
+        if getattr(first, "scenes", None) is not getattr(second, "scenes", None):
+            raise ValueError("the two planners of a chain must carry the same scenes")
         self.first, self.second = first, second
-        self.problem, self.device = first.problem, first.device
+        self.problem, self.device, self.scenes = first.problem, first.device, getattr(first, "scenes", None)
 
     def plan(self, z0, v_init=None, e=None, v_prev=None, w0=None, iters=None):
         """`iters` goes to `first` (closed_loop's iters_first); `second` always runs its own."""
@@ -791,8 +1008,9 @@ def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=Fa
     return out
 
 
-def audit_closed_loop(result, problem, goal_tol=0.1):
-    """Did the tube hold in closed loop?  Plain Python numbers (strict JSON).  coverage_by_step[k]: share of robots with
+def audit_closed_loop(result, problem, goal_tol=0.1, scenes=None):
+    """Did the tube hold in closed loop?  scenes: a Scenes of S = the robots; actually_safe and reached_goal are then taken against
+    each robot's own obstacles and goal.  Plain Python numbers (strict JSON).  coverage_by_step[k]: share of robots with
     w_k >= |z_k - pz_x_k|; coverage: its mean; covered_robots: share covered at every step; actually_safe: share whose realised path
     pz_x enters no obstacle; predicted_safe: share whose plans in force all had min_clear >= 0; reached_goal: share whose ROM path
     ends within goal_tol of the goal; goal_distance_mean: the mean of that distance."""
@@ -802,12 +1020,21 @@ def audit_closed_loop(result, problem, goal_tol=0.1):
     err = torch.linalg.vector_norm(z - pz, dim=-1)
     cov = w >= err
     act = torch.ones(z.shape[0], dtype=torch.bool)
-    for c, r in zip(problem.obs_c, problem.obs_r):
-        act &= ~(torch.linalg.vector_norm(pz - torch.tensor(c, dtype=torch.float64), dim=-1) < float(r)).any(dim=1)
+    goal = torch.tensor(problem.goal, dtype=torch.float64)
+    if scenes is not None:
+        act, goal = _scene_safe(pz, problem, scenes), torch.as_tensor(scenes.goals(problem))
+    else:
+        for c, r in zip(problem.obs_c, problem.obs_r):
+            act &= ~(torch.linalg.vector_norm(pz - torch.tensor(c, dtype=torch.float64), dim=-1) < float(r)).any(dim=1)
     pred = (f64(result["min_clear"]) >= 0).all(dim=1)
-    dist = torch.linalg.vector_norm(z[:, -1] - torch.tensor(problem.goal, dtype=torch.float64), dim=-1)
+    dist = torch.linalg.vector_norm(z[:, -1] - goal, dim=-1)
     share = lambda m: float(m.double().mean())
-    return {"robots": int(z.shape[0]), "steps": int(z.shape[1] - 1), "coverage_by_step": [float(v) for v in cov.double().mean(dim=0)],
-            "coverage": share(cov), "covered_robots": share(cov.all(dim=1)), "actually_safe": share(act), "predicted_safe": share(pred),
-            "goal_tol": float(goal_tol), "reached_goal": share(dist <= goal_tol), "goal_distance_mean": float(dist.mean()),
-            "error_mean": float(err.mean()), "error_max": float(err.max())}
+    res = {"robots": int(z.shape[0]), "steps": int(z.shape[1] - 1), "coverage_by_step": [float(v) for v in cov.double().mean(dim=0)],
+           "coverage": share(cov), "covered_robots": share(cov.all(dim=1)), "actually_safe": share(act), "predicted_safe": share(pred),
+           "goal_tol": float(goal_tol), "reached_goal": share(dist <= goal_tol), "goal_distance_mean": float(dist.mean()),
+           "error_mean": float(err.mean()), "error_max": float(err.max())}
+    if scenes is not None:                              # the audit per scene: robot p lives in scene p
+        res["by_robot"] = {"covered": [bool(x) for x in cov.all(dim=1)], "predicted_safe": [bool(x) for x in pred],
+                           "actually_safe": [bool(x) for x in act], "reached_goal": [bool(x) for x in dist <= goal_tol],
+                           "goal_distance": [float(x) for x in dist]}
+    return res

@@ -204,10 +204,16 @@ def track_env(env, policy, v, z0, H_rev=0, want=(), allow_fast=False):
 
 
 # ---------------------------------------------------------------- audit
-def audit_env(score, trk, problem):
+def _completed_scenes(scenes, B, idx):
+    from .plan import scenes_check
+    scenes_check(scenes, B)
+    return scenes.take(idx.numpy())
+
+
+def audit_env(score, trk, problem, scenes=None):
     """plan.audit over the completed plans, plus completed / terminated (robots that reset: fell or timed out) and
     covered_plans_of_all, in which a robot that did not complete counts as not covered.  "plans" counts all of them.  Strict JSON;
-    with no completed plan the shares are None."""
+    with no completed plan the shares are None.  scenes: a plan.Scenes of S = all the plans; the completed ones keep their own."""
     import torch
     done = trk["completed"].detach().cpu().bool()
     B, n = int(done.numel()), int(done.sum())
@@ -219,6 +225,7 @@ def audit_env(score, trk, problem):
     idx = done.nonzero().flatten()
     pick = lambda t: t.detach().cpu()[idx]
     res = audit({"w": pick(score["w"]), "min_clear": pick(score["min_clear"])},
-                {"w_true": pick(trk["w_true"]), "pz_x": pick(trk["pz_x"])}, problem)
+                {"w_true": pick(trk["w_true"]), "pz_x": pick(trk["pz_x"])}, problem,
+                scenes=None if scenes is None else _completed_scenes(scenes, B, idx))
     covered = (pick(score["w"]).double() >= pick(trk["w_true"]).double()).all(dim=1)
     return {**res, **head, "covered_plans_of_all": float(covered.sum()) / B}
