@@ -116,8 +116,8 @@ def minibatch_loss(ac, b, clip_param=0.2, value_loss_coef=1.0, entropy_coef=0.01
         kl = torch.sum(torch.log(sigma / b["sigma"] + 1.e-5)
                        + (torch.square(b["sigma"]) + torch.square(b["mu"] - mu)) / (2.0 * torch.square(sigma)) - 0.5, axis=-1)
         kl_mean = torch.mean(kl)
-    ratio = torch.exp(logp - torch.squeeze(b["log_prob"]))
-    adv = torch.squeeze(b["advantages"])
+    ratio = torch.exp(logp - torch.squeeze(b["log_prob"], -1))      # squeeze(-1): a bare squeeze also drops an env axis of one
+    adv = torch.squeeze(b["advantages"], -1)
     surrogate_loss = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - clip_param, 1.0 + clip_param)).mean()
     if use_clipped_value_loss:
         value_clipped = b["values"] + (value - b["values"]).clamp(-clip_param, clip_param)

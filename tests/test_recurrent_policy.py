@@ -1,7 +1,11 @@
 """rsl_rl's ActorCriticRecurrent (runner.policy_class_name = 'ActorCritic' | 'ActorCriticRecurrent', policy.rnn_*) on the HIP
 learner: config parsing (host only), then on the GPU parameters / initialisation, two rollouts, one minibatch's gradients, a full
-update, deterministic mode, checkpoints, the LSTM policy export and the refusals -- against tests/recurrent_ref.py (recalled
-rsl_rl semantics, see its docstring)."""
+update (also at a multi-tile shape with a privileged critic), deterministic mode, checkpoints, the LSTM policy export and the
+refusals -- against tests/recurrent_ref.py (recalled rsl_rl semantics, see its docstring).
+
+The numbers of the LSTM kernels themselves -- every row-tile shape, hidden size, dones pattern and the privileged critic, against
+float64 and tensor by tensor -- are in tests/test_hip_recurrent.py (cases and references: tests/recurrent_loss_ref.py; the CPU
+conditions on them: tests/test_recurrent_loss_host.py)."""
 import ctypes
 import os
 
@@ -91,27 +95,29 @@ def test_lstm_export_surface_matches_the_module(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
-def _make(N, O, A, T, H=64, policy=POLICY, alg=ALG, seed=3):
+def _make(N, O, A, T, H=64, policy=POLICY, alg=ALG, seed=3, critic_obs=None):
     from legged_gym_dev_amd.rl.ppo import HipPPO
     from tests.recurrent_ref import ActorCriticRecurrent
     torch.manual_seed(seed)
-    hip = HipPPO(N, O, None, A, dict(policy, rnn_hidden_size=H), alg, T, device="cuda:0", seed=seed,
+    hip = HipPPO(N, O, critic_obs, A, dict(policy, rnn_hidden_size=H), alg, T, device="cuda:0", seed=seed,
                  policy_class_name="ActorCriticRecurrent")
     torch.manual_seed(seed)
-    ac = ActorCriticRecurrent(O, O, A, policy["actor_hidden_dims"], policy["critic_hidden_dims"], policy["activation"],
+    ac = ActorCriticRecurrent(O, critic_obs or O, A, policy["actor_hidden_dims"], policy["critic_hidden_dims"], policy["activation"],
                               rnn_hidden_size=H, init_noise_std=policy["init_noise_std"]).cuda()
     return hip, ac
 
 
-def _rollout(hip, ac, T, N, O, A, g, dones_at):
-    """One rollout with injected noise on both sides; dones_at(t) -> uint8 (N,).  Returns the reference's per-step records."""
+def _rollout(hip, ac, T, N, O, A, g, dones_at, critic_obs=None):
+    """One rollout with injected noise on both sides; dones_at(t) -> uint8 (N,).  critic_obs: width of the privileged critic
+    observations, drawn on their own (None: the critic sees obs).  Returns the reference's per-step records."""
     hip.inject_noise(1)
     rec = []
     for t in range(T):
         obs = torch.randn(N, O, device="cuda", generator=g)
         noise = torch.randn(N, A, device="cuda", generator=g)
+        cobs = torch.randn(N, critic_obs, device="cuda", generator=g) if critic_obs else obs
         hip.t["noise"].copy_(noise)
-        hip.act(obs)
+        hip.act(obs, cobs)
         with torch.no_grad():
             hs = ac.get_hidden_states()                    # the transition keeps the state before the step (zero at the start)
             z = torch.zeros(N, hip.H, device="cuda")
@@ -120,14 +126,14 @@ def _rollout(hip, ac, T, N, O, A, g, dones_at):
             mu = ac.action_mean
             act = mu + ac.std * noise
             lp = ac.get_actions_log_prob(act)
-            v = ac.evaluate(obs).squeeze(-1)
+            v = ac.evaluate(cobs).squeeze(-1)
         rew = torch.randn(N, device="cuda", generator=g)
         dones = dones_at(t)
         hip.process_env_step(rew, dones, {})
         with torch.no_grad():
             ac.reset(dones.bool())
         rec.append(dict(obs=obs, act=act, mu=mu, lp=lp, v=v, saved=saved))
-    last = torch.randn(N, O, device="cuda", generator=g)
+    last = torch.randn(N, critic_obs or O, device="cuda", generator=g)
     rec[-1]["h_c_before_returns"] = hip.t["h_c"].clone()   # the critic state after the last step, before compute_returns
     hip.compute_returns(last)
     with torch.no_grad():
@@ -153,10 +159,10 @@ def _check_rollout(hip, rec):
             torch.testing.assert_close(hip.t[k][t], s, rtol=2e-5, atol=2e-5)
 
 
-def _storage(hip):
+def _storage(hip, critic_obs=None):
     st = {k: hip.t[k].clone() for k in ("obs", "dones", "actions", "values", "advantages", "returns", "log_prob", "mu",
                                         "saved_h_a", "saved_c_a", "saved_h_c", "saved_c_c", "sigma")}
-    st["critic_obs"] = st["obs"]
+    st["critic_obs"] = hip.t["critic_obs"].clone() if critic_obs else st["obs"]
     return st
 
 
@@ -231,21 +237,24 @@ def test_minibatch_gradients_match_autograd_through_split_and_pad(O, H):
 
 
 @pytest.mark.gpu
-def test_full_update_tracks_the_restatement():
+@pytest.mark.parametrize("N,nmb,H,OC", [(64, 4, 64, None), (130, 2, 96, 65)], ids=["one_tile", "multi_tile_privileged"])
+def test_full_update_tracks_the_restatement(N, nmb, H, OC):
+    """Five epochs over every minibatch.  The second shape has 65 envs per minibatch (a second row tile of one row), H = 96 and
+    critic observations of their own, so the gather-ahead double buffer runs with mb_critic_obs != mb_obs on the recurrent path."""
     from tests import recurrent_ref as rr
-    N, O, A, T = 64, 48, 12, 8
-    hip, ac = _make(N, O, A, T)
+    O, A, T = 48, 12, 8
+    hip, ac = _make(N, O, A, T, H=H, alg=dict(ALG, num_mini_batches=nmb), critic_obs=OC)
     g = torch.Generator(device="cuda").manual_seed(4)
-    _rollout(hip, ac, T, N, O, A, g, _dones(N, T, g))
-    st = _storage(hip)
+    _rollout(hip, ac, T, N, O, A, g, _dones(N, T, g), critic_obs=OC)
+    st = _storage(hip, OC)
     p0 = hip.t["params"][: hip.num_params].clone()
     vl, sl = hip.update()
     torch.cuda.synchronize()
     opt = torch.optim.Adam(ac.parameters(), lr=ALG["learning_rate"])
     lr = ALG["learning_rate"]
     for ep in range(5):
-        for mb in range(4):
-            loss, kl, _, _ = rr.minibatch_loss(ac, rr.recurrent_minibatch(st, mb, 4))
+        for mb in range(nmb):
+            loss, kl, _, _ = rr.minibatch_loss(ac, rr.recurrent_minibatch(st, mb, nmb))
             if kl > 0.02:
                 lr = max(1e-5, lr / 1.5)
             elif 0.0 < kl < 0.005:
