@@ -37,12 +37,19 @@ __device__ __forceinline__ void xcd_tile(int lin, int inner, int outer, int &o, 
 
 // Prologue of the GEMM kernels: the workgroup's problem z = blockIdx.z and its M x N output in BM x BN tiles.  The launch grid is
 // sized for the largest problem of the launch: false for the workgroups past this problem's tiles.
+// A kernel that remaps its workgroups over this problem's own tiles (xcd_tile on tiles_n x tiles_m) tests the raw blockIdx.x, as
+// gemm_tiles does.  One that remaps over the whole GRID (k_gemm_dw_t: the grid's tiles x its reduction slices) takes gemm_problem and
+// tests the REMAPPED tile: that map is a bijection on the grid only, not on the smaller problem's share of it.
 struct GemmTiles { int z, M, N, K, tiles_n, tiles_m; };
 template <int BM, int BN>
-__device__ __forceinline__ bool gemm_tiles(const GemmArgs &g, GemmTiles &t) {
+__device__ __forceinline__ void gemm_problem(const GemmArgs &g, GemmTiles &t) {
     t.z = blockIdx.z;
     t.M = g.M[t.z]; t.N = g.N[t.z]; t.K = g.K[t.z];
     t.tiles_n = (t.N + BN - 1) / BN; t.tiles_m = (t.M + BM - 1) / BM;
+}
+template <int BM, int BN>
+__device__ __forceinline__ bool gemm_tiles(const GemmArgs &g, GemmTiles &t) {
+    gemm_problem<BM, BN>(g, t);
     return (int)blockIdx.x < t.tiles_n * t.tiles_m;
 }
 // reduction range of slice `slice` when the launch splits K into gridDim.y slices of whole k-tiles; false when it is empty
@@ -639,10 +646,11 @@ __global__ void __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 4 : 2) k_gemm
     constexpr int APL = plt_plane_bytes<BM>(), BPL = plt_plane_bytes<BN>();
     constexpr int NVA = BM * BK / 4 / NT, NVB = BN * BK / 4 / NT;
     GemmTiles t;
-    if (!gemm_tiles<BM, BN>(g, t)) return;
+    gemm_problem<BM, BN>(g, t);
     const int z = t.z, M = t.M, N = t.N;
     int slice, tile;                                               // the output tiles of one reduction slice share its rows: one XCD
     xcd_tile((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)gridDim.x, (int)gridDim.y, slice, tile);
+    if (tile >= t.tiles_n * t.tiles_m) return;                     // gridDim.x = the tiles of the launch's LARGEST problem
     const int m0 = (tile / t.tiles_n) * BM, n0 = (tile % t.tiles_n) * BN;
     int k_begin, k_end;
     if (!k_slice(t.K, slice, k_begin, k_end)) return;
@@ -741,6 +749,9 @@ extern "C" void ppok_debug_set_x6(int v) { g_gemm_x6 = v != 0; }
 // Launch shape of every launcher: the largest problem of the launch, its 64 x 64 and 128 x 128 tile counts, and whether it takes
 // the 128 x 128 tiles -- when those alone (times the reduction slices) fill the chip and both dimensions exceed one small tile.
 struct GemmShape { int maxM, maxN; unsigned small_tiles, big_tiles; bool big; };
+// What a launcher launched: the kernel (GK_*: the codes ppok_debug_gemm_args reports) and the reduction slices of the launch.
+enum { GK_GEMM_SMALL = 1, GK_GEMM_BIG, GK_PL1_SMALL, GK_PL1_BIG, GK_PL2_SMALL, GK_PL2_BIG, GK_GLDS, GK_DW_SMALL, GK_DW_BIG, GK_REF };
+struct GemmLaunch { int kernel, slices; };
 static GemmShape gemm_shape(const GemmArgs &g, int nz, int splits) {
     GemmShape sh{0, 0, 0, 0, false};
     for (int z = 0; z < nz; ++z) { sh.maxM = g.M[z] > sh.maxM ? g.M[z] : sh.maxM; sh.maxN = g.N[z] > sh.maxN ? g.N[z] : sh.maxN; }
@@ -765,42 +776,45 @@ static bool planes_ok(const GemmArgs &g, int nz, int (GemmArgs::*chunked)[2]) {
 
 // forward (EPI 0) and input gradient (EPI 1) with B = pre-split weight planes: PL 1 reduction-contiguous, PL 2 read along their rows
 template <int EPI, bool B_RC = true, int PL = 1>
-static void launch_gemm_pl(const GemmArgs &g, int nz, hipStream_t s) {
+static GemmLaunch launch_gemm_pl(const GemmArgs &g, int nz, hipStream_t s) {
     const GemmShape sh = gemm_shape(g, nz, 1);
     // LDS-DMA forward (ppo_gemm_glds.h): 40 KB workgroups, up to four per CU -- update -2.6 % (profiles/r04_ab.txt)
     if (EPI == 0 && sh.maxM > 64 && glds_ok(g, nz)) {
         dim3 grid((unsigned)(((sh.maxM + GLDS_BM - 1) / GLDS_BM) * (sh.maxN / GLDS_BN)), 1, nz);
         hipLaunchKernelGGL(k_gemm_glds, grid, dim3(256), 0, s, g);
-        return;
+        return {GK_GLDS, 1};
     }
     if (sh.big) hipLaunchKernelGGL((k_gemm<true, B_RC, EPI, 2, 1, 2, 4, PL>), dim3(sh.big_tiles, 1, nz), dim3(512), 0, s, g);
     else hipLaunchKernelGGL((k_gemm<true, B_RC, EPI, 1, 1, 2, 2, PL>), dim3(sh.small_tiles, 1, nz), dim3(256), 0, s, g);
+    return {(PL == 1 ? GK_PL1_SMALL : GK_PL2_SMALL) + (sh.big ? 1 : 0), 1};
 }
 
 // fp32 operands in memory, split-bf16: 128x128 tiles on 8 waves (2x4, each 64x32); small problems (rollout forward on 4096 rows,
 // heads) use 64x64 tiles on 4 waves to fill more CUs
 template <bool A_RC, bool B_RC, int EPI>
-static void launch_gemm(const GemmArgs &g, int nz, hipStream_t s) {
+static GemmLaunch launch_gemm(const GemmArgs &g, int nz, hipStream_t s) {
     const GemmShape sh = gemm_shape(g, nz, 1);
     if (sh.big) hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 2, 1, 2, 4>), dim3(sh.big_tiles, 1, nz), dim3(512), 0, s, g);
     else hipLaunchKernelGGL((k_gemm<A_RC, B_RC, EPI, 1, 1>), dim3(sh.small_tiles, 1, nz), dim3(256), 0, s, g);
+    return {sh.big ? GK_GEMM_BIG : GK_GEMM_SMALL, 1};
 }
 template <bool A_RC, bool B_RC, int EPI>
-static void launch_gemm_ref(const GemmArgs &g, int nz, int splits, hipStream_t s) {
+static GemmLaunch launch_gemm_ref(const GemmArgs &g, int nz, int splits, hipStream_t s) {
     hipLaunchKernelGGL((k_gemm_ref<A_RC, B_RC, EPI>), dim3(gemm_shape(g, nz, splits).small_tiles, splits, nz), dim3(256), 0, s, g);
+    return {GK_REF, splits};
 }
 
 // weight gradients over `splits` reduction slices: k_gemm_dw_t on the split-bf16 path, the fp32-input reference otherwise
-static void launch_gemm_dw(const GemmArgs &g, int nz, int splits, hipStream_t s) {
+static GemmLaunch launch_gemm_dw(const GemmArgs &g, int nz, int splits, hipStream_t s) {
     if (!g_gemm_x6) {                          // the reference's store guard is its N: compute the true width only
         GemmArgs gt = g;
         for (int z = 0; z < nz; ++z) if (g.nstore[z]) gt.N[z] = g.nstore[z];
-        launch_gemm_ref<false, false, 2>(gt, nz, splits, s);
-        return;
+        return launch_gemm_ref<false, false, 2>(gt, nz, splits, s);
     }
     const GemmShape sh = gemm_shape(g, nz, splits);
     if (sh.big) hipLaunchKernelGGL((k_gemm_dw_t<2, 1, 2, 4>), dim3(sh.big_tiles, splits, nz), dim3(512), 0, s, g);
     else hipLaunchKernelGGL((k_gemm_dw_t<1, 1, 2, 2>), dim3(sh.small_tiles, splits, nz), dim3(256), 0, s, g);
+    return {sh.big ? GK_DW_BIG : GK_DW_SMALL, splits};
 }
 // Reduction slices of a weight-gradient launch: about 384 workgroups per net over (output tiles x slices), counted with the tile
 // each problem alone would get (128 x 128 when both dimensions exceed 64) -- swept 64..384 inside the update (side stream beside
@@ -827,22 +841,37 @@ static int dw_splits(const GemmArgs &g, int nz) {
 // g->Bpl (optional): bf16 planes of W [n_out][n_in] kept by the optimiser step; the caller passes both B (fp32 W) and Bpl,
 // whichever path is eligible is taken.  Forward: the planes are the reduction-contiguous operand.  Input gradient: the
 // SAME planes, reduced over their rows through the transposing LDS read (no second image of W^T to keep current).
-extern "C" void ppok_gemm_fwd(const GemmArgs *g, int nz, hipStream_t s) {
+static GemmLaunch gemm_fwd(const GemmArgs *g, int nz, hipStream_t s) {
     GemmArgs gp = *g;                          // the plane path's view of the reduction dimension (padded first layer, ppo_device.h)
     for (int z = 0; z < nz; ++z) {
         if (g->Kpl[z]) gp.K[z] = g->Kpl[z];
         if (g->ldbpl[z]) gp.ldb[z] = g->ldbpl[z];
     }
-    if (planes_ok(gp, nz, &GemmArgs::K)) launch_gemm_pl<0>(gp, nz, s);
-    else if (g_gemm_x6) launch_gemm<true, true, 0>(*g, nz, s);
-    else launch_gemm_ref<true, true, 0>(*g, nz, 1, s);
+    if (planes_ok(gp, nz, &GemmArgs::K)) return launch_gemm_pl<0>(gp, nz, s);
+    if (g_gemm_x6) return launch_gemm<true, true, 0>(*g, nz, s);
+    return launch_gemm_ref<true, true, 0>(*g, nz, 1, s);
 }
-extern "C" void ppok_gemm_dx(const GemmArgs *g, int nz, hipStream_t s) {
-    if (planes_ok(*g, nz, &GemmArgs::N)) launch_gemm_pl<1, false, 2>(*g, nz, s);
-    else if (g_gemm_x6) launch_gemm<true, false, 1>(*g, nz, s);
-    else launch_gemm_ref<true, false, 1>(*g, nz, 1, s);
+static GemmLaunch gemm_dx(const GemmArgs *g, int nz, hipStream_t s) {
+    if (planes_ok(*g, nz, &GemmArgs::N)) return launch_gemm_pl<1, false, 2>(*g, nz, s);
+    if (g_gemm_x6) return launch_gemm<true, false, 1>(*g, nz, s);
+    return launch_gemm_ref<true, false, 1>(*g, nz, 1, s);
 }
+extern "C" void ppok_gemm_fwd(const GemmArgs *g, int nz, hipStream_t s) { gemm_fwd(g, nz, s); }
+extern "C" void ppok_gemm_dx(const GemmArgs *g, int nz, hipStream_t s) { gemm_dx(g, nz, s); }
 extern "C" void ppok_gemm_dw(const GemmArgs *g, int nz, hipStream_t s) { launch_gemm_dw(*g, nz, dw_splits(*g, nz), s); }
+
+// Debug entry that launches what the product launches (tests/test_hip_ppo_gemm.py): kind 0 / 1 / 2 = forward / input gradient / weight
+// gradient on the caller's GemmArgs as it stands -- nz problems, every field as given.  kind 2: splits = 0 takes the product's own
+// dw_splits, a positive value forces that many reduction slices.  info[0] = the kernel the launcher chose (GK_*), info[1] = the
+// reduction slices, both as reported by the launcher itself.  Returns 0, or -1 for an unknown kind / nz.
+extern "C" int ppok_debug_gemm_args(const GemmArgs *g, int nz, int kind, int splits, void *stream, int *info) {
+    if (!g || nz < 1 || nz > 2 || kind < 0 || kind > 2 || splits < 0) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const GemmLaunch l = kind == 0 ? gemm_fwd(g, nz, s) : kind == 1 ? gemm_dx(g, nz, s) : launch_gemm_dw(*g, nz, splits ? splits : dw_splits(*g, nz), s);
+    if (info) { info[0] = l.kernel; info[1] = l.slices; }
+    return 0;
+}
+extern "C" int ppok_debug_gemm_args_size() { return (int)sizeof(GemmArgs); }
 
 // Debug / microbenchmark entry (tools/gemm_bench.py): C[M,N] = A . B with the layouts of `mode`
 // (0: A[m][k] B[n][k] forward; 1: A[m][k] B[k][n] input-gradient; 2: A[k][m] B[k][n] weight-gradient over `splits` reduction

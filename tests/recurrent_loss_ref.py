@@ -353,6 +353,9 @@ CASES = (
     # added: the 64-way split with a remainder (the issue's 16 448 = 64 * 257 divides exactly): 65 * 253 = 16 445 rows, 63 splits of
     # 257 and one of 254
     ("bias_split_64way_r16445", 65, 253, 1, 0, 45, None, 12, 32, M2, "elu", "rand"),
+    # added: a privileged critic on 2048 rows -- the dW_ih launch (4H = 128 rows of W_ih against Op = 64 and OCp = 128 columns: 2 and 4
+    # tiles of 64 x 64) takes 8 reduction slices, the count from which the weight-gradient kernel regroups its workgroups per XCD
+    ("privileged_r2048_unequal_wih_tiles", 8, 256, 1, 0, 48, 100, 12, 32, M2, "elu", "rand"),
 )
 DETERMINISTIC = ("tile_plus_1_h96_privileged_tanh", "three_tiles_last_2_rows_t24")
 
