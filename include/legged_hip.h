@@ -144,7 +144,8 @@ typedef struct lg_xterm {
  * env's ROM step counter LG_TG_K: the ROM step that takes k to k + 1 advances the window with v_plan[env][k] for 0 <= k < n_nodes and
  * with 0 otherwise (the reset's pre-roll at k < 0, past the plan's end, before any plan was set).  It draws nothing, is never
  * stationary, uses the inputs as given (bounds are the host's business) and leaves LG_TG_V = the input last applied to the window
- * (the ROM interval in force).  A reset env replays its plan from node 0 at its new root position.  It is what lets the env track
+ * (the ROM interval in force).  A reset env replays its plan from node 0 at its new root position.  lg_traj_replan moves a per-env
+ * base b (0 otherwise), and the node read is k - b: replanning on the robot.  It is what lets the env track
  * the plans of tube/plan.py the way deep_tube_learning/evaluation/evaluate_tube_simple_oneshot_on_mpc_traj.py:75-132 lets its ROM
  * stand-in track them (legged_gym_dev_amd/tube/plan_env.py). */
 #define LG_TG_KIND_RANDOM 0
@@ -332,6 +333,26 @@ int lg_traj_reset(lg_ctx *ctx, const float *z);
  * caller's array need not outlive the call.  The ROM step counters are not touched: lg_traj_reset / a reset restart the plans.
  * Refused (lg_last_error) for a non-trajectory env, a kind other than PLAN, n_nodes out of range, a null v with n_nodes > 0. */
 int lg_traj_set_plans(lg_ctx *ctx, const float *v, int32_t n_nodes);
+/* Trajectory env of kind LG_TG_KIND_PLAN: replanning on the robot, the "plan from z_k[k+1]" of the re-solve at every control step of
+ * trajopt/tube_planning_closed_loop.py:82-168 ("TPCL" :159-163), by rewriting the window instead of appending behind its head.
+ * v: DEVICE f32 (num_envs, n_nodes, 2), 1 <= n_nodes <= LG_PLAN_MAX_N, new plans that START AT WINDOW POINT 1, the node the robot
+ * is heading for (it tracks between window points 0 and 1).  skip: DEVICE u8 (num_envs) or NULL; env i with skip[i] != 0 keeps its
+ * window, plan and base untouched (pass the recorder's `dead`; the node count is the context's, so a skipped env's old plan is read
+ * with the new count).  One launch on the env's stream; the caller's arrays need not outlive the call.
+ * The law, as an "as if": with k = LG_TG_K at the call, the generator state of env i, and all that evolves from it, is afterwards
+ * that of an env whose inputs had always been the old ones for the ROM steps that produced window points 0 and 1, then v[i][0],
+ * v[i][1], ... from window point 1 on, and 0 past the plan.  With Nw = lg_traj_cfg.N window intervals (points w[0..Nw]):
+ *   w[0], w[1] are kept;  w[p] = w[p-1] + rom_dt v[i][p-2] for p = 2..Nw (input 0 where p - 2 >= n_nodes), one rounding per
+ *   operation, so the points are the nodes a plan scored from w[1] has, on the bits;
+ *   the plan is copied into the context's buffer and the env's plan base becomes k - (Nw - 1): the ROM step k' -> k' + 1 then takes
+ *   node j = k' - base, so the next head advance takes v[i][Nw - 1]; inputs are 0 for j < 0 and j >= n_nodes;
+ *   LG_TG_V = v[i][Nw - 2] (0 past the plan), the input last applied to the window; unchanged at Nw = 1;
+ *   lg_buffers.trajectory is re-interpolated from the new window at the env's stored LG_TG_T / LG_TG_K.
+ * LG_TG_K, LG_TG_T and the stationary flag are not touched.  The observation buffer's trajectory columns follow at the next step
+ * callback, as after lg_traj_reset.  lg_traj_set_plans, lg_traj_reset and every env reset put the base back to 0: a reset env
+ * replays the plan in its buffer from node 0.
+ * Refused (lg_last_error) for a non-trajectory env, a kind other than PLAN, n_nodes outside 1..LG_PLAN_MAX_N, a null v. */
+int lg_traj_replan(lg_ctx *ctx, const float *v, int32_t n_nodes, const uint8_t *skip);
 /* ROM-rate recorder of the trajectory env (any generator kind), per env and on the device: one small launch per env step, one
  * lane per env, no host read.  The caller owns the (device) buffers.  lg_traj_rec_begin writes row 0 -- z = trajectory[:, 0] (the
  * point the robot tracks), pz_x = root xy, x = the state vector in get_state()'s layout (base pose 7, joint positions, base twist

@@ -432,6 +432,8 @@ def declare_env_api(lib, prefix="lg_"):
             g("traj_rec_check").argtypes = [C.POINTER(lg_traj_rec), i64, i32]
             g("traj_rec_begin").argtypes = [vp, C.POINTER(lg_traj_rec)]
             g("traj_rec_step").argtypes = [vp, C.POINTER(lg_traj_rec)]
+        if hasattr(lib, "lg_traj_replan"):             # ... or before replanning on the robot
+            g("traj_replan").argtypes = [vp, vp, i32, vp]
         g("set_stream").argtypes = [vp, vp]
         lib.lg_version.restype = C.c_int
 

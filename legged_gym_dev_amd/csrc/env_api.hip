@@ -19,6 +19,7 @@ extern "C" void lgk_set_stage(DevParams *P, const lg_stage *st, int what, hipStr
 extern "C" void lgk_reset_all(const DevParams *P, int N, int64_t counter, int inject, int init_done, hipStream_t s);
 extern "C" void lgk_traj_reset(const DevParams *P, const float *z, int N, int64_t counter, int inject, hipStream_t s);
 extern "C" void lgk_traj_set_plans(DevParams *P, const float *v, int N, int n, hipStream_t s);
+extern "C" void lgk_traj_replan(DevParams *P, const float *v, int N, int n, const uint8_t *skip, hipStream_t s);
 extern "C" void lgk_traj_record(const DevParams *P, const lg_traj_rec *rec, int N, int begin, hipStream_t s);
 extern "C" void lgk_reset_ids(const DevParams *P, const int32_t *ids, int n, int N, int64_t counter, int inject, int init_done, int traj,
                               hipStream_t s);
@@ -261,6 +262,10 @@ int lg_set_traj_generator(lg_ctx *c, int kind, int weight_sampler) {
         int rc = dalloc(c, &c->h.tg_plan, (size_t)c->h.cfg.num_envs * LG_PLAN_MAX_N * 2);
         if (rc) return rc;
     }
+    if (kind == LG_TG_KIND_PLAN && !c->h.tg_plan_k0) {          // ... and every env's plan base: 0, the counter indexes the plan
+        int rc = dalloc(c, &c->h.tg_plan_k0, (size_t)c->h.cfg.num_envs);
+        if (rc) return rc;
+    }
     c->h.tg_kind = kind;
     c->h.tg_wsamp = weight_sampler;
     c->h.tg_plan_n = 0;
@@ -281,6 +286,21 @@ int lg_traj_set_plans(lg_ctx *c, const float *v, int32_t n_nodes) {
     flush_finalize(c);
     c->h.tg_plan_n = n_nodes;
     lgk_traj_set_plans(c->d, v, c->h.cfg.num_envs, n_nodes, c->stream);
+    return chk_launch();
+}
+int lg_traj_replan(lg_ctx *c, const float *v, int32_t n_nodes, const uint8_t *skip) {
+    if (!c) { g_err = "null argument"; return -1; }
+    if (!c->h.cfg.traj.enabled) { g_err = "lg_traj_replan: not a trajectory env"; return -1; }
+    if (c->h.tg_kind != LG_TG_KIND_PLAN || !c->h.tg_plan || !c->h.tg_plan_k0) {
+        g_err = "lg_traj_replan: the generator is not PlanTrajectoryGenerator (lg_set_traj_generator with LG_TG_KIND_PLAN)"; return -1;
+    }
+    if (n_nodes < 1 || n_nodes > LG_PLAN_MAX_N) {
+        g_err = "lg_traj_replan: n_nodes = " + std::to_string(n_nodes) + " must lie in 1.." + std::to_string(LG_PLAN_MAX_N); return -1;
+    }
+    if (!v) { g_err = "lg_traj_replan: v is null"; return -1; }
+    flush_finalize(c);
+    c->h.tg_plan_n = n_nodes;
+    lgk_traj_replan(c->d, v, c->h.cfg.num_envs, n_nodes, skip, c->stream);
     return chk_launch();
 }
 int lg_traj_rec_check(const lg_traj_rec *r, int64_t N, int32_t env_x_n) {

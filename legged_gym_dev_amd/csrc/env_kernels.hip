@@ -1102,6 +1102,25 @@ __global__ void __launch_bounds__(256) k_traj_set_plans(DevParams *__restrict__ 
         const size_t i = e / ((size_t)n * 2), r = e % ((size_t)n * 2);
         P->tg_plan[i * (LG_PLAN_MAX_N * 2) + r] = v[e];
     }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) P->tg_plan_k0[i] = 0;   // the counter indexes the plan again
+    if (blockIdx.x == 0 && threadIdx.x == 0) P->tg_plan_n = n;
+}
+
+// lg_traj_replan: the window of every env that is not skipped rewritten from its point 1 under the caller's (N, n, 2) plans (lg_traj.h
+// tg_replan, one lane per env, the inputs read from the caller's array), and the plans copied into the context's padded buffer per
+// element as k_traj_set_plans does.  Every write lands in the env's own rows; the two parts touch different buffers.
+__global__ void __launch_bounds__(256) k_traj_replan(DevParams *__restrict__ P, const float *__restrict__ v, int n, const uint8_t *__restrict__ skip) {
+    const int N = P->cfg.num_envs;
+    const size_t total = (size_t)N * n * 2;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t i = e / ((size_t)n * 2), r = e % ((size_t)n * 2);
+        if (skip && skip[i]) continue;
+        P->tg_plan[i * (LG_PLAN_MAX_N * 2) + r] = v[e];
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
+        if (skip && skip[i]) continue;
+        tg_replan(P, i, v + (size_t)i * n * 2, n);
+    }
     if (blockIdx.x == 0 && threadIdx.x == 0) P->tg_plan_n = n;
 }
 
@@ -1150,6 +1169,11 @@ extern "C" void lgk_traj_set_plans(DevParams *P, const float *v, int N, int n, h
     const size_t total = (size_t)N * n * 2;
     const size_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(k_traj_set_plans, dim3(blocks < 1 ? 1 : blocks > 1024 ? 1024 : (int)blocks), dim3(256), 0, s, P, v, n);
+}
+extern "C" void lgk_traj_replan(DevParams *P, const float *v, int N, int n, const uint8_t *skip, hipStream_t s) {
+    const size_t total = (size_t)N * n * 2;                       // n >= 1: at least one element per env, so the grid covers the envs too
+    const size_t blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_traj_replan, dim3(blocks > 1024 ? 1024 : (int)blocks), dim3(256), 0, s, P, v, n, skip);
 }
 extern "C" void lgk_traj_record(const DevParams *P, const lg_traj_rec *rec, int N, int begin, hipStream_t s) {
     hipLaunchKernelGGL(k_traj_record, dim3((N + 255) / 256), dim3(256), 0, s, P, *rec, begin);

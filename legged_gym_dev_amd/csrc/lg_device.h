@@ -96,6 +96,9 @@ struct DevParams {
     // allocated and zeroed when the kind is selected, null before.  After tg_kind / tg_wsamp for the same reason.
     float *tg_plan;
     int tg_plan_n;
+    // ... and every env's plan base (num_envs): node j = LG_TG_K - tg_plan_k0[env] of the plan is the input of the ROM step k -> k + 1.
+    // 0 after lg_traj_set_plans, lg_traj_reset and every env reset (the counter indexes the plan); lg_traj_replan moves it.
+    int32_t *tg_plan_k0;
 };
 
 struct lg_ctx {

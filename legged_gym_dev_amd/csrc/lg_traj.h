@@ -119,10 +119,11 @@ __device__ __forceinline__ void tg_input_circle(const TgPar &b, const float *s, 
 // PlanTrajectoryGenerator -- this project's own class, not one of rom_dynamics.py (legged_hip.h LG_TG_KIND_PLAN): the env's own plan,
 // piecewise constant per ROM step and indexed by the ROM step counter k (a whole number held in a float), not by comparing
 // accumulated fp32 time against corners as Square does.  0 outside 0 <= k < n_nodes; the inputs are used as given.
+// The node is j = k - tg_plan_k0[env]: the base is 0 unless lg_traj_replan moved it (tg_replan below), so j is the counter itself.
 __device__ __forceinline__ void tg_input_plan(const DevParams *P, int i, float k, float v[2]) {
-    const int j = (int)k;
+    const int j = (int)k - P->tg_plan_k0[i];
     v[0] = 0.0f; v[1] = 0.0f;
-    if (k >= 0.0f && j < P->tg_plan_n) {
+    if (j >= 0 && j < P->tg_plan_n) {
         const float *p = P->tg_plan + ((size_t)i * LG_PLAN_MAX_N + j) * 2;
         v[0] = p[0]; v[1] = p[1];
     }
@@ -177,6 +178,28 @@ __device__ inline void tg_window_interpolate(const DevParams *P, int i, const fl
         }
 }
 
+// lg_traj_replan for one env (legged_hip.h): window points 0 and 1 -- the pair the robot tracks between -- stay; points 2..Nw are
+// rebuilt from point 1 under the new plan's inputs v (n nodes, the caller's array; 0 past the plan) with tg_window_step's expression,
+// so they are the nodes a plan scored from point 1 has; the base makes the next head advance take node Nw - 1.  Straight on the
+// window's home in HBM: the lane reads back its own stores, no workspace.  t, k and the stationary flag are not touched.
+__device__ inline void tg_replan(const DevParams *P, int i, const float *__restrict__ v, int n) {
+#pragma clang fp contract(off)
+    const lg_traj_cfg &t = P->cfg.traj;
+    const int Nw = t.N * t.dN;
+    float *s = P->buf.tg_state + (size_t)i * LG_TG_STRIDE;
+    float *z = P->buf.tg_traj + (size_t)i * 2 * (Nw + 1);
+    float z0 = z[2], z1 = z[3], v0 = 0.0f, v1 = 0.0f;
+    for (int p = 2; p <= Nw; ++p) {
+        v0 = 0.0f; v1 = 0.0f;
+        if (p - 2 < n) { v0 = v[2 * (p - 2)]; v1 = v[2 * (p - 2) + 1]; }
+        z0 = z0 + t.rom_dt * v0; z1 = z1 + t.rom_dt * v1;
+        z[2 * p] = z0; z[2 * p + 1] = z1;
+    }
+    if (Nw >= 2) { s[LG_TG_V] = v0; s[LG_TG_V + 1] = v1; }         // the input last applied to the window: node Nw - 2
+    P->tg_plan_k0[i] = (int)s[LG_TG_K] - (Nw - 1);
+    tg_window_interpolate(P, i, z, s[LG_TG_T], s[LG_TG_K]);
+}
+
 // LT:409-411: traj_gen.step() (RD:567-576) + get_trajectory
 template <bool GEN = true>
 __device__ inline void tg_callback_step(const DevParams *P, int i, int64_t counter, int inject, float *__restrict__ w) {
@@ -220,7 +243,8 @@ __device__ inline void tg_reset(const DevParams *P, int i, float z0x, float z0y,
     if (kind == LG_TG_KIND_RANDOM) tg_resample<GEN>(P, tg_par_cfg(P), i, LG_TSLOT_RTG(A), counter, inject);
     else if (kind == LG_TG_KIND_ZERO) s[LG_TG_STATIONARY] = 1.0f;              // RD:620-621
     else if (kind == LG_TG_KIND_CIRCLE) { s[LG_TG_CENTER] = z0x - 0.5f; s[LG_TG_CENTER + 1] = z0y; }   // RD:679-681
-    else if (kind == LG_TG_KIND_PLAN) s[LG_TG_STATIONARY] = 0.0f;              // never stationary: tg_input_kind zeroes a stationary env
+    else if (kind == LG_TG_KIND_PLAN) { s[LG_TG_STATIONARY] = 0.0f; P->tg_plan_k0[i] = 0; }   // never stationary: tg_input_kind zeroes a stationary env;
+                                                                                          // the plan in the buffer replays from node 0
     float tt = s[LG_TG_T], k = s[LG_TG_K], v[2] = {0.0f, 0.0f};
     for (int it = 0; it < t.N * t.dN; ++it) {
         if (kind == LG_TG_KIND_RANDOM) tg_input(P, i, tt, v);

@@ -16,8 +16,8 @@ from .reward_terms import ExpNegWeightedSqErr, SlopedErrChange
 
 class _TrajGenView:
     """Read-only face of the device-side generator state under the reference's TrajectoryGenerator attribute names
-    (rom_dynamics.py:484-505); ``center`` for CircleTrajectoryGenerator (:679-681), ``reset(z)`` (:592-593), ``set_plans(v)`` for this
-    project's own PlanTrajectoryGenerator.  The class name
+    (rom_dynamics.py:484-505); ``center`` for CircleTrajectoryGenerator (:679-681), ``reset(z)`` (:592-593), ``set_plans(v)`` and
+    ``replan(v, skip)`` for this project's own PlanTrajectoryGenerator.  The class name
     is the configured generator's (trajectory_generator.cls)."""
 
     def __init__(self, env):
@@ -58,6 +58,29 @@ class _TrajGenView:
             raise ValueError(f"set_plans(v): n_nodes = {vc.shape[1]} exceeds LG_PLAN_MAX_N = {capi.PLAN_MAX_N}")
         self._plans = vc
         self._core.call("traj_set_plans", C.c_void_p(vc.data_ptr()) if vc.shape[1] else None, int(vc.shape[1]))
+
+    def replan(self, v, skip=None):
+        """Replanning on the robot (lg_traj_replan): new plans v (num_envs, n_nodes, 2), 1 <= n_nodes <= LG_PLAN_MAX_N, that start at
+        window point 1, the node the robot is heading for.  Window points 0 and 1 stay, points 2.. are rebuilt from the plan, and the
+        ROM steps that follow take the plan's later nodes.  skip (num_envs) uint8 / bool: envs left untouched (the recorder's dead)."""
+        import ctypes as C
+        if self._kind != capi.TG_KINDS["PlanTrajectoryGenerator"]:
+            raise ValueError("replan(v): trajectory_generator.cls is not 'PlanTrajectoryGenerator'")
+        dev = self._t["tg_traj"].device
+        vc = torch.as_tensor(v, device=dev, dtype=torch.float32).contiguous()
+        n_env = self._t["tg_traj"].shape[0]
+        if vc.dim() != 3 or vc.shape[0] != n_env or vc.shape[2] != 2:
+            raise ValueError(f"replan(v): v must be ({n_env}, n_nodes, 2); got {tuple(vc.shape)}")
+        if not 1 <= vc.shape[1] <= capi.PLAN_MAX_N:
+            raise ValueError(f"replan(v): n_nodes = {vc.shape[1]} must lie in 1..LG_PLAN_MAX_N = {capi.PLAN_MAX_N}")
+        sc = None
+        if skip is not None:
+            sc = torch.as_tensor(skip, device=dev)
+            if tuple(sc.shape) != (n_env,) or sc.dtype not in (torch.uint8, torch.bool):
+                raise ValueError(f"replan(v, skip): skip must be ({n_env},) uint8 or bool; got {tuple(sc.shape)} {sc.dtype}")
+            sc = sc.contiguous()                         # bool and uint8 are one byte each, 0 / 1
+        self._replan = (vc, sc)                          # kept alive until the next call (the launch is asynchronous)
+        self._core.call("traj_replan", C.c_void_p(vc.data_ptr()), int(vc.shape[1]), C.c_void_p(sc.data_ptr()) if sc is not None else None)
 
 
 class _RomView:

@@ -9,6 +9,7 @@ place of CasADi / IPOPT, for many starts at once.
         [--K 256] [--iters 20] [--sigma 0.3] [--sigma_decay 1] [--lambda 1] [--rho_g 1e4] [--rho_w 0] [--rho_z 0] [--seed 0] \\
         [--planner mppi|grad|mppi+grad] [--lr 0.05] [--grad_iters 100] \\
         [--starts P --start_noise s] [--closed_loop H] [--sim_cfg KEY=VALUE ...] [--out DIR] \\
+        [--robot [--task anymal_c_flat_trajectory] [--load_run R] [--policy_checkpoint K] [--push_robots] [--allow_fast]] \\
         [--scenes random|FILE.npz [--scene_seed n] [--scene_obs LO,HI] [--scene_radius LO,HI] [--scene_margin M]]
 
 --run, --tube, --calibration, --coverage, --level, --checkpoint, --sim_cfg: as audit_plans.py takes them; a run that audit_plans.py
@@ -27,6 +28,13 @@ the problem's start and goal span (padded by 0.25), goals within 0.5 of the prob
 --scene_margin (default 0.05) outside every obstacle.  scenes.npz is written beside plans.npz, one scene per row of it (with
 --closed_loop the starts' scenes once per step), so audit_plans.py --plans plans.npz --scenes scenes.npz reads both; plan.json gains
 "scenes" (the source) and the audit its per-scene lists (by_plan / by_robot).  Without --scenes the output is what it was.
+
+--closed_loop H --robot: the legged robot is the tracker -- one simulated robot of --task per start under the
+task's trained policy, replanning from the window point it is heading for at each of H ROM steps (plan_env.closed_loop_env), env,
+policy, planner and recorder on one device.  --task, --load_run, --policy_checkpoint, --push_robots, --allow_fast: as audit_plans.py
+--robot takes them.  plan.json gains "tracker": "robot", the task, the policy and audit_closed_loop_env's audit (completed /
+terminated / covered_robots_of_all); plans.npz holds the plans in force in the plan frame.  --robot without --closed_loop is refused:
+audit_plans.py --robot tracks open-loop plans.  Without --robot the output is what it was.
 
 Writes plan.json -- the audit, the history of the (first) plan, the settings -- and plans.npz with z0 (B, 2), v (B, N, 2): the final
 mean plans, or with --closed_loop every plan in force, step by step; audit_plans.py --plans reads it.
@@ -82,8 +90,23 @@ def parse_args(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
     add_scene_flags(ap)
+    ap.add_argument("--robot", action="store_true", help="with --closed_loop: replan on the legged robot (one env per start) instead of the ROM-on-ROM model")
+    ap.add_argument("--task", default=None, help="with --robot: a trajectory-tracking task (default anymal_c_flat_trajectory)")
+    ap.add_argument("--load_run", default=None, help="with --robot: the policy's run folder (default: the latest)")
+    ap.add_argument("--policy_checkpoint", type=int, default=None, help="with --robot: the policy's checkpoint number (default: the latest)")
+    ap.add_argument("--push_robots", action="store_true", help="with --robot: push the robots on the task's timers")
+    ap.add_argument("--allow_fast", action="store_true", help="with --robot: accept ROM input bounds beyond the task's rom.v_min / v_max")
     a = ap.parse_args(argv)
     check_scene_flags(ap, a)
+    if not a.robot:
+        for flag in ("task", "load_run", "policy_checkpoint", "push_robots", "allow_fast"):
+            if getattr(a, flag):
+                ap.error(f"--{flag} belongs to --robot")
+    elif a.closed_loop is None:
+        ap.error("--robot belongs to --closed_loop H: it replans on the legged robot at every ROM step; audit_plans.py --robot tracks "
+                 "open-loop plans on it")
+    elif a.sim_cfg:
+        ap.error("--sim_cfg configures the ROM-on-ROM tracking model; --robot tracks on the legged env")
     if a.problem not in pl.PROBLEMS and not a.problem.endswith(".json"):
         ap.error(f"--problem {a.problem}: one of {sorted(pl.PROBLEMS)} or a .json file")
     if a.calibration is not None and not a.run:
@@ -205,6 +228,21 @@ def starts(a, p):
     return s
 
 
+def main_robot(a, planner, z0, scenes=None):
+    """--closed_loop H --robot: closed_loop_env on audit_plans.py's --robot env, audit_closed_loop_env."""
+    import torch
+    from legged_gym_dev_amd.tube.plan_env import audit_closed_loop_env, closed_loop_env
+    env, runner, policy, path = audit_plans.robot_env(a, z0.shape[0])
+    try:
+        res = closed_loop_env(env, policy, planner, a.closed_loop, start=z0, keep_plans=True, w0=a.w0, allow_fast=a.allow_fast)
+        torch.cuda.synchronize()
+        audit = audit_closed_loop_env(res, planner.problem, goal_tol=a.goal_tol, **({} if scenes is None else {"scenes": scenes}))
+    finally:
+        runner.ppo.close()
+        env.close()
+    return res, audit, {"tracker": "robot", "task": a.task or "anymal_c_flat_trajectory", "policy": path, "push_robots": bool(a.push_robots)}
+
+
 def main(argv=None):
     a = parse_args(argv)
     cfg = audit_plans.run_config(a.run) if a.run else None
@@ -212,6 +250,7 @@ def main(argv=None):
     import torch
     from legged_gym_dev_amd.tube.rom_sim import HipRomSim
     model = calib = sim = None
+    robot = {}
     if a.run:
         from legged_gym_dev_amd.tube.model import HipTubeModel
         if cfg["dataset"] in audit_plans.LEVEL_RUNS and a.level is None:
@@ -226,7 +265,8 @@ def main(argv=None):
         if a.run:
             model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, device=a.device)
         planner = make_planner(a, model, p, calib, scenes)
-        sim = HipRomSim(audit_plans.sim_config(a, p), device=a.device)
+        if not a.robot:
+            sim = HipRomSim(audit_plans.sim_config(a, p), device=a.device)
         if a.closed_loop is None:
             sol = planner.plan(z0)
             t = pl.track(sim, sol["score"]["z"], sol["v"])
@@ -237,9 +277,12 @@ def main(argv=None):
                      "cost": [float(x) for x in sol["score"]["cost"].cpu()]}
         else:
             first = planner.plan(z0)                                     # the history of the first plan; closed_loop makes it again
-            res = pl.closed_loop(planner, sim, a.closed_loop, z0, keep_plans=True, w0=a.w0)
-            torch.cuda.synchronize()
-            audit = pl.audit_closed_loop(res, p, goal_tol=a.goal_tol, **({} if scenes is None else {"scenes": scenes}))
+            if a.robot:
+                res, audit, robot = main_robot(a, planner, z0, scenes)
+            else:
+                res = pl.closed_loop(planner, sim, a.closed_loop, z0, keep_plans=True, w0=a.w0)
+                torch.cuda.synchronize()
+                audit = pl.audit_closed_loop(res, p, goal_tol=a.goal_tol, **({} if scenes is None else {"scenes": scenes}))
             if scenes is not None:                                      # plans.npz holds (H, P) plans: the starts' scenes once per step
                 plan_scenes = scenes.take(np.tile(np.arange(scenes.S), a.closed_loop))
             hist = first["hist"]
@@ -256,7 +299,7 @@ def main(argv=None):
             model.close()
     out = {"audit": audit, "hist": hist.cpu().double().tolist(), "closed_loop": a.closed_loop, "starts": z0.double().tolist(),
            "mppi": {**{k: v for k, v in vars(mppi_cfg(a)).items() if k != "lambda_"}, "lambda": a.lambda_}, "problem": p.to_json(),
-           "run": a.run, "tube": a.tube or p.tube_kind, "level": a.level, "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), **extra}
+           "run": a.run, "tube": a.tube or p.tube_kind, "level": a.level, "calibrated": calib is not None, "sim_cfg": list(a.sim_cfg), **extra, **robot}
     if a.w0 != "zero":
         out["w0"] = a.w0
     if a.planner != "mppi":
@@ -273,7 +316,12 @@ def main(argv=None):
     if a.closed_loop is None:
         print(f"{audit['plans']} plans x {audit['nodes']} nodes: predicted safe {audit['predicted_safe']:.4f}, actually safe "
               f"{audit['actually_safe']:.4f}, covered at every node {audit['covered_plans']:.4f}")
+    elif a.robot and not audit["completed"]:
+        print(f"{audit['robots']} robots x {audit['steps']} steps on the robot: completed 0, terminated {audit['terminated']}")
     else:
+        if a.robot:
+            print(f"on the robot: completed {audit['completed']} of {audit['robots']}, terminated {audit['terminated']}, covered at every "
+                  f"step, of all: {audit['covered_robots_of_all']:.4f}; of the completed:")
         print(f"{audit['robots']} robots x {audit['steps']} steps: coverage {audit['coverage']:.4f}, covered at every step "
               f"{audit['covered_robots']:.4f}, actually safe {audit['actually_safe']:.4f}, reached the goal {audit['reached_goal']:.4f}")
     return out

@@ -12,12 +12,17 @@ so plan node j is recorder row Nw + j (j = 0..Np); rows 0..Nw - 1 are the lead-i
 step of the ROM step, after the env's clock moved on by env.dt, so ``z_ref`` sits env.dt into the interval past its node:
 z_ref[j] = Z_j + (Z_{j+1} - Z_j) env.dt / rom.dt.  That is how ``collect()`` (scripts/collect_trajectory_data.py) records the data
 the tube was trained on, so the audit measures the error the tube predicts.
+
+Replanning.  ``closed_loop_env`` is ``plan.closed_loop`` with the robot as the tracker: at every ROM step
+a new plan from window point 1, the node the robot is heading for, and ``traj_gen.replan`` (lg_traj_replan) rewrites the window
+behind it.  There recorder row r sits env.dt into the interval past node r - 1 -- node k is row k + 1 -- and ``rom_schedule`` tells the
+loop how many env steps each ROM step takes, so nothing is read back from the device inside it.
 """
 import copy
 import ctypes as C
 
 from .. import capi
-from .plan import audit
+from .plan import audit, audit_closed_loop, shift_past, shift_plan
 
 PLAN_KIND = capi.TG_KINDS["PlanTrajectoryGenerator"]
 
@@ -201,6 +206,159 @@ def track_env(env, policy, v, z0, H_rev=0, want=(), allow_fast=False):
     if "rec" in want:
         out["rec"] = rec
     return out
+
+
+# ---------------------------------------------------------------- replanning on the robot
+def clock_schedule(Nw, rom_dt, dt, n_rom_steps):
+    """The generator's clock in float32, one rounding per operation: after tg_reset -- t = -Nw rom_dt and Nw sums t += rom_dt, k = 0 --
+    every env step tests t >= k rom_dt - 1e-5 (a ROM step: k += 1) and then adds dt.  Returns, for each of the next n_rom_steps ROM
+    steps, the env steps up to and including the one it falls on.  The first is 1; an entry above round(rom_dt / dt) is a ROM step
+    that the comparison delays by one env step."""
+    import numpy as np
+    f32 = np.float32
+    rom_dt, dt = f32(rom_dt), f32(dt)
+    t = f32(f32(-int(Nw)) * rom_dt)
+    for _ in range(int(Nw)):
+        t = f32(t + rom_dt)
+    if not (dt > 0 and rom_dt > 0):
+        raise ValueError(f"the clock does not reach a ROM step: rom_dt = {float(rom_dt)}, dt = {float(dt)} must be positive")
+    k, out, steps = f32(0), [], 0
+    while len(out) < int(n_rom_steps):
+        steps += 1
+        if t >= f32(f32(k * rom_dt) - f32(1e-5)):
+            k = f32(k + f32(1))
+            out.append(steps)
+            steps = 0
+        t = f32(t + dt)
+    return out
+
+
+def rom_schedule(env, n_rom_steps):
+    """How many env steps each of the next n_rom_steps ROM steps takes after traj_gen.reset (clock_schedule on the env's N, rom_dt and
+    dt).  Every live env shares that clock, so the schedule is the same for all of them and a loop needs no device read to know when
+    a recorder row was written."""
+    tj = env.setup.traj
+    return clock_schedule(int(tj["N"]) * int(tj["dN"]), tj["rom_dt"], env.setup.dt, n_rom_steps)
+
+
+def check_closed_loop(env, problem, H, w0="zero", allow_fast=False):
+    """closed_loop_env's refusals (ValueError); returns (B, Nw, schedule of H + 1 ROM steps)."""
+    traj = getattr(env.setup, "traj", None)
+    if traj is None or traj["kind"] != PLAN_KIND:
+        raise ValueError("closed_loop_env needs an env with trajectory_generator.cls = 'PlanTrajectoryGenerator' (plan_env_cfg)")
+    if H < 1:
+        raise ValueError(f"H = {H} must be at least 1")
+    if w0 not in ("zero", "error"):
+        raise ValueError(f"w0 = {w0!r}: 'zero' or 'error'")
+    if float(problem.dt) != float(traj["rom_dt"]):
+        raise ValueError(f"problem.dt = {problem.dt} is not the env's rom.dt = {traj['rom_dt']}: replanning happens at the ROM's rate")
+    Nw = int(traj["N"])
+    if int(problem.N) < Nw:
+        raise ValueError(f"problem.N = {problem.N} is shorter than the env's window, trajectory_generator.N = {Nw}: the plan must fill the window")
+    sched = rom_schedule(env, H + 1)
+    if sum(sched) + 1 > int(env.max_episode_length):                # env.reset() leaves the episode at step 1
+        raise ValueError(f"the horizon takes {sum(sched)} env steps after the reset's own; max_episode_length is {int(env.max_episode_length)}")
+    if not allow_fast:
+        lo, hi = [float(x) for x in env.rom.v_min], [float(x) for x in env.rom.v_max]
+        if any(float(a) < b - 1e-6 for a, b in zip(problem.rom_v_min, lo)) or any(float(a) > b + 1e-6 for a, b in zip(problem.rom_v_max, hi)):
+            raise ValueError(f"problem.rom_v_min / rom_v_max = {list(problem.rom_v_min)} / {list(problem.rom_v_max)} reach beyond the env's "
+                             f"rom.v_min / v_max = {[round(x, 6) for x in lo]} / {[round(x, 6) for x in hi]}: rebuild the problem inside them "
+                             "(PlanProblem.named(name, rom_v_min=..., rom_v_max=...)) or pass allow_fast=True")
+    return env.num_envs, Nw, sched
+
+
+def closed_loop_env(env, policy, planner, H, start=None, iters_first=None, keep_plans=False, w0="zero", allow_fast=False):
+    """plan.closed_loop (trajopt/tube_planning_closed_loop.py:82-168, "TPCL") with the legged robot as the tracker, for
+    B = env.num_envs robots: H times -- plan from window point 1, the node the robot is heading for; rewrite the window behind it
+    (traj_gen.replan, skipping robots that reset); take the env steps of one ROM interval.  planner: HipMppiPlanner, HipGradPlanner or
+    ChainedPlanner (with Scenes, robot b lives in scene b).  start (2,) or (B, 2): the plan frame's image of the robots' start
+    points, None = problem.start; the plan frame is (world - start_world) + start in float64, rounded once.
+    Row r of the recorder is written env.dt into the interval past node r - 1, so node k is row k + 1; the tube item's past is the
+    robot's own record: e takes |z - pz_x| of row j + 1 (world coordinates), v_prev the committed input (TPCL:159-163).  The loop reads
+    nothing back: the env steps per ROM interval come from rom_schedule.  After it one device read checks that every robot that did
+    not reset has its H + 2 rows; RuntimeError naming the schedule otherwise.
+    Returns device tensors z, pz_x (B, H+1, 2) -- recorder rows 1..H+1 in the plan frame --, z_node (B, H+1, 2) the nodes planned
+    from (start, then every later window point 1), v (B, H, 2) the committed inputs, w (B, H+1) -- 0 or the first w0, then w_sol[:, 1]
+    of each plan in force --, cost, min_clear, best_J, n_bad (B, H), completed (B) bool, rows, dead and, with keep_plans, plans_v,
+    plans_z, plans_w as closed_loop returns them."""
+    import torch
+    p = planner.problem
+    B, Nw, sched = check_closed_loop(env, p, H, w0, allow_fast)
+    dev = env.device
+    s_plan = torch.as_tensor(p.start if start is None else start, dtype=torch.float32).to(dev)
+    s_plan = s_plan.reshape(-1, 2).expand(B, 2).contiguous() if s_plan.numel() == 2 else s_plan.reshape(-1, 2).contiguous()
+    if tuple(s_plan.shape) != (B, 2):
+        raise ValueError(f"start must be (2,) or {(B, 2)}; got {tuple(s_plan.shape)}")
+    tg = env.traj_gen
+    rec = TrajRecorder(env, H + 2)
+    norm = lambda d: torch.linalg.vector_norm(d, dim=-1)
+    with torch.no_grad():
+        env.reset()
+        tg.set_plans(torch.zeros(B, 0, 2, device=dev))
+        s_world = env.rom.proj_z(env.root_states).clone()
+        tg.reset(s_world)
+        env.trajectory.copy_(s_world[:, None, :].expand_as(env.trajectory))      # as track_env: the window is constant at the start
+        rec.begin()
+        frame = lambda t: ((t.double() - s_world.double().reshape((B,) + (1,) * (t.dim() - 2) + (2,))) +
+                           s_plan.double().reshape((B,) + (1,) * (t.dim() - 2) + (2,))).float()
+        e, v_prev = torch.zeros(B, p.H_rev, device=dev), torch.zeros(B, p.H_rev, 2, device=dev)
+        err = norm(rec.z[:, 0] - rec.pz_x[:, 0])
+        w_start = (lambda: None) if w0 == "zero" else (lambda: err)
+        nodes, v, w = [], [], [torch.zeros(B, device=dev) if w0 == "zero" else err]
+        cost, clear, bestJ, nbad, plans = [], [], [], [], {"v": [], "z": [], "w": []}
+        obs, warm = env.get_observations(), None
+        for j in range(H + 1):
+            origin = frame(tg.trajectory[:, 1]).contiguous()
+            nodes.append(origin)
+            if j < H:
+                sol = planner.plan(origin, warm, e, v_prev, w_start(), iters=iters_first) if j == 0 else \
+                    planner.plan(origin, warm, e, v_prev, w_start())
+                v_sol = sol["v"]
+                tg.replan(v_sol, skip=rec.dead)
+                v.append(v_sol[:, 0]), w.append(sol["score"]["w"][:, 1])
+                cost.append(sol["score"]["cost"]), clear.append(sol["score"]["min_clear"]), bestJ.append(sol["best_J"]), nbad.append(sol["n_bad"])
+                if keep_plans:
+                    plans["v"].append(v_sol), plans["z"].append(sol["score"]["z"]), plans["w"].append(sol["score"]["w"])
+                warm = shift_plan(v_sol)
+            for _ in range(sched[j]):
+                obs = env.step(policy(obs.detach()).detach())[0]
+                rec.step()
+            if j < H:                                               # recorder row j + 1 now exists
+                err = norm(rec.z[:, j + 1] - rec.pz_x[:, j + 1])    # world coordinates: the collector's error
+                e, v_prev = shift_past(e, v_prev, err, v_sol[:, 0])
+        rows, dead = rec.rows.cpu(), rec.dead.cpu()                 # the one device read
+    short = ((dead == 0) & (rows != H + 2)).nonzero().flatten()
+    if short.numel():
+        raise RuntimeError(f"{short.numel()} robot(s) that did not reset have not H + 2 = {H + 2} recorder rows (robot {int(short[0])}: "
+                           f"{int(rows[short[0]])}): the env steps per ROM step taken from rom_schedule, {sched}, are not the device's")
+    out = {"z": frame(rec.z[:, 1:]), "z_node": torch.stack(nodes, 1), "v": torch.stack(v, 1), "w": torch.stack(w, 1),
+           "pz_x": frame(rec.pz_x[:, 1:]), "cost": torch.stack(cost, 1), "min_clear": torch.stack(clear, 1), "best_J": torch.stack(bestJ, 1),
+           "n_bad": torch.stack(nbad, 1), "completed": (rec.rows == H + 2) & (rec.dead == 0), "rows": rec.rows, "dead": rec.dead != 0}
+    if keep_plans:
+        out.update({"plans_" + k: torch.stack(t, 0) for k, t in plans.items()})
+    return out
+
+
+def audit_closed_loop_env(result, problem, goal_tol=0.1, scenes=None):
+    """plan.audit_closed_loop over the completed robots, plus completed / terminated (robots that reset: fell or timed out) and
+    covered_robots_of_all, in which a robot that did not complete counts as not covered.  "robots" counts all of them.  Strict JSON;
+    with no completed robot the shares are None.  scenes: a plan.Scenes of S = all the robots; the completed ones keep their own."""
+    import torch
+    done = result["completed"].detach().cpu().bool()
+    B, n, H = int(done.numel()), int(done.sum()), int(result["v"].shape[1])
+    head = {"robots": B, "completed": n, "terminated": int(result["dead"].detach().cpu().bool().sum())}
+    if n == 0:
+        empty = {"steps": H, "coverage_by_step": None, "coverage": None, "covered_robots": None, "actually_safe": None, "predicted_safe": None,
+                 "goal_tol": float(goal_tol), "reached_goal": None, "goal_distance_mean": None, "error_mean": None, "error_max": None}
+        return {**empty, **head, "covered_robots_of_all": 0.0}
+    idx = done.nonzero().flatten()
+    picked = {k: result[k].detach().cpu()[idx] for k in ("z", "w", "pz_x", "min_clear")}
+    res = audit_closed_loop(picked, problem, goal_tol=goal_tol, scenes=None if scenes is None else _completed_scenes(scenes, B, idx))
+    err = torch.linalg.vector_norm(picked["z"].double() - picked["pz_x"].double(), dim=-1)
+    covered = (picked["w"].double() >= err).all(dim=1)
+    if "by_robot" in res:
+        res["by_robot"]["robot"] = [int(i) for i in idx]
+    return {**res, **head, "covered_robots_of_all": float(covered.sum()) / B}
 
 
 # ---------------------------------------------------------------- audit
