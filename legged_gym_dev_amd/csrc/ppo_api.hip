@@ -925,6 +925,19 @@ int lg_ppo_debug_bucket_extents(lg_ppo *p, int l, int64_t *offsets, int64_t *cou
     return n;
 }
 
+// The two minibatch buffer sets (host-side, for tests of the gathers): cur[5] = obs, critic_obs, actions, mu, scalars of the set the
+// next forward reads (after lg_ppo_minibatch_backward: the one it read), other[5] = those of the set lg_ppo_minibatch_step gathers the
+// following minibatch into; dims = {Op, OCp, mb_rows}.
+int lg_ppo_debug_mb_sets(lg_ppo *p, void **cur, void **other, int *dims) {
+    const PpoDev &d = p->dev;
+    const lg_ppo::MbSet &m = p->mbset[p->mb_cur ^ 1];
+    void *c[5] = {d.mb_obs, d.mb_critic_obs, d.mb_actions, d.mb_mu, d.mb_scalars};
+    void *o[5] = {m.obs, m.critic_obs, m.actions, m.mu, m.scalars};
+    for (int k = 0; k < 5; ++k) { cur[k] = c[k]; other[k] = o[k]; }
+    dims[0] = d.Op; dims[1] = d.OCp; dims[2] = d.mb_rows;
+    return 0;
+}
+
 int lg_ppo_act_inference(lg_ppo *p, const float *obs, float *actions_out, int64_t rows) {
     if (rows > p->Mmax) { lg_set_error("too many rows for act_inference"); return -11; }
     if (p->rnn.H) {                              // rsl_rl's act_inference advances memory_a

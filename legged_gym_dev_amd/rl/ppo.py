@@ -272,6 +272,17 @@ class HipPPO:
         switched on by LG_DETERMINISTIC=1 in the environment."""
         self._call("set_deterministic", 1 if on else 0)
 
+    def debug_mb_sets(self):
+        """lg_ppo_debug_mb_sets (tests of the gathers): (current, other) minibatch buffer sets as dicts of zero-copy views --
+        obs (R, Op), critic_obs (R, OCp), actions / mu (R, A), scalars (R, 4) = [v_old, return, advantage, log-prob]; `current` is what
+        the last minibatch_backward read, `other` what minibatch_step gathers the following minibatch into."""
+        cur, other, dims = (C.c_void_p * 5)(), (C.c_void_p * 5)(), (C.c_int * 3)()
+        self._call("debug_mb_sets", cur, other, dims)
+        Op, OCp, R = dims[0], dims[1], dims[2]
+        shapes = (("obs", (R, Op)), ("critic_obs", (R, OCp if self.privileged else Op)), ("actions", (R, self.A)), ("mu", (R, self.A)),
+                  ("scalars", (R, 4)))
+        return tuple({k: device_tensor(ptrs[i], s, "f4", self, self.device) for i, (k, s) in enumerate(shapes)} for ptrs in (cur, other))
+
     def params_changed(self):
         """Call after writing parameters through ``param_views`` / ``t["params"]``: the rollout's weight images are re-derived
         by the next act() (also in the middle of a rollout)."""

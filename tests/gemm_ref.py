@@ -254,8 +254,19 @@ def structural_bound(case, p, ref, slices):
     gradient: times |act'(aux)|, which fp32 evaluates with up to three roundings of its own."""
     kind, act = case["kind"], case["act"]
     B = (6 * p["K"] + slices + 8) * U * ref["S"]
-    if kind == 0 and act:
-        pre = ref["pre"]
+    if kind == 0:
+        return bound_through_activation(act, ref["pre"], ref["out"], B)
+    if kind == 1:
+        B = B * ref["factor"].abs() + 4 * U * ref["out"].abs()
+    if act in (1, 2, 5, 6):
+        B = B + EXPF_RTOL * ref["out"].abs() + EXPF_ATOL
+    return B
+
+
+def bound_through_activation(act, pre, out, B):
+    """The slope and kink rule of structural_bound on its own: B bounds the error of the pre-activation `pre` (float64 reference, `out`
+    = act(pre)); returns the bound behind the activation of code `act`, the __expf terms included."""
+    if act:
         slope = act_slope64(act, pre).abs()
         if act in (5, 6):                       # smooth: the largest slope on the interval is at its end nearer 0
             near = torch.where(pre.abs() > B, pre - torch.sign(pre) * B, torch.zeros_like(pre))
@@ -263,11 +274,9 @@ def structural_bound(case, p, ref, slices):
         else:
             slope = torch.where(pre.abs() > B, torch.maximum(slope, act_slope64(act, pre + B).abs()),
                                 torch.full_like(pre, ACT_LIPSCHITZ[act]))
-        B = B * slope + U * ref["out"].abs()
-    if kind == 1:
-        B = B * ref["factor"].abs() + 4 * U * ref["out"].abs()
+        B = B * slope + U * out.abs()
     if act in (1, 2, 5, 6):
-        B = B + EXPF_RTOL * ref["out"].abs() + EXPF_ATOL
+        B = B + EXPF_RTOL * out.abs() + EXPF_ATOL
     return B
 
 

@@ -5,7 +5,12 @@ forward/backward vs autograd), KL-adaptive lr + grad clip + Adam, full update.
 The gradient tests here update on the rollout's own parameters with 12 actions: importance ratio 1 and v_new = v_old, so every row is
 inside the surrogate clip and on the tie branch of the clipped value loss.  The other branches of the loss, value_loss_coef != 1,
 use_clipped_value_loss = False, 1 .. 16 actions and the second trip of the head kernels' tile loops are checked against float64, per
-head kernel, in tests/test_hip_ppo_loss.py (inputs: tests/ppo_loss_ref.py, their conditions: tests/test_ppo_loss_host.py)."""
+head kernel, in tests/test_hip_ppo_loss.py (inputs: tests/ppo_loss_ref.py, their conditions: tests/test_ppo_loss_host.py).
+
+The rollout half is checked against float64 elsewhere: act() on every dispatch path of the one-launch forward and on the per-layer path,
+with per-action std, a numpy Philox and derived log-prob bounds, in tests/test_hip_ppo_act.py (tests/ppo_act_ref.py,
+tests/test_ppo_act_host.py); process_env_step, GAE, the advantage moments and the episode bookkeeping in tests/test_hip_ppo_returns.py
+(tests/ppo_rollout_ref.py, tests/test_ppo_rollout_host.py); the minibatch gathers and the gather-ahead in tests/test_hip_ppo_gather.py."""
 import numpy as np
 import pytest
 import torch
