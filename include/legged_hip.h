@@ -396,7 +396,7 @@ typedef struct lg_ppo_buffers {
     float *obs, *critic_obs, *actions, *rewards, *values, *returns, *advantages, *log_prob, *mu, *sigma;
     uint8_t *dones;                                /* storage, time major (T, N, .) */
     float *act_actions, *act_values, *act_log_prob, *act_mu;   /* outputs of the last act() */
-    float *stats;                                  /* [lr, kl, value_loss, surrogate_loss, mean_std, n_updates, adv_mean, adv_std] */
+    float *stats;                                  /* [lr, kl, value_loss_sum, surrogate_loss_sum, adam_t, n_updates, adv_mean, adv_std] */
     float *noise;                                  /* (N, A) injected N(0,1) for act(), or unused */
     int32_t *perm;                                 /* minibatch permutation (T*N) */
     float *adv_partial;                            /* [sum, sumsq, count] for cross-rank normalisation */
@@ -469,8 +469,13 @@ int lg_ppo_params_changed(lg_ppo *p);
  * differs from run to run (last-bit differences in every gradient).  on != 0: the same contributions are accumulated as 2^-40
  * fixed-point 64-bit integers (order-independent) and folded into the float buffers before they are read: two runs from the
  * same seed then agree bit for bit, on one rank and across a fixed set of ranks.  Costs three small launches per optimiser step.
+ * Range: |sum| < 2^23 per accumulator; the squared gradient norm is kept in two such words (a norm below 1.9e8).
  * Not combinable with gradient buckets reduced inside the backward pass (lg_ppo_set_comm): returns an error then. */
 int lg_ppo_set_deterministic(lg_ppo *p, int on);
+/* Tests of the optimiser step: device pointers of the split-bf16 weight planes (uint16; plane h at *wpl, m and l *pl_stride and
+ * 2 * *pl_stride elements later, 3 * pl_stride + 8 elements in all) and of the int32 [num_params] map from a parameter to its element
+ * inside a plane (-1: biases, std, LSTM weights).  Read-only: nothing is launched or changed. */
+int lg_ppo_debug_weight_planes(lg_ppo *p, void **wpl, int64_t *pl_stride, void **pl_dest);
 /* actor mean only (act_inference) for play/eval */
 int lg_ppo_act_inference(lg_ppo *p, const float *obs, float *actions_out, int64_t rows);
 

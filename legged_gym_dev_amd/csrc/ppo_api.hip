@@ -902,7 +902,7 @@ int lg_ppo_params_changed(lg_ppo *p) { p->params_dirty = 1; return 0; }
 int lg_ppo_set_deterministic(lg_ppo *p, int on) {
     if (on && p->comm) { lg_set_error("deterministic mode cannot be combined with gradient buckets reduced inside the backward pass (lg_ppo_set_comm)"); return -14; }
     if (on && !p->det_buf) {
-        const size_t n = (size_t)p->dev.num_params + 10;
+        const size_t n = LG_DET_WORDS(p->dev.num_params);
         void *q = nullptr;
         if (hipMalloc(&q, n * sizeof(long long)) != hipSuccess || hipMemset(q, 0, n * sizeof(long long)) != hipSuccess) {
             lg_set_error("hipMalloc failed in lg_ppo_set_deterministic"); return -100;
@@ -935,6 +935,15 @@ int lg_ppo_debug_mb_sets(lg_ppo *p, void **cur, void **other, int *dims) {
     void *o[5] = {m.obs, m.critic_obs, m.actions, m.mu, m.scalars};
     for (int k = 0; k < 5; ++k) { cur[k] = c[k]; other[k] = o[k]; }
     dims[0] = d.Op; dims[1] = d.OCp; dims[2] = d.mb_rows;
+    return 0;
+}
+
+// The split-bf16 weight planes the optimiser step keeps current (host-side, for tests; device pointers only, nothing is launched):
+// *wpl = plane h, planes m and l follow *pl_stride and 2 * *pl_stride uint16 elements later (3 * pl_stride + 8 elements in all);
+// *pl_dest = int32 [num_params]: element index of each parameter inside a plane, -1 for parameters without an image.
+int lg_ppo_debug_weight_planes(lg_ppo *p, void **wpl, int64_t *pl_stride, void **pl_dest) {
+    if (!p || !wpl || !pl_stride || !pl_dest) { lg_set_error("null argument"); return -1; }
+    *wpl = p->dev.wpl; *pl_stride = p->dev.pl_stride; *pl_dest = p->dev.pl_dest;
     return 0;
 }
 

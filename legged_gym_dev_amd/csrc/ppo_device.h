@@ -40,7 +40,7 @@ struct PpoDev {                    // passed by value to kernels
     uint8_t *st_dones;
     float *act_actions, *act_values, *act_log_prob, *act_mu;
     float *stats;                  // [lr, kl, value_loss_sum, surrogate_sum, adam_t, n_updates, adv_mean, adv_std]
-    float *loss_acc;               // [value_loss, surrogate, grad_norm_sq]
+    float *loss_acc;               // [value_loss, surrogate, grad_norm_sq (even steps), grad_norm_sq (odd steps)]
     float *noise;
     int32_t *perm;
     float *adv_partial;
@@ -61,13 +61,29 @@ struct PpoDev {                    // passed by value to kernels
     // slices, bias column sums, the head's row sums, loss statistics, the gradient norm, the advantage moments -- is accumulated with
     // float atomics, whose order differs from run to run.  With det64 set the same contributions are added as 2^-40 fixed-point
     // 64-bit integers (integer addition is associative: any order gives the same bits) into a shadow of
-    // [grads (num_params + 2) | loss_acc (4) | adv_partial (4)], and k_det_fold adds the shadow into the float buffers before they are read.
+    // [grads (num_params + 2) | loss_acc (4) | adv_partial (4) | norm_lo (2)], and k_det_fold adds the shadow into the float buffers
+    // before they are read.  The two squared-gradient-norm slots (loss_acc[2], loss_acc[3]) do not fit the 2^-40 format -- a norm of
+    // 2 900 squares to 2^23 -- so they are kept in two words each (det_add_norm below): units of 2^-8 in the slot's own word, the
+    // remainder in units of 2^-40 in norm_lo.
     long long *det64;
 };
+#define LG_DET_WORDS(num_params) ((size_t)(num_params) + 12)
 
 #define LG_DET_SCALE 1099511627776.0          // 2^40: |sum| < 2^23, resolution 9.1e-13
 __device__ __forceinline__ void det_add64(long long *q, float v) {
     atomicAdd(reinterpret_cast<unsigned long long *>(q), (unsigned long long)__double2ll_rn((double)v * LG_DET_SCALE));
+}
+// Squared gradient norm, slot par.  The same integer det_add64 would add, x = rn(v 2^40), is formed as an integer-valued double (v is an
+// fp32 value: v 2^40 is exact) and split exactly into x = hi 2^32 + lo, |lo| <= 2^31; each word is an integer sum, so any order of the
+// contributions gives the same bits, and nothing here depends on the size of v.  k_det_fold adds (hi 2^32 + lo) 2^-40 in double: where
+// the one-word sum did not overflow (|sum| < 2^23) that is the same double, so the same float, as before.  Range: |sum| < 2^55, a
+// norm of 1.9e8; resolution 2^-40 as everywhere.
+#define LG_DET_NORM_SPLIT 4294967296.0               // 2^32
+__device__ __forceinline__ void det_add_norm(const PpoDev &P, int par, float v) {
+    const double x = rint((double)v * LG_DET_SCALE);
+    const double h = rint(x * (1.0 / LG_DET_NORM_SPLIT));
+    atomicAdd(reinterpret_cast<unsigned long long *>(P.det64 + P.num_params + 4 + par), (unsigned long long)__double2ll_rn(h));
+    atomicAdd(reinterpret_cast<unsigned long long *>(P.det64 + P.num_params + 10 + par), (unsigned long long)__double2ll_rn(x - h * LG_DET_NORM_SPLIT));
 }
 // atomicAdd(p, v) for p inside grads / loss_acc / adv_partial
 __device__ __forceinline__ void acc_add(const PpoDev &P, float *p, float v) {

@@ -805,7 +805,10 @@ __global__ void __launch_bounds__(256) k_opt_prepare(PpoDev P, int par, int prep
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) acc_add(P, &P.loss_acc[2 + par], red[0]);
+    if (threadIdx.x == 0) {
+        if (P.det64) det_add_norm(P, par, red[0]);           // two-word fixed point: a squared norm leaves the range of acc_add's format
+        else atomicAdd(&P.loss_acc[2 + par], red[0]);
+    }
 }
 // Deterministic mode: add the fixed-point shadow (PpoDev::det64) into the float buffers it stands for and clear it.  One adder per
 // element and launch, so the float result does not depend on the order the contributions arrived in.
@@ -813,8 +816,15 @@ __global__ void __launch_bounds__(256) k_det_fold(PpoDev P) {
     const int64_t n = P.num_params + 10;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const long long q = P.det64[i];
-        if (q == 0) continue;
         float *t = i < P.num_params + 2 ? P.grads + i : i < P.num_params + 6 ? P.loss_acc + (i - P.num_params - 2) : P.adv_partial + (i - P.num_params - 6);
+        if (i == P.num_params + 4 || i == P.num_params + 5) {          // a squared gradient norm: two words (det_add_norm)
+            const long long ql = P.det64[i + 6];
+            if (q == 0 && ql == 0) continue;
+            *t += (float)((double)q * (LG_DET_NORM_SPLIT / LG_DET_SCALE) + (double)ql * (1.0 / LG_DET_SCALE));
+            P.det64[i] = 0; P.det64[i + 6] = 0;
+            continue;
+        }
+        if (q == 0) continue;
         *t += (float)((double)q * (1.0 / LG_DET_SCALE));
         P.det64[i] = 0;
     }
@@ -837,6 +847,9 @@ __global__ void __launch_bounds__(256) k_opt_adam(PpoDev P, int par) {
     const float total = sqrtf(P.loss_acc[2 + par]);
     const float coef = fminf(P.max_grad_norm / (total + 1e-6f), 1.0f);
     const float lr = P.stats[0], t = P.stats[4];
+    // fp32 corrections: 0.999f is 1.3e-8 above 0.999 and 1 - 0.999^t cancels while t << 1000, so the step is up to 6.6e-6 + 3e-5 / t short
+    // or long of torch's (whose corrections are formed in double) -- inside the 1e-4 of a step this learner is held to; measured and
+    // bounded in tests/ppo_opt_ref.py (bc_allowance)
     const float bc1 = 1.0f - powf(0.9f, t), bc2 = 1.0f - powf(0.999f, t);
     const float inv_world = 1.0f / (float)P.world;
     for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < P.num_params; k += (int64_t)gridDim.x * blockDim.x) {

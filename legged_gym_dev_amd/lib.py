@@ -74,6 +74,7 @@ def _declare_ppo(lib):
     lib.lg_ppo_reset_hidden.argtypes = [vp, vp]
     lib.lg_ppo_debug_bucket_extents.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.lg_ppo_debug_mb_sets.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+    lib.lg_ppo_debug_weight_planes.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(vp)]
 
 
 _TORCH_DT = {"f4": "float32", "u1": "uint8", "i8": "int64", "i4": "int32"}

@@ -283,6 +283,16 @@ class HipPPO:
                   ("scalars", (R, 4)))
         return tuple({k: device_tensor(ptrs[i], s, "f4", self, self.device) for i, (k, s) in enumerate(shapes)} for ptrs in (cur, other))
 
+    def debug_weight_planes(self):
+        """lg_ppo_debug_weight_planes (tests of the optimiser step): (planes, pl_dest, pl_stride) as zero-copy views -- planes =
+        bfloat16 [3 * pl_stride + 8] (h at 0, m at pl_stride, l at 2 * pl_stride, 8 trailing elements), pl_dest = int32 [num_params]
+        element index of each parameter inside a plane, -1 where a parameter has no image."""
+        wpl, dest, stride = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._call("debug_weight_planes", C.byref(wpl), C.byref(stride), C.byref(dest))
+        n = 3 * stride.value + 8                    # segments are whole 16-byte chunks: an even number of 2-byte elements
+        planes = device_tensor(wpl.value, (n // 2,), "i4", self, self.device).view(torch.bfloat16)
+        return planes, device_tensor(dest.value, (self.num_params,), "i4", self, self.device), int(stride.value)
+
     def params_changed(self):
         """Call after writing parameters through ``param_views`` / ``t["params"]``: the rollout's weight images are re-derived
         by the next act() (also in the middle of a rollout)."""

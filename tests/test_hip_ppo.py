@@ -10,7 +10,9 @@ head kernel, in tests/test_hip_ppo_loss.py (inputs: tests/ppo_loss_ref.py, their
 The rollout half is checked against float64 elsewhere: act() on every dispatch path of the one-launch forward and on the per-layer path,
 with per-action std, a numpy Philox and derived log-prob bounds, in tests/test_hip_ppo_act.py (tests/ppo_act_ref.py,
 tests/test_ppo_act_host.py); process_env_step, GAE, the advantage moments and the episode bookkeeping in tests/test_hip_ppo_returns.py
-(tests/ppo_rollout_ref.py, tests/test_ppo_rollout_host.py); the minibatch gathers and the gather-ahead in tests/test_hip_ppo_gather.py."""
+(tests/ppo_rollout_ref.py, tests/test_ppo_rollout_host.py); the minibatch gathers and the gather-ahead in tests/test_hip_ppo_gather.py.
+The optimiser step (lr rule and clamps, clip, Adam, world, late steps, weight planes, deterministic norm) against float64 is in
+tests/test_hip_ppo_opt.py (tests/ppo_opt_ref.py, tests/test_ppo_opt_host.py)."""
 import numpy as np
 import pytest
 import torch
