@@ -1,9 +1,12 @@
 """GPU parity tests of the environment step: every call goes through the C-ABI of
 liblegged_hip.so.  (1) fixtures produced by the reference's own Python, (2) the CPU oracle on the
-same seeded inputs, (3) size-independent properties at the BASELINE size (4096 envs)."""
+same seeded inputs, (3) size-independent properties at the BASELINE size (4096 envs), (4) the comparisons of (2) again at env
+counts that are a whole number of no tile (tests/env_ragged_ref.py: 1, 7, 17, 47, 65 -- the ragged last tile of k_post_step, the
+dead lanes of k_substeps in each block shape, the scalar tail of finalize_body, the last block of the reset kernels)."""
 import numpy as np
 import pytest
 
+from tests import env_ragged_ref as rr
 from tests import harness
 
 pytestmark = pytest.mark.gpu
@@ -22,43 +25,8 @@ def test_hip_replays_reference_steps(name):
 
 
 def _pair(name, oracle_built, n=None):
-    z, meta = harness.load_fixture(name)
-    cfg = harness.make_cfg(name)
-    if n:
-        cfg.env.num_envs = n
-        meta = dict(meta, num_envs=n)
-    from legged_gym_dev_amd.envs.base.env_setup import EnvSetup, sim_dt_float
-    from legged_gym_dev_amd.model.robot_model import compile_model, resolve_model
-    cm = compile_model(resolve_model("", meta["robot"]))
-    terrain = harness.FixtureTerrain(z, meta, cfg) if "const_height_samples" in z.files else None
-    hs = z["const_height_samples"] if terrain else None
-
-    def mk():
-        return EnvSetup(cfg, cm, sim_dt_float(cfg.sim.dt), terrain=terrain, seed=7)
+    mk, hs, z, meta = rr.pair_inputs(name, n)
     return harness.HipHandle(mk(), hs), oracle_built.OracleEnv(mk(), hs), z, meta
-
-
-def _seed_state(envs, rng, n, A, z0, origins=None, spread=0.02):
-    root = np.zeros((n, 13), np.float32)
-    root[:, 2] = z0 + rng.uniform(-spread, 0.15, n)
-    if origins is not None:
-        root[:, :3] += origins
-        root[:, :2] += rng.uniform(-2, 2, (n, 2))
-    ang = rng.uniform(-0.3, 0.3, (n, 3))
-    qw = np.sqrt(np.maximum(1 - (ang ** 2).sum(1) / 4, 0))
-    root[:, 3:6], root[:, 6] = ang / 2, qw
-    root[:, 3:7] /= np.linalg.norm(root[:, 3:7], axis=1, keepdims=True)
-    root[:, 7:13] = rng.uniform(-0.5, 0.5, (n, 6))
-    dof = np.zeros((n, A, 2), np.float32)
-    dof[..., 0] = envs[0].setup.default_dof_pos + rng.uniform(-0.2, 0.2, (n, A))
-    dof[..., 1] = rng.uniform(-1, 1, (n, A))
-    fr = rng.uniform(0.2, 1.2, n).astype(np.float32)
-    dm = rng.uniform(-5, 5, n).astype(np.float32)
-    for e in envs:
-        e.set("root_states", root)
-        e.set("dof_state", dof)
-        e.set("friction", fr)
-        e.set("base_mass_delta", dm)
 
 
 @pytest.mark.parametrize("name,z0", [("anymal_c_flat", 0.50), ("anymal_c_rough", 0.55), ("cassie", 0.85),
@@ -68,27 +36,28 @@ def test_physics_substep_matches_oracle(name, z0, oracle_built):
     Tolerance: 2e-4 abs/rel on state, 0.5 N + 2e-3 rel on contact forces (fp32, different
     summation order at the base).  anymal_c_randomised: per-env restitution / compliance / thickness (lg_buffers.material) live in
     the contact law."""
-    hip, ora, z, meta = _pair(name, oracle_built, n=256)
+    _check_physics_substep(name, z0, 256, oracle_built)
+
+
+@pytest.mark.parametrize("name,z0,n", rr.SUBSTEP_CASES)
+def test_physics_substep_matches_oracle_at_ragged_counts(name, z0, n, oracle_built):
+    """The same comparison, same bands, with dead lanes in the last (or only) block of k_substeps: they integrate the root of env
+    N - 1 with the joints of another env next to live lanes and must leave no trace.  Env N - 1 is in ground contact;
+    anymal_c_randomised: its material row is the one the dead lanes read too."""
+    _check_physics_substep(name, z0, n, oracle_built)
+
+
+def _check_physics_substep(name, z0, n, oracle_built):
+    mk, hs, z, meta = rr.pair_inputs(name, n)
+    rr.events_first(lambda: oracle_built.OracleEnv(mk(), hs), lambda envs: rr.drive_substeps(envs, name, z0, n, z, meta),
+                    rr.assert_substep_events, n)
+    hip, ora = harness.HipHandle(mk(), hs), oracle_built.OracleEnv(mk(), hs)
     try:
-        rng = np.random.default_rng(3)
-        n, A = 256, meta["num_dofs"]
         if name == "anymal_c_randomised":
             assert hip.core.cfg_struct.material_rand == 1
-            mat = np.zeros((n, 4), np.float32)
-            mat[:, 0], mat[:, 1], mat[:, 2] = rng.uniform(0, 1, n), rng.uniform(0, 2e-6, n), rng.uniform(0, 0.03, n)
-            mat[::7] = 0.0
-            for e in (hip, ora):
-                e.set("material", mat)
-        origins = z["const_env_origins_init"][rng.integers(0, len(z["const_env_origins_init"]), n)] if meta["custom_origins"] else None
-        _seed_state([hip, ora], rng, n, A, z0, origins)
-        tau = rng.uniform(-20, 20, (n, A)).astype(np.float32)
-        n_contact = 0
-        for step in range(6):
-            for e in (hip, ora):
-                e.set("torques", tau)
-                e.call("simulate")
+
+        def check(step):
             cf_h, cf_o = hip.get("contact_forces"), ora.get("contact_forces")
-            n_contact += int((np.abs(cf_o).sum(-1) > 0).sum())
             np.testing.assert_allclose(hip.get("root_states"), ora.get("root_states"), rtol=2e-4, atol=2e-4)
             # Joint state: 2e-4 like the root.  What may leave that band -- asserted as stated -- is a joint RATE of an
             # environment that is in ground contact during this substep (the projected-Jacobi sweeps clamp impulses to the
@@ -106,10 +75,8 @@ def test_physics_substep_matches_oracle(name, z0, oracle_built):
             assert in_contact[np.nonzero(out)[0]].all(), "a joint rate of an env without ground contact left the 2e-4 band"
             assert (err[..., 1] <= 2e-3 + 2e-3 * np.abs(do[..., 1])).all(), err[..., 1].max()
             np.testing.assert_allclose(cf_h, cf_o, rtol=2e-3, atol=0.5)
-            # re-synchronise so fp32 drift does not accumulate across steps (chaotic contacts)
-            hip.set("root_states", ora.get("root_states"))
-            hip.set("dof_state", ora.get("dof_state"))
-        assert n_contact > 100, "test state never touched the ground"
+        log = rr.drive_substeps([hip, ora], name, z0, n, z, meta, check)
+        rr.assert_substep_events(log, n)
     finally:
         hip.close()
         ora.close()
@@ -127,7 +94,7 @@ def test_fallen_robots_match_oracle(name, min_bodies, oracle_built):
         rng = np.random.default_rng(17)
         n, A = 256, meta["num_dofs"]
         origins = z["const_env_origins_init"][rng.integers(0, len(z["const_env_origins_init"]), n)] if meta["custom_origins"] else None
-        _seed_state([hip, ora], rng, n, A, 0.10, origins)
+        rr.seed_state([hip, ora], rng, n, A, 0.10, origins)
         root = ora.get("root_states").copy()
         q = rng.normal(size=(n, 4)).astype(np.float32)                     # any orientation
         root[:, 3:7] = q / np.linalg.norm(q, axis=1, keepdims=True)
@@ -163,29 +130,52 @@ def test_fallen_robots_match_oracle(name, min_bodies, oracle_built):
 def test_full_step_philox_matches_oracle(name, oracle_built):
     """lg_step with the built-in Philox streams (no injection) vs the oracle on the same seed:
     masks / counters bit-exact, fp32 state within tolerance per policy step."""
-    hip, ora, z, meta = _pair(name, oracle_built, n=128)
+    _check_full_step(name, 128, oracle_built)
+
+
+@pytest.mark.parametrize("name,n", rr.FULL_STEP_CASES)
+def test_full_step_philox_matches_oracle_at_ragged_counts(name, n, oracle_built):
+    """The same comparison at env counts off every tile (tests/env_ragged_ref.py): env N - 1 times out on the second step, a step
+    without a reset follows the last one with (extras_time_outs keeps the stale mask), bodies touch the ground, and reset_all has
+    actuator-net state to clear in every row."""
+    _check_full_step(name, n, oracle_built)
+
+
+@pytest.mark.parametrize("name,shape,n", rr.SHAPE_CASES)
+def test_full_step_block_shapes_match_oracle_at_ragged_counts(name, shape, n, oracle_built):
+    """The block shapes of k_substeps that a robot does not take by default, each against the ORACLE
+    (test_control_loop_block_shapes_are_bit_identical compares them with the default shape only).  Quadruped: blocks of 2 waves and
+    8 envs (LG_SUBSTEPS_NW=2) and the build for two waves per SIMD; 7 envs sit below every block, 47 leave 7 (2 waves) or 15 (4 waves)
+    in the last one.  Cassie runs 2-wave blocks of 16 envs by default (its plain ragged cases), so here it takes the 4-wave block of
+    32 envs (LG_SUBSTEPS_NW=4): 7 below the block, 47 = 32 + 15."""
+    _check_full_step(name, n, oracle_built, shape=shape)
+
+
+def _check_full_step(name, n, oracle_built, shape=None):
+    """Added to what the comparison always asserted: extras_time_outs (bytes), extras_episode (1e-3 rel, as HIP-vs-oracle extras
+    after glued steps are compared in test_declared_extra_term_equals_the_builtin_it_mirrors), on the curriculum tasks
+    extras_terrain_level (1e-5 rel, the fixture replay's) and with a height scan measured_heights (1e-6, the product-env
+    comparison's), the fault / velocity-clamp counters (equal), and after reset_all the actuator-net state (zero)."""
+    mk, hs, z, meta = rr.pair_inputs(name, n)
+    rr.events_first(lambda: oracle_built.OracleEnv(mk(), hs), lambda envs: rr.drive_full_step(envs, name, n, z, meta),
+                    rr.assert_full_step_events, n)
+    hip, ora = harness.HipHandle(mk(), hs), oracle_built.OracleEnv(mk(), hs)
+    lib = hip.core.lib
     try:
-        rng = np.random.default_rng(5)
-        n, A = 128, meta["num_dofs"]
-        for e in (hip, ora):
-            if meta["custom_origins"]:
-                e.set("env_origins", z["const_env_origins_init"][np.arange(n) % len(z["const_env_origins_init"])])
-                e.set("terrain_levels", z["const_terrain_levels_init"][np.arange(n) % len(z["const_terrain_levels_init"])])
-                e.set("terrain_types", z["const_terrain_types"][np.arange(n) % len(z["const_terrain_types"])])
-            e.set_step_counter(0)
-            e.inject(0)
-            e.call("reset_all")
-        np.testing.assert_allclose(hip.get("root_states"), ora.get("root_states"), rtol=1e-6, atol=1e-6)
-        np.testing.assert_allclose(hip.get("dof_state"), ora.get("dof_state"), rtol=1e-6, atol=1e-6)
-        ep = rng.integers(0, 1000, n)
-        ep[:8] = [199, 499, 999, 1000, 1001, 399, 0, 1]
-        for e in (hip, ora):
-            e.set("episode_length", ep)
-            e.set_step_counter(748)                     # a push (751) falls inside the window
-        for t in range(4):
-            act = rng.uniform(-1, 1, (n, A)).astype(np.float32)
-            hip.step(act)
-            ora.step(act)
+        A = meta["num_dofs"]
+        if shape:
+            switch, value = rr.SHAPE_SWITCH[shape]
+            getattr(lib, "lg_debug_set_substeps_" + switch)(value)
+
+        def after_reset_all():
+            np.testing.assert_allclose(hip.get("root_states"), ora.get("root_states"), rtol=1e-6, atol=1e-6)
+            np.testing.assert_allclose(hip.get("dof_state"), ora.get("dof_state"), rtol=1e-6, atol=1e-6)
+            if meta["use_lstm"]:
+                for key in ("lstm_h", "lstm_c"):
+                    v = hip.get(key)
+                    assert v.size == n * A * 8 * 2 and not v.any(), f"{key} after reset_all"
+
+        def check(t):
             np.testing.assert_array_equal(hip.get("reset"), ora.get("reset"), err_msg=f"step {t} reset")
             np.testing.assert_array_equal(hip.get("time_out"), ora.get("time_out"))
             np.testing.assert_array_equal(hip.get("episode_length"), ora.get("episode_length"))
@@ -194,11 +184,20 @@ def test_full_step_philox_matches_oracle(name, oracle_built):
             for key, tol in (("obs", 2e-3), ("rew", 2e-3), ("root_states", 1e-3), ("dof_state", 2e-3),
                              ("commands", 1e-6), ("torques", 5e-3)):
                 np.testing.assert_allclose(hip.get(key), ora.get(key), rtol=tol, atol=tol, err_msg=f"step {t} {key}")
-            # keep the two trajectories glued together (contacts amplify fp32 noise)
-            for key in ("root_states", "dof_state", "lstm_h", "lstm_c", "last_dof_vel", "last_root_vel",
-                        "feet_air_time", "episode_sums"):
-                hip.set(key, ora.get(key))
+            np.testing.assert_array_equal(hip.get("extras_time_outs"), ora.get("extras_time_outs"), err_msg=f"step {t} extras_time_outs")
+            np.testing.assert_allclose(hip.get("extras_episode"), ora.get("extras_episode"), rtol=1e-3, atol=1e-6, err_msg=f"step {t} extras_episode")
+            if meta["curriculum"]:
+                np.testing.assert_allclose(hip.get("extras_terrain_level"), ora.get("extras_terrain_level"), rtol=1e-5, err_msg=f"step {t}")
+            if hip.setup.num_height_points:
+                np.testing.assert_allclose(hip.get("measured_heights"), ora.get("measured_heights"), rtol=1e-6, atol=1e-6, err_msg=f"step {t} heights")
+            for key in ("n_fault", "n_vel_clamp", "fault_total", "vel_clamp_total"):
+                assert int(hip.get(key)[0]) == int(ora.get(key)[0]), f"step {t} {key}"
+        log = rr.drive_full_step([hip, ora], name, n, z, meta, after_reset_all, check)
+        if rr.ragged(n):
+            rr.assert_full_step_events(log, n)
     finally:
+        lib.lg_debug_set_substeps_nw(0)                            # back to the default: by topology
+        lib.lg_debug_set_substeps_occ(0)                           # ... and by grid size
         hip.close()
         ora.close()
 
@@ -440,59 +439,54 @@ def test_env_shards_equal_the_unsharded_run():
             e.close()
 
 
-def _glue(hip, ora, keys=("root_states", "dof_state", "lstm_h", "lstm_c", "last_dof_vel", "last_root_vel", "feet_air_time",
-                          "episode_sums", "commands", "last_actions")):
-    for key in keys:
-        hip.set(key, ora.get(key))
-
-
 @pytest.mark.parametrize("name", ["anymal_c_flat", "anymal_c_rough", "cassie"])
 def test_reset_ids_matches_oracle(name, oracle_built):
     """lg_reset_ids = LeggedRobot.reset_idx(env_ids) for a caller-given subset (legged_robot.py:147-187, the indexed state
     writes of :428,452): state, commands, buffers, actuator-net state, terrain level / origin and the extras of the subset
     equal the oracle's reset_idx on the same ids and the same Philox slots; envs outside the subset are untouched."""
+    _check_reset_ids(name, 96, oracle_built)
+
+
+@pytest.mark.parametrize("name,n", rr.RESET_IDS_CASES)
+def test_reset_ids_matches_oracle_at_ragged_counts(name, n, oracle_built):
+    """The same with env 0, env N - 1, an id of the last full post-step tile and one of the partial tile in the list, and then a
+    second call that resets ALL N ids (k_reset_ids and finalize_body over the whole ragged range, nothing left outside)."""
+    _check_reset_ids(name, n, oracle_built)
+
+
+def _check_reset_ids(name, n, oracle_built):
+    import ctypes as C
     import torch
-    hip, ora, z, meta = _pair(name, oracle_built, n=96)
+    hip, ora, z, meta = _pair(name, oracle_built, n=n)
     try:
-        rng = np.random.default_rng(12)
-        n, A = 96, meta["num_dofs"]
-        for e in (hip, ora):
-            if meta["custom_origins"]:
-                e.set("env_origins", z["const_env_origins_init"][np.arange(n) % len(z["const_env_origins_init"])])
-                e.set("terrain_levels", z["const_terrain_levels_init"][np.arange(n) % len(z["const_terrain_levels_init"])])
-                e.set("terrain_types", z["const_terrain_types"][np.arange(n) % len(z["const_terrain_types"])])
-            e.set_step_counter(0)
-            e.inject(0)
-            e.call("reset_all")
-        for t in range(3):
-            act = rng.uniform(-1, 1, (n, A)).astype(np.float32)
-            hip.step(act)
-            ora.step(act)
-            _glue(hip, ora)
-        if meta["custom_origins"]:                          # walk some robots far enough for the curriculum to move them
-            root = ora.get("root_states")
-            root[::5, 0] += 5.0
-            for e in (hip, ora):
-                e.set("root_states", root)
-        ids = np.array(sorted(rng.choice(n, 17, replace=False)), np.int32)
-        before = {k: hip.get(k) for k in ("root_states", "dof_state", "commands", "episode_length", "episode_sums")}
-        ids_dev = torch.as_tensor(ids, device="cuda")
-        import ctypes as C
-        hip.core.call("reset_ids", C.c_void_p(ids_dev.data_ptr()), len(ids))
-        ora.call("reset_ids", ids.ctypes.data, len(ids))
-        for key in ("reset", "episode_length", "terrain_levels", "n_reset"):
-            np.testing.assert_array_equal(hip.get(key), ora.get(key), err_msg=key)
-        assert int(hip.get("n_reset")[0]) == 17
-        for key in ("root_states", "dof_state", "commands", "last_actions", "last_dof_vel", "feet_air_time", "env_origins",
-                    "episode_sums", "lstm_h", "lstm_c"):
-            np.testing.assert_allclose(hip.get(key), ora.get(key), rtol=1e-6, atol=1e-6, err_msg=key)
-        np.testing.assert_allclose(hip.get("extras_episode"), ora.get("extras_episode"), rtol=1e-4, atol=1e-6)
-        np.testing.assert_array_equal(hip.get("extras_time_outs"), ora.get("extras_time_outs"))
-        rest = np.setdiff1d(np.arange(n), ids)
-        for key in ("root_states", "dof_state", "commands", "episode_length"):
-            np.testing.assert_array_equal(hip.get(key)[rest], before[key][rest], err_msg=f"{key} outside the subset")
-        np.testing.assert_array_equal(hip.get("episode_sums")[:, rest], before["episode_sums"][:, rest])
-        assert (hip.get("episode_length")[ids] == 0).all() and (hip.get("dof_state")[ids][..., 1] == 0).all()
+        rng = rr.drive_reset_ids_prologue([hip, ora], name, n, z, meta)
+        lists = [rr.reset_id_list(rng, n)]
+        if rr.ragged(n):
+            lists.append(np.arange(n, dtype=np.int32))
+        else:
+            assert len(lists[0]) == 17
+        for ids in lists:
+            before = {k: hip.get(k) for k in ("root_states", "dof_state", "commands", "episode_length", "episode_sums")}
+            ids_dev = torch.as_tensor(ids, device="cuda")
+            hip.core.call("reset_ids", C.c_void_p(ids_dev.data_ptr()), len(ids))
+            ora.call("reset_ids", ids.ctypes.data, len(ids))
+            for key in ("reset", "episode_length", "terrain_levels", "n_reset"):
+                np.testing.assert_array_equal(hip.get(key), ora.get(key), err_msg=key)
+            assert int(hip.get("n_reset")[0]) == len(ids)
+            for key in ("root_states", "dof_state", "commands", "last_actions", "last_dof_vel", "feet_air_time", "env_origins",
+                        "episode_sums", "lstm_h", "lstm_c"):
+                np.testing.assert_allclose(hip.get(key), ora.get(key), rtol=1e-6, atol=1e-6, err_msg=key)
+            np.testing.assert_allclose(hip.get("extras_episode"), ora.get("extras_episode"), rtol=1e-4, atol=1e-6)
+            np.testing.assert_array_equal(hip.get("extras_time_outs"), ora.get("extras_time_outs"))
+            if meta["curriculum"]:
+                np.testing.assert_allclose(hip.get("extras_terrain_level"), ora.get("extras_terrain_level"), rtol=1e-5)
+            for key in ("n_fault", "n_vel_clamp", "fault_total", "vel_clamp_total"):
+                assert int(hip.get(key)[0]) == int(ora.get(key)[0]), key
+            rest = np.setdiff1d(np.arange(n), ids)
+            for key in ("root_states", "dof_state", "commands", "episode_length"):
+                np.testing.assert_array_equal(hip.get(key)[rest], before[key][rest], err_msg=f"{key} outside the subset")
+            np.testing.assert_array_equal(hip.get("episode_sums")[:, rest], before["episode_sums"][:, rest])
+            assert (hip.get("episode_length")[ids] == 0).all() and (hip.get("dof_state")[ids][..., 1] == 0).all()
         hip.core.call("reset_ids", None, 0)                 # empty list: early return (legged_robot.py:156-157)
     finally:
         hip.close()
@@ -788,7 +782,7 @@ def test_rollout_properties_at_baseline_size_on_terrain(task, z_lo, z_hi):
 
 
 # ------------------------------------------------------------------------------------------------ trajectory-tracking variant
-TRAJ = "anymal_c_flat_trajectory"
+TRAJ = rr.TRAJ
 
 
 @pytest.mark.parametrize("name", [TRAJ, "anymal_c_flat_trajectory_curriculum", "anymal_c_rough_trajectory"])
@@ -814,41 +808,29 @@ def test_trajectory_env_full_step_philox_matches_oracle(oracle_built):
     """lg_step of the trajectory env with its own Philox streams vs the oracle on the same seed over 30 policy steps (clocks
     scattered so that generator resamples, ROM steps, pushes, time-outs and resets all occur): masks, counters and the
     generator's discrete state bit-exact, fp32 state within tolerance (re-glued every step)."""
-    z, meta = harness.load_fixture(TRAJ)
-    cfg = harness.make_cfg(TRAJ)
-    n = cfg.env.num_envs = 128
-    from legged_gym_dev_amd.envs.base.env_setup import EnvSetup, sim_dt_float
-    from legged_gym_dev_amd.model.robot_model import compile_model, resolve_model
-    cm = compile_model(resolve_model("", "anymal_c"))
+    _check_trajectory_full_step(128, oracle_built)
 
-    def mk():
-        return EnvSetup(cfg, cm, sim_dt_float(cfg.sim.dt), seed=17, extra_terms=harness.extra_terms_for(cfg))
+
+@pytest.mark.parametrize("n", rr.TRAJ_COUNTS)
+def test_trajectory_env_full_step_matches_oracle_at_ragged_counts(n, oracle_built):
+    """The same at 1, 17 and 65 envs: the last block of k_traj_reset (64 envs per block) and of k_traj_late, the generator state
+    of env N - 1, which times out on the second step."""
+    _check_trajectory_full_step(n, oracle_built)
+
+
+def _check_trajectory_full_step(n, oracle_built):
+    mk = rr.traj_inputs(n)
+    rr.events_first(lambda: oracle_built.OracleEnv(mk()), lambda envs: rr.drive_trajectory(envs, n), rr.assert_trajectory_events, n)
     hip, ora = harness.HipHandle(mk()), oracle_built.OracleEnv(mk())
     try:
-        rng = np.random.default_rng(6)
-        tg = np.zeros((n, capi_TG_STRIDE()), np.float32)
         o = _tgf()
-        tg[:, o["ramp_v_end"][0]:o["ramp_v_end"][0] + 2] = rng.uniform(-0.35, 0.35, (n, 2))
-        for e in (hip, ora):
-            e.set("tg_state", tg)
-            e.set("push_timer", rng.uniform(0.0, 0.5, n).astype(np.float32) if e is hip else hip.get("push_timer"))
-            e.set_step_counter(0)
-            e.inject(0)
-            e.call("reset_all")
-        for key in ("tg_state", "tg_traj", "root_states", "dof_state", "prev_error"):
-            np.testing.assert_allclose(hip.get(key), ora.get(key), rtol=1e-6, atol=1e-6, err_msg=f"after reset_all: {key}")
-        ep = rng.integers(0, 1000, n)
-        ep[:4] = [1000, 1001, 999, 3]
-        for e in (hip, ora):
-            e.set("episode_length", ep)
-        seen = {"reset": 0, "pushed": 0, "resampled": 0, "rom": 0}
-        for t in range(30):
-            act = rng.uniform(-1, 1, (n, 12)).astype(np.float32)
-            before = ora.get("tg_state").copy()
-            pt_before = ora.get("push_timer").copy()
-            hip.step(act)
-            ora.step(act)
-            for key in ("reset", "time_out", "episode_length"):
+
+        def after_reset_all():
+            for key in ("tg_state", "tg_traj", "root_states", "dof_state", "prev_error"):
+                np.testing.assert_allclose(hip.get(key), ora.get(key), rtol=1e-6, atol=1e-6, err_msg=f"after reset_all: {key}")
+
+        def check(t):
+            for key in ("reset", "time_out", "episode_length", "extras_time_outs"):
                 np.testing.assert_array_equal(hip.get(key), ora.get(key), err_msg=f"step {t} {key}")
             assert int(hip.get("n_reset")[0]) == int(ora.get("n_reset")[0])
             gh, go = hip.get("tg_state"), ora.get("tg_state")
@@ -864,15 +846,8 @@ def test_trajectory_env_full_step_philox_matches_oracle(oracle_built):
                 d = np.abs(x - y)
                 bad = d > 2e-3 + 2e-3 * np.abs(y)
                 assert bad.mean() < 2e-3 and d.max() < 5e-2 * max(1.0, np.abs(y).max()), f"step {t} {key}: {int(bad.sum())} of {bad.size}, max {d.max():.3g}"
-            rst = ora.get("reset").astype(bool)
-            seen["reset"] += int(rst.sum())
-            seen["pushed"] += int((ora.get("push_timer") > pt_before).sum())
-            seen["resampled"] += int(((go[:, o["t_final"][0]] != before[:, o["t_final"][0]]) & ~rst).sum())
-            seen["rom"] += int(((go[:, o["k"][0]] != before[:, o["k"][0]]) & ~rst).sum())
-            for key in ("root_states", "dof_state", "lstm_h", "lstm_c", "last_dof_vel", "last_root_vel", "feet_air_time",
-                        "episode_sums", "tg_state", "tg_traj", "trajectory", "prev_error", "push_timer"):
-                hip.set(key, ora.get(key))
-        assert seen["reset"] > 5 and seen["pushed"] > 20 and seen["resampled"] > 10 and seen["rom"] > 500, seen
+        log = rr.drive_trajectory([hip, ora], n, after_reset_all, check)
+        rr.assert_trajectory_events(log, n)
     finally:
         hip.close()
         ora.close()
@@ -1002,11 +977,6 @@ def test_staged_curriculum_through_the_product_env(oracle_built):
     finally:
         hip.close()
         ora.close()
-
-
-def capi_TG_STRIDE():
-    from legged_gym_dev_amd import capi
-    return capi.TG_STRIDE
 
 
 def _tgf():
