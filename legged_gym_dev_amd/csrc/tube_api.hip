@@ -2,6 +2,7 @@
 // permutation, the two launches of a training step, the eval launch, and the inference entries: predict, window prediction and
 // the closed-loop roll-outs, single-tap and windowed, and the level entries of a level-conditioned model, flat or horizon (tube_kernels.hip).  lg_tube_sweep_*: K such trainers of one shape on one
 // dataset, stepped by the same two launches with the members along grid y.
+// The planner entries launch plan_kernels.hip through the argument structs of plan_device.h:
 // lg_plan_check / lg_plan_score: plans scored against a one-shot horizon handle or an analytic tube (k_plan_score).
 // The same entry points take the one-step kind LG_PLAN_TUBE_NN_STEP (k_plan_score_step, k_plan_sample_score_step; section 10.13).
 // lg_mppi_check / lg_plan_mppi*: the sampling planner on top of it (k_plan_sample_score, k_plan_mppi_update).
@@ -11,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "tube_device.h"
+#include "plan_device.h"
 #include "../../include/legged_hip.h"
 
 void lg_set_error(const std::string &s);
@@ -42,29 +43,19 @@ void tubek_predict(const TubeDev *D, const float *x, const float *y, const float
 void tubek_rollout(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed, float *o, hipStream_t s);
 void tubek_rollout_window(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, int taps, int dN, int stride,
                           const uint8_t *reseed, float *o, hipStream_t s);
-int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
-                         const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
-                         float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w,
-                         const lg_plan_scenes *sc, hipStream_t s);
+// plan_kernels.hip.  D: the handle's TubeDev, or null for an analytic kind
+int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const PlanArgs *A, int64_t B, hipStream_t s);
+int64_t tubek_plan_score_step(const TubeDev *D, const lg_plan_problem *prob, const PlanArgs *A, int64_t B, hipStream_t s);
 void tubek_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *vbar, int64_t P_, float *out,
                                 hipStream_t s);
-int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
-                                const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
-                                const float *vbar, float *J, float *cost, float *min_clear, float *pen, const lg_plan_scenes *sc,
-                                hipStream_t s);
+int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const PlanArgs *A, int64_t P_,
+                                const float *vbar, float *J, float *pen, hipStream_t s);
+int64_t tubek_plan_sample_score_step(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const PlanArgs *A,
+                                     int64_t P_, const float *vbar, float *J, float *pen, hipStream_t s);
 void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,
                             const float *J, float *best_J, float *best_v, float *hist, int32_t *n_bad, hipStream_t s);
-int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, const lg_plan_scenes *sc,
-                        hipStream_t s);
+int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, hipStream_t s);
 int64_t tubek_plan_step_bytes(const TubeDev *D, const lg_plan_problem *prob);
-int64_t tubek_plan_score_step(const TubeDev *D, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
-                              const float *v_prev, const float *w0, const float *offset, float level, int64_t B, float *cost,
-                              float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w,
-                              const lg_plan_scenes *sc, hipStream_t s);
-int64_t tubek_plan_sample_score_step(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *z0,
-                                     const float *e, const float *v_prev, const float *w0, const float *offset, float level, int64_t P_,
-                                     const float *vbar, float *J, float *cost, float *min_clear, float *pen, const lg_plan_scenes *sc,
-                                     hipStream_t s);
 }
 
 struct TubeCaps {                       // rows that a model's data-sized buffers hold
@@ -504,6 +495,17 @@ int lg_plan_scenes_check(const lg_plan_scenes *sc, int64_t count) {
     return 0;
 }
 
+// what every planner launch takes; the caller adds the outputs its kernel has
+static PlanArgs plan_args(const float *z0, const float *v, const float *e, const float *v_prev, const float *w0, const float *offset,
+                          int32_t has_level, float level, const lg_plan_scenes *scenes) {
+    PlanArgs A;
+    memset(&A, 0, sizeof(A));
+    A.z0 = z0; A.v = v; A.e = e; A.v_prev = v_prev; A.w0 = w0; A.offset = offset;
+    A.level = has_level ? level : 0.f;
+    A.scenes = scenes;
+    return A;
+}
+
 int lg_plan_score(lg_tube *tube, const lg_plan_problem *prob, const float *z0, const float *v, const float *e, const float *v_prev,
                   const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *cost, float *min_clear,
                   int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, void *stream) {
@@ -521,12 +523,11 @@ int lg_plan_score_scenes(lg_tube *tube, const lg_plan_problem *prob, const float
     if (!z0 || !v || !cost || !min_clear || !worst_node || !n_viol) {
         lg_set_error("lg_plan_score: missing array (z0, v, cost, min_clear, worst_node and n_viol are required)"); return -1;
     }
+    PlanArgs A = plan_args(z0, v, e, v_prev, w0, offset, has_level, level, scenes);
+    A.cost = cost; A.min_clear = min_clear; A.worst_node = worst_node; A.n_viol = n_viol; A.fw = fw; A.z = z; A.w = w;
     const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
-    const int64_t rc = prob->tube_kind == LG_PLAN_TUBE_NN_STEP
-        ? tubek_plan_score_step(&tube->dev, prob, z0, v, e, v_prev, w0, offset, has_level ? level : 0.f, B, cost, min_clear, worst_node,
-                                n_viol, fw, z, w, scenes, (hipStream_t)stream)
-        : tubek_plan_score(nn ? &tube->dev : nullptr, prob, z0, v, e, v_prev, w0, offset, has_level ? level : 0.f, B, cost,
-                           min_clear, worst_node, n_viol, fw, z, w, scenes, (hipStream_t)stream);
+    const int64_t rc = prob->tube_kind == LG_PLAN_TUBE_NN_STEP ? tubek_plan_score_step(&tube->dev, prob, &A, B, (hipStream_t)stream)
+                                                               : tubek_plan_score(nn ? &tube->dev : nullptr, prob, &A, B, (hipStream_t)stream);
     if (rc < 0) { lg_set_error("lg_plan_score: hipFuncSetAttribute failed"); return -2; }
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_score: launch failed"), -3);
 }
@@ -587,11 +588,11 @@ int lg_plan_mppi_step_scenes(lg_tube *tube, const lg_plan_problem *prob, const l
     }
     const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
     if (what & 1) {
+        PlanArgs A = plan_args(z0, nullptr, e, v_prev, w0, offset, has_level, level, scenes);
+        A.cost = cost; A.min_clear = min_clear;
         const int64_t rc = prob->tube_kind == LG_PLAN_TUBE_NN_STEP
-            ? tubek_plan_sample_score_step(&tube->dev, prob, cfg, it, z0, e, v_prev, w0, offset, has_level ? level : 0.f, P, vbar, J, cost,
-                                           min_clear, pen, scenes, (hipStream_t)stream)
-            : tubek_plan_sample_score(nn ? &tube->dev : nullptr, prob, cfg, it, z0, e, v_prev, w0, offset, has_level ? level : 0.f,
-                                      P, vbar, J, cost, min_clear, pen, scenes, (hipStream_t)stream);
+            ? tubek_plan_sample_score_step(&tube->dev, prob, cfg, it, &A, P, vbar, J, pen, (hipStream_t)stream)
+            : tubek_plan_sample_score(nn ? &tube->dev : nullptr, prob, cfg, it, &A, P, vbar, J, pen, (hipStream_t)stream);
         if (rc < 0) { lg_set_error("lg_plan_mppi_step: hipFuncSetAttribute failed"); return -2; }
     }
     if (what & 2) tubek_plan_mppi_update(prob, cfg, it, reset_best, P, vbar, J, best_J, best_v, hist_row, n_bad, (hipStream_t)stream);
@@ -647,11 +648,12 @@ int lg_plan_grad_check(const lg_grad_cfg *cfg, const lg_plan_problem *prob, cons
     return 0;
 }
 
-static void grad_args(PlanGradArgs *A, const lg_grad_cfg *cfg, const float *z0, const float *e, const float *v_prev, const float *w0,
-                      const float *offset, int32_t has_level, float level) {
+static void grad_args(PlanGradArgs *A, const lg_grad_cfg *cfg, const PlanArgs &plan, float *J, float *grad, float *cost, float *min_clear,
+                      float *pen) {
     memset(A, 0, sizeof(*A));
-    A->z0 = z0; A->e = e; A->v_prev = v_prev; A->w0 = w0; A->offset = offset;
-    A->level = has_level ? level : 0.f;
+    A->plan = plan;
+    A->plan.cost = cost; A->plan.min_clear = min_clear;
+    A->J = J; A->grad = grad; A->pen = pen;
     A->lr = cfg->lr; A->beta1 = cfg->beta1; A->beta2 = cfg->beta2; A->eps = cfg->eps; A->bc1 = 1.f; A->bc2 = 1.f;
     A->rho_g = cfg->rho_g; A->rho_w = cfg->rho_w; A->rho_z = cfg->rho_z;
 }
@@ -671,11 +673,9 @@ int lg_plan_grad_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_gra
     if (scenes && lg_plan_scenes_check(scenes, B)) return -1;
     if (!z0 || !v || !J || !grad) { lg_set_error("lg_plan_grad: missing array (z0, v, J and grad are required)"); return -1; }
     PlanGradArgs A;
-    grad_args(&A, cfg, z0, e, v_prev, w0, offset, has_level, level);
-    A.v = const_cast<float *>(v);       // read only: no step in this launch
-    A.J = J; A.grad = grad; A.cost = cost; A.min_clear = min_clear; A.pen = pen;
+    grad_args(&A, cfg, plan_args(z0, v, e, v_prev, w0, offset, has_level, level, scenes), J, grad, cost, min_clear, pen);
     const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
-    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, scenes, (hipStream_t)stream) < 0) {
+    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, (hipStream_t)stream) < 0) {
         lg_set_error("lg_plan_grad: hipFuncSetAttribute failed"); return -2;
     }
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_grad: launch failed"), -3);
@@ -706,14 +706,14 @@ int lg_plan_descend_step_scenes(lg_tube *tube, const lg_plan_problem *prob, cons
         lg_set_error("lg_plan_descend_step: missing array (z0, v, J, best_J, best_v and n_bad; m and s for the step)"); return -1;
     }
     PlanGradArgs A;
-    grad_args(&A, cfg, z0, e, v_prev, w0, offset, has_level, level);
-    A.v = v; A.J = J; A.grad = grad; A.cost = cost; A.min_clear = min_clear; A.pen = pen;
+    grad_args(&A, cfg, plan_args(z0, v, e, v_prev, w0, offset, has_level, level, scenes), J, grad, cost, min_clear, pen);
+    A.v = v;
     A.m = m; A.s = s; A.best_J = best_J; A.best_v = best_v; A.hist = hist_row; A.n_bad = n_bad;
     A.step = (what & 2) != 0; A.reset = reset != 0;
     A.bc1 = (float)(1.0 - std::pow((double)cfg->beta1, (double)it + 1.0));     // step index t = it + 1
     A.bc2 = (float)(1.0 - std::pow((double)cfg->beta2, (double)it + 1.0));
     const bool nn = prob->tube_kind == LG_PLAN_TUBE_NN;
-    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, scenes, (hipStream_t)stream) < 0) {
+    if (tubek_plan_grad(nn ? &tube->dev : nullptr, prob, &A, B, (hipStream_t)stream) < 0) {
         lg_set_error("lg_plan_descend_step: hipFuncSetAttribute failed"); return -2;
     }
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_plan_descend_step: launch failed"), -3);

@@ -1,4 +1,4 @@
-// Device-side struct of the tube-model trainer (tube_kernels.hip, tube_api.hip).
+// Device-side struct of the tube-model trainer (tube_kernels.hip, plan_kernels.hip, tube_api.hip).
 #pragma once
 #include "lg_device.h"
 #include "../../include/legged_hip.h"
@@ -38,18 +38,6 @@ struct TubeDev {                        // passed by value to kernels
     int level_input;                    // 1: the last input column is the row's level, drawn per row in [level_lo, level_hi)
     float level_lo, level_hi;
     float *levels;                      // level per row of the last step / eval
-};
-
-struct PlanGradArgs {                   // one launch of k_plan_grad (tube_kernels.hip), filled by tube_api.hip; every array a device pointer
-    const float *z0, *e, *v_prev, *w0, *offset;
-    float *v;                           // (B, N, 2) the plans: read by the gather, written by the step
-    float *J, *grad, *cost, *min_clear, *pen; // J required; the rest optional
-    float *m, *s, *best_J, *best_v, *hist;     // Adam moments (step); elite and history row (optional)
-    int32_t *n_bad;
-    float level;
-    int step, reset;                    // step: the optimiser tail runs; reset: moments, elite and n_bad start afresh
-    float lr, beta1, beta2, eps, bc1, bc2;     // bc = 1 - beta^t of the launch's step index t, rounded once from double
-    float rho_g, rho_w, rho_z;
 };
 
 struct TubeMember {                     // one model of a sweep (lg_tube_sweep); the kernels index a device array of these by blockIdx.y

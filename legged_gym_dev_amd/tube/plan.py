@@ -175,7 +175,7 @@ _STEP_ROWS, _STEP_LDS = 32, 144 * 1024               # LG_TUBE_ROWS, LG_TUBE_ROL
 
 
 def step_tile_bytes(input_dim, units, H_rev, N):
-    """Dynamic LDS of k_plan_score_step's tile without the weights (tube_kernels.hip plan_step_floats)."""
+    """Dynamic LDS of k_plan_score_step's tile without the weights (plan_kernels.hip plan_step_floats)."""
     return 4 * _STEP_ROWS * (((2 * (H_rev + N)) | 1) + ((H_rev + N + 1) | 1) + input_dim + 2 * units + (((N + 1) * 3) | 1))
 
 
