@@ -567,7 +567,11 @@ int lg_tube_set_step(lg_tube *t, int64_t step);    /* Adam / StepLR step count (
 int lg_tube_set_data(lg_tube *t, int which, const float *x, const float *y, const float *v, int64_t rows, int32_t T, int32_t nz,
                      int32_t m);
 int lg_tube_begin_epoch(lg_tube *t, int64_t epoch);   /* a new permutation of the training rows, keyed by (seed, epoch) */
-/* One Adam step on `count` rows: rows (device, count) or NULL = the next count rows of the epoch's permutation. */
+/* One Adam step on `count` rows (1..batch_size): rows (device, count) or NULL = the next count rows of the epoch's permutation.
+ * The ids are not checked on the host.  An id outside [0, rows of the training split) reads nothing: the kernel takes it as a row of
+ * zeros -- zero input, zero target; on a level_input handle its level column is still drawn -- that runs through the model and the
+ * loss like any other and COUNTS in the loss's divisor and in log[3].  With zero biases such a row contributes exactly nothing; in
+ * general it contributes the gradient of the loss at x = 0, w = 0.  Callers that mean to skip rows pass a shorter list. */
 int lg_tube_step(lg_tube *t, const int32_t *rows, int64_t count);
 int lg_tube_eval(lg_tube *t);                      /* metrics of the test split into lg_tube_buffers.eval (one window per row;
                                                       level_input: one drawn level per row) */
