@@ -998,6 +998,74 @@ int lg_plan_descend_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_
                            float *v, float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad,
                            const lg_plan_scenes *scenes, void *stream);
 
+/* ------------------------------------------------------------------ command tracker: ROM trajectories
+ * tracked by a VELOCITY-COMMAND policy, the loop of deep_tube_learning/data_collection_velocity.py:84-156 ("DV").  A SingleInt2D ROM
+ * at rom_dt = the env's dt runs beside the velocity-command env; a proportional law turns its desired pose and velocity into a
+ * body-frame velocity command, written over the three command columns of the observation; the velocity policy does the rest.
+ * One launch per env step, one lane per env, nothing read back.  Per env and step t, fp32 with one rounding per operation:
+ *   v = input(t rom_dt): RANDOM = TrajectoryGenerator.get_input_t with the stationary mask (the LG_TG_* row and the laws of
+ *       csrc/lg_traj.h, the hold time checked on every evaluation); PLAN = plan[env][t], 0 for t >= n_nodes, used as given;
+ *   des = (z_x, z_y, atan2(v_y, v_x)), des_vel = (v_x, v_y, 0)                                  (SingleInt2D.des_pose_vel)
+ *   yaw = atan2(2 (q_x q_y + q_w q_z), q_w^2 + q_x^2 - q_y^2 - q_z^2)   (quat2yaw: the xyz-Euler yaw, for a quaternion of any norm)
+ *   err = des - (x, y, yaw); err[2] = track_yaw ? ((err[2] + pi) mod 2 pi) - pi : 0, mod in the floor sense       (DV:129-130)
+ *   err_local[:2] = [[c, s], [-s, c]] err[:2], des_vel_local[:2] likewise, c = cos yaw, s = sin yaw                (DV:133,138)
+ *   u = min(max(des_vel_local + Kp err_local, u_min), u_max)                                                      (DV:140-141)
+ *   obs[env, cmd_col + j] = u[j] cmd_scale[j]  (DV:144 writes u raw: cmd_scale = 1; the env's own observation holds
+ *                                               command x commands_scale, which is what cmd_scale defaults to on the host)
+ * and, after the env step that consumed command t (DV:149-156): done[t] = the env's reset flag, v[t] = v, u[t] = u,
+ * z[t+1] = done ? root xy : z + rom_dt v, pz_x[t+1] = root xy, x[t+1] = get_state().  The next step's ROM state is z[t+1].  The
+ * generator is not reset on a done.  The env's commands buffer, rewards and heading logic are not touched.
+ * Records are ENV-MAJOR -- z, pz_x (N, T+1, 2), v (N, T, 2), done (N, T), u (N, T, 3), x (N, T+1, x_n) -- the layout of
+ * lg_romsim_collect and the epoch pickles; DV's own arrays are time-major.
+ * Draws (RANDOM): lg_romsim's keys, Philox (seed, env_offset + env, epoch << 32 | event, slot) with event 0 = the begin
+ * (LG_RS_SLOT_RAMP only, at the tracker's first begin) and event r + 1 = the env's r-th resample since the begin; with
+ * lg_cmdtrack_inject they are read from lg_cmdtrack_buffers.inject in lg_romsim_inject's block layout.
+ * Lifetime: the tracker holds no pointer into the env -- every entry that touches the device takes the env and borrows its
+ * buffers and stream for that call alone -- so either may be destroyed first; an entry refuses an env of other dimensions than
+ * the one the tracker was created for. */
+typedef struct lg_cmdtrack_cfg {
+    int32_t kind /*LG_TG_KIND_RANDOM | LG_TG_KIND_PLAN*/, track_yaw, cmd_col /*9 for every LeggedRobot observation*/;
+    int32_t weight_sampler /*LG_TG_WSAMP_**/, tg_N /*ROM steps of TrajectoryGenerator.reset's pre-roll, 1..LG_TRAJ_MAX_PTS-1*/;
+    int32_t x_n;                          /* floats per row of the optional x record: 0, or the env's 13 + 2 num_actions */
+    uint64_t seed;
+    float Kp[9];                          /* row-major 3 x 3 */
+    float u_min[3], u_max[3], cmd_scale[3];
+    float rom_v_min[2], rom_v_max[2];
+    float t_low, t_high, freq_low, freq_high, prob_stationary, _padf;
+} lg_cmdtrack_cfg;
+typedef struct lg_cmdtrack_rec {          /* caller-owned DEVICE buffers of one epoch */
+    int32_t T, _pad;
+    float *z, *v, *pz_x;                  /* (N, T+1, 2), (N, T, 2), (N, T+1, 2) */
+    uint8_t *done;                        /* (N, T) */
+    float *u;                             /* (N, T, 3) or NULL */
+    float *x;                             /* (N, T+1, x_n) or NULL */
+} lg_cmdtrack_rec;
+typedef struct lg_cmdtrack_buffers {
+    float *state;                         /* (N, 8): z 2, v 2, u 3 of the command in force, 1 unused */
+    float *tg_state;                      /* (N, LG_TG_STRIDE) */
+    float *plan;                          /* (N, LG_PLAN_MAX_N, 2) */
+    float *inject;                        /* (N, inject_K) or NULL before lg_cmdtrack_inject */
+    int32_t *n_resample, *inject_overrun; /* (N) each: resamples since the begin; resamples that found the injected blocks used up */
+    int64_t inject_K;                     /* LG_RS_NRESET + R LG_TG_NDRAW */
+} lg_cmdtrack_buffers;
+typedef struct lg_cmdtrack lg_cmdtrack;
+/* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error ("lg_cmdtrack: ...").  rec may be NULL (the
+ * configuration alone).  env_traj: the env is a trajectory env (refused); num_obs, env_x_n: the env's. */
+int lg_cmdtrack_check(const lg_cmdtrack_cfg *cfg, const lg_cmdtrack_rec *rec, int32_t env_traj, int32_t num_obs, int32_t env_x_n);
+int lg_cmdtrack_create(lg_ctx *env, const lg_cmdtrack_cfg *cfg, lg_cmdtrack **out);
+int lg_cmdtrack_destroy(lg_cmdtrack *tr);
+int lg_cmdtrack_get_buffers(lg_cmdtrack *tr, lg_cmdtrack_buffers *out);
+/* PLAN: v DEVICE f32 (N, n_nodes, 2), 0 <= n_nodes <= LG_PLAN_MAX_N (v may be NULL at 0); a copy ordered on the env's stream. */
+int lg_cmdtrack_set_plans(lg_cmdtrack *tr, lg_ctx *env, const float *v, int32_t n_nodes);
+int lg_cmdtrack_inject(lg_cmdtrack *tr, int enable, int32_t R);
+/* 0, or -1 if a resample found its block missing since the last call (waits for the device; clears the counts) */
+int lg_cmdtrack_inject_status(lg_cmdtrack *tr);
+/* One launch: the generator restarts as TrajectoryGenerator.reset(root xy) leaves it, z = root xy, row 0 of z, pz_x (x), then
+ * command 0 into obs.  epoch: 0..2^31-1, the key of this epoch's draws. */
+int lg_cmdtrack_begin(lg_cmdtrack *tr, lg_ctx *env, const lg_cmdtrack_rec *rec, int64_t epoch);
+/* One launch, after env step t (0 <= t < T; a host integer): the record of step t, then, if t + 1 < T, command t + 1 into obs. */
+int lg_cmdtrack_step(lg_cmdtrack *tr, lg_ctx *env, const lg_cmdtrack_rec *rec, int32_t t);
+
 #ifdef __cplusplus
 }
 #endif

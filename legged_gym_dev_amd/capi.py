@@ -402,6 +402,45 @@ class lg_traj_rec(C.Structure):
                 ("dead", C.c_void_p), ("k_mark", C.c_void_p), ("x", C.c_void_p)]
 
 
+class lg_cmdtrack_cfg(C.Structure):
+    """The command tracker's law and generator (include/legged_hip.h lg_cmdtrack_cfg)."""
+    _fields_ = [("kind", i32), ("track_yaw", i32), ("cmd_col", i32), ("weight_sampler", i32), ("tg_N", i32), ("x_n", i32),
+                ("seed", u64),
+                ("Kp", f32 * 9), ("u_min", f32 * 3), ("u_max", f32 * 3), ("cmd_scale", f32 * 3),
+                ("rom_v_min", f32 * 2), ("rom_v_max", f32 * 2),
+                ("t_low", f32), ("t_high", f32), ("freq_low", f32), ("freq_high", f32), ("prob_stationary", f32), ("_padf", f32)]
+
+
+class lg_cmdtrack_rec(C.Structure):
+    """One epoch's caller-owned device records, env-major (include/legged_hip.h lg_cmdtrack_rec)."""
+    _fields_ = [("T", i32), ("_pad", i32), ("z", C.c_void_p), ("v", C.c_void_p), ("pz_x", C.c_void_p), ("done", C.c_void_p),
+                ("u", C.c_void_p), ("x", C.c_void_p)]
+
+
+class lg_cmdtrack_buffers(C.Structure):
+    _fields_ = [("state", PF), ("tg_state", PF), ("plan", PF), ("inject", PF), ("n_resample", PI32), ("inject_overrun", PI32),
+                ("inject_K", i64)]
+
+
+CT_STATE = 8                                                    # LG_CT_STATE: z 2, v 2, u 3, 1 unused
+
+
+def declare_cmdtrack_api(lib):
+    """The lg_cmdtrack_* entries; raises if the library was built without them (there is no fallback)."""
+    vp, pc, pr = C.c_void_p, C.POINTER(lg_cmdtrack_cfg), C.POINTER(lg_cmdtrack_rec)
+    lib.lg_last_error.restype = C.c_char_p
+    lib.lg_cmdtrack_check.argtypes = [pc, pr, i32, i32, i32]
+    lib.lg_cmdtrack_create.argtypes = [vp, pc, C.POINTER(vp)]
+    lib.lg_cmdtrack_destroy.argtypes = [vp]
+    lib.lg_cmdtrack_get_buffers.argtypes = [vp, C.POINTER(lg_cmdtrack_buffers)]
+    lib.lg_cmdtrack_set_plans.argtypes = [vp, vp, vp, i32]
+    lib.lg_cmdtrack_inject.argtypes = [vp, C.c_int, i32]
+    lib.lg_cmdtrack_inject_status.argtypes = [vp]
+    lib.lg_cmdtrack_begin.argtypes = [vp, vp, pr, i64]
+    lib.lg_cmdtrack_step.argtypes = [vp, vp, pr, i32]
+    return lib
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p
