@@ -466,7 +466,8 @@ int lg_ppo_attach_env(lg_ppo *p, lg_ctx *env);
 int lg_ppo_params_changed(lg_ppo *p);
 /* Reproducible runs (debugging aid; off by default).  The learner's sums over the minibatch rows -- weight-gradient slices, bias
  * column sums, the head's row sums, loss statistics, the gradient norm, the advantage moments -- are float atomics, whose order
- * differs from run to run (last-bit differences in every gradient).  on != 0: the same contributions are accumulated as 2^-40
+ * differs from run to run (last-bit differences in every gradient; the gradient norm itself, taken from the reduced gradients,
+ * is added in a fixed order in either mode, so that ranks holding the same gradients clip alike).  on != 0: the same contributions are accumulated as 2^-40
  * fixed-point 64-bit integers (order-independent) and folded into the float buffers before they are read: two runs from the
  * same seed then agree bit for bit, on one rank and across a fixed set of ranks.  Costs three small launches per optimiser step.
  * Range: |sum| < 2^23 per accumulator; the squared gradient norm is kept in two such words (a norm below 1.9e8).
@@ -483,7 +484,11 @@ int lg_ppo_act_inference(lg_ppo *p, const float *obs, float *actions_out, int64_
  * replace -- it has no multi-GPU code; this is the exchange step the env-sharded learner needs).  One process per GPU; rank r
  * owns envs [r N/G, (r+1) N/G).  RCCL over xGMI, resolved from the librccl.so already in the process (no link dependency).
  * The Python runner may use torch.distributed instead (same RCCL underneath); these entries are for hosts without it, and for
- * the reduction overlapped with the backward pass, which needs the learner's own streams. */
+ * the reduction overlapped with the backward pass, which needs the learner's own streams.
+ * LG_RCCL_LIB (environment, read at the first lg_comm_* call of the process): the path of the library to resolve RCCL's entry
+ * points from instead -- a deployment hook for an RCCL at a non-default path.  It is opened as given (RTLD_NOW | RTLD_LOCAL) and
+ * there is no fallback: if it cannot be loaded the call fails with an error that names the path.  The tests use it to put a
+ * stand-in transport (tests/comm_standin) under these entries. */
 #define LG_COMM_ID_BYTES 128
 typedef struct lg_comm lg_comm;
 int lg_comm_get_unique_id(void *id_out /* LG_COMM_ID_BYTES, host */);   /* rank 0; the host carries the bytes to the other ranks */

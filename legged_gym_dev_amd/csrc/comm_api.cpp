@@ -1,9 +1,11 @@
 // lg_comm_*: the learner's collectives on RCCL, for hosts without torch.distributed (include/legged_hip.h).
 // The library does not link librccl: it resolves the few entry points it needs at first use from the librccl.so the process
-// already holds (torch ships one), else from the loader path -- one RCCL instance per process either way.
+// already holds (torch ships one), else from the loader path -- one RCCL instance per process either way.  LG_RCCL_LIB names
+// the library to take instead, with no fallback (include/legged_hip.h).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -30,10 +32,16 @@ const int kFloat32 = 7, kSum = 0;                                      // ncclFl
 
 bool load_rccl() {
     if (R.h) return true;
-    void *h = dlopen("librccl.so", RTLD_NOW | RTLD_NOLOAD);            // the instance torch loaded, when there is one
-    if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) { lg_set_error(std::string("librccl.so not found: ") + dlerror()); return false; }
+    void *h = nullptr;
+    if (const char *path = getenv("LG_RCCL_LIB")) {                    // exactly this library (an RCCL outside the loader path; the tests' stand-in)
+        h = *path ? dlopen(path, RTLD_NOW | RTLD_LOCAL) : nullptr;
+        if (!h) { lg_set_error(std::string("LG_RCCL_LIB=") + path + " could not be loaded: " + (*path ? dlerror() : "empty path")); return false; }
+    } else {
+        h = dlopen("librccl.so", RTLD_NOW | RTLD_NOLOAD);              // the instance torch loaded, when there is one
+        if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
+        if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
+        if (!h) { lg_set_error(std::string("librccl.so not found: ") + dlerror()); return false; }
+    }
 #define SYM(field, name) do { R.field = (decltype(R.field))dlsym(h, name); if (!R.field) { lg_set_error("librccl.so lacks " name); return false; } } while (0)
     SYM(get_uid, "ncclGetUniqueId"); SYM(init_rank, "ncclCommInitRank"); SYM(destroy, "ncclCommDestroy");
     SYM(allreduce, "ncclAllReduce"); SYM(bcast, "ncclBroadcast"); SYM(group_start, "ncclGroupStart"); SYM(group_end, "ncclGroupEnd");

@@ -555,7 +555,7 @@ static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **
     PA(d.st_actions, TN * A); PA(d.st_rewards, TN); PA(d.st_values, TN); PA(d.st_returns, TN); PA(d.st_adv, TN);
     PA(d.st_log_prob, TN); PA(d.st_mu, TN * A); PA(d.st_sigma, A); PA(d.st_dones, TN);
     PA(d.act_actions, (size_t)N * A); PA(d.act_values, N); PA(d.act_log_prob, N); PA(d.act_mu, (size_t)N * A);
-    PA(d.stats, 8); PA(d.loss_acc, 4); PA(d.noise, (size_t)N * A); PA(d.perm, TN); PA(d.adv_partial, 4);
+    PA(d.stats, 8); PA(d.loss_acc, 4 + LG_NORM_BLOCKS); PA(d.noise, (size_t)N * A); PA(d.perm, TN); PA(d.adv_partial, 4);
     for (int k = 0; k < 2; ++k) {
         lg_ppo::MbSet &m = p->mbset[k];
         PA(m.obs, (size_t)R * d.Op);                // pad columns: zeroed here, never written

@@ -40,7 +40,8 @@ struct PpoDev {                    // passed by value to kernels
     uint8_t *st_dones;
     float *act_actions, *act_values, *act_log_prob, *act_mu;
     float *stats;                  // [lr, kl, value_loss_sum, surrogate_sum, adam_t, n_updates, adv_mean, adv_std]
-    float *loss_acc;               // [value_loss, surrogate, grad_norm_sq (even steps), grad_norm_sq (odd steps)]
+    float *loss_acc;               // [value_loss, surrogate, grad_norm_sq (even steps), grad_norm_sq (odd steps)] (the norm slots: deterministic
+                                   // mode only) | LG_NORM_BLOCKS block partials of the squared gradient norm (k_opt_prepare -> k_opt_adam)
     float *noise;
     int32_t *perm;
     float *adv_partial;
@@ -68,6 +69,10 @@ struct PpoDev {                    // passed by value to kernels
     long long *det64;
 };
 #define LG_DET_WORDS(num_params) ((size_t)(num_params) + 12)
+// Workgroups of k_opt_prepare that sum squared gradients.  Each leaves its partial in loss_acc[4 + block] and k_opt_adam adds them in
+// a fixed order: ranks that hold the same reduced gradients then clip by the same bits (a float atomic per block would add them in
+// arrival order, and ranks whose norms differ in the last bit drift apart for good once the clip is active).
+#define LG_NORM_BLOCKS 128
 
 #define LG_DET_SCALE 1099511627776.0          // 2^40: |sum| < 2^23, resolution 9.1e-13
 __device__ __forceinline__ void det_add64(long long *q, float v) {

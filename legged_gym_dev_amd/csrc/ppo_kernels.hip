@@ -768,8 +768,9 @@ __global__ void __launch_bounds__(256) k_head_finish(PpoDev P, int nrows, int64_
 }
 
 // KL-adaptive learning rate (rsl_rl PPO.update) + reset of the norm accumulator
-// Optimiser step in two launches.  k_opt_prepare: squared gradient norm (block partials -> atomics into
-// loss_acc[2 + par]) and, on one lane, the KL-adaptive learning rate, the loss statistics and the Adam step
+// Optimiser step in two launches.  k_opt_prepare: squared gradient norm (one partial per block into loss_acc[4 + block],
+// added in a fixed order by k_opt_adam; deterministic mode: fixed point into loss_acc[2 + par]) and, on one lane, the
+// KL-adaptive learning rate, the loss statistics and the Adam step
 // count.  k_opt_adam: clip_grad_norm_(max_norm) + torch.optim.Adam step (betas 0.9/0.999, eps 1e-8), then
 // zeroes what it consumed -- the gradient buffer (+ KL tail) for the next minibatch and the OTHER norm slot
 // (par alternates per step, so no block can still be reading the slot that is cleared).
@@ -807,7 +808,7 @@ __global__ void __launch_bounds__(256) k_opt_prepare(PpoDev P, int par, int prep
     }
     if (threadIdx.x == 0) {
         if (P.det64) det_add_norm(P, par, red[0]);           // two-word fixed point: a squared norm leaves the range of acc_add's format
-        else atomicAdd(&P.loss_acc[2 + par], red[0]);
+        else P.loss_acc[4 + blockIdx.x] = red[0];            // blockIdx.x < prep_blocks = LG_NORM_BLOCKS; summed in order by k_opt_adam
     }
 }
 // Deterministic mode: add the fixed-point shadow (PpoDev::det64) into the float buffers it stands for and clear it.  One adder per
@@ -844,7 +845,15 @@ __global__ void __launch_bounds__(256) k_sync_planes(PpoDev P) {
         write_planes(P, k, P.params[k]);
 }
 __global__ void __launch_bounds__(256) k_opt_adam(PpoDev P, int par) {
-    const float total = sqrtf(P.loss_acc[2 + par]);
+    float norm_sq;
+    if (P.det64) norm_sq = P.loss_acc[2 + par];
+    else {                                                   // the block partials in one fixed order, the same in every wave and on every rank
+        static_assert(LG_NORM_BLOCKS == 128, "two partials per lane of a wave");
+        const int lane = threadIdx.x & 63;
+        norm_sq = P.loss_acc[4 + lane] + P.loss_acc[4 + 64 + lane];
+        for (int w = 32; w > 0; w >>= 1) norm_sq += __shfl_xor(norm_sq, w);
+    }
+    const float total = sqrtf(norm_sq);
     const float coef = fminf(P.max_grad_norm / (total + 1e-6f), 1.0f);
     const float lr = P.stats[0], t = P.stats[4];
     // fp32 corrections: 0.999f is 1.3e-8 above 0.999 and 1 - 0.999^t cancels while t << 1000, so the step is up to 6.6e-6 + 3e-5 / t short
@@ -929,7 +938,7 @@ void ppok_sync_planes(const PpoDev *P, hipStream_t s) { hipLaunchKernelGGL(k_syn
 int ppok_step(const PpoDev *P, int par, const PpoDev *G, int gather_mb, hipStream_t s) {
     const bool g4 = gather_mb >= 0 && (P->A & 3) == 0;
     const int gblocks = g4 ? (P->mb_rows * 32 + 255) / 256 : 0;
-    hipLaunchKernelGGL(k_opt_prepare, dim3(128 + gblocks), dim3(256), 0, s, *P, par, 128, g4 ? *G : *P, gather_mb);
+    hipLaunchKernelGGL(k_opt_prepare, dim3(LG_NORM_BLOCKS + gblocks), dim3(256), 0, s, *P, par, LG_NORM_BLOCKS, g4 ? *G : *P, gather_mb);
     if (P->det64) ppok_det_fold(P, s);                   // the squared gradient norm
     // one parameter per thread: the per-parameter chain (4 loads, Adam, 4 stores + the three plane stores through pl_dest) is a
     // memory round trip that a grid-stride loop repeats serially (6 x for [512,256,128] on 256 workgroups: 12.2 us; 8.9 us on 1024, 10.2 on 2048)

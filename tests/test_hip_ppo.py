@@ -580,7 +580,8 @@ def test_native_rccl_comm_single_rank():
     communicator, in-place all-reduce and broadcast on the caller's stream, and the learner's overlapped gradient reduction
     (lg_ppo_set_comm: per-layer buckets all-reduced on the communicator's stream while the backward GEMMs run).  With one rank
     every collective is the identity, so an update with the communicator attached must match one without it (tolerance: the
-    float atomics of the gradient kernels, as in test_two_rank_update_equals_single_process_update)."""
+    float atomics of the gradient kernels, as in test_two_rank_update_equals_single_process_update).  The same entries with 2 to 4
+    ranks, over a stand-in transport whose ranks are threads: tests/test_hip_comm_standin.py."""
     from legged_gym_dev_amd.rl.comm import NativeComm
     comm = NativeComm(0, 1)
     try:
@@ -625,8 +626,8 @@ def test_gradient_buckets_tile_the_reduce_buffer(hidden):
     """The overlapped RCCL reduction (lg_ppo_set_comm) sends one bucket per layer: W, b of both nets, and with the head's
     bucket std and the [KL | pad] tail.  Host-side check of the extents it hands to RCCL: over all layers they cover
     grads[0 : num_reduce) exactly once -- no gap, no overlap -- for the per-layer head ([96, 40]) and both fused-head widths.
-    (With one rank every collective is the identity, so a wrong extent would pass every numerical test here: world > 1 of the
-    native path is parity-unpinned on this one-GPU box)"""
+    (With one rank every collective is the identity, so a wrong extent would pass every numerical test in this file; with 2 and 4
+    ranks over a stand-in transport the extents decide the numbers: tests/test_hip_comm_standin.py)"""
     import ctypes as C
     pol = dict(POLICY, actor_hidden_dims=hidden, critic_hidden_dims=hidden)
     hip, _, _ = _make(64, 235, 12, 4, pol)
