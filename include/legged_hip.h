@@ -1071,6 +1071,48 @@ int lg_cmdtrack_begin(lg_cmdtrack *tr, lg_ctx *env, const lg_cmdtrack_rec *rec, 
 /* One launch, after env step t (0 <= t < T; a host integer): the record of step t, then, if t + 1 < T, command t + 1 into obs. */
 int lg_cmdtrack_step(lg_cmdtrack *tr, lg_ctx *env, const lg_cmdtrack_rec *rec, int32_t t);
 
+/* ------------------------------------------------------------------ privileged observations: the
+ * critic's own observation row, the buffer the reference allocates, clips and returns but never fills
+ * (legged_robot_config.py:38 num_privileged_obs; base_task.py:62-79 the buffer, :104-105 get_privileged_observations;
+ * legged_robot.py:100-104 the clip and step()'s second return value).  A row is a list of terms; entry j of a term is
+ *   out[env, off_term + j] = min(max(raw * scale_term, -clip_observations), +clip_observations)
+ * in fp32 with one rounding per operation, off_term = the widths of the terms before it.  raw per kind:
+ *   OBS                  num_obs      the policy observation entry BEFORE noise, by the expressions of legged_robot.py:208-226
+ *                                     (trajectory env: legged_robot_trajectory.py:280-288): with noise off and scale 1 it is obs
+ *   FRICTION             1            lg_buffers.friction          (legged_robot.py:259-282)
+ *   BASE_MASS            1            lg_buffers.base_mass_delta   (legged_robot.py:330-341)
+ *   MATERIAL             4            lg_buffers.material          (legged_robot.py:284-299,337-339)
+ *   FEET_CONTACT_FORCES  3 num_feet   contact_forces[env, feet_idx[f], :]
+ *   FEET_CONTACT         num_feet     contact_forces[env, feet_idx[f], 2] > 1 ? 1 : 0        (_reward_feet_air_time's contact test)
+ *   FEET_AIR_TIME        num_feet     lg_buffers.feet_air_time
+ *   BODY_CONTACT         num_pen      |contact_forces[env, pen_idx[b], :]|^2 > 0.01 ? 1 : 0  (_reward_collision's norm > 0.1)
+ *   TORQUES              num_actions  lg_buffers.torques
+ *   HEIGHTS              H            the height block of OBS; refused unless measure_heights
+ *   EPISODE_PROGRESS     1            (float)episode_length * float(1 / max_episode_length)
+ * One launch on the env's stream AFTER the step (lg_step / lg_post_physics_step), so an env the step reset shows its post-reset
+ * state, as obs does.  It reads the env's buffers, writes only its own, and leaves a deferred step epilogue (lg_ppo_attach_env)
+ * deferred.  Lifetime as lg_cmdtrack: the handle keeps no pointer into the env; lg_priv_obs_compute takes the env, borrows its
+ * buffers and stream for that call and refuses an env of other dimensions than the one the handle was created for. */
+#define LG_PRIV_MAX_TERMS 16
+#define LG_PRIV_MAX_WIDTH 1024
+enum { LG_PRIV_OBS = 0, LG_PRIV_FRICTION, LG_PRIV_BASE_MASS, LG_PRIV_MATERIAL, LG_PRIV_FEET_CONTACT_FORCES, LG_PRIV_FEET_CONTACT,
+       LG_PRIV_FEET_AIR_TIME, LG_PRIV_BODY_CONTACT, LG_PRIV_TORQUES, LG_PRIV_HEIGHTS, LG_PRIV_EPISODE_PROGRESS, LG_PRIV_NUM_KINDS };
+typedef struct lg_priv_term { int32_t kind /*LG_PRIV_**/; float scale; } lg_priv_term;
+typedef struct lg_priv_cfg {
+    int32_t num_terms /*1..LG_PRIV_MAX_TERMS, each kind at most once*/, _pad;
+    lg_priv_term terms[LG_PRIV_MAX_TERMS];
+} lg_priv_cfg;
+typedef struct lg_priv_obs lg_priv_obs;
+/* Host code, needs no GPU.  0 and *width (may be NULL) = the row's width, or -1 with the field named in lg_last_error
+ * ("lg_priv_obs: ...").  The dimensions are the env's lg_cfg fields of the same names. */
+int lg_priv_obs_check(const lg_priv_cfg *cfg, int32_t num_obs, int32_t num_actions, int32_t num_feet, int32_t num_pen,
+                      int32_t num_height_points, int32_t measure_heights, int32_t *width);
+int lg_priv_obs_create(lg_ctx *env, const lg_priv_cfg *cfg, lg_priv_obs **out);
+/* *out: DEVICE f32 (num_envs, *width), zeros until the first lg_priv_obs_compute */
+int lg_priv_obs_buffer(lg_priv_obs *po, float **out, int32_t *width);
+int lg_priv_obs_compute(lg_priv_obs *po, lg_ctx *env);
+int lg_priv_obs_destroy(lg_priv_obs *po);
+
 #ifdef __cplusplus
 }
 #endif

@@ -441,6 +441,32 @@ def declare_cmdtrack_api(lib):
     return lib
 
 
+PRIV_MAX_TERMS, PRIV_MAX_WIDTH = 16, 1024                       # LG_PRIV_MAX_*
+PRIV_TERMS = ["obs", "friction", "base_mass", "material", "feet_contact_forces", "feet_contact", "feet_air_time", "body_contact",
+              "torques", "heights", "episode_progress"]          # LG_PRIV_*: a term's kind is its index
+
+
+class lg_priv_term(C.Structure):
+    _fields_ = [("kind", i32), ("scale", f32)]
+
+
+class lg_priv_cfg(C.Structure):
+    """The privileged observation row, term by term (include/legged_hip.h lg_priv_cfg)."""
+    _fields_ = [("num_terms", i32), ("_pad", i32), ("terms", lg_priv_term * PRIV_MAX_TERMS)]
+
+
+def declare_priv_obs_api(lib):
+    """The lg_priv_obs_* entries; raises if the library was built without them (there is no fallback)."""
+    vp, pc = C.c_void_p, C.POINTER(lg_priv_cfg)
+    lib.lg_last_error.restype = C.c_char_p
+    lib.lg_priv_obs_check.argtypes = [pc, i32, i32, i32, i32, i32, i32, PI32]
+    lib.lg_priv_obs_create.argtypes = [vp, pc, C.POINTER(vp)]
+    lib.lg_priv_obs_buffer.argtypes = [vp, C.POINTER(vp), PI32]
+    lib.lg_priv_obs_compute.argtypes = [vp, vp]
+    lib.lg_priv_obs_destroy.argtypes = [vp]
+    return lib
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p

@@ -20,7 +20,8 @@ class BaseTask:
         self.num_obs = cfg.env.num_observations
         self.num_privileged_obs = cfg.env.num_privileged_obs
         self.num_actions = cfg.env.num_actions
-        if self.num_privileged_obs is not None:
+        # cfg.privileged_obs.terms (envs/base/privileged_obs.py) is what fills the buffer; a bare width has nothing to fill it with
+        if self.num_privileged_obs is not None and not (getattr(getattr(cfg, "privileged_obs", None), "terms", None) or []):
             raise NotImplementedError("privileged observations are not produced by the reference LeggedRobot either")
         self.privileged_obs_buf = None
         self.extras = {}

@@ -89,7 +89,8 @@ CONTRACT = [
     # ---- env
     ("env.num_envs", CONSUMED, "setup"),
     ("env.num_observations", CONSUMED, "setup (checked against the observation layout)"),
-    ("env.num_privileged_obs", CONSUMED, "base: BaseTask (LeggedRobot produces none, as in the reference)"),
+    ("env.num_privileged_obs", CONSUMED, "base: BaseTask; env: None or the width of privileged_obs.terms (privileged_obs.py); a number "
+     "without terms is refused: LeggedRobot then produces none, as in the reference"),
     ("env.num_actions", CONSUMED, "setup (checked against the asset)"),
     ("env.env_spacing", CONSUMED, "env: grid origins"),
     ("env.send_timeouts", CONSUMED, "setup"),
@@ -98,6 +99,9 @@ CONTRACT = [
     ("init_state.*", CONSUMED, "setup"),
     ("noise.*", CONSUMED, "setup: noise_scale_vec"),
     ("normalization.*", CONSUMED, "setup"),
+    # ---- privileged observations (this build's own section; the reference has the buffer, legged_robot_config.py:38, and no terms)
+    ("privileged_obs.terms", CONSUMED, "env: privileged_obs.PrivilegedObsSpec, the terms of the critic's row in order (lg_priv_cfg)"),
+    ("privileged_obs.scales.*", CONSUMED, "env: privileged_obs.PrivilegedObsSpec, lg_priv_term.scale of the term of that name"),
     ("rewards.scales.*", CONSUMED, "setup: reward terms"),
     ("rewards.differential_error.*", CONSUMED, "reward: declared term (trajectory env)"),
     ("rewards.reward_weighting.position", CONSUMED, "reward: tracking_rom weights (trajectory env, SingleInt2D.get_weighting_vector)"),

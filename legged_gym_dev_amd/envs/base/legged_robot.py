@@ -17,6 +17,7 @@ from legged_gym_dev_amd.model.robot_model import compile_model, resolve_model
 from legged_gym_dev_amd.utils.terrain import Terrain
 from .base_task import BaseTask
 from .env_setup import CurriculumClock, EnvSetup, sim_dt_float
+from .privileged_obs import HipPrivilegedObs, PrivilegedObsSpec
 
 
 def draw_env_constants(cfg, num_envs_total, body0_mass, terrain, num_shapes=0):
@@ -120,7 +121,12 @@ class LeggedRobot(BaseTask):
         body0_mass = float(self.robot_model["bodies"][0]["mass"])
         consts = draw_env_constants(cfg, total, body0_mass, self.terrain, num_shapes=cm["num_shapes"])
         hs = self.terrain.heightsamples if self.terrain is not None else None
+        # privileged observations (privileged_obs.py): resolved before any device work, so a bad term list costs no allocation
+        priv_spec = PrivilegedObsSpec.from_cfg(cfg, s)
+        if priv_spec.terms:
+            self.num_privileged_obs = priv_spec.resolve_num_privileged_obs(cfg.env.num_privileged_obs)
         self.core = HipEnvCore(s, hs, device=self.device)
+        self._priv = HipPrivilegedObs(self.core, priv_spec) if priv_spec.terms else None
         t = self.core.t
         lo, hi = rank * self.num_envs, (rank + 1) * self.num_envs
         t["env_origins"].copy_(consts["env_origins"][lo:hi])
@@ -198,6 +204,7 @@ class LeggedRobot(BaseTask):
         self.base_quat = self.root_states[:, 3:7]
         self.contact_forces = t["contact_forces"]
         self.obs_buf, self.rew_buf = t["obs"], t["rew"]
+        self.privileged_obs_buf = self._priv.buf if self._priv is not None else None
         self.reset_buf, self.time_out_buf = t["reset"].view(torch.bool), t["time_out"].view(torch.bool)
         self._episode_length_buf = t["episode_length"]
         self.torques, self.actions = t["torques"], t["actions"]
@@ -240,6 +247,8 @@ class LeggedRobot(BaseTask):
         a = actions.to(self.device, dtype=torch.float32).contiguous()
         self._curriculum_tick()
         self.core.step(a)
+        if self._priv is not None:                # one launch behind the step's, in stream order (privileged_obs.py)
+            self._priv.compute()
         self.common_step_counter += 1
         self.extras["episode"] = self._extras_episode
         if self.cfg.env.send_timeouts:
@@ -265,10 +274,14 @@ class LeggedRobot(BaseTask):
     def post_physics_step(self):
         self._curriculum_tick()
         self.core.call("post_physics_step")
+        if self._priv is not None:
+            self._priv.compute()
         self.common_step_counter += 1
 
     def compute_observations(self):
         return self.obs_buf
 
     def close(self):
+        if self._priv is not None:
+            self._priv.close()
         self.core.close()

@@ -83,6 +83,14 @@ LeggedRobotCfg = cfg_class("LeggedRobotCfg", BaseConfig, dict(
             dof_pos=0.01, dof_vel=1.5, lin_vel=0.1, ang_vel=0.2, gravity=0.05, height_measurements=0.1,
         ),
     ),
+    # this build's own section (envs/base/privileged_obs.py): the terms of the critic's observation row, in order, and their scales
+    privileged_obs=S(
+        terms=[],
+        scales=S(
+            obs=1.0, friction=1.0, base_mass=1.0, material=1.0, feet_contact_forces=1.0, feet_contact=1.0, feet_air_time=1.0,
+            body_contact=1.0, torques=1.0, heights=1.0, episode_progress=1.0,
+        ),
+    ),
     viewer=S(
         ref_env=0, pos=[10, 0, 6], lookat=[11.0, 5, 3.0],
     ),

@@ -62,6 +62,7 @@ LeggedRobotTrajectoryCfg = cfg_class("LeggedRobotTrajectoryCfg", BaseConfig, dic
     normalization=S(obs_scales=S(lin_vel=2.0, ang_vel=0.25, dof_pos=1.0, dof_vel=0.05, height_measurements=5.0, trajectory=[1.0, 1.0]),
                     clip_observations=100.0, clip_actions=100.0),
     noise=_B.noise,
+    privileged_obs=_B.privileged_obs,
     viewer=_B.viewer,
     sim=_B.sim,
 ), doc=None, module=__name__)

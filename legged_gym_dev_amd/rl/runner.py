@@ -100,6 +100,9 @@ class OnPolicyRunner:
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         ncrit = env.num_privileged_obs if env.num_privileged_obs is not None else env.num_obs
+        if env.get_privileged_observations() is not None and ncrit == env.num_obs:
+            raise ValueError(f"the privileged observation row is as wide as the policy's ({ncrit} columns): HipPPO takes a critic "
+                             "input of the actor's width to BE the actor's input; add a term to cfg.privileged_obs.terms (or drop one)")
         self.ppo = HipPPO(env.num_envs, env.num_obs, ncrit, env.num_actions, self.policy_cfg, self.alg_cfg,
                           self.num_steps_per_env, device=self.device, seed=train_cfg.get("seed", 1),
                           world_size=self.world_size, rank=self.rank,
@@ -134,17 +137,17 @@ class OnPolicyRunner:
         learner (lg_ppo_attach_env): the step's single-workgroup epilogue and process_env_step ride on the next act's launch --
         3 launches per policy step instead of 5, same results (LG_FUSE_EPILOGUE=0 keeps them as launches of their own)."""
         env, ppo = self.env, self.ppo
-        obs = env.get_observations()
+        obs, priv = env.get_observations(), env.get_privileged_observations()
         fuse = self.fuse_epilogue
         if fuse:
             ppo.attach_env(env.core)
         try:
             for _ in range(self.num_steps_per_env):
-                actions = ppo.act(obs, None)
+                actions = ppo.act(obs, priv)                 # priv: the critic's own row (env.num_privileged_obs columns) or None
                 obs, priv, rewards, dones, infos = env.step(actions)
                 ppo.process_env_step(rewards, env.core.t["reset"], {"time_outs": env.core.t["extras_time_outs"]}
                                      if "time_outs" in infos else {})
-            ppo.compute_returns(obs, self._all_reduce if self.world_size > 1 else None)
+            ppo.compute_returns(priv if priv is not None else obs, self._all_reduce if self.world_size > 1 else None)
         finally:
             if fuse:
                 ppo.attach_env(None)

@@ -1,5 +1,7 @@
 """python legged_gym_dev_amd/scripts/train.py --task=anymal_c_flat [--num_envs N --max_iterations K --headless ...]
-Same flow as the reference's scripts/train.py:40-44; multi-GPU: launch with torchrun (one rank per GPU)."""
+Same flow as the reference's scripts/train.py:40-44; multi-GPU: launch with torchrun (one rank per GPU).
+Asymmetric critic: --privileged_obs obs,friction,base_mass,feet_contact,feet_air_time gives the critic its own noise-free row
+(envs/base/privileged_obs.py lists the terms); the actor, checkpoints, play and export are unchanged."""
 import os
 import sys
 

@@ -96,6 +96,11 @@ def get_load_path(root, load_run=-1, checkpoint=-1):
 def update_cfg_from_args(env_cfg, cfg_train, args):
     if env_cfg is not None and getattr(args, "num_envs", None) is not None:
         env_cfg.env.num_envs = args.num_envs
+    if env_cfg is not None and getattr(args, "privileged_obs", None):
+        # the critic's own observation row (envs/base/privileged_obs.py); the scales stay the cfg's
+        if getattr(env_cfg, "privileged_obs", None) is None:      # a cfg class without the section: unit scales
+            env_cfg.privileged_obs = SimpleNamespace()
+        env_cfg.privileged_obs.terms = [t.strip() for t in args.privileged_obs.split(",") if t.strip()]
     if cfg_train is not None:
         if getattr(args, "seed", None) is not None:
             cfg_train.seed = args.seed
@@ -127,6 +132,9 @@ def get_args(argv=None):
     p.add_argument("--sim_device", type=str, default="cuda:0")
     p.add_argument("--pipeline", type=str, default="gpu")
     p.add_argument("--num_threads", type=int, default=0)
+    p.add_argument("--privileged_obs", type=str, help="comma-separated terms of the critic's privileged observation row, in order "
+                   "(obs,friction,base_mass,material,feet_contact_forces,feet_contact,feet_air_time,body_contact,torques,heights,"
+                   "episode_progress)")
     args, _ = p.parse_known_args(argv)
     args.physics_engine = 1          # SIM_PHYSX placeholder: the HIP physics is the only engine
     args.use_gpu_pipeline = args.pipeline.lower() in ("gpu", "cuda")
