@@ -965,9 +965,13 @@ typedef struct lg_plan_scenes {                    /* DEVICE pointers; one scene
     const float *goal;                             /* (S, 2), or NULL = prob->goal for every scene */
     const float *obs;                              /* (S, LG_PLAN_MAX_OBS, 3): cx, cy, r; slots past n_obs[s] are not read */
     const int32_t *n_obs;                          /* (S); obs and n_obs are both given or both NULL (= the problem's obstacles) */
+    const float *vel;                              /* (S, LG_PLAN_MAX_OBS, 2): ux, uy in m/s of every obstacle slot, or NULL = every
+                                                    * obstacle stands still (section 10.18).  obs holds the centres at node 0, "now";
+                                                    * at node k of the plan obstacle i is at c_i + u_i * t_k, t_k = (float)k * prob->dt,
+                                                    * three roundings (k dt, u t_k, c + ..).  Needs obs; slots past n_obs[s] are not read */
 } lg_plan_scenes;
 /* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error: S < 1, S != count, one of obs / n_obs without the other,
- * or all three pointers NULL (the struct then says nothing: pass NULL scenes).  The arrays are not read: n_obs[s] is clamped into
+ * all three of goal, obs, n_obs NULL (the struct then says nothing: pass NULL scenes), or vel without obs.  The arrays are not read: n_obs[s] is clamped into
  * 0..LG_PLAN_MAX_OBS on the device, and a scene without obstacles gives min_clear = +inf and worst_node = -1 as n_obs = 0 does.
  * Radii, centres and goals are the caller's to validate before upload (tube/plan.py Scenes does). */
 int lg_plan_scenes_check(const lg_plan_scenes *scenes, int64_t count);
@@ -1002,6 +1006,29 @@ int lg_plan_descend_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_
                            const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B,
                            float *v, float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad,
                            const lg_plan_scenes *scenes, void *stream);
+
+/* ------------------------------------------------------------------ a fleet's scenes: the robots of a fleet
+ * are each other's moving obstacles.  One launch writes, for every robot p of P, the obs / vel / n_obs arrays of an lg_plan_scenes of
+ * S = P from the fleet's own positions and velocities, with nothing read back:
+ *   1. its n_s = clamp(n_static[p], 0, 8) static obstacles first, each centre advanced to time t: c + u * t, two roundings, its
+ *      velocity static_vel (zeros where static_vel is NULL; n_s = 0 where static_obs is NULL);
+ *   2. then at most min(max_neighbours, 8 - n_s) other robots q != p with d2 = dx*dx + dy*dy <= sense_radius*sense_radius, d2 in
+ *      float32 with every operation rounded on its own; a d2 that is not finite never passes;
+ *   3. neighbours ordered by (d2, q) ascending -- the walk sums and takes minima over obstacles in slot order;
+ *   4. a neighbour's slot is (pos_q, separation) with velocity vel_q;
+ *   5. slots past n_obs[p] are zeros.
+ * Every array is a DEVICE pointer.  0, or -1 with the field named in lg_last_error before a device is touched: a null cfg or required
+ * array, separation or sense_radius negative or not finite, max_neighbours outside 0..8, P outside 1..2^31-1, static_obs without
+ * n_static or the reverse, static_vel without static_obs, t not finite. */
+typedef struct lg_fleet_cfg {
+    float separation;                              /* the radius of a neighbour's disc: the distance two robots keep, centre to centre */
+    float sense_radius;                            /* robots farther than this are not seen */
+    int32_t max_neighbours;                        /* 0..LG_PLAN_MAX_OBS */
+} lg_fleet_cfg;
+int lg_plan_fleet_scenes(const lg_fleet_cfg *cfg, const float *pos /*(P,2)*/, const float *vel /*(P,2)*/, int64_t P,
+                         const float *static_obs /*(P,8,3) or NULL*/, const float *static_vel /*(P,8,2) or NULL*/,
+                         const int32_t *n_static /*(P) or NULL*/, float t, float *obs /*(P,8,3)*/, float *obs_vel /*(P,8,2)*/,
+                         int32_t *n_obs /*(P)*/, void *stream);
 
 /* ------------------------------------------------------------------ command tracker: ROM trajectories
  * tracked by a VELOCITY-COMMAND policy, the loop of deep_tube_learning/data_collection_velocity.py:84-156 ("DV").  A SingleInt2D ROM

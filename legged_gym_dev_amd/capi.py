@@ -363,7 +363,12 @@ class lg_grad_cfg(C.Structure):
 
 class lg_plan_scenes(C.Structure):
     """One goal and obstacle list per plan or MPPI instance (include/legged_hip.h lg_plan_scenes); device pointers."""
-    _fields_ = [("S", i64), ("goal", C.c_void_p), ("obs", C.c_void_p), ("n_obs", C.c_void_p)]
+    _fields_ = [("S", i64), ("goal", C.c_void_p), ("obs", C.c_void_p), ("n_obs", C.c_void_p), ("vel", C.c_void_p)]
+
+
+class lg_fleet_cfg(C.Structure):
+    """How a fleet's robots see each other (include/legged_hip.h lg_fleet_cfg)."""
+    _fields_ = [("separation", f32), ("sense_radius", f32), ("max_neighbours", i32)]
 
 
 def declare_plan_api(lib):
@@ -394,6 +399,9 @@ def declare_plan_api(lib):
     for name in ("lg_plan_score", "lg_plan_mppi_step", "lg_plan_mppi", "lg_plan_grad", "lg_plan_descend_step", "lg_plan_descend"):
         a = list(getattr(lib, name).argtypes)
         getattr(lib, name + "_scenes").argtypes = a[:-1] + [ps, a[-1]]
+    if not hasattr(lib, "lg_plan_fleet_scenes"):   # an A/B library built before the fleet's scenes
+        return
+    lib.lg_plan_fleet_scenes.argtypes = [C.POINTER(lg_fleet_cfg), vp, vp, i64, vp, vp, vp, f32, vp, vp, vp, vp]
 
 
 class lg_traj_rec(C.Structure):

@@ -1,4 +1,4 @@
-// Planner kernels on a learned or analytic tube (DESIGN.md sections 10.9 to 10.14) and their launchers: scoring (k_plan_score), the
+// Planner kernels on a learned or analytic tube (DESIGN.md sections 10.9 to 10.14, 10.18) and their launchers: scoring (k_plan_score), the
 // sampling planner (k_plan_sample_score, k_plan_mppi_*), the one-step kind (k_plan_score_step, k_plan_sample_score_step) and the
 // gradient planner (k_plan_grad).  The MLP forward and backward are the trainer's and inference's own (tube_mlp.h).
 #include <cstring>
@@ -20,8 +20,9 @@ struct PlanDev {                        // passed by value
     int32_t *worst_node, *n_viol;
     float level;
     int Hr, I;                          // columns of the tile's item: Hr past errors, 2 (Hr + N) inputs, (level); analytic kinds: Hr = 0
-    const float *sc_goal, *sc_obs;      // lg_plan_scenes (section 10.14): read by the <SC = true> kernels alone
+    const float *sc_goal, *sc_obs;      // lg_plan_scenes (section 10.14): read by the kernels with SC != PLAN_SC_PROB alone
     const int32_t *sc_n;
+    const float *sc_vel;                // its velocities (section 10.18): read by the <SC = PLAN_SC_MOVING> kernels alone
 };
 
 #define PLAN_ZS(N) ((((N) + 1) * 3) | 1)    // floats of a plan's (z, w) nodes in LDS: odd, so that the lanes' rows fall on different banks
@@ -36,13 +37,19 @@ __device__ __forceinline__ float plan_quad(const float *M, float d0, float d1) {
 // PlanSceneProb: the call's one scene in the by-value problem -- uniform reads, the code of the entries without scenes.
 // PlanSceneRow: a row of PLAN_SCN floats in LDS, [goal x, y, (cx, cy, r) x LG_PLAN_MAX_OBS, count]; the stride is odd, so the 32
 // walking lanes read different banks.  plan_scene_stage fills the rows of a tile before its first barrier.
+// PlanSceneRowMoving (section 10.18): a row of PLAN_SCNM floats, the static row and then (ux, uy) x LG_PLAN_MAX_OBS; obstacle i has its
+// centre at node k at c_i + u_i t_k, t_k = (float)k dt, every operation rounded on its own.  The static accessors ignore k.
 #define PLAN_SCN (3 + 3 * LG_PLAN_MAX_OBS)
+#define PLAN_SCNM (PLAN_SCN + 2 * LG_PLAN_MAX_OBS)
 static_assert(PLAN_SCN == 27 && (PLAN_SCN & 1), "a scene row: 2 + 24 + 1 floats, an odd stride");
+static_assert(PLAN_SCNM == 43 && (PLAN_SCNM & 1), "a moving scene row: 27 + 16 floats, an odd stride");
+enum { PLAN_SC_PROB = 0, PLAN_SC_ROW = 1, PLAN_SC_MOVING = 2 };    // a kernel's SC flag: the scene its walks read
+constexpr int plan_scn(int sc) { return sc == PLAN_SC_MOVING ? PLAN_SCNM : (sc == PLAN_SC_ROW ? PLAN_SCN : 0); }   // floats of a row
 struct PlanSceneProb {
     const lg_plan_problem &p;
     __device__ __forceinline__ int n() const { return p.n_obs; }
-    __device__ __forceinline__ float cx(int i) const { return p.obs_c[i][0]; }
-    __device__ __forceinline__ float cy(int i) const { return p.obs_c[i][1]; }
+    __device__ __forceinline__ float cx(int i, int) const { return p.obs_c[i][0]; }
+    __device__ __forceinline__ float cy(int i, int) const { return p.obs_c[i][1]; }
     __device__ __forceinline__ float r(int i) const { return p.obs_r[i]; }
     __device__ __forceinline__ float gx() const { return p.goal[0]; }
     __device__ __forceinline__ float gy() const { return p.goal[1]; }
@@ -50,17 +57,38 @@ struct PlanSceneProb {
 struct PlanSceneRow {
     const float *s;
     __device__ __forceinline__ int n() const { return (int)s[PLAN_SCN - 1]; }
-    __device__ __forceinline__ float cx(int i) const { return s[2 + 3 * i]; }
-    __device__ __forceinline__ float cy(int i) const { return s[3 + 3 * i]; }
+    __device__ __forceinline__ float cx(int i, int) const { return s[2 + 3 * i]; }
+    __device__ __forceinline__ float cy(int i, int) const { return s[3 + 3 * i]; }
+    __device__ __forceinline__ float r(int i) const { return s[4 + 3 * i]; }
+    __device__ __forceinline__ float gx() const { return s[0]; }
+    __device__ __forceinline__ float gy() const { return s[1]; }
+};
+struct PlanSceneRowMoving {
+    const float *s;
+    float dt;
+    __device__ __forceinline__ int n() const { return (int)s[PLAN_SCN - 1]; }
+    __device__ __forceinline__ float cx(int i, int k) const {
+#pragma clang fp contract(off)
+        const float t = (float)k * dt, d = s[PLAN_SCN + 2 * i] * t;
+        return s[2 + 3 * i] + d;
+    }
+    __device__ __forceinline__ float cy(int i, int k) const {
+#pragma clang fp contract(off)
+        const float t = (float)k * dt, d = s[PLAN_SCN + 2 * i + 1] * t;
+        return s[3 + 3 * i] + d;
+    }
     __device__ __forceinline__ float r(int i) const { return s[4 + 3 * i]; }
     __device__ __forceinline__ float gx() const { return s[0]; }
     __device__ __forceinline__ float gy() const { return s[1]; }
 };
 // Rows 0 .. rows - 1 of SCN take scenes s0, s0 + 1, ..; rows at and past nr are zeros with a zero count.  A part the scenes leave
 // out (goal, or obs and n_obs) comes from the problem; n_obs[s] is clamped into 0 .. LG_PLAN_MAX_OBS and slots past it are not read.
+// SC = PLAN_SC_MOVING: rows of PLAN_SCNM floats, whose last 16 take the scene's velocities (zeros past the count).
+template <int SC>
 __device__ __forceinline__ void plan_scene_stage(const PlanDev &P, float *SCN, int64_t s0, int rows, int nr, int tid) {
-    for (int e = tid; e < rows * PLAN_SCN; e += NT) {
-        const int r = e / PLAN_SCN, c = e - r * PLAN_SCN;
+    constexpr int W = plan_scn(SC);
+    for (int e = tid; e < rows * W; e += NT) {
+        const int r = e / W, c = e - r * W;
         float x = 0.f;
         if (r < nr) {
             const int64_t s = s0 + r;
@@ -70,7 +98,10 @@ __device__ __forceinline__ void plan_scene_stage(const PlanDev &P, float *SCN, i
                 n = n < 0 ? 0 : (n > LG_PLAN_MAX_OBS ? LG_PLAN_MAX_OBS : n);
                 const int q = c - 2, i = q / 3, k = q - 3 * i;
                 if (c == PLAN_SCN - 1) x = (float)n;
-                else if (i < n) x = P.sc_obs ? P.sc_obs[s * (3 * LG_PLAN_MAX_OBS) + q] : (k < 2 ? P.p.obs_c[i][k] : P.p.obs_r[i]);
+                else if (SC == PLAN_SC_MOVING && c >= PLAN_SCN) {
+                    const int qv = c - PLAN_SCN;
+                    if ((qv >> 1) < n) x = P.sc_vel[s * (2 * LG_PLAN_MAX_OBS) + qv];
+                } else if (i < n) x = P.sc_obs ? P.sc_obs[s * (3 * LG_PLAN_MAX_OBS) + q] : (k < 2 ? P.p.obs_c[i][k] : P.p.obs_r[i]);
             }
         }
         SCN[e] = x;
@@ -115,7 +146,7 @@ __device__ __forceinline__ PlanWalk plan_walk(const lg_plan_problem &p, const SN
         zw[3 * k] = zx; zw[3 * k + 1] = zy; zw[3 * k + 2] = wk;
         bool hit = false;
         for (int i = 0; i < n_obs; ++i) {
-            const float dx = zx - sn.cx(i), dy = zy - sn.cy(i), rr = sn.r(i) + wk;
+            const float dx = zx - sn.cx(i, k), dy = zy - sn.cy(i, k), rr = sn.r(i) + wk;
             const float g = (dx * dx + dy * dy) - rr * rr;
             if (g < W.minc) { W.minc = g; W.worst = k; }
             hit = hit || g < 0.f;
@@ -145,13 +176,14 @@ __device__ __forceinline__ PlanWalk plan_walk(const lg_plan_problem &p, const SN
 }
 
 // The one place a kernel's SC flag turns into a scene: the row `scn` of the tile's SCN, or the problem's own.
-template <bool SC>
+template <int SC>
 __device__ __forceinline__ auto plan_scene(const PlanDev &P, const float *scn) {
-    if constexpr (SC) return PlanSceneRow{scn};
+    if constexpr (SC == PLAN_SC_MOVING) return PlanSceneRowMoving{scn, P.p.dt};
+    else if constexpr (SC == PLAN_SC_ROW) return PlanSceneRow{scn};
     else return PlanSceneProb{P.p};
 }
 // plan_walk of a lane of a tile of kernel flag SC
-template <bool PEN, bool SC>
+template <bool PEN, int SC>
 __device__ __forceinline__ PlanWalk plan_walk_tile(const PlanDev &P, const float *scn, bool nn, const float *vr, float *fw, float *zw, float zx,
                                                    float zy, float wk) {
     return plan_walk<PEN>(P.p, plan_scene<SC>(P, scn), nn, vr, fw, zw, zx, zy, wk, P.offset);
@@ -208,8 +240,8 @@ __device__ __forceinline__ void plan_gather(const PlanDev &P, float *X, int64_t 
 }
 
 // Dynamic LDS: X (R, I) the items -- for an analytic kind the plan's inputs alone --, H0, H1 (R, U) (NN kind), FW (R, N), ZW (R, PLAN_ZS),
-// and with SC the scenes SCN (R, PLAN_SCN): row r walks against scene base + r.
-template <bool SC>
+// and with SC the scenes SCN (R, plan_scn(SC)): row r walks against scene base + r.
+template <int SC>
 __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t count) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
@@ -219,7 +251,7 @@ __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t
     const int nr = (int)(count - base < R ? count - base : R);
     float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N, *SCN = ZW + R * ZS;
     plan_gather(P, X, base, nr, tid);
-    if (SC) plan_scene_stage(P, SCN, base, R, nr, tid);
+    if constexpr (SC != PLAN_SC_PROB) plan_scene_stage<SC>(P, SCN, base, R, nr, tid);
     __syncthreads();
     if (nn) {
         const float *in = tube_hidden<R, RB, NT>(tid, D, X, D.wt, D.params, H0, H1);
@@ -229,7 +261,7 @@ __global__ void __launch_bounds__(NT) k_plan_score(TubeDev D, PlanDev P, int64_t
     }
     if (tid < nr) {
         const int64_t b = base + tid;
-        plan_store_score(P, plan_walk_tile<false, SC>(P, SCN + tid * PLAN_SCN, nn, X + tid * I + 3 * Hr, FW + tid * N, ZW + tid * ZS,
+        plan_store_score(P, plan_walk_tile<false, SC>(P, SCN + tid * plan_scn(SC), nn, X + tid * I + 3 * Hr, FW + tid * N, ZW + tid * ZS,
                                                       P.z0[b * 2], P.z0[b * 2 + 1], P.w0 ? P.w0[b] : 0.f), b);
     }
     if (!P.z && !P.w && (nn || !P.fw)) return;
@@ -291,7 +323,7 @@ __global__ void __launch_bounds__(NT) k_plan_mppi_candidates(MppiDev M, int64_t 
 // w0 serves the tile.  The layers and the lane's walk are k_plan_score's.  J = ((cost + rho_g pen_g) + rho_w pen_w) + rho_z pen_z.
 // P.cost, P.min_clear and M.pen (P, K, 3) are optional here.  No atomics; a candidate depends on (seed, instance id, it, j) alone.
 // With SC the tile's instance has a scene of its own: one row SCN (PLAN_SCN) behind ZW, which every walking lane reads.
-template <bool SC>
+template <int SC>
 __global__ void __launch_bounds__(NT) k_plan_sample_score(TubeDev D, PlanDev P, MppiDev M) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
@@ -300,7 +332,7 @@ __global__ void __launch_bounds__(NT) k_plan_sample_score(TubeDev D, PlanDev P, 
     const int64_t base = (int64_t)blockIdx.x * R;
     const int pi = (int)(base / M.K), j0 = (int)(base - (int64_t)pi * M.K);
     float *X = lds, *H0 = X + R * I, *H1 = H0 + R * U, *FW = H1 + R * U, *ZW = FW + R * N, *SCN = ZW + R * ZS;
-    if (SC) plan_scene_stage(P, SCN, pi, 1, 1, tid);
+    if constexpr (SC != PLAN_SC_PROB) plan_scene_stage<SC>(P, SCN, pi, 1, 1, tid);
     for (int e = tid; e < R * I; e += NT) {         // the columns beside the plan: the instance's e, v_prev and the level
         const int r = e / I, c = e - r * I;
         if (c < Hr) X[e] = P.e ? P.e[(int64_t)pi * Hr + c] : 0.f;
@@ -332,7 +364,10 @@ __global__ void __launch_bounds__(NT) k_plan_sample_score(TubeDev D, PlanDev P, 
         const int64_t b = base + tid;
         const float *vr = X + tid * I + 3 * Hr;
         const float w0 = P.w0 ? P.w0[pi] : 0.f;
-        const PlanWalk W = SC ? plan_walk<true>(P.p, PlanSceneRow{SCN}, nn, vr, FW + tid * N, ZW + tid * ZS, P.z0[pi * 2], P.z0[pi * 2 + 1],
+        const PlanWalk W = SC == PLAN_SC_MOVING
+                               ? plan_walk<true>(P.p, PlanSceneRowMoving{SCN, P.p.dt}, nn, vr, FW + tid * N, ZW + tid * ZS, P.z0[pi * 2],
+                                                 P.z0[pi * 2 + 1], w0, P.offset)
+                           : SC ? plan_walk<true>(P.p, PlanSceneRow{SCN}, nn, vr, FW + tid * N, ZW + tid * ZS, P.z0[pi * 2], P.z0[pi * 2 + 1],
                                                 w0, P.offset)
                               : plan_walk<true>(P.p, PlanSceneProb{P.p}, nn, vr, FW + tid * N, ZW + tid * ZS, P.z0[pi * 2],
                                                 P.z0[pi * 2 + 1], w0, P.offset);
@@ -454,11 +489,11 @@ __global__ void __launch_bounds__(NT) k_plan_mppi_update(MppiDev M) {
 #define PLAN_STEP_VS(Hr, N) ((2 * ((Hr) + (N))) | 1)
 #define PLAN_STEP_WS(Hr, N) (((Hr) + (N) + 1) | 1)
 #define PLAN_STEP_PRE 4                 // row elements whose source a thread keeps in registers: R * 32 columns / NT
-constexpr size_t plan_step_floats(int I, int U, int Hr, int N, bool scenes) {   // the tile without the weights
-    return (size_t)R * (PLAN_STEP_VS(Hr, N) + PLAN_STEP_WS(Hr, N) + I + 2 * U + PLAN_ZS(N) + (scenes ? PLAN_SCN : 0));
+constexpr size_t plan_step_floats(int I, int U, int Hr, int N, int sc) {   // the tile without the weights; sc: the kernels' SC flag
+    return (size_t)R * (PLAN_STEP_VS(Hr, N) + PLAN_STEP_WS(Hr, N) + I + 2 * U + PLAN_ZS(N) + plan_scn(sc));
 }
 struct PlanStepTile {
-    float *W, *V, *WL, *X, *H0, *H1, *ZW, *SCN;         // SCN (R, PLAN_SCN): the tile's scenes, kernels with SC alone
+    float *W, *V, *WL, *X, *H0, *H1, *ZW, *SCN;         // SCN (R, plan_scn(SC)): the tile's scenes, kernels with SC alone
     int VS, WS;
 };
 __device__ __forceinline__ PlanStepTile plan_step_tile(float *lds, const TubeDev &D, const PlanDev &P, bool wlds) {
@@ -520,8 +555,8 @@ __device__ __forceinline__ void plan_step_roll(const TubeDev &D, const PlanDev &
 }
 
 // k_plan_score for the one-step kind.  Dynamic LDS: (W the parameters), V (R, VS), WL (R, WS), X (R, I), H0, H1 (R, U), ZW (R, PLAN_ZS),
-// (SCN (R, PLAN_SCN) the scenes).
-template <bool WLDS, bool SC>
+// (SCN (R, plan_scn(SC)) the scenes).
+template <bool WLDS, int SC>
 __global__ void __launch_bounds__(NT) k_plan_score_step(TubeDev D, PlanDev P, int64_t count) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, Hr = P.Hr, ZS = PLAN_ZS(N), VC = 2 * (Hr + N);
@@ -548,11 +583,11 @@ __global__ void __launch_bounds__(NT) k_plan_score_step(TubeDev D, PlanDev P, in
         }
         S.WL[r * S.WS + c] = x;
     }
-    if (SC) plan_scene_stage(P, S.SCN, base, R, nr, tid);
+    if constexpr (SC != PLAN_SC_PROB) plan_scene_stage<SC>(P, S.SCN, base, R, nr, tid);
     plan_step_roll<WLDS>(D, P, S, tid);
     if (tid < nr) {
         const int64_t b = base + tid;
-        plan_store_score(P, plan_walk_tile<false, SC>(P, S.SCN + tid * PLAN_SCN, true, S.V + tid * S.VS + 2 * Hr, S.WL + tid * S.WS + Hr + 1,
+        plan_store_score(P, plan_walk_tile<false, SC>(P, S.SCN + tid * plan_scn(SC), true, S.V + tid * S.VS + 2 * Hr, S.WL + tid * S.WS + Hr + 1,
                                                       S.ZW + tid * ZS, P.z0[b * 2], P.z0[b * 2 + 1], S.WL[tid * S.WS + Hr]), b);
     }
     if (P.fw)
@@ -566,7 +601,7 @@ __global__ void __launch_bounds__(NT) k_plan_score_step(TubeDev D, PlanDev P, in
 
 // k_plan_sample_score for the one-step kind: the same tile with the plan columns drawn in place; tile t holds candidates of one
 // instance, whose v_prev, e and w0 every row shares.  J is formed by k_plan_sample_score's expression.
-template <bool WLDS, bool SC>
+template <bool WLDS, int SC>
 __global__ void __launch_bounds__(NT) k_plan_sample_score_step(TubeDev D, PlanDev P, MppiDev M) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, Hr = P.Hr, ZS = PLAN_ZS(N);
@@ -587,7 +622,7 @@ __global__ void __launch_bounds__(NT) k_plan_sample_score_step(TubeDev D, PlanDe
         const int r = e / (Hr + 1), c = e - r * (Hr + 1);
         S.WL[r * S.WS + c] = c < Hr ? (P.e ? P.e[(int64_t)pi * Hr + c] : 0.f) : (P.w0 ? P.w0[pi] : 0.f);
     }
-    if (SC) plan_scene_stage(P, S.SCN, pi, 1, 1, tid);
+    if constexpr (SC != PLAN_SC_PROB) plan_scene_stage<SC>(P, S.SCN, pi, 1, 1, tid);
     plan_step_roll<WLDS>(D, P, S, tid);
     if (tid < R) {
         const PlanWalk W = plan_walk_tile<true, SC>(P, S.SCN, true, S.V + tid * S.VS + 2 * Hr, S.WL + tid * S.WS + Hr + 1, S.ZW + tid * ZS,
@@ -626,7 +661,7 @@ __device__ __forceinline__ void plan_walk_back(const lg_plan_problem &p, const S
         float ly = (M[1] + M[2]) * d0 + (M[3] + M[3]) * d1;
         float lw = (2.f * p.Qw) * wk;
         for (int i = 0; i < n_obs; ++i) {
-            const float dx = zx - sn.cx(i), dy = zy - sn.cy(i), rr = sn.r(i) + wk;
+            const float dx = zx - sn.cx(i, k), dy = zy - sn.cy(i, k), rr = sn.r(i) + wk;
             const float g = (dx * dx + dy * dy) - rr * rr;
             if (g < 0.f) {
                 lx = lx - rho_g * (2.f * dx);
@@ -688,7 +723,7 @@ struct GradDev {                        // passed by value
     float v_min[2], v_max[2];
 };
 
-template <bool SC>                      // SC: the scenes SCN (R, PLAN_SCN) follow ZW; both walks of row r read scene base + r
+template <int SC>                       // SC: the scenes SCN (R, plan_scn(SC)) follow ZW; both walks of row r read scene base + r
 __global__ void __launch_bounds__(NT) k_plan_grad(TubeDev D, PlanDev P, GradDev G, int64_t count) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, N = P.p.N, I = P.I, Hr = P.Hr;
@@ -698,7 +733,7 @@ __global__ void __launch_bounds__(NT) k_plan_grad(TubeDev D, PlanDev P, GradDev 
     const int nr = (int)(count - base < R ? count - base : R);
     float *X = lds, *H = X + R * I, *FW = H + R * U * L, *ZW = FW + R * N, *SCN = ZW + R * ZS;
     plan_gather(P, X, base, nr, tid);
-    if (SC) plan_scene_stage(P, SCN, base, R, nr, tid);
+    if constexpr (SC != PLAN_SC_PROB) plan_scene_stage<SC>(P, SCN, base, R, nr, tid);
     __syncthreads();
     if (nn) {
         const float *in = tube_hidden<R, RB, NT, true>(tid, D, X, D.wt, D.params, H, nullptr);
@@ -708,7 +743,7 @@ __global__ void __launch_bounds__(NT) k_plan_grad(TubeDev D, PlanDev P, GradDev 
     if (tid < nr) {
         const int64_t b = base + tid;
         float *zw = ZW + tid * ZS;
-        const float *vr = X + tid * I + 3 * Hr, *scn = SCN + tid * PLAN_SCN;
+        const float *vr = X + tid * I + 3 * Hr, *scn = SCN + tid * plan_scn(SC);
         const PlanWalk W = plan_walk_tile<true, SC>(P, scn, nn, vr, FW + tid * N, zw, P.z0[b * 2], P.z0[b * 2 + 1], P.w0 ? P.w0[b] : 0.f);
         const float J = plan_store_J(P, W, G.rho_g, G.rho_w, G.rho_z, G.J, G.pen, b);
         plan_walk_back(P.p, plan_scene<SC>(P, scn), nn, vr, FW + tid * N, zw, G.rho_g, G.rho_w, G.rho_z);
@@ -791,9 +826,10 @@ __global__ void __launch_bounds__(NT) k_plan_grad(TubeDev D, PlanDev P, GradDev 
 
 // ------------------------------------------------------------------ launchers
 // Per-plan scenes: without them (A->scenes null) a launch takes the instantiation without, the code of
-// the entries before scenes; otherwise the <SC = true> one, whose tile carries R scene rows (one row in the sampling kernels,
-// within the same budget).
-constexpr size_t PLAN_SCN_BYTES = sizeof(float) * (size_t)R * PLAN_SCN;
+// the entries before scenes; otherwise the <SC = PLAN_SC_ROW> one, whose tile carries R scene rows (one row in the sampling kernels,
+// within the same budget), or with scenes->vel (section 10.18) the <SC = PLAN_SC_MOVING> one, whose rows are 16 floats longer.
+static int plan_sc(const lg_plan_scenes *scenes) { return !scenes ? PLAN_SC_PROB : (scenes->vel ? PLAN_SC_MOVING : PLAN_SC_ROW); }
+static size_t plan_scn_bytes(int sc) { return sizeof(float) * (size_t)R * plan_scn(sc); }     // the R scene rows of a tile
 
 // The PlanDev of a launch.  D: the handle's TubeDev, or null for an analytic kind, whose item is the plan's inputs alone.
 static PlanDev plan_dev(const TubeDev *D, const lg_plan_problem *prob, const PlanArgs *A) {
@@ -805,7 +841,7 @@ static PlanDev plan_dev(const TubeDev *D, const lg_plan_problem *prob, const Pla
     P.level = A->level;
     P.Hr = D ? prob->H_rev : 0;
     P.I = D ? D->in_dim : 2 * prob->N;
-    if (A->scenes) { P.sc_goal = A->scenes->goal; P.sc_obs = A->scenes->obs; P.sc_n = A->scenes->n_obs; }
+    if (A->scenes) { P.sc_goal = A->scenes->goal; P.sc_obs = A->scenes->obs; P.sc_n = A->scenes->n_obs; P.sc_vel = A->scenes->vel; }
     return P;
 }
 // the TubeDev a kernel takes: the handle's, or zeros for an analytic kind
@@ -832,7 +868,7 @@ static int64_t plan_launch_kernel(unsigned nwg, size_t bytes, hipStream_t s, con
     hipLaunchKernelGGL(K, dim3(nwg), dim3(NT), bytes, s, args...);
     return (int64_t)bytes;
 }
-// One planner launch: instantiation `pick` of K... -- pick = scenes, or for a one-step kernel 2 (weights in LDS) + scenes.
+// One planner launch: instantiation `pick` of K... -- pick = the SC flag, or for a one-step kernel 3 (weights in LDS) + SC.
 template <auto... K, class... Args>
 static int64_t plan_launch(int pick, unsigned nwg, size_t bytes, hipStream_t s, const Args &...args) {
     using Launch = int64_t (*)(unsigned, size_t, hipStream_t, const Args &...);
@@ -844,14 +880,14 @@ extern "C" {
 // k_plan_score.  D: the horizon handle's TubeDev, or null for an analytic kind.  Returns the dynamic LDS of the launch in bytes, or
 // -1 where the kernel's ceiling cannot be set.  The reference shape (130 inputs, 128 units, N = 50) takes 74 KiB, past k_tube_predict's
 // own 64 KiB, so the ceiling is the roll-out kernels'; the largest shape of the envelope stays below it:
-static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + 2 * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N) + PLAN_SCN) <= LG_TUBE_ROLLOUT_LDS,
+static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + 2 * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N) + PLAN_SCNM) <= LG_TUBE_ROLLOUT_LDS,
               "k_plan_score: the envelope's largest tile set must fit the dynamic LDS ceiling");
 int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const PlanArgs *A, int64_t B, hipStream_t s) {
     const PlanDev P = plan_dev(D, prob, A);
     const TubeDev T = plan_tube(D);
-    const bool sc = A->scenes != nullptr;
-    const size_t bytes = sizeof(float) * plan_tile_floats(P, 2 * T.units) + (sc ? PLAN_SCN_BYTES : 0);
-    return plan_launch<k_plan_score<false>, k_plan_score<true>>(sc, (unsigned)((B + R - 1) / R), bytes, s, T, P, B);
+    const int sc = plan_sc(A->scenes);
+    const size_t bytes = sizeof(float) * plan_tile_floats(P, 2 * T.units) + plan_scn_bytes(sc);
+    return plan_launch<k_plan_score<0>, k_plan_score<1>, k_plan_score<2>>(sc, (unsigned)((B + R - 1) / R), bytes, s, T, P, B);
 }
 
 // The sampling planner's launches.  k_plan_sample_score's tile is k_plan_score's, so the assert above
@@ -884,22 +920,24 @@ int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, c
     const TubeDev T = plan_tube(D);
     MppiDev M = mppi_dev(prob, cfg, it);
     M.vbar_in = vbar; M.J = J; M.pen = pen;
-    const bool sc = A->scenes != nullptr;
-    const size_t bytes = sizeof(float) * (plan_tile_floats(P, 2 * T.units) + (sc ? PLAN_SCN : 0));
-    return plan_launch<k_plan_sample_score<false>, k_plan_sample_score<true>>(sc, (unsigned)(P_ * cfg->K / R), bytes, s, T, P, M);
+    const int sc = plan_sc(A->scenes);
+    const size_t bytes = sizeof(float) * (plan_tile_floats(P, 2 * T.units) + plan_scn(sc));
+    return plan_launch<k_plan_sample_score<0>, k_plan_sample_score<1>, k_plan_sample_score<2>>(sc, (unsigned)(P_ * cfg->K / R), bytes, s, T, P, M);
 }
 // The one-step kind.  Every shape of the envelope fits the ceiling without the weights -- the reference
 // configurations (T <= 10, units <= 128, N <= 64) with room to spare --; lg_plan_check asks tubek_plan_step_bytes all the same.
-static_assert(sizeof(float) * plan_step_floats(LG_TUBE_MAX_IN, LG_TUBE_MAX_UNITS, LG_PLAN_STEP_MAX_HREV, LG_PLAN_MAX_N, true) <= LG_TUBE_ROLLOUT_LDS,
+static_assert(sizeof(float) * plan_step_floats(LG_TUBE_MAX_IN, LG_TUBE_MAX_UNITS, LG_PLAN_STEP_MAX_HREV, LG_PLAN_MAX_N, PLAN_SC_MOVING) <=
+                  LG_TUBE_ROLLOUT_LDS,
               "k_plan_score_step: the envelope's largest tile set must fit the dynamic LDS ceiling");
-static_assert(sizeof(float) * plan_step_floats(31, 128, LG_PLAN_STEP_MAX_HREV, 64, true) <= LG_TUBE_ROLLOUT_LDS, "the reference one-step shapes fit");
+static_assert(sizeof(float) * plan_step_floats(31, 128, LG_PLAN_STEP_MAX_HREV, 64, PLAN_SC_MOVING) <= LG_TUBE_ROLLOUT_LDS,
+              "the reference one-step shapes fit");
 // dynamic LDS of the one-step tile in bytes, without the weights and without the scene rows
 int64_t tubek_plan_step_bytes(const TubeDev *D, const lg_plan_problem *prob) {
-    return (int64_t)(sizeof(float) * plan_step_floats(D->in_dim, D->units, prob->H_rev, prob->N, false));
+    return (int64_t)(sizeof(float) * plan_step_floats(D->in_dim, D->units, prob->H_rev, prob->N, PLAN_SC_PROB));
 }
 // weights go to LDS where weights + tile fit the ceiling; *bytes: the launch's dynamic LDS
-static bool plan_step_wlds(const TubeDev *D, const lg_plan_problem *prob, bool scenes, size_t *bytes) {
-    const size_t tile = (size_t)tubek_plan_step_bytes(D, prob) + (scenes ? PLAN_SCN_BYTES : 0);
+static bool plan_step_wlds(const TubeDev *D, const lg_plan_problem *prob, int sc, size_t *bytes) {
+    const size_t tile = (size_t)tubek_plan_step_bytes(D, prob) + plan_scn_bytes(sc);
     const size_t all = tile + sizeof(float) * (size_t)D->num_params;
     const bool wl = all <= LG_TUBE_ROLLOUT_LDS;
     *bytes = wl ? all : tile;
@@ -908,22 +946,23 @@ static bool plan_step_wlds(const TubeDev *D, const lg_plan_problem *prob, bool s
 // returns the dynamic LDS of the launch in bytes, or -1 where the kernel's ceiling cannot be set
 int64_t tubek_plan_score_step(const TubeDev *D, const lg_plan_problem *prob, const PlanArgs *A, int64_t B, hipStream_t s) {
     const PlanDev P = plan_dev(D, prob, A);
-    const bool sc = A->scenes != nullptr;
+    const int sc = plan_sc(A->scenes);
     size_t bytes;
     const bool wl = plan_step_wlds(D, prob, sc, &bytes);
-    return plan_launch<k_plan_score_step<false, false>, k_plan_score_step<false, true>, k_plan_score_step<true, false>,
-                       k_plan_score_step<true, true>>(2 * wl + sc, (unsigned)((B + R - 1) / R), bytes, s, *D, P, B);
+    return plan_launch<k_plan_score_step<false, 0>, k_plan_score_step<false, 1>, k_plan_score_step<false, 2>, k_plan_score_step<true, 0>,
+                       k_plan_score_step<true, 1>, k_plan_score_step<true, 2>>(3 * wl + sc, (unsigned)((B + R - 1) / R), bytes, s, *D, P, B);
 }
 int64_t tubek_plan_sample_score_step(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const PlanArgs *A,
                                      int64_t P_, const float *vbar, float *J, float *pen, hipStream_t s) {
     const PlanDev P = plan_dev(D, prob, A);
     MppiDev M = mppi_dev(prob, cfg, it);
     M.vbar_in = vbar; M.J = J; M.pen = pen;
-    const bool sc = A->scenes != nullptr;
+    const int sc = plan_sc(A->scenes);
     size_t bytes;
     const bool wl = plan_step_wlds(D, prob, sc, &bytes);   // one scene row is read; the tile's budget is k_plan_score_step's
-    return plan_launch<k_plan_sample_score_step<false, false>, k_plan_sample_score_step<false, true>, k_plan_sample_score_step<true, false>,
-                       k_plan_sample_score_step<true, true>>(2 * wl + sc, (unsigned)(P_ * cfg->K / R), bytes, s, *D, P, M);
+    return plan_launch<k_plan_sample_score_step<false, 0>, k_plan_sample_score_step<false, 1>, k_plan_sample_score_step<false, 2>,
+                       k_plan_sample_score_step<true, 0>, k_plan_sample_score_step<true, 1>, k_plan_sample_score_step<true, 2>>(
+        3 * wl + sc, (unsigned)(P_ * cfg->K / R), bytes, s, *D, P, M);
 }
 void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,
                             const float *J, float *best_J, float *best_v, float *hist, int32_t *n_bad, hipStream_t s) {
@@ -935,7 +974,7 @@ void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg,
 
 // k_plan_grad.  Its tile keeps every hidden layer's output, so the largest shape of the envelope -- 256
 // inputs, 4 x 128 units, N = 64 -- takes 128.4 KiB at R = 32 rows and stays below the ceiling; no smaller tile is needed:
-static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + (LG_TUBE_MAX_LIN - 1) * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N) + PLAN_SCN) <=
+static_assert(sizeof(float) * R * (LG_TUBE_MAX_IN + (LG_TUBE_MAX_LIN - 1) * LG_TUBE_MAX_UNITS + LG_PLAN_MAX_N + PLAN_ZS(LG_PLAN_MAX_N) + PLAN_SCNM) <=
                   LG_TUBE_ROLLOUT_LDS,
               "k_plan_grad: the envelope's largest tile set must fit the dynamic LDS ceiling");
 static_assert(PLAN_ZS(1) >= 6, "k_plan_grad keeps J, two flags and dJ/dv of step 0 in a row of nodes at N = 1 too");
@@ -951,8 +990,8 @@ int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const Pla
     G.lr = A->lr; G.beta1 = A->beta1; G.beta2 = A->beta2; G.eps = A->eps; G.bc1 = A->bc1; G.bc2 = A->bc2;
     G.rho_g = A->rho_g; G.rho_w = A->rho_w; G.rho_z = A->rho_z;
     for (int d = 0; d < 2; ++d) { G.v_min[d] = prob->rom_v_min[d]; G.v_max[d] = prob->rom_v_max[d]; }
-    const bool sc = A->plan.scenes != nullptr;
-    const size_t bytes = sizeof(float) * plan_tile_floats(P, T.layers * T.units) + (sc ? PLAN_SCN_BYTES : 0);
-    return plan_launch<k_plan_grad<false>, k_plan_grad<true>>(sc, (unsigned)((B + R - 1) / R), bytes, s, T, P, G, B);
+    const int sc = plan_sc(A->plan.scenes);
+    const size_t bytes = sizeof(float) * plan_tile_floats(P, T.layers * T.units) + plan_scn_bytes(sc);
+    return plan_launch<k_plan_grad<0>, k_plan_grad<1>, k_plan_grad<2>>(sc, (unsigned)((B + R - 1) / R), bytes, s, T, P, G, B);
 }
 }

@@ -491,6 +491,7 @@ int lg_plan_scenes_check(const lg_plan_scenes *sc, int64_t count) {
     else if (sc->obs && !sc->n_obs) e = "obs is given without n_obs";
     else if (!sc->obs && sc->n_obs) e = "n_obs is given without obs";
     else if (!sc->goal && !sc->obs) e = "goal, obs and n_obs are all NULL: the scenes say nothing (pass NULL scenes)";
+    else if (sc->vel && !sc->obs) e = "vel is given without obs: a velocity belongs to an obstacle slot of the scenes' own";
     if (!e.empty()) { lg_set_error("lg_plan_scenes: " + e); return -1; }
     return 0;
 }

@@ -32,7 +32,10 @@ dt must be the task's rom.dt and the inputs must lie inside its rom.v_min / v_ma
 --scenes F.npz: a Scenes file (plan_tube.py --scenes writes scenes.npz beside plans.npz): plan b is scored
 and audited against scene b's own goal and obstacles, so the file holds as many scenes as --plans holds plans.  With --warm_start
 every scene gets the warm start to its own goal and, with --perturb K, K perturbations of it (seed + the scene's number): S (K + 1)
-plans, scene by scene, each scene repeated K + 1 times on the host.  The audit gains its per-plan lists (by_plan).
+plans, scene by scene, each scene repeated K + 1 times on the host.  The audit gains its per-plan lists (by_plan).  A file with
+velocities (array obs_v; section 10.18) holds obstacles that move: obs_c is where they are at node 0, the plans are scored against
+c + u (k dt) at node k, and actual safety is taken against each obstacle where it is at each node's time.  --robot does not follow
+obstacles that move.
 
 Writes audit.json to --out (default: the run folder, or the working directory) and prints the reference script's
 "Total Success Rate" line: the share of (plan, node) pairs with tube >= realised error.
@@ -308,6 +311,8 @@ def main(argv=None):
     scenes = None
     if a.scenes is not None:
         z0, v, source, scenes = build_scene_plans(a, p)
+        if scenes.obs_v is not None and getattr(a, "robot", False):
+            raise ValueError(f"--scenes {a.scenes} carries velocities (obs_v): --robot does not follow obstacles that move")
     else:
         z0, v, source = build_plans(a, p)
     skw = {} if scenes is None else {"scenes": scenes}

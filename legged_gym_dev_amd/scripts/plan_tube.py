@@ -10,7 +10,8 @@ place of CasADi / IPOPT, for many starts at once.
         [--planner mppi|grad|mppi+grad] [--lr 0.05] [--grad_iters 100] \\
         [--starts P --start_noise s] [--closed_loop H] [--sim_cfg KEY=VALUE ...] [--out DIR] \\
         [--robot [--task anymal_c_flat_trajectory] [--load_run R] [--policy_checkpoint K] [--push_robots] [--allow_fast]] \\
-        [--scenes random|FILE.npz [--scene_seed n] [--scene_obs LO,HI] [--scene_radius LO,HI] [--scene_margin M]]
+        [--scenes random|FILE.npz [--scene_seed n] [--scene_obs LO,HI] [--scene_radius LO,HI] [--scene_margin M] [--scene_speed LO,HI]] \\
+        [--fleet SEPARATION [--fleet_sense R] [--fleet_neighbours K]]
 
 --run, --tube, --calibration, --coverage, --level, --checkpoint, --sim_cfg: as audit_plans.py takes them; a run that audit_plans.py
 refuses is refused here; a step run (dataset scalar / scalar_level, rolled along the plan: DESIGN.md section 10.13) plans with
@@ -28,6 +29,14 @@ the problem's start and goal span (padded by 0.25), goals within 0.5 of the prob
 --scene_margin (default 0.05) outside every obstacle.  scenes.npz is written beside plans.npz, one scene per row of it (with
 --closed_loop the starts' scenes once per step), so audit_plans.py --plans plans.npz --scenes scenes.npz reads both; plan.json gains
 "scenes" (the source) and the audit its per-scene lists (by_plan / by_robot).  Without --scenes the output is what it was.
+--scene_speed LO,HI (with --scenes random): every obstacle moves in a uniform direction at a uniform speed in
+[LO, HI] m/s; a FILE.npz brings its own velocities (obs_v).  With --closed_loop, scenes.npz then holds the scenes where they were at
+each step's time.
+
+--closed_loop H --fleet SEPARATION: the robots avoid each other (section 10.18) -- before each plan every robot's scene is rebuilt on
+the device from the fleet's positions: its static obstacles (the problem's, or its --scenes scene), then its --fleet_neighbours
+(default 8) nearest robots within --fleet_sense (default 1.0) as discs of radius SEPARATION that move with their plans' next input.
+The audit gains min_separation and collision_free, plan.json "fleet"; scenes.npz holds the scenes each plan ran against.
 
 --closed_loop H --robot: the legged robot is the tracker -- one simulated robot of --task per start under the
 task's trained policy, replanning from the window point it is heading for at each of H ROM steps (plan_env.closed_loop_env), env,
@@ -90,6 +99,9 @@ def parse_args(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda:0")
     add_scene_flags(ap)
+    ap.add_argument("--fleet", type=float, default=None, metavar="SEPARATION", help="with --closed_loop: the robots keep this distance from each other")
+    ap.add_argument("--fleet_sense", type=float, default=None, metavar="R", help="with --fleet: robots farther than this are not seen (default 1.0)")
+    ap.add_argument("--fleet_neighbours", type=int, default=None, metavar="K", help="with --fleet: the nearest K robots are kept (default 8)")
     ap.add_argument("--robot", action="store_true", help="with --closed_loop: replan on the legged robot (one env per start) instead of the ROM-on-ROM model")
     ap.add_argument("--task", default=None, help="with --robot: a trajectory-tracking task (default anymal_c_flat_trajectory)")
     ap.add_argument("--load_run", default=None, help="with --robot: the policy's run folder (default: the latest)")
@@ -98,6 +110,7 @@ def parse_args(argv=None):
     ap.add_argument("--allow_fast", action="store_true", help="with --robot: accept ROM input bounds beyond the task's rom.v_min / v_max")
     a = ap.parse_args(argv)
     check_scene_flags(ap, a)
+    check_fleet_flags(ap, a)
     if not a.robot:
         for flag in ("task", "load_run", "policy_checkpoint", "push_robots", "allow_fast"):
             if getattr(a, flag):
@@ -107,6 +120,8 @@ def parse_args(argv=None):
                  "open-loop plans on it")
     elif a.sim_cfg:
         ap.error("--sim_cfg configures the ROM-on-ROM tracking model; --robot tracks on the legged env")
+    elif a.scene_speed is not None:
+        ap.error("--scene_speed: obstacles that move are not followed by --robot's loop (its robots live in per-env frames)")
     if a.problem not in pl.PROBLEMS and not a.problem.endswith(".json"):
         ap.error(f"--problem {a.problem}: one of {sorted(pl.PROBLEMS)} or a .json file")
     if a.calibration is not None and not a.run:
@@ -140,11 +155,48 @@ def add_scene_flags(ap):
     ap.add_argument("--scene_obs", default=None, metavar="LO,HI", help="obstacles per random scene (default 1,3)")
     ap.add_argument("--scene_radius", default=None, metavar="LO,HI", help="radius of a random obstacle (default 0.1,0.4)")
     ap.add_argument("--scene_margin", type=float, default=None, help="start and goal stay this far outside every random obstacle")
+    ap.add_argument("--scene_speed", default=None, metavar="LO,HI", help="speed in m/s of a random obstacle (default: it stands still)")
+
+
+FLEET_DEFAULTS = {"fleet_sense": 1.0, "fleet_neighbours": 8}
+
+
+def check_fleet_flags(ap, a):
+    """Refuse what does not fit --fleet and fill its defaults."""
+    if a.fleet is None:
+        for k in FLEET_DEFAULTS:
+            if getattr(a, k) is not None:
+                ap.error(f"--{k} belongs to --fleet")
+        return
+    if a.closed_loop is None:
+        ap.error("--fleet belongs to --closed_loop H: the robots avoid each other while they replan")
+    if a.robot:
+        ap.error("--fleet plans in one common frame; --robot's robots live in per-env frames")
+    for k, v in FLEET_DEFAULTS.items():
+        if getattr(a, k) is None:
+            setattr(a, k, v)
+    try:
+        fleet_cfg(a).check()
+    except ValueError as e:
+        ap.error(f"--fleet: {e}")
+
+
+def fleet_cfg(a):
+    return pl.FleetCfg(separation=a.fleet, sense_radius=a.fleet_sense, max_neighbours=a.fleet_neighbours)
+
+
+def build_fleet(a, p, scenes):
+    """The FleetScenes of --fleet: the goals and obstacles of --scenes as its goals and static part, else the problem's obstacles."""
+    if scenes is not None:
+        static = None if scenes.obs_c is None else pl.Scenes(obs_c=scenes.obs_c, obs_r=scenes.obs_r, n_obs=scenes.n_obs, obs_v=scenes.obs_v)
+        return pl.FleetScenes(a.starts, fleet_cfg(a), goal=scenes.goal, static=static)
+    rep = pl.Scenes.repeat(p, a.starts) if p.n_obs else None
+    return pl.FleetScenes(a.starts, fleet_cfg(a), static=None if rep is None else pl.Scenes(obs_c=rep.obs_c, obs_r=rep.obs_r, n_obs=rep.n_obs))
 
 
 def check_scene_flags(ap, a):
     """Refuse what does not fit, parse the LO,HI pairs and fill the defaults of --scenes random."""
-    given = [k for k in SCENE_DEFAULTS if getattr(a, k) is not None]
+    given = [k for k in list(SCENE_DEFAULTS) + ["scene_speed"] if getattr(a, k) is not None]
     if a.scenes is None:
         if given:
             ap.error(f"--{given[0]} belongs to --scenes random")
@@ -155,7 +207,7 @@ def check_scene_flags(ap, a):
         if given:
             ap.error(f"--{given[0]} belongs to --scenes random; {a.scenes} is taken as it is")
         return
-    for k, kind in (("scene_obs", int), ("scene_radius", float)):
+    for k, kind in (("scene_obs", int), ("scene_radius", float), ("scene_speed", float)):
         v = getattr(a, k)
         if v is None:
             continue
@@ -186,6 +238,8 @@ def build_scenes(a, p):
     kw = dict(n_obs=a.scene_obs, radius=a.scene_radius, margin=a.scene_margin,
               centre_box=((np.minimum(s, g) - 0.25).tolist(), (np.maximum(s, g) + 0.25).tolist()),
               goal_box=((g - 0.5).tolist(), (g + 0.5).tolist()))
+    if a.scene_speed is not None:
+        kw["speed"] = a.scene_speed
     return pl.random_scenes(a.starts, a.scene_seed, p.start, **kw), {"random": {"seed": a.scene_seed, **{k: list(v) if isinstance(v, tuple) else v for k, v in kw.items()}}, "S": a.starts}
 
 
@@ -261,10 +315,13 @@ def main(argv=None):
     z0 = starts(a, p)
     scenes, scenes_src = build_scenes(a, p)
     plan_scenes = scenes
+    if a.robot and scenes is not None and scenes.obs_v is not None:
+        raise ValueError(f"--scenes {a.scenes} carries velocities (obs_v): obstacles that move are not followed by --robot's loop")
+    fleet = build_fleet(a, p, scenes) if a.fleet is not None else None
     try:
         if a.run:
             model = HipTubeModel.load(a.run, checkpoint=a.checkpoint, device=a.device)
-        planner = make_planner(a, model, p, calib, scenes)
+        planner = make_planner(a, model, p, calib, scenes if fleet is None else fleet)
         if not a.robot:
             sim = HipRomSim(audit_plans.sim_config(a, p), device=a.device)
         if a.closed_loop is None:
@@ -282,14 +339,26 @@ def main(argv=None):
             else:
                 res = pl.closed_loop(planner, sim, a.closed_loop, z0, keep_plans=True, w0=a.w0)
                 torch.cuda.synchronize()
-                audit = pl.audit_closed_loop(res, p, goal_tol=a.goal_tol, **({} if scenes is None else {"scenes": scenes}))
-            if scenes is not None:                                      # plans.npz holds (H, P) plans: the starts' scenes once per step
+                akw = {} if scenes is None else {"scenes": scenes}
+                if fleet is not None:
+                    akw = {"scenes": fleet, "fleet": fleet.cfg}
+                audit = pl.audit_closed_loop(res, p, goal_tol=a.goal_tol, **akw)
+            if fleet is not None:                                       # the scenes each plan ran against, as the loop built them
+                fo, fv, fn = (res["fleet_" + k].cpu().numpy() for k in ("obs", "vel", "n"))
+                plan_scenes = pl.Scenes(goal=None if fleet.goal is None else np.tile(fleet.goal, (a.closed_loop, 1)),
+                                        obs_c=fo[..., :2].reshape(-1, 8, 2), obs_r=fo[..., 2].reshape(-1, 8), n_obs=fn.reshape(-1),
+                                        obs_v=fv.reshape(-1, 8, 2))
+            elif scenes is not None and scenes.obs_v is not None:       # the starts' scenes where they were at each step's time
+                at = [scenes.at(k * p.dt) for k in range(a.closed_loop)]
+                cat = lambda key: None if getattr(scenes, key) is None else np.concatenate([getattr(s, key) for s in at])
+                plan_scenes = pl.Scenes(cat("goal"), cat("obs_c"), cat("obs_r"), cat("n_obs"), cat("obs_v"))
+            elif scenes is not None:                                    # plans.npz holds (H, P) plans: the starts' scenes once per step
                 plan_scenes = scenes.take(np.tile(np.arange(scenes.S), a.closed_loop))
             hist = first["hist"]
             plans_z0, plans_v = res["plans_z"][:, :, 0].reshape(-1, 2), res["plans_v"].reshape(-1, p.N, 2)
             extra = {"n_bad": [int(x) for x in res["n_bad"].sum(dim=1).cpu()], "cost": res["cost"].cpu().double().tolist(),
                      "min_clear": res["min_clear"].cpu().double().tolist() if p.n_obs else None}
-            if scenes is not None:                                      # a scene without obstacles has min_clear = +inf: null in JSON
+            if scenes is not None or fleet is not None:                 # a scene without obstacles has min_clear = +inf: null in JSON
                 clear = res["min_clear"].cpu().double()
                 extra["min_clear"] = [[float(x) if np.isfinite(x) else None for x in row] for row in clear.tolist()]
     finally:
@@ -306,6 +375,8 @@ def main(argv=None):
         out.update({"planner": a.planner, "grad": vars(grad_cfg(a))})
     if scenes is not None:
         out["scenes"] = scenes_src
+    if fleet is not None:
+        out["fleet"] = vars(fleet.cfg)
     folder = a.out or a.run or "."
     os.makedirs(folder, exist_ok=True)
     with open(os.path.join(folder, "plan.json"), "w") as f:

@@ -270,9 +270,13 @@ class Scenes:
     """lg_plan_scenes: a goal and an obstacle list of its own for each of S plans (scoring, gradient) or S instances (MPPI); the
     rest of the problem stays the PlanProblem's.  Host arrays, validated here: goal (S, 2) or None = the problem's goal; obs_c
     (S, M <= 8, 2), obs_r (S, M) and n_obs (S) in 0..M -- scene s has the first n_obs[s] obstacles; n_obs None = M each -- or all
-    three None = the problem's obstacles.  Radii are finite and not negative; centres and goals finite."""
+    three None = the problem's obstacles.  Radii are finite and not negative; centres and goals finite.
+    obs_v (S, M, 2) or None: the obstacles' velocities in m/s, finite in the live slots; obs_c then holds
+    the centres "now", at node 0 of a plan, and obstacle i is at c_i + u_i * (k * dt) at node k.  None = every obstacle stands still."""
 
-    def __init__(self, goal=None, obs_c=None, obs_r=None, n_obs=None):
+    def __init__(self, goal=None, obs_c=None, obs_r=None, n_obs=None, obs_v=None):
+        if obs_v is not None and obs_c is None:
+            raise ValueError("obs_v is given without obs_c and obs_r: a velocity belongs to an obstacle of the scenes' own")
         if goal is None and obs_c is None and obs_r is None and n_obs is None:
             raise ValueError("goal, obs_c, obs_r and n_obs are all None: the scenes say nothing (pass scenes=None)")
         if (obs_c is None) != (obs_r is None):
@@ -304,6 +308,12 @@ class Scenes:
                 raise ValueError("obs_c: a centre is finite")
             if self.goal is not None and self.goal.shape[0] != c.shape[0]:
                 raise ValueError(f"goal holds {self.goal.shape[0]} scenes and obs_c {c.shape[0]}")
+        self.obs_v = None if obs_v is None else np.ascontiguousarray(obs_v, np.float32)
+        if self.obs_v is not None:
+            if self.obs_v.shape != self.obs_c.shape:
+                raise ValueError(f"obs_v must be {self.obs_c.shape}, one velocity per centre; got {self.obs_v.shape}")
+            if not np.isfinite(self.obs_v[live]).all():
+                raise ValueError("obs_v: a velocity is finite")
         if self.goal is not None and not np.isfinite(self.goal).all():
             raise ValueError("goal: a goal is finite")
         self._dev = {}
@@ -326,10 +336,29 @@ class Scenes:
     def take(self, idx):
         """The scenes idx (an index array or slice) as Scenes of their own; repeats are allowed (there is no plan-to-scene map)."""
         g = lambda a: None if a is None else a[idx]
-        return Scenes(g(self.goal), g(self.obs_c), g(self.obs_r), g(self.n_obs))
+        return Scenes(g(self.goal), g(self.obs_c), g(self.obs_r), g(self.n_obs), g(self.obs_v))
+
+    def _live(self):
+        return np.arange(self.obs_c.shape[1])[None, :] < self.n_obs[:, None]
+
+    @property
+    def moving(self):
+        """Whether the scenes carry velocities (the device struct then has `vel`, and the kernels read moving rows)."""
+        return self.obs_v is not None
+
+    def at(self, t):
+        """The host scenes advanced to time t: every centre c + u * t in float32 with the device's roundings (u * t, then c + ..);
+        the velocities stay.  Without velocities: the same scenes."""
+        if self.obs_v is None:
+            return self.take(slice(None))
+        t = np.float32(t)
+        return Scenes(self.goal, self.obs_c + self.obs_v * t, self.obs_r, self.n_obs, self.obs_v)
 
     def problem(self, s, base):
-        """Scene s as a plain PlanProblem: `base` with the scene's goal and obstacles (float32 values, as the kernels read them)."""
+        """Scene s as a plain PlanProblem: `base` with the scene's goal and obstacles (float32 values, as the kernels read them).
+        ValueError for a scene with a live velocity that is not zero: a PlanProblem cannot express one (take([s]) can)."""
+        if self.obs_v is not None and (self.obs_v[s, :int(self.n_obs[s])] != 0).any():
+            raise ValueError(f"scene {s} has a moving obstacle, which a PlanProblem cannot express: plan against scenes.take([{s}])")
         kw = {}
         if self.goal is not None:
             kw["goal"] = [float(x) for x in self.goal[s]]
@@ -345,14 +374,22 @@ class Scenes:
             return np.tile(np.asarray(problem.goal, np.float64), (self.S, 1))
         return self.goal.astype(np.float64)
 
-    def obstacles(self, problem):
-        """(c (S, M, 2), r (S, M), live (S, M) bool) float64: every scene's obstacles (the problem's where the scenes carry none)."""
+    def obstacles(self, problem, t=None):
+        """(c (S, M, 2), r (S, M), live (S, M) bool) float64: every scene's obstacles (the problem's where the scenes carry none).
+        t: a time, or an array (T) of times, one per node; c is then (S, T, M, 2) for the array, the centres c + u * t in float64."""
         if self.obs_c is None:
             M = problem.n_obs
-            return (np.tile(np.asarray(problem.obs_c, np.float64).reshape(1, M, 2), (self.S, 1, 1)),
-                    np.tile(np.asarray(problem.obs_r, np.float64).reshape(1, M), (self.S, 1)), np.ones((self.S, M), bool))
-        live = np.arange(self.obs_c.shape[1])[None, :] < self.n_obs[:, None]
-        return self.obs_c.astype(np.float64), self.obs_r.astype(np.float64), live
+            c = np.tile(np.asarray(problem.obs_c, np.float64).reshape(1, M, 2), (self.S, 1, 1))
+            r, live, u = np.tile(np.asarray(problem.obs_r, np.float64).reshape(1, M), (self.S, 1)), np.ones((self.S, M), bool), None
+        else:
+            c, r, live, u = self.obs_c.astype(np.float64), self.obs_r.astype(np.float64), self._live(), self.obs_v
+        if t is None:
+            return c, r, live
+        t = np.asarray(t, np.float64)
+        u = np.zeros_like(c) if u is None else np.where(live[..., None], u.astype(np.float64), 0.0)
+        if t.ndim == 0:
+            return c + u * t, r, live
+        return c[:, None] + u[:, None] * t[None, :, None, None], r, live
 
     def packed(self):
         """obs (S, 8, 3) float32 [cx, cy, r], zeros past n_obs, as the library reads it; None without obstacles of their own."""
@@ -364,28 +401,48 @@ class Scenes:
         obs[:, :M] = np.where(live, np.concatenate([self.obs_c, self.obs_r[..., None]], axis=2), np.float32(0))
         return obs
 
+    def packed_vel(self):
+        """vel (S, 8, 2) float32 [ux, uy], zeros past n_obs, as the library reads it; None without velocities."""
+        if self.obs_v is None:
+            return None
+        M = self.obs_v.shape[1]
+        vel = np.zeros((self.S, capi.PLAN_MAX_OBS, 2), np.float32)
+        vel[:, :M] = np.where(self._live()[..., None], self.obs_v, np.float32(0))
+        return vel
+
     def to(self, device):
         """The device copy: (lg_plan_scenes, the tensors it points to), kept per device."""
         import torch
         key = str(torch.device(device))
         if key not in self._dev:
             up = lambda a: None if a is None else torch.as_tensor(a).to(device).contiguous()
-            t = (up(self.goal), up(self.packed()), up(self.n_obs))
+            t = (up(self.goal), up(self.packed()), up(self.n_obs), up(self.packed_vel()))
             st = capi.lg_plan_scenes()
             st.S = self.S
-            st.goal, st.obs, st.n_obs = (None if x is None else x.data_ptr() for x in t)
+            st.goal, st.obs, st.n_obs, st.vel = (None if x is None else x.data_ptr() for x in t)
+            if self.obs_v is not None:                  # set_time's sources: the centres at t = 0
+                t = t + (t[1][:, :, :2].clone(),)
             self._dev[key] = (st, t)
         return self._dev[key]
 
+    def set_time(self, device, t):
+        """Rewrite the centres of the cached device `obs` in place as c0 + u * t (float32: u * t, then c0 + ..): "now" becomes t.
+        The pointers stay, nothing is allocated for the scenes and nothing is read back.  Nothing to do without velocities."""
+        import torch
+        if self.obs_v is None:
+            return
+        _, (_, obs, _, vel, c0) = self.to(device)
+        torch.add(c0, vel * float(np.float32(t)), out=obs[:, :, :2])
+
     def save(self, path):
-        np.savez(path, **{k: getattr(self, k) for k in ("goal", "obs_c", "obs_r", "n_obs") if getattr(self, k) is not None})
+        np.savez(path, **{k: getattr(self, k) for k in ("goal", "obs_c", "obs_r", "n_obs", "obs_v") if getattr(self, k) is not None})
 
     @classmethod
     def load(cls, path):
         with np.load(path) as d:
-            bad = sorted(set(d.files) - {"goal", "obs_c", "obs_r", "n_obs"})
+            bad = sorted(set(d.files) - {"goal", "obs_c", "obs_r", "n_obs", "obs_v"})
             if bad:
-                raise ValueError(f"{path}: unknown scene array(s) {bad}; the arrays are goal, obs_c, obs_r, n_obs")
+                raise ValueError(f"{path}: unknown scene array(s) {bad}; the arrays are goal, obs_c, obs_r, n_obs, obs_v")
             return cls(**{k: d[k] for k in d.files})
 
 
@@ -395,15 +452,149 @@ def scenes_check(scenes, count):
         raise ValueError(f"{SCENES_ERR}S = {scenes.S} differs from the call's count of plans or instances = {count}")
 
 
+# ---------------------------------------------------------------- a fleet's scenes
+@dataclasses.dataclass
+class FleetCfg:
+    """lg_fleet_cfg, field for field: every other robot within sense_radius is a disc of radius `separation` (centre to centre)
+    that moves with the input its plan in force applies next; the max_neighbours nearest are kept."""
+    separation: float = 0.2
+    sense_radius: float = 1.0
+    max_neighbours: int = 8
+
+    def check(self):
+        """ValueError in lg_plan_fleet_scenes' words, the field named."""
+        for name in ("separation", "sense_radius"):
+            x = float(getattr(self, name))
+            if not (np.isfinite(x) and x >= 0):
+                raise ValueError(f"{name} must be finite and not negative")
+        if not 0 <= int(self.max_neighbours) <= capi.PLAN_MAX_OBS:
+            raise ValueError(f"max_neighbours = {self.max_neighbours} must lie in 0..{capi.PLAN_MAX_OBS}")
+
+    def to_struct(self):
+        c = capi.lg_fleet_cfg()
+        c.separation, c.sense_radius, c.max_neighbours = float(self.separation), float(self.sense_radius), int(self.max_neighbours)
+        return c
+
+
+def fleet_scenes(cfg, pos, vel, t=0.0, static=None, out=None):
+    """lg_plan_fleet_scenes: one launch from the robots' device positions and velocities (P, 2).  static: None or the device
+    tensors (obs (P, 8, 3), vel (P, 8, 2) or None, n (P) int32).  out: (obs, vel, n_obs) to write into, or None = new tensors.
+    Returns (obs (P, 8, 3), obs_vel (P, 8, 2), n_obs (P) int32)."""
+    import torch
+    from ..lib import LeggedHipError, load
+    cfg.check()
+    if pos.device.type != "cuda":
+        raise LeggedHipError("a fleet's scenes are built on a GPU device (no CPU fallback); got " + str(pos.device))
+    P, dev, M = pos.shape[0], pos.device, capi.PLAN_MAX_OBS
+    pos, vel = pos.to(torch.float32).contiguous(), vel.to(dev, torch.float32).contiguous()
+    if tuple(pos.shape) != (P, 2) or tuple(vel.shape) != (P, 2) or P < 1:
+        raise ValueError(f"pos and vel must be (P >= 1, 2); got {tuple(pos.shape)} and {tuple(vel.shape)}")
+    if out is None:
+        out = (torch.empty(P, M, 3, device=dev), torch.empty(P, M, 2, device=dev), torch.empty(P, device=dev, dtype=torch.int32))
+    s_obs, s_vel, s_n = (None, None, None) if static is None else static
+    for name, x, shape in (("obs", out[0], (P, M, 3)), ("obs_vel", out[1], (P, M, 2)), ("n_obs", out[2], (P,)),
+                           ("static obs", s_obs, (P, M, 3)), ("static vel", s_vel, (P, M, 2)), ("n_static", s_n, (P,))):
+        if x is not None and (tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev):
+            raise ValueError(f"{name} must be a contiguous {shape} tensor on {dev}")
+    lib = load()
+    torch.cuda.set_device(dev)
+    rc = lib.lg_plan_fleet_scenes(C.byref(cfg.to_struct()), _ptr(pos), _ptr(vel), P, _ptr(s_obs), _ptr(s_vel), _ptr(s_n), float(t),
+                                  _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise LeggedHipError(f"lg_plan_fleet_scenes failed ({rc}): {lib.lg_last_error().decode()}")
+    return out
+
+
+class FleetScenes(Scenes):
+    """The scenes of a fleet of P robots, rebuilt on the device from the fleet's own state (lg_plan_fleet_scenes): robot p's scene is
+    its static obstacles, then its nearest neighbours as moving discs.  goal (P, 2) or None: a goal per robot.  static: a Scenes of
+    S = P with obstacles (and velocities, maybe) of its own, or None.  The device tensors are persistent: to(device) always returns
+    the same struct and pointers, and update(pos, vel, t) rewrites obs, vel and n_obs in one launch.  The host arrays (obs_c, ..) are
+    the static part, which is what the audits test actual safety against; the robots themselves are audit_closed_loop(fleet=)'s."""
+
+    def __init__(self, P, cfg, goal=None, static=None):
+        cfg.check()
+        if static is not None and static.obs_c is None:
+            raise ValueError("static: a Scenes with obstacles of its own (obs_c, obs_r, n_obs)")
+        if static is not None and static.goal is not None:
+            raise ValueError("static carries goals: a fleet's goals are FleetScenes' own argument")
+        s, self.P = static, int(P)
+        if goal is not None or s is not None:
+            Scenes.__init__(self, goal, *((None,) * 4 if s is None else (s.obs_c, s.obs_r, s.n_obs, s.obs_v)))
+            if Scenes.S.fget(self) != int(P):
+                raise ValueError(f"the goals or the static scenes hold {Scenes.S.fget(self)} scenes; the fleet has P = {P} robots")
+        else:
+            self.goal = self.obs_c = self.obs_r = self.n_obs = self.obs_v = None
+            self._dev = {}
+        self.cfg = cfg
+        if self.P < 1:
+            raise ValueError(f"P = {P} must be at least 1")
+
+    @property
+    def S(self):
+        return self.P
+
+    @property
+    def moving(self):
+        return True
+
+    def take(self, idx):
+        raise ValueError("a fleet's scenes depend on the whole fleet: take() has no meaning (build a FleetScenes of the robots you want)")
+
+    def obstacles(self, problem, t=None):
+        if self.obs_c is None:                          # no static part: the device scenes hold neighbours alone, not the problem's
+            T = () if t is None or np.ndim(t) == 0 else (len(t),)
+            return np.zeros((self.P,) + T + (0, 2)), np.zeros((self.P, 0)), np.zeros((self.P, 0), bool)
+        return Scenes.obstacles(self, problem, t)
+
+    def to(self, device):
+        import torch
+        key = str(torch.device(device))
+        if key not in self._dev:
+            M = capi.PLAN_MAX_OBS
+            up = lambda a: None if a is None else torch.as_tensor(a).to(device).contiguous()
+            static = None if self.obs_c is None else (up(self.packed()), up(self.packed_vel()), up(self.n_obs))
+            zeros = lambda *s, **kw: torch.zeros(*s, device=device, **kw)
+            t = (up(self.goal), zeros(self.P, M, 3), zeros(self.P, dtype=torch.int32), zeros(self.P, M, 2), static)
+            if static is not None:                      # before the first update: the static part at t = 0
+                t[1].copy_(static[0]), t[2].copy_(static[2])
+                if static[1] is not None:
+                    t[3].copy_(static[1])
+            st = capi.lg_plan_scenes()
+            st.S = self.P
+            st.goal, st.obs, st.n_obs, st.vel = (None if x is None else x.data_ptr() for x in t[:4])
+            self._dev[key] = (st, t)
+        return self._dev[key]
+
+    def set_time(self, device, t):
+        raise ValueError("a fleet's scenes take their time in update(pos, vel, t)")
+
+    def update(self, pos, vel, t=0.0):
+        """The one launch: the scenes of the fleet at positions pos (P, 2) moving with vel (P, 2) (device tensors) at time t, into
+        the persistent tensors of pos's device.  Returns (obs, vel, n_obs), the tensors the struct points to."""
+        _, (_, obs, n, v, static) = self.to(pos.device)
+        if tuple(pos.shape) != (self.P, 2):
+            raise ValueError(f"pos must be {(self.P, 2)}; got {tuple(pos.shape)}")
+        fleet_scenes(self.cfg, pos, vel, t, static=static, out=(obs, v, n))
+        return obs, v, n
+
+    def save(self, path):
+        raise ValueError("a fleet's scenes are rebuilt from the fleet's state and have no file form: save the static part")
+
+
 RANDOM_SCENES_TRIES = 1000                          # rejections per scene before random_scenes gives up
 
 
 def random_scenes(S, seed, start, n_obs=(1, 3), centre_box=((0.0, 0.0), (2.0, 2.0)), radius=(0.1, 0.4),
-                  goal_box=((1.5, 1.5), (2.5, 2.5)), margin=0.05):
+                  goal_box=((1.5, 1.5), (2.5, 2.5)), margin=0.05, speed=None):
     """S random scenes from numpy's default_rng(seed): per scene n in n_obs = (lo, hi) inclusive, a goal uniform in goal_box
     ((x_lo, y_lo), (x_hi, y_hi)), n centres uniform in centre_box and radii uniform in radius = (lo, hi).  A draw is rejected
     unless `start` -- (2,) or (S, 2) -- and the goal lie at least `margin` outside every obstacle, taken in float64 on the float32
-    values kept; after RANDOM_SCENES_TRIES rejections of one scene a ValueError names it."""
+    values kept; after RANDOM_SCENES_TRIES rejections of one scene a ValueError names it.  speed = (lo, hi): every obstacle moves
+     in a uniform direction at a uniform speed in [lo, hi] m/s, drawn after its scene is accepted, so
+    speed=None draws the scenes it drew before speeds existed."""
+    if speed is not None and not 0 <= speed[0] <= speed[1]:
+        raise ValueError(f"speed = {tuple(speed)}: 0 <= lo <= hi")
     lo, hi = int(n_obs[0]), int(n_obs[1])
     if S < 1 or not 0 <= lo <= hi <= capi.PLAN_MAX_OBS:
         raise ValueError(f"S = {S} must be at least 1 and n_obs = {tuple(n_obs)} lie in 0..{capi.PLAN_MAX_OBS}, lo <= hi")
@@ -413,6 +604,7 @@ def random_scenes(S, seed, start, n_obs=(1, 3), centre_box=((0.0, 0.0), (2.0, 2.
     rng = np.random.default_rng(int(seed))
     cb, gb = np.asarray(centre_box, np.float64), np.asarray(goal_box, np.float64)
     goal, c, r, cnt = np.zeros((S, 2), np.float32), np.zeros((S, hi, 2), np.float32), np.zeros((S, hi), np.float32), np.zeros(S, np.int32)
+    u = None if speed is None else np.zeros((S, hi, 2), np.float32)
     for s in range(S):
         for _ in range(RANDOM_SCENES_TRIES):
             n = int(rng.integers(lo, hi + 1))
@@ -422,17 +614,27 @@ def random_scenes(S, seed, start, n_obs=(1, 3), centre_box=((0.0, 0.0), (2.0, 2.
             far = lambda q: (np.linalg.norm(q[None, :] - cs.astype(np.float64), axis=1) >= rs.astype(np.float64) + margin).all()
             if far(start[s]) and far(g.astype(np.float64)):
                 goal[s], c[s, :n], r[s, :n], cnt[s] = g, cs, rs, n
+                if speed is not None:
+                    ang, mag = rng.uniform(0.0, 2.0 * np.pi, n), rng.uniform(speed[0], speed[1], n)
+                    u[s, :n] = (mag[:, None] * np.stack([np.cos(ang), np.sin(ang)], axis=1)).astype(np.float32)
                 break
         else:
             raise ValueError(f"random_scenes: scene {s} was rejected {RANDOM_SCENES_TRIES} times: no draw keeps the start and the goal "
                              f"{margin} outside every obstacle (n_obs={tuple(n_obs)}, radius={tuple(radius)}, centre_box={cb.tolist()})")
-    return Scenes(goal=goal, obs_c=c, obs_r=r, n_obs=cnt)
+    return Scenes(goal=goal, obs_c=c, obs_r=r, n_obs=cnt, obs_v=u)
 
 
 def _scene_safe(pz, problem, scenes):
-    """actually_safe per plan: no node of pz (B, T, 2) float64 inside an obstacle of the plan's own scene."""
+    """actually_safe per plan: no node of pz (B, T, 2) float64 inside an obstacle of the plan's own scene; with velocities the
+    obstacle is taken where it is at the node's time, node j at j * dt."""
     import torch
     scenes_check(scenes, pz.shape[0])
+    if getattr(scenes, "obs_v", None) is not None:
+        c, r, live = (torch.as_tensor(a) for a in scenes.obstacles(problem, t=np.arange(pz.shape[1]) * float(problem.dt)))
+        if c.shape[2] == 0:
+            return torch.ones(pz.shape[0], dtype=torch.bool)
+        d = torch.linalg.vector_norm(pz[:, :, None, :] - c, dim=-1)
+        return ~((d < r[:, None, :]) & live[:, None, :]).any(dim=2).any(dim=1)
     c, r, live = (torch.as_tensor(a) for a in scenes.obstacles(problem))
     if c.shape[1] == 0:
         return torch.ones(pz.shape[0], dtype=torch.bool)
@@ -955,7 +1157,7 @@ def shift_past(e, v_prev, err, v_k):
     return torch.cat([e[:, 1:], err[:, None]], dim=1), torch.cat([v_prev[:, 1:], v_k[:, None]], dim=1)
 
 
-def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=False, track_fn=None, w0="zero"):
+def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=False, track_fn=None, w0="zero", fleet=None):
     """trajopt/tube_planning_closed_loop.py:82-168 ("TPCL") for P robots at once: plan, apply the first action, replan, H times.
     start (P, 2); x0 (P, 4) the robots' states, None = (start, 0, 0).  The first plan runs iters_first iterations (None = cfg.iters)
     from the warm start, every later one cfg.iters from the previous mean plan shifted by one step.
@@ -965,8 +1167,14 @@ def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=Fa
     plan starts from the ROM's z_{k+1} (TPCL:159).  No plan is made after the last step.
     w0: "zero" starts every plan's tube at 0 (w0 = None); "error" at |z_k - pz_x_k|, the tracking error at the replanning instant --
     the quantity the first column of a one-step tube model (tube_kind 'nn_step') was trained on.
+    Moving scenes: where planner.scenes carries velocities, scenes.set_time(device, k * dt) comes before
+    the plan of control step k, and the scenes are put back to time 0 at the end.  fleet: None = a FleetScenes as planner.scenes is
+    updated before the plan of step k with update(pz_x_k, v_k, k * dt), v_k being the input each robot's plan in force applies next:
+    zeros before the first plan, shift_plan(v_sol)[:, 0] afterwards; False = it is left as it stands.
     Returns device tensors z (P, H+1, 2), v (P, H, 2), w (P, H+1), pz_x (P, H+1, 2), x (P, H+1, 4), u (P, H S, 2), cost, min_clear,
-    best_J (P, H) of the plan in force, n_bad (P, H) and, with keep_plans, plans_v (H, P, N, 2), plans_z (H, P, N+1, 2), plans_w."""
+    best_J (P, H) of the plan in force, n_bad (P, H) and, with keep_plans, plans_v (H, P, N, 2), plans_z (H, P, N+1, 2), plans_w and,
+    for a fleet, fleet_obs (H, P, 8, 3), fleet_vel (H, P, 8, 2), fleet_n (H, P) and fleet_v (H, P, 2): the scenes each plan ran
+    against and the velocities they were built from."""
     import torch
     p = planner.problem
     track_fn = track if track_fn is None else track_fn
@@ -985,6 +1193,24 @@ def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=Fa
     z, v, w, pz, x, u = [zk], [], [torch.zeros(P, device=dev)], [xk[:, :2]], [xk], []
     cost, clear, bestJ, nbad, plans = [], [], [], [], {"v": [], "z": [], "w": []}
     w_start = (lambda: None) if w0 == "zero" else (lambda: torch.linalg.vector_norm(z[-1] - pz[-1], dim=1))
+    scenes = getattr(planner, "scenes", None)
+    if fleet not in (None, False, True) and fleet is not scenes:
+        raise ValueError("fleet: None, False, or the FleetScenes that is planner.scenes")
+    is_fleet = isinstance(scenes, FleetScenes) and fleet is not False
+    if fleet is not None and fleet is not False and not is_fleet:
+        raise ValueError("fleet is asked for, but planner.scenes is no FleetScenes")
+    timed = scenes is not None and not isinstance(scenes, FleetScenes) and scenes.obs_v is not None
+    built = {"obs": [], "vel": [], "n": [], "v": []}
+
+    def scene_step(k, v_next):                          # the scenes of control step k, before its plan
+        if timed:
+            scenes.set_time(dev, k * p.dt)
+        if is_fleet:
+            got = scenes.update(xk[:, :2].contiguous(), v_next, k * p.dt)
+            if keep_plans:
+                built["obs"].append(got[0].clone()), built["vel"].append(got[1].clone()), built["n"].append(got[2].clone())
+                built["v"].append(v_next.clone())
+    scene_step(0, torch.zeros(P, 2, device=dev))
     sol = planner.plan(zk, None, e, v_prev, w_start(), iters=iters_first)
     for k in range(H):
         v_sol, z_sol, w_sol = sol["v"], sol["score"]["z"], sol["score"]["w"]
@@ -999,17 +1225,42 @@ def closed_loop(planner, sim, H, start, x0=None, iters_first=None, keep_plans=Fa
             plans["v"].append(v_sol), plans["z"].append(z_sol), plans["w"].append(w_sol)
         e, v_prev = shift_past(e, v_prev, err, v_k)
         if k + 1 < H:
+            scene_step(k + 1, shift_plan(v_sol)[:, 0])
             sol = planner.plan(z[-1], shift_plan(v_sol), e, v_prev, w_start())
+    if timed:
+        scenes.set_time(dev, 0.0)
     out = {"z": torch.stack(z, 1), "v": torch.stack(v, 1), "w": torch.stack(w, 1), "pz_x": torch.stack(pz, 1), "x": torch.stack(x, 1),
            "u": torch.cat(u, 1), "cost": torch.stack(cost, 1), "min_clear": torch.stack(clear, 1), "best_J": torch.stack(bestJ, 1),
            "n_bad": torch.stack(nbad, 1)}
     if keep_plans:
         out.update({"plans_" + k: torch.stack(t, 0) for k, t in plans.items()})
+        if is_fleet:
+            out.update({"fleet_" + k: torch.stack(t, 0) for k, t in built.items()})
     return out
 
 
-def audit_closed_loop(result, problem, goal_tol=0.1, scenes=None):
-    """Did the tube hold in closed loop?  scenes: a Scenes of S = the robots; actually_safe and reached_goal are then taken against
+FLEET_AUDIT_CHUNK = 256                             # robots per block of pairs in fleet_separation
+
+
+def fleet_separation(pz):
+    """(P) float64: every robot's smallest distance to another robot at the same step, over all steps of pz (P, T, 2) float64; inf
+    for a fleet of one.  Chunked over pairs: FLEET_AUDIT_CHUNK x P x T distances at a time."""
+    import torch
+    P = pz.shape[0]
+    out = torch.full((P,), float("inf"), dtype=torch.float64)
+    for a in range(0, P, FLEET_AUDIT_CHUNK):
+        d = torch.linalg.vector_norm(pz[a:a + FLEET_AUDIT_CHUNK, None] - pz[None], dim=-1)      # (chunk, P, T)
+        d[torch.arange(d.shape[0]), torch.arange(a, a + d.shape[0])] = float("inf")
+        d = torch.nan_to_num(d, nan=float("inf"), posinf=float("inf"))
+        out[a:a + FLEET_AUDIT_CHUNK] = d.reshape(d.shape[0], -1).min(dim=1).values
+    return out
+
+
+def audit_closed_loop(result, problem, goal_tol=0.1, scenes=None, fleet=None):
+    """Did the tube hold in closed loop?  With moving scenes actual safety is taken against each obstacle where it is at step k's
+    time, k * dt.  fleet: a FleetCfg; adds min_separation (the smallest distance between two robots at one step of the realised
+    pz_x, float64; None for one robot), collision_free (the share of robots never closer than `separation` to another at the same
+    step) and by_robot["collision_free"].   scenes: a Scenes of S = the robots; actually_safe and reached_goal are then taken against
     each robot's own obstacles and goal.  Plain Python numbers (strict JSON).  coverage_by_step[k]: share of robots with
     w_k >= |z_k - pz_x_k|; coverage: its mean; covered_robots: share covered at every step; actually_safe: share whose realised path
     pz_x enters no obstacle; predicted_safe: share whose plans in force all had min_clear >= 0; reached_goal: share whose ROM path
@@ -1037,4 +1288,10 @@ def audit_closed_loop(result, problem, goal_tol=0.1, scenes=None):
         res["by_robot"] = {"covered": [bool(x) for x in cov.all(dim=1)], "predicted_safe": [bool(x) for x in pred],
                            "actually_safe": [bool(x) for x in act], "reached_goal": [bool(x) for x in dist <= goal_tol],
                            "goal_distance": [float(x) for x in dist]}
+    if fleet is not None:
+        sep = fleet_separation(pz)
+        free = sep >= float(fleet.separation)
+        res["min_separation"] = float(sep.min()) if bool(torch.isfinite(sep.min())) else None
+        res["collision_free"] = share(free)
+        res.setdefault("by_robot", {})["collision_free"] = [bool(x) for x in free]
     return res

@@ -1,0 +1,396 @@
+"""Moving obstacles in per-plan scenes and fleets that avoid each other, on the GPU:
+  1. zero velocities are the static scenes on the bits, for every entry and tube kind;
+  2. with heterogeneous moving scenes, plan b (MPPI instance p) is a call of one plan (instance) on scenes.take([b]);
+  3. cost and min_clear against tests/plan_moving_ref.py per plan in float64 under the chain yardstick (4 e32) and the margins (1e-5 on
+     g, 1e-6 on a bound) of tests/test_hip_plan_score.py; counts and worst_node exact outside them;
+  4. dJ/dv and J of lg_plan_grad_scenes against float64 autograd, away from kinks (1e-4), with an obstacle that binds only because it moves;
+  5. lg_plan_fleet_scenes against the rule restated in NumPy (plan_moving_ref.fleet_rule), array_equal;
+  6. eight robots that swap places on a circle, with and without seeing each other; 7. the scripts."""
+import dataclasses
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import plan_moving_ref as mr
+from tests import plan_ref
+from tests.test_hip_mppi import _analytic, _instances
+from tests.test_hip_mppi import _trainer as _horizon
+from tests.test_hip_plan_scenes import RHO, ROWS, TUBES, _hetero, _past, _problem
+from tests.test_hip_plan_score import _plans, _ref_problem, _same, _yardstick
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "legged_gym_dev_amd", "scripts"))
+
+
+def _moving(S, scene_seed, vel_seed):
+    """_hetero's scenes with a velocity of up to 0.1 m/s per axis in every slot."""
+    from legged_gym_dev_amd.tube.plan import Scenes
+    sc = _hetero(S, scene_seed)
+    u = np.random.default_rng(vel_seed).uniform(-0.1, 0.1, (S, 8, 2)).astype(np.float32)
+    return Scenes(sc.goal, sc.obs_c, sc.obs_r, sc.n_obs, u)
+
+
+def _model(name, N):
+    return TUBES[name][3](N) if TUBES[name][3] else None
+
+
+# ---------------------------------------------------------------- 1. zero velocities are the static scenes
+@pytest.mark.parametrize("N", [1, 5, 64])
+@pytest.mark.parametrize("name", list(TUBES))
+def test_zero_velocities_are_the_static_scenes(name, N):
+    from legged_gym_dev_amd.tube import plan as pl
+    tr = _model(name, N)
+    try:
+        p, Hr = _problem(name, N), TUBES[name][1]
+        sc = pl.HipPlanScorer(tr, p, device=DEV)
+        for B in (1, 33, 65):
+            d = _plans(B, N, Hr, seed=B)
+            past, still = _past(name, d), _hetero(B, B)
+            zero = pl.Scenes(still.goal, still.obs_c, still.obs_r, still.n_obs, np.zeros(still.obs_c.shape, np.float32))
+            assert zero.to(DEV)[0].vel and not still.to(DEV)[0].vel      # the moving rows are what runs
+            old, new = sc.score(d["z0"], d["v"], *past, scenes=still), sc.score(d["z0"], d["v"], *past, scenes=zero)
+            assert sorted(old) == sorted(new) == ["cost", "fw", "min_clear", "n_viol", "w", "worst_node", "z"]
+            for k in old:
+                _same(old[k], new[k], f"score {k}, B {B}")
+            if p.tube_kind != "nn_step":
+                a = pl.HipGradPlanner(tr, p, pl.GradCfg(**RHO), device=DEV, scenes=still).gradient(d["z0"], d["v"], *past)
+                b = pl.HipGradPlanner(tr, p, pl.GradCfg(**RHO), device=DEV, scenes=zero).gradient(d["z0"], d["v"], *past)
+                assert sorted(a) == ["J", "cost", "grad", "min_clear", "pen"]
+                for k in a:
+                    _same(a[k], b[k], f"grad {k}, B {B}")
+        P, cfg = 3, pl.MppiCfg(K=32, iters=1, sigma=0.1, seed=5, lambda_=5.0, **RHO)
+        d, still = _plans(P, N, Hr, seed=77), _hetero(P, 7)
+        zero = pl.Scenes(still.goal, still.obs_c, still.obs_r, still.n_obs, np.zeros(still.obs_c.shape, np.float32))
+        got = []
+        for scenes in (still, zero):
+            pln = pl.HipMppiPlanner(tr, p, cfg, device=DEV, scenes=scenes)
+            st = pln.state(d["z0"], d["v"], *_past(name, d), want=("cost", "min_clear", "pen"))
+            hist = torch.empty(P, 2, device=DEV)
+            pln.step(st, 0, what=3, reset=True, hist_row=hist)
+            got.append({**{k: st[k] for k in ("J", "cost", "min_clear", "pen", "vbar", "best_J", "best_v", "n_bad")}, "hist": hist})
+        for k in got[0]:
+            _same(got[0][k], got[1][k], f"mppi {k}")
+        assert not torch.equal(got[0]["vbar"].cpu(), d["v"])
+    finally:
+        if tr:
+            tr.close()
+
+
+# ---------------------------------------------------------------- 2. each plan sees its own moving scene
+@pytest.mark.parametrize("name", ["l1", "nn", "step-recursive-lds"])
+def test_each_plan_sees_its_own_moving_scene(name):
+    from legged_gym_dev_amd.tube import plan as pl
+    N, B, Hr = 16, 65, TUBES[name][1]
+    tr = _model(name, N)
+    try:
+        p, scenes = _problem(name, N), _moving(B, 2, 1002)
+        assert scenes.n_obs[list(ROWS)].tolist() == [7, 8, 0, 1, 6]
+        d = _plans(B, N, Hr, seed=3)
+        big = pl.HipPlanScorer(tr, p, device=DEV).score(d["z0"], d["v"], *_past(name, d), scenes=scenes)
+        still = pl.HipPlanScorer(tr, p, device=DEV).score(d["z0"], d["v"], *_past(name, d), scenes=_hetero(B, 2))
+        assert not torch.equal(big["cost"], still["cost"]) or not torch.equal(big["min_clear"], still["min_clear"])
+        assert not torch.equal(big["min_clear"], still["min_clear"]), "the velocities matter"
+        grad = p.tube_kind != "nn_step"
+        if grad:
+            gbig = pl.HipGradPlanner(tr, p, pl.GradCfg(**RHO), device=DEV, scenes=scenes).gradient(d["z0"], d["v"], *_past(name, d))
+        for b in ROWS:
+            row, own = slice(b, b + 1), scenes.take([b])
+            one = pl.HipPlanScorer(tr, p, device=DEV).score(d["z0"][row], d["v"][row], *_past(name, d, row), scenes=own)
+            for k in one:
+                _same(big[k][row], one[k], f"score {k}, plan {b}")
+            if grad:
+                gone = pl.HipGradPlanner(tr, p, pl.GradCfg(**RHO), device=DEV, scenes=own).gradient(d["z0"][row], d["v"][row], *_past(name, d, row))
+                for k in gone:
+                    _same(gbig[k][row], gone[k], f"grad {k}, plan {b}")
+        P, cfg = 3, pl.MppiCfg(K=32, iters=1, sigma=0.1, seed=5, lambda_=5.0, **RHO)
+        sub = scenes.take(np.array([ROWS[0], ROWS[1], ROWS[4]]))
+        m = _plans(P, N, Hr, seed=78)
+        pln = pl.HipMppiPlanner(tr, p, cfg, device=DEV, scenes=sub)
+        st = pln.state(m["z0"], m["v"], *_past(name, m), want=("cost", "min_clear", "pen"))
+        hist = torch.empty(P, 2, device=DEV)
+        pln.step(st, 0, what=3, reset=True, hist_row=hist)
+        for i in range(P):
+            row = slice(i, i + 1)
+            one = pl.HipMppiPlanner(tr, p, dataclasses.replace(cfg, instance_offset=i), device=DEV, scenes=sub.take([i]))
+            s1 = one.state(m["z0"][row], m["v"][row], *_past(name, m, row), want=("cost", "min_clear", "pen"))
+            h1 = torch.empty(1, 2, device=DEV)
+            one.step(s1, 0, what=3, reset=True, hist_row=h1)
+            for k in ("J", "cost", "min_clear", "pen", "vbar", "best_J", "best_v", "n_bad"):
+                _same(st[k][row], s1[k], f"mppi {k}, instance {i}")
+            _same(hist[row], h1, f"mppi hist, instance {i}")
+    finally:
+        if tr:
+            tr.close()
+
+
+# ---------------------------------------------------------------- 3. against the float64 restatement, plan by plan
+def _scene_dict(p, scenes, b):
+    """plan_moving_ref's problem of scene b."""
+    n = int(scenes.n_obs[b])
+    return {**_ref_problem(p), "goal": scenes.goal[b].tolist(), "obs_c": scenes.obs_c[b, :n].tolist(), "obs_r": scenes.obs_r[b, :n].tolist(),
+            "obs_v": scenes.obs_v[b, :n].tolist()}
+
+
+def _per_plan_ref(p, scenes, d, fw, D):
+    out = []
+    for b in range(scenes.S):
+        row = slice(b, b + 1)
+        out.append(mr.score(_scene_dict(p, scenes, b), d["z0"][row].numpy(), d["v"][row].numpy(), fw(b, D), d["w0"][row].numpy(), None, D))
+    cat = lambda k: np.concatenate([o[k] for o in out])
+    return {**{k: cat(k) for k in ("cost", "min_clear", "worst_node", "n_viol")}, "gmargin": np.concatenate([o["margin"][0] for o in out]),
+            "bmargin": np.concatenate([o["margin"][1] for o in out]),
+            "gap": np.array([(lambda s: s[1] - s[0] if len(s) > 1 else np.inf)(np.sort(o["g"][0].min(axis=1))) if o["g"].shape[2] else np.inf for o in out])}
+
+
+@pytest.mark.parametrize("name", ["l1", "nn"])
+def test_cost_clearance_and_counts_against_float64_per_moving_plan(name):
+    from legged_gym_dev_amd.tube import plan as pl
+    N, B, Hr = 16, 65, TUBES[name][1]
+    tr = _model(name, N)
+    try:
+        p, scenes = _problem(name, N), _moving(B, 1, 1001)
+        d = _plans(B, N, Hr, seed=3)
+        got = {k: t.cpu().numpy() for k, t in pl.HipPlanScorer(tr, p, device=DEV).score(d["z0"], d["v"], *_past(name, d), scenes=scenes).items()}
+        if name == "nn":                                                 # the MLP's values from the device: the walk is what is checked
+            fw = lambda b, D: got["fw"][b:b + 1]
+        else:
+            fw = lambda b, D: plan_ref.analytic("l1", d["v"][b:b + 1].numpy(), p.scaling, p.window_size, D)
+        r32, r64 = (_per_plan_ref(p, scenes, d, fw, D) for D in (np.float32, np.float64))
+        keep = (r64["gmargin"] >= 1e-5) & (r64["bmargin"] >= 1e-6)
+        print(f"{name}: {keep.mean():.3f} of the plans lie outside the margins; smallest gap {r64['gap'][keep].min():.2e}")
+        for k in ("cost", "min_clear"):
+            _yardstick(f"{name} {k}", got[k], r32[k], r64[k])
+        assert keep.mean() >= 0.9, f"the restatement leaves out {1 - keep.mean():.4f} of the plans"
+        assert r64["gap"][keep].min() >= 1e-5, "two nodes tie for the smallest clearance: choose other plans"
+        np.testing.assert_array_equal(got["n_viol"][keep], r64["n_viol"][keep])
+        np.testing.assert_array_equal(got["worst_node"][keep], r64["worst_node"][keep])
+        assert (r64["n_viol"][keep][:, 0] > 0).any() and len(np.unique(r64["worst_node"][keep])) > 2
+    finally:
+        if tr:
+            tr.close()
+
+
+# ---------------------------------------------------------------- 4. the gradient on moving scenes
+KINK = 1e-4                                                              # a plan is compared where its smallest float64 margin is at least this
+GRAD_TUBES = {"l2": ("l2", 0, None), "softplus5-Hr3": ("nn", 3, (16, 1, "softplus", 5.0, False))}
+GRAD_SHAPES = [(3, 8), (33, 8), (2, 64)]
+# (tube, B, N) -> seed of the inputs where the default, 100 + B + N, puts more than a tenth of the plans within KINK of a kink: the first
+# of 1, 2, 3, .. at which the float64 restatement alone keeps 90 % (tests/test_hip_plan_grad.py SEEDS shows the practice).  l2 2 x 64: the
+# default and 1 keep 1 of 2, 2 keeps both.  softplus 2 x 64 (the restatement on the device's weights): the default keeps 1 of 2, 1 keeps
+# both.  Seeds 2 .. 8 keep both as well; at seed 4 the float32 restatement of J happens to land within half an ulp of float64 on both
+# plans (e32 = 5.3e-4 at J = 1.1e4) and the device, 2.5 ulp off, measured 4.7 e32 there: with two plans e32 is a maximum over two numbers.
+GRAD_SEEDS = {("l2", 2, 64): 2, ("softplus5-Hr3", 2, 64): 1}
+MOVER_Y, MOVER_R = 0.5, 0.1                                              # instance 0's obstacle starts here, 0.5 above its path along y = 0
+
+
+def _grad_scenes(p, B, N, seed, moving=True):
+    """Instance 0 walks along y = 0 from the origin to x = 0.38.  Its scene is one disc that starts at (0.2, 0.5) -- too far to touch
+    the path while it stands still -- and comes down to meet the robot at x = 0.2.  The others keep the problem's two obstacles, each
+    with a velocity of up to 0.1 m/s per axis."""
+    from legged_gym_dev_amd.tube.plan import Scenes
+    c = np.tile(np.asarray(p.obs_c, np.float32)[None], (B, 1, 1))
+    r = np.tile(np.asarray(p.obs_r, np.float32)[None], (B, 1))
+    u = np.random.default_rng(seed).uniform(-0.1, 0.1, (B, 2, 2)).astype(np.float32)
+    n = np.full(B, 2, np.int32)
+    t_meet = (0.2 / 0.38) * N * p.dt
+    c[0, 0], r[0, 0], u[0, 0], n[0] = (0.2, MOVER_Y), MOVER_R, (0.0, -MOVER_Y / t_meet), 1
+    return Scenes(obs_c=c, obs_r=r, n_obs=n, obs_v=u if moving else None)
+
+
+def _grad_ref_problem(p, scenes, b):
+    n = int(scenes.n_obs[b])
+    return {**_ref_problem(p), "obs_c": scenes.obs_c[b, :n].tolist(), "obs_r": scenes.obs_r[b, :n].tolist(), "obs_v": scenes.obs_v[b, :n].tolist()}
+
+
+def _grad_ref(p, scenes, d, rkw, dtype):
+    """(J, dJ/dv, parts) per plan against its own scene, concatenated."""
+    rho = [RHO["rho_g"], RHO["rho_w"], RHO["rho_z"]]
+    out = []
+    for b in range(scenes.S):
+        row = slice(b, b + 1)
+        kw = {k: (v[row] if isinstance(v, torch.Tensor) else v) for k, v in rkw.items()}
+        out.append(mr.value_and_grad(_grad_ref_problem(p, scenes, b), rho, d["z0"][row], d["vbar"][row], dtype, **kw))
+    return (np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out]),
+            {k: np.concatenate([o[2][k] for o in out]) for k in ("pen", "margin")})
+
+
+@pytest.mark.parametrize("B,N", GRAD_SHAPES, ids=[f"{b}x{n}" for b, n in GRAD_SHAPES])
+@pytest.mark.parametrize("tube", list(GRAD_TUBES))
+def test_gradient_on_moving_scenes_against_float64_autograd(tube, B, N):
+    from legged_gym_dev_amd.tube.plan import GradCfg, HipGradPlanner
+    kind, Hr, m = GRAD_TUBES[tube]
+    tr = _horizon(Hr, N, *m) if m else None
+    try:
+        p = _analytic(N, kind, H_rev=Hr)
+        seed = GRAD_SEEDS.get((tube, B, N), 100 + B + N)
+        d = _instances(B, N, Hr, seed=seed, dt=0.105)
+        scenes = _grad_scenes(p, B, N, seed)
+        past = (d["e"], d["v_prev"]) if tr else (None, None)
+        got = HipGradPlanner(tr, p, GradCfg(**RHO), device=DEV, scenes=scenes).gradient(d["z0"], d["vbar"], *past, d["w0"])
+        still = HipGradPlanner(tr, p, GradCfg(**RHO), device=DEV, scenes=_grad_scenes(p, B, N, seed, moving=False)).gradient(
+            d["z0"], d["vbar"], *past, d["w0"])
+        assert float(got["pen"][0, 0]) > 0 and float(still["pen"][0, 0]) == 0, "instance 0's obstacle binds because it moves"
+        rkw = dict(w0=d["w0"])
+        if tr:
+            rkw.update(model={"sd": tr.state_dict(), "act": m[2], "beta": m[3]}, e=d["e"], v_prev=d["v_prev"])
+        J64, g64, parts = _grad_ref(p, scenes, d, rkw, torch.float64)
+        J32, g32, _ = _grad_ref(p, scenes, d, rkw, torch.float32)
+        ok = parts["margin"] >= KINK
+        print(f"{tube} {B}x{N}: {int(ok.sum())} of {len(ok)} plans compared (smallest margin {parts['margin'].min():.2e}); pen of instance 0 {parts['pen'][0]}")
+        assert ok.sum() >= 0.9 * len(ok), "at least 90 % of the plans lie away from every kink"
+        assert ok[0] and parts["pen"][0, 0] > 0, "instance 0, whose obstacle binds because it moves, is compared"
+        _yardstick(f"{tube} {B}x{N} J", got["J"].cpu().numpy()[ok], J32[ok], J64[ok])
+        _yardstick(f"{tube} {B}x{N} dJ/dv", got["grad"].cpu().numpy()[ok], g32[ok], g64[ok])
+        assert np.abs(g64[ok]).max() > 1.0 and bool(torch.isfinite(got["grad"]).all())
+    finally:
+        if tr:
+            tr.close()
+
+
+# ---------------------------------------------------------------- 5. the fleet's scenes against the rule
+def fleet_case(P, seed=0):
+    """Positions on a 0.25 grid of few cells -- coincident robots, ties in d2 and d2 == sense^2 = 0.5625 exactly --, one robot at NaN,
+    static obstacles of 0, 5 and 8 per robot that move."""
+    rng = np.random.default_rng(seed + P)
+    G = int(np.ceil(np.sqrt(P))) // 2 + 3
+    pos = (rng.integers(0, G, (P, 2)) * 0.25).astype(np.float32)
+    if P > 1:
+        pos[P // 2] = np.nan
+    vel = rng.uniform(-0.5, 0.5, (P, 2)).astype(np.float32)
+    s_obs = rng.uniform(0.05, 1.0, (P, 8, 3)).astype(np.float32)
+    s_vel = rng.uniform(-0.2, 0.2, (P, 8, 2)).astype(np.float32)
+    n_s = np.asarray([0, 5, 8], np.int32)[rng.integers(0, 3, P)]
+    n_s[:min(P, 3)] = [0, 5, 8][:min(P, 3)]
+    return pos, vel, s_obs, s_vel, n_s
+
+
+@pytest.mark.parametrize("K", [0, 3, 8])
+@pytest.mark.parametrize("P", [1, 2, 9, 65, 130])
+def test_fleet_scenes_against_the_rule(P, K):
+    from legged_gym_dev_amd.tube import plan as pl
+    pos, vel, s_obs, s_vel, n_s = fleet_case(P)
+    cfg, t = pl.FleetCfg(separation=0.2, sense_radius=0.75, max_neighbours=K), 0.3
+    dev = lambda a: torch.as_tensor(a).to(DEV)
+    for static in (True, False):
+        want = mr.fleet_rule(0.2, 0.75, K, pos, vel, *((s_obs, s_vel, n_s) if static else (None, None, None)), t=t)
+        got = pl.fleet_scenes(cfg, dev(pos), dev(vel), t, static=(dev(s_obs), dev(s_vel), dev(n_s)) if static else None)
+        for name, g, w in zip(("obs", "obs_vel", "n_obs"), got, want):
+            np.testing.assert_array_equal(g.cpu().numpy(), w, err_msg=f"{name}, static {static}")
+    if P >= 65 and K == 8:                                               # the case holds what it is made for
+        d2 = ((pos[:, None] - pos[None]) ** 2).sum(-1)
+        assert (d2 == np.float32(0.5625)).any() and (d2[~np.eye(P, dtype=bool)] == 0).any()
+        assert (want[2] == 8).any() and (want[2] < 8).any() and want[2][P // 2] == 0
+        assert not (want[0][:, :, 0] != want[0][:, :, 0]).any(), "the robot at NaN is nobody's neighbour"
+
+
+# ---------------------------------------------------------------- 6. a fleet in closed loop
+# Chosen by a sweep on the MI355X over the tube's scaling, the input bound, K, iters, the sense radius, the neighbour count and H (384 +
+# 192 settings): the tube is what keeps the margin -- the planner asks for separation + w between nodes 0.1 s apart, the audit for
+# separation on the realised path -- and with scaling 0.02 or 0.1 no setting kept all eight robots apart; with 0.25 and inputs of up to
+# 0.4 m/s they all cross and arrive within 120 steps.
+FLEET = dict(separation=0.2, sense_radius=1.3, max_neighbours=7)
+SWAP = dict(H=120, N=12, v_max=0.4, scaling=0.25, K=512, iters=8, sigma=0.3, lambda_=1.0, R=1.0)
+
+
+def _circle(P=8, radius=0.6):
+    a = 2 * np.pi * np.arange(P) / P
+    start = np.stack([radius * np.cos(a), radius * np.sin(a)], axis=1).astype(np.float32)
+    return start, -start
+
+
+def _swap_run(fleet, **kw):
+    from legged_gym_dev_amd.tube import plan as pl
+    from legged_gym_dev_amd.tube.rom_sim import HipRomSim, RomSimCfg
+    s = {**SWAP, **kw}
+    start, goal = _circle()
+    p = pl.PlanProblem(N=s["N"], dt=0.1, start=[0.6, 0.0], goal=[-0.6, 0.0], obs_c=[], obs_r=[], tube_kind="l1", scaling=s["scaling"],
+                       Q=[10.0, 0, 0, 10.0], R=[s["R"], 0, 0, s["R"]], rom_z_min=[-2.0, -2.0], rom_z_max=[2.0, 2.0],
+                       rom_v_min=[-s["v_max"]] * 2, rom_v_max=[s["v_max"]] * 2)
+    cfg = pl.FleetCfg(**{**FLEET, **{k: v for k, v in kw.items() if k in FLEET}})
+    scenes = pl.FleetScenes(8, cfg, goal=goal) if fleet else pl.Scenes(goal=goal)
+    planner = pl.HipMppiPlanner(None, p, pl.MppiCfg(K=s["K"], iters=s["iters"], sigma=s["sigma"], lambda_=s["lambda_"], seed=1), device=DEV,
+                                scenes=scenes)
+    sim = HipRomSim(RomSimCfg(), device=DEV)
+    try:
+        res = pl.closed_loop(planner, sim, s["H"], torch.as_tensor(start), keep_plans=True)
+        torch.cuda.synchronize()
+    finally:
+        sim.close()
+    return p, cfg, scenes, res
+
+
+def test_eight_robots_swap_places_on_a_circle():
+    from legged_gym_dev_amd.tube import plan as pl
+    p, cfg, _, blind = _swap_run(False)
+    _, _, scenes, seen = _swap_run(True)
+    _, _, _, again = _swap_run(True)
+    for k in seen:
+        _same(seen[k], again[k], f"rerun {k}")
+    a, b = (pl.audit_closed_loop(r, p, goal_tol=0.2, scenes=s, fleet=cfg) for r, s in ((blind, pl.Scenes(goal=_circle()[1])), (seen, scenes)))
+    print(f"without the fleet's scenes: min_separation {a['min_separation']:.4f}, collision_free {a['collision_free']:.3f}, reached {a['reached_goal']:.3f}; "
+          f"with: min_separation {b['min_separation']:.4f}, collision_free {b['collision_free']:.3f}, reached {b['reached_goal']:.3f}")
+    assert a["collision_free"] < 1, "robots that do not see each other collide at the centre"
+    assert b["min_separation"] > a["min_separation"] and b["collision_free"] > a["collision_free"]
+    # measured on the MI355X: 0.0169 and 0 of 8 without, 0.2279 and 8 of 8 with, every robot within 0.2 of its goal in both runs
+    assert b["collision_free"] == 1.0 and b["min_separation"] >= FLEET["separation"] and a["reached_goal"] == b["reached_goal"] == 1.0
+    assert len(b["by_robot"]["collision_free"]) == 8 and json.loads(json.dumps(b, allow_nan=False)) == b
+    # every scene the loop built is lg_plan_fleet_scenes on the recorded positions and on the input each plan in force applied next
+    H = seen["pz_x"].shape[1] - 1
+    assert tuple(seen["fleet_obs"].shape) == (H, 8, 8, 3) and not seen["fleet_v"][0].any()
+    for k in range(H):
+        if k:
+            _same(seen["fleet_v"][k], seen["plans_v"][k - 1][:, 1], f"the input of step {k}")
+        obs, vel, n = pl.fleet_scenes(cfg, seen["pz_x"][:, k].contiguous(), seen["fleet_v"][k], k * p.dt)
+        _same(obs, seen["fleet_obs"][k], f"obs of step {k}"), _same(vel, seen["fleet_vel"][k], f"vel of step {k}"), _same(n, seen["fleet_n"][k], f"n of step {k}")
+    assert int(seen["fleet_n"].max()) > 0 and "fleet_obs" not in blind
+
+
+# ---------------------------------------------------------------- 7. the scripts
+def test_scripts_with_moving_scenes_reproduce_the_library(tmp_path):
+    import audit_plans
+    import plan_tube
+    from legged_gym_dev_amd.tube import plan as pl
+    from legged_gym_dev_amd.tube.rom_sim import HipRomSim
+    out, H = str(tmp_path / "plan"), 5
+    argv = ["--tube", "l1", "--scaling", "0.1", "--problem", "gap", "--N", "20", "--K", "64", "--iters", "4", "--sigma", "0.05", "--starts", "8",
+            "--start_noise", "0.01", "--seed", "4", "--device", DEV]
+    sflags = ["--scenes", "random", "--scene_seed", "3", "--scene_obs", "1,3", "--scene_speed", "0.02,0.08", "--closed_loop", str(H)]
+    got = plan_tube.main(argv + sflags + ["--out", out])
+    assert json.load(open(os.path.join(out, "plan.json"))) == json.loads(json.dumps(got, allow_nan=False)) == got
+    assert got["scenes"]["random"]["speed"] == [0.02, 0.08] and len(got["audit"]["by_robot"]["actually_safe"]) == 8
+    a = plan_tube.parse_args(argv + sflags)
+    p = plan_tube.build_problem(a, None)
+    scenes = plan_tube.build_scenes(a, p)[0]
+    speed = np.linalg.norm(scenes.obs_v, axis=2)[scenes._live()]
+    assert speed.min() >= 0.02 - 1e-6 and speed.max() <= 0.08 + 1e-6
+    saved = pl.Scenes.load(os.path.join(out, "scenes.npz"))              # the starts' scenes where they were at each step's time
+    assert saved.S == 8 * H
+    for k in range(H):
+        at = scenes.at(k * p.dt)
+        for key in ("goal", "obs_c", "obs_r", "n_obs", "obs_v"):
+            np.testing.assert_array_equal(getattr(saved, key)[8 * k:8 * (k + 1)], getattr(at, key), err_msg=f"{key}, step {k}")
+    sim = HipRomSim(audit_plans.sim_config(a, p), device=DEV)
+    try:
+        planner = plan_tube.make_planner(a, None, p, None, scenes)
+        res = pl.closed_loop(planner, sim, H, plan_tube.starts(a, p), keep_plans=True)
+        torch.cuda.synchronize()
+        assert pl.audit_closed_loop(res, p, goal_tol=a.goal_tol, scenes=scenes) == got["audit"]
+        _same(scenes.to(DEV)[1][1], torch.as_tensor(scenes.packed()), "the loop leaves the device scenes at time 0")
+        plans = np.load(os.path.join(out, "plans.npz"))
+        np.testing.assert_array_equal(plans["v"], res["plans_v"].reshape(-1, p.N, 2).cpu().numpy())
+        # the plan in force at step k was scored against the scenes at k dt: audit_plans.py on the two files finds the loop's own figures
+        aud = audit_plans.main(["--tube", "l1", "--scaling", "0.1", "--problem", "gap", "--N", "20", "--plans", os.path.join(out, "plans.npz"),
+                                "--scenes", os.path.join(out, "scenes.npz"), "--device", DEV, "--out", str(tmp_path / "audit")])
+        sc = planner.scorer.score(plans["z0"], plans["v"], want=("z", "w"), scenes=saved)
+        _same(sc["cost"].reshape(H, 8).T, res["cost"], "the saved scenes reproduce the loop's scores")
+        t = pl.track(sim, sc["z"], torch.as_tensor(plans["v"]))
+        for k, v in pl.audit(sc, t, p, scenes=saved).items():
+            assert aud[k] == v, k
+    finally:
+        sim.close()
