@@ -1140,6 +1140,46 @@ int lg_priv_obs_buffer(lg_priv_obs *po, float **out, int32_t *width);
 int lg_priv_obs_compute(lg_priv_obs *po, lg_ctx *env);
 int lg_priv_obs_destroy(lg_priv_obs *po);
 
+/* ------------------------------------------------------------------ actor observation history: a
+ * stacked row for a feed-forward actor, W = num_obs + (length - 1) S wide, S = the number of selected obs columns.  Env i after
+ * step t holds, newest first,
+ *   [ obs_t (all num_obs columns) | sel(obs_t-1) | sel(obs_t-2) | ... | sel(obs_t-length+1) ]
+ * where a frame is lg_buffers.obs as the actor saw it (after noise and the clip) and sel() keeps the columns of the ranges in
+ * order.  An env is REINITIALISED by a compute when lg_buffers.reset (the step's dones) is set for it or when it was marked
+ * (lg_obs_hist_mark) since the previous compute: every past frame becomes sel(obs_t) (REPEAT) or zeros (ZERO), so no frame of
+ * the previous episode survives a reset.  Pure copying: the row can be restated bit for bit.
+ * One launch on the env's stream AFTER the step.  It reads only lg_buffers.obs and lg_buffers.reset, writes only the handle's
+ * row, and leaves a deferred step epilogue (lg_ppo_attach_env) deferred.  Lifetime as lg_priv_obs: the handle keeps no pointer into
+ * the env; every call takes the env, borrows its buffers and stream for that call and refuses an env whose num_envs or num_obs
+ * differ from those of the env the handle was created for.  Env and handle may be destroyed in either order. */
+#define LG_OBS_HIST_MAX_RANGES 8
+#define LG_OBS_HIST_MAX_LENGTH 64
+#define LG_OBS_HIST_MAX_WIDTH 1024
+enum { LG_OBS_HIST_REPEAT = 0, LG_OBS_HIST_ZERO = 1 };
+typedef struct lg_obs_hist_cfg {
+    int32_t length /*frames including the current one, 2..LG_OBS_HIST_MAX_LENGTH*/,
+            num_ranges /*0: every obs column is kept; else 1..LG_OBS_HIST_MAX_RANGES*/, reset_mode /*LG_OBS_HIST_**/, _pad;
+    int32_t lo[LG_OBS_HIST_MAX_RANGES], hi[LG_OBS_HIST_MAX_RANGES];      /* half-open [lo, hi) of obs columns, ascending, non-overlapping */
+} lg_obs_hist_cfg;
+typedef struct lg_obs_hist lg_obs_hist;
+/* Host code, needs no GPU.  0 and *width_out (may be NULL) = W, or -1 with the refused field named in lg_last_error
+ * ("lg_obs_hist: ...": length, num_ranges, reset_mode, lo[r], hi[r] or width). */
+int lg_obs_hist_check(const lg_obs_hist_cfg *cfg, int32_t num_obs, int32_t *width_out);
+/* Allocates the row (zeros) and marks every env, so that the first compute initialises every row.  Waits for the device. */
+int lg_obs_hist_create(lg_ctx *env, const lg_obs_hist_cfg *cfg, lg_obs_hist **out);
+/* *ptr: DEVICE f32 (num_envs, *W), zeros until the first lg_obs_hist_compute */
+int lg_obs_hist_buffer(lg_obs_hist *h, void **ptr, int32_t *W);
+/* Marks n envs (ids_device: DEVICE int32, kept alive by the caller until the stream has passed; NULL: all envs) for
+ * reinitialisation by the next compute; for a reset made outside the step (lg_reset_ids).  One small launch on the env's stream;
+ * the row itself is not touched. */
+int lg_obs_hist_mark(lg_obs_hist *h, lg_ctx *env, const int32_t *ids_device, int32_t n);
+/* Advances every env's row by one frame (or reinitialises it) in one launch on the env's stream; the marks lapse with it.
+ * A mark holds until the next successful compute: one that is refused (-1: null argument, an env of other dimensions) or whose
+ * launch fails (-3) touches neither row nor marks, and the marks stay meant for the next one. */
+int lg_obs_hist_compute(lg_obs_hist *h, lg_ctx *env);
+/* Waits for the device, frees the row and the marks.  NULL is accepted. */
+int lg_obs_hist_destroy(lg_obs_hist *h);
+
 #ifdef __cplusplus
 }
 #endif

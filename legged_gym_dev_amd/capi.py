@@ -475,6 +475,29 @@ def declare_priv_obs_api(lib):
     return lib
 
 
+OBS_HIST_MAX_RANGES, OBS_HIST_MAX_LENGTH, OBS_HIST_MAX_WIDTH = 8, 64, 1024     # LG_OBS_HIST_MAX_*
+OBS_HIST_RESET = ["repeat", "zero"]                              # LG_OBS_HIST_REPEAT / _ZERO: a mode's value is its index
+
+
+class lg_obs_hist_cfg(C.Structure):
+    """The actor's observation history (include/legged_hip.h lg_obs_hist_cfg)."""
+    _fields_ = [("length", i32), ("num_ranges", i32), ("reset_mode", i32), ("_pad", i32),
+                ("lo", i32 * OBS_HIST_MAX_RANGES), ("hi", i32 * OBS_HIST_MAX_RANGES)]
+
+
+def declare_obs_hist_api(lib):
+    """The lg_obs_hist_* entries; raises if the library was built without them (there is no fallback)."""
+    vp, pc = C.c_void_p, C.POINTER(lg_obs_hist_cfg)
+    lib.lg_last_error.restype = C.c_char_p
+    lib.lg_obs_hist_check.argtypes = [pc, i32, PI32]
+    lib.lg_obs_hist_create.argtypes = [vp, pc, C.POINTER(vp)]
+    lib.lg_obs_hist_buffer.argtypes = [vp, C.POINTER(vp), PI32]
+    lib.lg_obs_hist_mark.argtypes = [vp, vp, vp, i32]
+    lib.lg_obs_hist_compute.argtypes = [vp, vp]
+    lib.lg_obs_hist_destroy.argtypes = [vp]
+    return lib
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p

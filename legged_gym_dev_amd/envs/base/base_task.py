@@ -20,6 +20,7 @@ class BaseTask:
         self.num_obs = cfg.env.num_observations
         self.num_privileged_obs = cfg.env.num_privileged_obs
         self.num_actions = cfg.env.num_actions
+        self.num_actor_obs = self.num_obs         # the width of get_actor_observations(): wider under cfg.obs_history (obs_history.py)
         # cfg.privileged_obs.terms (envs/base/privileged_obs.py) is what fills the buffer; a bare width has nothing to fill it with
         if self.num_privileged_obs is not None and not (getattr(getattr(cfg, "privileged_obs", None), "terms", None) or []):
             raise NotImplementedError("privileged observations are not produced by the reference LeggedRobot either")
@@ -33,6 +34,10 @@ class BaseTask:
 
     def get_privileged_observations(self):
         return self.privileged_obs_buf
+
+    def get_actor_observations(self):
+        """What the policy is fed: obs_buf, or the stacked history row when cfg.obs_history is on."""
+        return getattr(self, "actor_obs_buf", self.obs_buf)
 
     def reset_idx(self, env_ids):
         raise NotImplementedError

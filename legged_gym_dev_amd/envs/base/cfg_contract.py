@@ -99,6 +99,10 @@ CONTRACT = [
     ("init_state.*", CONSUMED, "setup"),
     ("noise.*", CONSUMED, "setup: noise_scale_vec"),
     ("normalization.*", CONSUMED, "setup"),
+    # ---- actor observation history (this build's own section; the reference's actor sees one frame)
+    ("obs_history.length", CONSUMED, "env: obs_history.ObsHistorySpec, frames in the actor's row including the current one; 1 is off"),
+    ("obs_history.columns", CONSUMED, "env: obs_history.ObsHistorySpec, None or the [lo, hi) ranges of obs columns past frames keep"),
+    ("obs_history.reset", CONSUMED, "env: obs_history.ObsHistorySpec, what a reset leaves in the past frames: repeat | zero"),
     # ---- privileged observations (this build's own section; the reference has the buffer, legged_robot_config.py:38, and no terms)
     ("privileged_obs.terms", CONSUMED, "env: privileged_obs.PrivilegedObsSpec, the terms of the critic's row in order (lg_priv_cfg)"),
     ("privileged_obs.scales.*", CONSUMED, "env: privileged_obs.PrivilegedObsSpec, lg_priv_term.scale of the term of that name"),

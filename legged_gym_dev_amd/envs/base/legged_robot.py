@@ -17,6 +17,7 @@ from legged_gym_dev_amd.model.robot_model import compile_model, resolve_model
 from legged_gym_dev_amd.utils.terrain import Terrain
 from .base_task import BaseTask
 from .env_setup import CurriculumClock, EnvSetup, sim_dt_float
+from .obs_history import HipObsHistory, ObsHistorySpec
 from .privileged_obs import HipPrivilegedObs, PrivilegedObsSpec
 
 
@@ -125,8 +126,13 @@ class LeggedRobot(BaseTask):
         priv_spec = PrivilegedObsSpec.from_cfg(cfg, s)
         if priv_spec.terms:
             self.num_privileged_obs = priv_spec.resolve_num_privileged_obs(cfg.env.num_privileged_obs)
+        # the actor's observation history (obs_history.py): likewise refused before any device work
+        self.obs_history_spec = ObsHistorySpec.from_cfg(cfg, s)
+        if self.obs_history_spec.enabled:
+            self.num_actor_obs = self.obs_history_spec.width
         self.core = HipEnvCore(s, hs, device=self.device)
         self._priv = HipPrivilegedObs(self.core, priv_spec) if priv_spec.terms else None
+        self._hist = HipObsHistory(self.core, self.obs_history_spec) if self.obs_history_spec.enabled else None
         t = self.core.t
         lo, hi = rank * self.num_envs, (rank + 1) * self.num_envs
         t["env_origins"].copy_(consts["env_origins"][lo:hi])
@@ -205,6 +211,7 @@ class LeggedRobot(BaseTask):
         self.contact_forces = t["contact_forces"]
         self.obs_buf, self.rew_buf = t["obs"], t["rew"]
         self.privileged_obs_buf = self._priv.buf if self._priv is not None else None
+        self.actor_obs_buf = self._hist.buf if self._hist is not None else self.obs_buf
         self.reset_buf, self.time_out_buf = t["reset"].view(torch.bool), t["time_out"].view(torch.bool)
         self._episode_length_buf = t["episode_length"]
         self.torques, self.actions = t["torques"], t["actions"]
@@ -249,6 +256,8 @@ class LeggedRobot(BaseTask):
         self.core.step(a)
         if self._priv is not None:                # one launch behind the step's, in stream order (privileged_obs.py)
             self._priv.compute()
+        if self._hist is not None:                # likewise one launch: the actor's row moves on by one frame (obs_history.py)
+            self._hist.compute()
         self.common_step_counter += 1
         self.extras["episode"] = self._extras_episode
         if self.cfg.env.send_timeouts:
@@ -262,6 +271,8 @@ class LeggedRobot(BaseTask):
         if n == 0:
             return
         self.core.lib.lg_set_init_done(self.core.ctx, int(self.init_done))
+        if self._hist is not None:                # the next step reinitialises these envs' rows; nothing is refreshed here, as obs
+            self._hist.mark(ids)
         if n == self.num_envs and bool((ids == torch.arange(n, device=self.device)).all()):
             self.core.call("reset_all")               # reset_idx(arange(N)) of BaseTask.reset(): no episode logging needed
             return
@@ -276,6 +287,8 @@ class LeggedRobot(BaseTask):
         self.core.call("post_physics_step")
         if self._priv is not None:
             self._priv.compute()
+        if self._hist is not None:
+            self._hist.compute()
         self.common_step_counter += 1
 
     def compute_observations(self):
@@ -284,4 +297,7 @@ class LeggedRobot(BaseTask):
     def close(self):
         if self._priv is not None:
             self._priv.close()
+        if self._hist is not None:
+            self._hist.close()
+            self.actor_obs_buf = None
         self.core.close()

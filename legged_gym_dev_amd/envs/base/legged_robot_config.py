@@ -91,6 +91,10 @@ LeggedRobotCfg = cfg_class("LeggedRobotCfg", BaseConfig, dict(
             body_contact=1.0, torques=1.0, heights=1.0, episode_progress=1.0,
         ),
     ),
+    # this build's own section (envs/base/obs_history.py): a stacked observation history for the actor; length 1 is off
+    obs_history=S(
+        length=1, columns=None, reset="repeat",
+    ),
     viewer=S(
         ref_env=0, pos=[10, 0, 6], lookat=[11.0, 5, 3.0],
     ),

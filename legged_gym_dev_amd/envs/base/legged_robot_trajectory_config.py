@@ -63,6 +63,7 @@ LeggedRobotTrajectoryCfg = cfg_class("LeggedRobotTrajectoryCfg", BaseConfig, dic
                     clip_observations=100.0, clip_actions=100.0),
     noise=_B.noise,
     privileged_obs=_B.privileged_obs,
+    obs_history=_B.obs_history,
     viewer=_B.viewer,
     sim=_B.sim,
 ), doc=None, module=__name__)

@@ -117,12 +117,50 @@ class LSTMPolicy(torch.nn.Module):
         self.cell_state.zero_()
 
 
-def export_policy_as_jit(actor_critic, path, activation=None):
+class HistoryPolicy(torch.nn.Module):
+    """The actor MLP behind its observation history (envs/base/obs_history.py), one (1, num_obs) frame per call: ``history`` is the
+    (1, W) row [obs_t | sel(obs_t-1) | ...], moved on by one frame per call and reinitialised on the first call and on the call
+    after reset_memory() -- every past frame then sel(obs_t) ("repeat") or zeros ("zero").  The surface is LSTMPolicy's."""
+
+    def __init__(self, state_dict, activation, spec):
+        super().__init__()
+        self.actor = build_mlp(state_dict, "actor", activation)
+        self.num_obs, self.num_selected, self.length, self.width = int(spec.num_obs), int(spec.num_selected), int(spec.length), int(spec.width)
+        self.zero = spec.reset == "zero"
+        if self.actor[0].in_features != self.width:
+            raise ValueError(f"the actor takes {self.actor[0].in_features} columns but the history ({spec}) gives {self.width}")
+        self.register_buffer("columns", torch.tensor(spec.columns(), dtype=torch.long))
+        self.register_buffer("history", torch.zeros(1, self.width))
+        self.register_buffer("fresh", torch.ones(1, dtype=torch.bool))
+
+    def forward(self, obs):
+        sel = obs.index_select(1, self.columns)
+        if bool(self.fresh.item()):
+            past = torch.zeros(1, (self.length - 1) * self.num_selected) if self.zero else sel.repeat(1, self.length - 1)
+            self.fresh.zero_()
+        else:
+            older = self.history[:, self.num_obs:self.width - self.num_selected]
+            past = torch.cat([self.history[:, :self.num_obs].index_select(1, self.columns), older], 1)
+        self.history.copy_(torch.cat([obs, past], 1))
+        return self.actor(self.history)
+
+    @torch.jit.export
+    def reset_memory(self):
+        self.fresh.fill_(True)
+
+
+def export_policy_as_jit(actor_critic, path, activation=None, obs_history=None):
     """helpers.py:274-285: ``<path>/policy_1.pt`` = torch.jit.script(actor MLP on CPU); a recurrent policy (memory_a.* in its
-    state dict) goes to ``<path>/policy_lstm_1.pt`` instead (helpers.py:288-313)."""
+    state dict) goes to ``<path>/policy_lstm_1.pt`` instead (helpers.py:288-313).  With ``obs_history`` (an enabled
+    ObsHistorySpec) the actor goes out behind its history as ``<path>/policy_hist_1.pt`` (HistoryPolicy)."""
     os.makedirs(path, exist_ok=True)
     sd = actor_critic.state_dict()
     activation = activation or getattr(actor_critic, "activation", "elu")
+    if obs_history is not None and obs_history.enabled:
+        scripted = torch.jit.script(HistoryPolicy(sd, activation, obs_history).to("cpu"))
+        out = os.path.join(path, "policy_hist_1.pt")
+        scripted.save(out)
+        return out
     if "memory_a.rnn.weight_ih_l0" in sd:
         scripted = torch.jit.script(LSTMPolicy(sd, activation).to("cpu"))
         out = os.path.join(path, "policy_lstm_1.pt")

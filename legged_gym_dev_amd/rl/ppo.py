@@ -19,6 +19,14 @@ def _vp(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def check_width(t, width, what):
+    """The library takes bare pointers and reads ``width`` floats per row: a row of another width (obs_buf handed to a learner
+    built on the history row, say) is refused here, before it can become a read past the end of the buffer."""
+    if t is not None and (t.dim() < 1 or int(t.shape[-1]) != int(width)):
+        raise ValueError(f"{what} has shape {tuple(t.shape)} but the learner was built for {width} columns per row"
+                         " (with cfg.obs_history the policy reads env.get_actor_observations(), not obs_buf)")
+
+
 # rsl_rl v1.0.2 get_activation (rsl_rl/modules/actor_critic.py, third-party -- recalled, not in the reference tree): its "crelu"
 # entry returns nn.ReLU(), so the name listed at legged_robot_config.py:244 is plain ReLU with unchanged layer widths
 _ACTIVATIONS = {"elu": 0, "selu": 1, "relu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5, "crelu": 2}
@@ -184,6 +192,9 @@ class HipPPO:
 
     # ------------------------------------------------------------------ rsl_rl PPO surface
     def act(self, obs, critic_obs=None):
+        check_width(obs, self.O, "act: obs")
+        if self.privileged:
+            check_width(critic_obs, self.OC, "act: critic_obs")
         self._call("act", _vp(obs), _vp(critic_obs if self.privileged else None))
         return self.t["act_actions"]
 
@@ -192,6 +203,7 @@ class HipPPO:
         self._call("process_env_step", _vp(rewards), _vp(dones), _vp(to))
 
     def compute_returns(self, last_critic_obs, all_reduce=None):
+        check_width(last_critic_obs, self.OC, "compute_returns: last_critic_obs")
         self._call("compute_returns", _vp(last_critic_obs))
         if all_reduce is not None and self.world_size > 1:
             all_reduce(self.t["adv_partial"])
@@ -214,6 +226,7 @@ class HipPPO:
         return st[2] / st[5], st[3] / st[5]
 
     def act_inference(self, obs):
+        check_width(obs, self.O, "act_inference: obs")
         out = torch.empty(obs.shape[0], self.A, device=self.device)
         self._call("act_inference", _vp(obs.contiguous()), _vp(out), C.c_int64(obs.shape[0]))
         return out

@@ -100,10 +100,16 @@ class OnPolicyRunner:
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         ncrit = env.num_privileged_obs if env.num_privileged_obs is not None else env.num_obs
-        if env.get_privileged_observations() is not None and ncrit == env.num_obs:
+        # the actor's row: obs_buf, or the stacked history (envs/base/obs_history.py); the critic then keeps the single frame
+        nact = int(getattr(env, "num_actor_obs", env.num_obs))
+        self.obs_history_spec = getattr(env, "obs_history_spec", None) if nact != env.num_obs else None
+        if env.get_privileged_observations() is not None and ncrit == nact:
             raise ValueError(f"the privileged observation row is as wide as the policy's ({ncrit} columns): HipPPO takes a critic "
                              "input of the actor's width to BE the actor's input; add a term to cfg.privileged_obs.terms (or drop one)")
-        self.ppo = HipPPO(env.num_envs, env.num_obs, ncrit, env.num_actions, self.policy_cfg, self.alg_cfg,
+        if self.obs_history_spec is not None and self.cfg.get("policy_class_name", "ActorCritic") == "ActorCriticRecurrent":
+            raise ValueError(f"cfg.obs_history ({self.obs_history_spec}) with ActorCriticRecurrent: a stacked history in front of a "
+                             "memory; use one or the other")
+        self.ppo = HipPPO(env.num_envs, nact, ncrit, env.num_actions, self.policy_cfg, self.alg_cfg,
                           self.num_steps_per_env, device=self.device, seed=train_cfg.get("seed", 1),
                           world_size=self.world_size, rank=self.rank,
                           policy_class_name=self.cfg.get("policy_class_name", "ActorCritic"))
@@ -138,12 +144,16 @@ class OnPolicyRunner:
         3 launches per policy step instead of 5, same results (LG_FUSE_EPILOGUE=0 keeps them as launches of their own)."""
         env, ppo = self.env, self.ppo
         obs, priv = env.get_observations(), env.get_privileged_observations()
+        hist = self.obs_history_spec is not None
         fuse = self.fuse_epilogue
         if fuse:
             ppo.attach_env(env.core)
         try:
             for _ in range(self.num_steps_per_env):
-                actions = ppo.act(obs, priv)                 # priv: the critic's own row (env.num_privileged_obs columns) or None
+                if hist:    # the actor reads the history row (one buffer, advanced by the step); the critic keeps its own row, else obs
+                    actions = ppo.act(env.get_actor_observations(), priv if priv is not None else obs)
+                else:
+                    actions = ppo.act(obs, priv)             # priv: the critic's own row (env.num_privileged_obs columns) or None
                 obs, priv, rewards, dones, infos = env.step(actions)
                 ppo.process_env_step(rewards, env.core.t["reset"], {"time_outs": env.core.t["extras_time_outs"]}
                                      if "time_outs" in infos else {})
@@ -283,12 +293,20 @@ class OnPolicyRunner:
     def save(self, path, infos=None):
         os.makedirs(os.path.dirname(path), exist_ok=True)
         # rsl_rl OnPolicyRunner.save layout; the optimiser entry is torch.optim.Adam's own state_dict
-        torch.save({"model_state_dict": {k: v.cpu() for k, v in self.ppo.state_dict().items()},
-                    "optimizer_state_dict": self.ppo.optimizer_state_dict(),
-                    "iter": self.current_learning_iteration, "infos": infos}, path)
+        d = {"model_state_dict": {k: v.cpu() for k, v in self.ppo.state_dict().items()},
+             "optimizer_state_dict": self.ppo.optimizer_state_dict(),
+             "iter": self.current_learning_iteration, "infos": infos}
+        if self.obs_history_spec is not None:          # what the actor's first layer was trained on; rsl_rl's loader ignores the key
+            d["obs_history"] = self.obs_history_spec.as_dict()
+        torch.save(d, path)
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location="cpu", weights_only=True)
+        from legged_gym_dev_amd.envs.base.obs_history import ObsHistorySpec
+        saved, own = ObsHistorySpec.from_dict(d.get("obs_history")), self.obs_history_spec or ObsHistorySpec()
+        if not saved.same_row(own):
+            raise ValueError(f"{path}: the checkpoint's policy was trained on cfg.obs_history = ({saved}) but the env's is ({own}); "
+                             "pass the checkpoint's --obs_history / --obs_history_columns / --obs_history_reset")
         self.ppo.load_state_dict(d["model_state_dict"])
         if load_optimizer and d.get("optimizer_state_dict"):
             self.ppo.load_optimizer_state_dict(d["optimizer_state_dict"])

@@ -25,6 +25,8 @@ from legged_gym_dev_amd.utils import get_args, task_registry  # noqa: E402
 
 def collect(env, policy, epochs, episode_length_s=None, save_debugging_data=False, out_dir=None, progress=False):
     """The reference's epoch loop (data_collection_trajectory.py:97-183).  Returns the list of epoch dicts."""
+    from legged_gym_dev_amd.envs.base.obs_history import refuse_history
+    refuse_history(env, "collect_trajectory_data.collect")       # the loop hands obs to the policy itself
     rom, tg = env.rom, env.traj_gen
     N = env.num_envs
     T = int((episode_length_s if episode_length_s is not None else env.max_episode_length_s) / rom.dt)
@@ -77,6 +79,8 @@ def main():
     if not hasattr(env_cfg, "trajectory_generator"):
         raise SystemExit(f"{args.task} is not a trajectory-tracking task")
     env, env_cfg = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
+    from legged_gym_dev_amd.envs.base.obs_history import refuse_history
+    refuse_history(env, "collect_trajectory_data.py")             # before a checkpoint is looked for
     train_cfg.runner.resume = not own.untrained
     runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg, log_root=None if own.untrained else "default")
     policy = runner.get_inference_policy(device=env.device)

@@ -85,7 +85,7 @@ def evaluate(args):
         print("No checkpoint found: evaluating a freshly initialised policy")
     policy = ppo_runner.get_inference_policy(device=env.device)
 
-    obs = env.get_observations()
+    obs = env.get_actor_observations()                              # obs_buf, or the history row under --obs_history
     steps, n = args.steps, env.num_envs
     x_n = env.dof_pos.shape[1] + env.dof_vel.shape[1] + env.root_states.shape[1]
     x = torch.zeros((steps + 1, n, x_n), device=env.device)
@@ -99,7 +99,8 @@ def evaluate(args):
     with torch.no_grad():
         for t in range(steps - 1):                                 # evaluate_rl_policy.py:96-124
             actions = policy(obs.detach())
-            obs, _, _, done, _ = env.step(actions.detach())
+            _, _, _, done, _ = env.step(actions.detach())
+            obs = env.get_actor_observations()
             done = done.bool()
             proj = env.rom.proj_z(env.root_states)
             x[t + 1] = env.get_state()

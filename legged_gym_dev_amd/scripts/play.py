@@ -28,13 +28,14 @@ def play(args, num_steps=None, out_mat="play_data.mat"):
     env_cfg.domain_rand.randomize_friction = False
     env_cfg.domain_rand.push_robots = False
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
-    obs = env.get_observations()
+    obs = env.get_actor_observations()           # obs_buf, or the history row under --obs_history
     train_cfg.runner.resume = True
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg)
     policy = ppo_runner.get_inference_policy(device=env.device)
     if EXPORT_POLICY:
         path = os.path.join(LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name, "exported", "policies")
-        print("Exported policy as jit script to:", export_policy_as_jit(ppo_runner.alg.actor_critic, path))
+        print("Exported policy as jit script to:", export_policy_as_jit(ppo_runner.alg.actor_critic, path,
+                                                                        obs_history=getattr(env, "obs_history_spec", None)))
     logger = Logger(env.dt)
     robot_index, joint_index, stop_state_log = 0, 1, 100
     N = int(num_steps if num_steps else env.max_episode_length)
@@ -48,7 +49,8 @@ def play(args, num_steps=None, out_mat="play_data.mat"):
         rec["dof"][i] = env.dof_pos[robot_index].cpu().numpy()
         rec["ddof"][i] = env.dof_vel[robot_index].cpu().numpy()
         actions = policy(obs.detach())
-        obs, _, rews, dones, infos = env.step(actions.detach())
+        _, _, rews, dones, infos = env.step(actions.detach())
+        obs = env.get_actor_observations()
         rec["action"][i] = actions[robot_index].cpu().numpy()
         rec["torque"][i] = env.torques[robot_index].cpu().numpy()
         if i < stop_state_log:

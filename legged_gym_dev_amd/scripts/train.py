@@ -1,7 +1,9 @@
 """python legged_gym_dev_amd/scripts/train.py --task=anymal_c_flat [--num_envs N --max_iterations K --headless ...]
 Same flow as the reference's scripts/train.py:40-44; multi-GPU: launch with torchrun (one rank per GPU).
 Asymmetric critic: --privileged_obs obs,friction,base_mass,feet_contact,feet_air_time gives the critic its own noise-free row
-(envs/base/privileged_obs.py lists the terms); the actor, checkpoints, play and export are unchanged."""
+(envs/base/privileged_obs.py lists the terms); the actor, checkpoints, play and export are unchanged.
+Observation history: --obs_history H [--obs_history_columns lo:hi,... --obs_history_reset repeat|zero] stacks the actor's last H
+observations in front of the MLP (envs/base/obs_history.py); the checkpoint carries the spec and play.py needs the same flags."""
 import os
 import sys
 

@@ -135,6 +135,8 @@ class HipCommandTracker:
     def __init__(self, env, cfg=None):
         import torch
         from ..lib import LeggedHipError, device_tensor, load
+        from ..envs.base.obs_history import refuse_history
+        refuse_history(env, "HipCommandTracker")     # the command goes into obs[:, 9:12] after the step, hence after the history's launch
         self._err, self._device_tensor = LeggedHipError, device_tensor
         self.env = env
         self.cfg = cfg if cfg is not None else CmdTrackCfg.from_env(env)

@@ -126,6 +126,8 @@ def horizon_steps(Nw, Np, S):
 
 def check_track(env, v, z0, H_rev=0, allow_fast=False):
     """track_env's refusals (ValueError); returns (B, Np, Nw, S, steps).  v, z0: tensors."""
+    from ..envs.base.obs_history import refuse_history
+    refuse_history(env, "track_env")
     traj = getattr(env.setup, "traj", None)
     if traj is None or traj["kind"] != PLAN_KIND:
         raise ValueError("track_env needs an env with trajectory_generator.cls = 'PlanTrajectoryGenerator' (plan_env_cfg)")
@@ -243,6 +245,8 @@ def rom_schedule(env, n_rom_steps):
 
 def check_closed_loop(env, problem, H, w0="zero", allow_fast=False):
     """closed_loop_env's refusals (ValueError); returns (B, Nw, schedule of H + 1 ROM steps)."""
+    from ..envs.base.obs_history import refuse_history
+    refuse_history(env, "closed_loop_env")
     traj = getattr(env.setup, "traj", None)
     if traj is None or traj["kind"] != PLAN_KIND:
         raise ValueError("closed_loop_env needs an env with trajectory_generator.cls = 'PlanTrajectoryGenerator' (plan_env_cfg)")

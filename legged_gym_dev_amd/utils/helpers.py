@@ -101,6 +101,17 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
         if getattr(env_cfg, "privileged_obs", None) is None:      # a cfg class without the section: unit scales
             env_cfg.privileged_obs = SimpleNamespace()
         env_cfg.privileged_obs.terms = [t.strip() for t in args.privileged_obs.split(",") if t.strip()]
+    if env_cfg is not None and any(getattr(args, k, None) is not None for k in ("obs_history", "obs_history_columns", "obs_history_reset")):
+        # the actor's stacked observation history (envs/base/obs_history.py)
+        from legged_gym_dev_amd.envs.base.obs_history import parse_columns
+        if getattr(env_cfg, "obs_history", None) is None:         # a cfg class without the section
+            env_cfg.obs_history = SimpleNamespace(length=1, columns=None, reset="repeat")
+        if getattr(args, "obs_history", None) is not None:
+            env_cfg.obs_history.length = args.obs_history
+        if getattr(args, "obs_history_columns", None) is not None:
+            env_cfg.obs_history.columns = parse_columns(args.obs_history_columns)
+        if getattr(args, "obs_history_reset", None) is not None:
+            env_cfg.obs_history.reset = args.obs_history_reset
     if cfg_train is not None:
         if getattr(args, "seed", None) is not None:
             cfg_train.seed = args.seed
@@ -135,6 +146,9 @@ def get_args(argv=None):
     p.add_argument("--privileged_obs", type=str, help="comma-separated terms of the critic's privileged observation row, in order "
                    "(obs,friction,base_mass,material,feet_contact_forces,feet_contact,feet_air_time,body_contact,torques,heights,"
                    "episode_progress)")
+    p.add_argument("--obs_history", type=int, help="frames in the actor's observation row including the current one (1: off)")
+    p.add_argument("--obs_history_columns", type=str, help="lo:hi[,lo:hi...]: the obs columns that past frames keep (default: all)")
+    p.add_argument("--obs_history_reset", type=str, choices=["repeat", "zero"], help="what a reset leaves in the past frames")
     args, _ = p.parse_known_args(argv)
     args.physics_engine = 1          # SIM_PHYSX placeholder: the HIP physics is the only engine
     args.use_gpu_pipeline = args.pipeline.lower() in ("gpu", "cuda")
