@@ -841,9 +841,44 @@ typedef struct lg_plan_problem {                   /* one problem for every plan
  * bit for bit.  lg_plan_score, lg_plan_mppi_step and lg_plan_mppi take the kind (k_plan_score_step, k_plan_sample_score_step);
  * lg_plan_grad* and lg_plan_descend* refuse it: reverse mode through N chained MLP passes is not built. */
 int lg_plan_check(const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level);
-/* Score B plans in one launch (k_plan_score, 32 plans per 256-thread workgroup).  DEVICE pointers: z0 (B, 2), v (B, N, 2); e
- * (B, H_rev) past error norms, v_prev (B, H_rev, 2), w0 (B) the tube at node 0 -- each may be NULL = zeros; offset (N) a calibration
- * offset per step ahead or NULL.  level is read on a level_input handle only (has_level must say so).
+/* Per-plan scenes: a goal and an
+ * obstacle list of its own for every plan of a scoring or gradient launch, or for every instance of an MPPI launch, in place of the
+ * one goal and list of lg_plan_problem.  Everything else of the problem -- N, dt, the tube, the weights, the bounds -- stays shared.
+ * Row r of a tile reads scene base + r from a row of 27 floats in LDS (2 goal, 24 obstacles, the count), staged once per tile; a
+ * tile of candidates reads its instance's one row.  The walk and the reverse walk are the arithmetic of a call without scenes, operation
+ * for operation, so plan b of a call with scenes equals, bit for bit, a call of B = 1 without scenes on a problem that carries
+ * scene b (an MPPI instance p: a P = 1 call with instance_offset + p). */
+typedef struct lg_plan_scenes {                    /* DEVICE pointers; one scene per plan (scoring, gradient) or per instance (MPPI) */
+    int64_t S;                                     /* must equal the call's B (or P) */
+    const float *goal;                             /* (S, 2), or NULL = prob->goal for every scene */
+    const float *obs;                              /* (S, LG_PLAN_MAX_OBS, 3): cx, cy, r; slots past n_obs[s] are not read */
+    const int32_t *n_obs;                          /* (S); obs and n_obs are both given or both NULL (= the problem's obstacles) */
+    const float *vel;                              /* (S, LG_PLAN_MAX_OBS, 2): ux, uy in m/s of every obstacle slot, or NULL = every
+                                                    * obstacle stands still (section 10.18).  obs holds the centres at node 0, "now";
+                                                    * at node k of the plan obstacle i is at c_i + u_i * t_k, t_k = (float)k * prob->dt,
+                                                    * three roundings (k dt, u t_k, c + ..).  Needs obs; slots past n_obs[s] are not read */
+} lg_plan_scenes;
+/* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error: S < 1, S != count, one of obs / n_obs without the other,
+ * all three of goal, obs, n_obs NULL (the struct then says nothing: pass NULL scenes), or vel without obs.  The arrays are not read: n_obs[s] is clamped into
+ * 0..LG_PLAN_MAX_OBS on the device, and a scene without obstacles gives min_clear = +inf and worst_node = -1 as n_obs = 0 does.
+ * Radii, centres and goals are the caller's to validate before upload (tube/plan.py Scenes does). */
+int lg_plan_scenes_check(const lg_plan_scenes *scenes, int64_t count);
+/* What every planner launch reads, said once: the six entries below take it after the problem (and their cfg), then only their own
+ * arguments.  e, v_prev and w0 are per plan or per instance; level is read on a level_input handle only (has_level must say so).
+ * With scenes, prob->goal, obs_c, obs_r and n_obs are still checked by lg_plan_check but not read by the kernel for the parts the
+ * scenes supply; NULL scenes launch the kernels' instantiations without a scene row.  All six tube kinds are taken by the scoring
+ * and MPPI entries; the gradient entries refuse nn_step.  A NULL call is refused ("null argument"). */
+typedef struct lg_plan_call {                      /* DEVICE pointers */
+    const float *z0;                               /* (count, 2) */
+    const float *e, *v_prev, *w0;                  /* (count, H_rev) past error norms, (count, H_rev, 2), (count) the tube at node 0;
+                                                    * each may be NULL = zeros */
+    const float *offset;                           /* (N) a calibration offset per step ahead, or NULL */
+    const lg_plan_scenes *scenes;                  /* NULL: the problem's own goal and obstacles */
+    int64_t count;                                 /* B plans or P instances */
+    int32_t has_level; float level;
+    void *stream;
+} lg_plan_call;
+/* Score B = call->count plans in one launch (k_plan_score, 32 plans per 256-thread workgroup).  DEVICE pointers: v (B, N, 2).
  * Tube: fw (N) = MLP([e, v_prev.flatten(), v.flatten(), (level)]) -- the ScalarHorizonTubeDataset item at start = H_rev of w = e,
  * v = cat(v_prev, v), gathered on chip; it equals lg_tube_predict_windows (lg_tube_predict_windows_levels) on those arrays bit for
  * bit -- or the analytic kind.  The reference flattens v column-major (TT:563), not the order its dataset trained on; the dataset's
@@ -855,9 +890,8 @@ int lg_plan_check(const lg_plan_problem *prob, const lg_tube *tube, int32_t has_
  * rom_z_min/max, nodes with w > w_max; fw (B, N), z (B, N+1, 2), w (B, N+1) optional (NULL = not written).
  * A plan's outputs do not depend on B or on its place in the batch; no atomics.  -1 as lg_plan_check, for B < 1 or a missing array.
  * Every shape of the envelope fits the kernel's dynamic LDS (checked where the kernel is compiled). */
-int lg_plan_score(lg_tube *tube, const lg_plan_problem *prob, const float *z0, const float *v, const float *e, const float *v_prev,
-                  const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *cost, float *min_clear,
-                  int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w, void *stream);
+int lg_plan_score(lg_tube *tube, const lg_plan_problem *prob, const lg_plan_call *call, const float *v, float *cost, float *min_clear,
+                  int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w);
 /* Track B prescribed plans on the simulator's DoubleInt2D model under its DoubleSingleTracking law in one launch (k_plan_track, one
  * lane per plan; the loop of MT:75-88 at S = 1).  Kp, Kd, the velocity / acceleration bounds and the model dt are the handle's; its
  * generator state and buffers are neither read nor written.  DEVICE: z (B, N+1, 2), v (B, N, 2), x0 (B, 4) or NULL = (z[0], 0, 0).
@@ -872,7 +906,7 @@ int lg_plan_track(lg_romsim *sim, const float *z, const float *v, const float *x
 /* ------------------------------------------------------------------ sampling planner on a tube: MPPI for P
  * problem instances at once, in place of the reference's NLP solve -- trajopt/tube_trajopt.py:460 solve_tube ("TT") -- and of the
  * re-solve at every control step of trajopt/tube_planning_closed_loop.py:82-168 ("TPCL").  The instances share one lg_plan_problem
- * (its goal and obstacles can be each instance's own: lg_plan_mppi_step_scenes, section 10.14);
+ * (its goal and obstacles can be each instance's own: lg_plan_call.scenes, section 10.14);
  * each has its own z0 (P, 2), e (P, H_rev), v_prev (P, H_rev, 2), w0 (P) and mean plan vbar (P, N, 2).  One iteration is two
  * launches: k_plan_sample_score (K candidates per instance drawn around vbar and scored by k_plan_score's own code, no candidate
  * stored) and k_plan_mppi_update (softmin-weighted mean, elite, history). */
@@ -894,7 +928,7 @@ int lg_mppi_check(const lg_mppi_cfg *cfg, const lg_plan_problem *prob, const lg_
 int lg_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int32_t it, const float *vbar, int64_t P, float *out,
                             void *stream);
 /* One iteration `it` (cfg->iters is not read): what & 1 launches k_plan_sample_score, what & 2 k_plan_mppi_update.  DEVICE pointers;
- * e, v_prev, w0, offset, level as lg_plan_score takes them, per instance.
+ * P = call->count instances.
  * Score: J (P, K) = ((cost + rho_g pen_g) + rho_w pen_w) + rho_z pen_z, one rounding per operation, where cost and the nodes are
  * lg_plan_score's of the candidate and pen_g = sum_k sum_i max(0, -g[i, k]), pen_w = sum_k max(0, w_k - w_max), pen_z = sum_k sum_d
  * max(0, z_d - z_max_d) + max(0, z_min_d - z_d), nodes 0..N ascending.  Optional (NULL = not written): cost (P, K), min_clear (P, K),
@@ -903,16 +937,14 @@ int lg_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *cfg,
  * of the candidates, drawn again; sums in an order fixed by K alone, no float atomics.  With no finite J vbar[p] stays and n_bad[p]
  * (int32) counts the iteration.  best_J (P), best_v (P, N, 2): the first arg-min candidate wherever Jmin < best_J; reset_best != 0
  * starts them (and n_bad) afresh, so they need no initial value.  hist_row (P, 2) optional: (J of candidate 0, Jmin). */
-int lg_plan_mppi_step(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int32_t it, int32_t what, int32_t reset_best,
-                      const float *z0, const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level,
-                      float level, int64_t P, float *vbar, float *J, float *cost, float *min_clear, float *pen, float *best_J,
-                      float *best_v, float *hist_row, int32_t *n_bad, void *stream);
+int lg_plan_mppi_step(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, const lg_plan_call *call, int32_t it, int32_t what,
+                      int32_t reset_best, float *vbar, float *J, float *cost, float *min_clear, float *pen, float *best_J, float *best_v,
+                      float *hist_row, int32_t *n_bad);
 /* The plan of TT:460 by cfg->iters iterations of lg_plan_mppi_step from the mean plans in vbar (in-out): 2 iters launches on the
  * stream, no host synchronisation.  J_scratch (P, K); best_J (P), best_v (P, N, 2), n_bad (P) int32 are started by the call;
  * hist (iters, P, 2) optional. */
-int lg_plan_mppi(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, const float *z0, const float *e,
-                 const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t P, float *vbar,
-                 float *J_scratch, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream);
+int lg_plan_mppi(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, const lg_plan_call *call, float *vbar,
+                 float *J_scratch, float *best_J, float *best_v, float *hist, int32_t *n_bad);
 
 /* ------------------------------------------------------------------ gradient planner on a tube: the
  * objective of lg_plan_mppi_step, J = ((cost + rho_g pen_g) + rho_w pen_w) + rho_z pen_z, of B plans and its gradient dJ/dv by a
@@ -928,12 +960,11 @@ typedef struct lg_grad_cfg {
 /* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error: whatever lg_plan_check refuses, iters < 1, lr <= 0, a
  * beta outside [0, 1), eps <= 0, a negative rho, B < 1 or past int32. */
 int lg_plan_grad_check(const lg_grad_cfg *cfg, const lg_plan_problem *prob, const lg_tube *tube, int32_t has_level, int64_t B);
-/* One evaluation.  DEVICE pointers; z0 (B, 2), v (B, N, 2) required, e, v_prev, w0, offset, level as lg_plan_score takes them, per
- * plan.  Outputs: J (B), grad (B, N, 2) = dJ/dv; cost (B), min_clear (B), pen (B, 3) optional (NULL = not written).  Of cfg only the
+/* One evaluation of B = call->count plans.  DEVICE pointers; call->z0 and v (B, N, 2) required.
+ * Outputs: J (B), grad (B, N, 2) = dJ/dv; cost (B), min_clear (B), pen (B, 3) optional (NULL = not written).  Of cfg only the
  * rho are read (the rest is still checked).  A plan's outputs do not depend on B or on its place in a tile; no atomics. */
-int lg_plan_grad(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *v, const float *e,
-                 const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *J,
-                 float *grad, float *cost, float *min_clear, float *pen, void *stream);
+int lg_plan_grad(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const lg_plan_call *call, const float *v, float *J,
+                 float *grad, float *cost, float *min_clear, float *pen);
 /* One iteration `it` (cfg->iters is not read) in one launch: what = 1 evaluates the plans in v (B, N, 2); what = 3 also steps them
  * in place (the step is fused into the launch that makes the gradient, so 2 alone is refused).  Evaluation: J (B) required; grad,
  * cost, min_clear, pen optional as above; the elite best_J (B), best_v (B, N, 2) takes the plan evaluated wherever J is finite and
@@ -942,70 +973,14 @@ int lg_plan_grad(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *
  * rom_v_min, rom_v_max), the two bias corrections rounded once from double.  A plan whose J or gradient is not finite keeps v, m
  * and s, and n_bad[b] (int32) counts the step.  reset != 0 starts m, s (B, N, 2), the elite and n_bad afresh, so they need no
  * initial value; a reset without a finite J leaves best_J = inf and best_v = the plan. */
-int lg_plan_descend_step(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, int32_t it, int32_t what, int32_t reset,
-                         const float *z0, const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level,
-                         float level, int64_t B, float *v, float *J, float *grad, float *cost, float *min_clear, float *pen, float *m,
-                         float *s, float *best_J, float *best_v, float *hist_row, int32_t *n_bad, void *stream);
+int lg_plan_descend_step(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const lg_plan_call *call, int32_t it,
+                         int32_t what, int32_t reset, float *v, float *J, float *grad, float *cost, float *min_clear, float *pen, float *m,
+                         float *s, float *best_J, float *best_v, float *hist_row, int32_t *n_bad);
 /* cfg->iters stepping launches from the plans in v (in-out), then one evaluation-only launch, so that the elite also covers the
  * last iterate: iters + 1 launches on the stream, no host synchronisation.  J_scratch (B); m, s (B, N, 2), best_J, best_v and n_bad
  * are started by the call; hist (iters + 1, B, 2) optional. */
-int lg_plan_descend(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *e,
-                    const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B, float *v,
-                    float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad, void *stream);
-
-/* ------------------------------------------------------------------ per-plan scenes: a goal and an
- * obstacle list of its own for every plan of a scoring or gradient launch, or for every instance of an MPPI launch, in place of the
- * one goal and list of lg_plan_problem.  Everything else of the problem -- N, dt, the tube, the weights, the bounds -- stays shared.
- * Row r of a tile reads scene base + r from a row of 27 floats in LDS (2 goal, 24 obstacles, the count), staged once per tile; a
- * tile of candidates reads its instance's one row.  The walk and the reverse walk are the arithmetic of the entries above, operation
- * for operation, so plan b of a call with scenes equals, bit for bit, a call of B = 1 without scenes on a problem that carries
- * scene b (an MPPI instance p: a P = 1 call with instance_offset + p). */
-typedef struct lg_plan_scenes {                    /* DEVICE pointers; one scene per plan (scoring, gradient) or per instance (MPPI) */
-    int64_t S;                                     /* must equal the call's B (or P) */
-    const float *goal;                             /* (S, 2), or NULL = prob->goal for every scene */
-    const float *obs;                              /* (S, LG_PLAN_MAX_OBS, 3): cx, cy, r; slots past n_obs[s] are not read */
-    const int32_t *n_obs;                          /* (S); obs and n_obs are both given or both NULL (= the problem's obstacles) */
-    const float *vel;                              /* (S, LG_PLAN_MAX_OBS, 2): ux, uy in m/s of every obstacle slot, or NULL = every
-                                                    * obstacle stands still (section 10.18).  obs holds the centres at node 0, "now";
-                                                    * at node k of the plan obstacle i is at c_i + u_i * t_k, t_k = (float)k * prob->dt,
-                                                    * three roundings (k dt, u t_k, c + ..).  Needs obs; slots past n_obs[s] are not read */
-} lg_plan_scenes;
-/* Host code, needs no GPU.  0, or -1 with the field named in lg_last_error: S < 1, S != count, one of obs / n_obs without the other,
- * all three of goal, obs, n_obs NULL (the struct then says nothing: pass NULL scenes), or vel without obs.  The arrays are not read: n_obs[s] is clamped into
- * 0..LG_PLAN_MAX_OBS on the device, and a scene without obstacles gives min_clear = +inf and worst_node = -1 as n_obs = 0 does.
- * Radii, centres and goals are the caller's to validate before upload (tube/plan.py Scenes does). */
-int lg_plan_scenes_check(const lg_plan_scenes *scenes, int64_t count);
-/* The entries above with scenes: each takes its parent's arguments and `scenes` before `stream`.  scenes == NULL is the parent's
- * behaviour -- the parents are these entries called with NULL, and launch the kernels' instantiations without a scene row.  With
- * scenes, prob->goal, obs_c, obs_r and n_obs are still checked by lg_plan_check but not read by the kernel for the parts the scenes
- * supply.  All six tube kinds are taken by the scoring and MPPI entries; the gradient entries refuse nn_step as their parents do.
- * lg_plan_track reads no obstacle and needs no scenes. */
-int lg_plan_score_scenes(lg_tube *tube, const lg_plan_problem *prob, const float *z0, const float *v, const float *e,
-                         const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B,
-                         float *cost, float *min_clear, int32_t *worst_node, int32_t *n_viol, float *fw, float *z, float *w,
-                         const lg_plan_scenes *scenes, void *stream);
-int lg_plan_mppi_step_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int32_t it, int32_t what,
-                             int32_t reset_best, const float *z0, const float *e, const float *v_prev, const float *w0,
-                             const float *offset, int32_t has_level, float level, int64_t P, float *vbar, float *J, float *cost,
-                             float *min_clear, float *pen, float *best_J, float *best_v, float *hist_row, int32_t *n_bad,
-                             const lg_plan_scenes *scenes, void *stream);
-int lg_plan_mppi_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, const float *z0, const float *e,
-                        const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t P,
-                        float *vbar, float *J_scratch, float *best_J, float *best_v, float *hist, int32_t *n_bad,
-                        const lg_plan_scenes *scenes, void *stream);
-int lg_plan_grad_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *v,
-                        const float *e, const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level,
-                        int64_t B, float *J, float *grad, float *cost, float *min_clear, float *pen, const lg_plan_scenes *scenes,
-                        void *stream);
-int lg_plan_descend_step_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, int32_t it, int32_t what,
-                                int32_t reset, const float *z0, const float *e, const float *v_prev, const float *w0,
-                                const float *offset, int32_t has_level, float level, int64_t B, float *v, float *J, float *grad,
-                                float *cost, float *min_clear, float *pen, float *m, float *s, float *best_J, float *best_v,
-                                float *hist_row, int32_t *n_bad, const lg_plan_scenes *scenes, void *stream);
-int lg_plan_descend_scenes(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const float *z0, const float *e,
-                           const float *v_prev, const float *w0, const float *offset, int32_t has_level, float level, int64_t B,
-                           float *v, float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad,
-                           const lg_plan_scenes *scenes, void *stream);
+int lg_plan_descend(lg_tube *tube, const lg_plan_problem *prob, const lg_grad_cfg *cfg, const lg_plan_call *call, float *v,
+                    float *J_scratch, float *m, float *s, float *best_J, float *best_v, float *hist, int32_t *n_bad);
 
 /* ------------------------------------------------------------------ a fleet's scenes: the robots of a fleet
  * are each other's moving obstacles.  One launch writes, for every robot p of P, the obs / vel / n_obs arrays of an lg_plan_scenes of

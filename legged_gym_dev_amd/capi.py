@@ -371,37 +371,32 @@ class lg_fleet_cfg(C.Structure):
     _fields_ = [("separation", f32), ("sense_radius", f32), ("max_neighbours", i32)]
 
 
+class lg_plan_call(C.Structure):
+    """What every planner launch reads (include/legged_hip.h lg_plan_call); device pointers."""
+    _fields_ = [("z0", C.c_void_p), ("e", C.c_void_p), ("v_prev", C.c_void_p), ("w0", C.c_void_p), ("offset", C.c_void_p),
+                ("scenes", C.POINTER(lg_plan_scenes)), ("count", i64), ("has_level", i32), ("level", f32), ("stream", C.c_void_p)]
+
+
 def declare_plan_api(lib):
+    """An entry that an A/B library (LG_HIP_LIB) was built before stays undeclared.  lib.plan_api_old: the library still has the
+    *_scenes twins, so it was built before lg_plan_call and its six planning entries take the older positional lists; they stay
+    undeclared too, and HipPlanScorer refuses the library (calling them with today's lists would corrupt memory)."""
     vp = C.c_void_p
-    if not hasattr(lib, "lg_plan_score"):          # an A/B library (LG_HIP_LIB) built before the plan entries
-        return
-    lib.lg_plan_check.argtypes = [C.POINTER(lg_plan_problem), vp, i32]
-    lib.lg_plan_score.argtypes = [vp, C.POINTER(lg_plan_problem), vp, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.lg_plan_track.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp]
-    if not hasattr(lib, "lg_plan_mppi"):           # an A/B library built before the sampling planner
-        return
-    pp, pc = C.POINTER(lg_plan_problem), C.POINTER(lg_mppi_cfg)
-    lib.lg_mppi_check.argtypes = [pc, pp, vp, i32, i64]
-    lib.lg_plan_mppi_candidates.argtypes = [pp, pc, i32, vp, i64, vp, vp]
-    lib.lg_plan_mppi_step.argtypes = [vp, pp, pc, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.lg_plan_mppi.argtypes = [vp, pp, pc, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp, vp]
-    if not hasattr(lib, "lg_plan_grad"):           # an A/B library built before the gradient planner
-        return
-    pg = C.POINTER(lg_grad_cfg)
-    lib.lg_plan_grad_check.argtypes = [pg, pp, vp, i32, i64]
-    lib.lg_plan_grad.argtypes = [vp, pp, pg, vp, vp, vp, vp, vp, vp, i32, f32, i64, vp, vp, vp, vp, vp, vp]
-    lib.lg_plan_descend_step.argtypes = [vp, pp, pg, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32, i64] + [vp] * 13
-    lib.lg_plan_descend.argtypes = [vp, pp, pg, vp, vp, vp, vp, vp, i32, f32, i64] + [vp] * 9
-    if not hasattr(lib, "lg_plan_score_scenes"):   # an A/B library built before the per-plan scenes
-        return
-    ps = C.POINTER(lg_plan_scenes)                 # each *_scenes entry: its parent's arguments with the scenes before the stream
-    lib.lg_plan_scenes_check.argtypes = [ps, i64]
-    for name in ("lg_plan_score", "lg_plan_mppi_step", "lg_plan_mppi", "lg_plan_grad", "lg_plan_descend_step", "lg_plan_descend"):
-        a = list(getattr(lib, name).argtypes)
-        getattr(lib, name + "_scenes").argtypes = a[:-1] + [ps, a[-1]]
-    if not hasattr(lib, "lg_plan_fleet_scenes"):   # an A/B library built before the fleet's scenes
-        return
-    lib.lg_plan_fleet_scenes.argtypes = [C.POINTER(lg_fleet_cfg), vp, vp, i64, vp, vp, vp, f32, vp, vp, vp, vp]
+    pp, pc, pg = C.POINTER(lg_plan_problem), C.POINTER(lg_mppi_cfg), C.POINTER(lg_grad_cfg)
+    ps, pk = C.POINTER(lg_plan_scenes), C.POINTER(lg_plan_call)
+    lib.plan_api_old = hasattr(lib, "lg_plan_score_scenes")
+    sigs = {"lg_plan_check": [pp, vp, i32], "lg_plan_track": [vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp],
+            "lg_mppi_check": [pc, pp, vp, i32, i64], "lg_plan_mppi_candidates": [pp, pc, i32, vp, i64, vp, vp],
+            "lg_plan_grad_check": [pg, pp, vp, i32, i64], "lg_plan_scenes_check": [ps, i64],
+            "lg_plan_fleet_scenes": [C.POINTER(lg_fleet_cfg), vp, vp, i64, vp, vp, vp, f32, vp, vp, vp, vp]}
+    if not lib.plan_api_old:                       # (tube, prob, [cfg,] call, the entry's own arguments)
+        sigs.update({"lg_plan_score": [vp, pp, pk] + [vp] * 8,
+                     "lg_plan_mppi_step": [vp, pp, pc, pk, i32, i32, i32] + [vp] * 9, "lg_plan_mppi": [vp, pp, pc, pk] + [vp] * 6,
+                     "lg_plan_grad": [vp, pp, pg, pk] + [vp] * 6,
+                     "lg_plan_descend_step": [vp, pp, pg, pk, i32, i32, i32] + [vp] * 12, "lg_plan_descend": [vp, pp, pg, pk] + [vp] * 8})
+    for name, argtypes in sigs.items():
+        if hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
 
 
 class lg_traj_rec(C.Structure):

@@ -1,4 +1,4 @@
-// Device-side struct of the tube-model trainer (tube_kernels.hip, plan_kernels.hip, tube_api.hip).
+// Device-side struct of the tube-model trainer (tube_kernels.hip, plan_kernels.hip, tube_api.hip, plan_api.hip).
 #pragma once
 #include "lg_device.h"
 #include "../../include/legged_hip.h"
@@ -39,6 +39,11 @@ struct TubeDev {                        // passed by value to kernels
     float level_lo, level_hi;
     float *levels;                      // level per row of the last step / eval
 };
+
+// columns of a horizon handle's item built from z of width nz and v of width m; a conditioned handle's last column is the level
+inline int64_t window_dim(const TubeDev &D, int32_t nz, int32_t m) {
+    return D.H_rev + (int64_t)nz + (int64_t)(D.H_rev + D.H_fwd) * m + (D.level_input ? 1 : 0);
+}
 
 struct TubeMember {                     // one model of a sweep (lg_tube_sweep); the kernels index a device array of these by blockIdx.y
     TubeDev dev;                        // its own buffers, alpha / delta / activation / seed / level range; the shape is the same in every member

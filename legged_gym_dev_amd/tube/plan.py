@@ -642,6 +642,13 @@ def _scene_safe(pz, problem, scenes):
     return ~((d < r[:, None, :]) & live[:, None, :]).any(dim=2).any(dim=1)
 
 
+def refuse_old_library(lib):
+    """LeggedHipError for a library that capi.declare_plan_api marked as built before lg_plan_call."""
+    if getattr(lib, "plan_api_old", False):
+        from ..lib import LeggedHipError
+        raise LeggedHipError("the library (LG_HIP_LIB) still exports lg_plan_score_scenes: it was built before lg_plan_call, its planning "
+                             "entries take the older argument lists, and calling them from this tree would corrupt memory (rebuild it)")
+
 
 class HipPlanScorer:
     """lg_plan_score on one problem.  model: a HipTubeModel / HipTubeTrainer of a one-shot horizon tube ('nn'), of a flat scalar
@@ -681,21 +688,31 @@ class HipPlanScorer:
         if self.device.type != "cuda" or not torch.cuda.is_available():
             raise LeggedHipError("scoring plans needs a GPU device (no CPU fallback); got " + str(self.device))
         self.lib = load()
+        refuse_old_library(self.lib)
         self.struct = problem.to_struct()
         if self.offset is not None:
             self.offset = self.offset.to(self.device, torch.float32).contiguous()
         self._handle = getattr(self.model, "_tr", self.model).h if self.model is not None else None
 
-    def _scenes(self, scenes, count):
-        """(entry suffix, trailing arguments) of a call with `scenes` (a Scenes or None): None calls the entry without scenes."""
-        if scenes is None:
-            return "", ()
+    def call(self, count, z0, e=None, v_prev=None, w0=None, scenes=None):
+        """The lg_plan_call, by reference, of a launch over `count` plans or instances on the device's current stream, from the
+        state tensors (None = zeros), the scorer's offset and level, and `scenes` (a Scenes of S = count, or None).  The tensors it
+        points at are kept until the next call."""
+        import torch
         scenes_check(scenes, count)
-        return "_scenes", (C.byref(scenes.to(self.device)[0]),)
+        torch.cuda.set_device(self.device)
+        c = capi.lg_plan_call()
+        c.z0, c.e, c.v_prev, c.w0, c.offset = (None if t is None else t.data_ptr() for t in (z0, e, v_prev, w0, self.offset))
+        if scenes is not None:
+            c.scenes = C.pointer(scenes.to(self.device)[0])
+        c.count, c.has_level, c.level = count, int(self.level is not None), float(self.level if self.level is not None else 0.0)
+        c.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._keep = (z0, e, v_prev, w0, scenes)
+        return C.byref(c)
 
     def score(self, z0, v, e=None, v_prev=None, w0=None, want=("fw", "z", "w"), scenes=None):
         """z0 (B, 2), v (B, N, 2); e (B, H_rev), v_prev (B, H_rev, 2), w0 (B) or None = zeros.  scenes: a Scenes of S = B, plan b
-        scored against its own goal and obstacles (lg_plan_score_scenes).  Returns device tensors: cost (B),
+        scored against its own goal and obstacles.  Returns device tensors: cost (B),
         min_clear (B), worst_node (B) int32, n_viol (B, 4) int32 [obstacle nodes, input steps, state nodes, tube nodes] and
         whatever of fw (B, N), z (B, N+1, 2), w (B, N+1) `want` names."""
         import torch
@@ -716,17 +733,13 @@ class HipPlanScorer:
         opt = {"fw": (B, p.N), "z": (B, p.N + 1, 2), "w": (B, p.N + 1)}
         for k in want:
             out[k] = torch.empty(opt[k], device=dev)
-        torch.cuda.set_device(dev)
-        sfx, sargs = self._scenes(scenes, B)
-        rc = getattr(self.lib, "lg_plan_score" + sfx)(
-            self._handle, C.byref(self.struct), _ptr(z0), _ptr(v), _ptr(e), _ptr(v_prev), _ptr(w0), _ptr(self.offset),
-            int(self.level is not None), float(self.level if self.level is not None else 0.0), B,
+        rc = self.lib.lg_plan_score(
+            self._handle, C.byref(self.struct), self.call(B, z0, e, v_prev, w0, scenes), _ptr(v),
             _ptr(out["cost"]), _ptr(out["min_clear"]), _ptr(out["worst_node"]), _ptr(out["n_viol"]),
-            _ptr(out.get("fw")), _ptr(out.get("z")), _ptr(out.get("w")), *sargs,
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            _ptr(out.get("fw")), _ptr(out.get("z")), _ptr(out.get("w")))
         if rc != 0:
-            raise self._err(f"lg_plan_score{sfx} failed ({rc}): {self.lib.lg_last_error().decode()}")
-        self._keep = (z0, v, e, v_prev, w0)
+            raise self._err(f"lg_plan_score failed ({rc}): {self.lib.lg_last_error().decode()}")
+        self._keep += (v,)
         return out
 
 
@@ -864,6 +877,10 @@ class HipMppiPlanner:
     def _fail(self, name, rc):
         raise self._err(f"{name} failed ({rc}): {self.lib.lg_last_error().decode()}")
 
+    def _call(self, st):
+        """The scorer's lg_plan_call for a state() and the planner's scenes."""
+        return self.scorer.call(st["P"], st["z0"], st["e"], st["v_prev"], st["w0"], self.scenes)
+
     def _stream(self):
         import torch
         torch.cuda.set_device(self.device)
@@ -913,15 +930,12 @@ class HipMppiPlanner:
         """lg_plan_mppi_step on a state(): what & 1 the score (writes J and the optional outputs), what & 2 the update (reads J;
         writes vbar, best_J, best_v, n_bad and hist_row (P, 2) where given)."""
         sc = self.scorer
-        sfx, sargs = sc._scenes(self.scenes, st["P"])
-        rc = getattr(self.lib, "lg_plan_mppi_step" + sfx)(
-            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), int(it), int(what), int(bool(reset)),
-            _ptr(st["z0"]), _ptr(st["e"]), _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset),
-            int(sc.level is not None), float(sc.level if sc.level is not None else 0.0), st["P"],
+        rc = self.lib.lg_plan_mppi_step(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), self._call(st), int(it), int(what), int(bool(reset)),
             _ptr(st["vbar"]), _ptr(st["J"]), _ptr(st.get("cost")), _ptr(st.get("min_clear")), _ptr(st.get("pen")),
-            _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]), *sargs, self._stream())
+            _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]))
         if rc != 0:
-            self._fail("lg_plan_mppi_step" + sfx, rc)
+            self._fail("lg_plan_mppi_step", rc)
         return st
 
     def warm_start(self, z0):
@@ -955,14 +969,11 @@ class HipMppiPlanner:
         st = self.state(z0, v_init, e, v_prev, w0)
         hist = torch.empty(iters, st["P"], 2, device=self.device)
         sc = self.scorer
-        sfx, sargs = sc._scenes(self.scenes, st["P"])
-        rc = getattr(self.lib, "lg_plan_mppi" + sfx)(
-            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), _ptr(st["z0"]), _ptr(st["e"]),
-            _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset), int(sc.level is not None),
-            float(sc.level if sc.level is not None else 0.0), st["P"], _ptr(st["vbar"]), _ptr(st["J"]),
-            _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist), _ptr(st["n_bad"]), *sargs, self._stream())
+        rc = self.lib.lg_plan_mppi(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), self._call(st), _ptr(st["vbar"]), _ptr(st["J"]),
+            _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist), _ptr(st["n_bad"]))
         if rc != 0:
-            self._fail("lg_plan_mppi" + sfx, rc)
+            self._fail("lg_plan_mppi", rc)
         want = ("z", "w")
         return {"v": st["vbar"], "best_v": st["best_v"], "best_J": st["best_J"], "hist": hist, "n_bad": st["n_bad"],
                 "score": sc.score(st["z0"], st["vbar"], st["e"], st["v_prev"], st["w0"], want=want, scenes=self.scenes),
@@ -1017,7 +1028,7 @@ class HipGradPlanner:
 
     warm_start = HipMppiPlanner.warm_start
     _fail = HipMppiPlanner._fail
-    _stream = HipMppiPlanner._stream
+    _call = HipMppiPlanner._call
     needs_gradient = True
 
     def __init__(self, model, problem, cfg, calibration=None, level=None, coverage=None, device=None, scenes=None):
@@ -1055,23 +1066,16 @@ class HipGradPlanner:
             st[k] = torch.empty(opt[k], device=dev)
         return st
 
-    def _common(self, st):
-        sc = self.scorer
-        return (_ptr(st["e"]), _ptr(st["v_prev"]), _ptr(st["w0"]), _ptr(sc.offset), int(sc.level is not None),
-                float(sc.level if sc.level is not None else 0.0), st["P"])
-
     def gradient(self, z0, v, e=None, v_prev=None, w0=None, want=("cost", "min_clear", "pen")):
         """lg_plan_grad: J (B) and grad (B, N, 2) = dJ/dv of the plans v from z0 (B, 2), and whatever of cost, min_clear, pen
         (B, 3) `want` names, as device tensors."""
         st = self.state(z0, v, e, v_prev, w0, want=("grad",) + tuple(k for k in want if k != "grad"))
         sc = self.scorer
-        sfx, sargs = sc._scenes(self.scenes, st["P"])
-        rc = getattr(self.lib, "lg_plan_grad" + sfx)(
-            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), _ptr(st["z0"]), _ptr(st["v"]),
-            *self._common(st), _ptr(st["J"]), _ptr(st["grad"]), _ptr(st.get("cost")), _ptr(st.get("min_clear")),
-            _ptr(st.get("pen")), *sargs, self._stream())
+        rc = self.lib.lg_plan_grad(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), self._call(st), _ptr(st["v"]),
+            _ptr(st["J"]), _ptr(st["grad"]), _ptr(st.get("cost")), _ptr(st.get("min_clear")), _ptr(st.get("pen")))
         if rc != 0:
-            self._fail("lg_plan_grad" + sfx, rc)
+            self._fail("lg_plan_grad", rc)
         self._keep = st
         return {k: st[k] for k in ("J", "grad", "cost", "min_clear", "pen") if k in st}
 
@@ -1079,14 +1083,13 @@ class HipGradPlanner:
         """lg_plan_descend_step on a state(): what = 1 evaluates (J, the optional outputs, the elite, hist_row (P, 2)); what = 3
         also steps v, m and s in place."""
         sc = self.scorer
-        sfx, sargs = sc._scenes(self.scenes, st["P"])
-        rc = getattr(self.lib, "lg_plan_descend_step" + sfx)(
-            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), int(it), int(what), int(bool(reset)),
-            _ptr(st["z0"]), *self._common(st), _ptr(st["v"]), _ptr(st["J"]), _ptr(st.get("grad")),
+        rc = self.lib.lg_plan_descend_step(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct()), self._call(st), int(it), int(what), int(bool(reset)),
+            _ptr(st["v"]), _ptr(st["J"]), _ptr(st.get("grad")),
             _ptr(st.get("cost")), _ptr(st.get("min_clear")), _ptr(st.get("pen")), _ptr(st["m"]), _ptr(st["s"]),
-            _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]), *sargs, self._stream())
+            _ptr(st["best_J"]), _ptr(st["best_v"]), _ptr(hist_row), _ptr(st["n_bad"]))
         if rc != 0:
-            self._fail("lg_plan_descend_step" + sfx, rc)
+            self._fail("lg_plan_descend_step", rc)
         return st
 
     def plan(self, z0, v_init=None, e=None, v_prev=None, w0=None, iters=None):
@@ -1106,13 +1109,12 @@ class HipGradPlanner:
         st = self.state(z0, v_init, e, v_prev, w0)
         hist = torch.empty(iters + 1, st["P"], 2, device=self.device)
         sc = self.scorer
-        sfx, sargs = sc._scenes(self.scenes, st["P"])
-        rc = getattr(self.lib, "lg_plan_descend" + sfx)(
-            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), _ptr(st["z0"]), *self._common(st),
+        rc = self.lib.lg_plan_descend(
+            sc._handle, C.byref(sc.struct), C.byref(self.cfg.to_struct(iters)), self._call(st),
             _ptr(st["v"]), _ptr(st["J"]), _ptr(st["m"]), _ptr(st["s"]), _ptr(st["best_J"]), _ptr(st["best_v"]),
-            _ptr(hist), _ptr(st["n_bad"]), *sargs, self._stream())
+            _ptr(hist), _ptr(st["n_bad"]))
         if rc != 0:
-            self._fail("lg_plan_descend" + sfx, rc)
+            self._fail("lg_plan_descend", rc)
         want = ("z", "w")
         return {"v": st["v"], "best_v": st["best_v"], "best_J": st["best_J"], "hist": hist, "n_bad": st["n_bad"],
                 "score": sc.score(st["z0"], st["v"], st["e"], st["v_prev"], st["w0"], want=want, scenes=self.scenes),

@@ -3,7 +3,7 @@
   2. with heterogeneous moving scenes, plan b (MPPI instance p) is a call of one plan (instance) on scenes.take([b]);
   3. cost and min_clear against tests/plan_moving_ref.py per plan in float64 under the chain yardstick (4 e32) and the margins (1e-5 on
      g, 1e-6 on a bound) of tests/test_hip_plan_score.py; counts and worst_node exact outside them;
-  4. dJ/dv and J of lg_plan_grad_scenes against float64 autograd, away from kinks (1e-4), with an obstacle that binds only because it moves;
+  4. dJ/dv and J of lg_plan_grad with scenes against float64 autograd, away from kinks (1e-4), with an obstacle that binds only because it moves;
   5. lg_plan_fleet_scenes against the rule restated in NumPy (plan_moving_ref.fleet_rule), array_equal;
   6. eight robots that swap places on a circle, with and without seeing each other; 7. the scripts."""
 import dataclasses

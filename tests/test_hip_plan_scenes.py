@@ -1,7 +1,7 @@
 """Per-plan scenes on the GPU.  The contracts are equalities on the bits:
   1. uniform scenes (Scenes.repeat) give every output of the entries without scenes;
   2. with heterogeneous scenes, plan b (MPPI instance p) is a call of one plan (instance) of the entry without scenes on scenes.problem(b);
-  3. lg_plan_descend_scenes / lg_plan_mppi_scenes are their step entries composed by hand;
+  3. lg_plan_descend / lg_plan_mppi with scenes are their step entries composed by hand;
   4. independent of the old kernels: cost and min_clear against tests/plan_ref.py per plan in float64 under the chain yardstick
      (4 e32) and the margins (1e-5 on g, 1e-6 on a bound) of tests/test_hip_plan_score.py; counts and worst_node exact outside them;
   5. a fleet of 64 robots, each in its own scene, in closed loop; 6. the scripts."""
@@ -204,8 +204,9 @@ def test_the_library_refuses_a_wrong_S_and_nn_step_gradients_with_scenes():
     out = [torch.empty(5, device=DEV), torch.empty(5, device=DEV), torch.empty(5, dtype=torch.int32, device=DEV), torch.empty(5, 4, dtype=torch.int32, device=DEV)]
     ptr = lambda t: C.c_void_p(t.data_ptr())
     z0, v = d["z0"].to(DEV), d["v"].to(DEV)
-    rc = sc.lib.lg_plan_score_scenes(None, C.byref(sc.struct), ptr(z0), ptr(v), None, None, None, None, 0, 0.0, 5, *[ptr(t) for t in out], None, None,
-                                     None, C.byref(st), None)
+    from legged_gym_dev_amd import capi
+    call = capi.lg_plan_call(z0=z0.data_ptr(), count=5, scenes=C.pointer(st))
+    rc = sc.lib.lg_plan_score(None, C.byref(sc.struct), C.byref(call), ptr(v), *[ptr(t) for t in out], None, None, None)
     assert rc == -1 and "lg_plan_scenes: S = 4 differs" in sc.lib.lg_last_error().decode()
     tr = TUBES["step"][3](5)
     try:

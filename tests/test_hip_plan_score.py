@@ -266,10 +266,12 @@ def test_refusals():
             sc.score(d["z0"], d["v"][:, :4])
         z0, v = d["z0"].to(DEV), d["v"].to(DEV)
         st = _problem(N, Hr).to_struct()
-        assert lib.lg_plan_score(plain.h, C.byref(st), C.c_void_p(z0.data_ptr()), C.c_void_p(v.data_ptr()), None, None, None, None, 0, 0.0, 3,
-                                 None, None, None, None, None, None, None, None) == -1 and "missing array" in err()
-        assert lib.lg_plan_score(plain.h, C.byref(st), C.c_void_p(z0.data_ptr()), C.c_void_p(v.data_ptr()), None, None, None, None, 0, 0.0, 0,
-                                 None, None, None, None, None, None, None, None) == -1 and "B must be" in err()
+        from legged_gym_dev_amd import capi
+        call = lambda B: C.byref(capi.lg_plan_call(z0=z0.data_ptr(), count=B))
+        assert lib.lg_plan_score(plain.h, C.byref(st), call(3), C.c_void_p(v.data_ptr()),
+                                 None, None, None, None, None, None, None) == -1 and "missing array" in err()
+        assert lib.lg_plan_score(plain.h, C.byref(st), call(0), C.c_void_p(v.data_ptr()),
+                                 None, None, None, None, None, None, None) == -1 and "B must be" in err()
         assert LeggedHipError is not None
     finally:
         for t in (plain, cond, flat, wide):

@@ -347,8 +347,9 @@ def test_refusals():
         ptr = lambda t: C.c_void_p(t.data_ptr())
         assert lib.lg_plan_grad_check(C.byref(gcfg.to_struct()), C.byref(p.to_struct()), flat.h, 0, 2) == -1
         assert "nn_step" in err() and "chained MLP passes" in err()
-        assert lib.lg_plan_grad(flat.h, C.byref(p.to_struct()), C.byref(gcfg.to_struct()), ptr(d["z0"]), ptr(d["v"]), None, None, None, None, 0, 0.0,
-                                2, ptr(J), ptr(grad), None, None, None, None) == -1 and "chained MLP passes" in err()
+        call = capi.lg_plan_call(z0=d["z0"].data_ptr(), count=2)
+        assert lib.lg_plan_grad(flat.h, C.byref(p.to_struct()), C.byref(gcfg.to_struct()), C.byref(call), ptr(d["v"]),
+                                ptr(J), ptr(grad), None, None, None) == -1 and "chained MLP passes" in err()
         with pytest.raises(ValueError, match="chained MLP passes"):
             pl.HipGradPlanner(flat, p, gcfg)
         mp = pl.HipMppiPlanner(flat, p, pl.MppiCfg(K=32, iters=1), device=DEV)

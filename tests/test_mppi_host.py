@@ -60,11 +60,12 @@ def test_valid_configurations_pass_and_the_problem_is_checked_first(lib):
         assert lib.lg_last_error().decode().startswith("lg_plan: ") and word in lib.lg_last_error().decode()
     assert lib.lg_mppi_check(C.byref(cfg.to_struct()), C.byref(prob.to_struct()), None, 1, 1) == -1 and "level" in lib.lg_last_error().decode()
     # the entries refuse before they touch a device
-    assert lib.lg_plan_mppi(None, C.byref(prob.to_struct()), C.byref(pl.MppiCfg(K=33).to_struct()), *([None] * 5), 0, 0.0, 1, *([None] * 7)) == -1
+    one = C.byref(capi.lg_plan_call(count=1))
+    assert lib.lg_plan_mppi(None, C.byref(prob.to_struct()), C.byref(pl.MppiCfg(K=33).to_struct()), one, *([None] * 6)) == -1
     assert "K = 33" in lib.lg_last_error().decode()
-    assert lib.lg_plan_mppi_step(None, C.byref(prob.to_struct()), C.byref(cfg.to_struct()), 0, 0, 0, *([None] * 5), 0, 0.0, 1, *([None] * 10)) == -1
+    assert lib.lg_plan_mppi_step(None, C.byref(prob.to_struct()), C.byref(cfg.to_struct()), one, 0, 0, 0, *([None] * 9)) == -1
     assert "what" in lib.lg_last_error().decode()
-    assert lib.lg_plan_mppi_step(None, C.byref(prob.to_struct()), C.byref(cfg.to_struct()), 0, 3, 0, *([None] * 5), 0, 0.0, 1, *([None] * 10)) == -1
+    assert lib.lg_plan_mppi_step(None, C.byref(prob.to_struct()), C.byref(cfg.to_struct()), one, 0, 3, 0, *([None] * 9)) == -1
     assert "missing array" in lib.lg_last_error().decode()
     assert lib.lg_plan_mppi_candidates(C.byref(prob.to_struct()), C.byref(cfg.to_struct()), 0, None, 1, None, None) == -1
     assert "missing array" in lib.lg_last_error().decode()

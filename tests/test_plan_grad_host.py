@@ -60,17 +60,17 @@ def test_valid_configurations_pass_and_the_problem_is_checked_first(lib):
         assert lib.lg_last_error().decode().startswith("lg_plan: ") and word in lib.lg_last_error().decode()
     assert lib.lg_plan_grad_check(C.byref(cfg.to_struct()), C.byref(prob.to_struct()), None, 1, 1) == -1 and "level" in lib.lg_last_error().decode()
     # the entries refuse before they touch a device
-    ps, cs = C.byref(prob.to_struct()), C.byref(cfg.to_struct())
-    assert lib.lg_plan_grad(None, ps, C.byref(pl.GradCfg(lr=0.0).to_struct()), *([None] * 6), 0, 0.0, 1, *([None] * 6)) == -1
+    ps, cs, one = C.byref(prob.to_struct()), C.byref(cfg.to_struct()), C.byref(capi.lg_plan_call(count=1))
+    assert lib.lg_plan_grad(None, ps, C.byref(pl.GradCfg(lr=0.0).to_struct()), one, *([None] * 6)) == -1
     assert "lr must be positive" in lib.lg_last_error().decode()
-    assert lib.lg_plan_grad(None, ps, cs, *([None] * 6), 0, 0.0, 1, *([None] * 6)) == -1 and "missing array" in lib.lg_last_error().decode()
+    assert lib.lg_plan_grad(None, ps, cs, one, *([None] * 6)) == -1 and "missing array" in lib.lg_last_error().decode()
     for what in (0, 2, 4):
-        assert lib.lg_plan_descend_step(None, ps, cs, 0, what, 0, *([None] * 5), 0, 0.0, 1, *([None] * 13)) == -1
+        assert lib.lg_plan_descend_step(None, ps, cs, one, 0, what, 0, *([None] * 12)) == -1
         assert "what" in lib.lg_last_error().decode()
-    assert lib.lg_plan_descend_step(None, ps, cs, -1, 3, 0, *([None] * 5), 0, 0.0, 1, *([None] * 13)) == -1 and "it must" in lib.lg_last_error().decode()
-    assert lib.lg_plan_descend_step(None, ps, cs, 0, 3, 0, *([None] * 5), 0, 0.0, 1, *([None] * 13)) == -1
+    assert lib.lg_plan_descend_step(None, ps, cs, one, -1, 3, 0, *([None] * 12)) == -1 and "it must" in lib.lg_last_error().decode()
+    assert lib.lg_plan_descend_step(None, ps, cs, one, 0, 3, 0, *([None] * 12)) == -1
     assert "missing array" in lib.lg_last_error().decode()
-    assert lib.lg_plan_descend(None, ps, C.byref(pl.GradCfg(iters=0).to_struct()), *([None] * 5), 0, 0.0, 1, *([None] * 9)) == -1
+    assert lib.lg_plan_descend(None, ps, C.byref(pl.GradCfg(iters=0).to_struct()), one, *([None] * 8)) == -1
     assert "iters = 0" in lib.lg_last_error().decode()
 
 

@@ -107,6 +107,53 @@ def test_struct_matches_the_header(lib):
     assert out == [C.sizeof(capi.lg_plan_problem), capi.lg_plan_problem.goal.offset, capi.lg_plan_problem.rom_v_max.offset]
 
 
+def test_call_struct_matches_the_header():
+    import subprocess
+    import tempfile
+    from legged_gym_dev_amd import capi
+    T = capi.lg_plan_call
+    names = [n for n, _ in T._fields_]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "legged_hip.h"\nint main(){printf("%zu' + ' %zu' * len(names) + \
+          '\\n",sizeof(lg_plan_call)' + "".join(f",offsetof(lg_plan_call,{n})" for n in names) + ');return 0;}\n'
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        out = [int(v) for v in subprocess.check_output([os.path.join(d, "t")]).decode().split()]
+    assert names == ["z0", "e", "v_prev", "w0", "offset", "scenes", "count", "has_level", "level", "stream"]
+    assert out == [C.sizeof(T)] + [getattr(T, n).offset for n in names]
+
+
+def test_argtypes_match_the_prototypes(lib):
+    """Every lg_plan_* / lg_mppi_* prototype of the header against the ctypes declaration: as many arguments, and per position the
+    same class -- pointer, 32-bit integer, 64-bit integer or float.  ctypes checks none of this at a call."""
+    import re
+    import subprocess
+    from legged_gym_dev_amd.lib import SO_PATH
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "legged_hip.h")).read(), flags=re.S)
+    protos = dict(re.findall(r"\bint\s+(lg_(?:plan|mppi)_\w+)\s*\(([^)]*)\)\s*;", text))
+    assert len(protos) == 13 and {"lg_plan_score", "lg_plan_descend_step", "lg_mppi_check", "lg_plan_track", "lg_plan_fleet_scenes"} <= set(protos)
+
+    def of_c(param):
+        if "*" in param:
+            return "pointer"
+        return {"int": "i32", "int32_t": "i32", "int64_t": "i64", "float": "float"}[param.split()[-2]]
+
+    def of_ctypes(t):
+        if t is C.c_void_p or t is C.c_char_p or issubclass(t, C._Pointer):
+            return "pointer"
+        return {C.c_int32: "i32", C.c_int64: "i64", C.c_float: "float"}[t]
+
+    for name, params in protos.items():
+        want = [of_c(q.strip()) for q in params.split(",")]
+        got = [of_ctypes(t) for t in getattr(lib, name).argtypes]
+        assert got == want, name
+    # the twins are gone, from the header and from the library, and the library exports what the header declares
+    keep = {"lg_plan_scenes", "lg_plan_scenes_check", "lg_plan_fleet_scenes"}
+    assert set(re.findall(r"\blg_plan_\w*scenes\w*", text)) == keep
+    syms = {ln.split()[-1] for ln in subprocess.check_output(["nm", "-D", "--defined-only", SO_PATH]).decode().splitlines() if ln.strip()}
+    assert {n for n in syms if re.match(r"lg_(plan|mppi)_", n)} == set(protos)
+
+
 def test_warm_start_by_hand():
     z, v = pl.warm_start("interpolate", [0.0, 1.0], [2.0, 0.0], 4, 0.5)
     np.testing.assert_allclose(z, [[0, 1], [0.5, 0.75], [1.0, 0.5], [1.5, 0.25], [2.0, 0.0]], rtol=0, atol=1e-15)

@@ -1,5 +1,5 @@
 """Per-plan scenes, host side: lg_plan_scenes against the header, lg_plan_scenes_check's refusals and the
-*_scenes entries refusing a wrong S before a device is touched, Scenes' validation, round trips, random_scenes, the audits per scene
+planning entries refusing a wrong S before a device is touched, Scenes' validation, round trips, random_scenes, the audits per scene
 and the scripts' argument refusals.  No GPU."""
 import ctypes as C
 import dataclasses
@@ -65,27 +65,48 @@ def test_every_entry_refuses_a_wrong_S_before_a_device_is_touched(lib):
     mc, gc = pl.MppiCfg(K=32, iters=2).to_struct(), pl.GradCfg(iters=2).to_struct()
     bad = _struct(4)
     j = C.c_void_p(64)
-    pp, sc = C.byref(p), C.byref(bad)
+    pp = C.byref(p)
+    call = lambda scenes: C.byref(capi.lg_plan_call(z0=64, count=5, scenes=C.pointer(scenes)))
+    sc = call(bad)
     calls = {
-        "lg_plan_score_scenes": (None, pp, j, j, None, None, None, None, 0, 0.0, 5, j, j, j, j, None, None, None, sc, None),
-        "lg_plan_mppi_step_scenes": (None, pp, C.byref(mc), 0, 3, 1, j, None, None, None, None, 0, 0.0, 5, j, j, None, None, None, j, j, None, j, sc, None),
-        "lg_plan_mppi_scenes": (None, pp, C.byref(mc), j, None, None, None, None, 0, 0.0, 5, j, j, j, j, None, j, sc, None),
-        "lg_plan_grad_scenes": (None, pp, C.byref(gc), j, j, None, None, None, None, 0, 0.0, 5, j, j, None, None, None, sc, None),
-        "lg_plan_descend_step_scenes": (None, pp, C.byref(gc), 0, 3, 1, j, None, None, None, None, 0, 0.0, 5, j, j, None, None, None, None, j, j, j,
-                                        j, None, j, sc, None),
-        "lg_plan_descend_scenes": (None, pp, C.byref(gc), j, None, None, None, None, 0, 0.0, 5, j, j, j, j, j, j, None, j, sc, None)}
+        "lg_plan_score": (None, pp, sc, j, j, j, j, j, None, None, None),
+        "lg_plan_mppi_step": (None, pp, C.byref(mc), sc, 0, 3, 1, j, j, None, None, None, j, j, None, j),
+        "lg_plan_mppi": (None, pp, C.byref(mc), sc, j, j, j, j, None, j),
+        "lg_plan_grad": (None, pp, C.byref(gc), sc, j, j, j, None, None, None),
+        "lg_plan_descend_step": (None, pp, C.byref(gc), sc, 0, 3, 1, j, j, None, None, None, None, j, j, j, j, None, j),
+        "lg_plan_descend": (None, pp, C.byref(gc), sc, j, j, j, j, j, j, None, j)}
     for name, args in calls.items():
         assert getattr(lib, name)(*args) == -1, name
         assert "lg_plan_scenes: S = 4 differs" in lib.lg_last_error().decode(), name
-    # the gradient entries keep refusing nn_step in the parent's words, with scenes too, and the problem's own fields are still checked
+    # the gradient entries keep refusing nn_step in the same words with scenes as without, and the problem's own fields are still checked
     q = pl.PlanProblem.named("gap", tube_kind="nn_step", N=5).to_struct()
     ok = _struct(5)
-    assert lib.lg_plan_grad_scenes(None, C.byref(q), C.byref(gc), j, j, None, None, None, None, 0, 0.0, 5, j, j, None, None, None, C.byref(ok), None) == -1
+    assert lib.lg_plan_grad(None, C.byref(q), C.byref(gc), call(ok), j, j, j, None, None, None) == -1
     assert "nn_step has no gradient planner" in lib.lg_last_error().decode()
     q = pl.PlanProblem.named("gap", tube_kind="l1", N=5).to_struct()
     q.obs_r[1] = -1.0
-    assert lib.lg_plan_score_scenes(*calls["lg_plan_score_scenes"][:1], C.byref(q), *calls["lg_plan_score_scenes"][2:18], C.byref(ok), None) == -1
+    assert lib.lg_plan_score(None, C.byref(q), call(ok), *calls["lg_plan_score"][3:]) == -1
     assert "obs_r[1]" in lib.lg_last_error().decode()
+
+
+def test_a_library_from_before_the_call_struct_is_refused(lib):
+    """A library that still has lg_plan_score_scenes takes the older positional lists: declare_plan_api marks it and leaves its six
+    planning entries undeclared, and the scorer's helper refuses it -- host code, before any device work."""
+    import types
+    from legged_gym_dev_amd.lib import LeggedHipError
+    entry = lambda: types.SimpleNamespace(argtypes=None)
+    old = types.SimpleNamespace(lg_plan_score=entry(), lg_plan_score_scenes=entry(), lg_plan_check=entry(), lg_plan_scenes_check=entry())
+    capi.declare_plan_api(old)
+    assert old.plan_api_old is True and old.lg_plan_score.argtypes is None and old.lg_plan_score_scenes.argtypes is None
+    assert len(old.lg_plan_check.argtypes) == 3 and len(old.lg_plan_scenes_check.argtypes) == 2      # unchanged entries stay usable
+    with pytest.raises(LeggedHipError, match="lg_plan_score_scenes.*built before lg_plan_call"):
+        pl.refuse_old_library(old)
+    new = types.SimpleNamespace(lg_plan_score=entry(), lg_plan_check=entry())
+    capi.declare_plan_api(new)
+    assert new.plan_api_old is False and len(new.lg_plan_score.argtypes) == 11
+    pl.refuse_old_library(new)
+    assert lib.plan_api_old is False
+    pl.refuse_old_library(lib)
 
 
 G, OC, OR = np.zeros((3, 2)), np.zeros((3, 2, 2)), np.full((3, 2), 0.1)

@@ -71,8 +71,9 @@ def test_refusals_on_the_c_side_without_a_handle(lib):
     assert "nn_step" in err() and "chained MLP passes" in err()
     z = torch.zeros(4)
     p = C.c_void_p(z.data_ptr())
-    assert lib.lg_plan_descend(None, C.byref(st), C.byref(pl.GradCfg().to_struct()), p, None, None, None, None, 0, 0.0, 1, p, p, p, p, p, p, None,
-                               p, None) == -1 and "chained MLP passes" in err()
+    call = capi.lg_plan_call(z0=p, count=1)
+    assert lib.lg_plan_descend(None, C.byref(st), C.byref(pl.GradCfg().to_struct()), C.byref(call), p, p, p, p, p, p, None,
+                               p) == -1 and "chained MLP passes" in err()
 
 
 STAND_IN = [(dict(), _model(), None, None),
