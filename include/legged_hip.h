@@ -1155,6 +1155,48 @@ int lg_obs_hist_compute(lg_obs_hist *h, lg_ctx *env);
 /* Waits for the device, frees the row and the marks.  NULL is accepted. */
 int lg_obs_hist_destroy(lg_obs_hist *h);
 
+/* ------------------------------------------------------------------ empirical observation normalisation (DESIGN.md section
+ * 10.20): running per-column moments of the rows handed to a policy, and y = (x - mean) / (std + eps).  State per column: mean
+ * (0), var (1), std (1), all f32 on the device, and a row counter `count` (0) kept on the host.  update(x), x of (n, W):
+ *   nothing when until >= 0 and count >= until; else count += n, rate = n / count,
+ *   mean_x, var_x = column mean and BIASED column variance of the batch, delta = mean_x - mean,
+ *   mean += rate * delta;  var += rate * (var_x - var + delta * (mean_x - mean)) with the new mean;  std = sqrt(var)
+ * (Chan's merge: until `until` is reached the state is the pooled moments of every row seen).  The batch sums are taken in
+ * double and summed in a fixed order, the rule is evaluated in double from the f32 state and rounded once, so the state and y
+ * are bitwise reproducible.  A training compute (update = 1) updates and then normalises with the NEW state, in two launches
+ * (k_obs_norm_stats, k_obs_norm_apply) for one handle or for a pair; a frozen compute (update = 0, or `until` reached) only
+ * normalises, in one.  All launches go on the stream given; nothing in a compute waits for the device.  The handle holds no
+ * pointer into an env or a learner: x and y are the caller's (or y the handle's own (max_rows, W) buffer). */
+#define LG_OBS_NORM_MAX_WIDTH 1024          /* = LG_OBS_HIST_MAX_WIDTH */
+#define LG_OBS_NORM_ROWS 64                 /* rows per workgroup of either kernel: a training compute keeps one (S1, S2) per 64 rows */
+#define LG_OBS_NORM_COLS 64                 /* columns per workgroup: one lane per column */
+typedef struct lg_obs_norm_cfg {
+    int32_t width /*1..LG_OBS_NORM_MAX_WIDTH*/;
+    float eps /*finite, > 0; rsl_rl's default 1e-2*/;
+    int64_t until /*rows after which updates stop; -1: never; rsl_rl's default 10^8*/;
+} lg_obs_norm_cfg;
+typedef struct lg_obs_norm lg_obs_norm;
+/* Host code, needs no GPU.  0, or -1 with the refused field named in lg_last_error ("lg_obs_norm: ...": width, eps or until). */
+int lg_obs_norm_check(const lg_obs_norm_cfg *cfg);
+/* Allocates the state (two copies, flipped by the host per update), the slab of batch partials for max_rows rows and a
+ * (max_rows, width) output.  Waits for the device. */
+int lg_obs_norm_create(const lg_obs_norm_cfg *cfg, int64_t max_rows, lg_obs_norm **out);
+/* *y: DEVICE f32 (max_rows, *width), the handle's own output; zeros until the first compute into it */
+int lg_obs_norm_buffer(lg_obs_norm *h, void **y, int32_t *width);
+/* num = 1 or 2 handles (two different ones), x[i] DEVICE f32 (n, width_i), the same n for both.  y[i] NULL: the handle's own
+ * buffer (needs n <= max_rows); else DEVICE f32 (n, width_i), not x[i].  update = 1 needs n <= max_rows (the slab); a handle
+ * whose `until` is reached takes the frozen path by itself.  update = 0 takes any n >= 1 when y[i] is given.  A refused call
+ * (-1) or a failed launch (-3) leaves state and count as they were. */
+int lg_obs_norm_compute(lg_obs_norm *const *h, const float *const *x, float *const *y, int32_t num, int64_t n, int32_t update,
+                        void *stream);
+/* HOST pointers (each may be NULL), `width` floats each.  Waits for the device. */
+int lg_obs_norm_get_state(lg_obs_norm *h, float *mean, float *var, float *std, int64_t *count);
+/* HOST pointers; std = sqrtf(var) on the host.  Refuses a negative or non-finite var, a non-finite mean and a negative count.
+ * Waits for the device. */
+int lg_obs_norm_set_state(lg_obs_norm *h, const float *mean, const float *var, int64_t count);
+/* Waits for the device and frees everything.  NULL is accepted. */
+int lg_obs_norm_destroy(lg_obs_norm *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -493,6 +493,28 @@ def declare_obs_hist_api(lib):
     return lib
 
 
+OBS_NORM_MAX_WIDTH, OBS_NORM_ROWS, OBS_NORM_COLS = 1024, 64, 64       # LG_OBS_NORM_MAX_WIDTH / _ROWS / _COLS
+
+
+class lg_obs_norm_cfg(C.Structure):
+    """Empirical observation normalisation (include/legged_hip.h lg_obs_norm_cfg)."""
+    _fields_ = [("width", i32), ("eps", f32), ("until", i64)]
+
+
+def declare_obs_norm_api(lib):
+    """The lg_obs_norm_* entries; raises if the library was built without them (there is no fallback)."""
+    vp, pc, pf = C.c_void_p, C.POINTER(lg_obs_norm_cfg), C.POINTER(f32)
+    lib.lg_last_error.restype = C.c_char_p
+    lib.lg_obs_norm_check.argtypes = [pc]
+    lib.lg_obs_norm_create.argtypes = [pc, i64, C.POINTER(vp)]
+    lib.lg_obs_norm_buffer.argtypes = [vp, C.POINTER(vp), PI32]
+    lib.lg_obs_norm_compute.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i64, i32, vp]
+    lib.lg_obs_norm_get_state.argtypes = [vp, pf, pf, pf, C.POINTER(i64)]
+    lib.lg_obs_norm_set_state.argtypes = [vp, pf, pf, i64]
+    lib.lg_obs_norm_destroy.argtypes = [vp]
+    return lib
+
+
 def declare_env_api(lib, prefix="lg_"):
     """Attach argtypes/restypes for the env entry points on a loaded library."""
     vp = C.c_void_p

@@ -124,5 +124,8 @@ LeggedRobotCfgPPO = cfg_class("LeggedRobotCfgPPO", BaseConfig, dict(
         policy_class_name='ActorCritic', algorithm_class_name='PPO', num_steps_per_env=24, max_iterations=1500,
         save_interval=50, experiment_name='test', run_name='', resume=False, load_run=-1, checkpoint=-1,
         resume_path=None,
+        # rsl_rl's empirical_normalization (rl/obs_norm.py; this build's own fields): running mean / variance of the actor's and the
+        # critic's row in front of the learner, updated during the rollout, frozen for inference, saved with the checkpoint
+        empirical_normalization=False, empirical_normalization_eps=1e-2, empirical_normalization_until=10 ** 8,
     ),
 ), doc=None, module=__name__)

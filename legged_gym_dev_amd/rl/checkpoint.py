@@ -149,12 +149,33 @@ class HistoryPolicy(torch.nn.Module):
         self.fresh.fill_(True)
 
 
-def export_policy_as_jit(actor_critic, path, activation=None, obs_history=None):
+def fold_obs_normalizer(state_dict, norm):
+    """The frozen normaliser y = (x - mean) / (std + eps) folded into the layer that reads the row, so that the exported module takes
+    RAW rows: W' = W diag(1 / (std + eps)), b' = b - W' mean, in float64, rounded once.  The layer is ``actor.0`` (also behind a
+    history: it reads the (1, W) history row), or ``memory_a.rnn.weight_ih_l0`` / ``bias_ih_l0`` of the recurrent policy.  ``norm``:
+    the normaliser's state dict (``_mean``, ``_std`` of (1, W)), optionally with ``eps`` (default 1e-2).  Returns a new dict."""
+    wk, bk = (("memory_a.rnn.weight_ih_l0", "memory_a.rnn.bias_ih_l0") if "memory_a.rnn.weight_ih_l0" in state_dict
+              else ("actor.0.weight", "actor.0.bias"))
+    w, b = state_dict[wk].detach().cpu().double(), state_dict[bk].detach().cpu().double()
+    mean, std = norm["_mean"].detach().cpu().double().reshape(-1), norm["_std"].detach().cpu().double().reshape(-1)
+    if mean.numel() != w.shape[1] or std.numel() != w.shape[1]:
+        raise ValueError(f"the observation normaliser has {mean.numel()} columns but {wk} reads {w.shape[1]}")
+    w2 = w / (std + float(norm.get("eps", 1e-2))).reshape(1, -1)
+    out = {k: v for k, v in state_dict.items()}
+    out[wk], out[bk] = w2.float(), (b - w2 @ mean).float()
+    return out
+
+
+def export_policy_as_jit(actor_critic, path, activation=None, obs_history=None, obs_normalizer=None):
     """helpers.py:274-285: ``<path>/policy_1.pt`` = torch.jit.script(actor MLP on CPU); a recurrent policy (memory_a.* in its
     state dict) goes to ``<path>/policy_lstm_1.pt`` instead (helpers.py:288-313).  With ``obs_history`` (an enabled
-    ObsHistorySpec) the actor goes out behind its history as ``<path>/policy_hist_1.pt`` (HistoryPolicy)."""
+    ObsHistorySpec) the actor goes out behind its history as ``<path>/policy_hist_1.pt`` (HistoryPolicy).  With ``obs_normalizer``
+    (the state dict of the actor row's frozen normaliser, rl/obs_norm.py) the module takes raw rows: the normaliser is folded into
+    its first layer (fold_obs_normalizer); file names and module surfaces stay."""
     os.makedirs(path, exist_ok=True)
     sd = actor_critic.state_dict()
+    if obs_normalizer is not None:
+        sd = fold_obs_normalizer(sd, obs_normalizer)
     activation = activation or getattr(actor_critic, "activation", "elu")
     if obs_history is not None and obs_history.enabled:
         scripted = torch.jit.script(HistoryPolicy(sd, activation, obs_history).to("cpu"))

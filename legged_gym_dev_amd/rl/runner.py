@@ -27,6 +27,8 @@ class _ActorFacade(torch.nn.Module):
         self._ppo = ppo
 
     def forward(self, obs):
+        """Rows as the learner sees them: with runner.empirical_normalization these are rows that are ALREADY normalised, as
+        rsl_rl's actor takes them; runner.get_inference_policy() is the callable that takes raw rows."""
         return self._ppo.act_inference(obs)
 
 
@@ -56,6 +58,8 @@ class ActorCriticFacade:
         self._ppo.load_state_dict(sd)
 
     def act_inference(self, obs):
+        """Action means of rows as the learner sees them: with runner.empirical_normalization these are rows that are ALREADY
+        normalised (rsl_rl's act_inference takes the same); runner.get_inference_policy() normalises raw rows first."""
         return self._ppo.act_inference(obs)
 
     def eval(self):
@@ -79,6 +83,8 @@ class _Alg:
 
 
 class OnPolicyRunner:
+    obs_normalizer = critic_obs_normalizer = None        # rl/obs_norm.py handles when runner.empirical_normalization is set
+
     def __init__(self, env, train_cfg, log_dir=None, device="cuda:0", wandb_callback=None, comm=None):
         self.cfg = train_cfg["runner"]
         self.alg_cfg, self.policy_cfg = train_cfg["algorithm"], train_cfg["policy"]
@@ -109,6 +115,12 @@ class OnPolicyRunner:
         if self.obs_history_spec is not None and self.cfg.get("policy_class_name", "ActorCritic") == "ActorCriticRecurrent":
             raise ValueError(f"cfg.obs_history ({self.obs_history_spec}) with ActorCriticRecurrent: a stacked history in front of a "
                              "memory; use one or the other")
+        # empirical normalisation (rl/obs_norm.py): running moments of the actor's and the critic's row, off unless the cfg says so
+        self.empirical_normalization = bool(self.cfg.get("empirical_normalization", False))
+        if self.empirical_normalization and self.world_size > 1:
+            raise ValueError(f"runner.empirical_normalization with world_size = {self.world_size}: every rank would keep the moments "
+                             "of its own env shard and the ranks' policies would drift apart; merging the ranks' moments is not "
+                             "built yet, train on one GPU or switch it off")
         self.ppo = HipPPO(env.num_envs, nact, ncrit, env.num_actions, self.policy_cfg, self.alg_cfg,
                           self.num_steps_per_env, device=self.device, seed=train_cfg.get("seed", 1),
                           world_size=self.world_size, rank=self.rank,
@@ -120,6 +132,19 @@ class OnPolicyRunner:
             self.ppo.params_changed()
             if hasattr(self.comm, "attach"):
                 self.comm.attach(self.ppo)            # NativeComm: gradients reduced inside the backward pass from here on
+        self.obs_normalizer = self.critic_obs_normalizer = None
+        if self.empirical_normalization:
+            from .obs_norm import HipObsNormalizer, ObsNormSpec, refusal
+            eps, until = self.cfg.get("empirical_normalization_eps", 1e-2), self.cfg.get("empirical_normalization_until", 10 ** 8)
+            specs = [ObsNormSpec(w, 1e-2 if eps is None else float(eps), 10 ** 8 if until is None else int(until)) for w in (nact, ncrit)]
+            why = refusal(specs[0])
+            if why:
+                raise ValueError(f"runner.empirical_normalization: {why}")
+            self.obs_normalizer = HipObsNormalizer(specs[0], env.num_envs, self.device)
+            # one object when actor and critic read the same row; else the critic's own: the privileged row, or the single frame
+            self.critic_obs_normalizer = (HipObsNormalizer(specs[1], env.num_envs, self.device) if self.ppo.privileged
+                                          else self.obs_normalizer)
+            self._norm_scratch = None
         self.fuse_epilogue = os.environ.get("LG_FUSE_EPILOGUE", "1") != "0"
         self.log_dir = log_dir
         self.tot_timesteps, self.tot_time, self.current_learning_iteration = 0, 0.0, 0
@@ -142,6 +167,8 @@ class OnPolicyRunner:
         """24 x {act, env.step, process_env_step} + compute_returns.  For the duration of the rollout the env is attached to the
         learner (lg_ppo_attach_env): the step's single-workgroup epilogue and process_env_step ride on the next act's launch --
         3 launches per policy step instead of 5, same results (LG_FUSE_EPILOGUE=0 keeps them as launches of their own)."""
+        if self.obs_normalizer is not None:
+            return self._rollout_normalized()
         env, ppo = self.env, self.ppo
         obs, priv = env.get_observations(), env.get_privileged_observations()
         hist = self.obs_history_spec is not None
@@ -158,6 +185,37 @@ class OnPolicyRunner:
                 ppo.process_env_step(rewards, env.core.t["reset"], {"time_outs": env.core.t["extras_time_outs"]}
                                      if "time_outs" in infos else {})
             ppo.compute_returns(priv if priv is not None else obs, self._all_reduce if self.world_size > 1 else None)
+        finally:
+            if fuse:
+                ppo.attach_env(None)
+
+    def _rollout_normalized(self):
+        """rollout() with runner.empirical_normalization: the learner is handed the normalisers' buffers.  One frozen compute of
+        the current rows before the loop (the first rollout, a load, an env.reset made outside), one training compute after every
+        env.step -- two launches for the actor's and the critic's row together, which touch neither the env nor the learner, so
+        the fused epilogue stays fused.  count grows by num_steps_per_env * num_envs."""
+        from .obs_norm import compute_pair
+        env, ppo = self.env, self.ppo
+        a, c = self.obs_normalizer, self.critic_obs_normalizer
+        hist, fuse = self.obs_history_spec is not None, self.fuse_epilogue
+
+        def rows():
+            obs, priv = env.get_observations(), env.get_privileged_observations()
+            return (env.get_actor_observations() if hist else obs), (priv if priv is not None else obs)
+
+        xa, xc = rows()
+        ya, yc = compute_pair(a, xa, c, xc, False)
+        if fuse:
+            ppo.attach_env(env.core)
+        try:
+            for _ in range(self.num_steps_per_env):
+                actions = ppo.act(ya, yc if c is not a else None)
+                _, _, rewards, dones, infos = env.step(actions)
+                xa, xc = rows()
+                ya, yc = compute_pair(a, xa, c, xc, True)
+                ppo.process_env_step(rewards, env.core.t["reset"], {"time_outs": env.core.t["extras_time_outs"]}
+                                     if "time_outs" in infos else {})
+            ppo.compute_returns(yc, self._all_reduce if self.world_size > 1 else None)
         finally:
             if fuse:
                 ppo.attach_env(None)
@@ -298,6 +356,10 @@ class OnPolicyRunner:
              "iter": self.current_learning_iteration, "infos": infos}
         if self.obs_history_spec is not None:          # what the actor's first layer was trained on; rsl_rl's loader ignores the key
             d["obs_history"] = self.obs_history_spec.as_dict()
+        if self.obs_normalizer is not None:            # rsl_rl's keys; the two are equal when one normaliser serves both rows
+            d["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+            d["critic_obs_norm_state_dict"] = self.critic_obs_normalizer.state_dict()
+            d["obs_norm"] = {"eps": self.obs_normalizer.spec.eps, "until": self.obs_normalizer.spec.until}
         torch.save(d, path)
 
     def load(self, path, load_optimizer=True):
@@ -307,11 +369,47 @@ class OnPolicyRunner:
         if not saved.same_row(own):
             raise ValueError(f"{path}: the checkpoint's policy was trained on cfg.obs_history = ({saved}) but the env's is ({own}); "
                              "pass the checkpoint's --obs_history / --obs_history_columns / --obs_history_reset")
+        saved_norm = d.get("obs_norm_state_dict") is not None
+        if saved_norm != (self.obs_normalizer is not None):
+            raise ValueError(f"{path}: the checkpoint's policy was trained " + ("with" if saved_norm else "without") +
+                             " runner.empirical_normalization but the runner is set up " +
+                             ("without" if saved_norm else "with") + " it; " +
+                             ("pass --empirical_normalization" if saved_norm else "drop --empirical_normalization"))
+        if saved_norm:
+            pairs = [("obs_norm_state_dict", self.obs_normalizer), ("critic_obs_norm_state_dict", self.critic_obs_normalizer)]
+            for key, norm in pairs:                    # both widths are checked before either state is touched
+                if key not in d:
+                    raise ValueError(f"{path}: runner.empirical_normalization: the checkpoint has no {key}")
+                w = int(d[key]["_mean"].numel())
+                if w != norm.width:
+                    raise ValueError(f"{path}: runner.empirical_normalization: {key} has {w} columns but the runner's row has "
+                                     f"{norm.width}")
+            eps = float(d.get("obs_norm", {}).get("eps", self.obs_normalizer.spec.eps))
+            if eps != self.obs_normalizer.spec.eps:
+                raise ValueError(f"{path}: runner.empirical_normalization_eps = {self.obs_normalizer.spec.eps} but the checkpoint's "
+                                 f"policy was trained with {eps}")
         self.ppo.load_state_dict(d["model_state_dict"])
+        if saved_norm:
+            for key, norm in pairs[:1 if self.critic_obs_normalizer is self.obs_normalizer else 2]:
+                norm.load_state_dict(d[key])
         if load_optimizer and d.get("optimizer_state_dict"):
             self.ppo.load_optimizer_state_dict(d["optimizer_state_dict"])
         self.current_learning_iteration = d["iter"]
         return d.get("infos")
 
     def get_inference_policy(self, device=None):
-        return self.ppo.act_inference
+        """The callable every downstream tool drives the robot with: raw rows in, action means out.  With
+        runner.empirical_normalization it normalises the rows (frozen; any number of them, the learner's own row limit stands) into a
+        scratch tensor first."""
+        if self.obs_normalizer is None:
+            return self.ppo.act_inference
+        from .ppo import check_width
+        norm, ppo = self.obs_normalizer, self.ppo
+
+        def policy(obs):
+            check_width(obs, ppo.O, "act_inference: obs")
+            x = obs.to(torch.float32).contiguous()
+            if self._norm_scratch is None or self._norm_scratch.shape != x.shape:
+                self._norm_scratch = torch.empty_like(x)
+            return ppo.act_inference(norm.normalize(x, out=self._norm_scratch))
+        return policy

@@ -34,8 +34,11 @@ def play(args, num_steps=None, out_mat="play_data.mat"):
     policy = ppo_runner.get_inference_policy(device=env.device)
     if EXPORT_POLICY:
         path = os.path.join(LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name, "exported", "policies")
+        norm = getattr(ppo_runner, "obs_normalizer", None)       # --empirical_normalization: folded into the exported first layer
         print("Exported policy as jit script to:", export_policy_as_jit(ppo_runner.alg.actor_critic, path,
-                                                                        obs_history=getattr(env, "obs_history_spec", None)))
+                                                                        obs_history=getattr(env, "obs_history_spec", None),
+                                                                        obs_normalizer=None if norm is None else dict(
+                                                                            norm.state_dict(), eps=norm.spec.eps)))
     logger = Logger(env.dt)
     robot_index, joint_index, stop_state_log = 0, 1, 100
     N = int(num_steps if num_steps else env.max_episode_length)

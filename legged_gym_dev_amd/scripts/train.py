@@ -3,7 +3,9 @@ Same flow as the reference's scripts/train.py:40-44; multi-GPU: launch with torc
 Asymmetric critic: --privileged_obs obs,friction,base_mass,feet_contact,feet_air_time gives the critic its own noise-free row
 (envs/base/privileged_obs.py lists the terms); the actor, checkpoints, play and export are unchanged.
 Observation history: --obs_history H [--obs_history_columns lo:hi,... --obs_history_reset repeat|zero] stacks the actor's last H
-observations in front of the MLP (envs/base/obs_history.py); the checkpoint carries the spec and play.py needs the same flags."""
+observations in front of the MLP (envs/base/obs_history.py); the checkpoint carries the spec and play.py needs the same flags.
+Empirical normalisation: --empirical_normalization keeps running means and variances of the actor's and the critic's row in front of
+the learner (rl/obs_norm.py); the checkpoint carries them and play.py needs the flag again."""
 import os
 import sys
 

@@ -120,6 +120,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             r.max_iterations = args.max_iterations
         if getattr(args, "resume", False):
             r.resume = args.resume
+        if getattr(args, "empirical_normalization", False):      # rl/obs_norm.py; absent or False leaves the cfg's own value
+            r.empirical_normalization = True
         for name in ("experiment_name", "run_name", "load_run", "checkpoint"):
             if getattr(args, name, None) is not None:
                 setattr(r, name, getattr(args, name))
@@ -149,6 +151,8 @@ def get_args(argv=None):
     p.add_argument("--obs_history", type=int, help="frames in the actor's observation row including the current one (1: off)")
     p.add_argument("--obs_history_columns", type=str, help="lo:hi[,lo:hi...]: the obs columns that past frames keep (default: all)")
     p.add_argument("--obs_history_reset", type=str, choices=["repeat", "zero"], help="what a reset leaves in the past frames")
+    p.add_argument("--empirical_normalization", action="store_true", default=False, help="normalise the actor's and the critic's row by "
+                   "their running mean and variance (rsl_rl's empirical_normalization); play and evaluation need it iff training had it")
     args, _ = p.parse_known_args(argv)
     args.physics_engine = 1          # SIM_PHYSX placeholder: the HIP physics is the only engine
     args.use_gpu_pipeline = args.pipeline.lower() in ("gpu", "cuda")
