@@ -520,6 +520,7 @@ def declare_env_api(lib, prefix="lg_"):
     vp = C.c_void_p
     g = lambda n: getattr(lib, prefix + n)
     g("last_error").restype = C.c_char_p
+    g("last_error").argtypes = []
     g("create").argtypes = [C.POINTER(lg_cfg), C.POINTER(lg_model), C.c_void_p, C.POINTER(vp)]
     g("destroy").argtypes = [vp]
     g("get_buffers").argtypes = [vp, C.POINTER(lg_buffers)]
@@ -549,6 +550,56 @@ def declare_env_api(lib, prefix="lg_"):
             g("traj_replan").argtypes = [vp, vp, i32, vp]
         g("set_stream").argtypes = [vp, vp]
         lib.lg_version.restype = C.c_int
+        lib.lg_version.argtypes = []
+
+
+def declare_ppo_api(lib):
+    """The lg_ppo_* entries of the learner itself; a library built without the PPO sources keeps them undeclared."""
+    vp = C.c_void_p
+    if not hasattr(lib, "lg_ppo_create"):
+        return
+    lib.lg_ppo_create.argtypes = [C.POINTER(lg_ppo_cfg), C.POINTER(vp)]
+    lib.lg_ppo_destroy.argtypes = [vp]
+    lib.lg_ppo_get_buffers.argtypes = [vp, C.POINTER(lg_ppo_buffers)]
+    lib.lg_ppo_set_stream.argtypes = [vp, vp]
+    lib.lg_ppo_param_layout.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
+    lib.lg_ppo_inject_noise.argtypes = [vp, C.c_int]
+    lib.lg_ppo_act.argtypes = [vp, vp, vp]
+    lib.lg_ppo_process_env_step.argtypes = [vp, vp, vp, vp]
+    lib.lg_ppo_compute_returns.argtypes = [vp, vp]
+    lib.lg_ppo_normalize_advantages.argtypes = [vp]
+    lib.lg_ppo_begin_update.argtypes = [vp]
+    lib.lg_ppo_minibatch_backward.argtypes = [vp, C.c_int, C.c_int]
+    lib.lg_ppo_minibatch_step.argtypes = [vp]
+    lib.lg_ppo_end_update.argtypes = [vp]
+    lib.lg_ppo_act_inference.argtypes = [vp, vp, vp, C.c_int64]
+    lib.lg_ppo_params_changed.argtypes = [vp]
+    lib.lg_ppo_set_deterministic.argtypes = [vp, C.c_int]
+    lib.lg_ppo_attach_env.argtypes = [vp, vp]
+    lib.lg_ppo_create_recurrent.argtypes = [C.POINTER(lg_ppo_cfg), C.POINTER(lg_ppo_rnn_cfg), C.POINTER(vp)]
+    lib.lg_ppo_get_rnn_buffers.argtypes = [vp, C.POINTER(lg_ppo_rnn_buffers)]
+    lib.lg_ppo_reset_hidden.argtypes = [vp, vp]
+    lib.lg_ppo_debug_bucket_extents.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.lg_ppo_debug_mb_sets.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+    lib.lg_ppo_debug_weight_planes.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(vp)]
+    # the learner's entries that take a communicator (declare_comm_api)
+    lib.lg_ppo_set_comm.argtypes = [vp, vp]
+    lib.lg_ppo_comm_timing.argtypes = [vp, C.c_int]
+    lib.lg_ppo_comm_wait_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.lg_ppo_allreduce_adv_moments.argtypes = [vp, vp]
+    lib.lg_ppo_broadcast_params.argtypes = [vp, vp, C.c_int]
+
+
+def declare_comm_api(lib):
+    """The lg_comm_* collectives."""
+    vp = C.c_void_p
+    lib.lg_comm_get_unique_id.argtypes = [vp]
+    lib.lg_comm_init.argtypes = [C.c_int, C.c_int, vp, C.POINTER(vp)]
+    lib.lg_comm_destroy.argtypes = [vp]
+    lib.lg_comm_rank.argtypes = [vp]
+    lib.lg_comm_size.argtypes = [vp]
+    lib.lg_comm_allreduce_sum.argtypes = [vp, vp, C.c_int64, vp]
+    lib.lg_comm_broadcast.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
 
 
 ENV_SYMBOLS = ["last_error", "create", "destroy", "get_buffers", "set_step_counter", "get_step_counter",

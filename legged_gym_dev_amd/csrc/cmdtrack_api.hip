@@ -9,16 +9,7 @@
 #include <vector>
 
 #include "cmdtrack_device.h"
-
-void lg_set_error(const std::string &s);
-
-struct lg_ctx;
-extern "C" {
-void cmdtrackk_launch(const CmdTrackDev *D, const lg_cmdtrack_rec *rec, int t, int64_t epoch, int construct, hipStream_t st);
-// env_api.hip; same library, not in the header
-hipStream_t lg_internal_stream(lg_ctx *c);
-const DevParams *lg_internal_host_params(lg_ctx *c);
-}
+#include "lg_internal.h"
 
 struct lg_cmdtrack {
     lg_cmdtrack_cfg cfg;

@@ -20,3 +20,7 @@ struct CmdTrackDev {                    // passed by value to the kernel
     float rom_dt;
     float Kp[9], u_min[3], u_max[3], cmd_scale[3];
 };
+
+extern "C" {
+void cmdtrackk_launch(const CmdTrackDev *D, const lg_cmdtrack_rec *rec, int t, int64_t epoch, int construct, hipStream_t st);
+}

@@ -9,9 +9,7 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/legged_hip.h"
-
-void lg_set_error(const std::string &s);
+#include "lg_internal.h"
 
 namespace {
 typedef struct { char internal[128]; } nccl_uid;                      // ncclUniqueId (rccl.h:43)
@@ -110,7 +108,7 @@ int lg_comm_broadcast(lg_comm *c, float *buf, int64_t n, int root, void *stream)
     return chk(R.bcast(buf, buf, (size_t)n, kFloat32, root, c->comm, (hipStream_t)stream), "ncclBroadcast");
 }
 
-// internal: used by ppo_api.hip for the overlapped per-layer gradient reduction
+// internal (lg_internal.h): the learner's overlapped per-layer gradient reduction (ppo_sched.hip)
 hipStream_t lg_comm_stream_(lg_comm *c) { return c->stream; }
 hipEvent_t lg_comm_event_(lg_comm *c) { return c->done; }
 int lg_comm_group_allreduce_(lg_comm *c, float *const *bufs, const int64_t *counts, int n, hipStream_t s) {

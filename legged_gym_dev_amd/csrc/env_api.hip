@@ -6,23 +6,10 @@
 #include <string>
 
 #include "lg_device.h"
+#include "lg_internal.h"
 
 static thread_local std::string g_err;
 void lg_set_error(const std::string &s) { g_err = s; }
-
-extern "C" void lgk_set_actions(const DevParams *P, const float *a, int n, hipStream_t s);
-extern "C" int lgk_substeps(const DevParams *P, const float *a_in, int N, int L, int J, int lstm, int mode, int iters, hipStream_t s);
-extern "C" void lgk_post_step(const DevParams *P, int N, int64_t counter, int inject, int init_done, int traj, int push_now, int finalize,
-                              hipStream_t s);
-extern "C" void lgk_finalize(const DevParams *P, int accumulate, hipStream_t s);
-extern "C" void lgk_set_stage(DevParams *P, const lg_stage *st, int what, hipStream_t s);
-extern "C" void lgk_reset_all(const DevParams *P, int N, int64_t counter, int inject, int init_done, hipStream_t s);
-extern "C" void lgk_traj_reset(const DevParams *P, const float *z, int N, int64_t counter, int inject, hipStream_t s);
-extern "C" void lgk_traj_set_plans(DevParams *P, const float *v, int N, int n, hipStream_t s);
-extern "C" void lgk_traj_replan(DevParams *P, const float *v, int N, int n, const uint8_t *skip, hipStream_t s);
-extern "C" void lgk_traj_record(const DevParams *P, const lg_traj_rec *rec, int N, int begin, hipStream_t s);
-extern "C" void lgk_reset_ids(const DevParams *P, const int32_t *ids, int n, int N, int64_t counter, int inject, int init_done, int traj,
-                              hipStream_t s);
 
 #define HIPCHK(x)                                                                                  \
     do {                                                                                           \
@@ -342,7 +329,7 @@ static void flush_finalize(lg_ctx *c) {
     if (c->finalize_pending) { lgk_finalize(c->d, 1, c->stream); c->finalize_pending = 0; }
 }
 int lg_finalize(lg_ctx *c) { if (!c) return -1; flush_finalize(c); return chk_launch(); }
-// ---- internal (same library, not in the header): the learner's fused rollout epilogue (ppo_api.hip, lg_ppo_attach_env)
+// ---- internal (lg_internal.h): the learner's fused rollout epilogue (lg_ppo_attach_env)
 void lg_internal_defer_finalize(lg_ctx *c, int on) { if (!on) flush_finalize(c); c->defer_finalize = on; }
 int lg_internal_finalize_pending(lg_ctx *c) { return c->finalize_pending; }
 // the caller's launch runs the epilogue of the last step: hand over what it needs and clear the flag
@@ -430,8 +417,6 @@ int lg_reset_ids(lg_ctx *c, const int32_t *ids, int n) {        // legged_robot.
 }
 // the control loop alone (clip + decimation x {torques, physics}), without the post-step: timing / profiling entry
 int lg_debug_control_loop(lg_ctx *c, const float *actions) { return run_substeps(c, actions, 3, c->h.cfg.decimation); }
-extern "C" void lgk_debug_set_substeps_nw(int v);
-extern "C" void lgk_debug_set_substeps_occ(int v);
 int lg_debug_set_substeps_occ(int v) { lgk_debug_set_substeps_occ(v); return 0; }     // control-loop register budget: 0 by grid size, 1 / 2 forced
 int lg_debug_set_substeps_nw(int v) { lgk_debug_set_substeps_nw(v); return 0; }   // control-loop block shape: 4 waves / 64/L envs, or 2 / 32/L
 

@@ -5,14 +5,10 @@
 #include <cmath>
 #include <string>
 
-#include "../../include/legged_hip.h"
-
-void lg_set_error(const std::string &s);
+#include "fleet_device.h"
+#include "lg_internal.h"
 
 extern "C" {
-void fleetk_scenes(const lg_fleet_cfg *cfg, const float *pos, const float *vel, int64_t P, const float *static_obs, const float *static_vel,
-                   const int32_t *n_static, float t, float *obs, float *obs_vel, int32_t *n_obs, hipStream_t s);
-
 int lg_plan_fleet_scenes(const lg_fleet_cfg *cfg, const float *pos, const float *vel, int64_t P, const float *static_obs,
                          const float *static_vel, const int32_t *n_static, float t, float *obs, float *obs_vel, int32_t *n_obs,
                          void *stream) {

@@ -7,7 +7,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "../../include/legged_hip.h"
+#include "fleet_device.h"
 
 // One lane per robot, one wave per workgroup: FLEET_NT robots walk over all P candidates, staged through LDS FLEET_CH positions at a
 // time (a lane loads FLEET_CH / FLEET_NT of them), every lane reading the same candidate at the same time (an LDS broadcast).  A lane

@@ -238,3 +238,22 @@ __device__ __forceinline__ uint32_t feistel_perm(uint64_t seed, uint64_t key, in
     } while (x >= (uint32_t)n);
     return x;
 }
+
+extern "C" {
+// the launches of env_kernels.hip, as env_api.hip calls them
+void lgk_set_actions(const DevParams *P, const float *a, int n, hipStream_t s);
+int lgk_substeps(const DevParams *P, const float *a_in, int N, int L, int J, int lstm, int mode, int iters, hipStream_t s);
+void lgk_post_step(const DevParams *P, int N, int64_t counter, int inject, int init_done, int traj, int push_now, int finalize,
+                   hipStream_t s);
+void lgk_finalize(const DevParams *P, int accumulate, hipStream_t s);
+void lgk_set_stage(DevParams *P, const lg_stage *st, int what, hipStream_t s);
+void lgk_reset_all(const DevParams *P, int N, int64_t counter, int inject, int init_done, hipStream_t s);
+void lgk_traj_reset(const DevParams *P, const float *z, int N, int64_t counter, int inject, hipStream_t s);
+void lgk_traj_set_plans(DevParams *P, const float *v, int N, int n, hipStream_t s);
+void lgk_traj_replan(DevParams *P, const float *v, int N, int n, const uint8_t *skip, hipStream_t s);
+void lgk_traj_record(const DevParams *P, const lg_traj_rec *rec, int N, int begin, hipStream_t s);
+void lgk_reset_ids(const DevParams *P, const int32_t *ids, int n, int N, int64_t counter, int inject, int init_done, int traj,
+                   hipStream_t s);
+void lgk_debug_set_substeps_occ(int v);
+void lgk_debug_set_substeps_nw(int v);
+}

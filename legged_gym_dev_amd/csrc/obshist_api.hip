@@ -7,17 +7,7 @@
 #include <string>
 
 #include "obshist_device.h"
-
-void lg_set_error(const std::string &s);
-
-struct lg_ctx;
-extern "C" {
-void obshistk_launch(const ObsHistDev *D, hipStream_t st);
-void obshistk_mark(int64_t *marks, const int32_t *ids, int n, int num_envs, int64_t epoch, hipStream_t st);
-// env_api.hip; same library, not in the header
-hipStream_t lg_internal_stream(lg_ctx *c);
-const DevParams *lg_internal_host_params(lg_ctx *c);
-}
+#include "lg_internal.h"
 
 struct lg_obs_hist {
     ObsHistDev dev;                     // the env's pointers and the epoch in it are filled per call

@@ -17,3 +17,8 @@ struct ObsHistDev {                     // passed by value to the kernel: the ra
     int32_t lo[LG_OBS_HIST_MAX_RANGES], hi[LG_OBS_HIST_MAX_RANGES];
     int32_t pos[LG_OBS_HIST_MAX_RANGES];      // selected columns before range r
 };
+
+extern "C" {
+void obshistk_launch(const ObsHistDev *D, hipStream_t st);
+void obshistk_mark(int64_t *marks, const int32_t *ids, int n, int num_envs, int64_t epoch, hipStream_t st);
+}

@@ -7,13 +7,7 @@
 #include <vector>
 
 #include "obsnorm_device.h"
-
-void lg_set_error(const std::string &s);
-
-extern "C" {
-void obsnormk_stats(const ObsNormDev *D, int num, hipStream_t st);
-void obsnormk_apply(const ObsNormDev *D, int num, hipStream_t st);
-}
+#include "lg_internal.h"
 
 struct lg_obs_norm {
     lg_obs_norm_cfg cfg;

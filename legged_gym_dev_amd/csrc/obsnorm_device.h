@@ -23,3 +23,8 @@ struct ObsNormDev {                     // passed by value; blockIdx.z picks the
     long long n;                        // rows, the same for both problems
     int nrb;                            // row blocks of LG_OBS_NORM_ROWS = gridDim.x
 };
+
+extern "C" {
+void obsnormk_stats(const ObsNormDev *D, int num, hipStream_t st);
+void obsnormk_apply(const ObsNormDev *D, int num, hipStream_t st);
+}

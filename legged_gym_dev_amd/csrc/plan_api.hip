@@ -10,27 +10,7 @@
 #include <string>
 
 #include "plan_device.h"
-#include "../../include/legged_hip.h"
-
-void lg_set_error(const std::string &s);
-
-extern "C" {
-// plan_kernels.hip.  D: the handle's TubeDev, or null for an analytic kind
-int64_t tubek_plan_score(const TubeDev *D, const lg_plan_problem *prob, const PlanArgs *A, int64_t B, hipStream_t s);
-int64_t tubek_plan_score_step(const TubeDev *D, const lg_plan_problem *prob, const PlanArgs *A, int64_t B, hipStream_t s);
-void tubek_plan_mppi_candidates(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const float *vbar, int64_t P_, float *out,
-                                hipStream_t s);
-int64_t tubek_plan_sample_score(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const PlanArgs *A, int64_t P_,
-                                const float *vbar, float *J, float *pen, hipStream_t s);
-int64_t tubek_plan_sample_score_step(const TubeDev *D, const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, const PlanArgs *A,
-                                     int64_t P_, const float *vbar, float *J, float *pen, hipStream_t s);
-void tubek_plan_mppi_update(const lg_plan_problem *prob, const lg_mppi_cfg *cfg, int it, int reset, int64_t P_, float *vbar,
-                            const float *J, float *best_J, float *best_v, float *hist, int32_t *n_bad, hipStream_t s);
-int64_t tubek_plan_grad(const TubeDev *D, const lg_plan_problem *prob, const PlanGradArgs *A, int64_t B, hipStream_t s);
-int64_t tubek_plan_step_bytes(const TubeDev *D, const lg_plan_problem *prob);
-// tube_api.hip; same library, not in the header.  Null for a null handle
-const TubeDev *lg_internal_tube_dev(const lg_tube *t);
-}
+#include "lg_internal.h"
 
 // ---------------------------------------------------------------- plans against a tube
 // Taps of a one-step handle: with I' = input_dim minus the level column, I' = 1 + 2 T (not recursive) or

@@ -1,436 +1,15 @@
-// C-ABI (include/legged_hip.h, lg_ppo_*) for the PPO learner: parameter/storage allocation in
-// HBM, layer-by-layer GEMM scheduling of the ActorCritic forward/backward, update orchestration.
+// C-ABI (include/legged_hip.h, lg_ppo_*) for the PPO learner: parameter/storage allocation in HBM and the entries.  What an entry
+// launches, on which stream and in which order, is ppo_sched.hip's; the handle is ppo_learner.h's.
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "ppo_device.h"
-#include "ppo_mlp_args.h"
-#include "ppo_rnn.h"
-
-void lg_set_error(const std::string &s);
-
-extern "C" {
-void ppok_gemm_fwd(const GemmArgs *g, int nz, hipStream_t s);
-void ppok_gemm_dx(const GemmArgs *g, int nz, hipStream_t s);
-void ppok_sync_planes(const PpoDev *P, hipStream_t s);
-int ppok_mlp_fwd(const MlpArgs *g, const PpoDev *P, hipStream_t s);
-int ppok_mlp_supported(const MlpArgs *g);
-int64_t ppok_mlp_frag_elems(int K, int N);
-void ppok_mlp_frag_build(const MlpArgs *g, hipStream_t s);
-void ppok_gemm_dw(const GemmArgs *g, int nz, hipStream_t s);
-void ppok_act_sample(const PpoDev *P, const float *obs, const float *cobs, const float *mu, const float *val, int t,
-                     int64_t cnt, int inject, hipStream_t s);
-void ppok_process_step(const PpoDev *P, const float *rew, const uint8_t *dones, const uint8_t *tos, int t, hipStream_t s);
-void ppok_gae(const PpoDev *P, const float *last_values, hipStream_t s);
-void ppok_det_fold(const PpoDev *P, hipStream_t s);
-void ppok_adv_normalize(const PpoDev *P, hipStream_t s);
-void ppok_gather(const PpoDev *P, int mb, hipStream_t s);
-void ppok_randperm(const PpoDev *P, int n, uint64_t update_idx, hipStream_t s);
-void ppok_loss(const PpoDev *P, const float *mu, const float *v, float *dmu, float *dval, hipStream_t s);
-int ppok_step(const PpoDev *P, int par, const PpoDev *G, int gather_mb, hipStream_t s);
-size_t ppok_head_part_floats();
-int ppok_head_fused(const PpoDev *P, int H3, const float *xa, const float *xc, float *dza, float *dzc, int64_t w_a, int64_t b_a,
-                    int64_t w_c, int64_t b_c, int64_t b_prev_a, int64_t b_prev_c, hipStream_t s);
-void ppok_lstm_fwd(const RnnStepArgs *a, int nz, hipStream_t s);
-void ppok_lstm_bwd(const RnnBwdArgs *a, int nz, hipStream_t s);
-void ppok_lstm_bias_grad(const PpoDev *P, const RnnBiasArgs *a, hipStream_t s);
-void ppok_lstm_reset(float *h0, float *c0, float *h1, float *c1, const uint8_t *done, int N, int H, hipStream_t s);
-}
-
-// LSTM front ends of a recurrent learner (lg_ppo_create_recurrent); H = 0 on a feed-forward one
-struct Rnn {
-    int H, mbs;                              // hidden size; envs per minibatch
-    int in_dim[2];                           // LSTM input width: num_obs, num_critic_obs
-    int64_t w_ih[2], w_hh[2], b_ih[2], b_hh[2];   // flat parameter offsets
-    float *h[2], *c[2];                      // live state (N, H)
-    float *sv_h[2], *sv_c[2];                // state before each rollout step (T, N, H)
-    float *tmp_h[2], *tmp_c[2];              // input copy of the live state for the steps outside the rollout (N, H)
-    // update workspace, rows t-major over the minibatch's envs (T x mbs)
-    float *pg[2];                            // x . W_ih^T + b_ih (forward), then dG (backward)   [R][4H]
-    float *hout[2], *cout[2], *hused[2], *cused[2], *dh[2];   // [R][H]
-    float *gates[2];                         // [R][4H]
-    float *dc[2];                            // [mbs][H]
-};
-
-struct Net {
-    int nl;                                  // linear layers (hidden + head)
-    int dims[LG_PPO_MAX_LAYERS + 1];         // dims[0] = input, dims[nl] = output
-    int64_t w_off[LG_PPO_MAX_LAYERS], b_off[LG_PPO_MAX_LAYERS];
-    int64_t pl_off[LG_PPO_MAX_LAYERS];       // offset of this layer's weight matrix inside a bf16 plane (multiple of 8)
-    int pl_ld0;                              // row length of W_0's plane image: dims[0] rounded up to 32 = one k-tile (pad columns zero)
-    float *act[LG_PPO_MAX_LAYERS + 1];       // act[l], l >= 1: output of layer l-1 (workspace, Mmax rows)
-    float *dz[LG_PPO_MAX_LAYERS + 1];        // gradient wrt act[l] pre-activation
-};
-
-struct lg_comm;
-struct lg_ctx;
-extern "C" {
-// env side of the fused rollout epilogue (env_api.hip; same library, not in the header)
-void lg_internal_defer_finalize(lg_ctx *c, int on);
-hipStream_t lg_internal_stream(lg_ctx *c);
-int lg_internal_finalize_pending(lg_ctx *c);
-const DevParams *lg_internal_take_finalize(lg_ctx *c, int64_t *counter);
-const DevParams *lg_internal_host_params(lg_ctx *c);
-int lg_finalize(lg_ctx *c);
-hipStream_t lg_comm_stream_(lg_comm *c);
-hipEvent_t lg_comm_event_(lg_comm *c);
-int lg_comm_group_allreduce_(lg_comm *c, float *const *bufs, const int64_t *counts, int n, hipStream_t s);
-int lg_comm_allreduce_sum(lg_comm *c, float *buf, int64_t n, void *stream);
-int lg_comm_broadcast(lg_comm *c, float *buf, int64_t n, int root, void *stream);
-}
-
-struct lg_ppo {
-    lg_comm *comm;                           // when set: gradients are reduced per layer inside the backward pass
-    hipEvent_t ev_bucket;                    // a layer's weight gradients are complete on the side stream
-    int comm_rc;
-    int comm_timing;                         // lg_ppo_comm_timing: event pairs around the wait for the last bucket
-    std::vector<hipEvent_t> comm_ev;         // [2 k], [2 k + 1]: before / after the wait of recorded minibatch k
-    size_t comm_ev_used;
-    lg_ppo_cfg cfg;
-    PpoDev dev;
-    Net net[2];                              // 0 actor, 1 critic
-    hipStream_t stream;
-    hipStream_t side;                        // weight-gradient GEMMs run here, overlapping the input-gradient chain
-    hipEvent_t ev_dz, ev_side;
-    int overlap;
-    long long *det_buf;                      // fixed-point shadow of the accumulators (lg_ppo_set_deterministic); dev.det64 = it when on
-    int act_code;                            // kernels' activation code = cfg.activation + 1 (0 is 'none')
-    int grads_dirty;
-    // fused rollout epilogue (lg_ppo_attach_env): a process_env_step recorded for the next act launch
-    lg_ctx *env;
-    int pp_pending, pp_t, pp_use_tos;
-    int params_dirty;                        // the fp32 parameters changed since the rollout images (fragment-order weights / bf16 planes)
-                                             // were derived from them: optimiser step, broadcast, lg_ppo_params_changed()
-    int fused_act;                           // rollout forward through k_mlp_fwd when the network shape allows (else per-layer GEMMs)
-    MlpArgs mlp;                             // its arguments (fragment-order weight image allocated at create)
-                         // gradients hold a backward pass that no optimiser step has consumed (and zeroed)
-    int step, inject;
-    int64_t act_count, update_count;
-    int Mmax;
-    std::vector<void *> allocs;
-    int64_t perm_count;                      // updates begun: keys the device-side minibatch permutation
-    // minibatch gathers are double-buffered: the optimiser step of minibatch mb gathers mb + 1 into the other set in the spare
-    // workgroups of its norm-reduction launch (the gather depends on the rollout storage and the permutation only).  A gather launch
-    // of its own before each minibatch: 0.474 / 0.485 ms per minibatch against 0.465 / 0.469, within that bench's noise (profiles/r02_ab.txt)
-    struct MbSet { float *obs, *critic_obs, *actions, *mu, *scalars; } mbset[2];
-    int mb_cur, mb_ready, mb_last;           // set the kernels read now; minibatch held by the other set (-1: none); last backward
-    lg_ppo_buffers pub;
-    Rnn rnn;
-};
-
-template <typename T>
-static bool palloc(lg_ppo *p, T **out, size_t n) {
-    void *q = nullptr;
-    size_t bytes = (n ? n : 1) * sizeof(T);
-    if (hipMalloc(&q, bytes) != hipSuccess || hipMemset(q, 0, bytes) != hipSuccess) return false;
-    p->allocs.push_back(q);
-    *out = (T *)q;
-    return true;
-}
-#define PA(ptr, n) do { if (!palloc(p, &(ptr), (n))) { lg_set_error("hipMalloc failed in lg_ppo_create"); lg_ppo_destroy(p); return -100; } } while (0)
-
-static int launch_ok() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { lg_set_error(std::string("ppo kernel launch: ") + hipGetErrorString(e)); return -100; }
-    return 0;
-}
-
-// forward of the selected nets on M rows.  in[z] = input of net z.  mask bit z selects the net.
-// in_pad: the inputs are the minibatch gathers, rows padded to a multiple of 32 floats (PpoDev::Op / OCp); otherwise rows of dims[0]
-static void forward(lg_ppo *p, int M, const float *in0, const float *in1, int mask, int skip_head = 0, bool planes = false,
-                    bool in_pad = false, hipStream_t on = nullptr, int l_begin = 0, int l_end = 1 << 30) {
-    const hipStream_t fs = on ? on : p->stream;
-    const float *in[2] = {in0, in1};
-    const int in_ld[2] = {in_pad ? p->dev.Op : p->net[0].dims[0], in_pad ? p->dev.OCp : p->net[1].dims[0]};
-    int sel[2], nz = 0;
-    for (int z = 0; z < 2; ++z) if (mask & (1 << z)) sel[nz++] = z;
-    const int nl = p->net[sel[0]].nl;
-    for (int l = l_begin; l < nl - skip_head && l < l_end; ++l) {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        for (int k = 0; k < nz; ++k) {
-            Net &n = p->net[sel[k]];
-            g.A[k] = l == 0 ? in[sel[k]] : n.act[l];
-            g.B[k] = p->dev.params + n.w_off[l];
-            g.bias[k] = p->dev.params + n.b_off[l];
-            g.Bpl[k] = planes ? p->dev.wpl + n.pl_off[l] : nullptr;      // valid only inside an update (lg_ppo_begin_update syncs them)
-            g.C[k] = n.act[l + 1];
-            g.M[k] = M; g.N[k] = n.dims[l + 1]; g.K[k] = n.dims[l];
-            g.lda[k] = l == 0 ? in_ld[sel[k]] : n.dims[l]; g.ldb[k] = n.dims[l]; g.ldc[k] = n.dims[l + 1];
-            // W_0's plane image has rows as long as the padded gather rows: with both padded the plane path reduces over whole chunks
-            if (l == 0 && in_pad && planes && n.pl_ld0 != n.dims[0]) { g.Kpl[k] = n.pl_ld0; g.ldbpl[k] = n.pl_ld0; }
-            else if (l == 0 && n.pl_ld0 != n.dims[0]) g.Bpl[k] = nullptr;   // unpadded input against padded plane rows: fp32 operand
-        }
-        g.elu = l < nl - 1 ? p->act_code : 0;
-        g.pl_stride = p->dev.pl_stride;
-        ppok_gemm_fwd(&g, nz, fs);
-    }
-}
-
-// Gradient bucket of layer l (both nets: W_l and b_l are adjacent in the flat buffer), all-reduced on the communicator's stream
-// as soon as the layer's weight-gradient GEMM is done.  b_l was summed by the input-gradient GEMM of layer l+1 (or by the loss
-// kernel for the head), which the weight-gradient GEMM of layer l already waited for.  The head's bucket also carries std and
-// the [KL sum | pad] tail.  The collectives of one bucket are one RCCL group.
-static int bucket_extents(lg_ppo *p, int l, float **bufs, int64_t *counts) {
-    int n = 0;
-    for (int z = 0; z < 2; ++z) {
-        Net &net = p->net[z];
-        bufs[n] = p->dev.grads + net.w_off[l];
-        counts[n++] = (int64_t)net.dims[l + 1] * net.dims[l] + net.dims[l + 1];
-    }
-    if (l == p->net[0].nl - 1) {
-        bufs[n] = p->dev.grads + p->dev.off_std; counts[n++] = p->cfg.num_actions;
-        bufs[n] = p->dev.grads + p->dev.num_params; counts[n++] = 2;
-    }
-    return n;
-}
-static void reduce_layer_bucket(lg_ppo *p, int l, hipStream_t ready_on) {
-    float *bufs[4];
-    int64_t counts[4];
-    const int n = bucket_extents(p, l, bufs, counts);
-    hipStream_t cs = lg_comm_stream_(p->comm);
-    (void)hipEventRecord(p->ev_bucket, ready_on);
-    (void)hipStreamWaitEvent(cs, p->ev_bucket, 0);
-    const int rc = lg_comm_group_allreduce_(p->comm, bufs, counts, n, cs);
-    if (rc && !p->comm_rc) p->comm_rc = rc;
-}
-
-// backward of both nets on M rows given dz[nl] (head output gradients) already filled
-static void backward(lg_ppo *p, int M, const float *in0, const float *in1, int skip_head = 0) {
-    const float *in[2] = {in0, in1};
-    auto det_args = [&](GemmArgs &g) {                // deterministic mode: gradient atomics go to the fixed-point shadow
-        g.det_base = p->dev.grads; g.det64 = p->dev.det64; g.det_n = p->dev.num_params + 2;
-    };
-    const int nl = p->net[0].nl;
-    for (int l = nl - 1 - skip_head; l >= 0; --l) {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        det_args(g);
-        for (int z = 0; z < 2; ++z) {                // dW_l += dz[l+1]^T . act[l]
-            Net &n = p->net[z];
-            g.A[z] = n.dz[l + 1]; g.lda[z] = n.dims[l + 1];
-            g.B[z] = l == 0 ? in[z] : n.act[l]; g.ldb[z] = n.dims[l];
-            g.C[z] = p->dev.grads + n.w_off[l]; g.ldc[z] = n.dims[l];
-            g.M[z] = n.dims[l + 1]; g.N[z] = n.dims[l]; g.K[z] = M;
-            if (l == 0 && !p->rnn.H) {               // the minibatch gathers: padded rows, the pad columns computed but not stored
-                const int ldp = z == 0 ? p->dev.Op : p->dev.OCp;
-                g.ldb[z] = ldp;
-                if (ldp != n.dims[0]) { g.N[z] = ldp; g.nstore[z] = n.dims[0]; }
-            }
-        }
-        // the weight gradient of layer l runs beside the input-gradient chain on the side stream -- except the last one
-        // (l = 0), which has nothing left to overlap with: on the main stream it starts without the cross-stream event wait
-        // (on the side stream: 0.479 / 0.490 ms per minibatch against 0.465 / 0.469, within that bench's noise: profiles/r02_ab.txt)
-        const bool on_side = p->overlap && l > 0;
-        hipStream_t dw_stream = on_side ? p->side : p->stream;
-        if (on_side) {                               // dz[l+1] is complete on the main stream at this point
-            (void)hipEventRecord(p->ev_dz, p->stream);
-            (void)hipStreamWaitEvent(p->side, p->ev_dz, 0);
-        }
-        ppok_gemm_dw(&g, 2, dw_stream);
-        if (p->comm) reduce_layer_bucket(p, l, dw_stream);
-        if (l > 0) {                                 // dz[l] = (dz[l+1] . W_l) * act'(act[l]); db_{l-1} = colsum(dz[l])
-            memset(&g, 0, sizeof(g));
-            det_args(g);
-            for (int z = 0; z < 2; ++z) {
-                Net &n = p->net[z];
-                g.A[z] = n.dz[l + 1]; g.lda[z] = n.dims[l + 1];
-                g.B[z] = p->dev.params + n.w_off[l]; g.ldb[z] = n.dims[l];
-                g.Bpl[z] = p->dev.wpl + n.pl_off[l];         // current inside an update (begin_update / k_opt_adam keep them)
-                g.C[z] = n.dz[l]; g.ldc[z] = n.dims[l];
-                g.aux[z] = n.act[l]; g.ldaux[z] = n.dims[l];
-                g.colsum[z] = p->dev.grads + n.b_off[l - 1];
-                g.M[z] = M; g.N[z] = n.dims[l]; g.K[z] = n.dims[l + 1];
-            }
-            g.elu = p->act_code;                         // derivative of the hidden activation, through its output act[l]
-            g.pl_stride = p->dev.pl_stride;
-            ppok_gemm_dx(&g, 2, p->stream);
-        }
-    }
-    if (p->rnn.H) {                                  // recurrent: dL/dh = dz[1] . W_0 (no activation derivative: h feeds W_0 directly)
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        for (int z = 0; z < 2; ++z) {
-            Net &n = p->net[z];
-            g.A[z] = n.dz[1]; g.lda[z] = n.dims[1];
-            g.B[z] = p->dev.params + n.w_off[0]; g.ldb[z] = n.dims[0];
-            g.Bpl[z] = p->dev.wpl + n.pl_off[0];
-            g.C[z] = p->rnn.dh[z]; g.ldc[z] = n.dims[0];
-            g.aux[z] = p->rnn.dh[z]; g.ldaux[z] = n.dims[0];   // read before written by the same lane; activation code 0 ignores it
-            g.M[z] = M; g.N[z] = n.dims[0]; g.K[z] = n.dims[1];
-        }
-        g.elu = 0;
-        g.pl_stride = p->dev.pl_stride;
-        ppok_gemm_dx(&g, 2, p->stream);
-    }
-    if (p->overlap) {                                // join: the optimiser step (main stream) needs every dW
-        (void)hipEventRecord(p->ev_side, p->side);
-        (void)hipStreamWaitEvent(p->stream, p->ev_side, 0);
-    }
-    if (p->comm) {                                   // ... and every reduced bucket
-        const bool rec = p->comm_timing && p->comm_ev_used + 2 <= 2 * 4096;
-        if (rec) {
-            while (p->comm_ev.size() < p->comm_ev_used + 2) { hipEvent_t e; (void)hipEventCreate(&e); p->comm_ev.push_back(e); }
-            (void)hipEventRecord(p->comm_ev[p->comm_ev_used], p->stream);
-        }
-        (void)hipEventRecord(lg_comm_event_(p->comm), lg_comm_stream_(p->comm));
-        (void)hipStreamWaitEvent(p->stream, lg_comm_event_(p->comm), 0);
-        if (rec) { (void)hipEventRecord(p->comm_ev[p->comm_ev_used + 1], p->stream); p->comm_ev_used += 2; }
-    }
-}
-
-// What a deferred process_env_step (and the env's epilogue before it) still owes, the ordinary way: env epilogue first, then the
-// process kernel on the refreshed extras["time_outs"] -- the order of the unfused loop.
-static void flush_rollout_epilogue(lg_ppo *p) {
-    if (!p->env) return;
-    (void)lg_finalize(p->env);
-    if (p->pp_pending) {
-        const lg_buffers &b = lg_internal_host_params(p->env)->buf;
-        ppok_process_step(&p->dev, b.rew, b.reset, p->pp_use_tos ? b.extras_time_outs : nullptr, p->pp_t, p->stream);
-        p->pp_pending = 0;
-    }
-}
-
-// ------------------------------------------------------------------ recurrent learner (ActorCriticRecurrent)
-static void rnn_net_params(lg_ppo *p, int z, RnnNetArgs &n) {
-    const Rnn &q = p->rnn;
-    n.Wih = p->dev.params + q.w_ih[z]; n.Whh = p->dev.params + q.w_hh[z];
-    n.bih = p->dev.params + q.b_ih[z]; n.bhh = p->dev.params + q.b_hh[z];
-}
-
-// one step of the selected memories (mask bit z) on all N envs from (tmp_h, tmp_c) or, at rollout step t >= 0, from the saved state
-// of step t; the new state goes to the live buffers
-static void rnn_live_step(lg_ppo *p, int mask, const float *x0, const float *x1, int t) {
-    Rnn &q = p->rnn;
-    const int N = p->cfg.num_envs, H = q.H;
-    RnnStepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.M = N; a.H = H; a.reload_all = 1;
-    const float *x[2] = {x0, x1};
-    int nz = 0;
-    for (int z = 0; z < 2; ++z) {
-        if (!(mask & (1 << z))) continue;
-        RnnNetArgs &n = a.n[nz++];
-        rnn_net_params(p, z, n);
-        n.X = x[z]; n.ldx = q.in_dim[z]; n.K = q.in_dim[z];
-        n.h_sv = t >= 0 ? q.sv_h[z] + (size_t)t * N * H : q.tmp_h[z];
-        n.c_sv = t >= 0 ? q.sv_c[z] + (size_t)t * N * H : q.tmp_c[z];
-        n.h_out = q.h[z]; n.c_out = q.c[z];
-    }
-    ppok_lstm_fwd(&a, nz, p->stream);
-}
-
-// copy the live state of the selected memories to the saved state of rollout step t (t < 0: to tmp)
-static void rnn_stash_live(lg_ppo *p, int mask, int t) {
-    Rnn &q = p->rnn;
-    const size_t nh = (size_t)p->cfg.num_envs * q.H;
-    for (int z = 0; z < 2; ++z) {
-        if (!(mask & (1 << z))) continue;
-        float *dh = t >= 0 ? q.sv_h[z] + (size_t)t * nh : q.tmp_h[z];
-        float *dc = t >= 0 ? q.sv_c[z] + (size_t)t * nh : q.tmp_c[z];
-        (void)hipMemcpyAsync(dh, q.h[z], nh * sizeof(float), hipMemcpyDeviceToDevice, p->stream);
-        (void)hipMemcpyAsync(dc, q.c[z], nh * sizeof(float), hipMemcpyDeviceToDevice, p->stream);
-    }
-}
-
-// update forward of minibatch mb: the input projection of all T x mbs rows in one GEMM, then T step launches
-static void rnn_forward_seq(lg_ppo *p, int mb) {
-    Rnn &q = p->rnn;
-    PpoDev &d = p->dev;
-    const int T = d.T, N = d.N, mbs = q.mbs, H = q.H, R = d.mb_rows, e0 = mb * mbs;
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    for (int z = 0; z < 2; ++z) {
-        g.A[z] = z ? d.mb_critic_obs : d.mb_obs; g.lda[z] = z ? d.OCp : d.Op;
-        g.B[z] = d.params + q.w_ih[z]; g.ldb[z] = q.in_dim[z];
-        g.bias[z] = d.params + q.b_ih[z];
-        g.C[z] = q.pg[z]; g.ldc[z] = 4 * H;
-        g.M[z] = R; g.N[z] = 4 * H; g.K[z] = q.in_dim[z];
-    }
-    g.elu = 0;
-    ppok_gemm_fwd(&g, 2, p->stream);
-    for (int t = 0; t < T; ++t) {
-        RnnStepArgs a;
-        memset(&a, 0, sizeof(a));
-        a.M = mbs; a.H = H;
-        a.reload_all = t == 0;
-        a.reload = t ? d.st_dones + (size_t)(t - 1) * N + e0 : nullptr;
-        for (int z = 0; z < 2; ++z) {
-            RnnNetArgs &n = a.n[z];
-            rnn_net_params(p, z, n);
-            const size_t r0 = (size_t)t * mbs, rp = (size_t)(t ? t - 1 : 0) * mbs;
-            n.P = q.pg[z] + r0 * 4 * H; n.ldp = 4 * H;
-            n.h_prev = t ? q.hout[z] + rp * H : nullptr; n.c_prev = t ? q.cout[z] + rp * H : nullptr;
-            n.h_sv = q.sv_h[z] + ((size_t)t * N + e0) * H; n.c_sv = q.sv_c[z] + ((size_t)t * N + e0) * H;
-            n.h_out = q.hout[z] + r0 * H; n.c_out = q.cout[z] + r0 * H;
-            n.gates = q.gates[z] + r0 * 4 * H;
-            n.h_used = q.hused[z] + r0 * H; n.c_used = q.cused[z] + r0 * H;
-        }
-        ppok_lstm_fwd(&a, 2, p->stream);
-    }
-}
-
-// update backward of minibatch mb, after the MLP backward left dL/dh in rnn.dh: T step launches back through time, then the
-// weight gradients over all T x mbs rows (dW_ih = dG^T X, dW_hh = dG^T h_used, db_ih = db_hh = colsum dG)
-static void rnn_backward_seq(lg_ppo *p, int mb) {
-    Rnn &q = p->rnn;
-    PpoDev &d = p->dev;
-    const int T = d.T, N = d.N, mbs = q.mbs, H = q.H, R = d.mb_rows, e0 = mb * mbs;
-    for (int z = 0; z < 2; ++z) (void)hipMemsetAsync(q.dc[z], 0, (size_t)mbs * H * sizeof(float), p->stream);
-    for (int t = T - 1; t >= 0; --t) {
-        RnnBwdArgs a;
-        memset(&a, 0, sizeof(a));
-        a.M = mbs; a.H = H;
-        a.cut_next = t < T - 1 ? d.st_dones + (size_t)t * N + e0 : nullptr;
-        a.cut = t ? d.st_dones + (size_t)(t - 1) * N + e0 : nullptr;
-        a.cut_all = t == 0;
-        for (int z = 0; z < 2; ++z) {
-            RnnBwdNet &n = a.n[z];
-            const size_t r0 = (size_t)t * mbs;
-            n.dG_next = t < T - 1 ? q.pg[z] + (r0 + mbs) * 4 * H : nullptr;
-            n.Whh = d.params + q.w_hh[z];
-            n.dh_mlp = q.dh[z] + r0 * H;
-            n.dc = q.dc[z];
-            n.gates = q.gates[z] + r0 * 4 * H; n.c_t = q.cout[z] + r0 * H; n.c_used = q.cused[z] + r0 * H;
-            n.dG = q.pg[z] + r0 * 4 * H;
-        }
-        ppok_lstm_bwd(&a, 2, p->stream);
-    }
-    for (int w = 0; w < 2; ++w) {                   // 0: W_ih against the gathered inputs, 1: W_hh against the states used
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.det_base = d.grads; g.det64 = d.det64; g.det_n = d.num_params + 2;
-        for (int z = 0; z < 2; ++z) {
-            g.A[z] = q.pg[z]; g.lda[z] = 4 * H;
-            g.M[z] = 4 * H; g.K[z] = R;
-            if (w == 0) {
-                const int ldp = z ? d.OCp : d.Op;
-                g.B[z] = z ? d.mb_critic_obs : d.mb_obs; g.ldb[z] = ldp;
-                g.C[z] = d.grads + q.w_ih[z]; g.ldc[z] = q.in_dim[z];
-                g.N[z] = ldp;
-                if (ldp != q.in_dim[z]) g.nstore[z] = q.in_dim[z];
-            } else {
-                g.B[z] = q.hused[z]; g.ldb[z] = H;
-                g.C[z] = d.grads + q.w_hh[z]; g.ldc[z] = H;
-                g.N[z] = H;
-            }
-        }
-        ppok_gemm_dw(&g, 2, p->stream);
-    }
-    RnnBiasArgs b;
-    memset(&b, 0, sizeof(b));
-    b.M = R; b.H = H;
-    for (int z = 0; z < 2; ++z) { b.dG[z] = q.pg[z]; b.db_ih[z] = d.grads + q.b_ih[z]; b.db_hh[z] = d.grads + q.b_hh[z]; }
-    ppok_lstm_bias_grad(&d, &b, p->stream);
-}
+#include "ppo_learner.h"
 
 extern "C" {
 
 int lg_ppo_destroy(lg_ppo *p) {
     if (!p) return 0;
-    if (p->env) { flush_rollout_epilogue(p); lg_internal_defer_finalize(p->env, 0); p->env = nullptr; }
+    if (p->env) { sched::flush_rollout_epilogue(p); lg_internal_defer_finalize(p->env, 0); p->env = nullptr; }
     if (p->side) { (void)hipStreamSynchronize(p->side); (void)hipStreamDestroy(p->side); }
     if (p->ev_dz) (void)hipEventDestroy(p->ev_dz);
     if (p->ev_side) (void)hipEventDestroy(p->ev_side);
@@ -460,8 +39,6 @@ static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **
     }
     lg_ppo *p = new lg_ppo();
     p->cfg = *cfg;
-    memset(&p->rnn, 0, sizeof(p->rnn));
-    p->stream = nullptr;
     p->act_code = cfg->activation + 1;
     p->fused_act = getenv("LG_FUSED_ACT") ? atoi(getenv("LG_FUSED_ACT")) : 1;   // one-launch rollout forward (ppo_mlp_fused.hip) when the shape allows
     p->overlap = getenv("LG_PPO_OVERLAP") ? atoi(getenv("LG_PPO_OVERLAP")) : 1;
@@ -471,17 +48,12 @@ static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **
         hipEventCreateWithFlags(&p->ev_bucket, hipEventDisableTiming) != hipSuccess) {
         lg_set_error("stream/event creation failed"); delete p; return -100;
     }
-    p->step = 0; p->inject = 0; p->act_count = 0; p->update_count = 0; p->params_dirty = 1;
-    p->comm = nullptr; p->comm_rc = 0; p->comm_timing = 0; p->comm_ev_used = 0;
-    p->env = nullptr; p->pp_pending = 0;
-    p->perm_count = 0;
     const int R = (int)((long)N * T / cfg->num_mini_batches);
     p->Mmax = R > N ? R : N;
 
     // parameter layout: std, actor (W,b)*, critic (W,b)*  -- the order of ActorCritic.parameters()
     int64_t off = 0;
     PpoDev &d = p->dev;
-    memset(&d, 0, sizeof(d));
     d.off_std = (int)off; off += A;
     for (int z = 0; z < 2; ++z) {
         Net &n = p->net[z];
@@ -562,9 +134,7 @@ static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **
         if (cfg->num_critic_obs > 0) PA(m.critic_obs, (size_t)R * d.OCp); else m.critic_obs = m.obs;
         PA(m.actions, (size_t)R * A); PA(m.mu, (size_t)R * A); PA(m.scalars, (size_t)R * 4);
     }
-    p->mb_cur = 0; p->mb_ready = -1; p->mb_last = -1;
-    d.mb_obs = p->mbset[0].obs; d.mb_critic_obs = p->mbset[0].critic_obs; d.mb_actions = p->mbset[0].actions;
-    d.mb_mu = p->mbset[0].mu; d.mb_scalars = p->mbset[0].scalars;
+    use_mb_set(d, p->mbset[p->mb_cur]);
     PA(d.head_part, ppok_head_part_floats());
     PA(d.cur_reward_sum, N); PA(d.cur_episode_len, N); PA(d.ep_stats, 4); PA(d.ep_ring, 200); PA(d.ep_ring_count, 1);
     for (int z = 0; z < 2; ++z) {
@@ -592,7 +162,6 @@ static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **
     }
     if (p->fused_act) {                                         // arguments + weight image of the one-launch rollout forward
         MlpArgs &g = p->mlp;
-        memset(&g, 0, sizeof(g));
         g.params = d.params; g.M = N; g.nl = p->net[0].nl; g.act = p->act_code;
         int64_t tot = 0;
         if (p->net[0].nl != p->net[1].nl) p->fused_act = 0;
@@ -614,7 +183,6 @@ static int ppo_create(const lg_ppo_cfg *cfg, const lg_ppo_rnn_cfg *rc, lg_ppo **
         (void)hipMemcpy(d.stats, &lr, sizeof(float), hipMemcpyHostToDevice);
     }
     lg_ppo_buffers &b = p->pub;
-    memset(&b, 0, sizeof(b));
     b.params = d.params; b.grads = d.grads; b.adam_m = d.adam_m; b.adam_v = d.adam_v;
     b.obs = d.st_obs; b.critic_obs = d.st_critic_obs; b.actions = d.st_actions; b.rewards = d.st_rewards;
     b.values = d.st_values; b.returns = d.st_returns; b.advantages = d.st_adv; b.log_prob = d.st_log_prob;
@@ -644,7 +212,7 @@ int lg_ppo_get_rnn_buffers(lg_ppo *p, lg_ppo_rnn_buffers *out) {
 }
 int lg_ppo_reset_hidden(lg_ppo *p, const uint8_t *dones) {
     if (!p->rnn.H) { lg_set_error("lg_ppo_reset_hidden: not a recurrent learner"); return -15; }
-    flush_rollout_epilogue(p);
+    sched::flush_rollout_epilogue(p);
     const Rnn &q = p->rnn;
     ppok_lstm_reset(q.h[0], q.c[0], q.h[1], q.c[1], dones, p->cfg.num_envs, q.H, p->stream);
     return launch_ok();
@@ -681,7 +249,7 @@ int lg_ppo_param_layout(lg_ppo *p, int64_t *offsets, int64_t *shapes, int max_en
 }
 
 int lg_ppo_attach_env(lg_ppo *p, lg_ctx *env) {
-    flush_rollout_epilogue(p);
+    sched::flush_rollout_epilogue(p);
     if (p->env) lg_internal_defer_finalize(p->env, 0);
     p->env = nullptr;
     if (env) {
@@ -719,7 +287,7 @@ int lg_ppo_act(lg_ppo *p, const float *obs, const float *critic_obs) {
             g.pp_t = p->pp_t; g.pp_use_tos = p->pp_use_tos;
             g.pp_env = lg_internal_take_finalize(p->env, &g.pp_counter);
             p->pp_pending = 0;
-        } else flush_rollout_epilogue(p);
+        } else sched::flush_rollout_epilogue(p);
         fused = ppok_mlp_fwd(&g, &p->dev, p->stream);
         if (fused != 0 && g.pp) { lg_set_error("fused act launch refused with a rollout epilogue attached"); return -13; }
         if (fused == 0) {                                                         // sampled and stored by the same launch
@@ -729,17 +297,19 @@ int lg_ppo_act(lg_ppo *p, const float *obs, const float *critic_obs) {
             return rc;
         }
     }
-    if (!p->fused_act) flush_rollout_epilogue(p);
+    if (!p->fused_act) sched::flush_rollout_epilogue(p);
     if (fused != 0) {
         // per-layer GEMMs on the optimiser's weight planes (no re-split of W per tile); same freshness rule as above
         if (dirty) ppok_sync_planes(&p->dev, p->stream);
         const float *in0 = obs, *in1 = cobs;
         if (p->rnn.H) {                          // the transition keeps the state before the step; both memories advance
-            rnn_stash_live(p, 3, p->step);
-            rnn_live_step(p, 3, obs, cobs, p->step);
+            sched::rnn_stash_live(p, 3, p->step);
+            sched::rnn_live_step(p, 3, obs, cobs, p->step);
             in0 = p->rnn.h[0]; in1 = p->rnn.h[1];
         }
-        forward(p, p->cfg.num_envs, in0, in1, 3, 0, true);
+        sched::FwdOpts fo{};
+        fo.planes = true;
+        sched::forward(p, p->cfg.num_envs, in0, in1, 3, fo);
     }
     ppok_act_sample(&p->dev, obs, cobs, p->net[0].act[p->net[0].nl], p->net[1].act[p->net[1].nl], p->step, p->act_count,
                     p->inject, p->stream);
@@ -759,7 +329,7 @@ int lg_ppo_process_env_step(lg_ppo *p, const float *rew, const uint8_t *dones, c
             p->step++;
             return 0;
         }
-        flush_rollout_epilogue(p);
+        sched::flush_rollout_epilogue(p);
     }
     ppok_process_step(&p->dev, rew, dones, time_outs, p->step, p->stream);
     if (p->rnn.H) ppok_lstm_reset(p->rnn.h[0], p->rnn.c[0], p->rnn.h[1], p->rnn.c[1], dones, p->cfg.num_envs, p->rnn.H, p->stream);
@@ -768,13 +338,13 @@ int lg_ppo_process_env_step(lg_ppo *p, const float *rew, const uint8_t *dones, c
 }
 
 int lg_ppo_compute_returns(lg_ppo *p, const float *last_critic_obs) {
-    flush_rollout_epilogue(p);
+    sched::flush_rollout_epilogue(p);
     if (p->rnn.H) {                              // rsl_rl's evaluate() advances memory_c once more on the last observations
-        rnn_stash_live(p, 2, -1);
-        rnn_live_step(p, 2, nullptr, last_critic_obs, -1);
-        forward(p, p->cfg.num_envs, nullptr, p->rnn.h[1], 2);
+        sched::rnn_stash_live(p, 2, -1);
+        sched::rnn_live_step(p, 2, nullptr, last_critic_obs, -1);
+        sched::forward(p, p->cfg.num_envs, nullptr, p->rnn.h[1], 2);
     } else
-        forward(p, p->cfg.num_envs, nullptr, last_critic_obs, 2);
+        sched::forward(p, p->cfg.num_envs, nullptr, last_critic_obs, 2);
     ppok_gae(&p->dev, p->net[1].act[p->net[1].nl], p->stream);
     return launch_ok();
 }
@@ -792,7 +362,7 @@ static int rnn_update_refused(const lg_ppo *p) {
 
 int lg_ppo_begin_update(lg_ppo *p) {
     if (rnn_update_refused(p)) return -6;
-    flush_rollout_epilogue(p);
+    sched::flush_rollout_epilogue(p);
     // randperm(num_mini_batches * mini_batch_size), drawn once per update and reused by every epoch (Appendix B): on the device
     const size_t n = (size_t)p->dev.mb_rows * p->cfg.num_mini_batches;
     if (!p->rnn.H) ppok_randperm(&p->dev, (int)n, (uint64_t)p->perm_count++, p->stream);   // recurrent: the fixed table of create
@@ -813,13 +383,9 @@ int lg_ppo_minibatch_backward(lg_ppo *p, int epoch, int mb) {
     // k_opt_adam leaves the gradient buffer zeroed; only a backward pass that was never stepped needs a clear
     if (p->grads_dirty) (void)hipMemsetAsync(d.grads, 0, (size_t)(d.num_params + 2) * sizeof(float), p->stream);
     p->grads_dirty = 1;
-    auto use_set = [&](PpoDev &dev, int k) {
-        const lg_ppo::MbSet &m = p->mbset[k];
-        dev.mb_obs = m.obs; dev.mb_critic_obs = m.critic_obs; dev.mb_actions = m.actions; dev.mb_mu = m.mu; dev.mb_scalars = m.scalars;
-    };
     if (p->mb_ready == mb) {                                    // gathered ahead by the previous optimiser step
         p->mb_cur ^= 1;
-        use_set(d, p->mb_cur);
+        use_mb_set(d, p->mbset[p->mb_cur]);
     } else {
         ppok_gather(&d, mb, p->stream);
     }
@@ -832,23 +398,25 @@ int lg_ppo_minibatch_backward(lg_ppo *p, int epoch, int mb) {
     // at 128 wide the fused head was 18 us slower per minibatch while the weight-gradient stream had slack; with that stream the
     // long pole (profiles/r02_timelines.txt) it is 9 us faster than head GEMM + k_loss + two head-gradient GEMMs (A/B on one box)
     const bool fuse = p->act_code == 1 && nl >= 2 && nc.dims[nl - 1] == H3 && (H3 == 128 || H3 == 64 || H3 == 32);
+    sched::FwdOpts fo{};
+    fo.skip_head = fuse; fo.planes = true; fo.in_pad = !p->rnn.H;       // the LSTM's output rows are not padded, the gathers are
     if (p->rnn.H) {
-        rnn_forward_seq(p, mb);
-        forward(p, R, p->rnn.hout[0], p->rnn.hout[1], 3, fuse ? 1 : 0, true, false);
+        sched::rnn_forward_seq(p, mb);
+        sched::forward(p, R, p->rnn.hout[0], p->rnn.hout[1], 3, fo);
     } else
-        forward(p, R, d.mb_obs, d.mb_critic_obs, 3, fuse ? 1 : 0, true, true);
+        sched::forward(p, R, d.mb_obs, d.mb_critic_obs, 3, fo);
     if (fuse) {
         ppok_head_fused(&d, H3, na.act[nl - 1], nc.act[nl - 1], na.dz[nl - 1], nc.dz[nl - 1], na.w_off[nl - 1], na.b_off[nl - 1],
                         nc.w_off[nl - 1], nc.b_off[nl - 1], na.b_off[nl - 2], nc.b_off[nl - 2], p->stream);
     } else {
         ppok_loss(&d, na.act[na.nl], nc.act[nc.nl], na.dz[na.nl], nc.dz[nc.nl], p->stream);
     }
-    if (fuse && p->comm) reduce_layer_bucket(p, nl - 1, p->stream);   // the fused head produced the head layer's gradients itself
+    if (fuse && p->comm) sched::reduce_layer_bucket(p, nl - 1, p->stream);   // the fused head produced the head layer's gradients itself
     if (p->rnn.H) {
-        backward(p, R, p->rnn.hout[0], p->rnn.hout[1], fuse ? 1 : 0);
-        rnn_backward_seq(p, mb);
+        sched::backward(p, R, p->rnn.hout[0], p->rnn.hout[1], fuse);
+        sched::rnn_backward_seq(p, mb);
     } else
-        backward(p, R, d.mb_obs, d.mb_critic_obs, fuse ? 1 : 0);
+        sched::backward(p, R, d.mb_obs, d.mb_critic_obs, fuse);
     if (d.det64) ppok_det_fold(&d, p->stream);       // gradients, KL sum and loss sums of this minibatch, order-independent
     if (p->comm_rc) { const int rc = p->comm_rc; p->comm_rc = 0; return rc; }
     return launch_ok();
@@ -860,8 +428,7 @@ int lg_ppo_minibatch_step(lg_ppo *p) {
     if (p->cfg.num_mini_batches > 1 && p->mb_last >= 0) {
         // the next minibatch of the generator's order (the permutation is fixed for the whole update)
         next = (p->mb_last + 1) % p->cfg.num_mini_batches;
-        const lg_ppo::MbSet &m = p->mbset[p->mb_cur ^ 1];
-        other.mb_obs = m.obs; other.mb_critic_obs = m.critic_obs; other.mb_actions = m.actions; other.mb_mu = m.mu; other.mb_scalars = m.scalars;
+        use_mb_set(other, p->mbset[p->mb_cur ^ 1]);
     }
     if (ppok_step(&p->dev, (int)(p->update_count & 1), &other, next, p->stream)) p->mb_ready = next;
     p->mb_last = -1;
@@ -915,12 +482,12 @@ int lg_ppo_set_deterministic(lg_ppo *p, int on) {
     return launch_ok();
 }
 
-// The extents reduce_layer_bucket() hands to RCCL for layer l, as offsets into the flat gradient buffer (host-side, for tests:
+// The extents sched::reduce_layer_bucket() hands to RCCL for layer l, as offsets into the flat gradient buffer (host-side, for tests:
 // the buckets of all layers must tile [0, num_reduce) exactly once).  Returns the number of extents (<= 4).
 int lg_ppo_debug_bucket_extents(lg_ppo *p, int l, int64_t *offsets, int64_t *counts) {
     if (l < 0 || l >= p->net[0].nl) return -1;
     float *bufs[4];
-    const int n = bucket_extents(p, l, bufs, counts);
+    const int n = sched::bucket_extents(p, l, bufs, counts);
     for (int k = 0; k < n; ++k) offsets[k] = bufs[k] - p->dev.grads;
     return n;
 }
@@ -951,11 +518,11 @@ int lg_ppo_act_inference(lg_ppo *p, const float *obs, float *actions_out, int64_
     if (rows > p->Mmax) { lg_set_error("too many rows for act_inference"); return -11; }
     if (p->rnn.H) {                              // rsl_rl's act_inference advances memory_a
         if (rows != p->cfg.num_envs) { lg_set_error("act_inference of a recurrent learner takes exactly num_envs rows"); return -11; }
-        rnn_stash_live(p, 1, -1);
-        rnn_live_step(p, 1, obs, nullptr, -1);
+        sched::rnn_stash_live(p, 1, -1);
+        sched::rnn_live_step(p, 1, obs, nullptr, -1);
         obs = p->rnn.h[0];
     }
-    forward(p, (int)rows, obs, nullptr, 1);
+    sched::forward(p, (int)rows, obs, nullptr, 1);
     Net &na = p->net[0];
     if (hipMemcpyAsync(actions_out, na.act[na.nl], (size_t)rows * p->cfg.num_actions * sizeof(float), hipMemcpyDeviceToDevice,
                        p->stream) != hipSuccess) { lg_set_error("copy failed"); return -100; }

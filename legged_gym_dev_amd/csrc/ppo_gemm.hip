@@ -4,7 +4,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "ppo_device.h"
+#include "ppo_launch.h"
 #include "ppo_split_bf16.h"
 
 // XCD-aware workgroup -> tile map.  The 8 XCDs of an MI355X have private L2s and workgroups are dealt to them round-robin by

@@ -3,7 +3,7 @@
 // (SURVEY.md Appendix B -- third-party, not in the reference tree; call sites legged_gym/utils/task_registry.py:148-155).
 #include <type_traits>
 
-#include "ppo_device.h"
+#include "ppo_launch.h"
 #include "ppo_split_bf16.h"
 
 // ------------------------------------------------------------------------------------------------

@@ -9,8 +9,7 @@
 // come straight from the optimiser's bf16 weight planes in L2 (W [n][k]: 16 B per lane per plane, two k-steps
 // prefetched), six v_mfma_f32_32x32x16_bf16 per fp32 product block as in k_gemm.  Bias + activation in registers,
 // result back to LDS for the next layer; the head outputs (means, value) stay in LDS for the sampling epilogue.
-#include "ppo_device.h"
-#include "ppo_mlp_args.h"
+#include "ppo_launch.h"
 #include "lg_finalize.h"
 #include "ppo_split_bf16.h"
 

@@ -4,8 +4,7 @@
 // tiles -- exact fp32 products, the same standard as the MLP's split-bf16 / fp32-MFMA GEMMs.  Each workgroup owns hidden units j
 // and all four gate columns of them, so the LSTM cell (forward) and its derivative (backward) are the GEMM's epilogue.
 // Host side: ppo_api.hip (lg_ppo_create_recurrent).  DESIGN.md "Recurrent policy" has the schedule.
-#include "ppo_device.h"
-#include "ppo_rnn.h"
+#include "ppo_launch.h"
 
 #define RB_M 64                  // rows per workgroup
 #define RB_K 32                  // reduction chunk staged in LDS

@@ -7,16 +7,7 @@
 #include <string>
 
 #include "privobs_device.h"
-
-void lg_set_error(const std::string &s);
-
-struct lg_ctx;
-extern "C" {
-void privobsk_launch(const PrivObsDev *D, hipStream_t st);
-// env_api.hip; same library, not in the header
-hipStream_t lg_internal_stream(lg_ctx *c);
-const DevParams *lg_internal_host_params(lg_ctx *c);
-}
+#include "lg_internal.h"
 
 struct lg_priv_obs {
     PrivObsDev dev;                     // the env's pointers in it are filled per call

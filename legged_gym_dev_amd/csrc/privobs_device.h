@@ -21,3 +21,7 @@ struct PrivObsDev {                     // passed by value to the kernel: the te
     float default_dof_pos[LG_MAX_DOF];
     PrivTermDev terms[LG_PRIV_MAX_TERMS];
 };
+
+extern "C" {
+void privobsk_launch(const PrivObsDev *D, hipStream_t st);
+}

@@ -7,18 +7,7 @@
 #include <string>
 
 #include "romsim_device.h"
-
-void lg_set_error(const std::string &s);
-
-extern "C" {
-void romsimk_reset(const RomSimDev *D, int64_t epoch, int construct, hipStream_t st);
-void romsimk_step(const RomSimDev *D, int64_t epoch, const float *actions, hipStream_t st);
-void romsimk_policy(const RomSimDev *D, const float *obs, float *out, int64_t rows, hipStream_t st);
-void romsimk_collect(const RomSimDev *D, int64_t epoch, int construct, int T, int max_sub, float *z, float *v, float *pz,
-                     uint8_t *done, float *x, hipStream_t st);
-void romsimk_plan_track(const RomSimDev *D, const float *z, const float *v, const float *x0, int64_t B, int N, int S, float rom_dt,
-                        float *pz, float *wt, float *x, float *u, hipStream_t st);
-}
+#include "lg_internal.h"
 
 struct lg_romsim {
     lg_romsim_cfg cfg;

@@ -17,3 +17,13 @@ struct RomSimDev {                      // passed by value to kernels
     float vel_min[2], vel_max[2], acc_min[2], acc_max[2];
     float noise_lo[4], noise_hi[4], max_dist[2];
 };
+
+extern "C" {
+void romsimk_reset(const RomSimDev *D, int64_t epoch, int construct, hipStream_t st);
+void romsimk_step(const RomSimDev *D, int64_t epoch, const float *actions, hipStream_t st);
+void romsimk_policy(const RomSimDev *D, const float *obs, float *out, int64_t rows, hipStream_t st);
+void romsimk_collect(const RomSimDev *D, int64_t epoch, int construct, int T, int max_sub, float *z, float *v, float *pz,
+                     uint8_t *done, float *x, hipStream_t st);
+void romsimk_plan_track(const RomSimDev *D, const float *z, const float *v, const float *x0, int64_t B, int N, int S, float rom_dt,
+                        float *pz, float *wt, float *x, float *u, hipStream_t st);
+}

@@ -3,10 +3,8 @@
 // and the four passes of select_kernels.hip on the given stream and wait for nothing.
 #include <string>
 
-#include "../../include/legged_hip.h"
+#include "lg_internal.h"
 #include "select_device.h"
-
-void lg_set_error(const std::string &s);
 
 static bool refuse(const char *who, const std::string &e) {
     if (!e.empty()) lg_set_error(std::string(who) + ": " + e);

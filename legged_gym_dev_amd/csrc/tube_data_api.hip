@@ -3,10 +3,8 @@
 // wait for nothing.
 #include <string>
 
-#include "../../include/legged_hip.h"
+#include "lg_internal.h"
 #include "tube_data_device.h"
-
-void lg_set_error(const std::string &s);
 
 static const int64_t TD_MAX_T = (int64_t)1 << 24;
 

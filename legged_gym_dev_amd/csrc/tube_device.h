@@ -50,3 +50,32 @@ struct TubeMember {                     // one model of a sweep (lg_tube_sweep);
     double lr0, gamma;                  // its Adam rate and StepLR schedule
     int64_t step_size;
 };
+
+extern "C" {
+// tube_kernels.hip
+size_t tubek_lds_bytes(const TubeDev *D);
+int tubek_init();
+void tubek_step(const TubeDev *D, const TubeSplit *S, const int32_t *rows, int64_t count, uint64_t key, float norm, hipStream_t s);
+void tubek_adam(const TubeDev *D, int nwg, int64_t t, double lr0, double gamma, int64_t step_size, float norm, int64_t rows,
+                hipStream_t s);
+void tubek_eval(const TubeDev *D, const TubeSplit *S, const int32_t *rows, uint64_t key, float norm, float level, hipStream_t s);
+void tubek_wt(const TubeDev *D, hipStream_t s);
+void tubek_perm(const TubeDev *D, int n, uint64_t epoch, hipStream_t s);
+void tubek_iota(int32_t *p, int64_t n, hipStream_t s);
+void tubek_step_sweep(const TubeMember *M, int K, const TubeDev *D0, const TubeSplit *S, const int32_t *rows, int64_t pos, int64_t count,
+                      uint64_t key, float norm, hipStream_t s);
+void tubek_adam_sweep(const TubeMember *M, int K, const TubeDev *D0, int nwg, int64_t t, float norm, int64_t rows, hipStream_t s);
+void tubek_eval_sweep(const TubeMember *M, int K, const TubeDev *D0, const TubeSplit *S, const int32_t *rows, uint64_t key, float norm,
+                      float level, hipStream_t s);
+void tubek_predict_levels(const TubeDev *D, const float *x, const int32_t *rows, int64_t count, const float *levels, int n_levels,
+                          float *o, hipStream_t s);
+void tubek_predict_windows_levels(const TubeDev *D, const float *w, const float *z, const float *v, const int32_t *env,
+                                  const int32_t *start, int T, int nz, int m, int64_t count, const float *levels, int n_levels,
+                                  float *o, hipStream_t s);
+void tubek_perm_sweep(const TubeMember *M, int K, int n, uint64_t epoch, hipStream_t s);
+void tubek_predict(const TubeDev *D, const float *x, const float *y, const float *v, const int32_t *rows, const int32_t *env,
+                   const int32_t *start, int T, int nz, int m, int64_t count, float *o, hipStream_t s);
+void tubek_rollout(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, const uint8_t *reseed, float *o, hipStream_t s);
+void tubek_rollout_window(const TubeDev *D, const float *x, int64_t n_seq, int T, int fb, int taps, int dN, int stride,
+                          const uint8_t *reseed, float *o, hipStream_t s);
+}

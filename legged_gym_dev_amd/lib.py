@@ -38,43 +38,14 @@ def load():
                 "(there is no CPU fallback for the product path)")
         _lib = C.CDLL(SO_PATH)
         capi.declare_env_api(_lib, prefix="lg_")
-        _declare_ppo(_lib)
+        capi.declare_ppo_api(_lib)
+        capi.declare_comm_api(_lib)
         capi.declare_tube_api(_lib)
         capi.declare_romsim_api(_lib)
         capi.declare_tube_data_api(_lib)
         capi.declare_select_api(_lib)
         capi.declare_plan_api(_lib)
     return _lib
-
-
-def _declare_ppo(lib):
-    vp = C.c_void_p
-    if not hasattr(lib, "lg_ppo_create"):
-        return
-    lib.lg_ppo_create.argtypes = [C.POINTER(capi.lg_ppo_cfg), C.POINTER(vp)]
-    lib.lg_ppo_destroy.argtypes = [vp]
-    lib.lg_ppo_get_buffers.argtypes = [vp, C.POINTER(capi.lg_ppo_buffers)]
-    lib.lg_ppo_set_stream.argtypes = [vp, vp]
-    lib.lg_ppo_param_layout.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]
-    lib.lg_ppo_inject_noise.argtypes = [vp, C.c_int]
-    lib.lg_ppo_act.argtypes = [vp, vp, vp]
-    lib.lg_ppo_process_env_step.argtypes = [vp, vp, vp, vp]
-    lib.lg_ppo_compute_returns.argtypes = [vp, vp]
-    lib.lg_ppo_normalize_advantages.argtypes = [vp]
-    lib.lg_ppo_begin_update.argtypes = [vp]
-    lib.lg_ppo_minibatch_backward.argtypes = [vp, C.c_int, C.c_int]
-    lib.lg_ppo_minibatch_step.argtypes = [vp]
-    lib.lg_ppo_end_update.argtypes = [vp]
-    lib.lg_ppo_act_inference.argtypes = [vp, vp, vp, C.c_int64]
-    lib.lg_ppo_params_changed.argtypes = [vp]
-    lib.lg_ppo_set_deterministic.argtypes = [vp, C.c_int]
-    lib.lg_ppo_attach_env.argtypes = [vp, vp]
-    lib.lg_ppo_create_recurrent.argtypes = [C.POINTER(capi.lg_ppo_cfg), C.POINTER(capi.lg_ppo_rnn_cfg), C.POINTER(vp)]
-    lib.lg_ppo_get_rnn_buffers.argtypes = [vp, C.POINTER(capi.lg_ppo_rnn_buffers)]
-    lib.lg_ppo_reset_hidden.argtypes = [vp, vp]
-    lib.lg_ppo_debug_bucket_extents.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.lg_ppo_debug_mb_sets.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
-    lib.lg_ppo_debug_weight_planes.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(vp)]
 
 
 _TORCH_DT = {"f4": "float32", "u1": "uint8", "i8": "int64", "i4": "int32"}

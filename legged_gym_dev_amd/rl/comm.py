@@ -43,17 +43,10 @@ class NativeComm:
     def __init__(self, rank, world_size, unique_id=None, store=None):
         self.lib = load()
         self.rank, self.world_size = int(rank), int(world_size)
-        vp = C.c_void_p
-        self.lib.lg_comm_get_unique_id.argtypes = [vp]
-        self.lib.lg_comm_init.argtypes = [C.c_int, C.c_int, vp, C.POINTER(vp)]
-        self.lib.lg_comm_destroy.argtypes = [vp]
-        self.lib.lg_comm_allreduce_sum.argtypes = [vp, vp, C.c_int64, vp]
-        self.lib.lg_comm_broadcast.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
-        self.lib.lg_ppo_set_comm.argtypes = [vp, vp]
         if unique_id is None:
             unique_id = self._exchange_id(store)
         self._id = (C.c_char * ID_BYTES).from_buffer_copy(unique_id)
-        self.ctx = vp()
+        self.ctx = C.c_void_p()
         self._chk(self.lib.lg_comm_init(self.rank, self.world_size, self._id, C.byref(self.ctx)), "lg_comm_init")
 
     def _chk(self, rc, what):

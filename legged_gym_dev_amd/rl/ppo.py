@@ -263,13 +263,11 @@ class HipPPO:
 
     def comm_timing(self, enable):
         """lg_ppo_comm_timing: record the learner stream's wait for the gradient buckets (NativeComm) of every minibatch."""
-        self.lib.lg_ppo_comm_timing.argtypes = [C.c_void_p, C.c_int]
         self.lib.lg_ppo_comm_timing(self.ctx, int(bool(enable)))
 
     def comm_wait_ms(self):
         """(total ms the learner's stream waited for reduced buckets, minibatches recorded) since the last call; synchronises."""
         ms, n = C.c_double(), C.c_int64()
-        self.lib.lg_ppo_comm_wait_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         rc = self.lib.lg_ppo_comm_wait_ms(self.ctx, C.byref(ms), C.byref(n))
         if rc != 0:
             raise LeggedHipError(f"lg_ppo_comm_wait_ms failed ({rc}): {self.lib.lg_last_error().decode()}")

@@ -1,6 +1,6 @@
 """Test-only case builder and float64 references for the recurrent (LSTM) minibatch of the HIP learner: k_lstm_fwd, k_lstm_bwd,
 k_lstm_bias_grad (legged_gym_dev_amd/csrc/ppo_rnn.hip) and rnn_forward_seq / rnn_backward_seq / rnn_live_step
-(csrc/ppo_api.hip).  Plain torch, no GPU needed: tests/test_recurrent_loss_host.py checks what is built here on the CPU,
+(csrc/ppo_sched.hip).  Plain torch, no GPU needed: tests/test_recurrent_loss_host.py checks what is built here on the CPU,
 tests/test_hip_recurrent.py runs it through the library.  The pattern (and the TABLE / regime_of steering) is that of
 tests/ppo_loss_ref.py.
 

@@ -4,7 +4,7 @@ with 2 to 4 ranks over a stand-in transport.
 The pool gives a session one GPU, where RCCL runs one rank and every collective is the identity.  comm_api.cpp resolves its eight
 RCCL entry points by dlopen; LG_RCCL_LIB puts tests/comm_standin/standin.hip under them: ranks are threads of one process on
 cuda:0, a collective is events, stream waits, one summing kernel and asynchronous copies on the stream the caller hands in, and
-nothing in it synchronises a stream or the device.  The product's own stream order (ppo_api.hip: reduce_layer_bucket's wait for the
+nothing in it synchronises a stream or the device.  The product's own stream order (ppo_sched.hip: reduce_layer_bucket's wait for the
 weight-gradient GEMM, the fused head's bucket from the main stream, the learner stream's wait for the last bucket) and its bucket
 extents then decide the numbers.  A delay kernel in front of every copy-back (2000 us) makes a learner stream that does not wait
 read unreduced gradients for certain rather than by luck -- as far as the hardware queues allow: streams share them, and what a

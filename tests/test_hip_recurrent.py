@@ -1,4 +1,4 @@
-"""The LSTM learner (csrc/ppo_rnn.hip: k_lstm_fwd, k_lstm_bwd, k_lstm_bias_grad, k_lstm_reset; csrc/ppo_api.hip: rnn_forward_seq,
+"""The LSTM learner (csrc/ppo_rnn.hip: k_lstm_fwd, k_lstm_bwd, k_lstm_bias_grad, k_lstm_reset; csrc/ppo_sched.hip: rnn_forward_seq,
 rnn_backward_seq, rnn_live_step) against float64, across row tiles, hidden sizes, dones patterns and a privileged critic.
 
 tests/test_recurrent_policy.py, written with the feature, runs every kernel at one row tile (16 or 64 rows), H = 64 | 128, critic
