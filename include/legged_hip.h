@@ -627,9 +627,11 @@ int lg_tube_rollout(lg_tube *t, const float *x, int64_t n_seq, int32_t T, int32_
 int lg_tube_rollout_window(lg_tube *t, const float *x, int64_t n_seq, int32_t T, int32_t fb, int32_t taps, int32_t dN,
                            int32_t stride, const uint8_t *reseed, float *out);
 
-/* ------------------------------------------------------------------ sweep of tube trainers: K models
- * of one shape train on one dataset in the same two launches per step, the members along the grid's y axis.  Member k is, bit for
- * bit, the lg_tube built from cfgs[k] and given the same calls.  Members share input_dim, output_dim, num_units, num_layers, loss,
+/* ------------------------------------------------------------------ sweep of tube models (DESIGN.md sections 10.3, 10.21): K
+ * models of one shape train on one dataset in the same two launches per step, the members along the grid's y axis.  It is the
+ * trainer behind lg_tube with K members instead of one, on one host path; member k is, bit for bit, the lg_tube built from
+ * cfgs[k] and given the same calls.  With K > 1, create and set_data copy the member array to the device and wait for the
+ * handle's stream; step, eval and begin_epoch wait for nothing.  Members share input_dim, output_dim, num_units, num_layers, loss,
  * horizon, H_fwd, H_rev, batch_size and level_input; they may differ in alpha, delta, activation, softplus_beta, lr, gamma, step_size,
  * seed, level_lo and level_hi.
  * Every member owns a full set of a single trainer's buffers (parameters, moments, gradient slab, log, eval, starts, perm), so a

@@ -1,7 +1,14 @@
 // C-ABI (include/legged_hip.h, lg_tube_*) of the tube-model trainer: parameter / optimiser / slab allocation in HBM, epoch
 // permutation, the two launches of a training step, the eval launch, and the inference entries: predict, window prediction and
-// the closed-loop roll-outs, single-tap and windowed, and the level entries of a level-conditioned model, flat or horizon (tube_kernels.hip).  lg_tube_sweep_*: K such trainers of one shape on one
-// dataset, stepped by the same two launches with the members along grid y.
+// the closed-loop roll-outs, single-tap and windowed, and the level entries of a level-conditioned model, flat or horizon (tube_kernels.hip).
+// One trainer, TubeTrainer: K models of one shape on one dataset, stepped by the same two launches.  lg_tube is K = 1 and
+// lg_tube_sweep_* any K; every training operation is written once (trainer_*) and the entries of both families forward to it
+// with their name, which the error texts carry.
+// The K == 1 rule: one member is launched through the by-value kernels (k_tube_rows, k_tube_adam, ...: TubeDev in the kernel
+// arguments), K > 1 through the member-array kernels (*_sweep, the members along grid y).  The two sets compute the same bits; the
+// member-array set measured 1.2 us per step slower at K = 1 on the level-conditioned default config.
+// Waiting: with K > 1, create and set_data copy the member array to the device and wait for the handle's stream; nothing else
+// waits, and with one member nothing does.
 // The planner entries, which read a handle's TubeDev and nothing else of it (lg_internal_tube_dev), are plan_api.hip's.
 #include <cmath>
 #include <cstring>
@@ -15,30 +22,32 @@ struct TubeCaps {                       // rows that a model's data-sized buffer
     int64_t starts = 0, perm = 0, evpart = 0, levels = 0;
 };
 
-struct lg_tube {
-    lg_tube_cfg cfg;
-    TubeDev dev;
-    TubeSplit split[2];                 // train, test
+struct TubeTrainer {
+    std::vector<lg_tube_cfg> cfg;       // per member
+    std::vector<TubeMember> mem;        // host copy of the member array; mem[0].dev is what inference and the planner read
+    std::vector<TubeCaps> caps;
+    TubeMember *dmem = nullptr;         // device copy, what the member-array kernels index by blockIdx.y (K > 1)
+    TubeSplit split[2];                 // train, test; shared by all members
     hipStream_t stream = nullptr;
-    int64_t t = 0;                      // Adam steps taken
+    int64_t t = 0;                      // Adam steps taken; the members step together
     int64_t pos = 0;                    // rows of the epoch permutation consumed
     int64_t eval_count = 0;
-    TubeCaps caps;
     int64_t eval_rows_cap = 0;
     int32_t *eval_rows = nullptr;
 };
+struct lg_tube : TubeTrainer {};        // K = 1
+struct lg_tube_sweep : TubeTrainer {};
 
-struct lg_tube_sweep {
-    std::vector<lg_tube_cfg> cfg;       // per member
-    std::vector<TubeMember> mem;        // host copy of the member array
-    std::vector<TubeCaps> caps;
-    TubeMember *dmem = nullptr;         // device copy, what the kernels index by blockIdx.y
-    TubeSplit split[2];                 // shared by all members
-    hipStream_t stream = nullptr;
-    int64_t t = 0, pos = 0, eval_count = 0;   // the members step together
-    int64_t eval_rows_cap = 0;
-    int32_t *eval_rows = nullptr;
-};
+// what an entry's error texts take from its family: the prefix of its name and what it calls its handle
+struct Family { const char *prefix, *noun; };
+static const Family SINGLE{"lg_tube", "handle"}, SWEEP{"lg_tube_sweep", "sweep"};
+
+static std::string entry(const Family &f, const char *fn) { return std::string(f.prefix) + "_" + fn; }
+static int refuse(const Family &f, const char *fn, const std::string &why, int rc = -1) {
+    lg_set_error(entry(f, fn) + ": " + why);
+    return rc;
+}
+static int launched(const Family &f, const char *fn) { return hipGetLastError() == hipSuccess ? 0 : refuse(f, fn, "launch failed", -3); }
 
 static bool talloc(void **q, size_t bytes) {
     *q = nullptr;
@@ -175,6 +184,141 @@ static int fill_layout(const TubeDev &D, int64_t *offsets, int64_t *shapes, int 
     return n;
 }
 
+// ---------------------------------------------------------------- the trainer: every operation once, for both families
+static int trainer_upload(TubeTrainer &T, const Family &f) {   // the device copy of the member array follows the host copy
+    if (T.mem.size() == 1) return 0;    // one member goes to its kernels by value: nothing reads the device copy
+    if (hipMemcpyAsync(T.dmem, T.mem.data(), T.mem.size() * sizeof(TubeMember), hipMemcpyHostToDevice, T.stream) != hipSuccess ||
+        hipStreamSynchronize(T.stream) != hipSuccess) {
+        lg_set_error(std::string(f.prefix) + ": copying the member array failed"); return -3;
+    }
+    return 0;
+}
+
+static bool trainer_member(const TubeTrainer &T, const Family &f, const char *fn, int32_t k) {
+    if (k >= 0 && k < (int32_t)T.mem.size()) return true;
+    refuse(f, fn, "member " + std::to_string(k) + " is outside 0.." + std::to_string(T.mem.size() - 1));
+    return false;
+}
+
+template <class H>
+static int trainer_destroy(H *p) {
+    if (!p) return 0;
+    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    else (void)hipDeviceSynchronize();
+    for (TubeMember &m : p->mem) dev_free(m.dev);
+    if (p->dmem) (void)hipFree(p->dmem);
+    if (p->eval_rows) (void)hipFree(p->eval_rows);
+    delete p;
+    return 0;
+}
+
+// cfgs: K configurations that the caller has checked
+template <class H>
+static int trainer_create(const Family &f, const lg_tube_cfg *cfgs, int32_t K, H **out) {
+    if (tubek_init()) return refuse(f, "create", "hipFuncSetAttribute failed", -2);
+    H *p = new H();
+    p->cfg.assign(cfgs, cfgs + K);
+    p->mem.resize(K);                   // zeroed: a member that dev_init never reached frees nothing
+    p->caps.resize(K);
+    bool ok = talloc((void **)&p->dmem, (size_t)K * sizeof(TubeMember));
+    for (int k = 0; ok && k < K; ++k) {
+        ok = dev_init(cfgs + k, p->mem[k].dev);
+        p->mem[k].lr0 = cfgs[k].lr; p->mem[k].gamma = cfgs[k].gamma; p->mem[k].step_size = cfgs[k].step_size;
+    }
+    if (!ok) {
+        std::string e = "hipMalloc failed in " + entry(f, "create");
+        if (&f == &SWEEP) e += " (a sweep of " + std::to_string(K) + " members takes " + std::to_string(K) + " times a single trainer's memory)";
+        lg_set_error(e);
+        trainer_destroy(p);
+        return -100;
+    }
+    if (trainer_upload(*p, f)) { trainer_destroy(p); return -3; }
+    *out = p;
+    return 0;
+}
+
+static int trainer_get_buffers(TubeTrainer &T, const Family &f, int32_t k, lg_tube_buffers *out) {
+    if (!trainer_member(T, f, "get_buffers", k)) return -1;
+    fill_buffers(T.mem[k].dev, T.caps[k], T.t, out);
+    return 0;
+}
+
+// one k_tube_wt launch per member asked for (K launches for k = -1): initialisation and checkpoint loads, not the step
+static int trainer_params_changed(TubeTrainer &T, const Family &f, int32_t k) {
+    if (k != -1 && !trainer_member(T, f, "params_changed", k)) return -1;
+    for (int32_t i = k < 0 ? 0 : k; i < (k < 0 ? (int32_t)T.mem.size() : k + 1); ++i) tubek_wt(&T.mem[i].dev, T.stream);
+    return launched(f, "params_changed");
+}
+
+static int trainer_set_step(TubeTrainer &T, const Family &f, int64_t t) {
+    if (t < 0) return refuse(f, "set_step", "negative step");
+    T.t = t;
+    return 0;
+}
+
+static int trainer_set_data(TubeTrainer &T, const Family &f, int which, const float *x, const float *y, const float *v, int64_t rows,
+                            int32_t Tn, int32_t nz, int32_t m) {
+    // every member is asked: data_reason also records a horizon split's T / nz / m in that member's TubeDev (the members share the
+    // shape, so they all give the same verdict)
+    for (TubeMember &mb : T.mem)
+        if (const char *e = data_reason(mb.dev, which, x, y, v, rows, Tn, nz, m)) return refuse(f, "set_data", e);
+    T.split[which] = TubeSplit{x, y, v, rows};
+    bool ok = true;
+    for (size_t k = 0; ok && k < T.mem.size(); ++k) ok = data_alloc(T.mem[k].dev, T.caps[k], which, rows, T.cfg[k].batch_size);
+    ok = ok && (which != 1 || eval_rows_alloc(&T.eval_rows, &T.eval_rows_cap, rows, T.stream));
+    const int rc = trainer_upload(T, f);            // also after a failure: the array must not keep a freed pointer
+    if (!ok) { lg_set_error("hipMalloc failed in " + entry(f, "set_data")); return -100; }
+    return rc;
+}
+
+static int trainer_begin_epoch(TubeTrainer &T, const Family &f, int64_t epoch) {
+    if (!T.split[0].rows) return refuse(f, "begin_epoch", "no training data (" + entry(f, "set_data") + ")");
+    if (T.mem.size() == 1) tubek_perm(&T.mem[0].dev, (int)T.split[0].rows, (uint64_t)epoch, T.stream);
+    else tubek_perm_sweep(T.dmem, (int)T.mem.size(), (int)T.split[0].rows, (uint64_t)epoch, T.stream);
+    T.pos = 0;
+    return launched(f, "begin_epoch");
+}
+
+static int trainer_step(TubeTrainer &T, const Family &f, const int32_t *rows, int64_t count) {
+    if (!T.split[0].rows) return refuse(f, "step", "no training data (" + entry(f, "set_data") + ")");
+    if (count < 1 || count > T.cfg[0].batch_size) return refuse(f, "step", "count must be 1..batch_size");
+    int64_t pos = 0;
+    if (!rows) {                        // each member's own permutation, from the shared position
+        if (T.pos + count > T.split[0].rows) return refuse(f, "step", "the epoch's permutation is used up (" + entry(f, "begin_epoch") + ")");
+        pos = T.pos;
+        T.pos += count;
+    }
+    const float norm = loss_norm(T.cfg[0], count);
+    const int K = (int)T.mem.size(), nwg = (int)((count + LG_TUBE_ROWS - 1) / LG_TUBE_ROWS);
+    const TubeDev &D0 = T.mem[0].dev;
+    ++T.t;
+    if (K == 1) {                       // the K == 1 rule (top of the file)
+        tubek_step(&D0, &T.split[0], rows ? rows : D0.perm + pos, count, (uint64_t)T.t, norm, T.stream);
+        tubek_adam(&D0, nwg, T.t, T.cfg[0].lr, T.cfg[0].gamma, (int64_t)T.cfg[0].step_size, norm, count, T.stream);
+    } else {
+        tubek_step_sweep(T.dmem, K, &D0, &T.split[0], rows, pos, count, (uint64_t)T.t, norm, T.stream);
+        tubek_adam_sweep(T.dmem, K, &D0, nwg, T.t, norm, count, T.stream);
+    }
+    return launched(f, "step");
+}
+
+// level < 0: lg_tube_eval, one drawn level per row of a level_input handle; 0..1: lg_tube_eval_level
+static int trainer_eval(TubeTrainer &T, const Family &f, const char *fn, float level) {
+    const TubeSplit &S = T.split[1];
+    if (!S.rows) return refuse(f, fn, "no test data (" + entry(f, "set_data") + " with which = 1)");
+    const uint64_t key = level < 0.f ? 0x8000000000000000ull | (uint64_t)T.eval_count++ : 0;   // a fixed level draws nothing: no key
+    const float norm = loss_norm(T.cfg[0], S.rows);
+    if (T.mem.size() == 1) tubek_eval(&T.mem[0].dev, &S, T.eval_rows, key, norm, level, T.stream);
+    else tubek_eval_sweep(T.dmem, (int)T.mem.size(), &T.mem[0].dev, &S, T.eval_rows, key, norm, level, T.stream);
+    return launched(f, fn);
+}
+
+static int trainer_eval_level(TubeTrainer &T, const Family &f, float level) {
+    if (!T.mem[0].dev.level_input) return refuse(f, "eval_level", std::string("the ") + f.noun + " is not level-conditioned (lg_tube_cfg.level_input)");
+    if (!(level >= 0.f && level <= 1.f)) return refuse(f, "eval_level", "level must lie in 0..1");
+    return trainer_eval(T, f, "eval_level", level);
+}
+
 extern "C" {
 
 int lg_tube_check_cfg(const lg_tube_cfg *c) {
@@ -185,117 +329,44 @@ int lg_tube_check_cfg(const lg_tube_cfg *c) {
 
 int lg_tube_create(const lg_tube_cfg *cfg, lg_tube **out) {
     *out = nullptr;
-    if (lg_tube_check_cfg(cfg)) return -1;
-    if (tubek_init()) { lg_set_error("lg_tube_create: hipFuncSetAttribute failed"); return -2; }
-    lg_tube *p = new lg_tube();
-    p->cfg = *cfg;
-    const bool ok = dev_init(cfg, p->dev);
-    if (!ok) { lg_set_error("hipMalloc failed in lg_tube_create"); lg_tube_destroy(p); return -100; }
-    *out = p;
-    return 0;
+    return lg_tube_check_cfg(cfg) ? -1 : trainer_create(SINGLE, cfg, 1, out);
 }
-
-int lg_tube_destroy(lg_tube *p) {
-    if (!p) return 0;
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
-    else (void)hipDeviceSynchronize();
-    dev_free(p->dev);
-    if (p->eval_rows) (void)hipFree(p->eval_rows);
-    delete p;
-    return 0;
-}
-
+int lg_tube_destroy(lg_tube *p) { return trainer_destroy(p); }
 int lg_tube_set_stream(lg_tube *p, void *stream) { p->stream = (hipStream_t)stream; return 0; }
-
-// for plan_api.hip (lg_internal.h)
-const TubeDev *lg_internal_tube_dev(const lg_tube *p) { return p ? &p->dev : nullptr; }
-
-int lg_tube_get_buffers(lg_tube *p, lg_tube_buffers *out) {
-    fill_buffers(p->dev, p->caps, p->t, out);
-    return 0;
-}
-
+int lg_tube_get_buffers(lg_tube *p, lg_tube_buffers *out) { return trainer_get_buffers(*p, SINGLE, 0, out); }
 int lg_tube_param_layout(lg_tube *p, int64_t *offsets, int64_t *shapes, int max_entries) {
-    return fill_layout(p->dev, offsets, shapes, max_entries, "lg_tube_param_layout");
+    return fill_layout(p->mem[0].dev, offsets, shapes, max_entries, "lg_tube_param_layout");
 }
-
-int lg_tube_params_changed(lg_tube *p) { tubek_wt(&p->dev, p->stream); return 0; }
-
-int lg_tube_set_step(lg_tube *p, int64_t t) {
-    if (t < 0) { lg_set_error("lg_tube_set_step: negative step"); return -1; }
-    p->t = t;
-    return 0;
-}
-
+int lg_tube_params_changed(lg_tube *p) { return trainer_params_changed(*p, SINGLE, 0); }
+int lg_tube_set_step(lg_tube *p, int64_t t) { return trainer_set_step(*p, SINGLE, t); }
 int lg_tube_set_data(lg_tube *p, int which, const float *x, const float *y, const float *v, int64_t rows, int32_t T, int32_t nz,
                      int32_t m) {
-    TubeDev &D = p->dev;
-    if (const char *e = data_reason(D, which, x, y, v, rows, T, nz, m)) { lg_set_error(std::string("lg_tube_set_data: ") + e); return -1; }
-    p->split[which] = TubeSplit{x, y, v, rows};
-    if (!data_alloc(D, p->caps, which, rows, p->cfg.batch_size) ||
-        (which == 1 && !eval_rows_alloc(&p->eval_rows, &p->eval_rows_cap, rows, p->stream))) {
-        lg_set_error("hipMalloc failed"); return -100;
-    }
-    return 0;
+    return trainer_set_data(*p, SINGLE, which, x, y, v, rows, T, nz, m);
 }
+int lg_tube_begin_epoch(lg_tube *p, int64_t epoch) { return trainer_begin_epoch(*p, SINGLE, epoch); }
+int lg_tube_step(lg_tube *p, const int32_t *rows, int64_t count) { return trainer_step(*p, SINGLE, rows, count); }
+int lg_tube_eval(lg_tube *p) { return trainer_eval(*p, SINGLE, "eval", -1.f); }
+int lg_tube_eval_level(lg_tube *p, float level) { return trainer_eval_level(*p, SINGLE, level); }
 
-int lg_tube_begin_epoch(lg_tube *p, int64_t epoch) {
-    if (!p->split[0].rows) { lg_set_error("lg_tube_begin_epoch: no training data (lg_tube_set_data)"); return -1; }
-    tubek_perm(&p->dev, (int)p->split[0].rows, (uint64_t)epoch, p->stream);
-    p->pos = 0;
-    return 0;
-}
-
-int lg_tube_step(lg_tube *p, const int32_t *rows, int64_t count) {
-    if (!p->split[0].rows) { lg_set_error("lg_tube_step: no training data (lg_tube_set_data)"); return -1; }
-    if (count < 1 || count > p->cfg.batch_size) { lg_set_error("lg_tube_step: count must be 1..batch_size"); return -1; }
-    const int32_t *r = rows;
-    if (!r) {
-        if (p->pos + count > p->split[0].rows) { lg_set_error("lg_tube_step: the epoch's permutation is used up (lg_tube_begin_epoch)"); return -1; }
-        r = p->dev.perm + p->pos;
-        p->pos += count;
-    }
-    const float norm = loss_norm(p->cfg, count);
-    ++p->t;
-    tubek_step(&p->dev, &p->split[0], r, count, (uint64_t)p->t, norm, p->stream);
-    tubek_adam(&p->dev, (int)((count + LG_TUBE_ROWS - 1) / LG_TUBE_ROWS), p->t, (double)p->cfg.lr, (double)p->cfg.gamma,
-               (int64_t)p->cfg.step_size, norm, count, p->stream);
-    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_step: launch failed"), -3);
-}
-
-int lg_tube_eval(lg_tube *p) {
-    const TubeSplit &S = p->split[1];
-    if (!S.rows) { lg_set_error("lg_tube_eval: no test data (lg_tube_set_data with which = 1)"); return -1; }
-    const uint64_t key = 0x8000000000000000ull | (uint64_t)p->eval_count++;
-    tubek_eval(&p->dev, &S, p->eval_rows, key, loss_norm(p->cfg, S.rows), -1.f, p->stream);
-    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_eval: launch failed"), -3);
-}
-
-int lg_tube_eval_level(lg_tube *p, float level) {
-    const TubeSplit &S = p->split[1];
-    if (!p->dev.level_input) { lg_set_error("lg_tube_eval_level: the handle is not level-conditioned (lg_tube_cfg.level_input)"); return -1; }
-    if (!(level >= 0.f && level <= 1.f)) { lg_set_error("lg_tube_eval_level: level must lie in 0..1"); return -1; }
-    if (!S.rows) { lg_set_error("lg_tube_eval_level: no test data (lg_tube_set_data with which = 1)"); return -1; }
-    tubek_eval(&p->dev, &S, p->eval_rows, 0, loss_norm(p->cfg, S.rows), level, p->stream);     // nothing is drawn: no key
-    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_eval_level: launch failed"), -3);
-}
+// for plan_api.hip (lg_internal.h)
+const TubeDev *lg_internal_tube_dev(const lg_tube *p) { return p ? &p->mem[0].dev : nullptr; }
 
 // ---------------------------------------------------------------- inference: reads params / wt, changes neither
 int lg_tube_predict(lg_tube *p, const float *x, const int32_t *rows, int64_t count, float *out) {
-    if (p->dev.horizon) { lg_set_error("lg_tube_predict: a horizon handle predicts windows (lg_tube_predict_windows)"); return -1; }
+    if (p->mem[0].dev.horizon) { lg_set_error("lg_tube_predict: a horizon handle predicts windows (lg_tube_predict_windows)"); return -1; }
     if (count < 1) { lg_set_error("lg_tube_predict: count must be positive"); return -1; }
     if (!x || !out) { lg_set_error("lg_tube_predict: missing array"); return -1; }
-    tubek_predict(&p->dev, x, nullptr, nullptr, rows, nullptr, nullptr, 0, 0, 0, count, out, p->stream);
+    tubek_predict(&p->mem[0].dev, x, nullptr, nullptr, rows, nullptr, nullptr, 0, 0, 0, count, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict: launch failed"), -3);
 }
 
 int lg_tube_predict_levels(lg_tube *p, const float *x, const int32_t *rows, int64_t count, const float *levels, int32_t n_levels,
                            float *out) {
-    if (!p->dev.level_input) { lg_set_error("lg_tube_predict_levels: the handle is not level-conditioned (lg_tube_cfg.level_input)"); return -1; }
+    if (!p->mem[0].dev.level_input) { lg_set_error("lg_tube_predict_levels: the handle is not level-conditioned (lg_tube_cfg.level_input)"); return -1; }
     if (count < 1) { lg_set_error("lg_tube_predict_levels: count must be positive"); return -1; }
     if (n_levels < 1 || n_levels > LG_TUBE_MAX_LEVELS) { lg_set_error("lg_tube_predict_levels: n_levels must be 1..64"); return -1; }
     if (!x || !levels || !out) { lg_set_error("lg_tube_predict_levels: missing array"); return -1; }
-    tubek_predict_levels(&p->dev, x, rows, count, levels, n_levels, out, p->stream);
+    tubek_predict_levels(&p->mem[0].dev, x, rows, count, levels, n_levels, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict_levels: launch failed"), -3);
 }
 
@@ -312,7 +383,7 @@ static const char *windows_reason(const TubeDev &D, const float *w, const float 
 
 int lg_tube_predict_windows(lg_tube *p, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz, int32_t m,
                             const int32_t *env, const int32_t *start, int64_t count, float *out) {
-    const TubeDev &D = p->dev;
+    const TubeDev &D = p->mem[0].dev;
     if (!D.horizon) { lg_set_error("lg_tube_predict_windows: a flat handle predicts rows (lg_tube_predict)"); return -1; }
     if (D.level_input) {
         lg_set_error("lg_tube_predict_windows: the handle is level-conditioned (lg_tube_cfg.level_input): a window has no level, use "
@@ -322,14 +393,14 @@ int lg_tube_predict_windows(lg_tube *p, const float *w, const float *z, const fl
     if (const char *e = windows_reason(D, w, z, v, n, T, nz, m, env, start, count, out)) {
         lg_set_error(std::string("lg_tube_predict_windows: ") + e); return -1;
     }
-    tubek_predict(&p->dev, w, z, v, nullptr, env, start, T, nz, m, count, out, p->stream);
+    tubek_predict(&p->mem[0].dev, w, z, v, nullptr, env, start, T, nz, m, count, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict_windows: launch failed"), -3);
 }
 
 int lg_tube_predict_windows_levels(lg_tube *p, const float *w, const float *z, const float *v, int64_t n, int32_t T, int32_t nz,
                                    int32_t m, const int32_t *env, const int32_t *start, int64_t count, const float *levels,
                                    int32_t n_levels, float *out) {
-    const TubeDev &D = p->dev;
+    const TubeDev &D = p->mem[0].dev;
     const char *e = nullptr;
     if (!D.level_input) e = "the handle is not level-conditioned (lg_tube_cfg.level_input)";
     else if (!D.horizon) e = "not a horizon handle (lg_tube_cfg.horizon): a flat handle predicts rows (lg_tube_predict_levels)";
@@ -337,24 +408,24 @@ int lg_tube_predict_windows_levels(lg_tube *p, const float *w, const float *z, c
     else if (!levels) e = "missing array";
     else e = windows_reason(D, w, z, v, n, T, nz, m, env, start, count, out);
     if (e) { lg_set_error(std::string("lg_tube_predict_windows_levels: ") + e); return -1; }
-    tubek_predict_windows_levels(&p->dev, w, z, v, env, start, T, nz, m, count, levels, n_levels, out, p->stream);
+    tubek_predict_windows_levels(&p->mem[0].dev, w, z, v, env, start, T, nz, m, count, levels, n_levels, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_predict_windows_levels: launch failed"), -3);
 }
 
 int lg_tube_rollout(lg_tube *p, const float *x, int64_t n_seq, int32_t T, int32_t fb, const uint8_t *reseed, float *out) {
-    const TubeDev &D = p->dev;
+    const TubeDev &D = p->mem[0].dev;
     if (D.horizon) { lg_set_error("lg_tube_rollout: a horizon handle has no closed loop (lg_tube_predict_windows)"); return -1; }
     if (n_seq < 1 || T < 1) { lg_set_error("lg_tube_rollout: n_seq and T must be positive"); return -1; }
     if (n_seq > INT32_MAX / 16) { lg_set_error("lg_tube_rollout: n_seq must be below 2^27"); return -1; }
     if (fb < 0 || fb > D.in_dim || fb > D.out_dim) { lg_set_error("lg_tube_rollout: fb must be 0..min(input_dim, output_dim)"); return -1; }
     if (!x || !out) { lg_set_error("lg_tube_rollout: missing array"); return -1; }
-    tubek_rollout(&p->dev, x, n_seq, T, fb, reseed, out, p->stream);
+    tubek_rollout(&p->mem[0].dev, x, n_seq, T, fb, reseed, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_rollout: launch failed"), -3);
 }
 
 int lg_tube_rollout_window(lg_tube *p, const float *x, int64_t n_seq, int32_t T, int32_t fb, int32_t taps, int32_t dN, int32_t stride,
                            const uint8_t *reseed, float *out) {
-    const TubeDev &D = p->dev;
+    const TubeDev &D = p->mem[0].dev;
     const char *e = nullptr;
     if (D.horizon) e = "a horizon handle has no closed loop (lg_tube_predict_windows)";
     else if (n_seq < 1 || T < 1) e = "n_seq and T must be positive";
@@ -366,25 +437,11 @@ int lg_tube_rollout_window(lg_tube *p, const float *x, int64_t n_seq, int32_t T,
     else if (((int64_t)(taps - 1) * dN + 1) * fb > LG_TUBE_RING_MAX) e = "the ring ((taps - 1) * dN + 1) * fb must not exceed 1024 floats per sequence";
     else if (!x || !out) e = "missing array";
     if (e) { lg_set_error(std::string("lg_tube_rollout_window: ") + e); return -1; }
-    tubek_rollout_window(&p->dev, x, n_seq, T, fb, taps, dN, taps > 1 ? stride : D.in_dim, reseed, out, p->stream);
+    tubek_rollout_window(&p->mem[0].dev, x, n_seq, T, fb, taps, dN, taps > 1 ? stride : D.in_dim, reseed, out, p->stream);
     return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_rollout_window: launch failed"), -3);
 }
 
-// ---------------------------------------------------------------- sweep: K trainers of one shape on one dataset
-static int sweep_upload(lg_tube_sweep *s) {       // the device copy of the member array follows the host copy
-    if (hipMemcpyAsync(s->dmem, s->mem.data(), s->mem.size() * sizeof(TubeMember), hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipStreamSynchronize(s->stream) != hipSuccess) {
-        lg_set_error("lg_tube_sweep: copying the member array failed"); return -3;
-    }
-    return 0;
-}
-
-static bool sweep_member(const lg_tube_sweep *s, int32_t k, const char *who) {
-    if (k >= 0 && k < (int32_t)s->mem.size()) return true;
-    lg_set_error(std::string(who) + ": member " + std::to_string(k) + " is outside 0.." + std::to_string(s->mem.size() - 1));
-    return false;
-}
-
+// ---------------------------------------------------------------- sweep: the same trainer with K members
 int lg_tube_sweep_create(const lg_tube_cfg *cfgs, int32_t K, lg_tube_sweep **out) {
     *out = nullptr;
     if (K < 1 || K > LG_TUBE_SWEEP_MAX) {
@@ -407,122 +464,23 @@ int lg_tube_sweep_create(const lg_tube_cfg *cfgs, int32_t K, lg_tube_sweep **out
             return -1;
         }
     }
-    if (tubek_init()) { lg_set_error("lg_tube_sweep_create: hipFuncSetAttribute failed"); return -2; }
-    lg_tube_sweep *s = new lg_tube_sweep();
-    s->cfg.assign(cfgs, cfgs + K);
-    s->mem.resize(K);
-    s->caps.resize(K);
-    for (int k = 0; k < K; ++k) memset(&s->mem[k], 0, sizeof(TubeMember));
-    bool ok = talloc((void **)&s->dmem, (size_t)K * sizeof(TubeMember));
-    for (int k = 0; ok && k < K; ++k) {
-        ok = dev_init(cfgs + k, s->mem[k].dev);
-        s->mem[k].lr0 = cfgs[k].lr; s->mem[k].gamma = cfgs[k].gamma; s->mem[k].step_size = cfgs[k].step_size;
-    }
-    if (!ok) {
-        lg_set_error("hipMalloc failed in lg_tube_sweep_create (a sweep of " + std::to_string(K) + " members takes " + std::to_string(K) +
-                     " times a single trainer's memory)");
-        lg_tube_sweep_destroy(s);
-        return -100;
-    }
-    if (sweep_upload(s)) { lg_tube_sweep_destroy(s); return -3; }
-    *out = s;
-    return 0;
+    return trainer_create(SWEEP, cfgs, K, out);
 }
-
-int lg_tube_sweep_destroy(lg_tube_sweep *s) {
-    if (!s) return 0;
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    else (void)hipDeviceSynchronize();
-    for (TubeMember &m : s->mem) dev_free(m.dev);
-    if (s->dmem) (void)hipFree(s->dmem);
-    if (s->eval_rows) (void)hipFree(s->eval_rows);
-    delete s;
-    return 0;
-}
-
+int lg_tube_sweep_destroy(lg_tube_sweep *s) { return trainer_destroy(s); }
 int lg_tube_sweep_set_stream(lg_tube_sweep *s, void *stream) { s->stream = (hipStream_t)stream; return 0; }
-
-int lg_tube_sweep_get_buffers(lg_tube_sweep *s, int32_t k, lg_tube_buffers *out) {
-    if (!sweep_member(s, k, "lg_tube_sweep_get_buffers")) return -1;
-    fill_buffers(s->mem[k].dev, s->caps[k], s->t, out);
-    return 0;
-}
-
+int lg_tube_sweep_get_buffers(lg_tube_sweep *s, int32_t k, lg_tube_buffers *out) { return trainer_get_buffers(*s, SWEEP, k, out); }
 int lg_tube_sweep_param_layout(lg_tube_sweep *s, int64_t *offsets, int64_t *shapes, int max_entries) {
     return fill_layout(s->mem[0].dev, offsets, shapes, max_entries, "lg_tube_sweep_param_layout");
 }
-
-// one k_tube_wt launch per member asked for (K launches for k = -1): initialisation and checkpoint loads, not the step
-int lg_tube_sweep_params_changed(lg_tube_sweep *s, int32_t k) {
-    if (k != -1 && !sweep_member(s, k, "lg_tube_sweep_params_changed")) return -1;
-    for (int32_t i = k < 0 ? 0 : k; i < (k < 0 ? (int32_t)s->mem.size() : k + 1); ++i) tubek_wt(&s->mem[i].dev, s->stream);
-    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_sweep_params_changed: launch failed"), -3);
-}
-
-int lg_tube_sweep_set_step(lg_tube_sweep *s, int64_t t) {
-    if (t < 0) { lg_set_error("lg_tube_sweep_set_step: negative step"); return -1; }
-    s->t = t;
-    return 0;
-}
-
+int lg_tube_sweep_params_changed(lg_tube_sweep *s, int32_t k) { return trainer_params_changed(*s, SWEEP, k); }
+int lg_tube_sweep_set_step(lg_tube_sweep *s, int64_t t) { return trainer_set_step(*s, SWEEP, t); }
 int lg_tube_sweep_set_data(lg_tube_sweep *s, int which, const float *x, const float *y, const float *v, int64_t rows, int32_t T,
                            int32_t nz, int32_t m) {
-    // every member is asked: data_reason also records a horizon split's T / nz / m in that member's TubeDev (the members share the
-    // shape, so they all give the same verdict)
-    for (size_t k = 0; k < s->mem.size(); ++k)
-        if (const char *e = data_reason(s->mem[k].dev, which, x, y, v, rows, T, nz, m)) {
-            lg_set_error(std::string("lg_tube_sweep_set_data: ") + e); return -1;
-        }
-    s->split[which] = TubeSplit{x, y, v, rows};
-    bool ok = true;
-    for (size_t k = 0; ok && k < s->mem.size(); ++k) ok = data_alloc(s->mem[k].dev, s->caps[k], which, rows, s->cfg[k].batch_size);
-    ok = ok && (which != 1 || eval_rows_alloc(&s->eval_rows, &s->eval_rows_cap, rows, s->stream));
-    const int rc = sweep_upload(s);                 // also after a failure: the array must not keep a freed pointer
-    if (!ok) { lg_set_error("hipMalloc failed in lg_tube_sweep_set_data"); return -100; }
-    return rc;
+    return trainer_set_data(*s, SWEEP, which, x, y, v, rows, T, nz, m);
 }
-
-int lg_tube_sweep_begin_epoch(lg_tube_sweep *s, int64_t epoch) {
-    if (!s->split[0].rows) { lg_set_error("lg_tube_sweep_begin_epoch: no training data (lg_tube_sweep_set_data)"); return -1; }
-    tubek_perm_sweep(s->dmem, (int)s->mem.size(), (int)s->split[0].rows, (uint64_t)epoch, s->stream);
-    s->pos = 0;
-    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_sweep_begin_epoch: launch failed"), -3);
-}
-
-int lg_tube_sweep_step(lg_tube_sweep *s, const int32_t *rows, int64_t count) {
-    if (!s->split[0].rows) { lg_set_error("lg_tube_sweep_step: no training data (lg_tube_sweep_set_data)"); return -1; }
-    if (count < 1 || count > s->cfg[0].batch_size) { lg_set_error("lg_tube_sweep_step: count must be 1..batch_size"); return -1; }
-    int64_t pos = 0;
-    if (!rows) {
-        if (s->pos + count > s->split[0].rows) {
-            lg_set_error("lg_tube_sweep_step: the epoch's permutation is used up (lg_tube_sweep_begin_epoch)"); return -1;
-        }
-        pos = s->pos;
-        s->pos += count;
-    }
-    const float norm = loss_norm(s->cfg[0], count);
-    const int K = (int)s->mem.size();
-    ++s->t;
-    tubek_step_sweep(s->dmem, K, &s->mem[0].dev, &s->split[0], rows, pos, count, (uint64_t)s->t, norm, s->stream);
-    tubek_adam_sweep(s->dmem, K, &s->mem[0].dev, (int)((count + LG_TUBE_ROWS - 1) / LG_TUBE_ROWS), s->t, norm, count, s->stream);
-    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_sweep_step: launch failed"), -3);
-}
-
-int lg_tube_sweep_eval(lg_tube_sweep *s) {
-    const TubeSplit &S = s->split[1];
-    if (!S.rows) { lg_set_error("lg_tube_sweep_eval: no test data (lg_tube_sweep_set_data with which = 1)"); return -1; }
-    const uint64_t key = 0x8000000000000000ull | (uint64_t)s->eval_count++;
-    tubek_eval_sweep(s->dmem, (int)s->mem.size(), &s->mem[0].dev, &S, s->eval_rows, key, loss_norm(s->cfg[0], S.rows), -1.f, s->stream);
-    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_sweep_eval: launch failed"), -3);
-}
-
-int lg_tube_sweep_eval_level(lg_tube_sweep *s, float level) {
-    const TubeSplit &S = s->split[1];
-    if (!s->mem[0].dev.level_input) { lg_set_error("lg_tube_sweep_eval_level: the sweep is not level-conditioned (lg_tube_cfg.level_input)"); return -1; }
-    if (!(level >= 0.f && level <= 1.f)) { lg_set_error("lg_tube_sweep_eval_level: level must lie in 0..1"); return -1; }
-    if (!S.rows) { lg_set_error("lg_tube_sweep_eval_level: no test data (lg_tube_sweep_set_data with which = 1)"); return -1; }
-    tubek_eval_sweep(s->dmem, (int)s->mem.size(), &s->mem[0].dev, &S, s->eval_rows, 0, loss_norm(s->cfg[0], S.rows), level, s->stream);
-    return hipGetLastError() == hipSuccess ? 0 : (lg_set_error("lg_tube_sweep_eval_level: launch failed"), -3);
-}
+int lg_tube_sweep_begin_epoch(lg_tube_sweep *s, int64_t epoch) { return trainer_begin_epoch(*s, SWEEP, epoch); }
+int lg_tube_sweep_step(lg_tube_sweep *s, const int32_t *rows, int64_t count) { return trainer_step(*s, SWEEP, rows, count); }
+int lg_tube_sweep_eval(lg_tube_sweep *s) { return trainer_eval(*s, SWEEP, "eval", -1.f); }
+int lg_tube_sweep_eval_level(lg_tube_sweep *s, float level) { return trainer_eval_level(*s, SWEEP, level); }
 
 }  // extern "C"

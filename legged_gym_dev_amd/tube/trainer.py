@@ -1,5 +1,7 @@
 """HipTubeTrainer: the reference tube MLP trained and run by the HIP kernels of tube_kernels.hip (lg_tube_* in
-include/legged_hip.h).
+include/legged_hip.h).  TubeTraining holds what it shares with sweep.HipTubeSweep -- handle, buffer views, data, the training
+calls -- since a single trainer is a sweep of one member, in the library and here; HipTubeTrainer adds
+member 0's views as attributes and the inference methods.
 
 A step is two launches on the current stream -- fused forward / loss / backward over the minibatch, then the fixed-order gradient
 reduction, Adam and StepLR -- and nothing in it waits for the device.  Loss, lr and gradient norm of every step stay in a device
@@ -85,102 +87,97 @@ def initial_params(input_dim, output_dim, num_units, num_layers, seed):
     return sd
 
 
-class HipTubeTrainer:
-    def __init__(self, input_dim, output_dim, num_units=32, num_layers=2, activation="relu", softplus_beta=1.0,
-                 loss="scalar", alpha=0.8, delta=1.0, lr=1e-3, gamma=0.1, step_size=10000, batch_size=2048, seed=42,
-                 horizon=None, final_activation=None, device="cuda:0", level_lo=0.0, level_hi=1.0):
-        """horizon: None for the row datasets, (H_fwd, H_rev) for ScalarHorizonTubeDataset.  loss "scalar_level" /
-        "vector_level": the level-conditioned tube -- input_dim counts the level column (the last one), the data has
-        input_dim - 1 columns, every row of a step draws its level uniformly from [level_lo, level_hi), alpha is not read.
-        With a horizon the window item gains the level as its last column and the row's H_fwd outputs share it in the loss."""
-        if loss not in LOSSES:
-            raise ValueError(f"loss {loss!r}: one of {tuple(LOSSES)}")
-        self.level_input = loss in LEVEL_LOSSES
-        check_envelope(input_dim, output_dim, num_units, num_layers, activation, final_activation, loss=loss, horizon=horizon,
-                       level_input=self.level_input, level_lo=level_lo, level_hi=level_hi)
-        if loss in ("scalar", "scalar_horizon", "vector") and alpha is None:
-            raise ValueError(f"loss {loss!r} needs alpha")
+def make_cfg(input_dim, output_dim, c):
+    """The lg_tube_cfg of one model from the trainer's keywords in `c` (num_units .. level_hi, as HipTubeTrainer names them)."""
+    hz, lv = c["horizon"], c["loss"] in LEVEL_LOSSES
+    return capi.lg_tube_cfg(input_dim=input_dim, output_dim=output_dim, num_units=c["num_units"], num_layers=c["num_layers"],
+                            activation=capi.TUBE_ACT[c["activation"]], loss=capi.TUBE_LOSS[LOSSES[c["loss"]]],
+                            horizon=int(hz is not None), batch_size=c["batch_size"], H_fwd=hz[0] if hz else 0,
+                            H_rev=hz[1] if hz else 0, step_size=c["step_size"], seed=c["seed"],
+                            alpha=c["alpha"] if c["alpha"] is not None else 0.0, delta=c["delta"],
+                            softplus_beta=c["softplus_beta"], lr=c["lr"], gamma=c["gamma"], level_input=int(lv),
+                            level_lo=c["level_lo"] if lv else 0.0, level_hi=c["level_hi"] if lv else 0.0)
+
+
+VIEWS = ("params", "grads", "adam_m", "adam_v", "log", "eval_buf", "starts", "perm", "levels")
+
+
+class TubeTraining:
+    """What HipTubeTrainer (one model) and HipTubeSweep (K models) share: the handle of one C family (PREFIX), the views of every
+    member's buffers, the data and the training calls.  The library runs both through one trainer."""
+    PREFIX = NOUN = None                # "lg_tube_" / "trainer", "lg_tube_sweep_" / "sweep"
+    h = None
+
+    def _open(self, device):
         self.device = torch.device(device)
         if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise LeggedHipError("the tube trainer needs a GPU device (no CPU fallback); got " + str(device))
+            raise LeggedHipError(f"the tube {self.NOUN} needs a GPU device (no CPU fallback); got " + str(device))
         self.lib = load()
-        self.dims = (input_dim, output_dim, num_units, num_layers)
-        self.activation, self.softplus_beta, self.loss = activation, softplus_beta, loss
-        self.horizon = horizon
-        cfg = capi.lg_tube_cfg(input_dim=input_dim, output_dim=output_dim, num_units=num_units, num_layers=num_layers,
-                               activation=capi.TUBE_ACT[activation], loss=capi.TUBE_LOSS[LOSSES[loss]],
-                               horizon=int(horizon is not None), batch_size=batch_size,
-                               H_fwd=horizon[0] if horizon else 0, H_rev=horizon[1] if horizon else 0, step_size=step_size,
-                               seed=seed, alpha=alpha if alpha is not None else 0.0, delta=delta, softplus_beta=softplus_beta,
-                               lr=lr, gamma=gamma, level_input=int(self.level_input),
-                               level_lo=level_lo if self.level_input else 0.0, level_hi=level_hi if self.level_input else 0.0)
-        self.batch_size = batch_size
-        self.data_dim = input_dim - int(self.level_input)          # columns of the data: the level column is not in it
+
+    def _create(self, K, *args):
+        """Creates the handle (args: what the family's create takes before the handle) with its stream and views.  Needs dims."""
+        self.K = K
         torch.cuda.set_device(self.device)
-        self.h = C.c_void_p()
-        self._call("create", C.byref(cfg), C.byref(self.h), obj=False)
+        h = C.c_void_p()
+        self._call("create", *args, C.byref(h), obj=False)
+        self.h = h
         self.use_current_stream()
         self._views()
-        self.load_state_dict(initial_params(input_dim, output_dim, num_units, num_layers, seed))
         self._data = {}
 
-    # ---------------------------------------------------------------- plumbing
     def _call(self, fn, *args, obj=True):
-        rc = getattr(self.lib, "lg_tube_" + fn)(*((self.h,) if obj else ()), *args)
+        rc = getattr(self.lib, self.PREFIX + fn)(*((self.h,) if obj else ()), *args)
         if rc != 0:
-            raise LeggedHipError(f"lg_tube_{fn} failed ({rc}): {self.lib.lg_last_error().decode()}")
+            raise LeggedHipError(f"{self.PREFIX}{fn} failed ({rc}): {self.lib.lg_last_error().decode()}")
 
     def use_current_stream(self):
         self._call("set_stream", C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
 
+    def _member_arg(self, k):
+        """What the family's per-member entries take for member k."""
+        return (k,)
+
     def _views(self):
-        b = capi.lg_tube_buffers()
-        self._call("get_buffers", C.byref(b))
+        """Torch views of every member's buffers, {name of VIEWS: [per member]}, handed to _expose; the parameter layout."""
         ptr = lambda p: C.cast(p, C.c_void_p).value
-        P = int(b.num_params)
-        self.num_params, self.log_cap = P, int(b.log_cap)
-        self.params = device_tensor(ptr(b.params), (P,), "f4", self, self.device)
-        self.grads = device_tensor(ptr(b.grads), (P,), "f4", self, self.device)
-        self.adam_m = device_tensor(ptr(b.adam_m), (P,), "f4", self, self.device)
-        self.adam_v = device_tensor(ptr(b.adam_v), (P,), "f4", self, self.device)
-        self.log = device_tensor(ptr(b.log), (self.log_cap, 4), "f4", self, self.device)
-        self.eval_buf = device_tensor(ptr(b.eval), (4,), "f4", self, self.device)
-        self.starts = device_tensor(ptr(b.starts), (int(b.starts_cap),), "i4", self, self.device) if b.starts_cap else None
-        self.perm = device_tensor(ptr(b.perm), (int(b.perm_cap),), "i4", self, self.device) if b.perm_cap else None
-        self.levels = device_tensor(ptr(b.levels), (int(b.levels_cap),), "f4", self, self.device) if b.levels_cap else None
-        self.step_count = int(b.step)
+        views = {n: [] for n in VIEWS}
+        for k in range(self.K):
+            b = capi.lg_tube_buffers()
+            self._call("get_buffers", *self._member_arg(k), C.byref(b))
+            P = int(b.num_params)
+            self.num_params, self.log_cap, self.step_count = P, int(b.log_cap), int(b.step)
+            for n, p, shape, dt in (("params", b.params, (P,), "f4"), ("grads", b.grads, (P,), "f4"), ("adam_m", b.adam_m, (P,), "f4"),
+                                    ("adam_v", b.adam_v, (P,), "f4"), ("log", b.log, (self.log_cap, 4), "f4"),
+                                    ("eval_buf", b.eval, (4,), "f4"), ("starts", b.starts, (int(b.starts_cap),), "i4"),
+                                    ("perm", b.perm, (int(b.perm_cap),), "i4"), ("levels", b.levels, (int(b.levels_cap),), "f4")):
+                views[n].append(device_tensor(ptr(p), shape, dt, self, self.device) if shape[0] else None)
+        self._expose(views)
         offs, shp = (C.c_int64 * 16)(), (C.c_int64 * 32)()
-        n = self.lib.lg_tube_param_layout(self.h, offs, shp, 16)
-        self.layout = []
-        for (key, shape), i in zip(param_shapes(*self.dims), range(n)):
-            o = int(offs[i])
-            self.layout.append((key, o, shape))
+        n = getattr(self.lib, self.PREFIX + "param_layout")(self.h, offs, shp, 16)
+        self.layout = [(key, int(offs[i]), shape) for (key, shape), i in zip(param_shapes(*self.dims), range(n))]
 
-    # ---------------------------------------------------------------- model state
-    def state_dict(self):
-        """The reference MLP's keys (layers.{0,2,4,...}.weight / .bias); loads into deep_tube_learning.models.MLP."""
-        return OrderedDict((k, self.params[o:o + _numel(s)].view(s).detach().clone()) for k, o, s in self.layout)
+    def _state_of(self, params):
+        return OrderedDict((k, params[o:o + _numel(s)].view(s).detach().clone()) for k, o, s in self.layout)
 
-    def load_state_dict(self, sd):
+    def _load_params(self, params, sd):
         want = [k for k, _, _ in self.layout]
         if list(sd.keys()) != want:
             raise KeyError(f"state dict keys {list(sd.keys())} != {want}")
         for k, o, s in self.layout:
             if tuple(sd[k].shape) != tuple(s):
                 raise ValueError(f"{k}: shape {tuple(sd[k].shape)} != {tuple(s)}")
-            self.params[o:o + _numel(s)].copy_(sd[k].reshape(-1).to(self.device, torch.float32))
-        self._call("params_changed")
+            params[o:o + _numel(s)].copy_(sd[k].reshape(-1).to(self.device, torch.float32))
 
     # ---------------------------------------------------------------- data
     def set_data(self, train, test=None):
-        """train / test: TubeDataset-like (data, target) or ScalarHorizonTubeDataset-like (w, z, v)."""
+        """train / test: TubeDataset-like (data, target) or ScalarHorizonTubeDataset-like (w, z, v); shared by all members."""
         for which, ds in ((0, train), (1, test)):
             if ds is None:
                 continue
             if self.horizon is not None:
                 w, z, v = (t.to(self.device, torch.float32).contiguous() for t in (ds.w, ds.z, ds.v))
                 if (ds.H_fwd, ds.H_rev) != tuple(self.horizon):
-                    raise ValueError("dataset horizon != trainer horizon")
+                    raise ValueError(f"dataset horizon != {self.NOUN} horizon")
                 check_window_dims(self.dims[0], self.horizon, z.shape[2], v.shape[2], self.level_input)
                 self._data[which] = (w, z, v)
                 self._call("set_data", which, C.c_void_p(w.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(v.data_ptr()),
@@ -201,7 +198,8 @@ class HipTubeTrainer:
         self._call("begin_epoch", int(epoch))
 
     def step(self, count=None, rows=None):
-        """One Adam step on the next `count` rows of the epoch permutation, or on `rows` (int32 device tensor)."""
+        """One Adam step of every member: on the next `count` rows of each member's own epoch permutation, or on `rows`
+        (int32 device tensor) shared by all members."""
         if rows is not None:
             rows = rows.to(self.device, torch.int32).contiguous()
             self._rows_keep = rows
@@ -214,12 +212,75 @@ class HipTubeTrainer:
         self._call("set_step", int(step))
         self.step_count = int(step)
 
-    def read_log(self, first, last):
-        """Host copy (rows = steps first..last, 1-based, at most log_cap of them) of [loss, lr after the step, grad_norm, rows]."""
+    def _log_rows(self, log, first, last):
         if last - first + 1 > self.log_cap:
             raise ValueError("more steps than the device log holds")
         idx = torch.arange(first - 1, last, device=self.device) % self.log_cap
-        return self.log[idx].cpu()
+        return log[idx].cpu()
+
+    def close(self):
+        if getattr(self, "h", None):
+            for n in VIEWS:
+                setattr(self, n, None)
+            self._call("destroy")
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipTubeTrainer(TubeTraining):
+    PREFIX, NOUN = "lg_tube_", "trainer"
+
+    def __init__(self, input_dim, output_dim, num_units=32, num_layers=2, activation="relu", softplus_beta=1.0,
+                 loss="scalar", alpha=0.8, delta=1.0, lr=1e-3, gamma=0.1, step_size=10000, batch_size=2048, seed=42,
+                 horizon=None, final_activation=None, device="cuda:0", level_lo=0.0, level_hi=1.0):
+        """horizon: None for the row datasets, (H_fwd, H_rev) for ScalarHorizonTubeDataset.  loss "scalar_level" /
+        "vector_level": the level-conditioned tube -- input_dim counts the level column (the last one), the data has
+        input_dim - 1 columns, every row of a step draws its level uniformly from [level_lo, level_hi), alpha is not read.
+        With a horizon the window item gains the level as its last column and the row's H_fwd outputs share it in the loss."""
+        if loss not in LOSSES:
+            raise ValueError(f"loss {loss!r}: one of {tuple(LOSSES)}")
+        self.level_input = loss in LEVEL_LOSSES
+        check_envelope(input_dim, output_dim, num_units, num_layers, activation, final_activation, loss=loss, horizon=horizon,
+                       level_input=self.level_input, level_lo=level_lo, level_hi=level_hi)
+        if loss in ("scalar", "scalar_horizon", "vector") and alpha is None:
+            raise ValueError(f"loss {loss!r} needs alpha")
+        self._open(device)
+        self.dims = (input_dim, output_dim, num_units, num_layers)
+        self.activation, self.softplus_beta, self.loss = activation, softplus_beta, loss
+        self.horizon = horizon
+        cfg = make_cfg(input_dim, output_dim, dict(
+            num_units=num_units, num_layers=num_layers, activation=activation, softplus_beta=softplus_beta, loss=loss, alpha=alpha,
+            delta=delta, lr=lr, gamma=gamma, step_size=step_size, batch_size=batch_size, seed=seed, horizon=horizon,
+            level_lo=level_lo, level_hi=level_hi))
+        self.batch_size = batch_size
+        self.data_dim = input_dim - int(self.level_input)          # columns of the data: the level column is not in it
+        self._create(1, C.byref(cfg))
+        self.load_state_dict(initial_params(input_dim, output_dim, num_units, num_layers, seed))
+
+    def _member_arg(self, k):
+        return ()
+
+    def _expose(self, views):           # the one member's views as attributes: self.params, self.adam_m, ...
+        for n, v in views.items():
+            setattr(self, n, v[0])
+
+    # ---------------------------------------------------------------- model state
+    def state_dict(self):
+        """The reference MLP's keys (layers.{0,2,4,...}.weight / .bias); loads into deep_tube_learning.models.MLP."""
+        return self._state_of(self.params)
+
+    def load_state_dict(self, sd):
+        self._load_params(self.params, sd)
+        self._call("params_changed")
+
+    def read_log(self, first, last):
+        """Host copy (rows = steps first..last, 1-based, at most log_cap of them) of [loss, lr after the step, grad_norm, rows]."""
+        return self._log_rows(self.log, first, last)
 
     def evaluate(self):
         """Launches the eval over the test split; returns a device tensor [loss, fraction fw > w, mean |w - fw| where fw > w,
@@ -254,18 +315,8 @@ class HipTubeTrainer:
         x = self._f32(x)
         if x.dim() != 2 or x.shape[1] != self.data_dim or x.shape[0] < 1:
             raise ValueError(f"x must be (n >= 1, {self.data_dim}); got {tuple(x.shape)}")
-        levels = self._f32(torch.as_tensor(levels)).reshape(-1)
-        if not 1 <= levels.numel() <= capi.TUBE_MAX_LEVELS:
-            raise ValueError(f"{levels.numel()} levels: 1..{capi.TUBE_MAX_LEVELS}")
-        count, rp = x.shape[0], None
-        if rows is not None:
-            rows = rows.to(self.device, torch.int32).contiguous().reshape(-1)
-            count = rows.numel()
-            if count < 1:
-                raise ValueError("rows is empty")
-            if int(rows.min()) < 0 or int(rows.max()) >= x.shape[0]:
-                raise IndexError(f"rows must lie in 0..{x.shape[0] - 1}")
-            rp = C.c_void_p(rows.data_ptr())
+        levels = self._levels_arg(levels)
+        rows, count, rp = self._rows_arg(rows, x.shape[0])
         out = torch.empty(count, levels.numel(), self.dims[1], device=self.device, dtype=torch.float32)
         self._call("predict_levels", C.c_void_p(x.data_ptr()), rp, count, C.c_void_p(levels.data_ptr()), levels.numel(),
                    C.c_void_p(out.data_ptr()))
@@ -279,15 +330,7 @@ class HipTubeTrainer:
         x = self._f32(x)
         if x.dim() != 2 or x.shape[1] != self.dims[0] or x.shape[0] < 1:
             raise ValueError(f"x must be (n >= 1, {self.dims[0]}); got {tuple(x.shape)}")
-        count, rp = x.shape[0], None
-        if rows is not None:
-            rows = rows.to(self.device, torch.int32).contiguous().reshape(-1)
-            count = rows.numel()
-            if count < 1:
-                raise ValueError("rows is empty")
-            if int(rows.min()) < 0 or int(rows.max()) >= x.shape[0]:
-                raise IndexError(f"rows must lie in 0..{x.shape[0] - 1}")
-            rp = C.c_void_p(rows.data_ptr())
+        rows, count, rp = self._rows_arg(rows, x.shape[0])
         out = torch.empty(count, self.dims[1], device=self.device, dtype=torch.float32)
         self._call("predict", C.c_void_p(x.data_ptr()), rp, count, C.c_void_p(out.data_ptr()))
         self._keep = (x, rows)
@@ -336,9 +379,7 @@ class HipTubeTrainer:
         self._need_level("predict_windows_levels")
         if self.horizon is None:
             raise ValueError("predict_windows_levels: not a horizon model; a flat model predicts rows: predict_levels(x, levels)")
-        levels = self._f32(torch.as_tensor(levels)).reshape(-1)
-        if not 1 <= levels.numel() <= capi.TUBE_MAX_LEVELS:
-            raise ValueError(f"{levels.numel()} levels: 1..{capi.TUBE_MAX_LEVELS}")
+        levels = self._levels_arg(levels)
         w, z, v, n, T, env, start = self._windows(ds, env, start)
         out = torch.empty(env.numel(), levels.numel(), self.horizon[0], device=self.device, dtype=torch.float32)
         self._call("predict_windows_levels", C.c_void_p(w.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(v.data_ptr()), n, T,
@@ -358,12 +399,7 @@ class HipTubeTrainer:
             raise ValueError(f"x must be (n_seq >= 1, T >= 1, {self.dims[0]}); got {tuple(x.shape)}")
         if not 0 <= int(fb) <= min(self.dims[:2]):
             raise ValueError(f"fb={fb}: 0..min(input_dim, output_dim) = {min(self.dims[:2])}")
-        rp = None
-        if reseed is not None:
-            reseed = reseed.to(self.device).ne(0).to(torch.uint8).contiguous()
-            if tuple(reseed.shape) != tuple(x.shape[:2]):
-                raise ValueError(f"reseed must be {tuple(x.shape[:2])}; got {tuple(reseed.shape)}")
-            rp = C.c_void_p(reseed.data_ptr())
+        reseed, rp = self._reseed_arg(reseed, x)
         out = torch.empty(x.shape[0], x.shape[1], self.dims[1], device=self.device, dtype=torch.float32)
         self._call("rollout", C.c_void_p(x.data_ptr()), x.shape[0], x.shape[1], int(fb), rp, C.c_void_p(out.data_ptr()))
         self._keep = (x, reseed)
@@ -391,12 +427,7 @@ class HipTubeTrainer:
         if ((taps - 1) * dN + 1) * fb > capi.TUBE_RING_MAX:
             raise ValueError(f"ring ((taps - 1) * dN + 1) * fb = {((taps - 1) * dN + 1) * fb} floats per sequence exceeds "
                              f"{capi.TUBE_RING_MAX}")
-        rp = None
-        if reseed is not None:
-            reseed = reseed.to(self.device).ne(0).to(torch.uint8).contiguous()
-            if tuple(reseed.shape) != tuple(x.shape[:2]):
-                raise ValueError(f"reseed must be {tuple(x.shape[:2])}; got {tuple(reseed.shape)}")
-            rp = C.c_void_p(reseed.data_ptr())
+        reseed, rp = self._reseed_arg(reseed, x)
         out = torch.empty(x.shape[0], x.shape[1], self.dims[1], device=self.device, dtype=torch.float32)
         self._call("rollout_window", C.c_void_p(x.data_ptr()), x.shape[0], x.shape[1], fb, taps, dN, stride if taps > 1 else 0, rp,
                    C.c_void_p(out.data_ptr()))
@@ -406,17 +437,31 @@ class HipTubeTrainer:
     def _f32(self, t):
         return t.to(self.device, torch.float32).contiguous()
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.params = self.grads = self.adam_m = self.adam_v = self.log = self.eval_buf = self.starts = self.perm = self.levels = None
-            self.lib.lg_tube_destroy(self.h)
-            self.h = None
+    def _rows_arg(self, rows, n):
+        """The checked row list of a query over n rows: (rows on the device or None, count, pointer or None)."""
+        if rows is None:
+            return None, n, None
+        rows = rows.to(self.device, torch.int32).contiguous().reshape(-1)
+        if rows.numel() < 1:
+            raise ValueError("rows is empty")
+        if int(rows.min()) < 0 or int(rows.max()) >= n:
+            raise IndexError(f"rows must lie in 0..{n - 1}")
+        return rows, rows.numel(), C.c_void_p(rows.data_ptr())
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _levels_arg(self, levels):
+        levels = self._f32(torch.as_tensor(levels)).reshape(-1)
+        if not 1 <= levels.numel() <= capi.TUBE_MAX_LEVELS:
+            raise ValueError(f"{levels.numel()} levels: 1..{capi.TUBE_MAX_LEVELS}")
+        return levels
+
+    def _reseed_arg(self, reseed, x):
+        """The checked reseed flags of a roll-out over x (n_seq, T, .): (uint8 on the device or None, pointer or None)."""
+        if reseed is None:
+            return None, None
+        reseed = reseed.to(self.device).ne(0).to(torch.uint8).contiguous()
+        if tuple(reseed.shape) != tuple(x.shape[:2]):
+            raise ValueError(f"reseed must be {tuple(x.shape[:2])}; got {tuple(reseed.shape)}")
+        return reseed, C.c_void_p(reseed.data_ptr())
 
 
 def _numel(shape):

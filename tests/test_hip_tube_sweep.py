@@ -1,7 +1,9 @@
 """HipTubeSweep (k_tube_rows_sweep / k_tube_adam_sweep; lg_tube_sweep_*): member k of a sweep is, bit for bit, the single
 HipTubeTrainer built from member k's configuration and given the same calls -- on every loss and activation path, the horizon
 dataset, a tail step, explicit rows, K = 1 and K = LG_TUBE_SWEEP_MAX -- plus run-to-run determinism, the hand-over to
-HipTubeModel, the refusals, and train_tube.py --sweep -> evaluate_tube.py end to end.
+HipTubeModel, the refusals, and train_tube.py --sweep -> evaluate_tube.py end to end.  Both run on one host path (TubeTrainer in
+tube_api.hip); test_regrown_buffers_reach_the_kernels says that the kernels see every buffer that set_data regrew, through the
+host copy with one member and through the device copy of the member array with K.
 
 Every comparison is on the bits (floats viewed as int32), so a nan in an eval vector compares like any other value.
 """
@@ -182,6 +184,52 @@ def test_largest_sweep():
     finally:
         for obj in [sw] + list(singles.values()):
             obj.close()
+
+
+LEVELS3 = [dict(lr=1e-3, delta=1.0, seed=3, level_lo=0.5, level_hi=1.0), dict(lr=3e-3, delta=0.5, seed=4),
+           dict(lr=1e-2, delta=0.25, seed=5, level_lo=0.1, level_hi=0.9)]
+
+
+@pytest.mark.parametrize("batch", [32, 8])
+@pytest.mark.parametrize("kind", ["trainer", "sweep"])
+def test_regrown_buffers_reach_the_kernels(kind, batch):
+    """The training kernels read every buffer pointer from the trainer's member array: the host copy with one member, the device
+    copy with K.  set_data frees and reallocates starts, levels, perm and evpart when a split outgrows them, so a copy left stale
+    would send the next launch to freed memory.  A: a 16-env split (8 test envs), then the 40-env split (20 test envs): at batch 8 all four buffers regrow,
+    at batch 32 starts and levels start at the batch's size.  B: the 40-env split alone.  Horizon vector_level shape of
+    test_horizon_dataset with the level column.  Every buffer, the log and the eval vector are bit-equal."""
+    Hf, Hr, T = 4, 2, 12
+    g = torch.Generator().manual_seed(7)
+    w, z, v = torch.rand(60, T, generator=g), torch.randn(60, T, 2, generator=g), torch.randn(60, T, 2, generator=g)
+    split = lambda a, b: _Horizon(w[a:b], z[a:b], v[a:b], Hf, Hr)
+    shared = dict(num_units=128, num_layers=2, activation="softplus", softplus_beta=5.0, loss="vector_level", batch_size=batch,
+                  horizon=(Hf, Hr))
+    I = Hr + 2 + (Hr + Hf) * 2 + 1
+    make = (lambda: _single(I, Hf, LEVELS3[0], **shared)) if kind == "trainer" else (lambda: _sweep(I, Hf, LEVELS3, **shared))
+    pick = (lambda a: [a]) if kind == "trainer" else (lambda a: list(a))
+    A, B = make(), make()
+    try:
+        A.set_data(split(0, 16), split(40, 48))
+        got = []
+        for obj in (A, B):
+            obj.set_data(split(0, 40), split(40, 60))
+            obj.begin_epoch(0)
+            obj.step(batch)
+            obj.step(8)                                               # at batch 32 the epoch's tail
+            torch.cuda.synchronize()
+            state = {n: [_bits(t).clone() for t in pick(getattr(obj, n))]
+                     for n in ("params", "grads", "adam_m", "adam_v", "perm", "starts", "levels")}
+            state["log"] = [_bits(obj.read_log(1, 2))] if kind == "trainer" else [_bits(obj.read_log(k, 1, 2)) for k in range(3)]
+            state["eval"] = [_bits(e) for e in pick(obj.evaluate())]
+            got.append(state)
+        for name in ("perm", "starts", "levels"):                    # A's did grow to the second split
+            assert all(tuple(t.shape) == (40,) for t in got[0][name]), name
+        for name in got[0]:
+            for k, (a, b) in enumerate(zip(got[0][name], got[1][name])):
+                assert a.shape == b.shape and torch.equal(a, b), f"{name} of member {k}"
+    finally:
+        A.close()
+        B.close()
 
 
 def _member_states(members, shared, train, test, steps=3):
