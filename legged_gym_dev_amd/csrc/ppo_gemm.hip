@@ -856,9 +856,27 @@ static GemmLaunch gemm_dx(const GemmArgs *g, int nz, hipStream_t s) {
     if (g_gemm_x6) return launch_gemm<true, false, 1>(*g, nz, s);
     return launch_gemm_ref<true, false, 1>(*g, nz, 1, s);
 }
-extern "C" void ppok_gemm_fwd(const GemmArgs *g, int nz, hipStream_t s) { gemm_fwd(g, nz, s); }
-extern "C" void ppok_gemm_dx(const GemmArgs *g, int nz, hipStream_t s) { gemm_dx(g, nz, s); }
-extern "C" void ppok_gemm_dw(const GemmArgs *g, int nz, hipStream_t s) { launch_gemm_dw(*g, nz, dw_splits(*g, nz), s); }
+// Host-side trace of what the three entry points launched, for tests/test_hip_ppo_update.py: per launch {kind 0 / 1 / 2 = forward / input
+// gradient / weight gradient, nz, kernel (GK_*), reduction slices} as the launcher itself returned them, in launch order.  The first
+// GEMM_TRACE_CAP launches since the last read are kept, later ones dropped; ppok_debug_gemm_trace copies up to `cap` entries (4 ints
+// each) to `out`, clears the trace and returns how many it held.  Host code only; not synchronised (one learner per process in the tests).
+#define GEMM_TRACE_CAP 64
+static int g_gemm_trace[GEMM_TRACE_CAP][4];
+static int g_gemm_trace_n = 0;
+static void gemm_trace(int kind, int nz, const GemmLaunch &l) {
+    if (g_gemm_trace_n < 0 || g_gemm_trace_n >= GEMM_TRACE_CAP) return;
+    int *e = g_gemm_trace[g_gemm_trace_n++];
+    e[0] = kind; e[1] = nz; e[2] = l.kernel; e[3] = l.slices;
+}
+extern "C" int ppok_debug_gemm_trace(int *out, int cap) {
+    const int n = g_gemm_trace_n < GEMM_TRACE_CAP ? g_gemm_trace_n : GEMM_TRACE_CAP;
+    for (int k = 0; out && k < n && k < cap; ++k) memcpy(out + 4 * k, g_gemm_trace[k], sizeof(g_gemm_trace[k]));
+    g_gemm_trace_n = 0;
+    return n;
+}
+extern "C" void ppok_gemm_fwd(const GemmArgs *g, int nz, hipStream_t s) { gemm_trace(0, nz, gemm_fwd(g, nz, s)); }
+extern "C" void ppok_gemm_dx(const GemmArgs *g, int nz, hipStream_t s) { gemm_trace(1, nz, gemm_dx(g, nz, s)); }
+extern "C" void ppok_gemm_dw(const GemmArgs *g, int nz, hipStream_t s) { gemm_trace(2, nz, launch_gemm_dw(*g, nz, dw_splits(*g, nz), s)); }
 
 // Debug entry that launches what the product launches (tests/test_hip_ppo_gemm.py): kind 0 / 1 / 2 = forward / input gradient / weight
 // gradient on the caller's GemmArgs as it stands -- nz problems, every field as given.  kind 2: splits = 0 takes the product's own

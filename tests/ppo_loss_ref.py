@@ -48,30 +48,35 @@ SINGLE_REGIME_TABLE = tuple(t for t in TABLE if regime_of(*t) == (CLIPPED, CLIPP
 
 def _model(case, dtype):
     m = case["meta"]
-    ac = ppo_torch.ActorCritic(m["O"], m["O"], m["A"], m["hidden"], m["critic_hidden"], m["activation"], 1.0)
+    ac = ppo_torch.ActorCritic(m["O"], m.get("OC", m["O"]), m["A"], m["hidden"], m["critic_hidden"], m["activation"], 1.0)
     ac.load_state_dict(case["params"])
     return ac.to(dtype)
 
 
-def _build(O, A, hidden, activation, R, seed, critic_hidden, table):
+def _build(O, A, hidden, activation, R, seed, critic_hidden, table, OC=None):
+    """OC (tests/ppo_update_ref.py): a privileged critic with OC != O inputs and observations of its own, drawn from a generator of
+    their own, so that every draw of a case without them is what it was."""
     hidden = list(hidden)
     critic_hidden = list(critic_hidden) if critic_hidden is not None else hidden
     g = torch.Generator().manual_seed(seed)
     f64 = torch.float64
     with torch.random.fork_rng():
         torch.manual_seed(seed)
-        ac = ppo_torch.ActorCritic(O, O, A, hidden, critic_hidden, activation, 1.0)
+        ac = ppo_torch.ActorCritic(O, O if OC is None else OC, A, hidden, critic_hidden, activation, 1.0)
     with torch.no_grad():
         std = (ac.std.double() * (0.6 + 0.8 * torch.rand(A, generator=g, dtype=f64))).float()
         ac.std.copy_(std)
     params = {k: v.detach().clone() for k, v in ac.state_dict().items()}
     case = {"params": params, "meta": dict(O=O, A=A, hidden=hidden, critic_hidden=critic_hidden, activation=activation, R=R)}
+    if OC is not None:
+        case["meta"]["OC"] = OC
     ac64 = _model(case, f64)
     std64 = std.double()
     obs = torch.randn(R, O, generator=g, dtype=f64).float()
+    cobs = obs if OC is None else torch.randn(R, OC, generator=torch.Generator().manual_seed(seed + 1000003), dtype=f64).float()
     with torch.no_grad():
         mu_new = ac64.actor(obs.double())
-        v_new = ac64.critic(obs.double()).squeeze(-1)
+        v_new = ac64.critic(cobs.double()).squeeze(-1)
     sigma = (std64 * (0.8 + 0.45 * torch.rand(A, generator=g, dtype=f64))).float()
     mu = (mu_new + 0.3 * torch.randn(R, A, generator=g, dtype=f64)).float()
     actions = (mu_new + std64 * torch.randn(R, A, generator=g, dtype=f64)).float()
@@ -84,6 +89,8 @@ def _build(O, A, hidden, activation, R, seed, critic_hidden, table):
     case.update(obs=obs, actions=actions, mu=mu, sigma=sigma, log_prob=(lp_new - torch.log(r)).float(), values=(v_new - d).float(),
                 returns=(v_new - e).float(), advantages=adv.float(), targets=targets, surrogate_regime=labels[:, 0],
                 value_regime=labels[:, 1])
+    if OC is not None:
+        case["critic_obs"] = cobs
     return case
 
 
@@ -112,7 +119,7 @@ def batch_of(case, rows=None, dtype=torch.float64):
     idx = slice(None) if rows is None else rows
     pick = lambda k: case[k][idx].to(dtype)
     obs = pick("obs")
-    return (obs, obs, pick("actions"), pick("values").unsqueeze(-1), pick("advantages").unsqueeze(-1), pick("returns").unsqueeze(-1),
+    return (obs, pick("critic_obs") if "critic_obs" in case else obs, pick("actions"), pick("values").unsqueeze(-1), pick("advantages").unsqueeze(-1), pick("returns").unsqueeze(-1),
             pick("log_prob").unsqueeze(-1), pick("mu"), case["sigma"].to(dtype).expand(obs.shape[0], -1))
 
 
@@ -133,10 +140,10 @@ def reference(case, alg, rows=None, dtype=torch.float64):
 def row_quantities(case, clip=CLIP):
     """What the branches of the loss look at, per row in float64: ratio, v_new - v_old, the two value losses, the advantage."""
     ac = _model(case, torch.float64)
-    obs, _, actions, v_old, adv, ret, lp_old, _, _ = batch_of(case)
+    obs, cobs, actions, v_old, adv, ret, lp_old, _, _ = batch_of(case)
     with torch.no_grad():
         mu = ac.actor(obs)
-        v = ac.critic(obs)
+        v = ac.critic(cobs)
         lp = torch.distributions.Normal(mu, ac.std.expand_as(mu)).log_prob(actions).sum(-1)
     d = (v - v_old).squeeze(-1)
     vc = v_old + (v - v_old).clamp(-clip, clip)

@@ -6,6 +6,10 @@ The gradient tests here update on the rollout's own parameters with 12 actions: 
 inside the surrogate clip and on the tie branch of the clipped value loss.  The other branches of the loss, value_loss_coef != 1,
 use_clipped_value_loss = False, 1 .. 16 actions and the second trip of the head kernels' tile loops are checked against float64, per
 head kernel, in tests/test_hip_ppo_loss.py (inputs: tests/ppo_loss_ref.py, their conditions: tests/test_ppo_loss_host.py).
+The whole feed-forward minibatch -- forward, head and backward chain as lg_ppo_minibatch_backward schedules them -- is checked against
+float64 with a band on every parameter tensor and the launch of every GEMM named per case, at depths 1 .. 4, row counts off every tile
+grid, a privileged critic, every activation, the side stream on and off and deterministic mode, in tests/test_hip_ppo_update.py
+(tests/ppo_update_ref.py, tests/test_ppo_update_host.py).
 
 The rollout half is checked against float64 elsewhere: act() on every dispatch path of the one-launch forward and on the per-layer path,
 with per-action std, a numpy Philox and derived log-prob bounds, in tests/test_hip_ppo_act.py (tests/ppo_act_ref.py,
@@ -144,8 +148,9 @@ def test_returns_and_gradients_match_torch_at_baseline_size(O):
 
 
 def _returns_and_gradients(O, hidden, N, T, band_frac=5e-4):
-    """O: the observation widths of the four tasks.  235, 169 and 65 are not multiples of 8: the minibatch gathers and the
-    first layer's weight planes then carry zero pad columns (rows of 240 / 176 / 72) and the first layer's weight gradient is
+    """O: the observation widths of the four tasks.  None of 48, 235, 169 and 65 is a multiple of 32: the minibatch gathers and the
+    first layer's weight planes then carry zero pad columns (lg_ppo_create pads Op and OCp to whole k-tiles of 32: rows of
+    64 / 256 / 192 / 96) and the first layer's weight gradient is
     computed on the padded width and stored on the true one.  hidden = [128, 64, 32]: the reference's own flat-task policy
     (anymal_c_flat_config.py:62-65), whose 32-wide last hidden layer takes the k_head_fused<32> path."""
     A = 12
