@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "ppo_launch.h"
+#include "ppo_loss.h"
 #include "ppo_split_bf16.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -175,11 +176,11 @@ __global__ void __launch_bounds__(256) k_loss(PpoDev P, const float *__restrict_
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     const float *std = P.params + P.off_std;
     const float invR = 1.0f / (float)R;
-    // per-thread partials at fixed slots: [0..MA) dstd, [MA..2MA) dbias_actor_head, 2MA dbias_critic_head, kl, vloss, sloss
+    // per-thread partials at the fixed slots of ppo_loss.h
     constexpr int MA = LG_PPO_MAX_A;
-    float part[2 * MA + 4];
+    float part[PPO_NSUMS];
 #pragma unroll
-    for (int k = 0; k < 2 * MA + 4; ++k) part[k] = 0.f;
+    for (int k = 0; k < PPO_NSUMS; ++k) part[k] = 0.f;
     // the two logarithms of every action dimension depend on sigma only: once per block instead of once per row
     __shared__ float s_logs[MA], s_logr[MA];
     if ((int)threadIdx.x < A) {
@@ -192,6 +193,8 @@ __global__ void __launch_bounds__(256) k_loss(PpoDev P, const float *__restrict_
         const float4 sc = reinterpret_cast<const float4 *>(P.mb_scalars)[r];
         const float v_old = sc.x, ret = sc.y, adv = sc.z, lp_old = sc.w;
         float lp = 0.f, kl = 0.f, dd[MA];
+        // The Gaussian terms stay here, in division form: the fused heads (ppo_loss.h) multiply by staged reciprocals, which
+        // rounds differently, and this path keeps its last bits.
 #pragma unroll
         for (int a = 0; a < MA; ++a) {
             dd[a] = 0.f;
@@ -204,46 +207,29 @@ __global__ void __launch_bounds__(256) k_loss(PpoDev P, const float *__restrict_
                 kl += s_logr[a] + (so * so + (mo - m) * (mo - m)) / (2.0f * s * s) - 0.5f;
             }
         }
-        const float ratio = expf(lp - lp_old);
-        const float rc = fminf(fmaxf(ratio, 1.0f - P.clip), 1.0f + P.clip);
-        const float s1 = -adv * ratio, s2 = -adv * rc;
-        const float dl_dlp = (s1 >= s2 ? -adv : 0.0f) * ratio * invR;        // torch.max ties: see DESIGN.md
+        const PpoSurrogate sg = ppo_surrogate(P.clip, lp, lp_old, adv, invR);
 #pragma unroll
         for (int a = 0; a < MA; ++a)
             if (a < A) {
                 const float s = std[a], d = dd[a];
-                const float g = dl_dlp * d / (s * s);
+                const float g = sg.dl_dlp * d / (s * s);
                 dmu[(size_t)r * A + a] = g;
-                part[MA + a] = g;
-                part[a] = dl_dlp * (d * d / (s * s * s) - 1.0f / s) - P.entropy_coef * invR / s;
+                part[PPO_SUM_DBIAS_ACTOR + a] = g;
+                part[PPO_SUM_DSTD + a] = sg.dl_dlp * (d * d / (s * s * s) - 1.0f / s) - P.entropy_coef * invR / s;
             }
-        const float v = v_new[r];
-        float lv, dv;
-        if (P.clipped_value) {
-            const float dvv = v - v_old;
-            const float vc = v_old + fminf(fmaxf(dvv, -P.clip), P.clip);
-            const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
-            const float inside = (dvv >= -P.clip && dvv <= P.clip) ? 1.0f : 0.0f;
-            lv = fmaxf(l1, l2);
-            if (l1 > l2) dv = 2.0f * (v - ret);
-            else if (l1 < l2) dv = 2.0f * (vc - ret) * inside;
-            else dv = (v - ret) + (vc - ret) * inside;
-        } else {
-            lv = (ret - v) * (ret - v);
-            dv = 2.0f * (v - ret);
-        }
-        dv *= P.value_coef * invR;
+        const PpoValue vl = ppo_value(P.clipped_value, P.clip, v_new[r], v_old, ret);
+        const float dv = vl.dv * (P.value_coef * invR);
         dval[r] = dv;
-        part[2 * MA] = dv;
-        part[2 * MA + 1] = kl;
-        part[2 * MA + 2] = lv;
-        part[2 * MA + 3] = fmaxf(s1, s2);
+        part[PPO_SUM_DBIAS_CRITIC] = dv;
+        part[PPO_SUM_KL] = kl;
+        part[PPO_SUM_VLOSS] = vl.lv;
+        part[PPO_SUM_SLOSS] = fmaxf(sg.s1, sg.s2);
     }
     // wave64 butterfly per partial, one LDS slot per wave (summed in wave order below), one global atomic per block and partial
-    __shared__ float red[4][2 * MA + 4];
+    __shared__ float red[4][PPO_NSUMS];
 #pragma unroll
-    for (int k = 0; k < 2 * MA + 4; ++k) {
-        if (k >= 2 * MA || (k % MA) < A) {
+    for (int k = 0; k < PPO_NSUMS; ++k) {
+        if (ppo_sum_live(k, A)) {
             float v = part[k];
 #pragma unroll
             for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
@@ -252,14 +238,9 @@ __global__ void __launch_bounds__(256) k_loss(PpoDev P, const float *__restrict_
     }
     __syncthreads();
     const int k = threadIdx.x;
-    if (k < 2 * MA + 4 && (k >= 2 * MA || (k % MA) < A)) {
+    if (k < PPO_NSUMS && ppo_sum_live(k, A)) {
         const float v = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-        if (k < MA) acc_add(P, &P.grads[P.off_std + k], v);
-        else if (k < 2 * MA) acc_add(P, &P.grads[P.off_bias_actor_head + (k - MA)], v);
-        else if (k == 2 * MA) acc_add(P, &P.grads[P.off_bias_critic_head], v);
-        else if (k == 2 * MA + 1) acc_add(P, &P.grads[P.num_params], v);             // KL sum rides in the grad buffer tail
-        else if (k == 2 * MA + 2) acc_add(P, &P.loss_acc[0], v);
-        else acc_add(P, &P.loss_acc[1], v);
+        acc_add(P, ppo_sum_dest(P, k, P.off_bias_actor_head, P.off_bias_critic_head), v);
     }
 }
 
@@ -272,7 +253,7 @@ __global__ void __launch_bounds__(256) k_loss(PpoDev P, const float *__restrict_
 #define HEAD_ROWS 64
 #define HEAD_GRID 192
 #define HEAD_NET_GRID 384                                  // workgroups per network of k_head_net (= scratch rows per network)
-#define HEAD_PART_STRIDE(H3) ((LG_PPO_MAX_A + 1) * (H3) + 2 * LG_PPO_MAX_A + 4)
+#define HEAD_PART_STRIDE(H3) ((LG_PPO_MAX_A + 1) * (H3) + PPO_NSUMS)
 template <int H3>
 __global__ void __launch_bounds__(256) k_head_fused(PpoDev P, const float *__restrict__ xa_g, const float *__restrict__ xc_g,
                                                     float *__restrict__ dza_g, float *__restrict__ dzc_g, int64_t w_a, int64_t b_a,
@@ -282,24 +263,23 @@ __global__ void __launch_bounds__(256) k_head_fused(PpoDev P, const float *__res
     __shared__ float xa[HEAD_ROWS * LDX], xc[HEAD_ROWS * LDX];
     __shared__ float wa[MA * H3], wc[H3];
     __shared__ float mus[HEAD_ROWS][MA + 1], dmus[HEAD_ROWS][MA + 1];    // [..][MA]: value / d value
-    // per-action constants of the Gaussian terms (row independent): sigma_old^2, 1/(2 s^2), 1/s^2, 1/s, ln s + ln sqrt(2 pi),
-    // ln(s / s_old + 1e-5) -- so the per-row loss needs no log and no division
-    __shared__ float red[2 * MA + 4], s_so2[MA], s_i2s2[MA], s_is2[MA], s_is[MA], s_lgs[MA], s_klc[MA];
+    // per-action constants of the Gaussian terms (ppo_gauss)
+    __shared__ float red[PPO_NSUMS], s_so2[MA], s_i2s2[MA], s_is2[MA], s_is[MA], s_lgs[MA], s_klc[MA];
     if (tid < MA) {
-        const float sg = tid < A ? P.params[P.off_std + tid] : 1.f, so = tid < A ? P.st_sigma[tid] : 1.f;
-        s_so2[tid] = so * so; s_i2s2[tid] = 1.0f / (2.0f * sg * sg); s_is2[tid] = 1.0f / (sg * sg); s_is[tid] = 1.0f / sg;
-        s_lgs[tid] = logf(sg) + 0.9189385332046727f; s_klc[tid] = logf(sg / so + 1.e-5f) - 0.5f;
+        const PpoGauss gs = ppo_gauss(tid < A ? P.params[P.off_std + tid] : 1.f, tid < A ? P.st_sigma[tid] : 1.f);
+        s_so2[tid] = gs.so2; s_i2s2[tid] = gs.i2s2; s_is2[tid] = gs.is2; s_is[tid] = gs.is;
+        s_lgs[tid] = gs.lgs; s_klc[tid] = gs.klc;
     }
     for (int i = tid; i < A * H3; i += 256) wa[i] = P.params[w_a + i];
     for (int i = tid; i < H3; i += 256) wc[i] = P.params[w_c + i];
-    if (tid < 2 * MA + 4) red[tid] = 0.f;
+    if (tid < PPO_NSUMS) red[tid] = 0.f;
     // backward accumulators of this thread's column, kept in registers across all row tiles of the block
     const int c = tid % H3, half = tid / H3;
-    float dwa[MA], dwc = 0.f, dba = 0.f, dbc = 0.f, part[2 * MA + 4];
+    float dwa[MA], dwc = 0.f, dba = 0.f, dbc = 0.f, part[PPO_NSUMS];
 #pragma unroll
     for (int a = 0; a < MA; ++a) dwa[a] = 0.f;
 #pragma unroll
-    for (int k = 0; k < 2 * MA + 4; ++k) part[k] = 0.f;
+    for (int k = 0; k < PPO_NSUMS; ++k) part[k] = 0.f;
     const int ntiles = (R + HEAD_ROWS - 1) / HEAD_ROWS;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int r0 = tile * HEAD_ROWS;
@@ -349,7 +329,9 @@ __global__ void __launch_bounds__(256) k_head_fused(PpoDev P, const float *__res
             }
         }
         __syncthreads();
-        if (tid < HEAD_ROWS) {   // loss of one row (same arithmetic as k_loss), wave 0 only; partials stay in registers
+        // loss of one row (ppo_loss.h; the Gaussian terms multiply by the staged reciprocals where k_loss divides, so the two
+        // paths differ in the last bits), wave 0 only; partials stay in registers
+        if (tid < HEAD_ROWS) {
             const int r = r0 + tid;
             const float invR = 1.0f / (float)R;
             float dvl = 0.f;
@@ -375,43 +357,25 @@ __global__ void __launch_bounds__(256) k_head_fused(PpoDev P, const float *__res
                         const float m = mus[tid][a], mo = mo_r[a];
                         const float d = act_r[a] - m;
                         dd[a] = d;
-                        lp += -(d * d) * s_i2s2[a] - s_lgs[a];
-                        kl += s_klc[a] + (s_so2[a] + (mo - m) * (mo - m)) * s_i2s2[a];
+                        lp += ppo_lp_term(d, s_i2s2[a], s_lgs[a]);
+                        kl += ppo_kl_term(mo, m, s_so2[a], s_i2s2[a], s_klc[a]);
                     }
                 }
-                const float ratio = expf(lp - lp_old);
-                const float rc = fminf(fmaxf(ratio, 1.0f - P.clip), 1.0f + P.clip);
-                const float s1 = -adv * ratio, s2 = -adv * rc;
-                const float dl_dlp = (s1 >= s2 ? -adv : 0.0f) * ratio * invR;
+                const PpoSurrogate sg = ppo_surrogate(P.clip, lp, lp_old, adv, invR);
 #pragma unroll
                 for (int a = 0; a < MA; ++a)
                     if (a < A) {
-                        const float d = dd[a];
-                        const float g = dl_dlp * d * s_is2[a];
+                        const float g = ppo_dmu(sg.dl_dlp, dd[a], s_is2[a]);
                         dmus[tid][a] = g;
-                        part[MA + a] += g;
-                        part[a] += dl_dlp * (d * d * s_is2[a] * s_is[a] - s_is[a]) - P.entropy_coef * invR * s_is[a];
+                        part[PPO_SUM_DBIAS_ACTOR + a] += g;
+                        part[PPO_SUM_DSTD + a] += ppo_dstd(sg.dl_dlp, dd[a], s_is2[a], s_is[a], P.entropy_coef * invR);
                     }
-                const float v = mus[tid][MA];
-                float lv, dv;
-                if (P.clipped_value) {
-                    const float dvv = v - v_old;
-                    const float vc = v_old + fminf(fmaxf(dvv, -P.clip), P.clip);
-                    const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
-                    const float inside = (dvv >= -P.clip && dvv <= P.clip) ? 1.0f : 0.0f;
-                    lv = fmaxf(l1, l2);
-                    if (l1 > l2) dv = 2.0f * (v - ret);
-                    else if (l1 < l2) dv = 2.0f * (vc - ret) * inside;
-                    else dv = (v - ret) + (vc - ret) * inside;
-                } else {
-                    lv = (ret - v) * (ret - v);
-                    dv = 2.0f * (v - ret);
-                }
-                dvl = dv * P.value_coef * invR;
-                part[2 * MA] += dvl;
-                part[2 * MA + 1] += kl;
-                part[2 * MA + 2] += lv;
-                part[2 * MA + 3] += fmaxf(s1, s2);
+                const PpoValue vl = ppo_value(P.clipped_value, P.clip, mus[tid][MA], v_old, ret);
+                dvl = vl.dv * P.value_coef * invR;
+                part[PPO_SUM_DBIAS_CRITIC] += dvl;
+                part[PPO_SUM_KL] += kl;
+                part[PPO_SUM_VLOSS] += vl.lv;
+                part[PPO_SUM_SLOSS] += fmaxf(sg.s1, sg.s2);
             }
             dmus[tid][MA] = dvl;
         }
@@ -444,22 +408,17 @@ __global__ void __launch_bounds__(256) k_head_fused(PpoDev P, const float *__res
     }
     // ---- flush: loss partials of the row lanes (wave 0) transposed through LDS (lane r writes column r, thread k adds row k:
     // a 36 x 6 shuffle butterfly on one wave is several times slower), then column accumulators reduced over the NH row groups
-    __shared__ float ptmp[(2 * MA + 4) * HEAD_ROWS];
+    __shared__ float ptmp[PPO_NSUMS * HEAD_ROWS];
     if (tid < HEAD_ROWS) {
 #pragma unroll
-        for (int k = 0; k < 2 * MA + 4; ++k) ptmp[k * HEAD_ROWS + tid] = part[k];
+        for (int k = 0; k < PPO_NSUMS; ++k) ptmp[k * HEAD_ROWS + tid] = part[k];
     }
     __syncthreads();
-    if (tid < 2 * MA + 4 && (tid >= 2 * MA || (tid % MA) < A)) {
+    if (tid < PPO_NSUMS && ppo_sum_live(tid, A)) {
         const int k = tid;
         float v = 0.f;
         for (int r = 0; r < HEAD_ROWS; ++r) v += ptmp[k * HEAD_ROWS + r];
-        if (k < MA) acc_add(P, &P.grads[P.off_std + k], v);
-        else if (k < 2 * MA) acc_add(P, &P.grads[b_a + (k - MA)], v);
-        else if (k == 2 * MA) acc_add(P, &P.grads[b_c], v);
-        else if (k == 2 * MA + 1) acc_add(P, &P.grads[P.num_params], v);
-        else if (k == 2 * MA + 2) acc_add(P, &P.loss_acc[0], v);
-        else acc_add(P, &P.loss_acc[1], v);
+        acc_add(P, ppo_sum_dest(P, k, b_a, b_c), v);
     }
     float *acc = xa;                                      // reuse the tile buffer: [MA + 3][NH][H3]
     __syncthreads();
@@ -520,9 +479,9 @@ __global__ void __launch_bounds__(256, 3) k_head_net(PpoDev P, const float *__re
     __shared__ float s_so2[MA], s_i2s2[MA], s_is2[MA], s_is[MA], s_lgs[MA], s_klc[MA], s_bias[MA];
     float *x = buf, *outs_p = buf + HEAD_ROWS * LDX;
     if (tid < MA) {
-        const float sg = tid < A ? P.params[P.off_std + tid] : 1.f, so = tid < A ? P.st_sigma[tid] : 1.f;
-        s_so2[tid] = so * so; s_i2s2[tid] = 1.0f / (2.0f * sg * sg); s_is2[tid] = 1.0f / (sg * sg); s_is[tid] = 1.0f / sg;
-        s_lgs[tid] = logf(sg) + 0.9189385332046727f; s_klc[tid] = logf(sg / so + 1.e-5f) - 0.5f;
+        const PpoGauss gs = ppo_gauss(tid < A ? P.params[P.off_std + tid] : 1.f, tid < A ? P.st_sigma[tid] : 1.f);
+        s_so2[tid] = gs.so2; s_i2s2[tid] = gs.i2s2; s_is2[tid] = gs.is2; s_is[tid] = gs.is;
+        s_lgs[tid] = gs.lgs; s_klc[tid] = gs.klc;
         s_bias[tid] = tid < nout ? P.params[(actor ? b_a : b_c) + tid] : 0.f;
     }
     float wcol0[NA], wcol1[NA];                             // the head weights of this lane's two columns (backward)
@@ -531,11 +490,11 @@ __global__ void __launch_bounds__(256, 3) k_head_net(PpoDev P, const float *__re
         wcol0[a] = a < nout ? w_g[a * H3 + lane] : 0.f;
         wcol1[a] = a < nout ? w_g[a * H3 + lane + 64] : 0.f;
     }
-    float dw0[NA], dw1[NA], db0 = 0.f, db1 = 0.f, part[2 * MA + 4];
+    float dw0[NA], dw1[NA], db0 = 0.f, db1 = 0.f, part[PPO_NSUMS];
 #pragma unroll
     for (int a = 0; a < NA; ++a) { dw0[a] = 0.f; dw1[a] = 0.f; }
 #pragma unroll
-    for (int k = 0; k < 2 * MA + 4; ++k) part[k] = 0.f;
+    for (int k = 0; k < PPO_NSUMS; ++k) part[k] = 0.f;
     const int ntiles = (R + HEAD_ROWS - 1) / HEAD_ROWS;
     const float invR = 1.0f / (float)R;
 #ifdef LG_HEAD_STAMPS
@@ -621,47 +580,28 @@ __global__ void __launch_bounds__(256, 3) k_head_net(PpoDev P, const float *__re
                             const float m = outv[a] + s_bias[a], mo = s_am[HEAD_ROWS * NA + lane * A + a];
                             const float d = s_am[lane * A + a] - m;
                             dd[a] = d;
-                            lp += -(d * d) * s_i2s2[a] - s_lgs[a];
-                            kl += s_klc[a] + (s_so2[a] + (mo - m) * (mo - m)) * s_i2s2[a];
+                            lp += ppo_lp_term(d, s_i2s2[a], s_lgs[a]);
+                            kl += ppo_kl_term(mo, m, s_so2[a], s_i2s2[a], s_klc[a]);
                         }
                     }
-                    const float ratio = expf(lp - lp_old);
-                    const float rc = fminf(fmaxf(ratio, 1.0f - P.clip), 1.0f + P.clip);
-                    const float s1 = -adv * ratio, s2 = -adv * rc;
-                    const float dl_dlp = (s1 >= s2 ? -adv : 0.0f) * ratio * invR;
+                    const PpoSurrogate sg = ppo_surrogate(P.clip, lp, lp_old, adv, invR);
 #pragma unroll
                     for (int a = 0; a < NA; ++a)
                         if (a < A) {
-                            const float d = dd[a];
-                            const float g = dl_dlp * d * s_is2[a];
+                            const float g = ppo_dmu(sg.dl_dlp, dd[a], s_is2[a]);
                             dout[a] = g;
                             if (sums) {
-                                part[MA + a] += g;
-                                part[a] += dl_dlp * (d * d * s_is2[a] * s_is[a] - s_is[a]) - P.entropy_coef * invR * s_is[a];
+                                part[PPO_SUM_DBIAS_ACTOR + a] += g;
+                                part[PPO_SUM_DSTD + a] += ppo_dstd(sg.dl_dlp, dd[a], s_is2[a], s_is[a], P.entropy_coef * invR);
                             }
                         }
-                    if (sums) { part[2 * MA + 1] += kl; part[2 * MA + 3] += fmaxf(s1, s2); }
+                    if (sums) { part[PPO_SUM_KL] += kl; part[PPO_SUM_SLOSS] += fmaxf(sg.s1, sg.s2); }
                 }
             } else if (r < R) {
-                const float v_old = sc.x, ret = sc.y;
-                const float v = s_bias[0] + outv[0];
-                float lv, dv;
-                if (P.clipped_value) {
-                    const float dvv = v - v_old;
-                    const float vc = v_old + fminf(fmaxf(dvv, -P.clip), P.clip);
-                    const float l1 = (v - ret) * (v - ret), l2 = (vc - ret) * (vc - ret);
-                    const float inside = (dvv >= -P.clip && dvv <= P.clip) ? 1.0f : 0.0f;
-                    lv = fmaxf(l1, l2);
-                    if (l1 > l2) dv = 2.0f * (v - ret);
-                    else if (l1 < l2) dv = 2.0f * (vc - ret) * inside;
-                    else dv = (v - ret) + (vc - ret) * inside;
-                } else {
-                    lv = (ret - v) * (ret - v);
-                    dv = 2.0f * (v - ret);
-                }
-                const float dvl = dv * P.value_coef * invR;
+                const PpoValue vl = ppo_value(P.clipped_value, P.clip, s_bias[0] + outv[0], sc.x, sc.y);
+                const float dvl = vl.dv * P.value_coef * invR;
                 dout[0] = dvl;
-                if (sums) { part[2 * MA] += dvl; part[2 * MA + 2] += lv; }
+                if (sums) { part[PPO_SUM_DBIAS_CRITIC] += dvl; part[PPO_SUM_VLOSS] += vl.lv; }
             }
         }
         // backward for rows wv, wv + 4, ...: dz = (dout . W) act'(x); dW += dout^T x; the row's dout as scalars.  Written twice: without
@@ -692,7 +632,7 @@ __global__ void __launch_bounds__(256, 3) k_head_net(PpoDev P, const float *__re
     // Column sums: the four waves' partials [MA + 1][NWV][H3] meet in LDS; the loss lanes' row sums (wave 0) are transposed through
     // LDS (lane r writes its partials as column r, thread k adds the 64 entries of row k).
     float *acc = buf, *ptmp = buf + (MA + 1) * NWV * H3;
-    static_assert((MA + 1) * NWV * H3 + (2 * MA + 4) * HEAD_ROWS <= NBUF, "sums fit in the tile buffer");
+    static_assert((MA + 1) * NWV * H3 + PPO_NSUMS * HEAD_ROWS <= NBUF, "sums fit in the tile buffer");
     __syncthreads();                                        // every wave is done with the tile
 #pragma unroll
     for (int a = 0; a < MA; ++a) {
@@ -703,11 +643,11 @@ __global__ void __launch_bounds__(256, 3) k_head_net(PpoDev P, const float *__re
     acc[(MA * NWV + wv) * H3 + lane + 64] = db1;
     if (tid < HEAD_ROWS) {
 #pragma unroll
-        for (int k = 0; k < 2 * MA + 4; ++k) ptmp[k * HEAD_ROWS + tid] = part[k];
+        for (int k = 0; k < PPO_NSUMS; ++k) ptmp[k * HEAD_ROWS + tid] = part[k];
     }
     float *__restrict__ prow = P.head_part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * HEAD_PART_STRIDE(H3);
     __syncthreads();
-    if (tid < 2 * MA + 4) {
+    if (tid < PPO_NSUMS) {
         float v = 0.f;
         for (int rw = 0; rw < HEAD_ROWS; ++rw) v += ptmp[tid * HEAD_ROWS + rw];
         prow[(MA + 1) * H3 + tid] = v;
@@ -731,7 +671,7 @@ __global__ void __launch_bounds__(256, 3) k_head_net(PpoDev P, const float *__re
 template <int H3>
 __global__ void __launch_bounds__(256) k_head_finish(PpoDev P, int nrows, int64_t w_a, int64_t b_a, int64_t w_c, int64_t b_c, int64_t b_prev_a,
                                                      int64_t b_prev_c) {
-    constexpr int MA = LG_PPO_MAX_A, NW = (MA + 1) * H3, NTOT = NW + 2 * MA + 4;
+    constexpr int MA = LG_PPO_MAX_A, NW = (MA + 1) * H3, NTOT = NW + PPO_NSUMS;
     const int i = blockIdx.x * 256 + threadIdx.x, A = P.A;
     if (i >= NTOT) return;
     const bool actor = blockIdx.z == 0;
@@ -740,9 +680,7 @@ __global__ void __launch_bounds__(256) k_head_finish(PpoDev P, int nrows, int64_
     if (i < NW) { if (i / H3 < MA && i / H3 >= nout) return; }
     else {
         const int k = i - NW;
-        const bool used = actor ? ((k < MA && k < A) || (k >= MA && k < 2 * MA && k - MA < A) || k == 2 * MA + 1 || k == 2 * MA + 3)
-                                : (k == 2 * MA || k == 2 * MA + 2);
-        if (!used) return;
+        if (ppo_sum_of_actor(k) != actor || !ppo_sum_live(k, A)) return;
     }
     const int r0 = (int)((long)nrows * blockIdx.y / HEAD_FIN_CHUNKS), r1 = (int)((long)nrows * (blockIdx.y + 1) / HEAD_FIN_CHUNKS);
     const float *__restrict__ src = P.head_part + ((size_t)blockIdx.z * nrows + r0) * HEAD_PART_STRIDE(H3) + i;
@@ -753,18 +691,7 @@ __global__ void __launch_bounds__(256) k_head_finish(PpoDev P, int nrows, int64_
         const int q = i / H3, cc = i % H3;
         if (q < MA) acc_add(P, &P.grads[(actor ? w_a : w_c) + (int64_t)q * H3 + cc], v);
         else acc_add(P, &P.grads[(actor ? b_prev_a : b_prev_c) + cc], v);
-    } else {
-        const int k = i - NW;
-        if (actor) {
-            if (k < MA) acc_add(P, &P.grads[P.off_std + k], v);
-            else if (k < 2 * MA) acc_add(P, &P.grads[b_a + (k - MA)], v);
-            else if (k == 2 * MA + 1) acc_add(P, &P.grads[P.num_params], v);
-            else acc_add(P, &P.loss_acc[1], v);
-        } else {
-            if (k == 2 * MA) acc_add(P, &P.grads[b_c], v);
-            else acc_add(P, &P.loss_acc[0], v);
-        }
-    }
+    } else acc_add(P, ppo_sum_dest(P, i - NW, b_a, b_c), v);
 }
 
 // KL-adaptive learning rate (rsl_rl PPO.update) + reset of the norm accumulator

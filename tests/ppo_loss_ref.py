@@ -1,5 +1,5 @@
-"""Test-only case builder and float64 reference for the PPO minibatch loss of the HIP learner (the four copies of it in
-legged_gym_dev_amd/csrc/ppo_kernels.hip: k_loss, k_head_fused<32|64>, k_head_net<128, 12|16> + k_head_finish).  Plain torch, no
+"""Test-only case builder and float64 reference for the PPO minibatch loss of the HIP learner (csrc/ppo_loss.h, as the four kernels of
+legged_gym_dev_amd/csrc/ppo_kernels.hip run it: k_loss, k_head_fused<32|64>, k_head_net<128, 12|16> + k_head_finish).  Plain torch, no
 GPU needed: tests/test_ppo_loss_host.py checks the inputs built here on the CPU, tests/test_hip_ppo_loss.py runs them through the
 library.
 

@@ -1,8 +1,9 @@
 """The PPO minibatch loss of the HIP learner against float64, on every head kernel, clip regime and action count.
 
-The loss exists four times in legged_gym_dev_amd/csrc/ppo_kernels.hip (k_loss after the head GEMMs, k_head_fused<32>,
-k_head_fused<64>, k_head_net<128, 12 | 16> + k_head_finish<128>); lg_ppo_minibatch_backward picks one by activation, depth and
-last hidden widths (tests/ppo_loss_ref.py: PATHS / CASES name the path each case takes).  The gradient tests of
+Four kernels of legged_gym_dev_amd/csrc/ppo_kernels.hip evaluate the loss (k_loss after the head GEMMs, k_head_fused<32>,
+k_head_fused<64>, k_head_net<128, 12 | 16> + k_head_finish<128>), each with its own operand paths and reductions around the one
+copy of the row arithmetic in csrc/ppo_loss.h (k_loss keeps its Gaussian terms in division form); lg_ppo_minibatch_backward picks
+one by activation, depth and last hidden widths (tests/ppo_loss_ref.py: PATHS / CASES name the path each case takes).  The gradient tests of
 tests/test_hip_ppo.py update on the rollout's own parameters -- ratio 1, v_new = v_old, A = 12 -- so they sit on the tie branch
 of the clipped value loss and inside the surrogate clip.  Here the storage is written directly with rows steered to a table of
 (ratio, advantage, v_new - v_old, v_new - return) targets, which tests/test_ppo_loss_host.py shows to keep every row off every

@@ -9,6 +9,8 @@ storage and `stats`.  Shapes: the smallest at which the scheduling can still go 
 steps x 2 minibatches, 48 observations with a privileged critic row of 53 (both off the 32-column pad), hidden [64, 32]:
   ff/<act>/<widths>/act<0|1>/ov<0|1>   feed-forward: fused head (elu, equal last widths) against k_loss (tanh; unequal last widths),
                                        fused act on / off, overlap on / off
+  head/<label>/cv<0|1>                 every head path of tests/ppo_loss_ref.PATHS (generic, fused32, fused64, net128_12, net128_16 at
+                                       16 actions), `use_clipped_value_loss` on / off: 200 rows = three 64-row tiles and one of 8
   rnn/ov<0|1>                          the same sizes with an LSTM of 32
   runner                               one runner iteration at 64 envs with the env attached (fused rollout epilogue)
 --compare counts the arrays that differ in shape, dtype or bytes (a non-finite value equals itself).  One array is order-dependent by
@@ -45,13 +47,13 @@ def learner_state(ppo):
     return out
 
 
-def run_learner(activation, actor_hidden, critic_hidden, fused_act, overlap, recurrent):
+def run_learner(activation, actor_hidden, critic_hidden, fused_act, overlap, recurrent, A=A, clipped_value=True):
     import torch
     from legged_gym_dev_amd.rl.ppo import HipPPO
     torch.manual_seed(7)
     policy = dict(actor_hidden_dims=actor_hidden, critic_hidden_dims=critic_hidden, activation=activation, init_noise_std=1.0,
                   rnn_type="lstm", rnn_hidden_size=32, rnn_num_layers=1)
-    ppo = HipPPO(N, O, OC, A, policy, ALG, T, device="cuda:0", seed=3,
+    ppo = HipPPO(N, O, OC, A, policy, dict(ALG, use_clipped_value_loss=clipped_value), T, device="cuda:0", seed=3,
                  policy_class_name="ActorCriticRecurrent" if recurrent else "ActorCritic")
     ppo.set_deterministic(True)
     ppo.lib.lg_ppo_debug_set_overlap(ppo.ctx, overlap)
@@ -91,6 +93,11 @@ def paths():
         for fa in (1, 0):
             for ov in (1, 0):
                 yield (f"ff_{act}_{ah[-1]}-{ch[-1]}_act{fa}_ov{ov}", lambda act=act, ah=ah, ch=ch, fa=fa, ov=ov: run_learner(act, ah, ch, fa, ov, False))
+    from tests.ppo_loss_ref import PATHS
+    for label, (hidden, critic, act) in PATHS.items():
+        for cv in (1, 0):
+            yield (f"head_{label}_cv{cv}", lambda hidden=hidden, critic=critic, act=act, label=label, cv=cv: run_learner(
+                act, hidden, critic or hidden, 1, 1, False, A=16 if label == "net128_16" else 12, clipped_value=bool(cv)))
     for ov in (1, 0):
         yield f"rnn_ov{ov}", lambda ov=ov: run_learner("elu", [64, 32], [64, 32], 0, ov, True)
     yield "runner", run_runner
